@@ -25,6 +25,7 @@ Process model
 What is timed: K steps, serial, one host thread per rank, bracketed by barrier + synchronize.  The
 queries of the timed region, of the pre-warm and of every later block (CPU baseline, parity, extras)
 come from independent generators: no block depends on --steps/--warmup (plan_queries()).
+`--dump-outputs DIR` writes what rank 0's last timed search returned (ids, scores) as DIR/*.npy (dump_outputs()).
 
 Multi-GPU (`--gpus N`): the flat index is REPLICATED (each rank holds the full corpus) and ranks
 answer disjoint query streams -- no data-path collective; value = all ranks' queries / max time
@@ -99,6 +100,8 @@ def parse_args(argv=None):
     p.add_argument("--no-other-configs", action="store_true")
     p.add_argument("--no-full-size-cpu-check", action="store_true")
     p.add_argument("--no-checks", action="store_true")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what rank 0's last timed search returned as DIR/<name>.npy (dump_outputs())")
     p.add_argument("--inline", action="store_true", help="be the (single) rank in this process: no supervisor")
     p.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--result-file", default=None, help=argparse.SUPPRESS)
@@ -136,6 +139,21 @@ def ids_for(start: int, n: int) -> np.ndarray:
     # insertion-order tie-break is exercised on position, as in the reference
     pos = np.arange(start, start + n, dtype=np.uint64)
     return pos * np.uint64(2654435761) + np.uint64(97)
+
+
+def dump_outputs(out_dir: str, ids: np.ndarray, scores: np.ndarray) -> dict:
+    """What one search returned, as float64 .npy files a second build's dump can be compared with file for file.
+    ids are u64 beyond 2^53 (ids_for()), so they are written as their two exact 32-bit halves; scores are f64 already."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    arrays = {
+        "ids_hi32": (ids >> np.uint64(32)).astype(np.float64),
+        "ids_lo32": (ids & np.uint64(0xFFFFFFFF)).astype(np.float64),
+        "scores": np.ascontiguousarray(scores, dtype=np.float64),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def host_cores() -> int:
@@ -876,7 +894,7 @@ def run_rank(args) -> int:
     paths = set()
     stamps = []
     for i in range(args.warmup, args.warmup + args.steps):
-        idx.search_arrays(Q[i], k, metric)
+        last = idx.search_arrays(Q[i], k, metric)  # fresh host arrays (ids, scores): keeping them costs nothing
         stamps.append(time.perf_counter())
         paths.add(V.last_path())
     torch.cuda.synchronize()
@@ -909,6 +927,8 @@ def run_rank(args) -> int:
             wd.cancel()
         dist.destroy_process_group()
         return 0
+
+    dumped = dump_outputs(args.dump_outputs, *last) if args.dump_outputs else None
 
     qps = world * args.steps / elapsed_max
     ld = (dim + 3) // 4 * 4
@@ -966,6 +986,8 @@ def run_rank(args) -> int:
         },
     }
     out.update(step_rates(stamps, t1))
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
 
     def publish():
         """The line as it stands: to the supervisor's result file now, to stdout at the end."""

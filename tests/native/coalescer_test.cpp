@@ -3,7 +3,9 @@
 // Built and run by tests/test_coalescer_cpu.py with g++ -pthread.
 #include <atomic>
 #include <chrono>
+#include <condition_variable>
 #include <cstdio>
+#include <mutex>
 #include <stdexcept>
 #include <thread>
 #include <vector>
@@ -19,7 +21,10 @@ struct Req {
 // Adaptive gather (window 0): 8 callers in a closed loop on 2 ms passes.  Without it the passes alternate 1 / 7 (the first
 // caller back leads alone while the others are returning): ~2 passes per round.  With it the leader waits (<= a quarter of the
 // pass time) for as many requests as the last passes held: ~1 pass per round.  A lone caller never waits.
-static int closed_loop(bool adaptive, int threads, int rounds, uint64_t* passes, uint64_t* waits)
+// The callers start together: each one waits at a gate until all of them exist (creating a thread is slow under the
+// sanitizers, and callers that start while others are still being created fill the first passes only partly).  *ms, if
+// given, is the time from the gate's opening to the last caller's return.
+static int closed_loop(bool adaptive, int threads, int rounds, uint64_t* passes, uint64_t* waits, double* ms = nullptr)
 {
     vl::Coalescer<Req> co;
     co.configure(64, 0, 1024);
@@ -27,8 +32,17 @@ static int closed_loop(bool adaptive, int threads, int rounds, uint64_t* passes,
     auto same = [](const Req&, const Req&) { return true; };
     std::vector<std::thread> th;
     std::atomic<int> bad{0};
+    std::mutex gate_mu;
+    std::condition_variable gate_cv;
+    int ready = 0;
+    bool open = false;
     for (int t = 0; t < threads; ++t)
         th.emplace_back([&, t] {
+            {
+                std::unique_lock<std::mutex> g(gate_mu);
+                if (++ready == threads) gate_cv.notify_all();
+                gate_cv.wait(g, [&] { return open; });
+            }
             for (int i = 0; i < rounds; ++i) {
                 Req r{t * 1000 + i};
                 co.run(r, same, [&](std::vector<Req*>& batch) {
@@ -38,7 +52,16 @@ static int closed_loop(bool adaptive, int threads, int rounds, uint64_t* passes,
                 if (!r.done || r.rc != 0) bad.fetch_add(1);
             }
         });
+    std::chrono::steady_clock::time_point t0;
+    {
+        std::unique_lock<std::mutex> g(gate_mu);
+        gate_cv.wait(g, [&] { return ready == threads; });
+        open = true;
+        t0 = std::chrono::steady_clock::now();
+    }
+    gate_cv.notify_all();
     for (auto& t : th) t.join();
+    if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     uint64_t q = 0, us = 0;
     co.stats(passes, &q);
     co.gather_stats(waits, &us);
@@ -59,9 +82,8 @@ static int adaptive_gather()
     // many callers on few cores: arrivals wake the gathering leader only, so 200 callers x 6 rounds of 2 ms passes finish in
     // about 6 passes' time (a wake-up of every sleeper per arrival used to take tens of milliseconds per pass)
     uint64_t p_many = 0, w_many = 0;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (closed_loop(true, 200, 6, &p_many, &w_many)) return 15;
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    double ms = 0.0;
+    if (closed_loop(true, 200, 6, &p_many, &w_many, &ms)) return 15;
     std::printf("200 callers x 6 rounds: %llu passes, %.1f ms\n", (unsigned long long)p_many, ms);
     if (p_many > 30 || ms > 400.0) return 16;
     return 0;

@@ -130,3 +130,25 @@ def test_supervisor_reports_a_dead_worker_without_losing_the_line(tmp_path, monk
     with contextlib.redirect_stdout(buf):
         rc = bench.supervise(a, ["--steps", "2"])
     assert rc == 7 and buf.getvalue() == ""
+
+
+def test_dump_outputs_keeps_every_id_bit_and_score(tmp_path):
+    """--dump-outputs: ids beyond 2^53 survive as two exact float64 halves; scores are written as they are."""
+    ids = np.concatenate([bench.ids_for(9_999_990, 5), np.array([0, 2 ** 64 - 1], dtype=np.uint64)])
+    scores = np.array([0.5, -1.25, 1e-300, 3.0, np.nextafter(1.0, 2.0), 0.0, -0.0])
+    shapes = bench.dump_outputs(str(tmp_path / "d"), ids, scores)
+    assert shapes == {"ids_hi32": [7], "ids_lo32": [7], "scores": [7]}
+    got = {n: np.load(tmp_path / "d" / (n + ".npy")) for n in shapes}
+    assert all(a.dtype == np.float64 for a in got.values())
+    back = (got["ids_hi32"].astype(np.uint64) << np.uint64(32)) | got["ids_lo32"].astype(np.uint64)
+    assert back.tolist() == ids.tolist()
+    assert got["scores"].tobytes() == scores.tobytes()
+
+
+def test_dump_outputs_is_a_bench_argument():
+    assert bench.parse_args([]).dump_outputs is None
+    assert bench.parse_args(["--dump-outputs", "/tmp/x"]).dump_outputs == "/tmp/x"
+    # the supervisor hands it on to the rank process
+    argv = ["--steps", "3", "--dump-outputs", "/tmp/x"]
+    cmd = bench.launch_command(bench.parse_args(argv), argv, "/tmp/r.json", 1)
+    assert cmd[cmd.index("--dump-outputs") + 1] == "/tmp/x"

@@ -127,3 +127,30 @@ def test_bench_two_ranks_without_an_external_launcher():
     assert rs["identical_on_every_rank"] is True and rs["own_rows_match_single_search"] == "4/4"
     assert rs["roofline"]["bound"] == "mfma" and rs["roofline"]["whole_call"]["frac"] > 0
     assert "errors" not in out, out.get("errors")
+
+
+def test_bench_dumps_what_its_last_timed_step_returned(tmp_path):
+    """--dump-outputs DIR holds the answer of the last timed search, and that answer is the oracle's for the same
+    seeded corpus and query (so two builds' dumps can be compared file for file)."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import oracle as O
+
+    rows, dim, k, steps, warmup = 20000, 384, 10, 3, 1
+    d = tmp_path / "dump"
+    out, err = _run(["--gpus", "1", "--rows", str(rows), "--steps", str(steps), "--warmup", str(warmup),
+                     "--no-other-configs", "--no-checks", "--no-cpu-baseline", "--dump-outputs", str(d)])
+    assert out["steps"] == steps and out["ms_per_step"] > 0
+    assert out["dumped_outputs"]["arrays"] == {"ids_hi32": [k], "ids_lo32": [k], "scores": [k]}
+    got = {n: np.load(d / (n + ".npy")) for n in ("ids_hi32", "ids_lo32", "scores")}
+    ids = (got["ids_hi32"].astype(np.uint64) << np.uint64(32)) | got["ids_lo32"].astype(np.uint64)
+    # the same corpus (one chunk at this size) and the same last timed query, answered by the oracle
+    x = bench.gen_unit_rows(torch, torch.device("cuda", 0), rows, dim, 1234).cpu().numpy()
+    plan = bench.plan_queries(steps, warmup, 32)
+    q = bench.unit_queries(plan["timed"]["seed"], plan["timed"]["n"], dim)[warmup + steps - 1]
+    O.build()
+    ri, rs = O.FlatOracle(dim, bench.ids_for(0, rows), x).search(q, k, 0)
+    assert ids.tolist() == ri.tolist()
+    assert got["scores"].tolist() == rs.tolist()
