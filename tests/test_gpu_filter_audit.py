@@ -1,0 +1,418 @@
+"""Audit of every candidate filter against the exactness bound it is certified with.
+
+tests/native/filter_audit.hip runs the library's own stages on one case -- ingest, the bf16 row copies, ONE filter, the
+shipped bound_for_key on the device, the exact f64 scan of every row -- and writes the filter's 64-entry list per query.
+Here, for every query, with u = 2^-24 and n = the padded row length:
+  (a) key fidelity: every listed key equals the key host numpy computes in f64 from the same rounded inputs, within the
+      undoubled u-part of the bound ((n + 4) u times the sum of the absolute terms);
+  (b) completeness: no row outside the list has a host key above the list's 64th key t64 (plus the same allowance);
+  (c) certificate: every row outside the list has reference score <= B(t64), every listed row <= B(its key);
+  (d) ordering: (key desc, pos asc), no duplicate positions, none >= n.
+End-to-end answers would only notice a wrong key or a dropped row if it landed in the final top k; these checks look at
+the filter output itself.
+"""
+import os
+import struct
+import subprocess
+from dataclasses import dataclass, field
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+U = 2.0 ** -24
+TINY = 2.0 ** -126  # absolute allowance per term: f32 products and sums below the normal range
+KP = 64
+POS_SENTINEL = 0xFFFFFFFF
+MAGIC = 0x41464C56
+COS, EUC, MAN, DOT = 0, 1, 2, 3
+F32_QARG, F32_Q64, F32_BATCH, BF16_SINGLE, MFMA_BATCH = range(5)
+FILTER_NAME = {F32_QARG: "f32-qarg", F32_Q64: "f32-q64", F32_BATCH: "f32-batch", BF16_SINGLE: "bf16-single",
+               MFMA_BATCH: "mfma"}
+METRIC_NAME = {COS: "cosine", EUC: "euclidean", MAN: "manhattan", DOT: "dot"}
+ALL4 = (COS, EUC, MAN, DOT)
+BF16_METRICS = (COS, EUC, DOT)
+
+
+# ---------------------------------------------------------------------------------------------
+# host model of the rounded inputs the kernels read
+# ---------------------------------------------------------------------------------------------
+def dev_sumsq(x):
+    """Sum of squares of every row in the device's order (k_ingest, k_rows_bf16*): lane l adds columns l, l + 64, ...,
+    then a butterfly over the 64 lanes -- so the norms, 1/norm and the bf16 rows here are the device's bit for bit."""
+    n, d = x.shape
+    w = -(-d // 64) * 64
+    p = np.zeros((n, w))
+    p[:, :d] = x
+    p = p.reshape(n, w // 64, 64)
+    s = np.zeros((n, 64))
+    for j in range(w // 64):
+        s = s + p[:, j, :] * p[:, j, :]
+    lanes = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        s = s + s[:, lanes ^ o]
+    return s[:, 0]
+
+
+def bf16_rne(a32):
+    """f32 -> bf16 (round to nearest even), returned as f32 values (finite inputs)."""
+    b = np.ascontiguousarray(a32, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    r = ((b + 0x7FFF + ((b >> 16) & 1)) >> 16) << 16
+    return r.astype(np.uint32).view(np.float32)
+
+
+def f32(a):
+    return np.asarray(a, dtype=np.float64).astype(np.float32).astype(np.float64)
+
+
+class HostRows:
+    def __init__(self, rows):
+        self.rows = rows
+        ss = dev_sumsq(rows)
+        nrm = np.sqrt(ss)
+        self.x32 = f32(rows)
+        with np.errstate(divide="ignore"):
+            inv = np.where(nrm > 0.0, 1.0 / nrm, 0.0)
+        self.inv_norm = f32(inv)                                      # k_ingest: (float)(1.0 / norm)
+        self.xh = bf16_rne((rows * inv[:, None]).astype(np.float32)).astype(np.float64)  # x/|x| -> f32 -> bf16
+        self.nr = f32(nrm)                                            # |x| and |x|^2 rounded once to f32
+        self.sq = f32(ss)
+
+
+def host_keys(h, q, filt, metric, n_acc):
+    """(key, allowance) of every row for query q: the kernel's key in f64 from the same rounded inputs, and the undoubled
+    u-part of the bound for that row."""
+    g = (n_acc + 4) * U
+    if filt in (F32_QARG, F32_Q64, F32_BATCH):
+        q32 = f32(q)
+        if metric in (COS, DOT):
+            p = h.x32 @ q32
+            a = np.abs(h.x32) @ np.abs(q32)
+            if metric == COS:
+                return p * h.inv_norm, (g * a + n_acc * TINY) * h.inv_norm
+            return p, g * a + n_acc * TINY
+        d = h.x32 - q32[None, :]
+        s = np.sum(d * d, axis=1) if metric == EUC else np.sum(np.abs(d), axis=1)
+        return -s, g * s + n_acc * TINY
+    qv = f32(q) if filt == BF16_SINGLE else bf16_rne(f32(q).astype(np.float32)).astype(np.float64)
+    p = h.xh @ qv
+    a = np.abs(h.xh) @ np.abs(qv)
+    if metric == COS:
+        return p, g * a + n_acc * TINY
+    if metric == DOT:
+        return p * h.nr, (g * a + n_acc * TINY) * h.nr
+    return 2.0 * p * h.nr - h.sq, (g * a + n_acc * TINY) * 2.0 * h.nr + g * h.sq
+
+
+# ---------------------------------------------------------------------------------------------
+# case families
+# ---------------------------------------------------------------------------------------------
+def unit(rng, n, dim):
+    x = rng.standard_normal((n, dim))
+    return x / np.linalg.norm(x, axis=1, keepdims=True)
+
+
+def halfway(rng, shape, scale):
+    """f32 values whose low 16 bits are 0x8000: exactly halfway between two bf16 neighbours."""
+    v = (rng.standard_normal(shape) * scale).astype(np.float32).view(np.uint32)
+    v = (v & np.uint32(0xFFFF0000)) | np.uint32(0x8000)
+    return v.view(np.float32).astype(np.float64)
+
+
+def family(name, rng, n, dim, nq):
+    if name == "gauss":
+        return rng.standard_normal((n, dim)), rng.standard_normal((nq, dim))
+    if name == "scales":  # row norms over the whole domain 2^-40 .. 2^40, queries at both ends
+        rows = unit(rng, n, dim) * 2.0 ** rng.uniform(-39.9, 39.9, size=(n, 1))
+        rows[5] = 0.0
+        rows[5, 0] = 2.0 ** -40
+        rows[n // 2] = 0.0
+        rows[n // 2, 1] = 2.0 ** 40
+        q = unit(rng, nq, dim)
+        q[0::2] *= 2.0 ** -39.9
+        q[1::2] *= 2.0 ** 39.9
+        return rows, q
+    if name == "cancel":  # a big common component, a small distinct part, queries nearly orthogonal to it
+        base = unit(rng, 1, dim)[0]
+        rows = base[None, :] + 1e-3 * rng.standard_normal((n, dim))
+        q = rng.standard_normal((nq, dim))
+        q -= (q @ base)[:, None] * base[None, :]
+        q += 1e-7 * base[None, :]
+        q[0] = rows[3] - (rows[3] @ base) * base + 1e-7 * base  # the distinct part of one row: a clear winner
+        return rows, q
+    if name == "underflow":  # row norms ~2^-40 spread over every column, plus f64 subnormals
+        rows = unit(rng, n, dim) * 2.0 ** -39.5  # still >= 2^-40 once 5 % of the columns are subnormal
+        mask = rng.random((n, dim)) < 0.05
+        rows[mask] = rng.choice([-1.0, 1.0], size=mask.sum()) * 5e-324 * rng.integers(1, 1 << 40, size=mask.sum())
+        # a third of the rows: norm ~2^-40 in ONE column, the others 2^-100 .. 2^-155 -- f32 subnormal inputs, inputs that
+        # round to 0, and (against the tiny queries) products and differences below the f32 normal range
+        t = np.arange(0, n, 3)
+        rows[t] = rng.choice([-1.0, 1.0], size=(len(t), dim)) * 2.0 ** rng.uniform(-155.0, -100.0, size=(len(t), dim))
+        rows[t, rng.integers(0, dim, size=len(t))] = 2.0 ** -39.9
+        q = unit(rng, nq, dim)
+        q[1::2] *= 2.0 ** -39.9
+        q[0, ::7] = 1e-310
+        return rows, q
+    if name == "bf16edge":  # x/|x| exactly halfway between bf16 neighbours, and close to +-1
+        rows = np.zeros((n, dim))
+        h = n // 2
+        rows[:h, : dim - 4] = halfway(rng, (h, dim - 4), 0.9 / np.sqrt(dim))
+        rest = np.maximum(1.0 - np.sum(rows[:h] ** 2, axis=1), 0.0)
+        rows[:h, dim - 4:] = np.sqrt(rest / 4.0)[:, None] * rng.choice([-1.0, 1.0], size=(h, 4))
+        rows[h:] = 1e-3 * unit(rng, n - h, dim)
+        j = rng.integers(0, dim, size=n - h)
+        sign = rng.choice([-1.0, 1.0], size=n - h)
+        top = np.where(rng.random(n - h) < 0.5, 1.0 - 2.0 ** -9, 1.0 - 2.0 ** -30)
+        rows[h + np.arange(n - h), j] = sign * top
+        rows *= 2.0 ** rng.integers(-5, 6, size=(n, 1))  # exact scaling: x/|x| unchanged
+        q = halfway(rng, (nq, dim), 1.0)
+        q[0] = rows[7]
+        q[1] = rows[h + 3]
+        return rows, q
+    if name == "gemm":  # GEMM-form Euclidean: |q| far below and far above the row norms
+        rows = unit(rng, n, dim) * 2.0 ** rng.uniform(0.0, 4.0, size=(n, 1))
+        q = unit(rng, nq, dim)
+        q[0::2] *= 2.0 ** -12
+        q[1::2] *= 2.0 ** 12
+        return rows, q
+    raise ValueError(name)
+
+
+@dataclass
+class Case:
+    filt: int
+    fam: str
+    dim: int
+    n: int
+    nq: int
+    metrics: tuple
+    env: dict = field(default_factory=dict)
+    tag: str = ""
+
+    @property
+    def id(self):
+        return f"{FILTER_NAME[self.filt]}-{self.fam}-d{self.dim}-n{self.n}-q{self.nq}{'-' + self.tag if self.tag else ''}"
+
+
+N1 = 8192 + 37    # not a multiple of 16 / 32 / 64: the last block is masked
+NM = 8192 + 45
+CASES = (
+    # f32 single query: the query in the kernel arguments (k_scan), from device memory (k_scan_q64), k_scan_generic
+    [Case(F32_QARG, "gauss", d, N1, 4, ALL4) for d in (128, 384, 512, 768)]
+    + [Case(F32_Q64, "gauss", d, N1, 4, ALL4) for d in (100, 300, 384, 700, 1536)]
+    + [Case(F32_Q64, "gauss", 3072, 4133, 3, ALL4)]
+    + [Case(F32_QARG, "scales", 384, N1, 4, ALL4), Case(F32_Q64, "scales", 700, N1, 4, ALL4),
+       Case(F32_QARG, "cancel", 768, N1, 4, ALL4), Case(F32_Q64, "cancel", 300, N1, 4, ALL4),
+       Case(F32_QARG, "underflow", 512, N1, 4, ALL4), Case(F32_Q64, "underflow", 100, N1, 4, ALL4),
+       Case(F32_QARG, "bf16edge", 256, N1, 4, ALL4), Case(F32_Q64, "gemm", 1536, 4133, 4, ALL4)]
+    # f32 batch: 11 queries = two groups of 8; four lanes per row at 32 / 64
+    + [Case(F32_BATCH, "gauss", d, N1, 11, ALL4) for d in (32, 64, 96, 384, 768)]
+    + [Case(F32_BATCH, "scales", 256, N1, 11, ALL4), Case(F32_BATCH, "cancel", 128, N1, 11, ALL4),
+       Case(F32_BATCH, "underflow", 512, N1, 11, ALL4)]
+    # bf16 single query
+    + [Case(BF16_SINGLE, "gauss", d, N1, 4, BF16_METRICS) for d in (100, 384, 768)]
+    + [Case(BF16_SINGLE, f, d, N1, 4, BF16_METRICS) for f, d in
+       (("bf16edge", 256), ("scales", 512), ("cancel", 384), ("underflow", 300), ("gemm", 128))]
+    # MFMA batch: k_mfma_rows at every stride (128 / 256 / 384 / 512 / 768), k_mfma_scan, 2 query chunks, 2-4 pass-1 stages
+    + [Case(MFMA_BATCH, "gauss", d, NM, 40, BF16_METRICS) for d in (100, 256, 300, 512, 768)]
+    + [Case(MFMA_BATCH, "gauss", d, NM, 40, BF16_METRICS, {"VL_MFMA_KERNEL": "tile"}, "tile") for d in (384, 700)]
+    + [Case(MFMA_BATCH, "gauss", 384, NM, 160, BF16_METRICS, {}, "2chunks"),
+       Case(MFMA_BATCH, "gauss", 768, NM, 100, BF16_METRICS, {}, "2chunks"),
+       Case(MFMA_BATCH, "gauss", 512, NM, 40, BF16_METRICS, {"VL_MFMA_STREAM_LOADS": "0"}, "plainloads")]
+    + [Case(MFMA_BATCH, "gauss", 256, 41003, 24, BF16_METRICS,
+            {"VL_MFMA_GRID": "1", "VL_MFMA_STAGES": str(st), "VL_MFMA_STREAM_LOADS": str(st % 2)}, f"stages{st}")
+       for st in (2, 3, 4)]
+    + [Case(MFMA_BATCH, f, d, NM, 40, BF16_METRICS) for f, d in
+       (("bf16edge", 384), ("scales", 256), ("cancel", 512), ("underflow", 768), ("gemm", 384))]
+)
+
+
+# ---------------------------------------------------------------------------------------------
+# running one case
+# ---------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def audit_exe(tmp_path_factory):
+    from vectorlite_amd import build as vbuild
+    vbuild.build()  # the MFMA / bf16 launchers: mfma_scan.o of the library build
+    d = tmp_path_factory.mktemp("filter_audit")
+    exe, obj = d / "filter_audit", d / "filter_audit.o"
+    arch = [vbuild.hipcc(), f"--offload-arch={vbuild.ARCH}"]
+    for cmd in (arch + ["-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-result", "-I", os.path.join(ROOT, "include"), "-c",
+                        os.path.join(ROOT, "tests", "native", "filter_audit.hip"), "-o", str(obj)],
+                arch + [str(obj), os.path.join(vbuild.OBJ, "mfma_scan.o"), "-o", str(exe)]):
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200)
+        assert r.returncode == 0, r.stdout + r.stderr
+    return str(exe)
+
+
+RATIOS = {}        # (filter, metric, ld) -> largest (a) ratio
+SKIPPED = {}       # (filter, metric, ld) -> [MFMA lists skipped as overflowed (exact path), lists audited]
+_STATE = {"failed_child": None}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def ratio_report():
+    yield
+    if RATIOS:
+        lines = ["largest |key_dev - key_host| / allowance per (filter, metric, stride):"]
+        for (f, m, ld), r in sorted(RATIOS.items()):
+            sk, au = SKIPPED.get((f, m, ld), (0, 0))
+            lines.append(f"  {f:12s} {METRIC_NAME[m]:10s} ld {ld:5d}: {r:.3g}   ({au} lists audited, {sk} overflowed lists skipped)")
+        print("\n" + "\n".join(lines))
+
+
+def run_case(exe, case, tmp_path):
+    if _STATE["failed_child"]:
+        pytest.fail(f"not started: the audit child of {_STATE['failed_child']} failed")
+    rng = np.random.default_rng([case.filt, case.dim, case.n, case.nq, sum(map(ord, case.fam + case.tag))])
+    rows, queries = family(case.fam, rng, case.n, case.dim, case.nq)
+    src = tmp_path / "case.bin"
+    out = tmp_path / "out.bin"
+    mets = list(case.metrics) + [0] * (4 - len(case.metrics))
+    with open(src, "wb") as f:
+        f.write(struct.pack("<10I", MAGIC, case.filt, len(case.metrics), *mets, case.n, case.dim, case.nq))
+        f.write(np.ascontiguousarray(rows, dtype="<f8").tobytes())
+        f.write(np.ascontiguousarray(queries, dtype="<f8").tobytes())
+    env = dict(os.environ)
+    env.update(case.env)
+    # the flag is set BEFORE the child starts and cleared only when it exits cleanly: a hang (TimeoutExpired), a crash or
+    # any other exception leaves it set, so no later case starts a process on a card that may be wedged
+    _STATE["failed_child"] = case.id
+    r = subprocess.run([exe, str(src), str(out)], capture_output=True, text=True, timeout=180, env=env)
+    if r.returncode == 0 and "audit ok" in r.stdout:
+        _STATE["failed_child"] = None
+    else:
+        pytest.fail(f"audit child exited {r.returncode}:\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}")
+    return rows, queries, out.read_bytes()
+
+
+def parse_blocks(buf, n_metrics):
+    blocks, off = [], 0
+    for _ in range(n_metrics):
+        magic, metric, nq, n, ld, *info = struct.unpack_from("<9I", buf, off)
+        assert magic == MAGIC
+        off += 36
+        R, in_extra = struct.unpack_from("<2d", buf, off)
+        off += 16
+
+        def take(dtype, count):
+            nonlocal off
+            a = np.frombuffer(buf, dtype=dtype, count=count, offset=off)
+            off += a.nbytes
+            return a
+
+        b = dict(metric=metric, nq=nq, n=n, ld=ld, info=info, R=R, in_extra=in_extra)
+        b["Q"] = take("<f8", nq)
+        b["key"] = take("<f4", nq * KP).reshape(nq, KP).astype(np.float64)
+        b["pos"] = take("<u4", nq * KP).reshape(nq, KP)
+        b["bt"] = take("<f8", nq)
+        b["bk"] = take("<f8", nq * KP).reshape(nq, KP)
+        b["exact"] = take("<f8", nq * n).reshape(nq, n)
+        blocks.append(b)
+    assert off == len(buf)
+    return blocks
+
+
+def documented_bound(metric, t, n, R, Q, in_extra):
+    """DESIGN.md §3's bound with every u-term doubled, in plain f64: the shipped B must not fall below it."""
+    if metric == COS:
+        return t / Q + 2.0 * (n + 4) * U + in_extra
+    if metric == DOT:
+        return t + (2.0 * (n + 2) * U + in_extra) * R * Q
+    if metric == EUC and in_extra > 0.0:
+        err = 2.0 * in_extra * R * Q + 4.0 * (n + 4) * U * (R * Q + R * R)
+        return 1.0 / (1.0 + np.sqrt(np.maximum(Q * Q - t - err, 0.0)))
+    ts = np.maximum(-t, 0.0)
+    if metric == EUC:
+        d = np.sqrt(ts) * (1.0 - 2.0 * (n + 2) * U) - 4.0 * U * (R + Q)
+    else:
+        d = ts * (1.0 - 2.0 * (n + 2) * U) - 4.0 * U * np.sqrt(n) * (R + Q)
+    return 1.0 / (1.0 + np.maximum(d, 0.0))
+
+
+# in_extra of the bf16 filters, derived: a bf16 row is x/|x| rounded f64 -> f32 -> bf16 (relative 2^-8 + 2^-23 with the
+# double rounding); the single-query filter's query is f32 (2^-24), the MFMA filter's is bf16 like the rows
+UB = 2.0 ** -8 + 2.0 ** -23
+IN_EXTRA_MIN = {BF16_SINGLE: UB * (1.0 + U) + U, MFMA_BATCH: (2.0 + UB) * UB}
+
+
+def audit_block(case, h, queries, b):
+    """(a)-(d) for every query of one metric; returns the number of lists audited."""
+    filt, metric, n, ld = case.filt, b["metric"], b["n"], b["ld"]
+    ctx = (case.id, METRIC_NAME[metric])
+    audited = 0
+    skipped = 0
+    worst = 0.0
+    assert b["in_extra"] >= IN_EXTRA_MIN.get(filt, 0.0), (ctx, "in_extra below its derivation", b["in_extra"])
+    for qi in range(b["nq"]):
+        pos, key = b["pos"][qi], b["key"][qi]
+        live = pos != POS_SENTINEL
+        m = int(live.sum())
+        if filt == MFMA_BATCH and m == 0:
+            skipped += 1  # an overflowed candidate buffer: the library answers that query on the exact path
+            continue
+        assert live[:m].all() and not live[m:].any(), (ctx, qi, "sentinels inside the list")
+        assert m == min(KP, n), (ctx, qi, m, "short list")
+        p, kd = pos[:m].astype(np.int64), key[:m]
+        # (d) ordering, uniqueness, range
+        assert (p < n).all(), (ctx, qi, "position past the last row", p[p >= n])
+        assert len(np.unique(p)) == m, (ctx, qi, "duplicate positions")
+        order_ok = (kd[:-1] > kd[1:]) | ((kd[:-1] == kd[1:]) & (p[:-1] < p[1:]))
+        assert order_ok.all(), (ctx, qi, "list not sorted by (key desc, pos asc)", np.nonzero(~order_ok)[0][:5])
+        # (a) key fidelity
+        kh, tol = host_keys(h, queries[qi], filt, metric, ld)
+        err = np.abs(kd - kh[p])
+        ratio = err / tol[p]
+        bad = ratio > 1.0
+        assert not bad.any(), (ctx, qi, "key differs from the host key beyond the allowance",
+                               [(int(p[i]), kd[i], kh[p[i]], tol[p[i]]) for i in np.nonzero(bad)[0][:4]])
+        worst = max(worst, float(ratio.max()))
+        # the shipped bound keeps the documented terms and their 2x safety factor
+        doc = documented_bound(metric, kd, ld, b["R"], b["Q"][qi], b["in_extra"])
+        low = b["bk"][qi][:m] < doc - 1e-9 * np.abs(doc)
+        assert not low.any(), (ctx, qi, "B(key) below the documented bound", b["bk"][qi][:m][low][:3], doc[low][:3])
+        # (b) completeness
+        if m < n:
+            t64 = kd[-1]
+            outside = np.ones(n, dtype=bool)
+            outside[p] = False
+            above = outside & (kh > t64 + tol)
+            assert not above.any(), (ctx, qi, "rows missing from the list", t64,
+                                     [(int(i), kh[i], tol[i]) for i in np.nonzero(above)[0][:4]])
+            # (c) certificate: every row left out scores <= B(t64), every listed row <= B(its key)
+            ex = b["exact"][qi]
+            over = outside & (ex > b["bt"][qi])
+            assert not over.any(), (ctx, qi, "a row outside the list beats B(t64)", b["bt"][qi],
+                                    [(int(i), ex[i], kh[i]) for i in np.nonzero(over)[0][:4]])
+            over_l = ex[p] > b["bk"][qi][:m]
+            assert not over_l.any(), (ctx, qi, "a listed row beats B(its key)",
+                                      [(int(p[i]), ex[p[i]], b["bk"][qi][i]) for i in np.nonzero(over_l)[0][:4]])
+        audited += 1
+    k = (FILTER_NAME[filt], metric, ld)
+    RATIOS[k] = max(RATIOS.get(k, 0.0), worst)
+    sk = SKIPPED.setdefault(k, [0, 0])
+    sk[0] += skipped
+    sk[1] += audited
+    return audited
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
+def test_filter_list_against_its_bound(audit_exe, case, tmp_path):
+    rows, queries, buf = run_case(audit_exe, case, tmp_path)
+    blocks = parse_blocks(buf, len(case.metrics))
+    h = HostRows(rows)
+    R = float(np.sqrt(dev_sumsq(rows)).max())
+    for b in blocks:
+        assert b["R"] == R, (case.id, "IngestStats max norm", b["R"], R)
+        audited = audit_block(case, h, queries, b)
+        # an MFMA list may be empty (overflow -> exact path), but the audit must not be vacuous
+        assert audited >= (b["nq"] + 1) // 2, (case.id, METRIC_NAME[b["metric"]], audited, b["nq"])
+        if case.filt == MFMA_BATCH:
+            assert b["info"][3] == (0 if case.env.get("VL_MFMA_KERNEL") == "tile" else 1), b["info"]
+            if "chunks" in case.tag:
+                assert b["info"][1] >= 2, b["info"]
+            if "stages" in case.tag:
+                assert b["info"][2] == int(case.env["VL_MFMA_STAGES"]), b["info"]
+

@@ -1226,3 +1226,125 @@ def test_f32_batch_path_many_groups_per_launch_matches_the_oracle(V, O, dim):
                 for qi in sorted({min(q, nq - 1) for q in (0, 5, 6, 7, 8, 511, 512, 600, nq - 1)}):
                     ri, rs = ref.search(Q[qi], 10, metric)
                     assert bi[qi].tolist() == ri.tolist() and bs[qi].tolist() == rs.tolist(), (n, metric, nq, qi)
+
+
+# ---------------------------------------------------------------------------------------------
+# planted rows the filters cannot tell apart: only the bound check stands between the filter and a wrong answer
+# ---------------------------------------------------------------------------------------------
+def planted_rows(rng, n, dim, metric, count, rel, base=None):
+    """n unit rows, `count` of them (at sorted random positions) = base + (j + 1) eps dir: their differences from the base
+    stay below `rel` of every base component, so the filter's rounded images of them are identical, while their f64
+    scores against the returned query rise with position.  The list's (key desc, pos asc) tie-break keeps the first 64
+    and drops the true best."""
+    rows = unit_rows(rng, n, dim)
+    if base is None:
+        b = rng.choice([-1.0, 1.0], size=dim) * rng.uniform(0.5, 1.0, size=dim) / np.sqrt(dim)
+        b = b.astype(np.float32).astype(np.float64)
+    else:
+        b = base
+    q = b + 0.05 * rng.standard_normal(dim) / np.sqrt(dim)
+    if metric == M["dotproduct"]:
+        d = q.copy()
+    elif metric == M["cosine"]:
+        bh = b / np.linalg.norm(b)
+        d = q - (q @ bh) * bh
+    elif metric == M["euclidean"]:
+        d = q - b
+    else:
+        d = np.sign(q - b)
+    d /= np.abs(d).max()
+    eps = rel * 0.5 / np.sqrt(dim) / count
+    where = np.sort(rng.choice(np.arange(n), size=count, replace=False))
+    rows[where] = b[None, :] + (np.arange(1, count + 1) * eps)[:, None] * d[None, :]
+    return rows, q, where
+
+
+def check_planted(O, dim, ids, rows, q, where, metric):
+    ref = O.FlatOracle(dim, ids, rows)
+    ri, _ = ref.search(q, 3, metric)
+    assert ri.tolist() == [int(ids[p]) for p in where[::-1][:3]], "construction: the planted scores must rise with position"
+    return ref
+
+
+@pytest.mark.parametrize("metric", [0, 1, 2, 3])
+def test_planted_f32_ties_single_query_needs_the_bound(V, O, metric):
+    """150 rows with IDENTICAL f32 images and f64 scores rising with position: the f32 scan's list holds the first 64, the
+    best rows are outside it, and only B(t64) >= their score keeps the single search off the fast path."""
+    rng = np.random.default_rng(400 + metric)
+    n, dim = 20000, 128
+    rows, q, where = planted_rows(rng, n, dim, metric, 150, 2.0 ** -26)
+    assert (rows[where].astype(np.float32) == rows[where[0]].astype(np.float32)).all()
+    ids = permuted_ids(n)
+    gpu = V.FlatIndex(dim)
+    gpu.add_rows(ids, rows, validate=False)
+    ref = check_planted(O, dim, ids, rows, q, where, metric)
+    for k in (1, 10, 60):
+        assert_same(V, gpu.search_arrays(q, k, metric), ref.search(q, k, metric), ("planted f32", metric, k))
+        assert V.last_path() != V.PATH_FAST, (metric, k)
+    # a batch of 7: Manhattan takes the f32 batch kernel (it has no MFMA filter); cosine, Euclidean and dot take the MFMA
+    # filter (>= MFMA_MIN_BATCH queries on >= MFMA_MIN_ROWS rows)
+    Q = np.stack([q] + list(unit_rows(rng, 6, dim)))
+    bi, bs, bn = gpu.search_batch(Q, 10, metric)
+    for i in range(len(Q)):
+        ri, rs = ref.search(Q[i], 10, metric)
+        assert bi[i].tolist() == ri.tolist() and bs[i].tolist() == rs.tolist(), ("planted f32 batch", metric, i)
+
+
+def bf16_unit_images(x):
+    """What the bf16 filters store for rows x: x/|x| rounded to f32, then to bf16 (nearest even), as u16 bit patterns."""
+    u = (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32).view(np.uint32).astype(np.uint64)
+    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+
+
+@pytest.mark.parametrize("metric", [0, 1, 3])
+def test_planted_bf16_ties_single_and_mfma_batch(V, O, metric):
+    """Differences of ~2^-12 relative (between 2^-24 and 2^-8): f32 resolves the planted rows, bf16 does not -- the base row
+    is +-1/16 in every column, a unit vector of bf16 values, and the planted offsets stay far inside half a bf16 step, so
+    every planted row has the SAME bf16 unit image.  The opt-in bf16 single-query filter must not answer the planted query
+    itself (its f32 fallback resolves the rows and may answer on the fast path); the MFMA batch filter (the planted query
+    inside a batch of 128) must hand it on too.  Answers equal the oracle's."""
+    rng = np.random.default_rng(500 + metric)
+    n, dim = 9000 + 13, 256
+    base = rng.choice([-1.0, 1.0], size=dim) / 16.0
+    rows, q, where = planted_rows(rng, n, dim, metric, 150, 2.0 ** -11, base=base)
+    img = bf16_unit_images(rows[where])
+    assert (img == img[0]).all(), "construction: the planted rows' bf16 images must be identical"
+    assert len(np.unique(rows[where].astype(np.float32), axis=0)) == len(where), "construction: f32 must resolve them"
+    ids = permuted_ids(n)
+    gpu = V.FlatIndex(dim)
+    gpu.add_rows(ids, rows, validate=False)
+    ref = check_planted(O, dim, ids, rows, q, where, metric)
+    gpu.set_single_filter("bf16")
+    for k in (1, 10, 60):
+        gpu.profile_read()
+        gpu.profile_enable(True)
+        got = gpu.search_arrays(q, k, metric)
+        gpu.profile_enable(False)
+        passes = gpu.profile_read()[0]
+        assert_same(V, got, ref.search(q, k, metric), ("planted bf16", metric, k))
+        assert passes >= 2, ("the bf16 filter answered the planted query on its own", metric, k, passes)
+    gpu.set_single_filter("f32")
+    Q = unit_rows(rng, 128, dim)
+    Q[37] = q
+    for k in (1, 10, 60):
+        bi, bs, bn = gpu.search_batch(Q, k, metric)
+        for i in (0, 37, 127):
+            ri, rs = ref.search(Q[i], k, metric)
+            assert bi[i].tolist() == ri.tolist() and bs[i].tolist() == rs.tolist(), ("planted mfma", metric, k, i)
+
+
+@pytest.mark.parametrize("metric", [0, 1, 2, 3])
+def test_planted_f32_ties_multi_list_path(V, O, metric):
+    """k = 100 and 220 (2-4 partitions of 64 candidates): 300 planted f32-identical rows spread over every partition,
+    so each partition's 64 keeps its earliest planted rows and the best ones are outside all of them."""
+    rng = np.random.default_rng(600 + metric)
+    n, dim = 60000, 64
+    rows, q, where = planted_rows(rng, n, dim, metric, 300, 2.0 ** -26)
+    assert (rows[where].astype(np.float32) == rows[where[0]].astype(np.float32)).all()
+    ids = permuted_ids(n)
+    gpu = V.FlatIndex(dim)
+    gpu.add_rows(ids, rows, validate=False)
+    ref = check_planted(O, dim, ids, rows, q, where, metric)
+    for k in (100, 220):
+        assert_same(V, gpu.search_arrays(q, k, metric), ref.search(q, k, metric), ("planted multi-list", metric, k))
+        assert V.last_path() != V.PATH_FAST, (metric, k)

@@ -913,9 +913,9 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
         VL_HIP(launch_scan_bf16(st, metric, d_slab16_, d_norm16_, d_sqnorm_, ws->d_q64, n, (uint32_t)dim_,
                                 ws->d_partials, &grid));
         if (prof) VL_HIP(hipEventRecord(ws->ev1, st));
-        // rows are rounded to bf16 (relative 2^-8 after the f32 step), the query is f32: u_b (1 + u) + u
+        // rows are rounded to bf16, the query is f32 (mfma_scan.hpp)
         VL_HIP(launch_merge_finalize(st, metric, ws->d_partials, grid, 1, d_master_, ws->d_q64, ws->d_q64 + dim_,
-                                     (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_, ws->h_result, 0.00392));
+                                     (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_, ws->h_result, IN_EXTRA_BF16_SINGLE));
         VL_HIP(hipStreamSynchronize(st));
         if (prof) {
             float ms = 0.f;
@@ -1391,8 +1391,7 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
     const void* slab16 = frag ? d_slab16f_ : d_slab16_;
     VL_TRY(ensure_mfma_scratch(ws));
     hipStream_t st = ws->stream;
-    // (2 + u) * u with u = 2^-8 + 2^-23 (f64 -> f32 -> bf16 double rounding), see DESIGN.md
-    const double in_extra = 0.0079;
+    const double in_extra = IN_EXTRA_MFMA;  // bf16 rows and queries (mfma_scan.hpp)
     const bool prof = profile_.load();
     static const bool trace = getenv("VL_TRACE_BATCH") != nullptr;  // diagnostic: host-side phases of a sequence on stderr
     auto now = [] { return std::chrono::steady_clock::now(); };

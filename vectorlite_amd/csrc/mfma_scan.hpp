@@ -24,6 +24,13 @@ constexpr int MFMA_MIN_BATCH = 2;      // measured at N = 10 M x 384: one bf16 p
                                        // the f32 batch kernel needs 2.7-2.9 ms per pass of up to 8 (it stays for Manhattan,
                                        // row lengths without an MFMA shape, and as the fallback)
 
+// `in_extra` of the exactness bound (bound_for_key) for the two bf16 candidate filters: the relative
+// input-rounding term a bf16 row (and query) adds per product on top of the f32 scan's u-terms.
+// bf16 single-query filter (k_scan_bf16): bf16 row (2^-8 after the f32 step), f32 query: u_b (1 + u) + u, rounded up.
+constexpr double IN_EXTRA_BF16_SINGLE = 0.00392;
+// MFMA batch filter: bf16 row and bf16 query: (2 + u) u with u = 2^-8 + 2^-23 (f64 -> f32 -> bf16 double rounding), rounded up.
+constexpr double IN_EXTRA_MFMA = 0.0079;
+
 // bf16 slab row stride in elements: dim rounded up to the MFMA K step (16)
 // Row stride of the bf16 slab in elements: the next length the MFMA kernel has a shape for (8 / 16 / 24 / 32 / 48
 // K steps of 16), zero padded -- a 100- or 300-dimensional index takes the batch filter too, at the price of the
