@@ -207,6 +207,21 @@ int vl_index_search_ef(const vl_index *h, const double *queries, uint64_t nq, ui
  * width, which is why it is off unless asked for (env VL_HNSW_MIN_BEAM sets it for handles created afterwards). */
 int vl_index_hnsw_set_min_beam(vl_index *h, uint32_t min_beam);
 
+/* HNSW handle: how graph walks navigate.  VL_HNSW_NAV_F32 (DEFAULT) steers by f32 distances on the f32 rows and gives
+ * the final beam the reference's exact u64 Metric::distance (src/index/hnsw.rs:113-174) before ordering it by
+ * (u64, node).  VL_HNSW_NAV_REFERENCE (OPT-IN) makes EVERY evaluation that u64 on the f64 rows and keeps the beam in
+ * (u64, first seen) order -- the searcher's insertion order for tied values -- so the walk reproduces the published
+ * HNSW search as restated on the CPU (oracle/vl_hnsw_cpu.c) node for node, distance for distance, and evaluation for
+ * evaluation (vl_index_hnsw_walk_stats counts exactly that walk's evaluations).  What it does NOT pin: the crate
+ * `hnsw 0.11.0` itself (its source is not in the reference tree), nor the graph (built on the GPU either way).  Pinned
+ * for walks of beams <= 512 only; min(k, len) > 512 is answered by the exact scan in both modes.  Each hop costs more
+ * than an f32 hop (one lane walks one f64 row).  Result count, tombstones, ef and min_beam rules are
+ * the same in both modes.  A clone or a reloaded index starts in VL_HNSW_NAV_F32.  VL_ERR_INVALID_ARG for a non-HNSW
+ * handle or an unknown mode. */
+#define VL_HNSW_NAV_F32 0
+#define VL_HNSW_NAV_REFERENCE 1
+int vl_index_hnsw_set_navigation(vl_index *h, int mode);
+
 /* HNSW handle: the graph as it stands, every node (tombstoned ones included; node = insertion position).  level[n]
  * = top layer of each node; layer 0: cnt0[n] neighbours of node i at nbr0[i * m0 ..]; layer L >= 1 of node i: slot
  * upper_off[i] + L - 1 with cntU[slot] neighbours at nbrU[slot * m ..]; node_ids[n] the caller's ids, live[n] 0 for

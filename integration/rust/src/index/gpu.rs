@@ -49,6 +49,7 @@ extern "C" {
     #[allow(dead_code)]
     fn vl_index_set_coalescing(h: *mut vl_index, max_batch: c_int, window_us: c_int) -> c_int;
     fn vl_index_search_batch(h: *const vl_index, queries: *const f64, nq: u64, q_len: u64, k: u64, metric: c_int, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
+    fn vl_index_hnsw_set_navigation(h: *mut vl_index, mode: c_int) -> c_int;
     fn vl_index_search_ef(h: *const vl_index, queries: *const f64, nq: u64, q_len: u64, k: u64, ef: u32, metric: c_int, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_vlc_open(path: *const c_char, out: *mut *mut vl_vlc_doc) -> c_int;
     fn vl_vlc_close(doc: *mut vl_vlc_doc);
@@ -74,6 +75,8 @@ const VL_ERR_DUP_ID: c_int = 2;
 const VL_ERR_NOT_FOUND: c_int = 3;
 const VL_ERR_METRIC_MISMATCH: c_int = 4;
 const VL_ERR_NAN_SCORE: c_int = 5;
+const VL_HNSW_NAV_F32: c_int = 0;
+const VL_HNSW_NAV_REFERENCE: c_int = 1;
 
 fn last_error() -> String {
     unsafe { CStr::from_ptr(vl_last_error()).to_string_lossy().into_owned() }
@@ -479,6 +482,14 @@ impl GpuHnswIndex {
     }
     pub fn metric(&self) -> SimilarityMetric {
         self.metric
+    }
+    /// Opt-in: walks navigate by the reference's own u64 distances with ties in first-seen order
+    /// (`VL_HNSW_NAV_REFERENCE`); `false` returns to the default f32 navigation.  A clone starts in the default.
+    pub fn set_reference_navigation(&mut self, on: bool) -> Result<(), String> {
+        match unsafe { vl_index_hnsw_set_navigation(self.h.raw, if on { VL_HNSW_NAV_REFERENCE } else { VL_HNSW_NAV_F32 }) } {
+            VL_OK => Ok(()),
+            _ => Err(last_error()),
+        }
     }
     /// Bulk insert (one batched graph build on the device) for the custom Deserialize.
     pub fn add_all(&mut self, ids: &[u64], values: &[f64]) -> Result<(), String> {

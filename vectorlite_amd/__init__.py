@@ -613,6 +613,16 @@ class HNSWIndex:
         """Opt-in beam floor of searches that name no ef; default 0 = the reference's strict ef = min(k, len)."""
         _raise(self._L.vl_index_hnsw_set_min_beam(self._h, int(min_beam)))
 
+    _NAVIGATION = {"f32": 0, "reference": 1}  # VL_HNSW_NAV_F32, VL_HNSW_NAV_REFERENCE
+
+    def set_navigation(self, mode: str) -> None:
+        """How walks navigate: "f32" (default; f32 steering, the final beam re-scored with the reference's u64) or
+        "reference" (opt-in; every evaluation the reference's u64, ties in first-seen order: the CPU restatement of
+        the published walk, oracle/vl_hnsw_cpu.c, node for node).  A clone starts in "f32"."""
+        if not isinstance(mode, str) or mode not in self._NAVIGATION:
+            raise ValueError(f"navigation mode must be 'f32' or 'reference', got {mode!r}")
+        _raise(self._L.vl_index_hnsw_set_navigation(self._h, self._NAVIGATION[mode]))
+
     def walk_stats(self) -> Tuple[int, int]:
         """(queries walked, distance evaluations made for them) since creation."""
         a, b = C.c_uint64(0), C.c_uint64(0)

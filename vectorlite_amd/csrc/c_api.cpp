@@ -833,6 +833,20 @@ int vl_index_hnsw_set_min_beam(vl_index* h, uint32_t min_beam)
     return VL_OK;
 }
 
+int vl_index_hnsw_set_navigation(vl_index* h, int mode)
+{
+    if (!h || !h->hnsw) {
+        vl::set_last_error("this entry point needs an HNSW index handle");
+        return VL_ERR_INVALID_ARG;
+    }
+    if (mode != VL_HNSW_NAV_F32 && mode != VL_HNSW_NAV_REFERENCE) {
+        vl::set_last_error("unknown HNSW navigation mode " + std::to_string(mode) + " (VL_HNSW_NAV_F32 = 0, VL_HNSW_NAV_REFERENCE = 1)");
+        return VL_ERR_INVALID_ARG;
+    }
+    h->hnsw->set_navigation(mode == VL_HNSW_NAV_REFERENCE ? vl::HnswIndex::NAV_REFERENCE : vl::HnswIndex::NAV_F32);
+    return VL_OK;
+}
+
 int vl_index_hnsw_walk_stats(const vl_index* h, uint64_t* queries, uint64_t* distance_evals)
 {
     if (!h || !h->hnsw) return VL_ERR_INVALID_ARG;

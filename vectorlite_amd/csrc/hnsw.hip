@@ -13,7 +13,9 @@
 //     north_star -- from which the returned distances and scores are computed; the BUILD keeps f32-derived
 //     edge distances (used only to pick the farthest edge in the link phase);
 //   * the beam (result list + frontier in one) is a sorted list held one or two entries per lane,
-//     updated with ballot / DPP shifts like the flat scan's top-k list.
+//     updated with ballot / DPP shifts like the flat scan's top-k list;
+//   * opt-in (k_hnsw_search_ref): the query walk navigates by the reference's own u64 distances on the f64 rows, the
+//     beam in (u64, first seen) order -- oracle/vl_hnsw_cpu.c's walk, node for node and evaluation for evaluation.
 #include "hnsw.hpp"
 
 #include <mutex>
@@ -487,6 +489,236 @@ __global__ __launch_bounds__(256) void k_hnsw_search(HnswGraphView g, const doub
     }
 }
 
+// ---- reference navigation (opt-in, vl_index_hnsw_set_navigation) ----------------------------------------------------
+// The walk of oracle/vl_hnsw_cpu.c (vlo_hnsw_walk), step for step: every evaluation is the reference's u64
+// Metric::distance on the f64 rows, and the beam keeps tied u64 values in first-seen order (the searcher's
+// partition_point(d <= x) insertion).  First-seen order is a per-walk sequence number: the entry point is 0, every
+// freshly visited neighbour takes the next one in neighbour-list order, across layers.  (u64, seq) keys are unique and
+// a new key's seq is larger than every key already in the beam, so ranking by (u64, seq) puts it behind its ties
+// exactly like partition_point does, and the beam after a hop -- the best ef keys of everything offered -- does not
+// depend on the order in which the hop's lanes are inserted.
+
+// Sorted beam: ascending by (dist, seq); capacity 64*S, logical width `ef` <= 64*S.  Empty slots are (~0, ~0, NONE).
+template <int S>
+struct RefBeam {
+    unsigned long long d[S];
+    uint32_t sq[S];
+    uint32_t v[S];  // node | EXPANDED
+
+    __device__ __forceinline__ void init()
+    {
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            d[s] = ~0ull;
+            sq[s] = ~0u;
+            v[s] = HNSW_NONE;
+        }
+    }
+    __device__ __forceinline__ int rank_of(unsigned long long dist, uint32_t seq) const
+    {
+        int c = 0;
+#pragma unroll
+        for (int s = 0; s < S; ++s) c += __popcll(__ballot(d[s] < dist || (d[s] == dist && sq[s] < seq)));
+        return c;
+    }
+    __device__ __forceinline__ void insert(unsigned long long dist, uint32_t seq, uint32_t node, int ef)
+    {
+        const int idx = rank_of(dist, seq);
+        if (idx >= ef) return;  // wave-uniform
+        const int lane = lane_id();
+#pragma unroll
+        for (int s = S - 1; s >= 0; --s) {  // top slot first: it reads the slot below before that moves
+            if ((s + 1) * 64 <= idx) break;
+            const int j = s * 64 + lane;
+            unsigned long long pd = wave_shr1(d[s]);
+            uint32_t pq = wave_shr1(sq[s]);
+            uint32_t pv = wave_shr1(v[s]);
+            if (s > 0) {
+                const unsigned long long cd = read_lane(d[s > 0 ? s - 1 : 0], 63);
+                const uint32_t cq = read_lane(sq[s > 0 ? s - 1 : 0], 63);
+                const uint32_t cv = read_lane(v[s > 0 ? s - 1 : 0], 63);
+                if (lane == 0) {
+                    pd = cd;
+                    pq = cq;
+                    pv = cv;
+                }
+            }
+            if (j == idx) {
+                d[s] = dist;
+                sq[s] = seq;
+                v[s] = node;
+            } else if (j > idx) {
+                d[s] = pd;
+                sq[s] = pq;
+                v[s] = pv;
+            }
+            if (j >= ef) {
+                d[s] = ~0ull;
+                sq[s] = ~0u;
+                v[s] = HNSW_NONE;
+            }
+        }
+    }
+    __device__ __forceinline__ void get(int idx, unsigned long long& dist, uint32_t& node) const
+    {
+        const int si = idx >> 6, l = idx & 63;  // idx is wave-uniform
+        dist = read_lane(d[0], l);
+        node = read_lane(v[0], l);
+#pragma unroll
+        for (int s = 1; s < S; ++s)
+            if (si == s) {
+                dist = read_lane(d[s], l);
+                node = read_lane(v[s], l);
+            }
+    }
+    __device__ __forceinline__ int next_unexpanded() const
+    {
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const unsigned long long m = __ballot((v[s] & EXPANDED) == 0u);
+            if (m) return s * 64 + __ffsll((long long)m) - 1;
+        }
+        return -1;
+    }
+    __device__ __forceinline__ void mark_expanded(int idx)
+    {
+        const int lane = lane_id();
+#pragma unroll
+        for (int s = 0; s < S; ++s)
+            if (s * 64 + lane == idx) v[s] |= EXPANDED;
+    }
+    __device__ __forceinline__ void reopen()
+    {
+#pragma unroll
+        for (int s = 0; s < S; ++s)
+            if (v[s] != HNSW_NONE) v[s] &= ~EXPANDED;
+    }
+};
+
+// Metric::distance(query, row) -> u64 exactly (src/index/hnsw.rs:113-174): row_distance's f64 accumulation in the
+// reference's order, one lane per row, then `as u64` (walk_key_to_u64(walk_key(x)) == rust_as_u64(x) for every x).
+template <int METRIC>
+__device__ __forceinline__ unsigned long long row_distance_u64(const HnswGraphView& g, uint32_t node, const double* q)
+{
+    return walk_key_to_u64(row_distance<METRIC>(g.master + (size_t)node * g.dim, q, g.dim));
+}
+
+// One layer of vlo_hnsw_walk's search_layer: expand the first unexpanded beam entry until none is left.  Lane l
+// evaluates neighbour l of the expanded node (lists hold <= 64 entries: the launcher refuses m, m0 > 64).
+template <int METRIC, int S>
+__device__ __forceinline__ void beam_layer_ref(const HnswGraphView& g, const double* q, int layer, Visited& vis,
+                                               RefBeam<S>& L, int ef, uint32_t& seq, uint32_t& evals)
+{
+    const int lane = lane_id();
+    for (;;) {
+        const int idx = L.next_unexpanded();
+        if (idx < 0) break;
+        unsigned long long dc;
+        uint32_t c;
+        L.get(idx, dc, c);
+        L.mark_expanded(idx);
+        const LayerView lv = layer_of(g, c & ~EXPANDED, layer);
+        const uint32_t e = (uint32_t)lane < lv.cnt ? lv.nbr[lane] : HNSW_NONE;
+        // a list that names a node twice: the CPU walk visits it at its first position and skips the second (it is
+        // marked by then).  Lanes of one atomic-or have no order, so every later copy stays out of the marking.
+        bool first = e != HNSW_NONE;
+        for (uint32_t j = 0; j + 1 < lv.cnt; ++j) first = first && !((uint32_t)lane > j && e == read_lane(e, (int)j));
+        const bool act = vis.mark(e, first);
+        const unsigned long long mk = __ballot(act);
+        const uint32_t my_seq = seq + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+        seq += (uint32_t)__popcll(mk);
+        evals += (uint32_t)__popcll(mk);
+        unsigned long long de = ~0ull;
+        if (act) de = row_distance_u64<METRIC>(g, e, q);
+        // a candidate tied with the current worst ranks behind it (larger seq): only a strictly smaller u64 can enter a
+        // full beam.  The worst only shrinks while we insert; insert() re-checks the rank.
+        unsigned long long w;
+        uint32_t wn;
+        L.get(ef - 1, w, wn);
+        unsigned long long m = __ballot(act && (wn == HNSW_NONE || de < w));
+        while (m) {
+            const int src = __builtin_amdgcn_readfirstlane(__ffsll((long long)m) - 1);
+            m &= m - 1;
+            L.insert(read_lane(de, src), read_lane(my_seq, src), read_lane(e, src), ef);
+        }
+    }
+}
+
+template <int S>
+__device__ __forceinline__ void next_layer(RefBeam<S>& L, Visited& vis)
+{
+    vis.clear();
+    L.reopen();
+#pragma unroll
+    for (int s = 0; s < S; ++s) (void)vis.mark(L.v[s] & ~EXPANDED, L.v[s] != HNSW_NONE);
+}
+
+// Same arguments and outputs as k_hnsw_search; the beam it ends with already holds the reference's u64 values in the
+// reference's order, so there is no re-scoring and no sort: step (3) of k_hnsw_search reads it straight from the lanes.
+// LDS: the f64 query only (dim <= 3072: 96 KB per block of four walks).
+template <int METRIC, int S>
+__global__ __launch_bounds__(256) void k_hnsw_search_ref(HnswGraphView g, const double* __restrict__ queries, uint32_t nq,
+                                                         uint32_t ef, uint32_t entry, int max_level, uint32_t max_candidates,
+                                                         uint32_t refill, uint32_t k_stride, unsigned long long* __restrict__ out_ids,
+                                                         double* __restrict__ out_scores, unsigned long long* __restrict__ out_n,
+                                                         unsigned long long* __restrict__ stat_evals)
+{
+    extern __shared__ double q_lds[];
+    const int lane = lane_id();
+    const int wave = threadIdx.x >> 6;
+    const uint32_t slot = blockIdx.x * 4 + wave;
+    if (slot >= g.n_slots) return;
+    const size_t q_words = ((size_t)g.dim + 1) & ~(size_t)1;  // 16-byte granules per wave
+    double* q = q_lds + (size_t)wave * q_words;
+    Visited vis;
+    vis.attach(g, slot);
+
+    for (uint32_t qi = slot; qi < nq; qi += gridDim.x * 4) {
+        for (uint32_t i = lane; i < g.dim; i += 64) q[i] = queries[(size_t)qi * g.dim + i];
+        __builtin_amdgcn_wave_barrier();
+        RefBeam<S> L;
+        L.init();
+        uint32_t evals = 1, seq = 1;  // the entry point: one evaluation, sequence number 0
+        {
+            const unsigned long long d0 = read_lane(row_distance_u64<METRIC>(g, entry, q), 0);
+            L.insert(d0, 0u, entry, 1);
+            (void)vis.mark(entry, lane == 0);
+        }
+        for (int layer = max_level; layer >= 1; --layer) {
+            beam_layer_ref<METRIC, S>(g, q, layer, vis, L, 1, seq, evals);
+            next_layer(L, vis);
+        }
+        beam_layer_ref<METRIC, S>(g, q, 0, vis, L, (int)ef, seq, evals);
+        vis.clear();
+
+        // k_hnsw_search's step (3) on the beam as it stands: real entries are a prefix of it, in (u64, first seen) order
+        uint32_t n_real = 0;
+#pragma unroll
+        for (int s = 0; s < S; ++s) n_real += (uint32_t)__popcll(__ballot((uint32_t)(s * 64 + lane) < ef && L.v[s] != HNSW_NONE));
+        const uint32_t n_take = refill ? n_real : (n_real < max_candidates ? n_real : max_candidates);
+        uint32_t kept = 0;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const uint32_t r = s * 64 + lane;
+            const bool in = r < n_take;
+            const uint32_t node = in ? (L.v[s] & ~EXPANDED) : 0u;
+            const bool alive = in && g.live[node] != 0;
+            const unsigned long long mk = __ballot(alive);
+            const uint32_t pos = kept + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+            if (alive && pos < max_candidates) {
+                out_ids[(size_t)qi * k_stride + pos] = g.node_id[node];
+                out_scores[(size_t)qi * k_stride + pos] = hnsw_score_dev<METRIC>(L.d[s]);
+            }
+            kept += (uint32_t)__popcll(mk);
+        }
+        if (lane == 0) {
+            out_n[qi] = kept < max_candidates ? kept : max_candidates;
+            if (stat_evals) atomicAdd(stat_evals, (unsigned long long)evals);
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 // Build phase A: node p = first + i searches the graph of the nodes < first and fills its own lists.
 template <int METRIC, int S>
 __global__ __launch_bounds__(256) void k_hnsw_insert_search(HnswGraphView g, uint32_t first, uint32_t n, uint32_t efc,
@@ -831,6 +1063,35 @@ hipError_t launch_hnsw_search(hipStream_t s, int metric, const HnswGraphView& g,
         case 2: return launch(k_hnsw_search<MM, 2>);
         case 4: return launch(k_hnsw_search<MM, 4>);
         default: return launch(k_hnsw_search<MM, 8>);
+        }
+    });
+}
+
+hipError_t launch_hnsw_search_ref(hipStream_t s, int metric, const HnswGraphView& g, const double* queries, uint32_t nq,
+                                  uint32_t ef, uint32_t entry, int max_level, uint32_t max_candidates, uint32_t refill,
+                                  uint32_t k_stride, unsigned long long* out_ids, double* out_scores, unsigned long long* out_n,
+                                  unsigned long long* stat_evals)
+{
+    if (nq == 0) return hipSuccess;
+    if (ef == 0 || ef > (uint32_t)HNSW_MAX_EF || g.m0 > 64 || g.m > 64 || max_candidates > k_stride) return hipErrorInvalidValue;
+    const size_t q_words = ((size_t)g.dim + 1) & ~(size_t)1;
+    const size_t lds = (size_t)4 * q_words * sizeof(double);  // independent of ef
+    if (lds > HNSW_LDS_MAX) return hipErrorInvalidValue;
+    const int grid = grid_for(g, nq);
+    return dispatch_metric(metric, [&](auto M) -> hipError_t {
+        constexpr int MM = decltype(M)::value;
+        auto launch = [&](auto kern) -> hipError_t {
+            const hipError_t e = allow_big_lds(kern, lds);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, g, queries, nq, ef, entry, max_level, max_candidates,
+                               refill, k_stride, out_ids, out_scores, out_n, stat_evals);
+            return hipGetLastError();
+        };
+        switch (hnsw_beam_slots(ef)) {
+        case 1: return launch(k_hnsw_search_ref<MM, 1>);
+        case 2: return launch(k_hnsw_search_ref<MM, 2>);
+        case 4: return launch(k_hnsw_search_ref<MM, 4>);
+        default: return launch(k_hnsw_search_ref<MM, 8>);
         }
     });
 }

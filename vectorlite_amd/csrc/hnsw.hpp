@@ -7,7 +7,9 @@
 // What the reference delegates to crate `hnsw 0.11.0` (source not vendored, Cargo.lock:1111-1123):
 // the graph build and walk.  This is OUR OWN traversal (standard HNSW: greedy descent through the
 // upper layers, beam search of width ef on layer 0; M = 16, M0 = 32 like src/index/hnsw.rs:95-109).
-// Its parity with the crate is UNPINNED; it is judged by recall against exact search.
+// Its parity with the crate is UNPINNED; it is judged by recall against exact search.  The opt-in reference
+// navigation (launch_hnsw_search_ref) is pinned node for node to the CPU restatement of the published walk
+// (oracle/vl_hnsw_cpu.c) on the same graph -- still not to the crate itself.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -61,6 +63,16 @@ hipError_t launch_hnsw_search(hipStream_t s, int metric, const HnswGraphView& g,
                               uint32_t ef, uint32_t entry, int max_level, uint32_t max_candidates, uint32_t refill,
                               uint32_t k_stride, unsigned long long* out_ids, double* out_scores, unsigned long long* out_n,
                               unsigned long long* stat_evals);
+
+// The same walk navigated the reference's way (opt-in, VL_HNSW_NAV_REFERENCE): every evaluation -- navigation
+// included -- is the exact u64 Metric::distance on the f64 rows, the beam is ordered by (u64, first seen), and the final
+// beam is post-processed as above without a re-scoring pass.  It reproduces oracle/vl_hnsw_cpu.c (vlo_hnsw_walk) node
+// for node; stat_evals gets exactly that walk's evaluation count.  Same arguments as launch_hnsw_search; its LDS is
+// the f64 query only, so every dim the index accepts walks at every ef <= HNSW_MAX_EF.
+hipError_t launch_hnsw_search_ref(hipStream_t s, int metric, const HnswGraphView& g, const double* queries, uint32_t nq,
+                                  uint32_t ef, uint32_t entry, int max_level, uint32_t max_candidates, uint32_t refill,
+                                  uint32_t k_stride, unsigned long long* out_ids, double* out_scores, unsigned long long* out_n,
+                                  unsigned long long* stat_evals);
 
 // Build phase A: the rows [first, first+n) are new nodes; each walks the graph that holds the
 // nodes < first (entry/max_level describe it) with beam width ef_construction and writes its own

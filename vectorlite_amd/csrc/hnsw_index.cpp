@@ -804,8 +804,10 @@ int HnswIndex::search_batch(const double* queries, uint64_t nq, uint64_t q_len, 
     unsigned long long* d_ids = ws->d_out;
     double* d_scores = reinterpret_cast<double*>(ws->d_out + nq * kd);
     unsigned long long* d_n = ws->d_out + 2 * nq * kd;
-    hipError_t le = launch_hnsw_search(st, metric_, g, ws->d_q, (uint32_t)nq, (uint32_t)ef_walk, entry_, max_level_,
-                                       (uint32_t)max_candidates, ef ? 1u : 0u, (uint32_t)kd, d_ids, d_scores, d_n, d_stat_evals_);
+    // both navigations take the same arguments and finish the beam the same way; the mode is read once per launch
+    const auto walk = nav_.load() == NAV_REFERENCE ? launch_hnsw_search_ref : launch_hnsw_search;
+    hipError_t le = walk(st, metric_, g, ws->d_q, (uint32_t)nq, (uint32_t)ef_walk, entry_, max_level_,
+                         (uint32_t)max_candidates, ef ? 1u : 0u, (uint32_t)kd, d_ids, d_scores, d_n, d_stat_evals_);
     if (le == hipSuccess) le = hipMemcpyAsync(ws->h_out, ws->d_out, nq * (2 * kd + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
     const hipError_t se = hipStreamSynchronize(st);  // always: the scratch must be idle before it goes back to the pool
     if (le == hipSuccess) le = se;

@@ -101,6 +101,13 @@ public:
     // beam floor of searches that name no ef (0 = the reference's strict ef = min(k, len)); at most HNSW_MAX_EF
     void set_min_beam(uint32_t b) { min_beam_.store(b > (uint32_t)HNSW_MAX_EF ? (uint32_t)HNSW_MAX_EF : b); }
     uint32_t min_beam() const { return min_beam_.load(); }
+    // how walks navigate (opt-in): NAV_F32 (default) = f32 navigation, the final beam re-scored with the exact u64;
+    // NAV_REFERENCE = every evaluation the exact u64, ties in first-seen order (launch_hnsw_search_ref).  Read once
+    // per launch.  Pinned for walks only: a beam past HNSW_MAX_EF is answered by the exact scan in either mode.
+    // Like min_beam, a clone or a reloaded index starts in NAV_F32.
+    static constexpr int NAV_F32 = 0, NAV_REFERENCE = 1;
+    void set_navigation(int mode) { nav_.store(mode == NAV_REFERENCE ? NAV_REFERENCE : NAV_F32); }
+    int navigation() const { return nav_.load(); }
     int clone(HnswIndex** out) const;
     // live rows in node (insertion) order: the `vector_values` member of the serialised form
     int export_rows(uint64_t* out_ids, double* out_values) const;
@@ -161,6 +168,7 @@ private:
     uint64_t live_count_ = 0;
 
     std::atomic<uint32_t> min_beam_{0};  // 0 = the reference's strict ef = min(k, len); a wider floor is opt-in
+    std::atomic<int> nav_{NAV_F32};      // walk navigation; the reference's u64 order is opt-in
     mutable std::atomic<uint64_t> stat_queries_{0}, stat_evals_{0};  // stat_evals_: the exact-fallback's share only
     mutable Coalescer<CoalesceReq> co_;
 
