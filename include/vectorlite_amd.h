@@ -395,9 +395,14 @@ int vl_last_path(void);                                          /* vl_path of t
 /* Force every search onto an exact pipeline (testing): 0 = automatic, 2 / 3 = vl_path value. */
 int vl_index_force_path(vl_index *h, int path);
 
-/* Single-query candidate filter: 0 = stream the f32 slab (default, north_star's layout);
+/* Single-query candidate filter: 0 = stream the f32 slab only;
  * 1 = stream a bf16 copy of the slab first (half the HBM bytes) and fall back to the f32 scan when
- * the exactness bound cannot certify the answer.  Results are identical either way. */
+ * the exactness bound cannot certify the answer (switches itself off for good once more than a third of
+ * 64+ tries failed);
+ * 2 = auto (new handles; VL_SINGLE_FILTER=f32|bf16|auto sets the start mode): the bf16 copy first when the
+ * f32 slab is at least 512 MiB (VL_SINGLE_FILTER_MIN_MB), off while more than a third of the last 64 tries
+ * failed to certify, re-tried every 16th search while off.  The bf16 copy (+0.5 x the f32 slab) is built on the
+ * first search that uses it.  Results are identical in every mode. */
 int vl_index_set_single_filter(vl_index *h, int mode);
 
 /* Coalescing of concurrent vl_index_search calls, flat or HNSW handle (the reference serves searches

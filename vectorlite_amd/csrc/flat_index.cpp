@@ -184,8 +184,10 @@ int GpuFlatIndex::create(uint64_t dim, int device, GpuFlatIndex** out)
     VL_TRY(dev_alloc(&idx->d_stats_, 1));
     VL_HIP(hipMemsetAsync(idx->d_stats_, 0, sizeof(IngestStats), idx->mut_stream_));
     VL_HIP(hipStreamSynchronize(idx->mut_stream_));
-    if (const char* sf = getenv("VL_SINGLE_FILTER")) {
-        if (std::strcmp(sf, "bf16") == 0) idx->set_single_filter(1);
+    // VL_SINGLE_FILTER=f32|bf16|auto: the single-query filter a handle starts with (auto when unset or unrecognised)
+    idx->set_single_filter(parse_single_filter(getenv("VL_SINGLE_FILTER"), FILTER_AUTO));
+    if (const char* mb = getenv("VL_SINGLE_FILTER_MIN_MB")) {
+        if (*mb) idx->set_single_filter_min_bytes(std::strtoull(mb, nullptr, 10) << 20);
     }
     // Concurrent single searches share slab passes by default (the reference's many-readers model, src/client.rs:398):
     // window 0, so a lone caller leads a pass of one = the plain single-search path.  VL_COALESCE=0 starts handles with it off.
@@ -760,9 +762,9 @@ int GpuFlatIndex::search_batch_locked(const double* queries, uint64_t nq, uint64
     const bool f32_batch = scan_batch_supported(ld_);
     const bool batchable = nq > 1 && force_path_.load() == 0 && k_eff <= (uint64_t)KFAST_MAX && n_out_of_domain_ == 0;
     auto out_at = [&](uint64_t* base, uint64_t qi) { return base ? base + qi * k : nullptr; };
-    auto single = [&](uint64_t qi, bool skip_fast) -> int {
+    auto single = [&](uint64_t qi, bool skip_fast, bool skip_bf16 = false) -> int {
         return search_locked(ws, queries + qi * dim_, k_eff, metric, out_at(out_pos, qi), out_at(out_ids, qi),
-                             out_scores + qi * k, out_n + qi, skip_fast);
+                             out_scores + qi * k, out_n + qi, skip_fast, skip_bf16);
     };
     if (!batchable) {
         for (uint64_t qi = 0; qi < nq; ++qi) VL_TRY(single(qi, false));
@@ -784,8 +786,9 @@ int GpuFlatIndex::search_batch_locked(const double* queries, uint64_t nq, uint64
             return OK;
         }
         if (left <= 2 || !f32_batch) {  // one or two stragglers (or no 8-query f32 shape): one by one on the f32 path
+            // (a bf16 filter already failed them: the single-query bf16 stage would only add a pass)
             for (uint64_t qi = 0; qi < nq; ++qi)
-                if (!done[qi]) VL_TRY(single(qi, false));
+                if (!done[qi]) VL_TRY(single(qi, false, true));
             return OK;
         }
     }
@@ -862,9 +865,30 @@ int GpuFlatIndex::search_batch_locked(const double* queries, uint64_t nq, uint64
     return OK;
 }
 
+// Single-query filter choice (set_single_filter).  Mode 1 keeps its one-way switch-off; auto applies the recent-outcome
+// window of single_filter.hpp, so a bad streak pauses it and the periodic probes bring it back.
+bool GpuFlatIndex::bf16_first(uint64_t n) const
+{
+    const int mode = single_filter_.load(std::memory_order_relaxed);
+    if (mode == FILTER_BF16) {
+        const uint64_t tries = bf16_tries_.load(std::memory_order_relaxed);
+        return !(tries >= 64 && bf16_fails_.load(std::memory_order_relaxed) * 3 > tries);
+    }
+    if (mode != FILTER_AUTO || auto_unavailable_.load(std::memory_order_relaxed)) return false;
+    if (n * (uint64_t)ld_ * sizeof(float) < auto_min_bytes_) return false;
+    return auto_window_.want();
+}
+
+void GpuFlatIndex::bf16_outcome(bool certified) const
+{
+    bf16_tries_.fetch_add(1, std::memory_order_relaxed);
+    if (!certified) bf16_fails_.fetch_add(1, std::memory_order_relaxed);
+    auto_window_.record(certified);
+}
+
 int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_eff, int metric,
                                 uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
-                                bool skip_fast) const
+                                bool skip_fast, bool skip_bf16) const
 {
     const uint64_t n = ids_.size();
     hipStream_t st = ws->stream;
@@ -899,35 +923,56 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
     const bool fast_ok = !skip_fast && forced == 0 && k_eff <= (uint64_t)KFAST_MAX && n_out_of_domain_ == 0 &&
                          q_in_domain;
 
-    // Opt-in first stage: scan the bf16 copy of the slab (half the HBM bytes).  Its candidates get the
-    // same exact f64 rescoring and a bound with the bf16 row-rounding term; if that cannot certify
-    // the answer the f32 scan below runs as before.  The stage switches itself off on data where it
-    // rarely certifies (dense neighbourhoods).
-    if (fast_ok && single_filter_.load() == 1 && scan_bf16_supported((uint32_t)dim_, metric) &&
-        !(bf16_tries_.load() >= 64 && bf16_fails_.load() * 3 > bf16_tries_.load())) {
-        VL_TRY(ensure_bf16_slab(false));
-        VL_TRY(q_to_device());
+    // First stage on large indexes (auto) or on request (mode 1): scan the bf16 copy of the slab (half the HBM bytes).
+    // Its candidates get the same exact f64 rescoring and a bound with the bf16 row-rounding term; if that cannot
+    // certify the answer the f32 scan below runs as before.  Same protocol as the f32 scan: the f32 query in the kernel
+    // arguments, the finalize reading the pinned f64 query, a stamped result block -- nothing is copied to the device.
+    bool bf16_stage = fast_ok && !skip_bf16 && scan_bf16_supported((uint32_t)dim_, metric) && bf16_first(n);
+    if (bf16_stage) {
+        const int brc = ensure_bf16_slab(false);
+        if (brc != OK) {
+            if (single_filter_.load() != FILTER_AUTO) return brc;
+            auto_unavailable_.store(true);  // auto: no room for the copy, the f32 path answers
+            bf16_stage = false;
+        }
+    }
+    if (bf16_stage) {
         const bool prof = profile_.load();
-        int grid = 0;
+        const uint32_t ldb = mfma_ldb((uint32_t)dim_);
+        if (ws->q32.size() < ldb) ws->q32.assign(ldb, 0.0f);  // columns past dim_ stay zero
+        for (uint64_t i = 0; i < dim_; ++i) ws->q32[i] = (float)query[i];  // nearest even, like the kernel's own rounding
+        uint32_t seq = ++ws->seq;
+        if (seq == 0) seq = ++ws->seq;
+        ws->h_result->seq = 0;
+        int grid = 0, variant = 0;
         if (prof) VL_HIP(hipEventRecord(ws->ev0, st));
-        VL_HIP(launch_scan_bf16(st, metric, d_slab16_, d_norm16_, d_sqnorm_, ws->d_q64, n, (uint32_t)dim_,
-                                ws->d_partials, &grid));
+        VL_HIP(launch_scan_bf16(st, metric, d_slab16_, d_norm16_, d_sqnorm_, nullptr, n, (uint32_t)dim_, ws->d_partials,
+                                &grid, ws->q32.data(), &variant));
         if (prof) VL_HIP(hipEventRecord(ws->ev1, st));
         // rows are rounded to bf16, the query is f32 (mfma_scan.hpp)
-        VL_HIP(launch_merge_finalize(st, metric, ws->d_partials, grid, 1, d_master_, ws->d_q64, ws->d_q64 + dim_,
+        VL_HIP(launch_merge_finalize(st, seq, metric, ws->d_partials, grid, d_master_, ws->h_q64, ws->h_q64 + dim_,
                                      (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_, ws->h_result, IN_EXTRA_BF16_SINGLE));
-        VL_HIP(hipStreamSynchronize(st));
+        last_scan_variant_.store(variant, std::memory_order_relaxed);
+        last_scan_grid_.store(grid, std::memory_order_relaxed);
+        last_scan_qarg_.store(1, std::memory_order_relaxed);
+        VL_TRY(wait_result(ws, seq));
         if (prof) {
             float ms = 0.f;
-            VL_HIP(hipEventElapsedTime(&ms, ws->ev0, ws->ev1));
+            hipError_t pe = hipEventElapsedTime(&ms, ws->ev0, ws->ev1);
+            if (pe == hipErrorNotReady) {
+                VL_HIP(hipEventSynchronize(ws->ev1));
+                pe = hipEventElapsedTime(&ms, ws->ev0, ws->ev1);
+            }
+            VL_HIP(pe);
             std::lock_guard<std::mutex> g(prof_mu_);
             prof_n_ += 1;
             prof_ms_ += ms;
-            prof_bytes_ += n * (uint64_t)mfma_ldb((uint32_t)dim_) * 2;
+            prof_bytes_ += n * (uint64_t)ldb * 2;
         }
-        bf16_tries_.fetch_add(1);
         const SearchResultBlock& r = *ws->h_result;
-        if (!(r.flags & RESULT_NEEDS_EXACT) && r.n_out == k_eff) {
+        const bool certified = !(r.flags & RESULT_NEEDS_EXACT) && r.n_out == k_eff;
+        bf16_outcome(certified);
+        if (certified) {
             for (uint64_t i = 0; i < k_eff; ++i) {
                 const uint32_t p = r.pos[i];
                 if (p >= n) {
@@ -942,7 +987,6 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
             set_last_path(PATH_FAST);
             return OK;
         }
-        bf16_fails_.fetch_add(1);
     }
     if (fast_ok) {
         const bool prof = profile_.load();

@@ -22,6 +22,7 @@
 #include "coalescer.hpp"
 #include "kernels.hpp"
 #include "mfma_scan.hpp"
+#include "single_filter.hpp"
 
 namespace vl {
 
@@ -185,13 +186,20 @@ public:
     uint64_t capacity() const { return cap_; }
 
     void force_path(int p) { force_path_.store(p); }
-    // 0: single queries scan the f32 slab (default); 1: try the bf16 slab first (half the bytes)
+    // Which slab a single query scans first (single_filter.hpp).  0: the f32 slab only.  1: the bf16 copy first, always
+    // (half the bytes; switches itself off for good once more than a third of 64+ tries failed to certify).  2 ("auto",
+    // the default): the bf16 copy first when the f32 slab is at least SINGLE_FILTER_MIN_BYTES (VL_SINGLE_FILTER_MIN_MB at
+    // create), paused by AutoFilterWindow's rule while it fails to certify.
     void set_single_filter(int mode)
     {
         single_filter_.store(mode);
         bf16_tries_.store(0);
         bf16_fails_.store(0);
+        auto_window_.reset();
+        auto_unavailable_.store(false);
     }
+    int single_filter() const { return single_filter_.load(); }
+    void set_single_filter_min_bytes(uint64_t b) { auto_min_bytes_ = b; }
     // Group concurrent single-query search() calls into shared slab passes (coalescer.hpp, search_coalesced()).
     // max_batch <= 1 turns it off.  window_us: how long a lone caller waits for company.  create() turns it on with
     // (COALESCE_DEFAULT_BATCH, 0) unless VL_COALESCE=0.
@@ -236,8 +244,11 @@ private:
     int search_coalesced(const double* query, uint64_t q_len, uint64_t k, int metric, uint64_t* out_pos,
                          uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;
     void run_coalesced(std::vector<CoalesceReq*>& batch) const;
+    // skip_bf16: the query already failed a bf16 filter's certification (an MFMA batch straggler): straight to k_scan
     int search_locked(Workspace* ws, const double* query, uint64_t k_eff, int metric, uint64_t* out_pos,
-                      uint64_t* out_ids, double* out_scores, uint64_t* out_n, bool skip_fast) const;
+                      uint64_t* out_ids, double* out_scores, uint64_t* out_n, bool skip_fast, bool skip_bf16 = false) const;
+    bool bf16_first(uint64_t n) const;        // does this single search try the bf16 filter first
+    void bf16_outcome(bool certified) const;  // records one try of the bf16 filter
     int run_exact(Workspace* ws, int metric, uint64_t n, uint64_t k_eff, std::vector<uint32_t>* pos,
                   std::vector<double>* scores) const;
     int wait_result(Workspace* ws, uint32_t seq) const;
@@ -293,8 +304,14 @@ private:
     mutable Coalescer<CoalesceReq> co_;
 
     std::atomic<int> force_path_{0};
-    std::atomic<int> single_filter_{0};
-    mutable std::atomic<uint64_t> bf16_tries_{0}, bf16_fails_{0};
+    std::atomic<int> single_filter_{FILTER_AUTO};
+    mutable std::atomic<uint64_t> bf16_tries_{0}, bf16_fails_{0};  // mode 1
+    // auto: below this f32 slab size back-to-back searches find the slab in the 256 MiB Infinity Cache and the f32 scan
+    // is as fast as the bf16 one (profiles/single_filter_crossover.jsonl)
+    static constexpr uint64_t SINGLE_FILTER_MIN_BYTES = 512ull << 20;
+    uint64_t auto_min_bytes_ = SINGLE_FILTER_MIN_BYTES;
+    mutable AutoFilterWindow auto_window_;
+    mutable std::atomic<bool> auto_unavailable_{false};  // the bf16 copy could not be allocated: auto stays on f32
     std::atomic<bool> profile_{false};
     // single searches in flight on this handle: up to SPIN_MAX_SEARCHERS of them poll their result stamp,
     // more than that sleep in hipStreamSynchronize (wait_result)

@@ -124,6 +124,16 @@ hipError_t launch_merge_finalize(hipStream_t s, int metric, Cand32* partials, in
                                  const double* master, const double* q64, const double* q_norms, uint32_t dim,
                                  uint64_t n_rows, uint32_t k, double max_row_norm, SearchResultBlock* out,
                                  double in_extra = 0.0, uint32_t seq = 0, const ShardRecordSink* sink = nullptr);
+// The stamped single search (nq = 1, out->seq = seq stored last) of a candidate filter whose rows carry extra input
+// rounding: the filter's `in_extra` term of the bound comes last.
+inline hipError_t launch_merge_finalize(hipStream_t s, uint32_t seq, int metric, Cand32* partials, int n_lists,
+                                        const double* master, const double* q64, const double* q_norm, uint32_t dim,
+                                        uint64_t n_rows, uint32_t k, double max_row_norm, SearchResultBlock* out,
+                                        double in_extra)
+{
+    return launch_merge_finalize(s, metric, partials, n_lists, 1, master, q64, q_norm, dim, n_rows, k, max_row_norm, out,
+                                 in_extra, seq);
+}
 
 // K2 for a batch whose candidates already are ONE sorted top-64 list per query (lists[nq][KP], the MFMA filter's output):
 // the rescoring of each query's 64 rows split over four 256-thread workgroups + one wave per query that ranks, checks the

@@ -23,7 +23,9 @@
 #include "filter_plan.hpp"
 #include "xcd_map.hpp"
 
+#include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <type_traits>
 
@@ -984,11 +986,12 @@ __device__ __forceinline__ float dot8_bf16(float a, const u32x4 x, const f32x4 q
     return a;
 }
 
-template <int METRIC, int G, int VPL>
-__global__ __launch_bounds__(256) void k_scan_bf16(const u32x4* __restrict__ slab16, const float* __restrict__ row_nrm,
-                                                   const float* __restrict__ row_sqn,
-                                                   const double* __restrict__ q64, uint32_t dim, uint32_t n,
-                                                   Cand32* __restrict__ out)
+// Specialised: LD8 == G * VPL 16-byte chunks per row, U row steps in flight per wave (like k_scan's U).  `qv` is the lane's
+// slice of the f32 query (columns 8 (c + G j) .. + 7), loaded by the kernel entry that wraps this body.
+template <int METRIC, int G, int VPL, int U>
+__device__ __forceinline__ void scan_bf16_body(const u32x4* __restrict__ slab16, const float* __restrict__ row_nrm,
+                                               const float* __restrict__ row_sqn, const f32x4 (&qv)[VPL][2], uint32_t n,
+                                               Cand32* __restrict__ out)
 {
     constexpr int RPS = WAVE / G;
     constexpr uint32_t LD8 = G * VPL;  // 16-byte chunks (8 bf16) per row
@@ -997,6 +1000,58 @@ __global__ __launch_bounds__(256) void k_scan_bf16(const u32x4* __restrict__ sla
     const int wave = threadIdx.x >> 6;
     const int g = lane / G, c = lane % G;
 
+    const uint32_t n_steps = (n + RPS - 1) / RPS;
+    const uint32_t n_waves = gridDim.x * 4;
+    TopList<float> L;
+    L.init();
+    for (uint32_t s0 = blockIdx.x * 4 + wave; s0 < n_steps; s0 += n_waves * U) {
+        u32x4 x[U][VPL];
+        uint32_t row[U];
+        float nr[U], sq[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t s = s0 + (uint32_t)u * n_waves;
+            row[u] = s < n_steps ? s * RPS + g : n;  // n marks "no row"
+            const uint32_t r = row[u] < n ? row[u] : n - 1;  // clamp: loads stay in bounds
+            const u32x4* p = slab16 + (size_t)r * LD8 + c;
+#pragma unroll
+            for (int j = 0; j < VPL; ++j) x[u][j] = __builtin_nontemporal_load(p + G * j);
+            nr[u] = 1.0f;
+            sq[u] = 0.0f;
+            if (METRIC != COSINE) nr[u] = row_nrm[r];
+            if (METRIC == EUCLIDEAN) sq[u] = row_sqn[r];
+        }
+        __builtin_amdgcn_sched_barrier(0);  // every load of the iteration issued before the first FMA (see k_scan)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float a = 0.0f;
+#pragma unroll
+            for (int j = 0; j < VPL; ++j) a = dot8_bf16(a, x[u][j], qv[j][0], qv[j][1]);
+#pragma unroll
+            for (int o = G / 2; o >= 1; o >>= 1) a += __shfl_xor(a, o);
+            float key = a;                                              // cosine: x^.q
+            if (METRIC == DOT) key = a * nr[u];                         // x.q
+            if (METRIC == EUCLIDEAN) key = 2.0f * a * nr[u] - sq[u];    // |q|^2 - |x - q|^2
+            L.offer(key, row[u], row[u] < n && c == 0);
+        }
+    }
+    block_merge<float, Cand32, 4>(L, sh);
+    if (wave == 0) {
+        Cand32 e;
+        e.key = L.key;
+        e.pos = L.pos;
+        out[(size_t)blockIdx.x * KP + lane] = e;
+    }
+}
+
+// The f64 query in device memory: each lane rounds its slice itself.
+template <int METRIC, int G, int VPL, int U>
+__global__ __launch_bounds__(256) void k_scan_bf16(const u32x4* __restrict__ slab16, const float* __restrict__ row_nrm,
+                                                   const float* __restrict__ row_sqn,
+                                                   const double* __restrict__ q64, uint32_t dim, uint32_t n,
+                                                   Cand32* __restrict__ out)
+{
+    const int c = lane_id() % G;
     f32x4 qv[VPL][2];
 #pragma unroll
     for (int j = 0; j < VPL; ++j) {
@@ -1015,39 +1070,29 @@ __global__ __launch_bounds__(256) void k_scan_bf16(const u32x4* __restrict__ sla
             qv[j][h] = v;
         }
     }
-    const uint32_t n_steps = (n + RPS - 1) / RPS;
-    const uint32_t n_waves = gridDim.x * 4;
-    TopList<float> L;
-    L.init();
-    for (uint32_t s = blockIdx.x * 4 + wave; s < n_steps; s += n_waves) {
-        const uint32_t row = s * RPS + g;
-        const bool valid = row < n;
-        const uint32_t r = valid ? row : n - 1;
-        const u32x4* p = slab16 + (size_t)r * LD8 + c;
-        u32x4 x[VPL];
+    scan_bf16_body<METRIC, G, VPL, U>(slab16, row_nrm, row_sqn, qv, n, out);
+}
+
+// The single search's form: the f32 query, zero padded to ldb columns, in the KERNEL ARGUMENTS (rounded on the host
+// exactly as the entry above rounds it, f64 -> f32 nearest even), so nothing is copied to the device before the launch.
+struct alignas(16) Scan16QArg {
+    float v[SCAN16_QARG_FLOATS];
+};
+
+template <int METRIC, int G, int VPL, int U>
+__global__ __launch_bounds__(256) void k_scan_bf16_qarg(const u32x4* __restrict__ slab16, const float* __restrict__ row_nrm,
+                                                        const float* __restrict__ row_sqn, uint32_t n,
+                                                        Cand32* __restrict__ out, const Scan16QArg qa)
+{
+    static_assert(G * VPL * 8 <= SCAN16_QARG_FLOATS, "row too long for the kernarg query");
+    const int c = lane_id() % G;
+    f32x4 qv[VPL][2];
 #pragma unroll
-        for (int j = 0; j < VPL; ++j) x[j] = __builtin_nontemporal_load(p + G * j);
-        float nr = 1.0f, sq = 0.0f;
-        if (METRIC != COSINE) nr = row_nrm[r];
-        if (METRIC == EUCLIDEAN) sq = row_sqn[r];
-        __builtin_amdgcn_sched_barrier(0);
-        float a = 0.0f;
-#pragma unroll
-        for (int j = 0; j < VPL; ++j) a = dot8_bf16(a, x[j], qv[j][0], qv[j][1]);
-#pragma unroll
-        for (int o = G / 2; o >= 1; o >>= 1) a += __shfl_xor(a, o);
-        float key = a;                                            // cosine: x^.q
-        if (METRIC == DOT) key = a * nr;                          // x.q
-        if (METRIC == EUCLIDEAN) key = 2.0f * a * nr - sq;        // |q|^2 - |x - q|^2
-        L.offer(key, row, valid && c == 0);
+    for (int j = 0; j < VPL; ++j) {
+        qv[j][0] = *reinterpret_cast<const f32x4*>(&qa.v[8 * (c + G * j)]);
+        qv[j][1] = *reinterpret_cast<const f32x4*>(&qa.v[8 * (c + G * j) + 4]);
     }
-    block_merge<float, Cand32, 4>(L, sh);
-    if (wave == 0) {
-        Cand32 e;
-        e.key = L.key;
-        e.pos = L.pos;
-        out[(size_t)blockIdx.x * KP + lane] = e;
-    }
+    scan_bf16_body<METRIC, G, VPL, U>(slab16, row_nrm, row_sqn, qv, n, out);
 }
 
 // T_q = the 64th largest group maximum (a lower bound of the query's 64th best key); -inf when fewer
@@ -1856,14 +1901,19 @@ hipError_t launch_mfma_candidates(hipStream_t s, int metric, const void* slab_bf
     return hipGetLastError();
 }
 
-#define VL_BF16_SCAN_SHAPES(X) X(8, 2) X(8, 4) X(8, 6) X(8, 8) X(16, 6)
+// (lanes per row G, 16-byte chunks per lane VPL, row steps in flight U) per bf16 row stride (ldb / 8 = G * VPL chunks).
+// The first shape whose G * VPL matches the stride runs; VL_SCAN16_SHAPE="G,VPL,U" picks another listed one (tuning).
+// Measured (profiles/single_filter_shape_sweep.jsonl): a second row step in flight (U = 2) does not stream faster at
+// 10 M x 384 or 1.25 M x 768; G = 4 / VPL = 12 at stride 384 and G = 8 / VPL = 12 at stride 768 were 16 % / 1-2 % slower.
+#define VL_BF16_SCAN_SHAPES(X) \
+    X(8, 2, 1) X(8, 2, 2) X(8, 4, 1) X(8, 4, 2) X(8, 6, 1) X(8, 6, 2) X(8, 8, 1) X(8, 8, 2) X(16, 6, 1) X(16, 6, 2)
 
 bool scan_bf16_supported(uint32_t dim, int metric)
 {
     if (metric != COSINE && metric != DOT && metric != EUCLIDEAN) return false;
     const uint32_t ld8 = mfma_ldb(dim) / 8;
     bool ok = false;
-#define VL_CHK(G, VPL) ok = ok || (ld8 == (uint32_t)(G * VPL));
+#define VL_CHK(G, VPL, U) ok = ok || (ld8 == (uint32_t)(G * VPL));
     VL_BF16_SCAN_SHAPES(VL_CHK)
 #undef VL_CHK
     return ok;
@@ -1871,40 +1921,60 @@ bool scan_bf16_supported(uint32_t dim, int metric)
 
 hipError_t launch_scan_bf16(hipStream_t s, int metric, const void* slab_bf16, const float* row_norm,
                             const float* row_sqnorm, const double* q64, uint64_t n, uint32_t dim, Cand32* partials,
-                            int* grid_out)
+                            int* grid_out, const float* q32_host, int* variant_out)
 {
     if (n == 0 || n >= 0xFFFFFFFFull || !scan_bf16_supported(dim, metric)) return hipErrorInvalidValue;
-    const uint32_t ld8 = mfma_ldb(dim) / 8;
+    const uint32_t ldb = mfma_ldb(dim), ld8 = ldb / 8;
+    if (!q32_host && !q64) return hipErrorInvalidValue;
+    if (q32_host && ldb > (uint32_t)SCAN16_QARG_FLOATS) return hipErrorInvalidValue;
     const u32x4* slab = reinterpret_cast<const u32x4*>(slab_bf16);
     int dev = 0, cus = 256;
     (void)hipGetDevice(&dev);
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     const char* ge = getenv("VL_SCAN16_BPC");
-    const int bpc = ge && *ge ? atoi(ge) : 3;  // measured: 2-3 workgroups per CU stream fastest (like k_scan)
-    bool launched = false;
-    int grid = 1;
-#define VL_L3(MET, G, VPL)                                                                                     \
-    {                                                                                                          \
-        const uint64_t steps = (n + (64 / G) - 1) / (64 / G);                                                  \
-        uint64_t blocks = (steps + 3) / 4;                                                                     \
-        if (blocks > (uint64_t)(cus * bpc)) blocks = (uint64_t)(cus * bpc);                                    \
-        if (blocks > (uint64_t)SCAN_MAX_GRID) blocks = SCAN_MAX_GRID;                                          \
-        grid = (int)(blocks < 1 ? 1 : blocks);                                                                 \
-        hipLaunchKernelGGL((k_scan_bf16<MET, G, VPL>), dim3(grid), dim3(256), 0, s, slab, row_norm, row_sqnorm, \
-                           q64, dim, (uint32_t)n, partials);                                                   \
-        launched = true;                                                                                       \
+    // workgroups per CU: 3 (12 waves) streams fastest at stride 384 and below, 2 at stride 768 (0.279 vs 0.285 ms at 1.25 M)
+    const int bpc = ge && *ge ? atoi(ge) : (ld8 >= 96 ? SCAN16_BPC_LONG : SCAN16_BPC);
+    int want_g = 0, want_vpl = 0, want_u = 0;
+    if (const char* se = getenv("VL_SCAN16_SHAPE")) {
+        if (sscanf(se, "%d,%d,%d", &want_g, &want_vpl, &want_u) != 3) want_g = 0;
     }
-#define VL_L(G, VPL)                                               \
-    if (!launched && ld8 == (uint32_t)(G * VPL)) {                 \
-        if (metric == COSINE) VL_L3(COSINE, G, VPL)                \
-        else if (metric == EUCLIDEAN) VL_L3(EUCLIDEAN, G, VPL)     \
-        else VL_L3(DOT, G, VPL)                                    \
+    bool want_listed = false;
+#define VL_CHK(G, VPL, U) want_listed = want_listed || (want_g == G && want_vpl == VPL && want_u == U && ld8 == (uint32_t)(G * VPL));
+    VL_BF16_SCAN_SHAPES(VL_CHK)
+#undef VL_CHK
+    bool launched = false;
+    int grid = 1, variant = 0;
+    Scan16QArg qa;
+    if (q32_host) memcpy(qa.v, q32_host, (size_t)ldb * sizeof(float));
+#define VL_L3(MET, G, VPL, U)                                                                                       \
+    {                                                                                                               \
+        const uint64_t steps = (n + (64 / G) - 1) / (64 / G);                                                       \
+        uint64_t blocks = (steps + 3) / 4;                                                                          \
+        if (blocks > (uint64_t)(cus * bpc)) blocks = (uint64_t)(cus * bpc);                                         \
+        if (blocks > (uint64_t)SCAN_MAX_GRID) blocks = SCAN_MAX_GRID;                                               \
+        grid = (int)(blocks < 1 ? 1 : blocks);                                                                      \
+        if (q32_host)                                                                                               \
+            hipLaunchKernelGGL((k_scan_bf16_qarg<MET, G, VPL, U>), dim3(grid), dim3(256), 0, s, slab, row_norm,     \
+                               row_sqnorm, (uint32_t)n, partials, qa);                                              \
+        else                                                                                                        \
+            hipLaunchKernelGGL((k_scan_bf16<MET, G, VPL, U>), dim3(grid), dim3(256), 0, s, slab, row_norm,          \
+                               row_sqnorm, q64, dim, (uint32_t)n, partials);                                        \
+        launched = true;                                                                                            \
+    }
+#define VL_L(G, VPL, U)                                                                             \
+    if (!launched && ld8 == (uint32_t)(G * VPL) &&                                                  \
+        (!want_listed || (want_g == G && want_vpl == VPL && want_u == U))) {                        \
+        variant = SCAN16_VARIANT_BASE + G * 10000 + VPL * 100 + U;                                  \
+        if (metric == COSINE) VL_L3(COSINE, G, VPL, U)                                              \
+        else if (metric == EUCLIDEAN) VL_L3(EUCLIDEAN, G, VPL, U)                                   \
+        else VL_L3(DOT, G, VPL, U)                                                                  \
     }
     VL_BF16_SCAN_SHAPES(VL_L)
 #undef VL_L
 #undef VL_L3
     if (!launched) return hipErrorInvalidValue;
     if (grid_out) *grid_out = grid;
+    if (variant_out) *variant_out = variant;
     return hipGetLastError();
 }
 

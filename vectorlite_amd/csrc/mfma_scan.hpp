@@ -109,10 +109,18 @@ hipError_t launch_mfma_candidates(hipStream_t s, int metric, const void* slab_bf
                                   const MfmaScratch& w, Cand32* out_lists, MfmaLaunchInfo* info = nullptr,
                                   bool queries_prepared = false);
 
-// Single-query scan of the bf16 slab (opt-in filter): per-workgroup top-64 lists like launch_scan.
+// Single-query scan of the bf16 slab (the single-query candidate filter): per-workgroup top-64 lists like launch_scan.
+// Two ways to hand over the query, as launch_scan: q32_host != nullptr is the f32 query rounded from the f64 one to
+// nearest even and zero padded to mfma_ldb(dim) floats, copied into the kernel arguments (q64 may then be null);
+// otherwise q64 is the f64 query in device memory and each lane rounds its slice itself.  Both forms produce the same
+// keys.  variant_out: SCAN16_VARIANT_BASE + G * 10000 + VPL * 100 + U of the shape that ran (above every k_scan variant).
+constexpr int SCAN16_QARG_FLOATS = 768;
+constexpr int SCAN16_VARIANT_BASE = 1000000;
+constexpr int SCAN16_BPC = 3;       // workgroups per CU, row strides up to 512 (VL_SCAN16_BPC overrides)
+constexpr int SCAN16_BPC_LONG = 2;  // ... stride 768
 bool scan_bf16_supported(uint32_t dim, int metric);
 hipError_t launch_scan_bf16(hipStream_t s, int metric, const void* slab_bf16, const float* row_norm,
                             const float* row_sqnorm, const double* q64, uint64_t n, uint32_t dim, Cand32* partials,
-                            int* grid_out);
+                            int* grid_out, const float* q32_host = nullptr, int* variant_out = nullptr);
 
 }  // namespace vl
