@@ -31,8 +31,13 @@ Multi-GPU (`--gpus N`): the flat index is REPLICATED (each rank holds the full c
 answer disjoint query streams -- no data-path collective; value = all ranks' queries / max time
 (weak scaling).
 
-After the published timed region (never inside `value`) the same run measures the other BASELINE.json
-configurations, each with its own `roofline` object under `config.other_configs`:
+A plain run does only what the headline needs: build the index, pre-warm, warm up, time the K steps,
+write --dump-outputs, print the line (`roofline` comes from HIP events inside the timed region).
+Everything else runs only with `--full`, after the published timed region (never inside `value`):
+the CPU baselines and parity against the oracle (N = 1, `--no-cpu-baseline` drops them), the
+fast-vs-exact check at full size, `concurrent_16_threads`, the copy ceiling, the opt-in bf16 filter
+(`--no-checks` drops all of these) and the other BASELINE.json configurations, each with its own
+`roofline` object under `config.other_configs` (`--no-other-configs` drops them):
   N = 1   c2 (1 M x 384 single query, HBM), c5 (4096-query batch on the resident corpus, MFMA), c3_shard (one
           rank's 1.25 M x 768 shard of config 3 through vl_shard_search_batch over a world-1 RCCL communicator,
           HIP events around the all-gather and the merge), c4_hnsw (build, recall@10, QPS at ef 10 / 32 / 128
@@ -80,6 +85,8 @@ def parse_args(argv=None):
     p.add_argument("--k", type=int, default=10)
     p.add_argument("--metric", default="cosine", choices=["cosine", "euclidean", "manhattan", "dotproduct"])
     p.add_argument("--chunk", type=int, default=500_000, help="rows generated per device chunk")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run the CPU baselines, the checks and the other configurations (the --no-* options below trim them)")
     p.add_argument("--cpu-sample-rows", type=int, default=1_000_000)
     p.add_argument("--cpu-queries", type=int, default=32)
     p.add_argument("--cpu-budget-s", type=float, default=30.0, help="stop the CPU baseline after this much CPU time")
@@ -846,7 +853,7 @@ def run_rank(args) -> int:
     idx = V.FlatIndex(dim, device=dev_index)
     idx.reserve(n)
     sample_rows = None
-    want_cpu = (rank == 0 and world == 1 and not args.no_cpu_baseline)
+    want_cpu = (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline)
     n_sample = min(args.cpu_sample_rows, n)
     sample_parts = []
     done = 0
@@ -908,7 +915,7 @@ def run_rank(args) -> int:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed_max = float(t.item())
 
-    run_sharded = use_dist and world > 1 and not args.no_checks and not args.no_other_configs
+    run_sharded = args.full and use_dist and world > 1 and not args.no_checks and not args.no_other_configs
     STUCK_S = 420.0  # a collective that never returns: give up, non-zero (a rank that touched the GPU never exits 0 on a hang)
 
     def c3_all_ranks():
@@ -1016,9 +1023,11 @@ def run_rank(args) -> int:
     if use_dist:
         dist.barrier()
 
-    extras = world == 1 and not args.no_checks  # N>1: every rank leaves together, nothing runs on rank 0 alone
+    extras = args.full and world == 1 and not args.no_checks  # N>1: every rank leaves together, nothing runs on rank 0 alone
+    if not args.full:
+        log("[bench] headline only: --full adds the CPU baselines, the checks and the other configurations")
 
-    other = out["config"].setdefault("other_configs", {})
+    other = out["config"].setdefault("other_configs", {}) if args.full else {}
 
     if run_sharded:
         def on_stuck():  # a collective that never returns must not take the measured line with it

@@ -152,3 +152,16 @@ def test_dump_outputs_is_a_bench_argument():
     argv = ["--steps", "3", "--dump-outputs", "/tmp/x"]
     cmd = bench.launch_command(bench.parse_args(argv), argv, "/tmp/r.json", 1)
     assert cmd[cmd.index("--dump-outputs") + 1] == "/tmp/x"
+
+
+def test_full_is_off_by_default_and_reaches_the_ranks():
+    """A plain run is the headline alone; --full (the baselines, checks and other configurations) is the worker's to read,
+    so the supervisor hands it on in both launch forms."""
+    assert bench.parse_args([]).full is False
+    argv = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"]
+    assert bench.parse_args(argv).full is True
+    for gpus in ("1", "2"):
+        argv[1] = gpus
+        cmd = bench.launch_command(bench.parse_args(argv), argv, "/tmp/r.json", 1)
+        tail = cmd[cmd.index(os.path.join(ROOT, "bench.py")) + 1:]
+        assert "--full" in tail and bench.parse_args(tail).full is True

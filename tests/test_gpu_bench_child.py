@@ -1,6 +1,7 @@
 """bench.py as the driver runs it: a fresh child process, the supervisor form, small sizes.
 Every field the measurement contract names must be on the ONE stdout line, for argument pairs that
-used to break the post-processing (few steps, no warmup)."""
+used to break the post-processing (few steps, no warmup): the headline fields on a plain run, and the
+baselines, checks and other configurations as well with --full."""
 import json
 import os
 import subprocess
@@ -31,7 +32,7 @@ def _run(extra, timeout=600):
 
 @pytest.mark.parametrize("steps,warmup", [(3, 1), (1, 0)])
 def test_bench_child_process_prints_the_whole_contract_line(steps, warmup):
-    out, err = _run(["--gpus", "1", "--rows", "200000", "--steps", str(steps), "--warmup", str(warmup),
+    out, err = _run(["--gpus", "1", "--rows", "200000", "--steps", str(steps), "--warmup", str(warmup), "--full",
                      "--cpu-sample-rows", "20000", "--cpu-queries", "4"] + SMALL_OTHER)
     assert "errors" not in out, out["errors"]
     assert out["metric"].startswith("flat-cosine QPS") and out["unit"] == "queries/s"
@@ -106,12 +107,30 @@ def test_bench_child_process_prints_the_whole_contract_line(steps, warmup):
     assert rf["kernel_variant"]["query_in_kernarg"] == 1
 
 
+def test_plain_bench_run_prints_the_headline_alone():
+    """Without --full the line carries the headline and its roofline, and nothing that needs a run of its own."""
+    steps, warmup = 3, 1
+    out, err = _run(["--gpus", "1", "--rows", "200000", "--steps", str(steps), "--warmup", str(warmup)])
+    assert "errors" not in out, out["errors"]
+    assert out["metric"].startswith("flat-cosine QPS") and out["unit"] == "queries/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and out["steps"] == steps and out["warmup"] == warmup
+    assert out["value"] > 0 and out["ms_per_step"] > 0
+    rf = out["roofline"]
+    assert rf["launches_timed"] == steps and rf["achieved"] > 0 and "measured_d2d_copy_GBps" not in rf
+    assert out["config"]["search_paths_seen"] == [1] and out["config"]["prewarm_queries_untimed"] >= 10
+    assert "value_first_5_steps" in out
+    for key in ("cpu_baseline", "cpu_baseline_fair", "parity", "value_sustained", "concurrent_16_threads", "nccl_ranks_seen"):
+        assert key not in out, key
+    for key in ("other_configs", "fast_vs_exact_full_size", "bf16_first_filter_optin"):
+        assert key not in out["config"], key
+
+
 def test_bench_two_ranks_without_an_external_launcher():
     """`--gpus 2` alone starts two ranks (rehearsal: both on this card, gloo rendezvous)."""
     env_before = os.environ.get("VL_BENCH_REHEARSE")
     os.environ["VL_BENCH_REHEARSE"] = "1"
     try:
-        out, err = _run(["--gpus", "2", "--rows", "100000", "--steps", "4", "--warmup", "1", "--c3-rows", "60000", "--c3-batch", "128"])
+        out, err = _run(["--gpus", "2", "--rows", "100000", "--steps", "4", "--warmup", "1", "--full", "--c3-rows", "60000", "--c3-batch", "128"])
     finally:
         if env_before is None:
             os.environ.pop("VL_BENCH_REHEARSE", None)
