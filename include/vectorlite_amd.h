@@ -399,10 +399,14 @@ int vl_index_force_path(vl_index *h, int path);
  * 1 = stream a bf16 copy of the slab first (half the HBM bytes) and fall back to the f32 scan when
  * the exactness bound cannot certify the answer (switches itself off for good once more than a third of
  * 64+ tries failed);
- * 2 = auto (new handles; VL_SINGLE_FILTER=f32|bf16|auto sets the start mode): the bf16 copy first when the
- * f32 slab is at least 512 MiB (VL_SINGLE_FILTER_MIN_MB), off while more than a third of the last 64 tries
- * failed to certify, re-tried every 16th search while off.  The bf16 copy (+0.5 x the f32 slab) is built on the
- * first search that uses it.  Results are identical in every mode. */
+ * 2 = auto (new handles; VL_SINGLE_FILTER=f32|bf16|auto|i8 sets the start mode): the ladder int8 -> bf16 -> f32.
+ * The int8 copy first when the metric is cosine or dot and the f32 slab is at least 1 GiB
+ * (VL_SINGLE_FILTER_I8_MIN_MB; VL_SINGLE_FILTER_MIN_MB does not lower it); a query it cannot certify goes on to the
+ * bf16 copy when the f32 slab is at least 512 MiB (VL_SINGLE_FILTER_MIN_MB), else to the f32 slab.  Each stage is off
+ * while more than a third of its last 64 tries failed to certify, re-tried every 16th search while off;
+ * 3 = the int8 copy first, always (cosine and dot; mode 1's one-way switch-off), then the f32 slab.
+ * The int8 copy (+0.25 x the f32 slab) and the bf16 copy (+0.5 x) are built on the first search that uses them.
+ * Results are identical in every mode. */
 int vl_index_set_single_filter(vl_index *h, int mode);
 
 /* Coalescing of concurrent vl_index_search calls, flat or HNSW handle (the reference serves searches

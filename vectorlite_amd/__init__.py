@@ -36,6 +36,8 @@ VL_ERR_NAN_SCORE, VL_ERR_DEVICE, VL_ERR_OOM, VL_ERR_INVALID_ARG = 5, 6, 7, 8
 PATH_NONE, PATH_FAST, PATH_EXACT_SELECT, PATH_EXACT_SORT = 0, 1, 2, 3
 # set_single_filter: the modes of vl_index_set_single_filter (2 = auto, what new handles start in)
 SINGLE_FILTER_MODES = {"f32": 0, "bf16": 1, "auto": 2}
+# ... and mode 3, the int8 copy first always (kept out of SINGLE_FILTER_MODES, whose three entries callers enumerate)
+SINGLE_FILTER_I8 = 3
 
 
 class SimilarityMetric(enum.IntEnum):
@@ -463,9 +465,10 @@ class FlatIndex:
 
     def set_single_filter(self, mode: str) -> None:
         """Which copy of the slab single queries scan first: "f32" (the f32 slab only), "bf16" (the bf16 copy first,
-        always) or "auto" (new handles: the bf16 copy first on indexes whose f32 slab is at least 512 MiB, paused
-        while it fails to certify).  Answers are identical in every mode."""
-        _raise(self._L.vl_index_set_single_filter(self._h, SINGLE_FILTER_MODES[mode]))
+        always), "i8" (the int8 copy first, always; cosine and dot) or "auto" (new handles: the int8 copy first on
+        indexes whose f32 slab is at least 1 GiB, then the bf16 copy on those of at least 512 MiB, each paused while it
+        fails to certify).  Answers are identical in every mode."""
+        _raise(self._L.vl_index_set_single_filter(self._h, SINGLE_FILTER_I8 if mode == "i8" else SINGLE_FILTER_MODES[mode]))
 
     def set_coalescing(self, max_batch: int, window_us: int = 0) -> None:
         """Answer concurrent search() calls (other threads) with shared slab passes; 0 turns it off."""

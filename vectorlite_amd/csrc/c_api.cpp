@@ -772,7 +772,7 @@ int vl_index_force_path(vl_index* h, int path)
 
 int vl_index_set_single_filter(vl_index* h, int mode)
 {
-    if (!h || h->hnsw || mode < 0 || mode > 2) return VL_ERR_INVALID_ARG;
+    if (!h || h->hnsw || mode < 0 || mode > 3) return VL_ERR_INVALID_ARG;
     return on_flat(h, [&](auto* f) { f->set_single_filter(mode); return (int)VL_OK; });
 }
 

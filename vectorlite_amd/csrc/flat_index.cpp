@@ -184,10 +184,13 @@ int GpuFlatIndex::create(uint64_t dim, int device, GpuFlatIndex** out)
     VL_TRY(dev_alloc(&idx->d_stats_, 1));
     VL_HIP(hipMemsetAsync(idx->d_stats_, 0, sizeof(IngestStats), idx->mut_stream_));
     VL_HIP(hipStreamSynchronize(idx->mut_stream_));
-    // VL_SINGLE_FILTER=f32|bf16|auto: the single-query filter a handle starts with (auto when unset or unrecognised)
+    // VL_SINGLE_FILTER=f32|bf16|auto|i8: the single-query filter a handle starts with (auto when unset or unrecognised)
     idx->set_single_filter(parse_single_filter(getenv("VL_SINGLE_FILTER"), FILTER_AUTO));
     if (const char* mb = getenv("VL_SINGLE_FILTER_MIN_MB")) {
         if (*mb) idx->set_single_filter_min_bytes(std::strtoull(mb, nullptr, 10) << 20);
+    }
+    if (const char* mb = getenv("VL_SINGLE_FILTER_I8_MIN_MB")) {
+        if (*mb) idx->set_single_filter_i8_min_bytes(std::strtoull(mb, nullptr, 10) << 20);
     }
     // Concurrent single searches share slab passes by default (the reference's many-readers model, src/client.rs:398):
     // window 0, so a lone caller leads a pass of one = the plain single-search path.  VL_COALESCE=0 starts handles with it off.
@@ -246,7 +249,8 @@ GpuFlatIndex::~GpuFlatIndex()
     (void)hipSetDevice(device_);
     if (ws_pool_) detach_pool(device_, dim_);
     if (mut_stream_) (void)hipStreamSynchronize(mut_stream_);
-    void* dev[] = {d_master_, d_slab_, d_inv_norm_, d_flags_, d_stats_, d_bounce_, d_slab16_, d_sqnorm_, d_norm16_, d_slab16f_, d_ids_};
+    void* dev[] = {d_master_, d_slab_, d_inv_norm_, d_flags_, d_stats_, d_bounce_, d_slab16_, d_sqnorm_, d_norm16_, d_slab16f_, d_ids_,
+                   d_slab8_, d_sr8_, d_norm8_};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     if (mut_stream_) (void)hipStreamDestroy(mut_stream_);
@@ -276,6 +280,7 @@ void GpuFlatIndex::truncate(uint64_t n_rows)
     id_counts_valid_ = false;  // rebuilt on demand from ids_
     if (slab16_rows_ > n_rows) slab16_rows_ = n_rows;
     if (slab16f_rows_ > n_rows) slab16f_rows_ = n_rows;
+    if (slab8_rows_ > n_rows) slab8_rows_ = n_rows;
     if (d_ids_rows_ > n_rows) d_ids_rows_ = n_rows;
 }
 
@@ -299,6 +304,15 @@ int GpuFlatIndex::ensure_capacity(uint64_t rows)
         d_norm16_ = nullptr;
         slab16_rows_ = 0;
         slab16f_rows_ = 0;
+    }
+    if (d_slab8_) {  // ... and so does the int8 copy of the single-query filter
+        (void)hipFree(d_slab8_);
+        (void)hipFree(d_sr8_);
+        (void)hipFree(d_norm8_);
+        d_slab8_ = nullptr;
+        d_sr8_ = nullptr;
+        d_norm8_ = nullptr;
+        slab8_rows_ = 0;
     }
     const uint64_t n = ids_.size();
     // One array at a time: allocate the larger one, copy, free the old one.  The transient need is the index as it stands
@@ -471,6 +485,7 @@ int GpuFlatIndex::remove_position(uint64_t pos)
     if (row_flags_[pos] & ROW_OUT_OF_DOMAIN) --n_out_of_domain_;
     if (slab16_rows_ > pos) slab16_rows_ = pos;  // rows behind the hole are re-converted on demand
     if (slab16f_rows_ > pos) slab16f_rows_ = pos;
+    if (slab8_rows_ > pos) slab8_rows_ = pos;
     if (d_ids_rows_ > pos) d_ids_rows_ = pos;    // ... and the device id table re-uploaded from there
     ids_.erase(ids_.begin() + pos);
     row_flags_.erase(row_flags_.begin() + pos);
@@ -865,18 +880,34 @@ int GpuFlatIndex::search_batch_locked(const double* queries, uint64_t nq, uint64
     return OK;
 }
 
-// Single-query filter choice (set_single_filter).  Mode 1 keeps its one-way switch-off; auto applies the recent-outcome
-// window of single_filter.hpp, so a bad streak pauses it and the periodic probes bring it back.
+// Single-query filter choice (set_single_filter, single_filter.hpp's ladder_stage).  Modes 1 and 3 keep their one-way
+// switch-off; auto applies each stage's recent-outcome window, so a bad streak pauses it and the periodic probes bring
+// it back.
 bool GpuFlatIndex::bf16_first(uint64_t n) const
 {
     const int mode = single_filter_.load(std::memory_order_relaxed);
-    if (mode == FILTER_BF16) {
-        const uint64_t tries = bf16_tries_.load(std::memory_order_relaxed);
-        return !(tries >= 64 && bf16_fails_.load(std::memory_order_relaxed) * 3 > tries);
-    }
-    if (mode != FILTER_AUTO || auto_unavailable_.load(std::memory_order_relaxed)) return false;
-    if (n * (uint64_t)ld_ * sizeof(float) < auto_min_bytes_) return false;
-    return auto_window_.want();
+    const bool ok = !(mode == FILTER_AUTO && auto_unavailable_.load(std::memory_order_relaxed));
+    return ladder_stage(
+        FILTER_BF16, mode, ok, n * (uint64_t)ld_ * sizeof(float), auto_min_bytes_,
+        [&] { return forced_stage_on(bf16_tries_.load(std::memory_order_relaxed), bf16_fails_.load(std::memory_order_relaxed)); },
+        [&] { return auto_window_.want(); });
+}
+
+bool GpuFlatIndex::i8_first(uint64_t n) const
+{
+    const int mode = single_filter_.load(std::memory_order_relaxed);
+    const bool ok = !(mode == FILTER_AUTO && i8_unavailable_.load(std::memory_order_relaxed));
+    return ladder_stage(
+        FILTER_I8, mode, ok, n * (uint64_t)ld_ * sizeof(float), i8_min_bytes_,
+        [&] { return forced_stage_on(i8_tries_.load(std::memory_order_relaxed), i8_fails_.load(std::memory_order_relaxed)); },
+        [&] { return i8_window_.want(); });
+}
+
+void GpuFlatIndex::i8_outcome(bool certified) const
+{
+    i8_tries_.fetch_add(1, std::memory_order_relaxed);
+    if (!certified) i8_fails_.fetch_add(1, std::memory_order_relaxed);
+    i8_window_.record(certified);
 }
 
 void GpuFlatIndex::bf16_outcome(bool certified) const
@@ -923,7 +954,77 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
     const bool fast_ok = !skip_fast && forced == 0 && k_eff <= (uint64_t)KFAST_MAX && n_out_of_domain_ == 0 &&
                          q_in_domain;
 
-    // First stage on large indexes (auto) or on request (mode 1): scan the bf16 copy of the slab (half the HBM bytes).
+    // A certified answer of a filter stage: the result block's positions -> the caller's arrays.
+    auto take_result = [&](const char* what) -> int {
+        const SearchResultBlock& r = *ws->h_result;
+        for (uint64_t i = 0; i < k_eff; ++i) {
+            const uint32_t p = r.pos[i];
+            if (p >= n) {
+                set_last_error(std::string(what) + " returned an out-of-range position (kernel bug)");
+                return ERR_DEVICE;
+            }
+            if (out_pos) out_pos[i] = p;
+            if (out_ids) out_ids[i] = ids_[p];
+            out_scores[i] = r.score[i];
+        }
+        *out_n = k_eff;
+        set_last_path(PATH_FAST);
+        return OK;
+    };
+
+    // First stage on the largest indexes (auto) or on request (mode 3): scan the int8 copy (a quarter of the f32 slab's
+    // bytes).  Its keys bound the score from above, so the same exact f64 rescoring and bound check (with the int8 key's
+    // evaluation term) certify the answer or hand the query on: to the bf16 stage when that one is on, else to the f32
+    // scan.  Same protocol as below: the query in the kernel arguments, the finalize reading the pinned f64 query.
+    bool i8_stage = fast_ok && !skip_bf16 && scan_i8_supported((uint32_t)dim_, metric) && i8_first(n);
+    if (i8_stage) {
+        const int irc = ensure_i8_slab();
+        if (irc != OK) {
+            if (single_filter_.load() != FILTER_AUTO) return irc;
+            i8_unavailable_.store(true);  // auto: no room for the copy, the next stage answers
+            i8_stage = false;
+        }
+    }
+    if (i8_stage) {
+        const bool prof = profile_.load();
+        const uint32_t ldb = mfma_ldb((uint32_t)dim_);
+        I8Query q8;
+        prepare_i8_query(query, (uint32_t)dim_, &q8);
+        uint32_t seq = ++ws->seq;
+        if (seq == 0) seq = ++ws->seq;
+        ws->h_result->seq = 0;
+        int grid = 0, variant = 0;
+        if (prof) VL_HIP(hipEventRecord(ws->ev0, st));
+        VL_HIP(launch_scan_i8(st, metric, d_slab8_, d_sr8_, d_norm8_, q8, n, (uint32_t)dim_, ws->d_partials, &grid, &variant));
+        if (prof) VL_HIP(hipEventRecord(ws->ev1, st));
+        // the keys are upper bounds up to their f32 evaluation (mfma_scan.hpp)
+        VL_HIP(launch_merge_finalize(st, seq, metric, ws->d_partials, grid, d_master_, ws->h_q64, ws->h_q64 + dim_,
+                                     (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_, ws->h_result, IN_EXTRA_I8_SINGLE));
+        last_scan_variant_.store(variant, std::memory_order_relaxed);
+        last_scan_grid_.store(grid, std::memory_order_relaxed);
+        last_scan_qarg_.store(1, std::memory_order_relaxed);
+        VL_TRY(wait_result(ws, seq));
+        if (prof) {
+            float ms = 0.f;
+            hipError_t pe = hipEventElapsedTime(&ms, ws->ev0, ws->ev1);
+            if (pe == hipErrorNotReady) {
+                VL_HIP(hipEventSynchronize(ws->ev1));
+                pe = hipEventElapsedTime(&ms, ws->ev0, ws->ev1);
+            }
+            VL_HIP(pe);
+            std::lock_guard<std::mutex> g(prof_mu_);
+            prof_n_ += 1;
+            prof_ms_ += ms;
+            // the rows plus the per-row (s, r) pair, and |row| for dot
+            prof_bytes_ += n * ((uint64_t)ldb + 2 * sizeof(float) + (metric == DOT ? sizeof(float) : 0));
+        }
+        const SearchResultBlock& r = *ws->h_result;
+        const bool certified = !(r.flags & RESULT_NEEDS_EXACT) && r.n_out == k_eff;
+        i8_outcome(certified);
+        if (certified) return take_result("int8 filter");
+    }
+
+    // Next stage on large indexes (auto) or on request (mode 1): scan the bf16 copy of the slab (half the HBM bytes).
     // Its candidates get the same exact f64 rescoring and a bound with the bf16 row-rounding term; if that cannot
     // certify the answer the f32 scan below runs as before.  Same protocol as the f32 scan: the f32 query in the kernel
     // arguments, the finalize reading the pinned f64 query, a stamped result block -- nothing is copied to the device.
@@ -972,21 +1073,7 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
         const SearchResultBlock& r = *ws->h_result;
         const bool certified = !(r.flags & RESULT_NEEDS_EXACT) && r.n_out == k_eff;
         bf16_outcome(certified);
-        if (certified) {
-            for (uint64_t i = 0; i < k_eff; ++i) {
-                const uint32_t p = r.pos[i];
-                if (p >= n) {
-                    set_last_error("bf16 filter returned an out-of-range position (kernel bug)");
-                    return ERR_DEVICE;
-                }
-                if (out_pos) out_pos[i] = p;
-                if (out_ids) out_ids[i] = ids_[p];
-                out_scores[i] = r.score[i];
-            }
-            *out_n = k_eff;
-            set_last_path(PATH_FAST);
-            return OK;
-        }
+        if (certified) return take_result("bf16 filter");
     }
     if (fast_ok) {
         const bool prof = profile_.load();
@@ -1277,6 +1364,43 @@ int GpuFlatIndex::ensure_bf16_slab(bool frag_major) const
         }
         VL_HIP(hipStreamSynchronize(mut_stream_));
         rows_done = n;
+    }
+    return OK;
+}
+
+// The int8 copy of the single-query filter: allocated all at once (the three arrays or none), converted from the f64
+// master incrementally (rows added since the last build; a delete rewinds slab8_rows_, growth frees the copy).
+int GpuFlatIndex::ensure_i8_slab() const
+{
+    std::lock_guard<std::mutex> g(bf16_mu_);
+    const uint64_t n = ids_.size();
+    const uint32_t ldb = mfma_ldb((uint32_t)dim_);
+    if (!d_slab8_) {
+        void* s8 = nullptr;
+        float* sr = nullptr;
+        float* nr = nullptr;
+        hipError_t e = hipMalloc(&s8, cap_ * (size_t)ldb);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sr), cap_ * 2 * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&nr), cap_ * sizeof(float));
+        if (e != hipSuccess) {
+            if (s8) (void)hipFree(s8);
+            if (sr) (void)hipFree(sr);
+            if (nr) (void)hipFree(nr);
+            (void)hipGetLastError();
+            set_last_error(std::string("int8 slab allocation failed: ") + hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? (int)ERR_OOM : (int)ERR_DEVICE;
+        }
+        d_slab8_ = s8;
+        d_sr8_ = sr;
+        d_norm8_ = nr;
+        slab8_rows_ = 0;
+    }
+    if (slab8_rows_ < n) {
+        char* dst = reinterpret_cast<char*>(d_slab8_) + slab8_rows_ * (size_t)ldb;
+        VL_HIP(launch_rows_i8(mut_stream_, d_master_ + slab8_rows_ * dim_, n - slab8_rows_, (uint32_t)dim_, dst,
+                              d_sr8_ + 2 * slab8_rows_, d_norm8_ + slab8_rows_));
+        VL_HIP(hipStreamSynchronize(mut_stream_));
+        slab8_rows_ = n;
     }
     return OK;
 }

@@ -186,20 +186,27 @@ public:
     uint64_t capacity() const { return cap_; }
 
     void force_path(int p) { force_path_.store(p); }
-    // Which slab a single query scans first (single_filter.hpp).  0: the f32 slab only.  1: the bf16 copy first, always
-    // (half the bytes; switches itself off for good once more than a third of 64+ tries failed to certify).  2 ("auto",
-    // the default): the bf16 copy first when the f32 slab is at least SINGLE_FILTER_MIN_BYTES (VL_SINGLE_FILTER_MIN_MB at
-    // create), paused by AutoFilterWindow's rule while it fails to certify.
+    // Which copies a single query scans before the f32 slab (single_filter.hpp).  0: the f32 slab only.  1: the bf16 copy
+    // first, always (half the bytes; switches itself off for good once more than a third of 64+ tries failed to certify).
+    // 2 ("auto", the default): the ladder int8 -> bf16 -> f32: the int8 copy (a quarter of the bytes) when the f32 slab is
+    // at least SINGLE_FILTER_I8_MIN_BYTES (VL_SINGLE_FILTER_I8_MIN_MB at create), the bf16 copy when it is at least
+    // SINGLE_FILTER_MIN_BYTES (VL_SINGLE_FILTER_MIN_MB), each paused by its own AutoFilterWindow while it fails to
+    // certify.  3: the int8 copy first, always (cosine and dot; mode 1's one-way rule), then the f32 slab.
     void set_single_filter(int mode)
     {
         single_filter_.store(mode);
         bf16_tries_.store(0);
         bf16_fails_.store(0);
+        i8_tries_.store(0);
+        i8_fails_.store(0);
         auto_window_.reset();
+        i8_window_.reset();
         auto_unavailable_.store(false);
+        i8_unavailable_.store(false);
     }
     int single_filter() const { return single_filter_.load(); }
     void set_single_filter_min_bytes(uint64_t b) { auto_min_bytes_ = b; }
+    void set_single_filter_i8_min_bytes(uint64_t b) { i8_min_bytes_ = b; }
     // Group concurrent single-query search() calls into shared slab passes (coalescer.hpp, search_coalesced()).
     // max_batch <= 1 turns it off.  window_us: how long a lone caller waits for company.  create() turns it on with
     // (COALESCE_DEFAULT_BATCH, 0) unless VL_COALESCE=0.
@@ -244,14 +251,18 @@ private:
     int search_coalesced(const double* query, uint64_t q_len, uint64_t k, int metric, uint64_t* out_pos,
                          uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;
     void run_coalesced(std::vector<CoalesceReq*>& batch) const;
-    // skip_bf16: the query already failed a bf16 filter's certification (an MFMA batch straggler): straight to k_scan
+    // skip_bf16: the query already failed a bf16 filter's certification (an MFMA batch straggler): neither the int8 nor the
+    // bf16 stage, straight to k_scan
     int search_locked(Workspace* ws, const double* query, uint64_t k_eff, int metric, uint64_t* out_pos,
                       uint64_t* out_ids, double* out_scores, uint64_t* out_n, bool skip_fast, bool skip_bf16 = false) const;
-    bool bf16_first(uint64_t n) const;        // does this single search try the bf16 filter first
+    bool bf16_first(uint64_t n) const;        // does this single search try the bf16 filter (after the int8 one)
     void bf16_outcome(bool certified) const;  // records one try of the bf16 filter
+    bool i8_first(uint64_t n) const;          // does this single search try the int8 filter first
+    void i8_outcome(bool certified) const;    // records one try of the int8 filter
     int run_exact(Workspace* ws, int metric, uint64_t n, uint64_t k_eff, std::vector<uint32_t>* pos,
                   std::vector<double>* scores) const;
     int wait_result(Workspace* ws, uint32_t seq) const;
+    int ensure_i8_slab() const;  // lazily builds the int8 copy the single-query int8 filter streams
     int ensure_bf16_slab(bool frag_major) const;  // lazily builds the bf16 slab (row-major, or MFMA fragment order) a filter streams
     int ensure_mfma_scratch(Workspace* ws) const;
     int search_batch_locked(const double* queries, uint64_t nq, uint64_t q_len, uint64_t k, int metric, uint64_t* out_pos,
@@ -278,7 +289,13 @@ private:
     mutable uint64_t slab16_rows_ = 0;     // rows converted so far (== len() once built)
     mutable void* d_slab16f_ = nullptr;    // the same rows in MFMA fragment order: what k_mfma_rows streams (lazy; dims <= 384)
     mutable uint64_t slab16f_rows_ = 0;
-    mutable std::mutex bf16_mu_;
+    // The int8 copy (rebuilt on demand like the row-major bf16 one; never cloned, exported or persisted): [cap, ldb]
+    // offset-binary bytes of the unit rows, per row the (s, r) pair of k_rows_i8 and |row| (f32).  All three or none.
+    mutable void* d_slab8_ = nullptr;
+    mutable float* d_sr8_ = nullptr;     // [cap][2]
+    mutable float* d_norm8_ = nullptr;   // [cap]
+    mutable uint64_t slab8_rows_ = 0;    // rows converted so far
+    mutable std::mutex bf16_mu_;         // (also guards the int8 copy)
     mutable unsigned long long* d_ids_ = nullptr;  // [d_ids_cap_] position -> id on the device (lazy: row-sharded batches only)
     mutable uint64_t d_ids_cap_ = 0, d_ids_rows_ = 0;  // rows uploaded so far (a delete rewinds it like the bf16 copies)
     IngestStats* d_stats_ = nullptr;
@@ -306,12 +323,19 @@ private:
     std::atomic<int> force_path_{0};
     std::atomic<int> single_filter_{FILTER_AUTO};
     mutable std::atomic<uint64_t> bf16_tries_{0}, bf16_fails_{0};  // mode 1
+    mutable std::atomic<uint64_t> i8_tries_{0}, i8_fails_{0};      // mode 3
     // auto: below this f32 slab size back-to-back searches find the slab in the 256 MiB Infinity Cache and the f32 scan
     // is as fast as the bf16 one (profiles/single_filter_crossover.jsonl)
     static constexpr uint64_t SINGLE_FILTER_MIN_BYTES = 512ull << 20;
     uint64_t auto_min_bytes_ = SINGLE_FILTER_MIN_BYTES;
     mutable AutoFilterWindow auto_window_;
     mutable std::atomic<bool> auto_unavailable_{false};  // the bf16 copy could not be allocated: auto stays on f32
+    // auto's int8 stage: its own floor (VL_SINGLE_FILTER_MIN_MB does not lower it).  Below 1 GiB the copy -- a fourth
+    // image of the data, +0.25 x the f32 slab -- would save a few tens of us at most (profiles/single_filter_i8_crossover.jsonl).
+    static constexpr uint64_t SINGLE_FILTER_I8_MIN_BYTES = 1024ull << 20;
+    uint64_t i8_min_bytes_ = SINGLE_FILTER_I8_MIN_BYTES;
+    mutable AutoFilterWindow i8_window_;
+    mutable std::atomic<bool> i8_unavailable_{false};  // the int8 copy could not be allocated: auto goes on to bf16
     std::atomic<bool> profile_{false};
     // single searches in flight on this handle: up to SPIN_MAX_SEARCHERS of them poll their result stamp,
     // more than that sleep in hipStreamSynchronize (wait_result)

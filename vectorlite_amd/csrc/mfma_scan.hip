@@ -27,6 +27,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <cmath>
 #include <type_traits>
 
 #include "device_common.hpp"
@@ -1095,6 +1096,110 @@ __global__ __launch_bounds__(256) void k_scan_bf16_qarg(const u32x4* __restrict_
     scan_bf16_body<METRIC, G, VPL, U>(slab16, row_nrm, row_sqn, qv, n, out);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Single-query scan of the int8 copy (the first stage of the single-query ladder: a quarter of the f32 slab's bytes).
+// Row i holds offset-binary bytes b = k + 128 (k in [-127, 127]) and a pair (s, r): x^ = x/|x| = s k + e with
+// |e| <= r.  The key is an UPPER bound of x^.q (up to its f32 evaluation error, IN_EXTRA_I8_SINGLE):
+//   cosine  s (k.q16) 2^-e + r (Q + D) + D        dot  |x| (the same)
+// where q16 = the f16 query scaled by 2^e and D >= |q - 2^-e q16| (Scan8QArg).  A byte pair becomes two exact f16
+// values with one v_perm_b32 (0x64 as their high byte: 1024 + b) and one packed subtract (of 1152), and meets the
+// query in v_dot2_f32_f16: 1.5 VALU ops per byte.  Structure of scan_bf16_body.
+// ---------------------------------------------------------------------------------------------
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float dot4_i8(float a, uint32_t w, uint32_t q01, uint32_t q23)
+{
+    const f16x2 off = {(_Float16)1152.0f, (_Float16)1152.0f};
+    const uint32_t lo = __builtin_amdgcn_perm(0x64646464u, w, 0x04010400u);  // bytes b0, 0x64, b1, 0x64
+    const uint32_t hi = __builtin_amdgcn_perm(0x64646464u, w, 0x04030402u);  // bytes b2, 0x64, b3, 0x64
+    const f16x2 k01 = __builtin_bit_cast(f16x2, lo) - off;                   // exact: k in [-127, 127]
+    const f16x2 k23 = __builtin_bit_cast(f16x2, hi) - off;
+    a = __builtin_amdgcn_fdot2(k01, __builtin_bit_cast(f16x2, q01), a, false);
+    a = __builtin_amdgcn_fdot2(k23, __builtin_bit_cast(f16x2, q23), a, false);
+    return a;
+}
+
+// The query half of the kernel arguments: the f16 query (scaled by 2^e, zero padded to ldb halves) and the three
+// per-query scalars of the key.
+struct alignas(16) Scan8QArg {
+    uint32_t h[SCAN8_QARG_HALVES / 2];  // halves 2j, 2j + 1 in word j
+    float inv_scale;                     // 2^-e
+    float qd;                            // Q + D, rounded up
+    float d;                             // D, rounded up
+    float pad_;
+};
+
+// LD16 == G * VPL 16-byte chunks per row; lane c of a row's G lanes holds chunks c + G j (16 bytes each: query halves
+// 16 (c + G j) .. + 15 in qv[j][0..1]).
+template <int METRIC, int G, int VPL, int U>
+__global__ __launch_bounds__(256) void k_scan_i8_qarg(const u32x4* __restrict__ slab8, const float2* __restrict__ row_sr,
+                                                      const float* __restrict__ row_nrm, uint32_t n,
+                                                      Cand32* __restrict__ out, const Scan8QArg qa)
+{
+    static_assert(G * VPL * 16 <= SCAN8_QARG_HALVES, "row too long for the kernarg query");
+    constexpr int RPS = WAVE / G;
+    constexpr uint32_t LD16 = G * VPL;
+    __shared__ Cand32 sh[4 * WAVE];
+    const int lane = lane_id();
+    const int wave = threadIdx.x >> 6;
+    const int g = lane / G, c = lane % G;
+    u32x4 qv[VPL][2];
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+        qv[j][0] = *reinterpret_cast<const u32x4*>(&qa.h[8 * (c + G * j)]);
+        qv[j][1] = *reinterpret_cast<const u32x4*>(&qa.h[8 * (c + G * j) + 4]);
+    }
+    const float inv_scale = qa.inv_scale, qd = qa.qd, dq = qa.d;
+
+    const uint32_t n_steps = (n + RPS - 1) / RPS;
+    const uint32_t n_waves = gridDim.x * 4;
+    TopList<float> L;
+    L.init();
+    for (uint32_t s0 = blockIdx.x * 4 + wave; s0 < n_steps; s0 += n_waves * U) {
+        u32x4 x[U][VPL];
+        uint32_t row[U];
+        float2 sr[U];
+        float nr[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t s = s0 + (uint32_t)u * n_waves;
+            row[u] = s < n_steps ? s * RPS + g : n;  // n marks "no row"
+            const uint32_t r = row[u] < n ? row[u] : n - 1;  // clamp: loads stay in bounds
+            const u32x4* p = slab8 + (size_t)r * LD16 + c;
+#pragma unroll
+            for (int j = 0; j < VPL; ++j) x[u][j] = __builtin_nontemporal_load(p + G * j);
+            sr[u] = row_sr[r];
+            nr[u] = 1.0f;
+            if (METRIC == DOT) nr[u] = row_nrm[r];
+        }
+        __builtin_amdgcn_sched_barrier(0);  // every load of the iteration issued before the first product
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float a = 0.0f;
+#pragma unroll
+            for (int j = 0; j < VPL; ++j) {
+                a = dot4_i8(a, x[u][j].x, qv[j][0].x, qv[j][0].y);
+                a = dot4_i8(a, x[u][j].y, qv[j][0].z, qv[j][0].w);
+                a = dot4_i8(a, x[u][j].z, qv[j][1].x, qv[j][1].y);
+                a = dot4_i8(a, x[u][j].w, qv[j][1].z, qv[j][1].w);
+            }
+#pragma unroll
+            for (int o = G / 2; o >= 1; o >>= 1) a += __shfl_xor(a, o);
+            const float m = a * inv_scale;                           // exact: a power of two
+            float key = sr[u].x * m + (sr[u].y * qd + dq);            // >= x^.q (cosine: ranks like x^.q / Q)
+            if (METRIC == DOT) key = key * nr[u];                    // >= x.q
+            L.offer(key, row[u], row[u] < n && c == 0);
+        }
+    }
+    block_merge<float, Cand32, 4>(L, sh);
+    if (wave == 0) {
+        Cand32 e;
+        e.key = L.key;
+        e.pos = L.pos;
+        out[(size_t)blockIdx.x * KP + lane] = e;
+    }
+}
+
 // T_q = the 64th largest group maximum (a lower bound of the query's 64th best key); -inf when fewer
 // than 64 groups exist.  One wave per query.
 // A query of norm 0 (a zero query, or one the host zeroed because it is outside the fast-path domain) scores 0 on every
@@ -1575,6 +1680,67 @@ __global__ __launch_bounds__(256) void k_rows_bf16_frag(const double* __restrict
     }
 }
 
+// x > 0 in f64 -> the smallest f32 >= x (x below FLT_MAX)
+__device__ __forceinline__ float f32_up(double x)
+{
+    float f = (float)x;
+    if ((double)f < x) f = __uint_as_float(__float_as_uint(f) + 1u);
+    return f;
+}
+
+// f64 master rows -> the int8 copy [n, ldb] (offset-binary bytes k + 128, padding k = 0) of the UNIT-NORMALISED rows
+// x^ = x/|x| (f64, as k_rows_bf16), the pair (s, r) and |row| rounded once to f32.  s = max|x^_i| / 127 rounded up to
+// f32, so k_i = rint(x^_i / s) stays in [-127, 127] without clamping; r >= |x/|x| - s k| in real arithmetic: the f64
+// residual inflated for its own rounding and for x^'s error against the exact unit row ((dim + 8) 2^-52 each, far
+// above the worst case), rounded up to f32.  Zero rows: s = r = 0, k = 0.  One wave per row.
+__global__ __launch_bounds__(256) void k_rows_i8(const double* __restrict__ master, uint64_t n, uint32_t dim, uint32_t ldb,
+                                                 uint32_t* __restrict__ out, float2* __restrict__ out_sr,
+                                                 float* __restrict__ out_nrm)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t n_waves = (uint64_t)gridDim.x * 4;
+    for (uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += n_waves) {
+        const double* src = master + row * dim;
+        double ss = 0.0, mx = 0.0;
+        for (uint32_t c = lane; c < dim; c += 64) {
+            const double v = src[c];
+            ss += v * v;
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
+        const double nrm = sqrt(ss);
+        const double inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
+        for (uint32_t c = lane; c < dim; c += 64) mx = fmax(mx, fabs(src[c] * inv));
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+        const float s = mx > 0.0 ? f32_up(mx / 127.0) : 0.0f;
+        const double sd = (double)s, rs = s > 0.0f ? 1.0 / sd : 0.0;
+        double res = 0.0;
+        for (uint32_t p = lane; p < ldb / 4; p += 64) {
+            uint32_t w = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint32_t c = 4 * p + e;
+                const double xh = c < dim ? src[c] * inv : 0.0;
+                double k = rint(xh * rs);
+                k = fmin(127.0, fmax(-127.0, k));  // a no-op (s is rounded up); kept so a byte can never wrap
+                const double d = xh - sd * k;       // s k is exact in f64
+                res += d * d;
+                w |= (uint32_t)((int)k + 128) << (8 * e);
+            }
+            out[(row * ldb) / 4 + p] = w;
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) res += __shfl_xor(res, o);
+        if (lane == 0) {
+            const double slack = (double)(dim + 8) * 2.220446049250313e-16;  // (dim + 8) 2^-52
+            const double r = sqrt(res) * (1.0 + slack) + slack;
+            out_sr[row] = make_float2(s, s > 0.0f ? f32_up(r) : 0.0f);
+            out_nrm[row] = (float)nrm;
+        }
+    }
+}
+
 }  // namespace
 
 #define VL_MFMA_KSTEPS(X) X(8) X(16) X(24) X(32) X(48)
@@ -1970,6 +2136,143 @@ hipError_t launch_scan_bf16(hipStream_t s, int metric, const void* slab_bf16, co
         else VL_L3(DOT, G, VPL, U)                                                                  \
     }
     VL_BF16_SCAN_SHAPES(VL_L)
+#undef VL_L
+#undef VL_L3
+    if (!launched) return hipErrorInvalidValue;
+    if (grid_out) *grid_out = grid;
+    if (variant_out) *variant_out = variant;
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// The int8 single-query filter
+// ---------------------------------------------------------------------------------------------
+hipError_t launch_rows_i8(hipStream_t s, const double* master, uint64_t n, uint32_t dim, void* out_i8, float* out_sr,
+                          float* out_norm)
+{
+    if (n == 0) return hipSuccess;
+    const uint32_t ldb = mfma_ldb(dim);
+    const int grid = (int)std::min<uint64_t>((n + 3) / 4, 16384);
+    hipLaunchKernelGGL(k_rows_i8, dim3(grid), dim3(256), 0, s, master, n, dim, ldb, reinterpret_cast<uint32_t*>(out_i8),
+                       reinterpret_cast<float2*>(out_sr), out_norm);
+    return hipGetLastError();
+}
+
+// (lanes per row G, 16-byte chunks per lane VPL, row steps in flight U) per int8 row stride (ldb / 16 = G * VPL chunks).
+// The first shape whose G * VPL matches the stride runs; VL_SCAN8_SHAPE="G,VPL,U" picks another listed one (tuning).
+// Measured (profiles/single_filter_i8_shape_sweep.jsonl, 3 workgroups per CU): G = 8 streams fastest -- 10 M x 384:
+// (8,3,1) 0.584 ms, (8,3,2) 0.591, (4,6,2) 0.640, (4,6,1) 0.653, (2,12,1) 1.145; 5 M x 768: (8,6,1) 0.567, (8,6,2)
+// 0.567, (16,3,1) 0.570, (4,12,1) 0.653.  Four lanes per row leave each row's reduction and offer to fewer lanes but
+// give every lane twice the bytes to widen before its row is done.
+#define VL_I8_SCAN_SHAPES(X)                                                                                       \
+    X(8, 1, 1) X(8, 2, 1) X(8, 3, 1) X(8, 4, 1) X(8, 6, 1)                                                         \
+    X(4, 2, 1) X(4, 4, 1) X(4, 6, 1) X(4, 8, 1) X(8, 3, 2) X(4, 6, 2) X(2, 12, 1) X(8, 6, 2) X(4, 12, 1) X(16, 3, 1)
+
+bool scan_i8_supported(uint32_t dim, int metric)
+{
+    if (metric != COSINE && metric != DOT) return false;
+    const uint32_t ldb = mfma_ldb(dim), ld16 = ldb / 16;
+    if (ldb > (uint32_t)SCAN8_QARG_HALVES) return false;
+    bool ok = false;
+#define VL_CHK(G, VPL, U) ok = ok || (ld16 == (uint32_t)(G * VPL));
+    VL_I8_SCAN_SHAPES(VL_CHK)
+#undef VL_CHK
+    return ok;
+}
+
+namespace {
+double f64_up(double x, double rel) { return x * (1.0 + rel) + 1e-300; }
+// x >= 0 -> the smallest f32 >= x
+float f32_up_host(double x)
+{
+    float f = (float)x;
+    if ((double)f < x) f = std::nextafter(f, INFINITY);
+    return f;
+}
+}  // namespace
+
+void prepare_i8_query(const double* q, uint32_t dim, I8Query* out)
+{
+    I8Query& p = *out;
+    memset(p.h, 0, sizeof(p.h));
+    double mx = 0.0, qq = 0.0;
+    dim = std::min<uint32_t>(dim, (uint32_t)SCAN8_QARG_HALVES);
+    for (uint32_t i = 0; i < dim; ++i) {
+        mx = std::max(mx, std::fabs(q[i]));
+        qq += q[i] * q[i];
+    }
+    // 2^e: the largest |q_i| lands in [2^14, 2^15), far from the f16 limit 65504 and from its subnormals
+    int ex = 0;
+    if (mx > 0.0) (void)std::frexp(mx, &ex);  // mx = m 2^ex, m in [0.5, 1)
+    const int e = mx > 0.0 ? 15 - ex : 0;
+    double dd = 0.0;
+    for (uint32_t i = 0; i < dim; ++i) {
+        const double v = std::ldexp(q[i], e);  // exact
+        _Float16 h = (_Float16)v;
+        if (std::fabs((double)h) < 6.103515625e-05) h = (_Float16)0.0f;  // no f16 subnormals reach the dot instruction
+        const double back = std::ldexp((double)h, -e);                   // exact
+        const double d = q[i] - back;
+        dd += d * d;
+        uint16_t bits;
+        memcpy(&bits, &h, 2);
+        p.h[i] = bits;
+    }
+    // |q| and D = |q - 2^-e q16| rounded UP through f64 (their sums carry (dim + 2) 2^-53 relative; inflated 4x) to f32
+    const double rel = 4.0 * (double)(dim + 2) * 1.1102230246251565e-16;
+    const double qn = f64_up(std::sqrt(qq), rel), dn = f64_up(std::sqrt(dd), rel);
+    p.inv_scale = std::ldexp(1.0f, -e);
+    p.d = f32_up_host(dn);
+    p.qd = f32_up_host(f64_up((double)f32_up_host(qn) + (double)p.d, 2.220446049250313e-16));
+}
+
+hipError_t launch_scan_i8(hipStream_t s, int metric, const void* slab_i8, const float* row_sr, const float* row_norm,
+                          const I8Query& q, uint64_t n, uint32_t dim, Cand32* partials, int* grid_out, int* variant_out)
+{
+    if (n == 0 || n >= 0xFFFFFFFFull || !scan_i8_supported(dim, metric)) return hipErrorInvalidValue;
+    const uint32_t ldb = mfma_ldb(dim), ld16 = ldb / 16;
+    const u32x4* slab = reinterpret_cast<const u32x4*>(slab_i8);
+    const float2* sr = reinterpret_cast<const float2*>(row_sr);
+    int dev = 0, cus = 256;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    const char* ge = getenv("VL_SCAN8_BPC");
+    // workgroups per CU: 3 at every stride (5 M x 768: 0.567 ms against 0.577 with 2)
+    const int bpc = ge && *ge ? atoi(ge) : SCAN8_BPC;
+    int want_g = 0, want_vpl = 0, want_u = 0;
+    if (const char* se = getenv("VL_SCAN8_SHAPE")) {
+        if (sscanf(se, "%d,%d,%d", &want_g, &want_vpl, &want_u) != 3) want_g = 0;
+    }
+    bool want_listed = false;
+#define VL_CHK(G, VPL, U) want_listed = want_listed || (want_g == G && want_vpl == VPL && want_u == U && ld16 == (uint32_t)(G * VPL));
+    VL_I8_SCAN_SHAPES(VL_CHK)
+#undef VL_CHK
+    bool launched = false;
+    int grid = 1, variant = 0;
+    Scan8QArg qa;
+    memset(&qa, 0, sizeof(qa));
+    memcpy(qa.h, q.h, (size_t)ldb * sizeof(uint16_t));
+    qa.inv_scale = q.inv_scale;
+    qa.qd = q.qd;
+    qa.d = q.d;
+#define VL_L3(MET, G, VPL, U)                                                                                       \
+    {                                                                                                               \
+        const uint64_t steps = (n + (64 / G) - 1) / (64 / G);                                                       \
+        uint64_t blocks = (steps + 3) / 4;                                                                          \
+        if (blocks > (uint64_t)(cus * bpc)) blocks = (uint64_t)(cus * bpc);                                         \
+        if (blocks > (uint64_t)SCAN_MAX_GRID) blocks = SCAN_MAX_GRID;                                               \
+        grid = (int)(blocks < 1 ? 1 : blocks);                                                                      \
+        hipLaunchKernelGGL((k_scan_i8_qarg<MET, G, VPL, U>), dim3(grid), dim3(256), 0, s, slab, sr, row_norm,       \
+                           (uint32_t)n, partials, qa);                                                              \
+        launched = true;                                                                                            \
+    }
+#define VL_L(G, VPL, U)                                                                             \
+    if (!launched && ld16 == (uint32_t)(G * VPL) &&                                                 \
+        (!want_listed || (want_g == G && want_vpl == VPL && want_u == U))) {                        \
+        variant = SCAN8_VARIANT_BASE + G * 10000 + VPL * 100 + U;                                   \
+        if (metric == COSINE) VL_L3(COSINE, G, VPL, U)                                              \
+        else VL_L3(DOT, G, VPL, U)                                                                  \
+    }
+    VL_I8_SCAN_SHAPES(VL_L)
 #undef VL_L
 #undef VL_L3
     if (!launched) return hipErrorInvalidValue;

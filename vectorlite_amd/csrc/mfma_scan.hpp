@@ -30,6 +30,10 @@ constexpr int MFMA_MIN_BATCH = 2;      // measured at N = 10 M x 384: one bf16 p
 constexpr double IN_EXTRA_BF16_SINGLE = 0.00392;
 // MFMA batch filter: bf16 row and bf16 query: (2 + u) u with u = 2^-8 + 2^-23 (f64 -> f32 -> bf16 double rounding), rounded up.
 constexpr double IN_EXTRA_MFMA = 0.0079;
+// int8 single-query filter (k_scan_i8_qarg): its keys are upper bounds of the score in real arithmetic, so the term only
+// covers their f32 evaluation: 2 (n + 8) u (1 + 2 r_max) (1 + D/Q) with n = 768, u = 2^-24,
+// r_max = sqrt(768) / 254, D/Q <= 2^-11 + sqrt(768) 2^-28, rounded up.  Relative to Q (cosine) and R Q (dot).
+constexpr double IN_EXTRA_I8_SINGLE = 0.000113;
 
 // bf16 slab row stride in elements: dim rounded up to the MFMA K step (16)
 // Row stride of the bf16 slab in elements: the next length the MFMA kernel has a shape for (8 / 16 / 24 / 32 / 48
@@ -122,5 +126,29 @@ bool scan_bf16_supported(uint32_t dim, int metric);
 hipError_t launch_scan_bf16(hipStream_t s, int metric, const void* slab_bf16, const float* row_norm,
                             const float* row_sqnorm, const double* q64, uint64_t n, uint32_t dim, Cand32* partials,
                             int* grid_out, const float* q32_host = nullptr, int* variant_out = nullptr);
+
+// Single-query scan of the int8 copy (the first stage of the single-query ladder, cosine and dot only): per-workgroup
+// top-64 lists like launch_scan_bf16, keys that bound the score from above (k_scan_i8_qarg).  The rows: launch_rows_i8
+// writes [n, mfma_ldb(dim)] offset-binary bytes, one (s, r) f32 pair per row (row_sr: [n][2]) and |row| in f32.
+// The query always travels in the kernel arguments, as prepare_i8_query made it.
+// variant_out: SCAN8_VARIANT_BASE + G * 10000 + VPL * 100 + U (above every k_scan and k_scan_bf16 variant).
+constexpr int SCAN8_QARG_HALVES = 768;
+constexpr int SCAN8_VARIANT_BASE = 2000000;
+constexpr int SCAN8_BPC = 3;  // workgroups per CU (VL_SCAN8_BPC overrides)
+// A fixed array, filled in place (no allocation on the search path).
+struct I8Query {
+    uint16_t h[SCAN8_QARG_HALVES];  // f16 bits of q 2^e, zero padded past dim (f16 subnormals flushed to 0)
+    float inv_scale = 1.0f;   // 2^-e
+    float qd = 0.0f;          // >= |q| + D
+    float d = 0.0f;           // D >= |q - 2^-e q16|
+};
+// dim <= SCAN8_QARG_HALVES (scan_i8_supported); fills *out
+void prepare_i8_query(const double* q, uint32_t dim, I8Query* out);
+bool scan_i8_supported(uint32_t dim, int metric);
+hipError_t launch_rows_i8(hipStream_t s, const double* master, uint64_t n, uint32_t dim, void* out_i8, float* out_sr,
+                          float* out_norm);
+hipError_t launch_scan_i8(hipStream_t s, int metric, const void* slab_i8, const float* row_sr, const float* row_norm,
+                          const I8Query& q, uint64_t n, uint32_t dim, Cand32* partials, int* grid_out,
+                          int* variant_out = nullptr);
 
 }  // namespace vl
