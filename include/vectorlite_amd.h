@@ -183,6 +183,38 @@ int vl_index_search_batch(const vl_index *h, const double *queries, uint64_t nq,
 int vl_index_search_batch_cap(const vl_index *h, const double *queries, uint64_t nq, uint64_t q_len, uint64_t k,
                               int metric, uint64_t out_stride, uint64_t *out_ids, double *out_scores, uint64_t *out_n);
 
+/* NEW capability (the reference restricts nothing): search among the rows whose id is in a set -- "documents of this
+ * user", "chunks of this file", "rows whose metadata matches".  A filtered search returns exactly, ids and f64 scores,
+ * what FlatIndex::search (src/index/flat.rs:98-119) returns on a FlatIndex holding ONLY the rows of h whose id is in the
+ * set, in their storage order: ranking (score desc, insertion position asc) over the subset, every row whose id is in the
+ * set qualifies (duplicate-id rows included), ids the index does not hold are ignored.  VL_ERR_NAN_SCORE only when a
+ * subset row scores NaN (a lone qualifying row is returned whatever its score).  Errors are the unfiltered search's on
+ * the WHOLE index: the dimension check runs whenever len(h) != 0 (an empty subset included), an unknown metric is
+ * VL_ERR_INVALID_ARG, an empty subset or k = 0 gives *out_n = 0.
+ * Single-GPU flat handles only: HNSW and vl_flat_create_multi handles return VL_ERR_INVALID_ARG.  Filtered calls never
+ * join a coalesced pass.
+ *
+ * vl_index_filter_create: ids [n_ids] in any order, repeats allowed -> *out_filter, a token of this handle (never 0, never
+ * reused); *out_rows (may be NULL) = rows that qualify now.  A filter follows the index: after add / delete the next use
+ * resolves it again against the current rows.  vl_index_clone does not copy filters; vl_index_destroy frees them.
+ * vl_index_filter_rows: rows that qualify now (resolving again if rows changed).
+ * vl_index_filter_destroy: frees the token (a search using it at that moment finishes normally).
+ * An unknown or destroyed token is VL_ERR_INVALID_ARG. */
+int vl_index_filter_create(vl_index *h, const uint64_t *ids, uint64_t n_ids, uint64_t *out_filter, uint64_t *out_rows);
+int vl_index_filter_rows(const vl_index *h, uint64_t filter, uint64_t *out_rows);
+int vl_index_filter_destroy(vl_index *h, uint64_t filter);
+
+/* The filtered search, vl_index_search_cap's capacity rule: min(k, rows in the subset, out_capacity) entries, the prefix
+ * of the k results. */
+int vl_index_search_filtered(const vl_index *h, uint64_t filter, const double *query, uint64_t q_len, uint64_t k,
+                             int metric, uint64_t out_capacity, uint64_t *out_ids, double *out_scores, uint64_t *out_n);
+
+/* nq filtered searches with one filter, vl_index_search_batch_cap's layout: row i ([nq, out_stride]) is exactly
+ * vl_index_search_filtered's answer for queries[i]. */
+int vl_index_search_batch_filtered(const vl_index *h, uint64_t filter, const double *queries, uint64_t nq, uint64_t q_len,
+                                   uint64_t k, int metric, uint64_t out_stride, uint64_t *out_ids, double *out_scores,
+                                   uint64_t *out_n);
+
 uint64_t vl_index_len(const vl_index *h);      /* len()       src/index/flat.rs:121-123 */
 int vl_index_is_empty(const vl_index *h);      /* is_empty()  src/index/flat.rs:125-127 */
 uint64_t vl_index_dimension(const vl_index *h);/* dimension() src/index/flat.rs:133-135 */

@@ -27,7 +27,7 @@ from . import _lib
 
 __all__ = [
     "SimilarityMetric", "Vector", "SearchResult", "FlatIndex", "MultiFlatIndex", "HNSWIndex", "VectorLiteError", "DimensionMismatch",
-    "MetricMismatch", "NaNScore", "DeviceError", "IndexOpError", "hnsw_score", "runtime_info",
+    "MetricMismatch", "NaNScore", "DeviceError", "IndexOpError", "IdFilter", "hnsw_score", "runtime_info",
     "PATH_FAST", "PATH_EXACT_SELECT", "PATH_EXACT_SORT",
 ]
 
@@ -179,6 +179,60 @@ def _add_embeddings(L, h, dim: int, ids, embeddings, normalize: bool, validate: 
     _raise(rc)
 
 
+class IdFilter:
+    """A set of ids of one FlatIndex (vl_index_filter_create): searches given it rank only the rows whose id is in the set,
+    exactly as FlatIndex::search would on an index holding just those rows in their storage order.  It follows the index:
+    after add / delete the next use resolves it against the current rows.  `rows()` = rows that qualify now; `close()`
+    (or leaving a `with` block) frees it."""
+
+    def __init__(self, index: "FlatIndex", token: int):
+        self._index = index
+        self._token = token
+
+    @property
+    def token(self) -> int:
+        return self._token
+
+    def rows(self) -> int:
+        if not self._token:
+            raise IndexOpError("filter is closed")
+        out = C.c_uint64(0)
+        rc = self._index._L.vl_index_filter_rows(self._index._h, self._token, C.byref(out))
+        if rc == VL_ERR_INVALID_ARG:
+            raise IndexOpError(_last_error())
+        _raise(rc)
+        return int(out.value)
+
+    def close(self) -> None:
+        tok, self._token = self._token, 0
+        h = getattr(self._index, "_h", None)
+        if tok and h:
+            self._index._L.vl_index_filter_destroy(h, tok)
+
+    def __enter__(self) -> "IdFilter":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _make_filter(L, h, owner, ids) -> IdFilter:
+    ids = np.ascontiguousarray(np.fromiter((int(i) for i in ids), dtype=np.uint64)
+                               if not isinstance(ids, np.ndarray) else ids.astype(np.uint64, copy=False))
+    tok, rows = C.c_uint64(0), C.c_uint64(0)
+    rc = L.vl_index_filter_create(h, _pu64(ids), ids.size, C.byref(tok), C.byref(rows))
+    if rc == VL_ERR_INVALID_ARG:
+        raise IndexOpError(_last_error())
+    _raise(rc)
+    return IdFilter(owner, int(tok.value))
+
+
 class FlatIndex:
     """GPU-resident counterpart of `FlatIndex` (src/index/flat.rs:60-135).
 
@@ -228,8 +282,10 @@ class FlatIndex:
         _raise(self._L.vl_index_delete(self._h, int(id)))
         self._meta.pop(int(id), None)
 
-    def search(self, query, k: int, similarity_metric: int = SimilarityMetric.Cosine) -> List[SearchResult]:
-        ids, scores = self.search_arrays(query, k, similarity_metric)
+    def search(self, query, k: int, similarity_metric: int = SimilarityMetric.Cosine, filter=None) -> List[SearchResult]:
+        """`filter`: None, an IdFilter of this index, or an iterable of ids (a one-shot filter): the top k among the rows
+        whose id is in the set."""
+        ids, scores = self.search_arrays(query, k, similarity_metric, filter=filter)
         out = []
         for i, s in zip(ids.tolist(), scores.tolist()):
             text, md = self._meta.get(i, ("", None))
@@ -280,15 +336,44 @@ class FlatIndex:
             tl.buf = buf
         return buf
 
-    def search_arrays(self, query, k: int, metric: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    def search_arrays(self, query, k: int, metric: int = 0, filter=None) -> Tuple[np.ndarray, np.ndarray]:
         q = query
         if not (type(q) is np.ndarray and q.dtype == np.float64 and q.ndim == 1 and q.flags.c_contiguous):
             q = _f64(query).ravel()
         k = min(max(int(k), 0), 1 << 62)
         cap, ids, scores, n, p_ids, p_scores, p_n = self._out_buffers(k)
+        if filter is not None:
+            return self._search_filtered(q, k, metric, filter, cap, ids, scores, n, p_ids, p_scores, p_n)
         rc = self._L.vl_index_search_cap(self._h, q.ctypes.data, q.size, k, metric, cap, p_ids, p_scores, p_n)
         if rc:
             _raise(rc)
+        m = n.value
+        return ids[:m].copy(), scores[:m].copy()
+
+    # ---- id filters -------------------------------------------------------------------------
+    def make_filter(self, ids) -> IdFilter:
+        """An IdFilter over `ids` (any order, repeats allowed; ids the index does not hold are ignored)."""
+        return _make_filter(self._L, self._h, self, ids)
+
+    def _filter_token(self, filter):
+        """(token, one-shot filter to close afterwards or None)"""
+        if isinstance(filter, IdFilter):
+            if filter._index is not self:
+                raise ValueError("the filter belongs to another index")
+            return filter.token, None
+        f = self.make_filter(filter)
+        return f.token, f
+
+    def _search_filtered(self, q, k, metric, filter, cap, ids, scores, n, p_ids, p_scores, p_n):
+        tok, temp = self._filter_token(filter)
+        try:
+            rc = self._L.vl_index_search_filtered(self._h, tok, q.ctypes.data, q.size, k, int(metric), cap, p_ids, p_scores, p_n)
+        finally:
+            if temp is not None:
+                temp.close()
+        if rc == VL_ERR_INVALID_ARG:
+            raise IndexOpError(_last_error())
+        _raise(rc)
         m = n.value
         return ids[:m].copy(), scores[:m].copy()
 
@@ -304,9 +389,10 @@ class FlatIndex:
                                                  _pu64(ids), _pf64(scores), C.byref(n)))
         return pos[: n.value].copy(), ids[: n.value].copy(), scores[: n.value].copy()
 
-    def search_batch(self, queries, k: int, metric: int = 0):
+    def search_batch(self, queries, k: int, metric: int = 0, filter=None):
         """New capability (no reference counterpart): nq independent searches.
-        Returns (ids [nq, k], scores [nq, k], n [nq]); row i is exactly search(queries[i])."""
+        Returns (ids [nq, k], scores [nq, k], n [nq]); row i is exactly search(queries[i]) (with `filter`: exactly
+        search(queries[i], filter=filter))."""
         Q = _f64(queries)
         if Q.ndim != 2:
             raise ValueError("queries must be [nq, dim]")
@@ -316,6 +402,18 @@ class FlatIndex:
         ids = np.zeros((nq, kk), dtype=np.uint64)
         scores = np.zeros((nq, kk), dtype=np.float64)
         n = np.zeros(max(nq, 1), dtype=np.uint64)
+        if filter is not None:
+            tok, temp = self._filter_token(filter)
+            try:
+                rc = self._L.vl_index_search_batch_filtered(self._h, tok, _pf64(Q), nq, qlen, kc, int(metric), kk, _pu64(ids),
+                                                            _pf64(scores), _pu64(n))
+            finally:
+                if temp is not None:
+                    temp.close()
+            if rc == VL_ERR_INVALID_ARG:
+                raise IndexOpError(_last_error())
+            _raise(rc)
+            return ids[:, :kc], scores[:, :kc], n[:nq]
         _raise(self._L.vl_index_search_batch(self._h, _pf64(Q), nq, qlen, kc, int(metric), _pu64(ids),
                                              _pf64(scores), _pu64(n)))
         return ids[:, :kc], scores[:, :kc], n[:nq]
@@ -724,12 +822,20 @@ class HNSWIndex:
         self._raise_search(rc, metric)
         return ids[:, :kc], scores[:, :kc], n[:nq]
 
-    def search_arrays(self, query, k: int, metric: int, ef: int = 0):
+    def make_filter(self, ids) -> IdFilter:
+        """Filtered search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""
+        return _make_filter(self._L, self._h, self, ids)
+
+    def search_arrays(self, query, k: int, metric: int, ef: int = 0, filter=None):
+        if filter is not None:
+            self.make_filter(filter if not isinstance(filter, IdFilter) else [])  # raises: no filtered HNSW walk
         ids, scores, n = self.search_batch(_f64(query).ravel()[None, :], k, metric, ef)
         m = int(n[0])
         return ids[0, :m].copy(), scores[0, :m].copy()
 
-    def search(self, query, k: int, similarity_metric: int) -> List[SearchResult]:
+    def search(self, query, k: int, similarity_metric: int, filter=None) -> List[SearchResult]:
+        if filter is not None:
+            self.make_filter(filter if not isinstance(filter, IdFilter) else [])  # raises: no filtered HNSW walk
         q = _f64(query).ravel()
         kk = max(min(int(k), self.len()), 1)
         ids = np.zeros(kk, dtype=np.uint64)

@@ -14,7 +14,7 @@ import enum
 import itertools
 import threading
 from dataclasses import dataclass
-from typing import Any, Dict, List, Optional
+from typing import Any, Callable, Dict, List, Optional
 
 from . import (DimensionMismatch, FlatIndex, HNSWIndex, IndexOpError, SearchResult, SimilarityMetric, Vector,
                VectorLiteError)
@@ -99,9 +99,15 @@ class Collection:
                 raise VectorNotFound(f"Vector ID {id} not found") from e
             raise VectorLiteError(str(e)) from e
 
-    def search_text(self, query_text: str, k: int, similarity_metric: SimilarityMetric, embedding_function
-                    ) -> List[SearchResult]:
-        return self.index.search(embedding_function.generate_embedding(query_text), k, similarity_metric)
+    def search_text(self, query_text: str, k: int, similarity_metric: SimilarityMetric, embedding_function,
+                    where: Optional[Callable[[Any], bool]] = None) -> List[SearchResult]:
+        """`where`: a predicate on a row's metadata; only rows for which it holds are ranked (an exact filtered search
+        over the ids whose metadata matches -- flat collections)."""
+        embedding = embedding_function.generate_embedding(query_text)
+        if where is None:
+            return self.index.search(embedding, k, similarity_metric)
+        ids = [i for i, (_text, md) in list(self.index._meta.items()) if where(md)]
+        return self.index.search(embedding, k, similarity_metric, filter=ids)
 
     def get_vector(self, id: int) -> Optional[Vector]:
         return self.index.get_vector(id)
@@ -166,11 +172,12 @@ class VectorLiteClient:
         return self._get(collection_name).add_text_with_metadata(text, metadata, self.embedding_function)
 
     def search_text_in_collection(self, collection_name: str, query_text: str, k: int,
-                                  similarity_metric: Optional[SimilarityMetric] = None) -> List[SearchResult]:
+                                  similarity_metric: Optional[SimilarityMetric] = None,
+                                  where: Optional[Callable[[Any], bool]] = None) -> List[SearchResult]:
         c = self._get(collection_name)
         if similarity_metric is None:  # src/client.rs:143-155
             similarity_metric = c.index.metric() if isinstance(c.index, HNSWIndex) else SimilarityMetric.Cosine
-        return c.search_text(query_text, k, similarity_metric, self.embedding_function)
+        return c.search_text(query_text, k, similarity_metric, self.embedding_function, where=where)
 
     def delete_from_collection(self, collection_name: str, id: int) -> None:
         self._get(collection_name).delete(id)

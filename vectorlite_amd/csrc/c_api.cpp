@@ -314,6 +314,76 @@ int vl_index_search_cap(const vl_index* h, const double* query, uint64_t q_len, 
     return vl_index_search(h, query, q_len, k < out_capacity ? k : out_capacity, metric, out_ids, out_scores, out_n);
 }
 
+// Id filters live on single-GPU flat handles only.
+#define VL_FILTER_HANDLE(h)                                                                          \
+    if (!(h)) return VL_ERR_INVALID_ARG;                                                             \
+    if (!(h)->flat) {                                                                                \
+        vl::set_last_error("filtered search is served by single-GPU flat indexes");                  \
+        return VL_ERR_INVALID_ARG;                                                                   \
+    }
+
+int vl_index_filter_create(vl_index* h, const uint64_t* ids, uint64_t n_ids, uint64_t* out_filter, uint64_t* out_rows)
+{
+    return guarded([&]() -> int {
+        VL_FILTER_HANDLE(h);
+        if (!out_filter) return VL_ERR_INVALID_ARG;
+        return h->flat->filter_create(ids, n_ids, out_filter, out_rows);
+    });
+}
+
+int vl_index_filter_rows(const vl_index* h, uint64_t filter, uint64_t* out_rows)
+{
+    return guarded([&]() -> int {
+        VL_FILTER_HANDLE(h);
+        if (!out_rows) return VL_ERR_INVALID_ARG;
+        return h->flat->filter_rows(filter, out_rows);
+    });
+}
+
+int vl_index_filter_destroy(vl_index* h, uint64_t filter)
+{
+    return guarded([&]() -> int {
+        VL_FILTER_HANDLE(h);
+        return h->flat->filter_destroy(filter);
+    });
+}
+
+int vl_index_search_filtered(const vl_index* h, uint64_t filter, const double* query, uint64_t q_len, uint64_t k, int metric,
+                             uint64_t out_capacity, uint64_t* out_ids, double* out_scores, uint64_t* out_n)
+{
+    return guarded([&]() -> int {
+        if (!h || !out_n) return VL_ERR_INVALID_ARG;
+        *out_n = 0;
+        VL_FILTER_HANDLE(h);
+        const uint64_t kk = k < out_capacity ? k : out_capacity;  // a smaller k's answer is a prefix (vl_index_search_cap)
+        if (!out_ids && kk != 0) return VL_ERR_INVALID_ARG;
+        return h->flat->search_filtered(filter, query, q_len, kk, metric, nullptr, out_ids, out_scores, out_n);
+    });
+}
+
+int vl_index_search_batch_filtered(const vl_index* h, uint64_t filter, const double* queries, uint64_t nq, uint64_t q_len,
+                                   uint64_t k, int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores,
+                                   uint64_t* out_n)
+{
+    return guarded([&]() -> int {
+        if (!h || (!out_n && nq)) return VL_ERR_INVALID_ARG;
+        for (uint64_t q = 0; q < nq; ++q) out_n[q] = 0;
+        VL_FILTER_HANDLE(h);
+        if (nq == 0) return VL_OK;
+        if (!queries && q_len) return VL_ERR_INVALID_ARG;
+        const uint64_t kk = k < out_stride ? k : out_stride;
+        if ((!out_ids || !out_scores) && kk != 0) return VL_ERR_INVALID_ARG;
+        // each row is the single filtered search's answer, rows out_stride apart
+        for (uint64_t q = 0; q < nq; ++q) {
+            const int rc = h->flat->search_filtered(filter, queries + q * q_len, q_len, kk, metric, nullptr,
+                                                    kk ? out_ids + q * out_stride : nullptr,
+                                                    kk ? out_scores + q * out_stride : nullptr, out_n + q);
+            if (rc != VL_OK) return rc;
+        }
+        return VL_OK;
+    });
+}
+
 int vl_index_search_batch_cap(const vl_index* h, const double* queries, uint64_t nq, uint64_t q_len, uint64_t k,
                               int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores, uint64_t* out_n)
 {

@@ -277,6 +277,7 @@ void GpuFlatIndex::truncate(uint64_t n_rows)
         if (row_flags_[p] & ROW_OUT_OF_DOMAIN) --n_out_of_domain_;
     ids_.resize(n_rows);
     row_flags_.resize(n_rows);
+    ++mutations_;
     id_counts_valid_ = false;  // rebuilt on demand from ids_
     if (slab16_rows_ > n_rows) slab16_rows_ = n_rows;
     if (slab16f_rows_ > n_rows) slab16f_rows_ = n_rows;
@@ -448,6 +449,7 @@ int GpuFlatIndex::add_bulk(const uint64_t* ids, const double* values, uint64_t n
         return rc;
     }
     ids_.insert(ids_.end(), ids, ids + n_take);
+    ++mutations_;
     return rc_after;
 }
 
@@ -489,6 +491,7 @@ int GpuFlatIndex::remove_position(uint64_t pos)
     if (d_ids_rows_ > pos) d_ids_rows_ = pos;    // ... and the device id table re-uploaded from there
     ids_.erase(ids_.begin() + pos);
     row_flags_.erase(row_flags_.begin() + pos);
+    ++mutations_;
     return OK;
 }
 
@@ -1221,7 +1224,7 @@ int GpuFlatIndex::wait_result(Workspace* ws, uint32_t seq) const
 }
 
 int GpuFlatIndex::run_exact(Workspace* ws, int metric, uint64_t n, uint64_t k_eff, std::vector<uint32_t>* pos,
-                            std::vector<double>* scores) const
+                            std::vector<double>* scores, const uint32_t* plist) const
 {
     hipStream_t st = ws->stream;
     if (ws->scores_cap < n) {
@@ -1233,7 +1236,10 @@ int GpuFlatIndex::run_exact(Workspace* ws, int metric, uint64_t n, uint64_t k_ef
         ws->scores_cap = cap;
     }
     VL_HIP(hipMemsetAsync(ws->d_nan, 0, sizeof(uint32_t), st));
-    VL_HIP(launch_exact_scan(st, metric, d_master_, ws->d_q64, n, (uint32_t)dim_, ws->d_scores, ws->d_nan));
+    if (plist)
+        VL_HIP(launch_exact_scan_subset(st, metric, d_master_, ws->d_q64, plist, n, (uint32_t)dim_, ws->d_scores, ws->d_nan));
+    else
+        VL_HIP(launch_exact_scan(st, metric, d_master_, ws->d_q64, n, (uint32_t)dim_, ws->d_scores, ws->d_nan));
     VL_HIP(hipMemcpyAsync(ws->h_nan, ws->d_nan, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     pos->resize(k_eff);
     scores->resize(k_eff);
@@ -1311,6 +1317,311 @@ int GpuFlatIndex::run_exact(Workspace* ws, int metric, uint64_t n, uint64_t k_ef
     } else {
         set_last_path(PATH_EXACT_SORT);
     }
+    return OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Search restricted to an id filter.  The contract: exactly FlatIndex::search (src/index/flat.rs:98-119) on a FlatIndex
+// that holds only the rows whose id is in the set, in their storage order.  A filter is resolved on the device into the
+// ascending list of qualifying storage positions; the subset scan streams only those rows and hands storage positions to
+// the same finalize kernel, whose bound check and "the list must hold every row" rule then refer to the m subset rows.
+// ---------------------------------------------------------------------------------------------
+IdFilter::~IdFilter()
+{
+    (void)hipSetDevice(device);
+    void* dev[] = {d_ids, d_counts, d_plist};
+    for (void* p : dev)
+        if (p) (void)hipFree(p);
+}
+
+namespace {
+std::atomic<uint64_t> g_next_filter_token{1};  // process-wide: a token is never 0 and never handed out twice
+}  // namespace
+
+std::shared_ptr<IdFilter> GpuFlatIndex::find_filter(uint64_t token) const
+{
+    std::lock_guard<std::mutex> g(filters_mu_);
+    auto it = filters_.find(token);
+    return it == filters_.end() ? nullptr : it->second;
+}
+
+int GpuFlatIndex::filter_create(const uint64_t* ids, uint64_t n_ids, uint64_t* out_token, uint64_t* out_rows)
+{
+    if (!out_token || (!ids && n_ids)) return ERR_INVALID_ARG;
+    *out_token = 0;
+    if (n_ids >= 0xFFFFFFFFull) {
+        set_last_error("a filter holds fewer than 2^32 ids");
+        return ERR_INVALID_ARG;
+    }
+    auto f = std::make_shared<IdFilter>();
+    f->device = device_;
+    f->ids.assign(ids, ids + n_ids);
+    std::sort(f->ids.begin(), f->ids.end());
+    f->ids.erase(std::unique(f->ids.begin(), f->ids.end()), f->ids.end());
+    VL_HIP(hipSetDevice(device_));
+    if (!f->ids.empty()) {
+        VL_TRY(dev_alloc(&f->d_ids, f->ids.size()));
+        VL_HIP(hipMemcpy(f->d_ids, f->ids.data(), f->ids.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+        VL_TRY(dev_alloc(&f->d_counts, (size_t)FILTER_COUNTS_MAX + 1));
+    }
+    uint64_t rows = 0;
+    {
+        std::shared_lock<RwLock> lk(mu_);
+        std::lock_guard<std::mutex> fg(f->mu);
+        Workspace* ws = acquire_ws();
+        if (!ws) return ERR_DEVICE;
+        const int rc = resolve_filter(ws, f.get());
+        if (rc != OK) (void)hipStreamSynchronize(ws->stream);
+        release_ws(ws);
+        if (rc != OK) return rc;
+        rows = f->m;
+    }
+    const uint64_t token = g_next_filter_token.fetch_add(1);
+    {
+        std::lock_guard<std::mutex> g(filters_mu_);
+        filters_[token] = std::move(f);
+    }
+    *out_token = token;
+    if (out_rows) *out_rows = rows;
+    return OK;
+}
+
+int GpuFlatIndex::filter_destroy(uint64_t token)
+{
+    std::shared_ptr<IdFilter> f;  // a search still using it holds its own reference: freed when that one ends
+    {
+        std::lock_guard<std::mutex> g(filters_mu_);
+        auto it = filters_.find(token);
+        if (it == filters_.end()) {
+            set_last_error("unknown or destroyed filter");
+            return ERR_INVALID_ARG;
+        }
+        f = std::move(it->second);
+        filters_.erase(it);
+    }
+    return OK;
+}
+
+int GpuFlatIndex::filter_rows(uint64_t token, uint64_t* out_rows) const
+{
+    if (!out_rows) return ERR_INVALID_ARG;
+    std::shared_ptr<IdFilter> f = find_filter(token);
+    if (!f) {
+        set_last_error("unknown or destroyed filter");
+        return ERR_INVALID_ARG;
+    }
+    std::shared_lock<RwLock> lk(mu_);
+    std::lock_guard<std::mutex> fg(f->mu);
+    if (f->resolved_at != mutations_) {
+        VL_HIP(hipSetDevice(device_));
+        Workspace* ws = acquire_ws();
+        if (!ws) return ERR_DEVICE;
+        const int rc = resolve_filter(ws, f.get());
+        if (rc != OK) (void)hipStreamSynchronize(ws->stream);
+        release_ws(ws);
+        if (rc != OK) return rc;
+    }
+    *out_rows = f->m;
+    return OK;
+}
+
+// positions p < len() whose ids_[p] is in f->ids -> f->d_plist[0..m), ascending.  Two launches, one 4-byte read-back (m, which
+// sizes the list and the scan's grid), one launch; nothing per row crosses PCIe.
+int GpuFlatIndex::resolve_filter(Workspace* ws, IdFilter* f) const
+{
+    const uint64_t n = ids_.size();
+    f->m = 0;
+    f->h_plist_valid = false;
+    f->resolved_at = ~0ull;
+    if (n != 0 && !f->ids.empty()) {
+        hipStream_t st = ws->stream;
+        VL_TRY(ensure_device_ids());
+        VL_HIP(launch_filter_count(st, d_ids_, n, f->d_ids, f->ids.size(), f->d_counts, f->d_counts + FILTER_COUNTS_MAX));
+        uint32_t m = 0;
+        VL_HIP(hipMemcpyAsync(&m, f->d_counts + FILTER_COUNTS_MAX, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipStreamSynchronize(st));
+        if (m > n) {
+            set_last_error("filter resolution counted more rows than the index holds (kernel bug)");
+            return ERR_DEVICE;
+        }
+        if (m > f->plist_cap) {
+            if (f->d_plist) (void)hipFree(f->d_plist);
+            f->d_plist = nullptr;
+            f->plist_cap = 0;
+            VL_TRY(dev_alloc(&f->d_plist, m));
+            f->plist_cap = m;
+        }
+        if (m) {
+            VL_HIP(launch_filter_compact(st, d_ids_, n, f->d_ids, f->ids.size(), f->d_counts, m, f->d_plist));
+            VL_HIP(hipStreamSynchronize(st));
+        }
+        f->m = m;
+    }
+    f->resolved_at = mutations_;
+    return OK;
+}
+
+int GpuFlatIndex::search_filtered(uint64_t token, const double* query, uint64_t q_len, uint64_t k, int metric,
+                                  uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n) const
+{
+    if (!out_n) return ERR_INVALID_ARG;
+    *out_n = 0;
+    std::shared_ptr<IdFilter> f = find_filter(token);
+    if (!f) {
+        set_last_error("unknown or destroyed filter");
+        return ERR_INVALID_ARG;
+    }
+    if (metric < 0 || metric > 3) {
+        set_last_error("unknown metric");
+        return ERR_INVALID_ARG;
+    }
+    std::shared_lock<RwLock> lk(mu_);  // readers share it; every writer waits: the resolved list cannot move under the search
+    const uint64_t n = ids_.size();
+    if (n != 0 && q_len != dim_) {  // the whole index's check, even when the subset is empty
+        set_dim_mismatch(dim_, q_len);
+        set_last_error("Dimension mismatch: expected " + std::to_string(dim_) + ", got " + std::to_string(q_len));
+        return ERR_DIM_MISMATCH;
+    }
+    if (n == 0 || k == 0) return OK;
+    if ((!query && dim_) || !out_scores) return ERR_INVALID_ARG;
+
+    VL_HIP(hipSetDevice(device_));
+    Workspace* ws = acquire_ws();
+    if (!ws) return ERR_DEVICE;
+    int rc = OK;
+    {
+        std::lock_guard<std::mutex> fg(f->mu);
+        if (f->resolved_at != mutations_) rc = resolve_filter(ws, f.get());
+    }
+    // from here on the list is read only: a reader that finds it current leaves it alone, and writers are shut out
+    if (rc == OK && f->m != 0) {
+        active_searches_.fetch_add(1, std::memory_order_relaxed);
+        rc = search_subset(ws, f.get(), query, std::min<uint64_t>(k, f->m), metric, out_pos, out_ids, out_scores, out_n);
+        active_searches_.fetch_sub(1, std::memory_order_relaxed);
+    }
+    if (rc != OK) (void)hipStreamSynchronize(ws->stream);
+    release_ws(ws);
+    return rc;
+}
+
+int GpuFlatIndex::search_subset(Workspace* ws, IdFilter* f, const double* query, uint64_t k_eff, int metric,
+                                uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n) const
+{
+    const uint64_t n = ids_.size();
+    const uint64_t m = f->m;
+    const uint32_t* plist = f->d_plist;
+    hipStream_t st = ws->stream;
+
+    // the query staged as search_locked stages it: pinned f64 values, then the norm
+    double qq = 0.0, qmax = 0.0;
+    bool q_finite = true;
+    for (uint64_t i = 0; i < dim_; ++i) {
+        const double v = query[i];
+        ws->h_q64[i] = v;
+        qq += v * v;
+        const double av = std::fabs(v);
+        if (!(av <= 1.797693134862315708e308)) q_finite = false;
+        if (av > qmax) qmax = av;
+    }
+    const double q_norm = std::sqrt(qq);
+    const bool q_in_domain = q_finite && qmax <= DOMAIN_MAX_ABS && (q_norm == 0.0 || q_norm >= DOMAIN_MIN_NORM);
+    ws->h_q64[dim_] = q_norm;
+    bool q_on_device = false;
+    auto q_to_device = [&]() -> int {
+        if (!q_on_device) {
+            VL_HIP(hipMemcpyAsync(ws->d_q64, ws->h_q64, (dim_ + 1) * sizeof(double), hipMemcpyHostToDevice, st));
+            q_on_device = true;
+        }
+        return OK;
+    };
+
+    // the fast path's conditions are search_locked's; the out-of-domain count is the whole index's (conservative)
+    const bool fast_ok = force_path_.load() == 0 && k_eff <= (uint64_t)KFAST_MAX && n_out_of_domain_ == 0 && q_in_domain;
+    if (fast_ok) {
+        const bool prof = profile_.load();
+        ScanPlan plan;
+        const bool qarg = scan_subset_takes_qarg(ld_);
+        const float* q32 = nullptr;
+        if (qarg) {
+            if (ws->q32.size() < ld_) ws->q32.assign(ld_, 0.0f);
+            for (uint64_t i = 0; i < dim_; ++i) ws->q32[i] = (float)query[i];  // nearest even, like load_q4 on the device
+            q32 = ws->q32.data();
+        } else {
+            VL_TRY(q_to_device());
+        }
+        const double* fq = q_on_device ? ws->d_q64 : ws->h_q64;
+        uint32_t seq = ++ws->seq;
+        if (seq == 0) seq = ++ws->seq;
+        ws->h_result->seq = 0;
+        if (prof) VL_HIP(hipEventRecord(ws->ev0, st));
+        VL_HIP(launch_scan_subset(st, metric, d_slab_, d_inv_norm_, plist, m, ws->d_q64, (uint32_t)dim_, ld_, ws->d_partials,
+                                  &plan, q32));
+        if (prof) VL_HIP(hipEventRecord(ws->ev1, st));
+        // n_rows = m: the bound check and the "a list of every row" rule are about the subset (every row left out of the
+        // lists is a subset row with a key at or below the 64th; rows outside the subset are no part of the answer)
+        VL_HIP(launch_merge_finalize(st, metric, ws->d_partials, plan.grid, 1, d_master_, fq, fq + dim_, (uint32_t)dim_, m,
+                                     (uint32_t)k_eff, max_row_norm_, ws->h_result, 0.0, seq));
+        last_scan_variant_.store(plan.variant, std::memory_order_relaxed);
+        last_scan_grid_.store(plan.grid, std::memory_order_relaxed);
+        last_scan_qarg_.store(qarg ? 1 : 0, std::memory_order_relaxed);
+        VL_TRY(wait_result(ws, seq));
+        if (prof) {
+            float ms = 0.f;
+            hipError_t pe = hipEventElapsedTime(&ms, ws->ev0, ws->ev1);
+            if (pe == hipErrorNotReady) {
+                VL_HIP(hipEventSynchronize(ws->ev1));
+                pe = hipEventElapsedTime(&ms, ws->ev0, ws->ev1);
+            }
+            VL_HIP(pe);
+            std::lock_guard<std::mutex> g(prof_mu_);
+            prof_n_ += 1;
+            prof_ms_ += ms;
+            // the rows read, the position list, and 1/|row| for cosine
+            prof_bytes_ += m * ((uint64_t)ld_ * sizeof(float) + sizeof(uint32_t) + (metric == COSINE ? sizeof(float) : 0));
+        }
+        const SearchResultBlock& r = *ws->h_result;
+        if (!(r.flags & RESULT_NEEDS_EXACT) && r.n_out == k_eff) {
+            for (uint64_t i = 0; i < k_eff; ++i) {
+                const uint32_t p = r.pos[i];
+                if (p >= n) {
+                    set_last_error("filtered fast path returned an out-of-range position (kernel bug)");
+                    return ERR_DEVICE;
+                }
+                if (out_pos) out_pos[i] = p;
+                if (out_ids) out_ids[i] = ids_[p];
+                out_scores[i] = r.score[i];
+            }
+            *out_n = k_eff;
+            set_last_path(PATH_FAST);
+            return OK;
+        }
+        // ties at the cut or a failed bound: the exact kernels over the subset
+    }
+
+    std::vector<uint32_t> idx;
+    std::vector<double> scores;
+    VL_TRY(q_to_device());
+    VL_TRY(run_exact(ws, metric, m, k_eff, &idx, &scores, plist));
+    {
+        std::lock_guard<std::mutex> fg(f->mu);
+        if (!f->h_plist_valid) {  // one copy of the list per resolution, on the first exact answer that needs it
+            f->h_plist.resize(m);
+            VL_HIP(hipMemcpyAsync(f->h_plist.data(), plist, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            VL_HIP(hipStreamSynchronize(st));
+            f->h_plist_valid = true;
+        }
+    }
+    for (uint64_t i = 0; i < k_eff; ++i) {
+        const uint32_t p = idx[i] < m ? f->h_plist[idx[i]] : POS_SENTINEL;
+        if (p >= n) {
+            set_last_error("filtered exact path returned an out-of-range position (kernel bug)");
+            return ERR_DEVICE;
+        }
+        if (out_pos) out_pos[i] = p;
+        if (out_ids) out_ids[i] = ids_[p];
+        out_scores[i] = scores[i];
+    }
+    *out_n = k_eff;
     return OK;
 }
 

@@ -112,6 +112,25 @@ struct WorkspacePool {
     size_t users = 0;
 };
 
+// An id filter of one single-GPU flat handle (vl_index_filter_create): the caller's ids, sorted and deduplicated, and -- resolved
+// against the rows as they stood when the handle's mutation count was `resolved_at` -- the ascending storage positions of
+// every row whose id is in the set.  A search that finds the count moved on resolves it again first.
+struct IdFilter {
+    std::mutex mu;                         // guards everything below (taken after the index lock)
+    int device = 0;
+    std::vector<uint64_t> ids;             // sorted, unique
+    unsigned long long* d_ids = nullptr;   // the same on the device
+    uint32_t* d_counts = nullptr;          // [FILTER_COUNTS_MAX + 1] resolution scratch: per-chunk offsets, then m
+    uint32_t* d_plist = nullptr;           // [plist_cap] positions of the qualifying rows, ascending
+    uint64_t plist_cap = 0;
+    uint64_t m = 0;                        // qualifying rows
+    uint64_t resolved_at = ~0ull;          // the handle's mutation count the list belongs to (none yet)
+    std::vector<uint32_t> h_plist;         // host copy of the list (the exact path maps its winners back), made on demand
+    bool h_plist_valid = false;
+
+    ~IdFilter();
+};
+
 class GpuFlatIndex {
 public:
     struct CoalesceReq {  // one caller waiting in search_coalesced()
@@ -163,6 +182,14 @@ public:
     // caller then builds the record on the host as before.  Word 0..3 of the record (status, len, dim) are the caller's.
     int search_batch_to_record(const double* queries, bool queries_on_device, uint64_t nq, uint64_t q_len, uint64_t ks,
                                int metric, uint64_t row_offset, unsigned long long* d_record, bool* handled) const;
+    // NEW (no reference counterpart): search restricted to the rows whose id is in a set.  The answer is exactly what
+    // FlatIndex::search returns on a FlatIndex holding only those rows, in their storage order.  A filter is a token of this
+    // handle (never 0, never reused); ids may be unsorted and repeat; ids the index does not hold are ignored.
+    int filter_create(const uint64_t* ids, uint64_t n_ids, uint64_t* out_token, uint64_t* out_rows);
+    int filter_rows(uint64_t token, uint64_t* out_rows) const;  // resolves the filter again if rows changed since
+    int filter_destroy(uint64_t token);
+    int search_filtered(uint64_t token, const double* query, uint64_t q_len, uint64_t k, int metric, uint64_t* out_pos,
+                        uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;
     uint64_t len() const;
     bool is_empty() const { return len() == 0; }
     uint64_t dimension() const { return dim_; }
@@ -259,8 +286,13 @@ private:
     void bf16_outcome(bool certified) const;  // records one try of the bf16 filter
     bool i8_first(uint64_t n) const;          // does this single search try the int8 filter first
     void i8_outcome(bool certified) const;    // records one try of the int8 filter
+    // plist != nullptr: the n rows are plist[0..n) (a filter's subset) and pos[] returns indices into that list
     int run_exact(Workspace* ws, int metric, uint64_t n, uint64_t k_eff, std::vector<uint32_t>* pos,
-                  std::vector<double>* scores) const;
+                  std::vector<double>* scores, const uint32_t* plist = nullptr) const;
+    std::shared_ptr<IdFilter> find_filter(uint64_t token) const;
+    int resolve_filter(Workspace* ws, IdFilter* f) const;  // mu_ held (shared or unique), f->mu held
+    int search_subset(Workspace* ws, IdFilter* f, const double* query, uint64_t k_eff, int metric, uint64_t* out_pos,
+                      uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;  // mu_ held (shared), f resolved
     int wait_result(Workspace* ws, uint32_t seq) const;
     int ensure_i8_slab() const;  // lazily builds the int8 copy the single-query int8 filter streams
     int ensure_bf16_slab(bool frag_major) const;  // lazily builds the bf16 slab (row-major, or MFMA fragment order) a filter streams
@@ -307,6 +339,7 @@ private:
 
     // host bookkeeping
     std::vector<uint64_t> ids_;        // position -> id (insertion order)
+    uint64_t mutations_ = 0;           // changes of ids_ or of the row order so far (an id filter's staleness test)
     std::vector<uint8_t> row_flags_;   // position -> ROW_* flags
     uint64_t n_out_of_domain_ = 0;
     double max_row_norm_ = 0.0;        // upper bound over in-domain rows ever stored
@@ -319,6 +352,9 @@ private:
     WorkspacePool* ws_pool_ = nullptr;
 
     mutable Coalescer<CoalesceReq> co_;
+
+    mutable std::mutex filters_mu_;  // the filter table; never held while an index lock or a filter's mutex is taken
+    std::unordered_map<uint64_t, std::shared_ptr<IdFilter>> filters_;
 
     std::atomic<int> force_path_{0};
     std::atomic<int> single_filter_{FILTER_AUTO};

@@ -259,6 +259,237 @@ __global__ __launch_bounds__(256) void k_scan_generic(const f32x4* __restrict__ 
     }
 }
 
+// K1 over a subset: the rows are plist[0..m) (ascending storage positions, an id filter's resolution).  The same per-row
+// arithmetic as scan_body -- acc4 in column order, group_reduce, scan_key -- so a row's key is the one k_scan gives it; the
+// list entries carry STORAGE positions and reach offer() in ascending order within each wave's stream, as in k_scan.
+// A separate body (scan_body is the headline kernel's and stays as it is): the only difference is the row index, which is
+// one dependent read away -- the list entries of the NEXT iteration are requested before this iteration's row loads, so
+// that read is in flight while the rows stream and never stands alone in front of them.
+template <int METRIC, int G, int VPL, int U>
+__device__ __forceinline__ void scan_subset_body(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
+                                                 const uint32_t* __restrict__ plist, const f32x4 (&qv)[VPL], uint32_t m,
+                                                 Cand32* __restrict__ out)
+{
+    constexpr int RPS = WAVE / G;
+    constexpr uint32_t LD4 = G * VPL;
+    __shared__ Cand32 sh[4 * WAVE];
+
+    const int lane = lane_id();
+    const int wave = threadIdx.x >> 6;
+    const int g = lane / G, c = lane % G;
+
+    const uint32_t n_steps = (m + RPS - 1) / RPS;
+    const uint32_t n_waves = gridDim.x * 4;
+    const uint32_t wave_global = blockIdx.x * 4 + wave;
+    const uint32_t stride = n_waves * U;
+
+    TopList<float> L;
+    L.init();
+
+    uint32_t pn[U];
+    bool vn[U];
+    auto fetch = [&](uint32_t s0) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t s = s0 + (uint32_t)u * n_waves;
+            const uint32_t i = s < n_steps ? s * RPS + g : m;  // m marks "no row"
+            vn[u] = i < m;
+            pn[u] = plist[i < m ? i : m - 1];  // clamp: the load stays in bounds
+        }
+    };
+    fetch(wave_global);
+    for (uint32_t s0 = wave_global; s0 < n_steps; s0 += stride) {
+        uint32_t pos[U];
+        bool valid[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            pos[u] = pn[u];
+            valid[u] = vn[u];
+        }
+        fetch(s0 + stride);
+        __builtin_amdgcn_sched_barrier(0);  // the list loads go out in front of the row loads
+        f32x4 x[U][VPL];
+        float inv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const f32x4* p = slab + (size_t)pos[u] * LD4 + c;
+#pragma unroll
+            for (int j = 0; j < VPL; ++j) x[u][j] = __builtin_nontemporal_load(p + G * j);
+            inv[u] = 1.0f;
+            if (METRIC == COSINE) inv[u] = inv_norm[pos[u]];
+        }
+        __builtin_amdgcn_sched_barrier(0);  // every row load of this iteration is issued before the first FMA
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float a = 0.0f;
+#pragma unroll
+            for (int j = 0; j < VPL; ++j) a = acc4<METRIC>(a, x[u][j], qv[j]);
+            a = group_reduce<G>(a);
+            const float key = scan_key<METRIC>(a, inv[u]);
+            L.offer(key, pos[u], valid[u] && c == 0);
+        }
+    }
+
+    block_merge<float, Cand32, 4>(L, sh);
+    if (wave == 0) {
+        Cand32 e;
+        e.key = L.key;
+        e.pos = L.pos;
+        out[(size_t)blockIdx.x * KP + lane] = e;
+    }
+}
+
+// the kernel-argument query (k_scan's form)
+template <int METRIC, int G, int VPL, int U>
+__global__ __launch_bounds__(256) void k_scan_subset(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
+                                                     const uint32_t* __restrict__ plist, uint32_t m, Cand32* __restrict__ out,
+                                                     const ScanQArg qa)
+{
+    static_assert(G * VPL * 4 <= SCAN_QARG_FLOATS, "row too long for the kernarg query");
+    const int c = lane_id() % G;
+    f32x4 qv[VPL];
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) qv[j] = *reinterpret_cast<const f32x4*>(&qa.v[4 * (c + G * j)]);
+    scan_subset_body<METRIC, G, VPL, U>(slab, inv_norm, plist, qv, m, out);
+}
+
+// the f64 query in device memory (k_scan_q64's form: strides past the kernarg query)
+template <int METRIC, int G, int VPL, int U>
+__global__ __launch_bounds__(256) void k_scan_subset_q64(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
+                                                         const uint32_t* __restrict__ plist, const double* __restrict__ q64,
+                                                         uint32_t dim, uint32_t m, Cand32* __restrict__ out)
+{
+    const int c = lane_id() % G;
+    f32x4 qv[VPL];
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) qv[j] = load_q4(q64, c + G * j, dim);
+    scan_subset_body<METRIC, G, VPL, U>(slab, inv_norm, plist, qv, m, out);
+}
+
+// Generic subset scan: any ld4, G lanes per row (k_scan_generic's arithmetic and order).
+template <int METRIC, int G>
+__global__ __launch_bounds__(256) void k_scan_subset_generic(const f32x4* __restrict__ slab,
+                                                             const float* __restrict__ inv_norm,
+                                                             const uint32_t* __restrict__ plist,
+                                                             const double* __restrict__ q64, uint32_t dim, uint32_t m,
+                                                             uint32_t ld4, Cand32* __restrict__ out)
+{
+    constexpr int RPS = WAVE / G;
+    __shared__ Cand32 sh[4 * WAVE];
+
+    const int lane = lane_id();
+    const int wave = threadIdx.x >> 6;
+    const int g = lane / G, c = lane % G;
+
+    const uint32_t n_steps = (m + RPS - 1) / RPS;
+    const uint32_t n_waves = gridDim.x * 4;
+
+    TopList<float> L;
+    L.init();
+
+    uint32_t s = blockIdx.x * 4 + wave;
+    uint32_t i_next = s < n_steps ? s * RPS + g : m;
+    uint32_t p_next = plist[i_next < m ? i_next : m - 1];
+    for (; s < n_steps; s += n_waves) {
+        const bool valid = i_next < m;
+        const uint32_t r = p_next;
+        const uint32_t sn = s + n_waves;
+        i_next = sn < n_steps ? sn * RPS + g : m;
+        p_next = plist[i_next < m ? i_next : m - 1];  // next row's list entry, in flight during this row
+        const f32x4* p = slab + (size_t)r * ld4;
+        float a = 0.0f;
+        for (uint32_t j = c; j < ld4; j += G) a = acc4<METRIC>(a, p[j], load_q4(q64, j, dim));
+        a = group_reduce<G>(a);
+        float inv = 1.0f;
+        if (METRIC == COSINE) inv = inv_norm[r];
+        L.offer(scan_key<METRIC>(a, inv), r, valid && c == 0);
+    }
+
+    block_merge<float, Cand32, 4>(L, sh);
+    if (wave == 0) {
+        Cand32 e;
+        e.key = L.key;
+        e.pos = L.pos;
+        out[(size_t)blockIdx.x * KP + lane] = e;
+    }
+}
+
+// Resolution of an id filter: which storage positions hold an id of the sorted, deduplicated set fids[0..nf).  Workgroup b
+// owns positions [b chunk, (b+1) chunk); pass 1 counts its matches, one workgroup turns the counts into offsets (and m), pass 2
+// writes the matching positions of each chunk in ascending order at its offset: the list comes out ascending.
+__device__ __forceinline__ bool id_in_set(unsigned long long id, const unsigned long long* __restrict__ fids, uint32_t nf)
+{
+    uint32_t lo = 0, hi = nf;  // lower_bound
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (fids[mid] < id) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < nf && fids[lo] == id;
+}
+
+constexpr int FILTER_MAX_GRID = FILTER_COUNTS_MAX;
+
+__global__ __launch_bounds__(256) void k_filter_count(const unsigned long long* __restrict__ pos_ids, uint32_t n,
+                                                      const unsigned long long* __restrict__ fids, uint32_t nf,
+                                                      uint32_t chunk, uint32_t* __restrict__ counts)
+{
+    __shared__ uint32_t sh_cnt[4];
+    const uint32_t lo = blockIdx.x * chunk;
+    const uint32_t hi = (uint64_t)lo + chunk < n ? lo + chunk : n;
+    uint32_t cnt = 0;
+    for (uint32_t p = lo + threadIdx.x; p < hi; p += 256) cnt += id_in_set(pos_ids[p], fids, nf) ? 1u : 0u;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if (lane_id() == 0) sh_cnt[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = sh_cnt[0] + sh_cnt[1] + sh_cnt[2] + sh_cnt[3];
+}
+
+// exclusive scan of the nb <= FILTER_MAX_GRID counts in place; total -> *m_out
+__global__ __launch_bounds__(FILTER_MAX_GRID) void k_filter_scan(uint32_t* __restrict__ counts, uint32_t nb,
+                                                                 uint32_t* __restrict__ m_out)
+{
+    __shared__ uint32_t sh[FILTER_MAX_GRID];
+    const uint32_t t = threadIdx.x;
+    sh[t] = t < nb ? counts[t] : 0u;
+    __syncthreads();
+    for (uint32_t o = 1; o < FILTER_MAX_GRID; o <<= 1) {  // Hillis-Steele inclusive scan
+        const uint32_t v = t >= o ? sh[t - o] : 0u;
+        __syncthreads();
+        sh[t] += v;
+        __syncthreads();
+    }
+    if (t < nb) counts[t] = t ? sh[t - 1] : 0u;
+    if (t == FILTER_MAX_GRID - 1) *m_out = sh[t];
+}
+
+__global__ __launch_bounds__(256) void k_filter_compact(const unsigned long long* __restrict__ pos_ids, uint32_t n,
+                                                        const unsigned long long* __restrict__ fids, uint32_t nf,
+                                                        uint32_t chunk, const uint32_t* __restrict__ offsets,
+                                                        uint32_t m_cap, uint32_t* __restrict__ plist)
+{
+    __shared__ uint32_t sh_cnt[4];
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const uint32_t lo = blockIdx.x * chunk;
+    const uint32_t hi = (uint64_t)lo + chunk < n ? lo + chunk : n;
+    uint32_t base = offsets[blockIdx.x];
+    for (uint32_t t0 = lo; t0 < hi; t0 += 256) {  // block-uniform trip count
+        const uint32_t p = t0 + threadIdx.x;
+        const bool hit = p < hi && id_in_set(pos_ids[p], fids, nf);
+        const unsigned long long bal = __ballot(hit);
+        if (lane == 0) sh_cnt[wave] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t before = 0;
+        for (int w = 0; w < wave; ++w) before += sh_cnt[w];
+        const uint32_t total = sh_cnt[0] + sh_cnt[1] + sh_cnt[2] + sh_cnt[3];
+        const uint32_t rank = before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        if (hit && base + rank < m_cap) plist[base + rank] = p;
+        base += total;
+        __syncthreads();  // sh_cnt is rewritten by the next tile
+    }
+}
+
 // K3: small-batch scan.  One pass over the slab serves QB queries: each row group is loaded ONCE into
 // registers and scored against QB queries whose f32 copies sit in LDS (lanes that share a column read
 // the same 16 bytes: an LDS broadcast).  Per wave, QB independent top-64 lists.  Still streams
@@ -1026,6 +1257,78 @@ __global__ __launch_bounds__(256) void k_exact_scan(const double* __restrict__ m
     }
 }
 
+// k_exact_scan over a subset: scores[i] = the reference score of row plist[i], i < m.  The same tile walk and the same
+// Acc64 steps (separate multiply and add, index order); only a tile row's source is plist[row0 + r] instead of row0 + r.
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_exact_scan_subset(const double* __restrict__ master,
+                                                           const double* __restrict__ q64,
+                                                           const uint32_t* __restrict__ plist, uint64_t m, uint32_t dim,
+                                                           double* __restrict__ scores, uint32_t* __restrict__ nan_flag)
+{
+    __shared__ double tile[EX_ROWS][EX_CH + 1];
+    __shared__ double qtile[EX_CH];
+    const int tid = threadIdx.x;
+    const uint64_t n_tiles = (m + EX_ROWS - 1) / EX_ROWS;
+    const uint32_t n_chunks = (dim + EX_CH - 1) / EX_CH;
+    for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const uint64_t row0 = t * EX_ROWS;
+        const uint64_t rows_here = (m - row0) < (uint64_t)EX_ROWS ? (m - row0) : (uint64_t)EX_ROWS;
+        // the storage rows this thread fetches from (the same for every chunk)
+        uint64_t src[EX_CH];
+#pragma unroll
+        for (int i = 0; i < EX_CH; ++i) {
+            uint64_t r = (uint64_t)((tid + i * 256) / EX_CH);
+            r = r < rows_here ? r : rows_here - 1;
+            src[i] = (uint64_t)plist[row0 + r] * dim;
+        }
+        Acc64<METRIC> A;
+        A.init();
+        double pre[EX_CH];
+        double qpre = 0.0;
+        auto fetch = [&](uint32_t c0) {
+            const uint32_t cw = (dim - c0) < (uint32_t)EX_CH ? (dim - c0) : (uint32_t)EX_CH;
+#pragma unroll
+            for (int i = 0; i < EX_CH; ++i) {
+                uint32_t cc = (uint32_t)((tid + i * 256) % EX_CH);
+                cc = cc < cw ? cc : cw - 1;
+                pre[i] = master[src[i] + c0 + cc];
+            }
+            {
+                uint32_t qc = (uint32_t)(tid % EX_CH);
+                qc = qc < cw ? qc : cw - 1;
+                qpre = q64[c0 + qc];
+            }
+        };
+        fetch(0);
+        for (uint32_t ch = 0; ch < n_chunks; ++ch) {
+            const uint32_t c0 = ch * EX_CH;
+            const uint32_t cw = (dim - c0) < (uint32_t)EX_CH ? (dim - c0) : (uint32_t)EX_CH;
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < EX_CH; ++i) {
+                const int idx = tid + i * 256;
+                tile[idx / EX_CH][idx % EX_CH] = pre[i];
+            }
+            if (tid < EX_CH) qtile[tid] = qpre;
+            __syncthreads();
+            if (ch + 1 < n_chunks) fetch(c0 + EX_CH);
+            if ((uint64_t)tid < rows_here) {
+                if (cw == (uint32_t)EX_CH) {
+#pragma unroll
+                    for (uint32_t cc = 0; cc < (uint32_t)EX_CH; ++cc) A.step(tile[tid][cc], qtile[cc]);
+                } else {
+                    for (uint32_t cc = 0; cc < cw; ++cc) A.step(tile[tid][cc], qtile[cc]);
+                }
+            }
+        }
+        if ((uint64_t)tid < rows_here) {
+            const double sc = A.score();
+            scores[row0 + tid] = sc;
+            if (sc != sc) atomicOr(nan_flag, 1u);
+        }
+    }
+}
+
 // top-64 of scores[] by (score desc, pos asc): per-wave lists, then per-workgroup merge
 // `after` (optional): the result block of the previous round; only rows ranked strictly behind its last
 // entry are offered, so round r yields ranks 64 r .. 64 r + 63 of the full (score desc, pos asc) order.
@@ -1734,6 +2037,134 @@ hipError_t launch_exact_scan(hipStream_t s, int metric, const double* master, co
         hipLaunchKernelGGL((k_exact_scan<MM>), dim3(grid), dim3(256), 0, s, master, q64, n, dim, scores, nan_flag);
         return hipGetLastError();
     });
+}
+
+hipError_t launch_exact_scan_subset(hipStream_t s, int metric, const double* master, const double* q64, const uint32_t* plist,
+                                    uint64_t m, uint32_t dim, double* scores, uint32_t* nan_flag)
+{
+    if (m == 0) return hipSuccess;
+    const uint64_t tiles = (m + EX_ROWS - 1) / EX_ROWS;
+    const int grid = (int)(tiles < 4096 ? tiles : 4096);
+    return dispatch_metric(metric, [&](auto M) -> hipError_t {
+        constexpr int MM = decltype(M)::value;
+        hipLaunchKernelGGL((k_exact_scan_subset<MM>), dim3(grid), dim3(256), 0, s, master, q64, plist, m, dim, scores, nan_flag);
+        return hipGetLastError();
+    });
+}
+
+// The subset scan's shapes: for every stride VL_SCAN_VARIANTS specialises, its default entry (the first one with that
+// G * VPL, the shape k_scan runs unless a tuning variable picks another), so that a row's key is k_scan's; other strides
+// take the generic kernel with k_scan_generic's lanes per row.
+#define VL_SUBSET_VARIANTS(X) X(8, 4, 3, 3) X(8, 8, 2, 3) X(8, 12, 1, 3) X(8, 16, 1, 3) X(16, 12, 1, 3) X(16, 16, 1, 3) X(16, 24, 1, 2)
+
+bool scan_subset_takes_qarg(uint32_t ld)
+{
+    if ((ld & 3) || ld > (uint32_t)SCAN_QARG_FLOATS) return false;
+    bool special = false;
+#define VL_CHK(G, VPL, U, BPC) special = special || (uint32_t)(G * VPL) == ld / 4;
+    VL_SUBSET_VARIANTS(VL_CHK)
+#undef VL_CHK
+    return special;
+}
+
+hipError_t launch_scan_subset(hipStream_t s, int metric, const float* slab, const float* inv_norm, const uint32_t* plist,
+                              uint64_t m, const double* q64, uint32_t dim, uint32_t ld, Cand32* partials, ScanPlan* plan,
+                              const float* q32_host)
+{
+    if (m == 0 || m >= 0xFFFFFFFFull || (ld & 3)) return hipErrorInvalidValue;
+    const uint32_t ld4 = ld / 4;
+    const f32x4* slab4 = reinterpret_cast<const f32x4*>(slab);
+    const uint32_t m32 = (uint32_t)m;
+    ScanShape sh{false, lanes_per_row(ld4), 0, 1, 4};
+#define VL_PICK(G, VPL, U, BPC) \
+    if (!sh.special && (uint32_t)(G * VPL) == ld4) sh = ScanShape{true, G, VPL, U, BPC};
+    VL_SUBSET_VARIANTS(VL_PICK)
+#undef VL_PICK
+    const bool qarg = q32_host != nullptr && sh.special && ld <= (uint32_t)SCAN_QARG_FLOATS;
+    if (!qarg && !q64) return hipErrorInvalidValue;
+    int grid = 0;
+    hipError_t rc = dispatch_metric(metric, [&](auto M) -> hipError_t {
+        constexpr int MM = decltype(M)::value;
+        if (sh.special) {
+            bool launched = false;
+#define VL_SUBSET_TRY(G, VPL, U, BPC)                                                                                  \
+    if (!launched && sh.g == G && sh.vpl == VPL && sh.u == U) {                                                    \
+        if constexpr (G * VPL * 4 <= SCAN_QARG_FLOATS) {                                                            \
+            if (qarg) {                                                                                             \
+                auto kern = k_scan_subset<MM, G, VPL, U>;                                                           \
+                grid = scan_grid(m, sh, reinterpret_cast<const void*>(kern));                                       \
+                ScanQArg qa;                                                                                        \
+                memcpy(qa.v, q32_host, (size_t)ld * sizeof(float));                                                 \
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, slab4, inv_norm, plist, m32, partials, qa);   \
+                launched = true;                                                                                    \
+            }                                                                                                       \
+        } else {                                                                                                    \
+            auto kern = k_scan_subset_q64<MM, G, VPL, U>;                                                           \
+            grid = scan_grid(m, sh, reinterpret_cast<const void*>(kern));                                           \
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, slab4, inv_norm, plist, q64, dim, m32, partials); \
+            launched = true;                                                                                        \
+        }                                                                                                           \
+    }
+            VL_SUBSET_VARIANTS(VL_SUBSET_TRY)
+#undef VL_SUBSET_TRY
+            if (!launched) return hipErrorInvalidValue;  // a kernarg-sized stride always comes with its query there
+        } else {
+#define VL_SUBSET_GEN(G)                                                                                               \
+    case G: {                                                                                                          \
+        auto kern = k_scan_subset_generic<MM, G>;                                                                      \
+        grid = scan_grid(m, sh, reinterpret_cast<const void*>(kern));                                                  \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, slab4, inv_norm, plist, q64, dim, m32, ld4, partials);   \
+    } break;
+            switch (sh.g) {
+                VL_SUBSET_GEN(1)
+                VL_SUBSET_GEN(2)
+                VL_SUBSET_GEN(4)
+                VL_SUBSET_GEN(8)
+                VL_SUBSET_GEN(16)
+                VL_SUBSET_GEN(32)
+                VL_SUBSET_GEN(64)
+            default: return hipErrorInvalidValue;
+            }
+#undef VL_SUBSET_GEN
+        }
+        return hipGetLastError();
+    });
+    if (plan) {
+        plan->grid = grid;
+        plan->variant = sh.special ? (SUBSET_VARIANT_BASE + sh.g * 10000 + sh.vpl * 100 + sh.u) : -(SUBSET_VARIANT_BASE + sh.g);
+    }
+    return rc;
+}
+
+int filter_grid_for(uint64_t n, uint32_t* chunk)
+{
+    // at least 4 tiles of 256 positions per workgroup, at most FILTER_MAX_GRID workgroups
+    uint64_t c = (n + FILTER_MAX_GRID - 1) / FILTER_MAX_GRID;
+    if (c < 1024) c = 1024;
+    *chunk = (uint32_t)c;
+    return (int)((n + c - 1) / c);
+}
+
+hipError_t launch_filter_count(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
+                               uint64_t nf, uint32_t* counts, uint32_t* m_out)
+{
+    if (n == 0 || n >= 0xFFFFFFFFull || nf == 0 || nf >= 0xFFFFFFFFull) return hipErrorInvalidValue;
+    uint32_t chunk = 0;
+    const int grid = filter_grid_for(n, &chunk);
+    hipLaunchKernelGGL(k_filter_count, dim3(grid), dim3(256), 0, s, pos_ids, (uint32_t)n, fids, (uint32_t)nf, chunk, counts);
+    hipLaunchKernelGGL(k_filter_scan, dim3(1), dim3(FILTER_MAX_GRID), 0, s, counts, (uint32_t)grid, m_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_filter_compact(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
+                                 uint64_t nf, const uint32_t* offsets, uint64_t m, uint32_t* plist)
+{
+    if (n == 0 || n >= 0xFFFFFFFFull || nf == 0 || nf >= 0xFFFFFFFFull || m == 0) return hipErrorInvalidValue;
+    uint32_t chunk = 0;
+    const int grid = filter_grid_for(n, &chunk);
+    hipLaunchKernelGGL(k_filter_compact, dim3(grid), dim3(256), 0, s, pos_ids, (uint32_t)n, fids, (uint32_t)nf, chunk, offsets,
+                       (uint32_t)m, plist);
+    return hipGetLastError();
 }
 
 int select_grid_for(uint64_t n)

@@ -154,6 +154,27 @@ hipError_t launch_scan_batch(hipStream_t s, int metric, const float* slab, const
 // Exact path: reference-order f64 score of every row.
 hipError_t launch_exact_scan(hipStream_t s, int metric, const double* master, const double* q64, uint64_t n,
                              uint32_t dim, double* scores, uint32_t* nan_flag);
+// Search restricted to an id filter: the rows are plist[0..m), ascending storage positions.
+// K1 over the subset: the same partial lists as launch_scan (positions are storage positions, the keys k_scan's), on a grid
+// sized from m.  q32_host != nullptr and scan_subset_takes_qarg(ld): the query in the kernel arguments, else q64 on the device.
+// plan->variant = SUBSET_VARIANT_BASE + G * 10000 + VPL * 100 + U, or -(SUBSET_VARIANT_BASE + G) for the generic kernel.
+constexpr int SUBSET_VARIANT_BASE = 3000000;
+bool scan_subset_takes_qarg(uint32_t ld);
+hipError_t launch_scan_subset(hipStream_t s, int metric, const float* slab, const float* inv_norm, const uint32_t* plist,
+                              uint64_t m, const double* q64, uint32_t dim, uint32_t ld, Cand32* partials, ScanPlan* plan,
+                              const float* q32_host = nullptr);
+// Exact path over the subset: scores[i] = reference f64 score of row plist[i].
+hipError_t launch_exact_scan_subset(hipStream_t s, int metric, const double* master, const double* q64, const uint32_t* plist,
+                                    uint64_t m, uint32_t dim, double* scores, uint32_t* nan_flag);
+// Resolution of an id filter against the position -> id table pos_ids[0..n): fids[0..nf) sorted, unique.  Step 1 counts the
+// matches per chunk of positions and turns the counts into offsets, *m_out = total (counts: FILTER_COUNTS_MAX words); step 2
+// writes the m matching positions in ascending order into plist[0..m).
+constexpr int FILTER_COUNTS_MAX = 1024;
+hipError_t launch_filter_count(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
+                               uint64_t nf, uint32_t* counts, uint32_t* m_out);
+hipError_t launch_filter_compact(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
+                                 uint64_t nf, const uint32_t* offsets, uint64_t m, uint32_t* plist);
+
 // Exact path, k <= KP: top-k of scores[] by (score desc, pos asc).
 int select_grid_for(uint64_t n);
 // Ranks 64 r .. 64 r + k - 1 of the exact order: `after` = the (full, k = 64) block of round r - 1, nullptr for r = 0.
