@@ -215,6 +215,26 @@ int vl_index_search_batch_filtered(const vl_index *h, uint64_t filter, const dou
                                    uint64_t k, int metric, uint64_t out_stride, uint64_t *out_ids, double *out_scores,
                                    uint64_t *out_n);
 
+/* NEW capability (the reference only answers "the best k"): every row that is at least this similar.  min_score is a
+ * score in the reference's sense (higher is better for all four metrics, src/lib.rs:425-572; Euclidean and Manhattan are
+ * 1 / (1 + d)).  The answer is the LONGEST PREFIX of FlatIndex::search(q, len, metric) (src/index/flat.rs:98-119) whose
+ * scores satisfy the IEEE comparison score >= min_score, ids and f64 scores bit for bit: order (score desc, storage
+ * position asc), rows that tie with the threshold are in, duplicate-id rows all count.  filter != 0 (a token of
+ * vl_index_filter_create): "the index" is the FlatIndex holding only the filter's rows in storage order; 0 = whole index.
+ * *out_total = rows that qualify, always; min(total, out_capacity) entries are written, the prefix of that ranking
+ * (vl_index_search_cap's rule), *out_n of them.  out_capacity = 0 with NULL outputs is a legal "count only" call.
+ * min_score = -inf returns the whole ranking; +inf, or anything above the best score, returns nothing with VL_OK; NaN is
+ * VL_ERR_INVALID_ARG.  Errors are vl_index_search's on the same handle and query (dimension check whenever len != 0,
+ * unknown metric); VL_ERR_NAN_SCORE exactly when search(q, len, metric) on the same (sub)index would return it.
+ * Single-GPU flat handles only: HNSW and vl_flat_create_multi handles return VL_ERR_INVALID_ARG.  Range calls never
+ * join a coalesced pass and read the f32 slab (no bf16 / int8 stage).  Other searches may run concurrently; add / delete
+ * exclude it through the handle's reader/writer lock.  vl_last_path: VL_PATH_FAST, or VL_PATH_EXACT_SORT when more rows
+ * pass the key-space threshold than the candidate buffer holds (2^20), data or query lie outside the fast-path domain,
+ * or a path is forced. */
+int vl_index_search_range(const vl_index *h, uint64_t filter, const double *query, uint64_t q_len, double min_score,
+                          int metric, uint64_t *out_ids, double *out_scores, uint64_t out_capacity, uint64_t *out_n,
+                          uint64_t *out_total);
+
 uint64_t vl_index_len(const vl_index *h);      /* len()       src/index/flat.rs:121-123 */
 int vl_index_is_empty(const vl_index *h);      /* is_empty()  src/index/flat.rs:125-127 */
 uint64_t vl_index_dimension(const vl_index *h);/* dimension() src/index/flat.rs:133-135 */

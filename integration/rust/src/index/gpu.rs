@@ -45,6 +45,7 @@ extern "C" {
     fn vl_index_filter_create(h: *mut vl_index, ids: *const u64, n_ids: u64, out_filter: *mut u64, out_rows: *mut u64) -> c_int;
     fn vl_index_filter_destroy(h: *mut vl_index, filter: u64) -> c_int;
     fn vl_index_search_filtered(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, k: u64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
+    fn vl_index_search_range(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, min_score: f64, metric: c_int, out_ids: *mut u64, out_scores: *mut f64, out_capacity: u64, out_n: *mut u64, out_total: *mut u64) -> c_int;
     fn vl_flat_create_multi(dim: u64, device_ids: *const c_int, n_dev: c_int, mode: c_int, out: *mut *mut vl_index) -> c_int;
     fn vl_index_len(h: *const vl_index) -> u64;
     fn vl_index_get_vector(h: *const vl_index, id: u64, out: *mut f64) -> c_int;
@@ -315,6 +316,41 @@ impl GpuFlatIndex {
             }
             VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
             _ => Err(VectorLiteError::InternalError(err)),
+        }
+    }
+
+    /// Every row whose score is at least `min_score` (no reference counterpart): the longest prefix of
+    /// `FlatIndex::search(query, len, metric)` whose scores satisfy `score >= min_score`, at most `limit` of them (None: all).
+    /// Returns the results and the number of rows that qualify.  Single-GPU handles only.
+    pub fn search_range(&self, query: &[f64], min_score: f64, metric: SimilarityMetric, limit: Option<usize>) -> VectorLiteResult<(Vec<SearchResult>, usize)> {
+        let mut cap = limit.unwrap_or(1024);
+        loop {
+            let (mut out_ids, mut scores, mut n, mut total) = (vec![0u64; cap.max(1)], vec![0f64; cap.max(1)], 0u64, 0u64);
+            let rc = unsafe {
+                vl_index_search_range(self.0.raw, 0, query.as_ptr(), query.len() as u64, min_score, metric_code(metric), out_ids.as_mut_ptr(), scores.as_mut_ptr(), cap as u64, &mut n, &mut total)
+            };
+            match rc {
+                VL_OK => {
+                    if limit.is_none() && total as usize > cap {
+                        cap = total as usize; // rows arrived since the count: ask again with room for all of them
+                        continue;
+                    }
+                    let results = (0..n as usize)
+                        .map(|i| {
+                            let (text, metadata) = self.0.side.get(&out_ids[i]).cloned().unwrap_or_default();
+                            SearchResult { id: out_ids[i], score: scores[i], text, metadata }
+                        })
+                        .collect();
+                    return Ok((results, total as usize));
+                }
+                VL_ERR_DIM_MISMATCH => {
+                    let (mut e, mut a) = (0u64, 0u64);
+                    unsafe { vl_last_dim_mismatch(&mut e, &mut a) };
+                    return Err(VectorLiteError::DimensionMismatch { expected: e as usize, actual: a as usize });
+                }
+                VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
+                _ => return Err(VectorLiteError::InternalError(last_error())),
+            }
         }
     }
 

@@ -233,6 +233,28 @@ def _make_filter(L, h, owner, ids) -> IdFilter:
     return IdFilter(owner, int(tok.value))
 
 
+def _search_range(L, h, query, min_score: float, metric: int, token: int, limit):
+    """vl_index_search_range -> (ids, scores, total).  limit=None: everything (the first call's buffers hold 1024 entries;
+    a larger total is fetched by a second call sized from the first one's count, repeated if rows arrived in between)."""
+    q = _f64(query).ravel()
+    cap = 1024 if limit is None else max(int(limit), 0)
+    while True:
+        ids = np.empty(max(cap, 1), dtype=np.uint64)
+        scores = np.empty(max(cap, 1), dtype=np.float64)
+        n, total = C.c_uint64(0), C.c_uint64(0)
+        rc = L.vl_index_search_range(h, int(token), q.ctypes.data, q.size, float(min_score), int(metric),
+                                     ids.ctypes.data if cap else None, scores.ctypes.data if cap else None, cap,
+                                     C.byref(n), C.byref(total))
+        if rc == VL_ERR_INVALID_ARG:
+            raise IndexOpError(_last_error())
+        _raise(rc)
+        if limit is None and total.value > cap:
+            cap = int(total.value)
+            continue
+        m = int(n.value)
+        return ids[:m].copy(), scores[:m].copy(), int(total.value)
+
+
 class FlatIndex:
     """GPU-resident counterpart of `FlatIndex` (src/index/flat.rs:60-135).
 
@@ -376,6 +398,29 @@ class FlatIndex:
         _raise(rc)
         m = n.value
         return ids[:m].copy(), scores[:m].copy()
+
+    # ---- range search -----------------------------------------------------------------------
+    def search_range_arrays(self, query, min_score: float, metric: int = 0, filter=None, limit=None):
+        """(ids, scores, total): every row whose score is >= min_score -- the longest prefix of search(query, len, metric)
+        with score >= min_score (among the filter's rows when `filter` is given: an IdFilter or an iterable of ids).
+        `total` = rows that qualify; `limit` caps what is returned (0: count only), None returns all of them."""
+        if filter is None:
+            return _search_range(self._L, self._h, query, min_score, metric, 0, limit)
+        tok, temp = self._filter_token(filter)
+        try:
+            return _search_range(self._L, self._h, query, min_score, metric, tok, limit)
+        finally:
+            if temp is not None:
+                temp.close()
+
+    def search_range(self, query, min_score: float, similarity_metric: int = SimilarityMetric.Cosine, filter=None,
+                     limit=None) -> List[SearchResult]:
+        ids, scores, _ = self.search_range_arrays(query, min_score, similarity_metric, filter=filter, limit=limit)
+        out = []
+        for i, s in zip(ids.tolist(), scores.tolist()):
+            text, md = self._meta.get(i, ("", None))
+            out.append(SearchResult(id=i, score=s, text=text, metadata=md))
+        return out
 
     def search_positions(self, query, k: int, metric: int = 0):
         """(positions, ids, scores): positions are storage positions, for row-shard merging."""
@@ -825,6 +870,13 @@ class HNSWIndex:
     def make_filter(self, ids) -> IdFilter:
         """Filtered search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""
         return _make_filter(self._L, self._h, self, ids)
+
+    def search_range_arrays(self, query, min_score: float, metric: int = 0, filter=None, limit=None):
+        """Range search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""
+        return _search_range(self._L, self._h, query, min_score, metric, 0, limit)
+
+    def search_range(self, query, min_score: float, similarity_metric: int = SimilarityMetric.Cosine, filter=None, limit=None):
+        return self.search_range_arrays(query, min_score, similarity_metric, filter, limit)
 
     def search_arrays(self, query, k: int, metric: int, ef: int = 0, filter=None):
         if filter is not None:

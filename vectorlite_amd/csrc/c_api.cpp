@@ -361,6 +361,23 @@ int vl_index_search_filtered(const vl_index* h, uint64_t filter, const double* q
     });
 }
 
+int vl_index_search_range(const vl_index* h, uint64_t filter, const double* query, uint64_t q_len, double min_score, int metric,
+                          uint64_t* out_ids, double* out_scores, uint64_t out_capacity, uint64_t* out_n, uint64_t* out_total)
+{
+    return guarded([&]() -> int {
+        if (!h || !out_n || !out_total) return VL_ERR_INVALID_ARG;
+        *out_n = 0;
+        *out_total = 0;
+        if (!h->flat) {
+            vl::set_last_error("range search is served by single-GPU flat indexes");
+            return VL_ERR_INVALID_ARG;
+        }
+        if ((!out_ids || !out_scores) && out_capacity != 0) return VL_ERR_INVALID_ARG;
+        return h->flat->search_range(filter, query, q_len, min_score, metric, out_capacity, nullptr, out_ids, out_scores, out_n,
+                                     out_total);
+    });
+}
+
 int vl_index_search_batch_filtered(const vl_index* h, uint64_t filter, const double* queries, uint64_t nq, uint64_t q_len,
                                    uint64_t k, int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores,
                                    uint64_t* out_n)

@@ -7,6 +7,7 @@
 // src/index/flat.rs:106-114).  There is no CPU compute fallback.
 #include "flat_index.hpp"
 #include "shard.hpp"
+#include "score_bound.hpp"
 
 #include <chrono>
 
@@ -85,10 +86,10 @@ Workspace::~Workspace()
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
     void* dev[] = {d_q64, d_partials, d_partials64, d_result, d_nan, d_scores, d_okeys,
-                   d_opos, d_out_pos, d_out_scores, d_positions, d_dists};
+                   d_opos, d_out_pos, d_out_scores, d_positions, d_dists, rg_ctr, rg_cand, rg_scores, rg_keys, rg_pv};
     for (void* p : dev)
         if (p) (void)hipFree(p);
-    void* host[] = {h_q64, h_result, h_nan, mf_h_q64, mf_h_result, mf_h_dom, k3_h_q64, k3_h_result};
+    void* host[] = {h_q64, h_result, h_nan, mf_h_q64, mf_h_result, mf_h_dom, k3_h_q64, k3_h_result, rg_h_ctr, rg_h_pos, rg_h_scores};
     for (void* p : host)
         if (p) (void)hipHostFree(p);
     void* mfd[] = {mf.q_bf16, mf.gmax, mf.thr, mf.cand, mf.cnt, mf_d_q64, mf_lists, mf_scores, k3_d_q64};
@@ -1623,6 +1624,270 @@ int GpuFlatIndex::search_subset(Workspace* ws, IdFilter* f, const double* query,
     }
     *out_n = k_eff;
     return OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Range search: every row whose reference score is >= min_score.  The contract: the longest prefix
+// of FlatIndex::search(q, len, metric) (src/index/flat.rs:98-119) -- over the filter's rows when a filter is given -- whose
+// scores satisfy score >= min_score.  The threshold becomes a threshold on scan keys through the shipped bound
+// (score_bound.hpp): a row whose bound is below min_score is provably out, every other row is rescored in the
+// reference's f64 order and cut on that score.  Nothing is left to certify, so the fast route has no "could not certify"
+// exit; it leaves for the exact route only when the candidate buffer overflows (or data / query are out of the domain).
+// ---------------------------------------------------------------------------------------------
+namespace {
+uint32_t range_candidate_capacity()
+{
+    // VL_RANGE_CAND_CAP: a smaller candidate buffer (tests drive the overflow route with it)
+    if (const char* e = getenv("VL_RANGE_CAND_CAP")) {
+        const long long v = atoll(e);
+        if (v >= 1 && v <= (long long)RANGE_CAND_MAX) return (uint32_t)v;
+    }
+    return RANGE_CAND_MAX;
+}
+}  // namespace
+
+int GpuFlatIndex::ensure_range_ws(Workspace* ws, uint64_t sort_cap, uint64_t out_cap) const
+{
+    if (!ws->rg_ctr) {
+        VL_TRY(dev_alloc(&ws->rg_ctr, (size_t)RANGE_CTR_WORDS));
+        VL_TRY(pinned_alloc(&ws->rg_h_ctr, (size_t)RANGE_CTR_WORDS));
+        VL_TRY(pinned_alloc(&ws->rg_h_pos, (size_t)RANGE_SMALL));
+        VL_TRY(pinned_alloc(&ws->rg_h_scores, (size_t)RANGE_SMALL));
+    }
+    if (ws->rg_sort_cap < sort_cap) {
+        if (ws->rg_keys) (void)hipFree(ws->rg_keys);
+        if (ws->rg_pv) (void)hipFree(ws->rg_pv);
+        ws->rg_keys = nullptr;
+        ws->rg_pv = nullptr;
+        ws->rg_sort_cap = 0;
+        VL_TRY(dev_alloc(&ws->rg_keys, sort_cap));
+        VL_TRY(dev_alloc(&ws->rg_pv, sort_cap));
+        ws->rg_sort_cap = sort_cap;
+    }
+    if (ws->out_cap < out_cap) {
+        if (ws->d_out_pos) (void)hipFree(ws->d_out_pos);
+        if (ws->d_out_scores) (void)hipFree(ws->d_out_scores);
+        ws->d_out_pos = nullptr;
+        ws->d_out_scores = nullptr;
+        ws->out_cap = 0;
+        VL_TRY(dev_alloc(&ws->d_out_pos, out_cap));
+        VL_TRY(dev_alloc(&ws->d_out_scores, out_cap));
+        ws->out_cap = out_cap;
+    }
+    return OK;
+}
+
+int GpuFlatIndex::search_range(uint64_t token, const double* query, uint64_t q_len, double min_score, int metric,
+                               uint64_t out_capacity, uint64_t* out_pos, uint64_t* out_ids, double* out_scores,
+                               uint64_t* out_n, uint64_t* out_total) const
+{
+    if (!out_n || !out_total) return ERR_INVALID_ARG;
+    *out_n = 0;
+    *out_total = 0;
+    std::shared_ptr<IdFilter> f;
+    if (token != 0) {
+        f = find_filter(token);
+        if (!f) {
+            set_last_error("unknown or destroyed filter");
+            return ERR_INVALID_ARG;
+        }
+    }
+    if (metric < 0 || metric > 3) {
+        set_last_error("unknown metric");
+        return ERR_INVALID_ARG;
+    }
+    std::shared_lock<RwLock> lk(mu_);  // readers share it; add / delete wait
+    const uint64_t n = ids_.size();
+    if (n != 0 && q_len != dim_) {  // the whole index's check, as in search
+        set_dim_mismatch(dim_, q_len);
+        set_last_error("Dimension mismatch: expected " + std::to_string(dim_) + ", got " + std::to_string(q_len));
+        return ERR_DIM_MISMATCH;
+    }
+    if (min_score != min_score) {
+        set_last_error("min_score is NaN");
+        return ERR_INVALID_ARG;
+    }
+    if (n == 0) return OK;
+    if ((!query && dim_) || (out_capacity != 0 && !out_scores)) return ERR_INVALID_ARG;
+
+    VL_HIP(hipSetDevice(device_));
+    Workspace* ws = acquire_ws();
+    if (!ws) return ERR_DEVICE;
+    int rc = OK;
+    if (f) {
+        std::lock_guard<std::mutex> fg(f->mu);
+        if (f->resolved_at != mutations_) rc = resolve_filter(ws, f.get());
+    }
+    if (rc == OK && (!f || f->m != 0)) {
+        active_searches_.fetch_add(1, std::memory_order_relaxed);
+        rc = search_range_locked(ws, f.get(), query, min_score, metric, out_capacity, out_pos, out_ids, out_scores, out_n,
+                                 out_total);
+        active_searches_.fetch_sub(1, std::memory_order_relaxed);
+    }
+    if (rc != OK) (void)hipStreamSynchronize(ws->stream);
+    release_ws(ws);
+    return rc;
+}
+
+int GpuFlatIndex::search_range_locked(Workspace* ws, IdFilter* f, const double* query, double min_score, int metric,
+                                      uint64_t out_capacity, uint64_t* out_pos, uint64_t* out_ids, double* out_scores,
+                                      uint64_t* out_n, uint64_t* out_total) const
+{
+    const uint64_t n = ids_.size();
+    const uint64_t m = f ? f->m : n;               // the rows of "the index" the contract speaks of
+    const uint32_t* plist = f ? f->d_plist : nullptr;
+    hipStream_t st = ws->stream;
+
+    // the query staged as search_subset stages it: pinned f64 values, then the norm
+    double qq = 0.0, qmax = 0.0;
+    bool q_finite = true;
+    for (uint64_t i = 0; i < dim_; ++i) {
+        const double v = query[i];
+        ws->h_q64[i] = v;
+        qq += v * v;
+        const double av = std::fabs(v);
+        if (!(av <= 1.797693134862315708e308)) q_finite = false;
+        if (av > qmax) qmax = av;
+    }
+    const double q_norm = std::sqrt(qq);
+    const bool q_in_domain = q_finite && qmax <= DOMAIN_MAX_ABS && (q_norm == 0.0 || q_norm >= DOMAIN_MIN_NORM);
+    ws->h_q64[dim_] = q_norm;
+    VL_HIP(hipMemcpyAsync(ws->d_q64, ws->h_q64, (dim_ + 1) * sizeof(double), hipMemcpyHostToDevice, st));
+
+    // writes the answer's first `want` entries from (positions, scores) on the host
+    auto deliver = [&](const uint32_t* pos, const double* scores, uint64_t want, uint64_t total) -> int {
+        for (uint64_t i = 0; i < want; ++i) {
+            const uint32_t p = pos[i];
+            if (p >= n) {
+                set_last_error("range search returned an out-of-range position (kernel bug)");
+                return ERR_DEVICE;
+            }
+            if (out_pos) out_pos[i] = p;
+            if (out_ids) out_ids[i] = ids_[p];
+            out_scores[i] = scores[i];
+        }
+        *out_n = want;
+        *out_total = total;
+        return OK;
+    };
+
+    const uint32_t cap = range_candidate_capacity();
+    const bool fast_ok = force_path_.load() == 0 && n_out_of_domain_ == 0 && q_in_domain;
+    if (fast_ok) {
+        VL_TRY(ensure_range_ws(ws, RANGE_CAND_MAX, RANGE_SMALL));
+        if (!ws->rg_cand) {
+            VL_TRY(dev_alloc(&ws->rg_cand, (size_t)RANGE_CAND_MAX));
+            VL_TRY(dev_alloc(&ws->rg_scores, (size_t)RANGE_CAND_MAX));
+        }
+        // the score threshold in key space: rows with key <= tau are provably below min_score (R over the whole index
+        // bounds a filter's rows too); no such key: every row is a candidate (NaN fails the device's comparison)
+        float tau = 0.0f;
+        if (!range_tau(metric, ld_, max_row_norm_, q_norm, min_score, &tau)) tau = std::nanf("");
+        const bool qarg = scan_range_takes_qarg(ld_);
+        const float* q32 = nullptr;
+        if (qarg) {
+            if (ws->q32.size() < ld_) ws->q32.assign(ld_, 0.0f);
+            for (uint64_t i = 0; i < dim_; ++i) ws->q32[i] = (float)query[i];  // nearest even, like load_q4 on the device
+            q32 = ws->q32.data();
+        }
+        const bool prof = profile_.load();
+        ScanPlan plan;
+        VL_HIP(hipMemsetAsync(ws->rg_ctr, 0, RANGE_CTR_WORDS * sizeof(uint32_t), st));
+        if (prof) VL_HIP(hipEventRecord(ws->ev0, st));
+        VL_HIP(launch_scan_range(st, metric, d_slab_, d_inv_norm_, plist, m, ws->d_q64, (uint32_t)dim_, ld_, tau, ws->rg_cand, cap,
+                                 ws->rg_ctr, &plan, q32));
+        if (prof) VL_HIP(hipEventRecord(ws->ev1, st));
+        VL_HIP(launch_range_rescore(st, metric, d_master_, ws->d_q64, ws->rg_cand, cap, (uint32_t)dim_, ws->rg_scores, ws->rg_ctr));
+        VL_HIP(launch_range_cut(st, ws->rg_scores, ws->rg_cand, ws->rg_ctr + RANGE_CTR_APPENDED, cap, min_score, ws->rg_keys,
+                                ws->rg_pv, cap, ws->rg_ctr));
+        // up to RANGE_SMALL survivors are ranked and copied back before the host knows their number: one round trip
+        const uint64_t k_spec = std::min<uint64_t>(out_capacity, RANGE_SMALL);
+        VL_HIP(launch_range_rank(st, ws->rg_keys, ws->rg_pv, ws->rg_scores, ws->rg_ctr + RANGE_CTR_TOTAL, 0, k_spec, ws->d_out_pos,
+                                 ws->d_out_scores));
+        VL_HIP(hipMemcpyAsync(ws->rg_h_ctr, ws->rg_ctr, RANGE_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (k_spec) {
+            VL_HIP(hipMemcpyAsync(ws->rg_h_pos, ws->d_out_pos, k_spec * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            VL_HIP(hipMemcpyAsync(ws->rg_h_scores, ws->d_out_scores, k_spec * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        VL_HIP(hipStreamSynchronize(st));
+        last_scan_variant_.store(plan.variant, std::memory_order_relaxed);
+        last_scan_grid_.store(plan.grid, std::memory_order_relaxed);
+        last_scan_qarg_.store(qarg ? 1 : 0, std::memory_order_relaxed);
+        if (prof) {
+            float ms = 0.f;
+            VL_HIP(hipEventElapsedTime(&ms, ws->ev0, ws->ev1));
+            std::lock_guard<std::mutex> g(prof_mu_);
+            prof_n_ += 1;
+            prof_ms_ += ms;
+            prof_bytes_ += m * ((uint64_t)ld_ * sizeof(float) + (plist ? sizeof(uint32_t) : 0) + (metric == COSINE ? sizeof(float) : 0));
+        }
+        const uint64_t appended = ws->rg_h_ctr[RANGE_CTR_APPENDED], total = ws->rg_h_ctr[RANGE_CTR_TOTAL];
+        // in-domain rows cannot score NaN; a raised flag sends the call to the exact route, which decides the status
+        if (appended <= cap && ws->rg_h_ctr[RANGE_CTR_NAN] == 0) {
+            if (appended > m || total > appended) {
+                set_last_error("range scan counted more rows than it was given (kernel bug)");
+                return ERR_DEVICE;
+            }
+            const uint64_t want = std::min<uint64_t>(total, out_capacity);
+            set_last_path(PATH_FAST);
+            if (total <= RANGE_SMALL) return deliver(ws->rg_h_pos, ws->rg_h_scores, want, total);
+            std::vector<uint32_t> pos(want);
+            std::vector<double> scores(want);
+            if (want) {
+                VL_TRY(ensure_range_ws(ws, RANGE_CAND_MAX, want));
+                VL_HIP(launch_range_rank(st, ws->rg_keys, ws->rg_pv, ws->rg_scores, nullptr, total, want, ws->d_out_pos,
+                                         ws->d_out_scores));
+                VL_HIP(hipMemcpyAsync(pos.data(), ws->d_out_pos, want * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                VL_HIP(hipMemcpyAsync(scores.data(), ws->d_out_scores, want * sizeof(double), hipMemcpyDeviceToHost, st));
+                VL_HIP(hipStreamSynchronize(st));
+            }
+            return deliver(pos.data(), scores.data(), want, total);
+        }
+        // more candidates than the buffer holds: every score, then the cut
+    }
+
+    // the exact route: the reference score of every row, the cut, the sort on (score desc, position asc)
+    VL_TRY(ensure_range_ws(ws, 0, 0));
+    if (ws->scores_cap < m) {
+        if (ws->d_scores) (void)hipFree(ws->d_scores);
+        ws->d_scores = nullptr;
+        ws->scores_cap = 0;
+        const size_t c = std::max<size_t>(m, 1024);
+        VL_TRY(dev_alloc(&ws->d_scores, c));
+        ws->scores_cap = c;
+    }
+    VL_HIP(hipMemsetAsync(ws->rg_ctr, 0, RANGE_CTR_WORDS * sizeof(uint32_t), st));
+    if (plist)
+        VL_HIP(launch_exact_scan_subset(st, metric, d_master_, ws->d_q64, plist, m, (uint32_t)dim_, ws->d_scores,
+                                        ws->rg_ctr + RANGE_CTR_NAN));
+    else
+        VL_HIP(launch_exact_scan(st, metric, d_master_, ws->d_q64, m, (uint32_t)dim_, ws->d_scores, ws->rg_ctr + RANGE_CTR_NAN));
+    VL_HIP(launch_range_cut(st, ws->d_scores, plist, nullptr, m, min_score, nullptr, nullptr, 0, ws->rg_ctr));  // count only
+    VL_HIP(hipMemcpyAsync(ws->rg_h_ctr, ws->rg_ctr, RANGE_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    VL_HIP(hipStreamSynchronize(st));
+    if (ws->rg_h_ctr[RANGE_CTR_NAN] && m >= 2) {  // a 1-element sort never calls the comparator (and NaN >= x is false)
+        set_last_error("NaN similarity score: the reference panics in partial_cmp().unwrap()");
+        return ERR_NAN_SCORE;
+    }
+    const uint64_t total = ws->rg_h_ctr[RANGE_CTR_TOTAL];
+    if (total > m) {
+        set_last_error("range cut counted more rows than it was given (kernel bug)");
+        return ERR_DEVICE;
+    }
+    const uint64_t want = std::min<uint64_t>(total, out_capacity);
+    std::vector<uint32_t> pos(want);
+    std::vector<double> scores(want);
+    if (want) {
+        VL_TRY(ensure_range_ws(ws, sort_capacity_for(total), want));
+        VL_HIP(hipMemsetAsync(ws->rg_ctr + RANGE_CTR_TOTAL, 0, sizeof(uint32_t), st));
+        VL_HIP(launch_range_cut(st, ws->d_scores, plist, nullptr, m, min_score, ws->rg_keys, ws->rg_pv, total, ws->rg_ctr));
+        VL_HIP(launch_range_rank(st, ws->rg_keys, ws->rg_pv, ws->d_scores, nullptr, total, want, ws->d_out_pos, ws->d_out_scores));
+        VL_HIP(hipMemcpyAsync(pos.data(), ws->d_out_pos, want * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipMemcpyAsync(scores.data(), ws->d_out_scores, want * sizeof(double), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipStreamSynchronize(st));
+    }
+    set_last_path(PATH_EXACT_SORT);
+    return deliver(pos.data(), scores.data(), want, total);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -79,6 +79,16 @@ struct Workspace {
     uint32_t* d_positions = nullptr;
     uint64_t* d_dists = nullptr;
     size_t hn_cap = 0;
+    // range search (lazy): counters, the scan's candidate positions and their scores, the cut's sort keys and payloads
+    uint32_t* rg_ctr = nullptr;
+    uint32_t* rg_h_ctr = nullptr;    // pinned
+    uint32_t* rg_cand = nullptr;     // [RANGE_CAND_MAX]
+    double* rg_scores = nullptr;     // [RANGE_CAND_MAX]
+    uint64_t* rg_keys = nullptr;     // [rg_sort_cap]
+    uint64_t* rg_pv = nullptr;       // [rg_sort_cap]
+    size_t rg_sort_cap = 0;
+    uint32_t* rg_h_pos = nullptr;    // pinned [RANGE_SMALL]
+    double* rg_h_scores = nullptr;   // pinned [RANGE_SMALL]
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<float> q32;   // the f32 query handed to k_scan in its kernel arguments
     uint32_t seq = 0;         // stamp of the last single search issued from this workspace (h_result->seq)
@@ -190,6 +200,11 @@ public:
     int filter_destroy(uint64_t token);
     int search_filtered(uint64_t token, const double* query, uint64_t q_len, uint64_t k, int metric, uint64_t* out_pos,
                         uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;
+    // NEW (no reference counterpart): every row whose score is >= min_score -- the longest prefix of FlatIndex::search(q, len,
+    // metric) with score >= min_score, over the filter's rows when token != 0.  *out_total = rows that qualify, always;
+    // min(total, out_capacity) entries are written (out_capacity = 0: count only, outputs may be null).
+    int search_range(uint64_t token, const double* query, uint64_t q_len, double min_score, int metric, uint64_t out_capacity,
+                     uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n, uint64_t* out_total) const;
     uint64_t len() const;
     bool is_empty() const { return len() == 0; }
     uint64_t dimension() const { return dim_; }
@@ -293,6 +308,10 @@ private:
     int resolve_filter(Workspace* ws, IdFilter* f) const;  // mu_ held (shared or unique), f->mu held
     int search_subset(Workspace* ws, IdFilter* f, const double* query, uint64_t k_eff, int metric, uint64_t* out_pos,
                       uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;  // mu_ held (shared), f resolved
+    int ensure_range_ws(Workspace* ws, uint64_t sort_cap, uint64_t out_cap) const;
+    int search_range_locked(Workspace* ws, IdFilter* f, const double* query, double min_score, int metric, uint64_t out_capacity,
+                            uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
+                            uint64_t* out_total) const;  // mu_ held (shared), f resolved (nullptr: the whole index)
     int wait_result(Workspace* ws, uint32_t seq) const;
     int ensure_i8_slab() const;  // lazily builds the int8 copy the single-query int8 filter streams
     int ensure_bf16_slab(bool frag_major) const;  // lazily builds the bf16 slab (row-major, or MFMA fragment order) a filter streams

@@ -22,6 +22,7 @@
 //   * k_hnsw_dist: the four HNSW distance callbacks, f64 reference order, Rust `as u64` semantics.
 #include "kernels.hpp"
 #include "device_common.hpp"
+#include "score_bound.hpp"
 
 #include <math.h>
 #include <stdlib.h>
@@ -32,6 +33,8 @@
 
 namespace vl {
 using namespace dev;
+static_assert(BOUND_COSINE == COSINE && BOUND_EUCLIDEAN == EUCLIDEAN && BOUND_MANHATTAN == MANHATTAN && BOUND_DOT == DOT,
+              "score_bound.hpp carries the metric codes of kernels.hpp");
 namespace {
 
 // Merge level: workgroup (b, q) folds lists [64b, 64b+64) of query q (16 waves x 4 lists, then a
@@ -490,6 +493,206 @@ __global__ __launch_bounds__(256) void k_filter_compact(const unsigned long long
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Range search: the scan that APPENDS.  scan_body's loop with the TopList taken out: the same
+// 16-byte non-temporal row loads, all loads of an iteration issued before the first FMA, the same acc4 column order,
+// group_reduce and scan_key, so a row's key is bit for bit the one k_scan gives it.  A row is a candidate unless
+// key <= tau (tau: the largest key whose bound_for_key is below the caller's score threshold, chosen on the host; a NaN
+// tau or key fails the comparison and keeps the row).  Lane c == 0 of each row group tests; the wave ballots, ONE lane
+// reserves the slots of all U row groups with one global atomic add on *ctr, the flagged lanes store their storage
+// positions.  The counter keeps counting past `cap`; stores past it are dropped (the host then takes the exact route).
+// No LDS list, no block merge, no partial lists.  SUBSET: the rows are plist[0..n) with scan_subset_body's prefetch
+// discipline (the next iteration's list entries are requested before this iteration's row loads).
+// ---------------------------------------------------------------------------------------------
+template <int U>
+__device__ __forceinline__ void range_append(const bool (&hit)[U], const uint32_t (&pos)[U], uint32_t* __restrict__ cand,
+                                             uint32_t cap, uint32_t* __restrict__ ctr)
+{
+    const int lane = lane_id();
+    unsigned long long bal[U];
+    uint32_t total = 0;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        bal[u] = __ballot(hit[u]);
+        total += (uint32_t)__popcll(bal[u]);
+    }
+    if (total == 0) return;  // wave-uniform: a selective threshold leaves the stream alone
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(ctr, total);
+    base = __shfl(base, 0);
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const uint32_t slot = base + (uint32_t)__popcll(bal[u] & below);
+        if (hit[u] && slot < cap) cand[slot] = pos[u];
+        base += (uint32_t)__popcll(bal[u]);
+    }
+}
+
+template <int METRIC, int G, int VPL, int U, bool SUBSET>
+__device__ __forceinline__ void scan_range_body(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
+                                                const uint32_t* __restrict__ plist, const f32x4 (&qv)[VPL], uint32_t n,
+                                                float tau, uint32_t* __restrict__ cand, uint32_t cap,
+                                                uint32_t* __restrict__ ctr)
+{
+    constexpr int RPS = WAVE / G;  // rows per step of one wave
+    constexpr uint32_t LD4 = G * VPL;
+    const int lane = lane_id();
+    const int wave = threadIdx.x >> 6;
+    const int g = lane / G, c = lane % G;
+    const uint32_t n_steps = (n + RPS - 1) / RPS;
+    const uint32_t n_waves = gridDim.x * 4;
+    const uint32_t wave_global = blockIdx.x * 4 + wave;
+    const uint32_t stride = n_waves * U;
+
+    if constexpr (!SUBSET) {
+        for (uint32_t s0 = wave_global; s0 < n_steps; s0 += stride) {
+            f32x4 x[U][VPL];
+            uint32_t row[U];
+            float inv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const uint32_t s = s0 + (uint32_t)u * n_waves;
+                row[u] = s < n_steps ? s * RPS + g : n;  // n marks "no row"
+                const uint32_t r = row[u] < n ? row[u] : n - 1;  // clamp: loads stay in bounds
+                const f32x4* p = slab + (size_t)r * LD4 + c;
+#pragma unroll
+                for (int j = 0; j < VPL; ++j) x[u][j] = __builtin_nontemporal_load(p + G * j);
+                inv[u] = 1.0f;
+                if (METRIC == COSINE) inv[u] = inv_norm[r];
+            }
+            __builtin_amdgcn_sched_barrier(0);  // every load of this iteration is issued before the first FMA
+            bool hit[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                float a = 0.0f;
+#pragma unroll
+                for (int j = 0; j < VPL; ++j) a = acc4<METRIC>(a, x[u][j], qv[j]);
+                a = group_reduce<G>(a);
+                const float key = scan_key<METRIC>(a, inv[u]);
+                hit[u] = row[u] < n && c == 0 && !(key <= tau);
+            }
+            range_append<U>(hit, row, cand, cap, ctr);
+        }
+    } else {
+        uint32_t pn[U];
+        bool vn[U];
+        auto fetch = [&](uint32_t s0) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const uint32_t s = s0 + (uint32_t)u * n_waves;
+                const uint32_t i = s < n_steps ? s * RPS + g : n;  // n marks "no row"
+                vn[u] = i < n;
+                pn[u] = plist[i < n ? i : n - 1];  // clamp: the load stays in bounds
+            }
+        };
+        fetch(wave_global);
+        for (uint32_t s0 = wave_global; s0 < n_steps; s0 += stride) {
+            uint32_t pos[U];
+            bool valid[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                pos[u] = pn[u];
+                valid[u] = vn[u];
+            }
+            fetch(s0 + stride);
+            __builtin_amdgcn_sched_barrier(0);  // the list loads go out in front of the row loads
+            f32x4 x[U][VPL];
+            float inv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const f32x4* p = slab + (size_t)pos[u] * LD4 + c;
+#pragma unroll
+                for (int j = 0; j < VPL; ++j) x[u][j] = __builtin_nontemporal_load(p + G * j);
+                inv[u] = 1.0f;
+                if (METRIC == COSINE) inv[u] = inv_norm[pos[u]];
+            }
+            __builtin_amdgcn_sched_barrier(0);  // every row load of this iteration is issued before the first FMA
+            bool hit[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                float a = 0.0f;
+#pragma unroll
+                for (int j = 0; j < VPL; ++j) a = acc4<METRIC>(a, x[u][j], qv[j]);
+                a = group_reduce<G>(a);
+                const float key = scan_key<METRIC>(a, inv[u]);
+                hit[u] = valid[u] && c == 0 && !(key <= tau);
+            }
+            range_append<U>(hit, pos, cand, cap, ctr);
+        }
+    }
+}
+
+// the kernel-argument query (k_scan's form)
+template <int METRIC, int G, int VPL, int U, bool SUBSET>
+__global__ __launch_bounds__(256) void k_scan_range(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
+                                                    const uint32_t* __restrict__ plist, uint32_t n, float tau,
+                                                    uint32_t* __restrict__ cand, uint32_t cap, uint32_t* __restrict__ ctr,
+                                                    const ScanQArg qa)
+{
+    static_assert(G * VPL * 4 <= SCAN_QARG_FLOATS, "row too long for the kernarg query");
+    const int c = lane_id() % G;
+    f32x4 qv[VPL];
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) qv[j] = *reinterpret_cast<const f32x4*>(&qa.v[4 * (c + G * j)]);
+    scan_range_body<METRIC, G, VPL, U, SUBSET>(slab, inv_norm, plist, qv, n, tau, cand, cap, ctr);
+}
+
+// the f64 query in device memory (k_scan_q64's form: strides past the kernarg query)
+template <int METRIC, int G, int VPL, int U, bool SUBSET>
+__global__ __launch_bounds__(256) void k_scan_range_q64(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
+                                                        const uint32_t* __restrict__ plist,
+                                                        const double* __restrict__ q64, uint32_t dim, uint32_t n, float tau,
+                                                        uint32_t* __restrict__ cand, uint32_t cap,
+                                                        uint32_t* __restrict__ ctr)
+{
+    const int c = lane_id() % G;
+    f32x4 qv[VPL];
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) qv[j] = load_q4(q64, c + G * j, dim);
+    scan_range_body<METRIC, G, VPL, U, SUBSET>(slab, inv_norm, plist, qv, n, tau, cand, cap, ctr);
+}
+
+// Generic: any ld4, G lanes per row (k_scan_generic's arithmetic and order; SUBSET: k_scan_subset_generic's prefetch).
+template <int METRIC, int G, bool SUBSET>
+__global__ __launch_bounds__(256) void k_scan_range_generic(const f32x4* __restrict__ slab,
+                                                            const float* __restrict__ inv_norm,
+                                                            const uint32_t* __restrict__ plist,
+                                                            const double* __restrict__ q64, uint32_t dim, uint32_t n,
+                                                            uint32_t ld4, float tau, uint32_t* __restrict__ cand,
+                                                            uint32_t cap, uint32_t* __restrict__ ctr)
+{
+    constexpr int RPS = WAVE / G;
+    const int lane = lane_id();
+    const int wave = threadIdx.x >> 6;
+    const int g = lane / G, c = lane % G;
+    const uint32_t n_steps = (n + RPS - 1) / RPS;
+    const uint32_t n_waves = gridDim.x * 4;
+
+    uint32_t s = blockIdx.x * 4 + wave;
+    uint32_t i_next = s < n_steps ? s * RPS + g : n;
+    uint32_t p_next = i_next;
+    if (SUBSET) p_next = plist[i_next < n ? i_next : n - 1];
+    for (; s < n_steps; s += n_waves) {
+        const bool valid = i_next < n;
+        const uint32_t pos[1] = {p_next};
+        const uint32_t sn = s + n_waves;
+        i_next = sn < n_steps ? sn * RPS + g : n;
+        p_next = i_next;
+        if (SUBSET) p_next = plist[i_next < n ? i_next : n - 1];  // next row's list entry, in flight during this row
+        const uint32_t r = SUBSET ? pos[0] : (valid ? pos[0] : n - 1);
+        const f32x4* p = slab + (size_t)r * ld4;
+        float a = 0.0f;
+        for (uint32_t j = c; j < ld4; j += G) a = acc4<METRIC>(a, p[j], load_q4(q64, j, dim));
+        a = group_reduce<G>(a);
+        float inv = 1.0f;
+        if (METRIC == COSINE) inv = inv_norm[r];
+        const float key = scan_key<METRIC>(a, inv);
+        const bool hit[1] = {valid && c == 0 && !(key <= tau)};
+        range_append<1>(hit, pos, cand, cap, ctr);
+    }
+}
+
 // K3: small-batch scan.  One pass over the slab serves QB queries: each row group is loaded ONCE into
 // registers and scored against QB queries whose f32 copies sit in LDS (lanes that share a column read
 // the same 16 bytes: an LDS broadcast).  Per wave, QB independent top-64 lists.  Still streams
@@ -846,42 +1049,8 @@ __device__ __forceinline__ void rescore_rows_par(const double* __restrict__ mast
     }
 }
 
-// Upper bound B on the REFERENCE f64 score of any row whose f32 scan key is <= t, for in-domain data
-// (finite, |v| <= 2^40, row norms 0 or >= 2^-40).  u = 2^-24, n = padded dim, R = max row norm,
-// Q = |query|.  Derivation in DESIGN.md ("Exactness bound"); every u-term carries a 2x safety factor.
-// `in_extra` is the additional relative input-rounding term of a lower-precision candidate filter
-// (bf16 MFMA path: (2 + 2^-8) * 2^-8 per product, rigorous, no safety factor needed); 0 for the f32 scan.
-template <int METRIC>
-__device__ __forceinline__ double bound_for_key(float t_key, uint32_t n, double R, double Q, double in_extra)
-{
-    const double u = 5.9604644775390625e-08;  // 2^-24
-    const double nn = (double)n;
-    const double t = (double)t_key;
-    if (METRIC == COSINE) {
-        if (!(Q > 0.0)) return (double)INFINITY;
-        return t / Q + 2.0 * (nn + 4.0) * u + in_extra + 1e-12;
-    }
-    if (METRIC == DOT) {
-        return t + (2.0 * (nn + 2.0) * u + in_extra) * R * Q + 1e-12 * (1.0 + R * Q);
-    }
-    if (METRIC == EUCLIDEAN && in_extra > 0.0) {
-        // GEMM-form key of the MFMA path: key = 2 x.q - |x|^2 = |q|^2 - |x - q|^2 (real numbers).
-        // |key32 - key| <= 2 (in_extra + (n+2)u) R Q + u R^2 + u (2 R Q + R^2); u-terms doubled.
-        const double err = 2.0 * in_extra * R * Q + 4.0 * (nn + 4.0) * u * (R * Q + R * R);
-        double s_lo = Q * Q - t - err;
-        if (!(s_lo > 0.0)) s_lo = 0.0;
-        return (1.0 / (1.0 + sqrt(s_lo) * (1.0 - 1e-12))) * (1.0 + 1e-15);
-    }
-    const double ts = t < 0.0 ? -t : 0.0;  // key = -sum
-    double d_lo;
-    if (METRIC == EUCLIDEAN) {
-        d_lo = sqrt(ts) * (1.0 - 2.0 * (nn + 2.0) * u) - 4.0 * u * (R + Q);
-    } else {
-        d_lo = ts * (1.0 - 2.0 * (nn + 2.0) * u) - 4.0 * u * sqrt(nn) * (R + Q);
-    }
-    if (!(d_lo > 0.0)) d_lo = 0.0;
-    return (1.0 / (1.0 + d_lo * (1.0 - 1e-12))) * (1.0 + 1e-15);
-}
+// bound_for_key<METRIC> -- the upper bound on the reference score of any row whose scan key is <= t -- lives in
+// score_bound.hpp: a range search evaluates the same function on the host.
 
 // Phase 3 of a finalize, one WAVE per query: lane j holds candidate j's reference score and position (lanes >= n_cand hold
 // nothing); key64 = the candidate list's 64th scan key.  Rank by (score desc, pos asc) = the reference's stable sort, run the
@@ -1260,10 +1429,9 @@ __global__ __launch_bounds__(256) void k_exact_scan(const double* __restrict__ m
 // k_exact_scan over a subset: scores[i] = the reference score of row plist[i], i < m.  The same tile walk and the same
 // Acc64 steps (separate multiply and add, index order); only a tile row's source is plist[row0 + r] instead of row0 + r.
 template <int METRIC>
-__global__ __launch_bounds__(256) void k_exact_scan_subset(const double* __restrict__ master,
-                                                           const double* __restrict__ q64,
-                                                           const uint32_t* __restrict__ plist, uint64_t m, uint32_t dim,
-                                                           double* __restrict__ scores, uint32_t* __restrict__ nan_flag)
+__device__ __forceinline__ void exact_scan_subset_body(const double* __restrict__ master, const double* __restrict__ q64,
+                                                       const uint32_t* __restrict__ plist, uint64_t m, uint32_t dim,
+                                                       double* __restrict__ scores, uint32_t* __restrict__ nan_flag)
 {
     __shared__ double tile[EX_ROWS][EX_CH + 1];
     __shared__ double qtile[EX_CH];
@@ -1327,6 +1495,28 @@ __global__ __launch_bounds__(256) void k_exact_scan_subset(const double* __restr
             if (sc != sc) atomicOr(nan_flag, 1u);
         }
     }
+}
+
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_exact_scan_subset(const double* __restrict__ master,
+                                                           const double* __restrict__ q64,
+                                                           const uint32_t* __restrict__ plist, uint64_t m, uint32_t dim,
+                                                           double* __restrict__ scores, uint32_t* __restrict__ nan_flag)
+{
+    exact_scan_subset_body<METRIC>(master, q64, plist, m, dim, scores, nan_flag);
+}
+
+// Range search: the reference score of every candidate the range scan appended, scores[i] for cand[i], i < ctr[0] -- the
+// count is read on the device, no host round trip stands between the scan and this kernel.  A counter above `cap` means
+// the candidate buffer overflowed: nothing is done, the host takes the exact route.  ctr[2] is the NaN flag.
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_range_rescore(const double* __restrict__ master, const double* __restrict__ q64,
+                                                       const uint32_t* __restrict__ cand, uint32_t cap, uint32_t dim,
+                                                       double* __restrict__ scores, uint32_t* __restrict__ ctr)
+{
+    const uint32_t m = ctr[RANGE_CTR_APPENDED];
+    if (m == 0 || m > cap) return;
+    exact_scan_subset_body<METRIC>(master, q64, cand, (uint64_t)m, dim, scores, ctr + RANGE_CTR_NAN);
 }
 
 // top-64 of scores[] by (score desc, pos asc): per-wave lists, then per-workgroup merge
@@ -1418,19 +1608,24 @@ __global__ void k_sort_init(const double* __restrict__ scores, uint64_t n, uint6
     }
 }
 
-__device__ __forceinline__ bool pair_greater(unsigned long long ka, uint32_t pa, unsigned long long kb, uint32_t pb)
+// P: the payload that breaks ties -- a u32 position (the exact sort: index = position), or a range search's u64
+// (position << 32 | slot of the score)
+template <typename P>
+__device__ __forceinline__ bool pair_greater(unsigned long long ka, P pa, unsigned long long kb, P pb)
 {
     return ka > kb || (ka == kb && pa > pb);
 }
 
 constexpr int SORT_LOCAL = 2048;  // elements sorted in LDS by one 1024-thread workgroup
+static_assert((uint32_t)SORT_LOCAL == RANGE_SMALL, "a range search's speculative ranking is one local sort");
 
 // All stages with j < SORT_LOCAL for k in [k_lo, k_hi] (k_lo == k_hi > SORT_LOCAL: tail of one k).
-__global__ __launch_bounds__(1024) void k_bitonic_local(unsigned long long* __restrict__ okeys,
-                                                        uint32_t* __restrict__ opos, uint64_t k_lo, uint64_t k_hi)
+template <typename P>
+__global__ __launch_bounds__(1024) void k_bitonic_local(unsigned long long* __restrict__ okeys, P* __restrict__ opos,
+                                                        uint64_t k_lo, uint64_t k_hi)
 {
     __shared__ unsigned long long sk[SORT_LOCAL];
-    __shared__ uint32_t sp[SORT_LOCAL];
+    __shared__ P sp[SORT_LOCAL];
     const uint64_t base = (uint64_t)blockIdx.x * SORT_LOCAL;
     const int tid = threadIdx.x;
     sk[tid] = okeys[base + tid];
@@ -1447,8 +1642,8 @@ __global__ __launch_bounds__(1024) void k_bitonic_local(unsigned long long* __re
             const uint32_t l = i | jj;
             const bool up = (((base + i) & k) == 0);
             const unsigned long long ka = sk[i], kb = sk[l];
-            const uint32_t pa = sp[i], pb = sp[l];
-            const bool gt = pair_greater(ka, pa, kb, pb);
+            const P pa = sp[i], pb = sp[l];
+            const bool gt = pair_greater<P>(ka, pa, kb, pb);
             if (gt == up) {
                 sk[i] = kb;
                 sp[i] = pb;
@@ -1464,8 +1659,9 @@ __global__ __launch_bounds__(1024) void k_bitonic_local(unsigned long long* __re
     opos[base + tid + 1024] = sp[tid + 1024];
 }
 
-__global__ void k_bitonic_global(unsigned long long* __restrict__ okeys, uint32_t* __restrict__ opos,
-                                 uint64_t cap, uint64_t j, uint64_t k)
+template <typename P>
+__global__ void k_bitonic_global(unsigned long long* __restrict__ okeys, P* __restrict__ opos, uint64_t cap, uint64_t j,
+                                 uint64_t k)
 {
     for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < (cap >> 1);
          t += (uint64_t)gridDim.x * blockDim.x) {
@@ -1473,8 +1669,8 @@ __global__ void k_bitonic_global(unsigned long long* __restrict__ okeys, uint32_
         const uint64_t l = i | j;
         const bool up = ((i & k) == 0);
         const unsigned long long ka = okeys[i], kb = okeys[l];
-        const uint32_t pa = opos[i], pb = opos[l];
-        if (pair_greater(ka, pa, kb, pb) == up) {
+        const P pa = opos[i], pb = opos[l];
+        if (pair_greater<P>(ka, pa, kb, pb) == up) {
             okeys[i] = kb;
             opos[i] = pb;
             okeys[l] = ka;
@@ -1491,6 +1687,67 @@ __global__ void k_sort_emit(const uint32_t* __restrict__ opos, const double* __r
         const uint32_t p = opos[i];
         out_pos[i] = p;
         out_scores[i] = scores[p];
+    }
+}
+
+// ---- range search: cut at the threshold, rank, emit ---------------------------------------------
+// The cut: every slot i < m whose score satisfies the IEEE comparison score >= min_score is appended (one atomic per wave)
+// to (keys, pv) as (desc_key(score), position << 32 | i); ctr[RANGE_CTR_TOTAL] counts them all, entries past
+// `store_cap` are counted and not stored (store_cap = 0: count only).  cand == nullptr: slot i IS the position (the exact
+// route's scores[] of every row); else the position is cand[i] (the fast route's candidates, or a filter's list).
+// m_ptr != nullptr: m is the range scan's counter, and nothing is done when it ran past cap_in.
+__global__ __launch_bounds__(256) void k_range_cut(const double* __restrict__ scores, const uint32_t* __restrict__ cand,
+                                                   const uint32_t* __restrict__ m_ptr, uint32_t m_val, uint32_t cap_in,
+                                                   double min_score, unsigned long long* __restrict__ keys,
+                                                   unsigned long long* __restrict__ pv, uint32_t store_cap,
+                                                   uint32_t* __restrict__ ctr)
+{
+    const uint32_t m = m_ptr ? *m_ptr : m_val;
+    if (m_ptr && m > cap_in) return;
+    const int lane = lane_id();
+    const uint32_t step = gridDim.x * 256;
+    for (uint32_t b0 = blockIdx.x * 256; b0 < m; b0 += step) {  // workgroup-uniform trip count
+        const uint32_t i = b0 + threadIdx.x;
+        const bool valid = i < m;
+        const double sc = scores[valid ? i : m - 1];
+        const bool keep = valid && sc >= min_score;
+        const unsigned long long bal = __ballot(keep);
+        if (bal == 0ull) continue;  // wave-uniform
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(ctr + RANGE_CTR_TOTAL, (uint32_t)__popcll(bal));
+        base = __shfl(base, 0);
+        const uint32_t slot = base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        if (keep && slot < store_cap) {
+            const uint32_t pos = cand ? cand[i] : i;
+            keys[slot] = desc_key(sc);
+            pv[slot] = ((unsigned long long)pos << 32) | (unsigned long long)i;
+        }
+    }
+}
+
+// Pads (keys, pv) from the survivor count up to the sort's capacity with entries that sort last.  total_ptr != nullptr:
+// the count is ctr's (the speculative small sort, before the host knows it); a count above `cap` leaves the buffers alone.
+__global__ void k_range_pad(unsigned long long* __restrict__ keys, unsigned long long* __restrict__ pv,
+                            const uint32_t* __restrict__ total_ptr, uint64_t total_val, uint64_t cap)
+{
+    const uint64_t total = total_ptr ? (uint64_t)*total_ptr : total_val;
+    if (total > cap) return;
+    for (uint64_t i = total + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * blockDim.x) {
+        keys[i] = ~0ull;
+        pv[i] = ~0ull;
+    }
+}
+
+// The first min(total, k) entries of the sorted (keys, pv): position and the score's own bits (scores[slot]).
+__global__ void k_range_emit(const unsigned long long* __restrict__ pv, const double* __restrict__ scores,
+                             const uint32_t* __restrict__ total_ptr, uint64_t k, uint32_t* __restrict__ out_pos,
+                             double* __restrict__ out_scores)
+{
+    if (total_ptr && (uint64_t)*total_ptr < k) k = *total_ptr;
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < k; i += (uint64_t)gridDim.x * blockDim.x) {
+        const unsigned long long e = pv[i];
+        out_pos[i] = (uint32_t)(e >> 32);
+        out_scores[i] = scores[(uint32_t)e];
     }
 }
 
@@ -2198,6 +2455,25 @@ uint64_t sort_capacity_for(uint64_t n)
     return cap;
 }
 
+namespace {
+// ascending sort of cap (a power of two >= SORT_LOCAL) entries on (key, payload)
+template <typename P>
+void bitonic_network(hipStream_t s, unsigned long long* ok, P* opos, uint64_t cap)
+{
+    const int lgrid = (int)(cap / SORT_LOCAL);
+    // k = 2 .. SORT_LOCAL entirely in LDS
+    hipLaunchKernelGGL((k_bitonic_local<P>), dim3(lgrid), dim3(1024), 0, s, ok, opos, (uint64_t)2, (uint64_t)SORT_LOCAL);
+    for (uint64_t kk = (uint64_t)SORT_LOCAL << 1; kk <= cap; kk <<= 1) {
+        for (uint64_t j = kk >> 1; j >= (uint64_t)SORT_LOCAL; j >>= 1) {
+            const uint64_t pairs = cap >> 1;
+            const int g = (int)((pairs / 256) < 16384 ? (pairs / 256) : 16384);
+            hipLaunchKernelGGL((k_bitonic_global<P>), dim3(g), dim3(256), 0, s, ok, opos, cap, j, kk);
+        }
+        hipLaunchKernelGGL((k_bitonic_local<P>), dim3(lgrid), dim3(1024), 0, s, ok, opos, kk, kk);
+    }
+}
+}  // namespace
+
 hipError_t launch_exact_sort(hipStream_t s, const double* scores, uint64_t n, uint64_t k, uint64_t* okeys,
                              uint32_t* opos, uint32_t* out_pos, double* out_scores)
 {
@@ -2206,17 +2482,7 @@ hipError_t launch_exact_sort(hipStream_t s, const double* scores, uint64_t n, ui
     unsigned long long* ok = reinterpret_cast<unsigned long long*>(okeys);
     const int tgrid = (int)((cap / 256) < 8192 ? (cap / 256) : 8192);
     hipLaunchKernelGGL(k_sort_init, dim3(tgrid), dim3(256), 0, s, scores, n, cap, ok, opos);
-    const int lgrid = (int)(cap / SORT_LOCAL);
-    // k = 2 .. SORT_LOCAL entirely in LDS
-    hipLaunchKernelGGL(k_bitonic_local, dim3(lgrid), dim3(1024), 0, s, ok, opos, (uint64_t)2, (uint64_t)SORT_LOCAL);
-    for (uint64_t kk = (uint64_t)SORT_LOCAL << 1; kk <= cap; kk <<= 1) {
-        for (uint64_t j = kk >> 1; j >= (uint64_t)SORT_LOCAL; j >>= 1) {
-            const uint64_t pairs = cap >> 1;
-            const int g = (int)((pairs / 256) < 16384 ? (pairs / 256) : 16384);
-            hipLaunchKernelGGL(k_bitonic_global, dim3(g), dim3(256), 0, s, ok, opos, cap, j, kk);
-        }
-        hipLaunchKernelGGL(k_bitonic_local, dim3(lgrid), dim3(1024), 0, s, ok, opos, kk, kk);
-    }
+    bitonic_network<uint32_t>(s, ok, opos, cap);
     const uint64_t kk = k < n ? k : n;
     if (kk > 0) {
         const int egrid = (int)(((kk + 255) / 256) < 4096 ? ((kk + 255) / 256) : 4096);
@@ -2236,6 +2502,136 @@ hipError_t launch_hnsw_distances(hipStream_t s, int metric, const double* master
                            reinterpret_cast<unsigned long long*>(out));
         return hipGetLastError();
     });
+}
+
+// ---- range search -------------------------------------------------------------------------------
+// The range scan's shapes are the subset scan's: for every stride VL_SCAN_VARIANTS specialises, k_scan's default entry.
+bool scan_range_takes_qarg(uint32_t ld) { return scan_subset_takes_qarg(ld); }
+
+namespace {
+template <int MM, bool SUBSET>
+hipError_t launch_scan_range_t(hipStream_t s, const f32x4* slab4, const float* inv_norm, const uint32_t* plist, uint64_t n,
+                               const double* q64, uint32_t dim, uint32_t ld, float tau, uint32_t* cand, uint32_t cap,
+                               uint32_t* ctr, const ScanShape& sh, bool qarg, const float* q32_host, int* grid_out)
+{
+    const uint32_t n32 = (uint32_t)n, ld4 = ld / 4;
+    int grid = 0;
+    if (sh.special) {
+        bool launched = false;
+#define VL_RANGE_TRY(G, VPL, U, BPC)                                                                                    \
+    if (!launched && sh.g == G && sh.vpl == VPL && sh.u == U) {                                                     \
+        if constexpr (G * VPL * 4 <= SCAN_QARG_FLOATS) {                                                             \
+            if (qarg) {                                                                                              \
+                auto kern = k_scan_range<MM, G, VPL, U, SUBSET>;                                                     \
+                grid = scan_grid(n, sh, reinterpret_cast<const void*>(kern));                                        \
+                ScanQArg qa;                                                                                         \
+                memcpy(qa.v, q32_host, (size_t)ld * sizeof(float));                                                  \
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, slab4, inv_norm, plist, n32, tau, cand, cap, ctr, qa); \
+                launched = true;                                                                                     \
+            }                                                                                                        \
+        } else {                                                                                                     \
+            auto kern = k_scan_range_q64<MM, G, VPL, U, SUBSET>;                                                     \
+            grid = scan_grid(n, sh, reinterpret_cast<const void*>(kern));                                            \
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, slab4, inv_norm, plist, q64, dim, n32, tau, cand, cap, ctr); \
+            launched = true;                                                                                         \
+        }                                                                                                            \
+    }
+        VL_SUBSET_VARIANTS(VL_RANGE_TRY)
+#undef VL_RANGE_TRY
+        if (!launched) return hipErrorInvalidValue;  // a kernarg-sized stride always comes with its query there
+    } else {
+#define VL_RANGE_GEN(G)                                                                                                 \
+    case G: {                                                                                                           \
+        auto kern = k_scan_range_generic<MM, G, SUBSET>;                                                                \
+        grid = scan_grid(n, sh, reinterpret_cast<const void*>(kern));                                                   \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, slab4, inv_norm, plist, q64, dim, n32, ld4, tau, cand, cap, ctr); \
+    } break;
+        switch (sh.g) {
+            VL_RANGE_GEN(1)
+            VL_RANGE_GEN(2)
+            VL_RANGE_GEN(4)
+            VL_RANGE_GEN(8)
+            VL_RANGE_GEN(16)
+            VL_RANGE_GEN(32)
+            VL_RANGE_GEN(64)
+        default: return hipErrorInvalidValue;
+        }
+#undef VL_RANGE_GEN
+    }
+    *grid_out = grid;
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_scan_range(hipStream_t s, int metric, const float* slab, const float* inv_norm, const uint32_t* plist,
+                             uint64_t n, const double* q64, uint32_t dim, uint32_t ld, float tau, uint32_t* cand,
+                             uint32_t cap, uint32_t* ctr, ScanPlan* plan, const float* q32_host)
+{
+    if (n == 0 || n >= 0xFFFFFFFFull || (ld & 3) || cap == 0) return hipErrorInvalidValue;
+    const uint32_t ld4 = ld / 4;
+    const f32x4* slab4 = reinterpret_cast<const f32x4*>(slab);
+    ScanShape sh{false, lanes_per_row(ld4), 0, 1, 4};
+#define VL_PICK(G, VPL, U, BPC) \
+    if (!sh.special && (uint32_t)(G * VPL) == ld4) sh = ScanShape{true, G, VPL, U, BPC};
+    VL_SUBSET_VARIANTS(VL_PICK)
+#undef VL_PICK
+    const bool qarg = q32_host != nullptr && sh.special && ld <= (uint32_t)SCAN_QARG_FLOATS;
+    if (!qarg && !q64) return hipErrorInvalidValue;
+    int grid = 0;
+    hipError_t rc = dispatch_metric(metric, [&](auto M) -> hipError_t {
+        constexpr int MM = decltype(M)::value;
+        if (plist) return launch_scan_range_t<MM, true>(s, slab4, inv_norm, plist, n, q64, dim, ld, tau, cand, cap, ctr, sh, qarg, q32_host, &grid);
+        return launch_scan_range_t<MM, false>(s, slab4, inv_norm, nullptr, n, q64, dim, ld, tau, cand, cap, ctr, sh, qarg, q32_host, &grid);
+    });
+    if (plan) {
+        plan->grid = grid;
+        plan->variant = sh.special ? (RANGE_VARIANT_BASE + sh.g * 10000 + sh.vpl * 100 + sh.u) : -(RANGE_VARIANT_BASE + sh.g);
+    }
+    return rc;
+}
+
+hipError_t launch_range_rescore(hipStream_t s, int metric, const double* master, const double* q64, const uint32_t* cand,
+                                uint32_t cap, uint32_t dim, double* scores, uint32_t* ctr)
+{
+    if (cap == 0) return hipErrorInvalidValue;
+    // the candidate count is the device's: enough workgroups for a full buffer, those without a tile leave at once
+    const uint32_t tiles = (cap + EX_ROWS - 1) / EX_ROWS;
+    const int grid = (int)(tiles < 1024u ? tiles : 1024u);
+    return dispatch_metric(metric, [&](auto M) -> hipError_t {
+        constexpr int MM = decltype(M)::value;
+        hipLaunchKernelGGL((k_range_rescore<MM>), dim3(grid), dim3(256), 0, s, master, q64, cand, cap, dim, scores, ctr);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_range_cut(hipStream_t s, const double* scores, const uint32_t* cand, const uint32_t* m_ptr, uint64_t m_max,
+                            double min_score, uint64_t* keys, uint64_t* pv, uint64_t store_cap, uint32_t* ctr)
+{
+    if (m_max == 0 || m_max >= 0xFFFFFFFFull || store_cap >= 0xFFFFFFFFull) return hipErrorInvalidValue;
+    const uint64_t blocks = (m_max + 255) / 256;
+    const int grid = (int)(blocks < 2048 ? blocks : 2048);
+    hipLaunchKernelGGL(k_range_cut, dim3(grid), dim3(256), 0, s, scores, cand, m_ptr, (uint32_t)m_max, (uint32_t)m_max, min_score,
+                       reinterpret_cast<unsigned long long*>(keys), reinterpret_cast<unsigned long long*>(pv),
+                       (uint32_t)store_cap, ctr);
+    return hipGetLastError();
+}
+
+hipError_t launch_range_rank(hipStream_t s, uint64_t* keys, uint64_t* pv, const double* scores, const uint32_t* total_ptr,
+                             uint64_t total, uint64_t k, uint32_t* out_pos, double* out_scores)
+{
+    unsigned long long* ok = reinterpret_cast<unsigned long long*>(keys);
+    unsigned long long* op = reinterpret_cast<unsigned long long*>(pv);
+    const uint64_t cap = total_ptr ? (uint64_t)RANGE_SMALL : sort_capacity_for(total);
+    if (total_ptr && k > cap) k = cap;
+    if (!total_ptr && (total == 0 || total >= 0xFFFFFFFFull)) return hipErrorInvalidValue;
+    const int pgrid = (int)((cap / 256) < 4096 ? (cap / 256) : 4096);
+    hipLaunchKernelGGL(k_range_pad, dim3(pgrid), dim3(256), 0, s, ok, op, total_ptr, total, cap);
+    bitonic_network<unsigned long long>(s, ok, op, cap);
+    if (k > 0) {
+        const int egrid = (int)(((k + 255) / 256) < 4096 ? ((k + 255) / 256) : 4096);
+        hipLaunchKernelGGL(k_range_emit, dim3(egrid), dim3(256), 0, s, op, scores, total_ptr, k, out_pos, out_scores);
+    }
+    return hipGetLastError();
 }
 
 }  // namespace vl

@@ -175,6 +175,34 @@ hipError_t launch_filter_count(hipStream_t s, const unsigned long long* pos_ids,
 hipError_t launch_filter_compact(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
                                  uint64_t nf, const uint32_t* offsets, uint64_t m, uint32_t* plist);
 
+// Range search (score >= min_score).  ctr: RANGE_CTR_WORDS words of device memory, zeroed by the
+// caller in front of each sequence: [APPENDED] rows the scan appended (it keeps counting past the buffer), [TOTAL] rows
+// that pass the cut, [NAN] set when a rescored row is NaN.
+constexpr int RANGE_VARIANT_BASE = 4000000;
+constexpr uint32_t RANGE_CAND_MAX = 1u << 20;  // C: positions the candidate buffer holds (4 MB; with scores, keys and payloads 28 MB)
+constexpr uint32_t RANGE_SMALL = 2048;         // survivors ranked before the host knows their number (one workgroup's LDS sort)
+constexpr int RANGE_CTR_APPENDED = 0, RANGE_CTR_TOTAL = 1, RANGE_CTR_NAN = 2, RANGE_CTR_WORDS = 4;
+// The scan that appends: cand[] receives the storage position of every row whose key is NOT <= tau (tau NaN: every row), up to
+// cap of them.  plist != nullptr: over the rows plist[0..n) (an id filter's list).  Keys, query forms and grid are k_scan's.
+// plan->variant = RANGE_VARIANT_BASE + G * 10000 + VPL * 100 + U, or -(RANGE_VARIANT_BASE + G) for the generic kernel.
+bool scan_range_takes_qarg(uint32_t ld);
+hipError_t launch_scan_range(hipStream_t s, int metric, const float* slab, const float* inv_norm, const uint32_t* plist,
+                             uint64_t n, const double* q64, uint32_t dim, uint32_t ld, float tau, uint32_t* cand,
+                             uint32_t cap, uint32_t* ctr, ScanPlan* plan, const float* q32_host = nullptr);
+// scores[i] = reference f64 score of row cand[i], i < ctr[APPENDED]; nothing when the counter ran past cap.  q64 on the device.
+hipError_t launch_range_rescore(hipStream_t s, int metric, const double* master, const double* q64, const uint32_t* cand,
+                                uint32_t cap, uint32_t dim, double* scores, uint32_t* ctr);
+// The cut: slots i < m with scores[i] >= min_score are appended to (keys, pv) = (descending-order key of the score,
+// position << 32 | i), position = cand ? cand[i] : i; ctr[TOTAL] counts them, entries past store_cap are only counted.
+// m = *m_ptr when given (nothing is done when it exceeds m_max), else m_max.
+hipError_t launch_range_cut(hipStream_t s, const double* scores, const uint32_t* cand, const uint32_t* m_ptr, uint64_t m_max,
+                            double min_score, uint64_t* keys, uint64_t* pv, uint64_t store_cap, uint32_t* ctr);
+// Rank (keys, pv) by (score desc, position asc) and write the first min(total, k) (position, score).  total_ptr != nullptr:
+// the count is still the device's -- ranks up to RANGE_SMALL survivors (more: the output is unspecified, call again with
+// the count); else `total` entries, buffers of sort_capacity_for(total).
+hipError_t launch_range_rank(hipStream_t s, uint64_t* keys, uint64_t* pv, const double* scores, const uint32_t* total_ptr,
+                             uint64_t total, uint64_t k, uint32_t* out_pos, double* out_scores);
+
 // Exact path, k <= KP: top-k of scores[] by (score desc, pos asc).
 int select_grid_for(uint64_t n);
 // Ranks 64 r .. 64 r + k - 1 of the exact order: `after` = the (full, k = 64) block of round r - 1, nullptr for r = 0.
