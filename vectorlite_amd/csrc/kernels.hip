@@ -22,6 +22,7 @@
 //   * k_hnsw_dist: the four HNSW distance callbacks, f64 reference order, Rust `as u64` semantics.
 #include "kernels.hpp"
 #include "device_common.hpp"
+#include "scan_stream.hpp"
 #include "score_bound.hpp"
 
 #include <math.h>
@@ -29,6 +30,7 @@
 #include <string.h>
 
 #include <mutex>
+#include <tuple>
 #include <type_traits>
 
 namespace vl {
@@ -100,92 +102,24 @@ __device__ __forceinline__ float scan_key(float sum, float inv_norm)
     return -sum;
 }
 
-// The query arrives as f64 (the reference's `search(&[f64])`); each lane rounds its own slice to
-// f32 (round to nearest even, the same rounding the slab rows got at ingest).  Columns past `dim`
-// (slab padding) read as zero.
-__device__ __forceinline__ f32x4 load_q4(const double* __restrict__ q64, uint32_t j4, uint32_t dim)
-{
-    // Clamped, never predicated: `i < dim ? q64[i] : 0` makes hipcc branch around every load and wait for
-    // each in turn (48 dependent L2 round trips in the prologue of every wave of the dim-384 scan).
-    const uint32_t i = j4 * 4, last = dim - 1;
-    const double v0 = q64[i + 0 < dim ? i + 0 : last];
-    const double v1 = q64[i + 1 < dim ? i + 1 : last];
-    const double v2 = q64[i + 2 < dim ? i + 2 : last];
-    const double v3 = q64[i + 3 < dim ? i + 3 : last];
-    f32x4 r;
-    r.x = i + 0 < dim ? (float)v0 : 0.0f;
-    r.y = i + 1 < dim ? (float)v1 : 0.0f;
-    r.z = i + 2 < dim ? (float)v2 : 0.0f;
-    r.w = i + 3 < dim ? (float)v3 : 0.0f;
-    return r;
-}
-
-template <int G>
-__device__ __forceinline__ float group_reduce(float a)
-{
-#pragma unroll
-    for (int o = G / 2; o >= 1; o >>= 1) a += __shfl_xor(a, o);
-    return a;
-}
-
-// Specialised: ld4 == G * VPL float4 per row, U row groups in flight per wave.  `qv` is the lane's slice of the
-// f32 query (columns c + G j), loaded by the kernel entry that wraps this body.
-template <int METRIC, int G, int VPL, int U>
-__device__ __forceinline__ void scan_body(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
-                                          const f32x4 (&qv)[VPL], uint32_t n, Cand32* __restrict__ out)
-{
-    constexpr int RPS = WAVE / G;  // rows per step of one wave
-    constexpr uint32_t LD4 = G * VPL;
-    __shared__ Cand32 sh[4 * WAVE];
-
-    const int lane = lane_id();
-    const int wave = threadIdx.x >> 6;
-    const int g = lane / G, c = lane % G;
-
-    const uint32_t n_steps = (n + RPS - 1) / RPS;
-    const uint32_t n_waves = gridDim.x * 4;
-    const uint32_t wave_global = blockIdx.x * 4 + wave;
-
-    TopList<float> L;
-    L.init();
-
-    for (uint32_t s0 = wave_global; s0 < n_steps; s0 += n_waves * U) {
-        f32x4 x[U][VPL];
-        uint32_t row[U];
-        float inv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t s = s0 + (uint32_t)u * n_waves;
-            row[u] = s < n_steps ? s * RPS + g : n;  // n marks "no row"
-            const uint32_t r = row[u] < n ? row[u] : n - 1;  // clamp: loads stay in bounds
-            const f32x4* p = slab + (size_t)r * LD4 + c;
-#pragma unroll
-            for (int j = 0; j < VPL; ++j) x[u][j] = __builtin_nontemporal_load(p + G * j);
-            inv[u] = 1.0f;
-            if (METRIC == COSINE) inv[u] = inv_norm[r];  // issued with the row loads, not after them
-        }
-        // every load of this iteration is issued before the first FMA: left alone, the scheduler
-        // trades memory-level parallelism for registers and serialises the loads two at a time
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            float a = 0.0f;
-#pragma unroll
-            for (int j = 0; j < VPL; ++j) a = acc4<METRIC>(a, x[u][j], qv[j]);
-            a = group_reduce<G>(a);
-            const float key = scan_key<METRIC>(a, inv[u]);
-            L.offer(key, row[u], row[u] < n && c == 0);
-        }
+// The f32 slab as scan_stream()'s row format: a chunk is four columns, cosine carries 1/|row| with the row loads.
+template <int METRIC, int VPL_>
+struct F32Rows {
+    typedef f32x4 Chunk;
+    typedef f32x4 Query;
+    typedef float Scalars;
+    static constexpr int VPL = VPL_;
+    const f32x4* __restrict__ slab;
+    const float* __restrict__ inv_norm;
+    __device__ __forceinline__ float load_scalars(uint32_t r) const
+    {
+        float inv = 1.0f;
+        if (METRIC == COSINE) inv = inv_norm[r];
+        return inv;
     }
-
-    block_merge<float, Cand32, 4>(L, sh);
-    if (wave == 0) {
-        Cand32 e;
-        e.key = L.key;
-        e.pos = L.pos;
-        out[(size_t)blockIdx.x * KP + lane] = e;
-    }
-}
+    static __device__ __forceinline__ float accumulate(float a, const f32x4 x, const f32x4 q) { return acc4<METRIC>(a, x, q); }
+    __device__ __forceinline__ float key(float sum, float inv) const { return scan_key<METRIC>(sum, inv); }
+};
 
 // K1, the single-query form: the f32 query travels IN THE KERNEL ARGUMENTS (rows of up to SCAN_QARG_FLOATS padded
 // columns = 3 KB of the 4 KB kernarg segment), rounded on the host exactly as load_q4 rounds it here (f64 -> f32,
@@ -194,182 +128,117 @@ struct alignas(16) ScanQArg {
     float v[SCAN_QARG_FLOATS];
 };
 
+// The lane's slice of the f32 query (columns c + G j), from the kernel arguments ...
+template <int G, int VPL>
+__device__ __forceinline__ void load_query(f32x4 (&qv)[VPL], const ScanQArg& qa)
+{
+    static_assert(G * VPL * 4 <= SCAN_QARG_FLOATS, "row too long for the kernarg query");
+    const int c = lane_id() % G;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) qv[j] = *reinterpret_cast<const f32x4*>(&qa.v[4 * (c + G * j)]);
+}
+
+// ... or from the f64 query in device memory (rows longer than the kernarg form holds; the multi-list k > 60 path,
+// which stages the query on the device anyway).
+template <int G, int VPL>
+__device__ __forceinline__ void load_query(f32x4 (&qv)[VPL], const double* __restrict__ q64, uint32_t dim)
+{
+    const int c = lane_id() % G;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) qv[j] = load_q4(q64, c + G * j, dim);
+}
+
+// Specialised: ld4 == G * VPL float4 per row, U row groups in flight per wave.
 template <int METRIC, int G, int VPL, int U>
 __global__ __launch_bounds__(256) void k_scan(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
                                               uint32_t n, Cand32* __restrict__ out, const ScanQArg qa)
 {
-    static_assert(G * VPL * 4 <= SCAN_QARG_FLOATS, "row too long for the kernarg query");
-    const int c = lane_id() % G;
     f32x4 qv[VPL];
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) qv[j] = *reinterpret_cast<const f32x4*>(&qa.v[4 * (c + G * j)]);
-    scan_body<METRIC, G, VPL, U>(slab, inv_norm, qv, n, out);
+    load_query<G>(qv, qa);
+    scan_stream<G, U>(F32Rows<METRIC, VPL>{slab, inv_norm}, qv, AllRows{}, n, TopSink(out));
 }
 
-// The same scan with the f64 query in device memory (rows longer than the kernarg form holds; the multi-list
-// k > 60 path, which stages the query on the device anyway).
 template <int METRIC, int G, int VPL, int U>
 __global__ __launch_bounds__(256) void k_scan_q64(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
                                                   const double* __restrict__ q64, uint32_t dim, uint32_t n,
                                                   Cand32* __restrict__ out)
 {
-    const int c = lane_id() % G;
     f32x4 qv[VPL];
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) qv[j] = load_q4(q64, c + G * j, dim);
-    scan_body<METRIC, G, VPL, U>(slab, inv_norm, qv, n, out);
+    load_query<G>(qv, q64, dim);
+    scan_stream<G, U>(F32Rows<METRIC, VPL>{slab, inv_norm}, qv, AllRows{}, n, TopSink(out));
 }
 
-// Generic: any ld4 (float4 per row), G = lanes per row (power of two <= 64).
-template <int METRIC, int G>
-__global__ __launch_bounds__(256) void k_scan_generic(const f32x4* __restrict__ slab,
-                                                      const float* __restrict__ inv_norm,
-                                                      const double* __restrict__ q64, uint32_t dim, uint32_t n,
-                                                      uint32_t ld4, Cand32* __restrict__ out)
+// Generic: any ld4 (float4 per row), G = lanes per row (power of two <= 64), one row group per step, the query read
+// as it is needed.  scan_stream()'s row sources and sinks; the same acc4 column order, group_reduce and scan_key, so a
+// row's key does not depend on which of the three families scores it.  A listed row's entry for the NEXT step is
+// requested before this step's row is read.
+template <int METRIC, int G, class Rows, class Sink>
+__device__ __forceinline__ void scan_stream_generic(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
+                                                    const double* __restrict__ q64, uint32_t dim, uint32_t n, uint32_t ld4,
+                                                    const Rows rows, Sink sink)
 {
     constexpr int RPS = WAVE / G;
-    __shared__ Cand32 sh[4 * WAVE];
-
     const int lane = lane_id();
     const int wave = threadIdx.x >> 6;
     const int g = lane / G, c = lane % G;
-
     const uint32_t n_steps = (n + RPS - 1) / RPS;
     const uint32_t n_waves = gridDim.x * 4;
 
-    TopList<float> L;
-    L.init();
-
-    for (uint32_t s = blockIdx.x * 4 + wave; s < n_steps; s += n_waves) {
-        const uint32_t row = s * RPS + g;
-        const bool valid = row < n;
-        const uint32_t r = valid ? row : n - 1;
+    uint32_t s = blockIdx.x * 4 + wave;
+    uint32_t i_next = s < n_steps ? s * RPS + g : n;  // n marks "no row"
+    uint32_t p_next = rows.at(i_next, n);
+    for (; s < n_steps; s += n_waves) {
+        const bool valid = i_next < n;
+        const uint32_t pos = p_next;
+        const uint32_t sn = s + n_waves;
+        i_next = sn < n_steps ? sn * RPS + g : n;
+        p_next = rows.at(i_next, n);
+        const uint32_t r = rows.load_row(pos, valid, n);
         const f32x4* p = slab + (size_t)r * ld4;
         float a = 0.0f;
         for (uint32_t j = c; j < ld4; j += G) a = acc4<METRIC>(a, p[j], load_q4(q64, j, dim));
         a = group_reduce<G>(a);
         float inv = 1.0f;
         if (METRIC == COSINE) inv = inv_norm[r];
-        L.offer(scan_key<METRIC>(a, inv), row, valid && c == 0);
+        sink.offer(0, scan_key<METRIC>(a, inv), pos, valid && c == 0);
+        sink.step();
     }
-
-    block_merge<float, Cand32, 4>(L, sh);
-    if (wave == 0) {
-        Cand32 e;
-        e.key = L.key;
-        e.pos = L.pos;
-        out[(size_t)blockIdx.x * KP + lane] = e;
-    }
+    sink.finish();
 }
 
-// K1 over a subset: the rows are plist[0..m) (ascending storage positions, an id filter's resolution).  The same per-row
-// arithmetic as scan_body -- acc4 in column order, group_reduce, scan_key -- so a row's key is the one k_scan gives it; the
-// list entries carry STORAGE positions and reach offer() in ascending order within each wave's stream, as in k_scan.
-// A separate body (scan_body is the headline kernel's and stays as it is): the only difference is the row index, which is
-// one dependent read away -- the list entries of the NEXT iteration are requested before this iteration's row loads, so
-// that read is in flight while the rows stream and never stands alone in front of them.
-template <int METRIC, int G, int VPL, int U>
-__device__ __forceinline__ void scan_subset_body(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
-                                                 const uint32_t* __restrict__ plist, const f32x4 (&qv)[VPL], uint32_t m,
-                                                 Cand32* __restrict__ out)
+template <int METRIC, int G>
+__global__ __launch_bounds__(256) void k_scan_generic(const f32x4* __restrict__ slab,
+                                                      const float* __restrict__ inv_norm,
+                                                      const double* __restrict__ q64, uint32_t dim, uint32_t n,
+                                                      uint32_t ld4, Cand32* __restrict__ out)
 {
-    constexpr int RPS = WAVE / G;
-    constexpr uint32_t LD4 = G * VPL;
-    __shared__ Cand32 sh[4 * WAVE];
-
-    const int lane = lane_id();
-    const int wave = threadIdx.x >> 6;
-    const int g = lane / G, c = lane % G;
-
-    const uint32_t n_steps = (m + RPS - 1) / RPS;
-    const uint32_t n_waves = gridDim.x * 4;
-    const uint32_t wave_global = blockIdx.x * 4 + wave;
-    const uint32_t stride = n_waves * U;
-
-    TopList<float> L;
-    L.init();
-
-    uint32_t pn[U];
-    bool vn[U];
-    auto fetch = [&](uint32_t s0) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t s = s0 + (uint32_t)u * n_waves;
-            const uint32_t i = s < n_steps ? s * RPS + g : m;  // m marks "no row"
-            vn[u] = i < m;
-            pn[u] = plist[i < m ? i : m - 1];  // clamp: the load stays in bounds
-        }
-    };
-    fetch(wave_global);
-    for (uint32_t s0 = wave_global; s0 < n_steps; s0 += stride) {
-        uint32_t pos[U];
-        bool valid[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            pos[u] = pn[u];
-            valid[u] = vn[u];
-        }
-        fetch(s0 + stride);
-        __builtin_amdgcn_sched_barrier(0);  // the list loads go out in front of the row loads
-        f32x4 x[U][VPL];
-        float inv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const f32x4* p = slab + (size_t)pos[u] * LD4 + c;
-#pragma unroll
-            for (int j = 0; j < VPL; ++j) x[u][j] = __builtin_nontemporal_load(p + G * j);
-            inv[u] = 1.0f;
-            if (METRIC == COSINE) inv[u] = inv_norm[pos[u]];
-        }
-        __builtin_amdgcn_sched_barrier(0);  // every row load of this iteration is issued before the first FMA
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            float a = 0.0f;
-#pragma unroll
-            for (int j = 0; j < VPL; ++j) a = acc4<METRIC>(a, x[u][j], qv[j]);
-            a = group_reduce<G>(a);
-            const float key = scan_key<METRIC>(a, inv[u]);
-            L.offer(key, pos[u], valid[u] && c == 0);
-        }
-    }
-
-    block_merge<float, Cand32, 4>(L, sh);
-    if (wave == 0) {
-        Cand32 e;
-        e.key = L.key;
-        e.pos = L.pos;
-        out[(size_t)blockIdx.x * KP + lane] = e;
-    }
+    scan_stream_generic<METRIC, G>(slab, inv_norm, q64, dim, n, ld4, AllRows{}, TopSink(out));
 }
 
-// the kernel-argument query (k_scan's form)
+// K1 over a subset: the rows are plist[0..m) (ascending storage positions, an id filter's resolution).  The list
+// entries carry STORAGE positions and reach the sink in ascending order within each wave's stream, as in k_scan.
+// The kernel-argument query (k_scan's form) ...
 template <int METRIC, int G, int VPL, int U>
 __global__ __launch_bounds__(256) void k_scan_subset(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
                                                      const uint32_t* __restrict__ plist, uint32_t m, Cand32* __restrict__ out,
                                                      const ScanQArg qa)
 {
-    static_assert(G * VPL * 4 <= SCAN_QARG_FLOATS, "row too long for the kernarg query");
-    const int c = lane_id() % G;
     f32x4 qv[VPL];
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) qv[j] = *reinterpret_cast<const f32x4*>(&qa.v[4 * (c + G * j)]);
-    scan_subset_body<METRIC, G, VPL, U>(slab, inv_norm, plist, qv, m, out);
+    load_query<G>(qv, qa);
+    scan_stream<G, U>(F32Rows<METRIC, VPL>{slab, inv_norm}, qv, ListedRows{plist}, m, TopSink(out));
 }
 
-// the f64 query in device memory (k_scan_q64's form: strides past the kernarg query)
+// ... and the f64 query in device memory (k_scan_q64's form: strides past the kernarg query)
 template <int METRIC, int G, int VPL, int U>
 __global__ __launch_bounds__(256) void k_scan_subset_q64(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
                                                          const uint32_t* __restrict__ plist, const double* __restrict__ q64,
                                                          uint32_t dim, uint32_t m, Cand32* __restrict__ out)
 {
-    const int c = lane_id() % G;
     f32x4 qv[VPL];
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) qv[j] = load_q4(q64, c + G * j, dim);
-    scan_subset_body<METRIC, G, VPL, U>(slab, inv_norm, plist, qv, m, out);
+    load_query<G>(qv, q64, dim);
+    scan_stream<G, U>(F32Rows<METRIC, VPL>{slab, inv_norm}, qv, ListedRows{plist}, m, TopSink(out));
 }
 
-// Generic subset scan: any ld4, G lanes per row (k_scan_generic's arithmetic and order).
 template <int METRIC, int G>
 __global__ __launch_bounds__(256) void k_scan_subset_generic(const f32x4* __restrict__ slab,
                                                              const float* __restrict__ inv_norm,
@@ -377,44 +246,7 @@ __global__ __launch_bounds__(256) void k_scan_subset_generic(const f32x4* __rest
                                                              const double* __restrict__ q64, uint32_t dim, uint32_t m,
                                                              uint32_t ld4, Cand32* __restrict__ out)
 {
-    constexpr int RPS = WAVE / G;
-    __shared__ Cand32 sh[4 * WAVE];
-
-    const int lane = lane_id();
-    const int wave = threadIdx.x >> 6;
-    const int g = lane / G, c = lane % G;
-
-    const uint32_t n_steps = (m + RPS - 1) / RPS;
-    const uint32_t n_waves = gridDim.x * 4;
-
-    TopList<float> L;
-    L.init();
-
-    uint32_t s = blockIdx.x * 4 + wave;
-    uint32_t i_next = s < n_steps ? s * RPS + g : m;
-    uint32_t p_next = plist[i_next < m ? i_next : m - 1];
-    for (; s < n_steps; s += n_waves) {
-        const bool valid = i_next < m;
-        const uint32_t r = p_next;
-        const uint32_t sn = s + n_waves;
-        i_next = sn < n_steps ? sn * RPS + g : m;
-        p_next = plist[i_next < m ? i_next : m - 1];  // next row's list entry, in flight during this row
-        const f32x4* p = slab + (size_t)r * ld4;
-        float a = 0.0f;
-        for (uint32_t j = c; j < ld4; j += G) a = acc4<METRIC>(a, p[j], load_q4(q64, j, dim));
-        a = group_reduce<G>(a);
-        float inv = 1.0f;
-        if (METRIC == COSINE) inv = inv_norm[r];
-        L.offer(scan_key<METRIC>(a, inv), r, valid && c == 0);
-    }
-
-    block_merge<float, Cand32, 4>(L, sh);
-    if (wave == 0) {
-        Cand32 e;
-        e.key = L.key;
-        e.pos = L.pos;
-        out[(size_t)blockIdx.x * KP + lane] = e;
-    }
+    scan_stream_generic<METRIC, G>(slab, inv_norm, q64, dim, m, ld4, ListedRows{plist}, TopSink(out));
 }
 
 // Resolution of an id filter: which storage positions hold an id of the sorted, deduplicated set fids[0..nf).  Workgroup b
@@ -494,133 +326,14 @@ __global__ __launch_bounds__(256) void k_filter_compact(const unsigned long long
 }
 
 // ---------------------------------------------------------------------------------------------
-// Range search: the scan that APPENDS.  scan_body's loop with the TopList taken out: the same
-// 16-byte non-temporal row loads, all loads of an iteration issued before the first FMA, the same acc4 column order,
-// group_reduce and scan_key, so a row's key is bit for bit the one k_scan gives it.  A row is a candidate unless
-// key <= tau (tau: the largest key whose bound_for_key is below the caller's score threshold, chosen on the host; a NaN
-// tau or key fails the comparison and keeps the row).  Lane c == 0 of each row group tests; the wave ballots, ONE lane
-// reserves the slots of all U row groups with one global atomic add on *ctr, the flagged lanes store their storage
-// positions.  The counter keeps counting past `cap`; stores past it are dropped (the host then takes the exact route).
-// No LDS list, no block merge, no partial lists.  SUBSET: the rows are plist[0..n) with scan_subset_body's prefetch
-// discipline (the next iteration's list entries are requested before this iteration's row loads).
+// Range search: the f32 scan with RangeSink in the TopList's place, over every row or
+// (SUBSET) over plist[0..n).  A row's key is bit for bit the one k_scan gives it.
 // ---------------------------------------------------------------------------------------------
-template <int U>
-__device__ __forceinline__ void range_append(const bool (&hit)[U], const uint32_t (&pos)[U], uint32_t* __restrict__ cand,
-                                             uint32_t cap, uint32_t* __restrict__ ctr)
+template <bool SUBSET>
+__device__ __forceinline__ auto range_rows(const uint32_t* __restrict__ plist)
 {
-    const int lane = lane_id();
-    unsigned long long bal[U];
-    uint32_t total = 0;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        bal[u] = __ballot(hit[u]);
-        total += (uint32_t)__popcll(bal[u]);
-    }
-    if (total == 0) return;  // wave-uniform: a selective threshold leaves the stream alone
-    uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(ctr, total);
-    base = __shfl(base, 0);
-    const unsigned long long below = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const uint32_t slot = base + (uint32_t)__popcll(bal[u] & below);
-        if (hit[u] && slot < cap) cand[slot] = pos[u];
-        base += (uint32_t)__popcll(bal[u]);
-    }
-}
-
-template <int METRIC, int G, int VPL, int U, bool SUBSET>
-__device__ __forceinline__ void scan_range_body(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
-                                                const uint32_t* __restrict__ plist, const f32x4 (&qv)[VPL], uint32_t n,
-                                                float tau, uint32_t* __restrict__ cand, uint32_t cap,
-                                                uint32_t* __restrict__ ctr)
-{
-    constexpr int RPS = WAVE / G;  // rows per step of one wave
-    constexpr uint32_t LD4 = G * VPL;
-    const int lane = lane_id();
-    const int wave = threadIdx.x >> 6;
-    const int g = lane / G, c = lane % G;
-    const uint32_t n_steps = (n + RPS - 1) / RPS;
-    const uint32_t n_waves = gridDim.x * 4;
-    const uint32_t wave_global = blockIdx.x * 4 + wave;
-    const uint32_t stride = n_waves * U;
-
-    if constexpr (!SUBSET) {
-        for (uint32_t s0 = wave_global; s0 < n_steps; s0 += stride) {
-            f32x4 x[U][VPL];
-            uint32_t row[U];
-            float inv[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const uint32_t s = s0 + (uint32_t)u * n_waves;
-                row[u] = s < n_steps ? s * RPS + g : n;  // n marks "no row"
-                const uint32_t r = row[u] < n ? row[u] : n - 1;  // clamp: loads stay in bounds
-                const f32x4* p = slab + (size_t)r * LD4 + c;
-#pragma unroll
-                for (int j = 0; j < VPL; ++j) x[u][j] = __builtin_nontemporal_load(p + G * j);
-                inv[u] = 1.0f;
-                if (METRIC == COSINE) inv[u] = inv_norm[r];
-            }
-            __builtin_amdgcn_sched_barrier(0);  // every load of this iteration is issued before the first FMA
-            bool hit[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                float a = 0.0f;
-#pragma unroll
-                for (int j = 0; j < VPL; ++j) a = acc4<METRIC>(a, x[u][j], qv[j]);
-                a = group_reduce<G>(a);
-                const float key = scan_key<METRIC>(a, inv[u]);
-                hit[u] = row[u] < n && c == 0 && !(key <= tau);
-            }
-            range_append<U>(hit, row, cand, cap, ctr);
-        }
-    } else {
-        uint32_t pn[U];
-        bool vn[U];
-        auto fetch = [&](uint32_t s0) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const uint32_t s = s0 + (uint32_t)u * n_waves;
-                const uint32_t i = s < n_steps ? s * RPS + g : n;  // n marks "no row"
-                vn[u] = i < n;
-                pn[u] = plist[i < n ? i : n - 1];  // clamp: the load stays in bounds
-            }
-        };
-        fetch(wave_global);
-        for (uint32_t s0 = wave_global; s0 < n_steps; s0 += stride) {
-            uint32_t pos[U];
-            bool valid[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                pos[u] = pn[u];
-                valid[u] = vn[u];
-            }
-            fetch(s0 + stride);
-            __builtin_amdgcn_sched_barrier(0);  // the list loads go out in front of the row loads
-            f32x4 x[U][VPL];
-            float inv[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const f32x4* p = slab + (size_t)pos[u] * LD4 + c;
-#pragma unroll
-                for (int j = 0; j < VPL; ++j) x[u][j] = __builtin_nontemporal_load(p + G * j);
-                inv[u] = 1.0f;
-                if (METRIC == COSINE) inv[u] = inv_norm[pos[u]];
-            }
-            __builtin_amdgcn_sched_barrier(0);  // every row load of this iteration is issued before the first FMA
-            bool hit[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                float a = 0.0f;
-#pragma unroll
-                for (int j = 0; j < VPL; ++j) a = acc4<METRIC>(a, x[u][j], qv[j]);
-                a = group_reduce<G>(a);
-                const float key = scan_key<METRIC>(a, inv[u]);
-                hit[u] = valid[u] && c == 0 && !(key <= tau);
-            }
-            range_append<U>(hit, pos, cand, cap, ctr);
-        }
-    }
+    if constexpr (SUBSET) return ListedRows{plist};
+    else return AllRows{};
 }
 
 // the kernel-argument query (k_scan's form)
@@ -630,12 +343,9 @@ __global__ __launch_bounds__(256) void k_scan_range(const f32x4* __restrict__ sl
                                                     uint32_t* __restrict__ cand, uint32_t cap, uint32_t* __restrict__ ctr,
                                                     const ScanQArg qa)
 {
-    static_assert(G * VPL * 4 <= SCAN_QARG_FLOATS, "row too long for the kernarg query");
-    const int c = lane_id() % G;
     f32x4 qv[VPL];
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) qv[j] = *reinterpret_cast<const f32x4*>(&qa.v[4 * (c + G * j)]);
-    scan_range_body<METRIC, G, VPL, U, SUBSET>(slab, inv_norm, plist, qv, n, tau, cand, cap, ctr);
+    load_query<G>(qv, qa);
+    scan_stream<G, U>(F32Rows<METRIC, VPL>{slab, inv_norm}, qv, range_rows<SUBSET>(plist), n, RangeSink<U>(tau, cand, cap, ctr));
 }
 
 // the f64 query in device memory (k_scan_q64's form: strides past the kernarg query)
@@ -646,14 +356,11 @@ __global__ __launch_bounds__(256) void k_scan_range_q64(const f32x4* __restrict_
                                                         uint32_t* __restrict__ cand, uint32_t cap,
                                                         uint32_t* __restrict__ ctr)
 {
-    const int c = lane_id() % G;
     f32x4 qv[VPL];
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) qv[j] = load_q4(q64, c + G * j, dim);
-    scan_range_body<METRIC, G, VPL, U, SUBSET>(slab, inv_norm, plist, qv, n, tau, cand, cap, ctr);
+    load_query<G>(qv, q64, dim);
+    scan_stream<G, U>(F32Rows<METRIC, VPL>{slab, inv_norm}, qv, range_rows<SUBSET>(plist), n, RangeSink<U>(tau, cand, cap, ctr));
 }
 
-// Generic: any ld4, G lanes per row (k_scan_generic's arithmetic and order; SUBSET: k_scan_subset_generic's prefetch).
 template <int METRIC, int G, bool SUBSET>
 __global__ __launch_bounds__(256) void k_scan_range_generic(const f32x4* __restrict__ slab,
                                                             const float* __restrict__ inv_norm,
@@ -662,35 +369,7 @@ __global__ __launch_bounds__(256) void k_scan_range_generic(const f32x4* __restr
                                                             uint32_t ld4, float tau, uint32_t* __restrict__ cand,
                                                             uint32_t cap, uint32_t* __restrict__ ctr)
 {
-    constexpr int RPS = WAVE / G;
-    const int lane = lane_id();
-    const int wave = threadIdx.x >> 6;
-    const int g = lane / G, c = lane % G;
-    const uint32_t n_steps = (n + RPS - 1) / RPS;
-    const uint32_t n_waves = gridDim.x * 4;
-
-    uint32_t s = blockIdx.x * 4 + wave;
-    uint32_t i_next = s < n_steps ? s * RPS + g : n;
-    uint32_t p_next = i_next;
-    if (SUBSET) p_next = plist[i_next < n ? i_next : n - 1];
-    for (; s < n_steps; s += n_waves) {
-        const bool valid = i_next < n;
-        const uint32_t pos[1] = {p_next};
-        const uint32_t sn = s + n_waves;
-        i_next = sn < n_steps ? sn * RPS + g : n;
-        p_next = i_next;
-        if (SUBSET) p_next = plist[i_next < n ? i_next : n - 1];  // next row's list entry, in flight during this row
-        const uint32_t r = SUBSET ? pos[0] : (valid ? pos[0] : n - 1);
-        const f32x4* p = slab + (size_t)r * ld4;
-        float a = 0.0f;
-        for (uint32_t j = c; j < ld4; j += G) a = acc4<METRIC>(a, p[j], load_q4(q64, j, dim));
-        a = group_reduce<G>(a);
-        float inv = 1.0f;
-        if (METRIC == COSINE) inv = inv_norm[r];
-        const float key = scan_key<METRIC>(a, inv);
-        const bool hit[1] = {valid && c == 0 && !(key <= tau)};
-        range_append<1>(hit, pos, cand, cap, ctr);
-    }
+    scan_stream_generic<METRIC, G>(slab, inv_norm, q64, dim, n, ld4, range_rows<SUBSET>(plist), RangeSink<1>(tau, cand, cap, ctr));
 }
 
 // K3: small-batch scan.  One pass over the slab serves QB queries: each row group is loaded ONCE into
@@ -1984,30 +1663,54 @@ struct ScanShape {
     int g, vpl, u, bpc;
 };
 
+constexpr int SCAN_TABLE[][4] = {
+#define VL_ROW(G, VPL, U, BPC) {G, VPL, U, BPC},
+    VL_SCAN_VARIANTS(VL_ROW)
+#undef VL_ROW
+};
+constexpr int SCAN_TABLE_N = (int)(sizeof(SCAN_TABLE) / sizeof(SCAN_TABLE[0]));
+
+// the default entry of a stride: the first one with that G * VPL; -1: the stride is not specialised
+constexpr int default_scan_entry(uint32_t ld4)
+{
+    for (int i = 0; i < SCAN_TABLE_N; ++i)
+        if ((uint32_t)(SCAN_TABLE[i][0] * SCAN_TABLE[i][1]) == ld4) return i;
+    return -1;
+}
+
+constexpr bool is_default_scan_shape(int g, int vpl, int u)
+{
+    const int i = default_scan_entry((uint32_t)(g * vpl));
+    return i >= 0 && SCAN_TABLE[i][0] == g && SCAN_TABLE[i][1] == vpl && SCAN_TABLE[i][2] == u;
+}
+
+ScanShape scan_shape_at(int i, uint32_t ld4)
+{
+    if (i < 0) return {false, lanes_per_row(ld4), 0, 1, 4};  // the generic kernel
+    return {true, SCAN_TABLE[i][0], SCAN_TABLE[i][1], SCAN_TABLE[i][2], SCAN_TABLE[i][3]};
+}
+
+// The shape the subset and range scans run, and k_scan unless a tuning variable picks another: with it a row's key is
+// the same in all three.
+ScanShape default_scan_shape(uint32_t ld4) { return scan_shape_at(default_scan_entry(ld4), ld4); }
+
+// k_scan's shape: the default one, or the entry VL_SCAN_G / VL_SCAN_U name
 ScanShape scan_shape(uint32_t ld4)
 {
-    static const int table[][4] = {
-#define VL_ROW(G, VPL, U, BPC) {G, VPL, U, BPC},
-        VL_SCAN_VARIANTS(VL_ROW)
-#undef VL_ROW
-    };
     const int want_g = env_int("VL_SCAN_G", 0), want_u = env_int("VL_SCAN_U", 0);
-    const int n = (int)(sizeof(table) / sizeof(table[0]));
-    int pick = -1;
-    for (int i = 0; i < n; ++i) {
-        if ((uint32_t)(table[i][0] * table[i][1]) != ld4) continue;
-        if (pick < 0) pick = i;
-        if (want_g && table[i][0] == want_g && (!want_u || table[i][2] == want_u)) {
+    int pick = default_scan_entry(ld4);
+    for (int i = pick; i >= 0 && i < SCAN_TABLE_N; ++i) {
+        if ((uint32_t)(SCAN_TABLE[i][0] * SCAN_TABLE[i][1]) != ld4) continue;
+        if (want_g && SCAN_TABLE[i][0] == want_g && (!want_u || SCAN_TABLE[i][2] == want_u)) {
             pick = i;
             break;
         }
-        if (!want_g && want_u && table[i][2] == want_u && table[i][0] == table[pick][0]) {
+        if (!want_g && want_u && SCAN_TABLE[i][2] == want_u && SCAN_TABLE[i][0] == SCAN_TABLE[pick][0]) {
             pick = i;
             break;
         }
     }
-    if (pick < 0) return {false, lanes_per_row(ld4), 0, 1, 4};
-    return {true, table[pick][0], table[pick][1], table[pick][2], table[pick][3]};
+    return scan_shape_at(pick, ld4);
 }
 }  // namespace
 
@@ -2072,69 +1775,114 @@ extern "C" int vl_dbg_read_stamps(unsigned long long* out)
 }
 #endif
 
+namespace {
+// One f32 scan family = three kernels (kernel-argument query, f64 query in device memory, run-time stride) whose
+// argument lists are  head..., [q64, dim,] n, [ld4,] tail..., [qa]:  `head` / `tail` are what the family puts in front
+// of and behind the arguments every scan takes.  A family names its kernels and says
+//   ALL_SHAPES         every VL_SCAN_VARIANTS entry is compiled (k_scan: the tuning variables can pick any), or only
+//                      the default entry of each stride
+//   Q64_AT_ANY_STRIDE  the q64 form exists at every specialised stride (k_scan: the k > 60 multi-list path passes no
+//                      host query), or only at strides past the kernel-argument query
+template <int MM>
+struct TopFamily {
+    static constexpr bool ALL_SHAPES = true, Q64_AT_ANY_STRIDE = true;
+    template <int G, int VPL, int U> static auto qarg() { return k_scan<MM, G, VPL, U>; }
+    template <int G, int VPL, int U> static auto q64() { return k_scan_q64<MM, G, VPL, U>; }
+    template <int G> static auto generic() { return k_scan_generic<MM, G>; }
+};
+template <int MM>
+struct SubsetFamily {
+    static constexpr bool ALL_SHAPES = false, Q64_AT_ANY_STRIDE = false;
+    template <int G, int VPL, int U> static auto qarg() { return k_scan_subset<MM, G, VPL, U>; }
+    template <int G, int VPL, int U> static auto q64() { return k_scan_subset_q64<MM, G, VPL, U>; }
+    template <int G> static auto generic() { return k_scan_subset_generic<MM, G>; }
+};
+template <int MM, bool SUBSET>
+struct RangeFamily {
+    static constexpr bool ALL_SHAPES = false, Q64_AT_ANY_STRIDE = false;
+    template <int G, int VPL, int U> static auto qarg() { return k_scan_range<MM, G, VPL, U, SUBSET>; }
+    template <int G, int VPL, int U> static auto q64() { return k_scan_range_q64<MM, G, VPL, U, SUBSET>; }
+    template <int G> static auto generic() { return k_scan_range_generic<MM, G, SUBSET>; }
+};
+
+// does a scan of this shape and stride take its query in the kernel arguments
+bool shape_takes_qarg(const ScanShape& sh, uint32_t ld, const float* q32_host)
+{
+    return q32_host != nullptr && sh.special && ld <= (uint32_t)SCAN_QARG_FLOATS;
+}
+
+// shape match -> kernel-argument or q64 form -> scan_grid -> launch
+template <class Fam, class Head, class Tail>
+hipError_t launch_scan_family(hipStream_t s, const ScanShape& sh, uint64_t n, uint32_t ld, const double* q64, uint32_t dim,
+                              const float* q32_host, const Head& head, const Tail& tail, int* grid)
+{
+    const uint32_t n32 = (uint32_t)n, ld4 = ld / 4;
+    const bool qarg = shape_takes_qarg(sh, ld, q32_host);
+    auto launch = [&](auto kern, const auto& mid, const auto& last) {
+        *grid = scan_grid(n, sh, reinterpret_cast<const void*>(kern));
+        std::apply([&](const auto&... a) { hipLaunchKernelGGL(kern, dim3(*grid), dim3(256), 0, s, a...); },
+                   std::tuple_cat(head, mid, tail, last));
+    };
+    if (sh.special) {
+        bool launched = false;
+#define VL_TRY_VARIANT(G, VPL, U, BPC)                                                                      \
+    if constexpr (Fam::ALL_SHAPES || is_default_scan_shape(G, VPL, U)) {                                    \
+        if (!launched && sh.g == G && sh.vpl == VPL && sh.u == U) {                                         \
+            if constexpr (G * VPL * 4 <= SCAN_QARG_FLOATS) {                                                \
+                if (qarg) {                                                                                 \
+                    ScanQArg qa;                                                                            \
+                    memcpy(qa.v, q32_host, (size_t)ld * sizeof(float));                                     \
+                    launch(Fam::template qarg<G, VPL, U>(), std::make_tuple(n32), std::make_tuple(qa));     \
+                    launched = true;                                                                        \
+                }                                                                                           \
+            }                                                                                               \
+            if constexpr (Fam::Q64_AT_ANY_STRIDE || G * VPL * 4 > SCAN_QARG_FLOATS) {                       \
+                if (!launched) {                                                                            \
+                    launch(Fam::template q64<G, VPL, U>(), std::make_tuple(q64, dim, n32), std::tuple<>()); \
+                    launched = true;                                                                        \
+                }                                                                                           \
+            }                                                                                               \
+        }                                                                                                   \
+    }
+        VL_SCAN_VARIANTS(VL_TRY_VARIANT)
+#undef VL_TRY_VARIANT
+        if (!launched) return hipErrorInvalidValue;  // a kernarg-sized stride without its query there
+    } else {
+#define VL_SCAN_GEN(G) \
+    case G: launch(Fam::template generic<G>(), std::make_tuple(q64, dim, n32, ld4), std::tuple<>()); break;
+        switch (sh.g) {
+            VL_SCAN_GEN(1)
+            VL_SCAN_GEN(2)
+            VL_SCAN_GEN(4)
+            VL_SCAN_GEN(8)
+            VL_SCAN_GEN(16)
+            VL_SCAN_GEN(32)
+            VL_SCAN_GEN(64)
+        default: return hipErrorInvalidValue;
+        }
+#undef VL_SCAN_GEN
+    }
+    return hipGetLastError();
+}
+}  // namespace
+
 bool scan_takes_qarg(uint32_t ld)
 {
     if ((ld & 3) || ld > (uint32_t)SCAN_QARG_FLOATS) return false;
-    return scan_shape(ld / 4).special;
+    return default_scan_shape(ld / 4).special;
 }
 
 hipError_t launch_scan(hipStream_t s, int metric, const float* slab, const float* inv_norm, const double* q64,
                        uint64_t n, uint32_t dim, uint32_t ld, Cand32* partials, ScanPlan* plan, const float* q32_host)
 {
     if (n == 0 || n >= 0xFFFFFFFFull || (ld & 3)) return hipErrorInvalidValue;
-    const uint32_t ld4 = ld / 4;
-    const ScanShape sh = scan_shape(ld4);
+    const ScanShape sh = scan_shape(ld / 4);
     const f32x4* slab4 = reinterpret_cast<const f32x4*>(slab);
-    const uint32_t n32 = (uint32_t)n;
-    const bool qarg = q32_host != nullptr && sh.special && ld <= (uint32_t)SCAN_QARG_FLOATS;
-    if (!qarg && !q64) return hipErrorInvalidValue;
+    if (!shape_takes_qarg(sh, ld, q32_host) && !q64) return hipErrorInvalidValue;
     int grid = 0;
     hipError_t rc = dispatch_metric(metric, [&](auto M) -> hipError_t {
-        constexpr int MM = decltype(M)::value;
-        if (sh.special) {
-            bool launched = false;
-#define VL_TRY_VARIANT(G, VPL, U, BPC)                                                                          \
-    if (!launched && sh.g == G && sh.vpl == VPL && sh.u == U) {                                             \
-        if constexpr (G * VPL * 4 <= SCAN_QARG_FLOATS) {                                                     \
-            if (qarg) {                                                                                      \
-                auto kern = k_scan<MM, G, VPL, U>;                                                           \
-                grid = scan_grid(n, sh, reinterpret_cast<const void*>(kern));                                \
-                ScanQArg qa;                                                                                 \
-                memcpy(qa.v, q32_host, (size_t)ld * sizeof(float));                                          \
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, slab4, inv_norm, n32, partials, qa);   \
-                launched = true;                                                                             \
-            }                                                                                                \
-        }                                                                                                    \
-        if (!launched) {                                                                                     \
-            auto kern = k_scan_q64<MM, G, VPL, U>;                                                           \
-            grid = scan_grid(n, sh, reinterpret_cast<const void*>(kern));                                    \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, slab4, inv_norm, q64, dim, n32, partials); \
-            launched = true;                                                                                 \
-        }                                                                                                    \
-    }
-            VL_SCAN_VARIANTS(VL_TRY_VARIANT)
-#undef VL_TRY_VARIANT
-            if (!launched) return hipErrorInvalidValue;
-        } else {
-#define VL_SCAN_GEN(G)                                                                                        \
-    case G: {                                                                                                 \
-        auto kern = k_scan_generic<MM, G>;                                                                    \
-        grid = scan_grid(n, sh, reinterpret_cast<const void*>(kern));                                         \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, slab4, inv_norm, q64, dim, n32, ld4, partials);       \
-    } break;
-            switch (sh.g) {
-                VL_SCAN_GEN(1)
-                VL_SCAN_GEN(2)
-                VL_SCAN_GEN(4)
-                VL_SCAN_GEN(8)
-                VL_SCAN_GEN(16)
-                VL_SCAN_GEN(32)
-                VL_SCAN_GEN(64)
-            default: return hipErrorInvalidValue;
-            }
-#undef VL_SCAN_GEN
-        }
-        return hipGetLastError();
+        return launch_scan_family<TopFamily<decltype(M)::value>>(s, sh, n, ld, q64, dim, q32_host,
+                                                                 std::make_tuple(slab4, inv_norm), std::make_tuple(partials), &grid);
     });
     if (plan) {
         plan->grid = grid;
@@ -2309,82 +2057,23 @@ hipError_t launch_exact_scan_subset(hipStream_t s, int metric, const double* mas
     });
 }
 
-// The subset scan's shapes: for every stride VL_SCAN_VARIANTS specialises, its default entry (the first one with that
-// G * VPL, the shape k_scan runs unless a tuning variable picks another), so that a row's key is k_scan's; other strides
-// take the generic kernel with k_scan_generic's lanes per row.
-#define VL_SUBSET_VARIANTS(X) X(8, 4, 3, 3) X(8, 8, 2, 3) X(8, 12, 1, 3) X(8, 16, 1, 3) X(16, 12, 1, 3) X(16, 16, 1, 3) X(16, 24, 1, 2)
-
-bool scan_subset_takes_qarg(uint32_t ld)
-{
-    if ((ld & 3) || ld > (uint32_t)SCAN_QARG_FLOATS) return false;
-    bool special = false;
-#define VL_CHK(G, VPL, U, BPC) special = special || (uint32_t)(G * VPL) == ld / 4;
-    VL_SUBSET_VARIANTS(VL_CHK)
-#undef VL_CHK
-    return special;
-}
+// The subset scan runs the default shape of every stride VL_SCAN_VARIANTS specialises, so that a row's key is k_scan's;
+// other strides take the generic kernel with k_scan_generic's lanes per row.
+bool scan_subset_takes_qarg(uint32_t ld) { return scan_takes_qarg(ld); }
 
 hipError_t launch_scan_subset(hipStream_t s, int metric, const float* slab, const float* inv_norm, const uint32_t* plist,
                               uint64_t m, const double* q64, uint32_t dim, uint32_t ld, Cand32* partials, ScanPlan* plan,
                               const float* q32_host)
 {
     if (m == 0 || m >= 0xFFFFFFFFull || (ld & 3)) return hipErrorInvalidValue;
-    const uint32_t ld4 = ld / 4;
+    const ScanShape sh = default_scan_shape(ld / 4);
     const f32x4* slab4 = reinterpret_cast<const f32x4*>(slab);
-    const uint32_t m32 = (uint32_t)m;
-    ScanShape sh{false, lanes_per_row(ld4), 0, 1, 4};
-#define VL_PICK(G, VPL, U, BPC) \
-    if (!sh.special && (uint32_t)(G * VPL) == ld4) sh = ScanShape{true, G, VPL, U, BPC};
-    VL_SUBSET_VARIANTS(VL_PICK)
-#undef VL_PICK
-    const bool qarg = q32_host != nullptr && sh.special && ld <= (uint32_t)SCAN_QARG_FLOATS;
-    if (!qarg && !q64) return hipErrorInvalidValue;
+    if (!shape_takes_qarg(sh, ld, q32_host) && !q64) return hipErrorInvalidValue;
     int grid = 0;
     hipError_t rc = dispatch_metric(metric, [&](auto M) -> hipError_t {
-        constexpr int MM = decltype(M)::value;
-        if (sh.special) {
-            bool launched = false;
-#define VL_SUBSET_TRY(G, VPL, U, BPC)                                                                                  \
-    if (!launched && sh.g == G && sh.vpl == VPL && sh.u == U) {                                                    \
-        if constexpr (G * VPL * 4 <= SCAN_QARG_FLOATS) {                                                            \
-            if (qarg) {                                                                                             \
-                auto kern = k_scan_subset<MM, G, VPL, U>;                                                           \
-                grid = scan_grid(m, sh, reinterpret_cast<const void*>(kern));                                       \
-                ScanQArg qa;                                                                                        \
-                memcpy(qa.v, q32_host, (size_t)ld * sizeof(float));                                                 \
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, slab4, inv_norm, plist, m32, partials, qa);   \
-                launched = true;                                                                                    \
-            }                                                                                                       \
-        } else {                                                                                                    \
-            auto kern = k_scan_subset_q64<MM, G, VPL, U>;                                                           \
-            grid = scan_grid(m, sh, reinterpret_cast<const void*>(kern));                                           \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, slab4, inv_norm, plist, q64, dim, m32, partials); \
-            launched = true;                                                                                        \
-        }                                                                                                           \
-    }
-            VL_SUBSET_VARIANTS(VL_SUBSET_TRY)
-#undef VL_SUBSET_TRY
-            if (!launched) return hipErrorInvalidValue;  // a kernarg-sized stride always comes with its query there
-        } else {
-#define VL_SUBSET_GEN(G)                                                                                               \
-    case G: {                                                                                                          \
-        auto kern = k_scan_subset_generic<MM, G>;                                                                      \
-        grid = scan_grid(m, sh, reinterpret_cast<const void*>(kern));                                                  \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, slab4, inv_norm, plist, q64, dim, m32, ld4, partials);   \
-    } break;
-            switch (sh.g) {
-                VL_SUBSET_GEN(1)
-                VL_SUBSET_GEN(2)
-                VL_SUBSET_GEN(4)
-                VL_SUBSET_GEN(8)
-                VL_SUBSET_GEN(16)
-                VL_SUBSET_GEN(32)
-                VL_SUBSET_GEN(64)
-            default: return hipErrorInvalidValue;
-            }
-#undef VL_SUBSET_GEN
-        }
-        return hipGetLastError();
+        return launch_scan_family<SubsetFamily<decltype(M)::value>>(s, sh, m, ld, q64, dim, q32_host,
+                                                                    std::make_tuple(slab4, inv_norm, plist),
+                                                                    std::make_tuple(partials), &grid);
     });
     if (plan) {
         plan->grid = grid;
@@ -2506,82 +2195,23 @@ hipError_t launch_hnsw_distances(hipStream_t s, int metric, const double* master
 
 // ---- range search -------------------------------------------------------------------------------
 // The range scan's shapes are the subset scan's: for every stride VL_SCAN_VARIANTS specialises, k_scan's default entry.
-bool scan_range_takes_qarg(uint32_t ld) { return scan_subset_takes_qarg(ld); }
-
-namespace {
-template <int MM, bool SUBSET>
-hipError_t launch_scan_range_t(hipStream_t s, const f32x4* slab4, const float* inv_norm, const uint32_t* plist, uint64_t n,
-                               const double* q64, uint32_t dim, uint32_t ld, float tau, uint32_t* cand, uint32_t cap,
-                               uint32_t* ctr, const ScanShape& sh, bool qarg, const float* q32_host, int* grid_out)
-{
-    const uint32_t n32 = (uint32_t)n, ld4 = ld / 4;
-    int grid = 0;
-    if (sh.special) {
-        bool launched = false;
-#define VL_RANGE_TRY(G, VPL, U, BPC)                                                                                    \
-    if (!launched && sh.g == G && sh.vpl == VPL && sh.u == U) {                                                     \
-        if constexpr (G * VPL * 4 <= SCAN_QARG_FLOATS) {                                                             \
-            if (qarg) {                                                                                              \
-                auto kern = k_scan_range<MM, G, VPL, U, SUBSET>;                                                     \
-                grid = scan_grid(n, sh, reinterpret_cast<const void*>(kern));                                        \
-                ScanQArg qa;                                                                                         \
-                memcpy(qa.v, q32_host, (size_t)ld * sizeof(float));                                                  \
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, slab4, inv_norm, plist, n32, tau, cand, cap, ctr, qa); \
-                launched = true;                                                                                     \
-            }                                                                                                        \
-        } else {                                                                                                     \
-            auto kern = k_scan_range_q64<MM, G, VPL, U, SUBSET>;                                                     \
-            grid = scan_grid(n, sh, reinterpret_cast<const void*>(kern));                                            \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, slab4, inv_norm, plist, q64, dim, n32, tau, cand, cap, ctr); \
-            launched = true;                                                                                         \
-        }                                                                                                            \
-    }
-        VL_SUBSET_VARIANTS(VL_RANGE_TRY)
-#undef VL_RANGE_TRY
-        if (!launched) return hipErrorInvalidValue;  // a kernarg-sized stride always comes with its query there
-    } else {
-#define VL_RANGE_GEN(G)                                                                                                 \
-    case G: {                                                                                                           \
-        auto kern = k_scan_range_generic<MM, G, SUBSET>;                                                                \
-        grid = scan_grid(n, sh, reinterpret_cast<const void*>(kern));                                                   \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, slab4, inv_norm, plist, q64, dim, n32, ld4, tau, cand, cap, ctr); \
-    } break;
-        switch (sh.g) {
-            VL_RANGE_GEN(1)
-            VL_RANGE_GEN(2)
-            VL_RANGE_GEN(4)
-            VL_RANGE_GEN(8)
-            VL_RANGE_GEN(16)
-            VL_RANGE_GEN(32)
-            VL_RANGE_GEN(64)
-        default: return hipErrorInvalidValue;
-        }
-#undef VL_RANGE_GEN
-    }
-    *grid_out = grid;
-    return hipGetLastError();
-}
-}  // namespace
+bool scan_range_takes_qarg(uint32_t ld) { return scan_takes_qarg(ld); }
 
 hipError_t launch_scan_range(hipStream_t s, int metric, const float* slab, const float* inv_norm, const uint32_t* plist,
                              uint64_t n, const double* q64, uint32_t dim, uint32_t ld, float tau, uint32_t* cand,
                              uint32_t cap, uint32_t* ctr, ScanPlan* plan, const float* q32_host)
 {
     if (n == 0 || n >= 0xFFFFFFFFull || (ld & 3) || cap == 0) return hipErrorInvalidValue;
-    const uint32_t ld4 = ld / 4;
+    const ScanShape sh = default_scan_shape(ld / 4);
     const f32x4* slab4 = reinterpret_cast<const f32x4*>(slab);
-    ScanShape sh{false, lanes_per_row(ld4), 0, 1, 4};
-#define VL_PICK(G, VPL, U, BPC) \
-    if (!sh.special && (uint32_t)(G * VPL) == ld4) sh = ScanShape{true, G, VPL, U, BPC};
-    VL_SUBSET_VARIANTS(VL_PICK)
-#undef VL_PICK
-    const bool qarg = q32_host != nullptr && sh.special && ld <= (uint32_t)SCAN_QARG_FLOATS;
-    if (!qarg && !q64) return hipErrorInvalidValue;
+    if (!shape_takes_qarg(sh, ld, q32_host) && !q64) return hipErrorInvalidValue;
     int grid = 0;
     hipError_t rc = dispatch_metric(metric, [&](auto M) -> hipError_t {
         constexpr int MM = decltype(M)::value;
-        if (plist) return launch_scan_range_t<MM, true>(s, slab4, inv_norm, plist, n, q64, dim, ld, tau, cand, cap, ctr, sh, qarg, q32_host, &grid);
-        return launch_scan_range_t<MM, false>(s, slab4, inv_norm, nullptr, n, q64, dim, ld, tau, cand, cap, ctr, sh, qarg, q32_host, &grid);
+        const auto head = std::make_tuple(slab4, inv_norm, plist);
+        const auto tail = std::make_tuple(tau, cand, cap, ctr);
+        if (plist) return launch_scan_family<RangeFamily<MM, true>>(s, sh, n, ld, q64, dim, q32_host, head, tail, &grid);
+        return launch_scan_family<RangeFamily<MM, false>>(s, sh, n, ld, q64, dim, q32_host, head, tail, &grid);
     });
     if (plan) {
         plan->grid = grid;

@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "device_common.hpp"
+#include "scan_stream.hpp"
 
 namespace vl {
 using namespace dev;
@@ -969,10 +970,9 @@ void k_mfma_rows(const __bf16* __restrict__ slab16,
 }
 
 // ---------------------------------------------------------------------------------------------
-// Single-query scan of the bf16 slab (opt-in candidate filter: half the HBM bytes of the f32 scan).
-// Same structure as k_scan (kernels.hip): G lanes share a row, 16-byte non-temporal loads straight to
-// registers (8 bf16 each), shuffle reduction, one sorted top-64 list per wave.  The query stays f32
-// (only the rows carry bf16 rounding), bf16 -> f32 is a shift, the products accumulate with fmaf.
+// Single-query scan of the bf16 slab (candidate filter: half the HBM bytes of the f32 scan): scan_stream()
+// (scan_stream.hpp) over rows of 8 bf16 per 16-byte chunk.  The query stays f32 (only the rows carry bf16 rounding),
+// bf16 -> f32 is a shift, the products accumulate with fmaf.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float dot8_bf16(float a, const u32x4 x, const f32x4 q0, const f32x4 q1)
 {
@@ -987,63 +987,38 @@ __device__ __forceinline__ float dot8_bf16(float a, const u32x4 x, const f32x4 q
     return a;
 }
 
-// Specialised: LD8 == G * VPL 16-byte chunks per row, U row steps in flight per wave (like k_scan's U).  `qv` is the lane's
-// slice of the f32 query (columns 8 (c + G j) .. + 7), loaded by the kernel entry that wraps this body.
-template <int METRIC, int G, int VPL, int U>
-__device__ __forceinline__ void scan_bf16_body(const u32x4* __restrict__ slab16, const float* __restrict__ row_nrm,
-                                               const float* __restrict__ row_sqn, const f32x4 (&qv)[VPL][2], uint32_t n,
-                                               Cand32* __restrict__ out)
-{
-    constexpr int RPS = WAVE / G;
-    constexpr uint32_t LD8 = G * VPL;  // 16-byte chunks (8 bf16) per row
-    __shared__ Cand32 sh[4 * WAVE];
-    const int lane = lane_id();
-    const int wave = threadIdx.x >> 6;
-    const int g = lane / G, c = lane % G;
-
-    const uint32_t n_steps = (n + RPS - 1) / RPS;
-    const uint32_t n_waves = gridDim.x * 4;
-    TopList<float> L;
-    L.init();
-    for (uint32_t s0 = blockIdx.x * 4 + wave; s0 < n_steps; s0 += n_waves * U) {
-        u32x4 x[U][VPL];
-        uint32_t row[U];
-        float nr[U], sq[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t s = s0 + (uint32_t)u * n_waves;
-            row[u] = s < n_steps ? s * RPS + g : n;  // n marks "no row"
-            const uint32_t r = row[u] < n ? row[u] : n - 1;  // clamp: loads stay in bounds
-            const u32x4* p = slab16 + (size_t)r * LD8 + c;
-#pragma unroll
-            for (int j = 0; j < VPL; ++j) x[u][j] = __builtin_nontemporal_load(p + G * j);
-            nr[u] = 1.0f;
-            sq[u] = 0.0f;
-            if (METRIC != COSINE) nr[u] = row_nrm[r];
-            if (METRIC == EUCLIDEAN) sq[u] = row_sqn[r];
-        }
-        __builtin_amdgcn_sched_barrier(0);  // every load of the iteration issued before the first FMA (see k_scan)
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            float a = 0.0f;
-#pragma unroll
-            for (int j = 0; j < VPL; ++j) a = dot8_bf16(a, x[u][j], qv[j][0], qv[j][1]);
-#pragma unroll
-            for (int o = G / 2; o >= 1; o >>= 1) a += __shfl_xor(a, o);
-            float key = a;                                              // cosine: x^.q
-            if (METRIC == DOT) key = a * nr[u];                         // x.q
-            if (METRIC == EUCLIDEAN) key = 2.0f * a * nr[u] - sq[u];    // |q|^2 - |x - q|^2
-            L.offer(key, row[u], row[u] < n && c == 0);
-        }
+// The row format: LD8 == G * VPL chunks per row; the lane's query slice of chunk c + G j is the f32 columns
+// 8 (c + G j) .. + 7.  The rows are unit vectors x^: dot and Euclidean carry |x| (and |x|^2) with the row loads.
+template <int METRIC, int VPL_>
+struct Bf16Rows {
+    typedef u32x4 Chunk;
+    typedef f32x4 Query[2];
+    struct Scalars {
+        float nr, sq;
+    };
+    static constexpr int VPL = VPL_;
+    const u32x4* __restrict__ slab;
+    const float* __restrict__ row_nrm;
+    const float* __restrict__ row_sqn;
+    __device__ __forceinline__ Scalars load_scalars(uint32_t r) const
+    {
+        Scalars sc = {1.0f, 0.0f};
+        if (METRIC != COSINE) sc.nr = row_nrm[r];
+        if (METRIC == EUCLIDEAN) sc.sq = row_sqn[r];
+        return sc;
     }
-    block_merge<float, Cand32, 4>(L, sh);
-    if (wave == 0) {
-        Cand32 e;
-        e.key = L.key;
-        e.pos = L.pos;
-        out[(size_t)blockIdx.x * KP + lane] = e;
+    static __device__ __forceinline__ float accumulate(float a, const u32x4 x, const f32x4 (&q)[2])
+    {
+        return dot8_bf16(a, x, q[0], q[1]);
     }
-}
+    __device__ __forceinline__ float key(float a, const Scalars& sc) const
+    {
+        float key = a;                                              // cosine: x^.q
+        if (METRIC == DOT) key = a * sc.nr;                         // x.q
+        if (METRIC == EUCLIDEAN) key = 2.0f * a * sc.nr - sc.sq;    // |q|^2 - |x - q|^2
+        return key;
+    }
+};
 
 // The f64 query in device memory: each lane rounds its slice itself.
 template <int METRIC, int G, int VPL, int U>
@@ -1056,22 +1031,10 @@ __global__ __launch_bounds__(256) void k_scan_bf16(const u32x4* __restrict__ sla
     f32x4 qv[VPL][2];
 #pragma unroll
     for (int j = 0; j < VPL; ++j) {
-        const uint32_t e0 = 8u * (uint32_t)(c + G * j);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            f32x4 v;
-            // clamped, never predicated (see load_q4 in kernels.hip)
-            const uint32_t b0 = e0 + 4 * h, last = dim - 1;
-            const double d0 = q64[b0 + 0 < dim ? b0 + 0 : last], d1 = q64[b0 + 1 < dim ? b0 + 1 : last];
-            const double d2 = q64[b0 + 2 < dim ? b0 + 2 : last], d3 = q64[b0 + 3 < dim ? b0 + 3 : last];
-            v.x = b0 + 0 < dim ? (float)d0 : 0.0f;
-            v.y = b0 + 1 < dim ? (float)d1 : 0.0f;
-            v.z = b0 + 2 < dim ? (float)d2 : 0.0f;
-            v.w = b0 + 3 < dim ? (float)d3 : 0.0f;
-            qv[j][h] = v;
-        }
+        qv[j][0] = load_q4(q64, 2u * (uint32_t)(c + G * j), dim);
+        qv[j][1] = load_q4(q64, 2u * (uint32_t)(c + G * j) + 1u, dim);
     }
-    scan_bf16_body<METRIC, G, VPL, U>(slab16, row_nrm, row_sqn, qv, n, out);
+    scan_stream<G, U>(Bf16Rows<METRIC, VPL>{slab16, row_nrm, row_sqn}, qv, AllRows{}, n, TopSink(out));
 }
 
 // The single search's form: the f32 query, zero padded to ldb columns, in the KERNEL ARGUMENTS (rounded on the host
@@ -1093,17 +1056,18 @@ __global__ __launch_bounds__(256) void k_scan_bf16_qarg(const u32x4* __restrict_
         qv[j][0] = *reinterpret_cast<const f32x4*>(&qa.v[8 * (c + G * j)]);
         qv[j][1] = *reinterpret_cast<const f32x4*>(&qa.v[8 * (c + G * j) + 4]);
     }
-    scan_bf16_body<METRIC, G, VPL, U>(slab16, row_nrm, row_sqn, qv, n, out);
+    scan_stream<G, U>(Bf16Rows<METRIC, VPL>{slab16, row_nrm, row_sqn}, qv, AllRows{}, n, TopSink(out));
 }
 
 // ---------------------------------------------------------------------------------------------
-// Single-query scan of the int8 copy (the first stage of the single-query ladder: a quarter of the f32 slab's bytes).
+// Single-query scan of the int8 copy (the first stage of the single-query ladder: a quarter of the f32 slab's bytes):
+// scan_stream() over rows of 16 bytes per chunk.
 // Row i holds offset-binary bytes b = k + 128 (k in [-127, 127]) and a pair (s, r): x^ = x/|x| = s k + e with
 // |e| <= r.  The key is an UPPER bound of x^.q (up to its f32 evaluation error, IN_EXTRA_I8_SINGLE):
 //   cosine  s (k.q16) 2^-e + r (Q + D) + D        dot  |x| (the same)
 // where q16 = the f16 query scaled by 2^e and D >= |q - 2^-e q16| (Scan8QArg).  A byte pair becomes two exact f16
 // values with one v_perm_b32 (0x64 as their high byte: 1024 + b) and one packed subtract (of 1152), and meets the
-// query in v_dot2_f32_f16: 1.5 VALU ops per byte.  Structure of scan_bf16_body.
+// query in v_dot2_f32_f16: 1.5 VALU ops per byte.
 // ---------------------------------------------------------------------------------------------
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
@@ -1129,75 +1093,58 @@ struct alignas(16) Scan8QArg {
     float pad_;
 };
 
-// LD16 == G * VPL 16-byte chunks per row; lane c of a row's G lanes holds chunks c + G j (16 bytes each: query halves
-// 16 (c + G j) .. + 15 in qv[j][0..1]).
+// The row format: LD16 == G * VPL chunks per row; the lane's query slice of chunk c + G j is the halves
+// 16 (c + G j) .. + 15.  (s, r) travel with the row loads, and |x| for dot.
+template <int METRIC, int VPL_>
+struct I8Rows {
+    typedef u32x4 Chunk;
+    typedef u32x4 Query[2];
+    struct Scalars {
+        float2 sr;
+        float nr;
+    };
+    static constexpr int VPL = VPL_;
+    const u32x4* __restrict__ slab;
+    const float2* __restrict__ row_sr;
+    const float* __restrict__ row_nrm;
+    float inv_scale, qd, dq;
+    __device__ __forceinline__ Scalars load_scalars(uint32_t r) const
+    {
+        Scalars sc = {row_sr[r], 1.0f};
+        if (METRIC == DOT) sc.nr = row_nrm[r];
+        return sc;
+    }
+    static __device__ __forceinline__ float accumulate(float a, const u32x4 x, const u32x4 (&q)[2])
+    {
+        a = dot4_i8(a, x.x, q[0].x, q[0].y);
+        a = dot4_i8(a, x.y, q[0].z, q[0].w);
+        a = dot4_i8(a, x.z, q[1].x, q[1].y);
+        a = dot4_i8(a, x.w, q[1].z, q[1].w);
+        return a;
+    }
+    __device__ __forceinline__ float key(float a, const Scalars& sc) const
+    {
+        const float m = a * inv_scale;                         // exact: a power of two
+        float key = sc.sr.x * m + (sc.sr.y * qd + dq);         // >= x^.q (cosine: ranks like x^.q / Q)
+        if (METRIC == DOT) key = key * sc.nr;                  // >= x.q
+        return key;
+    }
+};
+
 template <int METRIC, int G, int VPL, int U>
 __global__ __launch_bounds__(256) void k_scan_i8_qarg(const u32x4* __restrict__ slab8, const float2* __restrict__ row_sr,
                                                       const float* __restrict__ row_nrm, uint32_t n,
                                                       Cand32* __restrict__ out, const Scan8QArg qa)
 {
     static_assert(G * VPL * 16 <= SCAN8_QARG_HALVES, "row too long for the kernarg query");
-    constexpr int RPS = WAVE / G;
-    constexpr uint32_t LD16 = G * VPL;
-    __shared__ Cand32 sh[4 * WAVE];
-    const int lane = lane_id();
-    const int wave = threadIdx.x >> 6;
-    const int g = lane / G, c = lane % G;
+    const int c = lane_id() % G;
     u32x4 qv[VPL][2];
 #pragma unroll
     for (int j = 0; j < VPL; ++j) {
         qv[j][0] = *reinterpret_cast<const u32x4*>(&qa.h[8 * (c + G * j)]);
         qv[j][1] = *reinterpret_cast<const u32x4*>(&qa.h[8 * (c + G * j) + 4]);
     }
-    const float inv_scale = qa.inv_scale, qd = qa.qd, dq = qa.d;
-
-    const uint32_t n_steps = (n + RPS - 1) / RPS;
-    const uint32_t n_waves = gridDim.x * 4;
-    TopList<float> L;
-    L.init();
-    for (uint32_t s0 = blockIdx.x * 4 + wave; s0 < n_steps; s0 += n_waves * U) {
-        u32x4 x[U][VPL];
-        uint32_t row[U];
-        float2 sr[U];
-        float nr[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t s = s0 + (uint32_t)u * n_waves;
-            row[u] = s < n_steps ? s * RPS + g : n;  // n marks "no row"
-            const uint32_t r = row[u] < n ? row[u] : n - 1;  // clamp: loads stay in bounds
-            const u32x4* p = slab8 + (size_t)r * LD16 + c;
-#pragma unroll
-            for (int j = 0; j < VPL; ++j) x[u][j] = __builtin_nontemporal_load(p + G * j);
-            sr[u] = row_sr[r];
-            nr[u] = 1.0f;
-            if (METRIC == DOT) nr[u] = row_nrm[r];
-        }
-        __builtin_amdgcn_sched_barrier(0);  // every load of the iteration issued before the first product
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            float a = 0.0f;
-#pragma unroll
-            for (int j = 0; j < VPL; ++j) {
-                a = dot4_i8(a, x[u][j].x, qv[j][0].x, qv[j][0].y);
-                a = dot4_i8(a, x[u][j].y, qv[j][0].z, qv[j][0].w);
-                a = dot4_i8(a, x[u][j].z, qv[j][1].x, qv[j][1].y);
-                a = dot4_i8(a, x[u][j].w, qv[j][1].z, qv[j][1].w);
-            }
-#pragma unroll
-            for (int o = G / 2; o >= 1; o >>= 1) a += __shfl_xor(a, o);
-            const float m = a * inv_scale;                           // exact: a power of two
-            float key = sr[u].x * m + (sr[u].y * qd + dq);            // >= x^.q (cosine: ranks like x^.q / Q)
-            if (METRIC == DOT) key = key * nr[u];                    // >= x.q
-            L.offer(key, row[u], row[u] < n && c == 0);
-        }
-    }
-    block_merge<float, Cand32, 4>(L, sh);
-    if (wave == 0) {
-        Cand32 e;
-        e.key = L.key;
-        e.pos = L.pos;
-        out[(size_t)blockIdx.x * KP + lane] = e;
-    }
+    scan_stream<G, U>(I8Rows<METRIC, VPL>{slab8, row_sr, row_nrm, qa.inv_scale, qa.qd, qa.d}, qv, AllRows{}, n, TopSink(out));
 }
 
 // T_q = the 64th largest group maximum (a lower bound of the query's 64th best key); -inf when fewer
@@ -2067,22 +2014,80 @@ hipError_t launch_mfma_candidates(hipStream_t s, int metric, const void* slab_bf
     return hipGetLastError();
 }
 
-// (lanes per row G, 16-byte chunks per lane VPL, row steps in flight U) per bf16 row stride (ldb / 8 = G * VPL chunks).
-// The first shape whose G * VPL matches the stride runs; VL_SCAN16_SHAPE="G,VPL,U" picks another listed one (tuning).
+namespace {
+// What launch_scan_bf16 and launch_scan_i8 decide the same way: which listed (G, VPL, U) runs at a row stride of `ldc`
+// 16-byte chunks, with how many workgroups, and the variant code the search reports.
+struct RowScanPlan {
+    int g, vpl, u;  // g == 0: no listed shape has this stride
+    int grid, variant;
+};
+
+// The first listed shape whose G * VPL matches the stride runs; $shape_env = "G,VPL,U" picks another listed one and
+// $bpc_env another number of workgroups per CU (tuning).  One persistent wave of workgroups strides over the rows.
+RowScanPlan plan_row_scan(const int (*shapes)[3], int n_shapes, uint32_t ldc, uint64_t n, const char* shape_env,
+                          const char* bpc_env, int bpc_default, int variant_base)
+{
+    int want[3] = {0, 0, 0};
+    if (const char* se = getenv(shape_env)) {
+        if (sscanf(se, "%d,%d,%d", &want[0], &want[1], &want[2]) != 3) want[0] = 0;
+    }
+    int pick = -1;
+    for (int i = 0; i < n_shapes; ++i) {
+        if ((uint32_t)(shapes[i][0] * shapes[i][1]) != ldc) continue;
+        if (pick < 0) pick = i;
+        if (shapes[i][0] == want[0] && shapes[i][1] == want[1] && shapes[i][2] == want[2]) {
+            pick = i;
+            break;
+        }
+    }
+    if (pick < 0) return {0, 0, 0, 1, 0};
+    const int g = shapes[pick][0], vpl = shapes[pick][1], u = shapes[pick][2];
+    int dev = 0, cus = 256;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    const char* ge = getenv(bpc_env);
+    const int bpc = ge && *ge ? atoi(ge) : bpc_default;
+    const uint64_t steps = (n + (64 / g) - 1) / (64 / g);
+    uint64_t blocks = (steps + 3) / 4;
+    if (blocks > (uint64_t)(cus * bpc)) blocks = (uint64_t)(cus * bpc);
+    if (blocks > (uint64_t)SCAN_MAX_GRID) blocks = SCAN_MAX_GRID;
+    return {g, vpl, u, (int)(blocks < 1 ? 1 : blocks), variant_base + g * 10000 + vpl * 100 + u};
+}
+
+bool row_scan_listed(const int (*shapes)[3], int n_shapes, uint32_t ldc)
+{
+    for (int i = 0; i < n_shapes; ++i)
+        if ((uint32_t)(shapes[i][0] * shapes[i][1]) == ldc) return true;
+    return false;
+}
+
+#define VL_ROW(G, VPL, U) {G, VPL, U},
+// (lanes per row G, 16-byte chunks per lane VPL, row steps in flight U) per bf16 row stride (ldb / 8 = G * VPL chunks);
+// VL_SCAN16_SHAPE picks among them.
 // Measured (profiles/single_filter_shape_sweep.jsonl): a second row step in flight (U = 2) does not stream faster at
 // 10 M x 384 or 1.25 M x 768; G = 4 / VPL = 12 at stride 384 and G = 8 / VPL = 12 at stride 768 were 16 % / 1-2 % slower.
 #define VL_BF16_SCAN_SHAPES(X) \
     X(8, 2, 1) X(8, 2, 2) X(8, 4, 1) X(8, 4, 2) X(8, 6, 1) X(8, 6, 2) X(8, 8, 1) X(8, 8, 2) X(16, 6, 1) X(16, 6, 2)
+constexpr int BF16_SCAN_SHAPES[][3] = {VL_BF16_SCAN_SHAPES(VL_ROW)};
+constexpr int N_BF16_SCAN_SHAPES = (int)(sizeof(BF16_SCAN_SHAPES) / sizeof(BF16_SCAN_SHAPES[0]));
+
+// The same per int8 row stride (ldb / 16 = G * VPL chunks); VL_SCAN8_SHAPE picks among them.
+// Measured (profiles/single_filter_i8_shape_sweep.jsonl, 3 workgroups per CU): G = 8 streams fastest -- 10 M x 384:
+// (8,3,1) 0.584 ms, (8,3,2) 0.591, (4,6,2) 0.640, (4,6,1) 0.653, (2,12,1) 1.145; 5 M x 768: (8,6,1) 0.567, (8,6,2)
+// 0.567, (16,3,1) 0.570, (4,12,1) 0.653.  Four lanes per row leave each row's reduction and offer to fewer lanes but
+// give every lane twice the bytes to widen before its row is done.
+#define VL_I8_SCAN_SHAPES(X)                                                                                       \
+    X(8, 1, 1) X(8, 2, 1) X(8, 3, 1) X(8, 4, 1) X(8, 6, 1)                                                         \
+    X(4, 2, 1) X(4, 4, 1) X(4, 6, 1) X(4, 8, 1) X(8, 3, 2) X(4, 6, 2) X(2, 12, 1) X(8, 6, 2) X(4, 12, 1) X(16, 3, 1)
+constexpr int I8_SCAN_SHAPES[][3] = {VL_I8_SCAN_SHAPES(VL_ROW)};
+constexpr int N_I8_SCAN_SHAPES = (int)(sizeof(I8_SCAN_SHAPES) / sizeof(I8_SCAN_SHAPES[0]));
+#undef VL_ROW
+}  // namespace
 
 bool scan_bf16_supported(uint32_t dim, int metric)
 {
     if (metric != COSINE && metric != DOT && metric != EUCLIDEAN) return false;
-    const uint32_t ld8 = mfma_ldb(dim) / 8;
-    bool ok = false;
-#define VL_CHK(G, VPL, U) ok = ok || (ld8 == (uint32_t)(G * VPL));
-    VL_BF16_SCAN_SHAPES(VL_CHK)
-#undef VL_CHK
-    return ok;
+    return row_scan_listed(BF16_SCAN_SHAPES, N_BF16_SCAN_SHAPES, mfma_ldb(dim) / 8);
 }
 
 hipError_t launch_scan_bf16(hipStream_t s, int metric, const void* slab_bf16, const float* row_norm,
@@ -2094,43 +2099,24 @@ hipError_t launch_scan_bf16(hipStream_t s, int metric, const void* slab_bf16, co
     if (!q32_host && !q64) return hipErrorInvalidValue;
     if (q32_host && ldb > (uint32_t)SCAN16_QARG_FLOATS) return hipErrorInvalidValue;
     const u32x4* slab = reinterpret_cast<const u32x4*>(slab_bf16);
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    const char* ge = getenv("VL_SCAN16_BPC");
     // workgroups per CU: 3 (12 waves) streams fastest at stride 384 and below, 2 at stride 768 (0.279 vs 0.285 ms at 1.25 M)
-    const int bpc = ge && *ge ? atoi(ge) : (ld8 >= 96 ? SCAN16_BPC_LONG : SCAN16_BPC);
-    int want_g = 0, want_vpl = 0, want_u = 0;
-    if (const char* se = getenv("VL_SCAN16_SHAPE")) {
-        if (sscanf(se, "%d,%d,%d", &want_g, &want_vpl, &want_u) != 3) want_g = 0;
-    }
-    bool want_listed = false;
-#define VL_CHK(G, VPL, U) want_listed = want_listed || (want_g == G && want_vpl == VPL && want_u == U && ld8 == (uint32_t)(G * VPL));
-    VL_BF16_SCAN_SHAPES(VL_CHK)
-#undef VL_CHK
+    const RowScanPlan p = plan_row_scan(BF16_SCAN_SHAPES, N_BF16_SCAN_SHAPES, ld8, n, "VL_SCAN16_SHAPE", "VL_SCAN16_BPC",
+                                        ld8 >= 96 ? SCAN16_BPC_LONG : SCAN16_BPC, SCAN16_VARIANT_BASE);
     bool launched = false;
-    int grid = 1, variant = 0;
     Scan16QArg qa;
     if (q32_host) memcpy(qa.v, q32_host, (size_t)ldb * sizeof(float));
 #define VL_L3(MET, G, VPL, U)                                                                                       \
     {                                                                                                               \
-        const uint64_t steps = (n + (64 / G) - 1) / (64 / G);                                                       \
-        uint64_t blocks = (steps + 3) / 4;                                                                          \
-        if (blocks > (uint64_t)(cus * bpc)) blocks = (uint64_t)(cus * bpc);                                         \
-        if (blocks > (uint64_t)SCAN_MAX_GRID) blocks = SCAN_MAX_GRID;                                               \
-        grid = (int)(blocks < 1 ? 1 : blocks);                                                                      \
         if (q32_host)                                                                                               \
-            hipLaunchKernelGGL((k_scan_bf16_qarg<MET, G, VPL, U>), dim3(grid), dim3(256), 0, s, slab, row_norm,     \
+            hipLaunchKernelGGL((k_scan_bf16_qarg<MET, G, VPL, U>), dim3(p.grid), dim3(256), 0, s, slab, row_norm,   \
                                row_sqnorm, (uint32_t)n, partials, qa);                                              \
         else                                                                                                        \
-            hipLaunchKernelGGL((k_scan_bf16<MET, G, VPL, U>), dim3(grid), dim3(256), 0, s, slab, row_norm,          \
+            hipLaunchKernelGGL((k_scan_bf16<MET, G, VPL, U>), dim3(p.grid), dim3(256), 0, s, slab, row_norm,        \
                                row_sqnorm, q64, dim, (uint32_t)n, partials);                                        \
         launched = true;                                                                                            \
     }
 #define VL_L(G, VPL, U)                                                                             \
-    if (!launched && ld8 == (uint32_t)(G * VPL) &&                                                  \
-        (!want_listed || (want_g == G && want_vpl == VPL && want_u == U))) {                        \
-        variant = SCAN16_VARIANT_BASE + G * 10000 + VPL * 100 + U;                                  \
+    if (!launched && p.g == G && p.vpl == VPL && p.u == U) {                                        \
         if (metric == COSINE) VL_L3(COSINE, G, VPL, U)                                              \
         else if (metric == EUCLIDEAN) VL_L3(EUCLIDEAN, G, VPL, U)                                   \
         else VL_L3(DOT, G, VPL, U)                                                                  \
@@ -2139,8 +2125,8 @@ hipError_t launch_scan_bf16(hipStream_t s, int metric, const void* slab_bf16, co
 #undef VL_L
 #undef VL_L3
     if (!launched) return hipErrorInvalidValue;
-    if (grid_out) *grid_out = grid;
-    if (variant_out) *variant_out = variant;
+    if (grid_out) *grid_out = p.grid;
+    if (variant_out) *variant_out = p.variant;
     return hipGetLastError();
 }
 
@@ -2158,26 +2144,12 @@ hipError_t launch_rows_i8(hipStream_t s, const double* master, uint64_t n, uint3
     return hipGetLastError();
 }
 
-// (lanes per row G, 16-byte chunks per lane VPL, row steps in flight U) per int8 row stride (ldb / 16 = G * VPL chunks).
-// The first shape whose G * VPL matches the stride runs; VL_SCAN8_SHAPE="G,VPL,U" picks another listed one (tuning).
-// Measured (profiles/single_filter_i8_shape_sweep.jsonl, 3 workgroups per CU): G = 8 streams fastest -- 10 M x 384:
-// (8,3,1) 0.584 ms, (8,3,2) 0.591, (4,6,2) 0.640, (4,6,1) 0.653, (2,12,1) 1.145; 5 M x 768: (8,6,1) 0.567, (8,6,2)
-// 0.567, (16,3,1) 0.570, (4,12,1) 0.653.  Four lanes per row leave each row's reduction and offer to fewer lanes but
-// give every lane twice the bytes to widen before its row is done.
-#define VL_I8_SCAN_SHAPES(X)                                                                                       \
-    X(8, 1, 1) X(8, 2, 1) X(8, 3, 1) X(8, 4, 1) X(8, 6, 1)                                                         \
-    X(4, 2, 1) X(4, 4, 1) X(4, 6, 1) X(4, 8, 1) X(8, 3, 2) X(4, 6, 2) X(2, 12, 1) X(8, 6, 2) X(4, 12, 1) X(16, 3, 1)
-
 bool scan_i8_supported(uint32_t dim, int metric)
 {
     if (metric != COSINE && metric != DOT) return false;
-    const uint32_t ldb = mfma_ldb(dim), ld16 = ldb / 16;
+    const uint32_t ldb = mfma_ldb(dim);
     if (ldb > (uint32_t)SCAN8_QARG_HALVES) return false;
-    bool ok = false;
-#define VL_CHK(G, VPL, U) ok = ok || (ld16 == (uint32_t)(G * VPL));
-    VL_I8_SCAN_SHAPES(VL_CHK)
-#undef VL_CHK
-    return ok;
+    return row_scan_listed(I8_SCAN_SHAPES, N_I8_SCAN_SHAPES, ldb / 16);
 }
 
 namespace {
@@ -2232,22 +2204,10 @@ hipError_t launch_scan_i8(hipStream_t s, int metric, const void* slab_i8, const 
     const uint32_t ldb = mfma_ldb(dim), ld16 = ldb / 16;
     const u32x4* slab = reinterpret_cast<const u32x4*>(slab_i8);
     const float2* sr = reinterpret_cast<const float2*>(row_sr);
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    const char* ge = getenv("VL_SCAN8_BPC");
     // workgroups per CU: 3 at every stride (5 M x 768: 0.567 ms against 0.577 with 2)
-    const int bpc = ge && *ge ? atoi(ge) : SCAN8_BPC;
-    int want_g = 0, want_vpl = 0, want_u = 0;
-    if (const char* se = getenv("VL_SCAN8_SHAPE")) {
-        if (sscanf(se, "%d,%d,%d", &want_g, &want_vpl, &want_u) != 3) want_g = 0;
-    }
-    bool want_listed = false;
-#define VL_CHK(G, VPL, U) want_listed = want_listed || (want_g == G && want_vpl == VPL && want_u == U && ld16 == (uint32_t)(G * VPL));
-    VL_I8_SCAN_SHAPES(VL_CHK)
-#undef VL_CHK
+    const RowScanPlan p = plan_row_scan(I8_SCAN_SHAPES, N_I8_SCAN_SHAPES, ld16, n, "VL_SCAN8_SHAPE", "VL_SCAN8_BPC", SCAN8_BPC,
+                                        SCAN8_VARIANT_BASE);
     bool launched = false;
-    int grid = 1, variant = 0;
     Scan8QArg qa;
     memset(&qa, 0, sizeof(qa));
     memcpy(qa.h, q.h, (size_t)ldb * sizeof(uint16_t));
@@ -2256,19 +2216,12 @@ hipError_t launch_scan_i8(hipStream_t s, int metric, const void* slab_i8, const 
     qa.d = q.d;
 #define VL_L3(MET, G, VPL, U)                                                                                       \
     {                                                                                                               \
-        const uint64_t steps = (n + (64 / G) - 1) / (64 / G);                                                       \
-        uint64_t blocks = (steps + 3) / 4;                                                                          \
-        if (blocks > (uint64_t)(cus * bpc)) blocks = (uint64_t)(cus * bpc);                                         \
-        if (blocks > (uint64_t)SCAN_MAX_GRID) blocks = SCAN_MAX_GRID;                                               \
-        grid = (int)(blocks < 1 ? 1 : blocks);                                                                      \
-        hipLaunchKernelGGL((k_scan_i8_qarg<MET, G, VPL, U>), dim3(grid), dim3(256), 0, s, slab, sr, row_norm,       \
+        hipLaunchKernelGGL((k_scan_i8_qarg<MET, G, VPL, U>), dim3(p.grid), dim3(256), 0, s, slab, sr, row_norm,     \
                            (uint32_t)n, partials, qa);                                                              \
         launched = true;                                                                                            \
     }
 #define VL_L(G, VPL, U)                                                                             \
-    if (!launched && ld16 == (uint32_t)(G * VPL) &&                                                 \
-        (!want_listed || (want_g == G && want_vpl == VPL && want_u == U))) {                        \
-        variant = SCAN8_VARIANT_BASE + G * 10000 + VPL * 100 + U;                                   \
+    if (!launched && p.g == G && p.vpl == VPL && p.u == U) {                                        \
         if (metric == COSINE) VL_L3(COSINE, G, VPL, U)                                              \
         else VL_L3(DOT, G, VPL, U)                                                                  \
     }
@@ -2276,8 +2229,8 @@ hipError_t launch_scan_i8(hipStream_t s, int metric, const void* slab_i8, const 
 #undef VL_L
 #undef VL_L3
     if (!launched) return hipErrorInvalidValue;
-    if (grid_out) *grid_out = grid;
-    if (variant_out) *variant_out = variant;
+    if (grid_out) *grid_out = p.grid;
+    if (variant_out) *variant_out = p.variant;
     return hipGetLastError();
 }
 
