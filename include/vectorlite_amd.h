@@ -235,6 +235,37 @@ int vl_index_search_range(const vl_index *h, uint64_t filter, const double *quer
                           int metric, uint64_t *out_ids, double *out_scores, uint64_t out_capacity, uint64_t *out_n,
                           uint64_t *out_total);
 
+/* NEW capability (the reference only answers "the best k"): k results that are relevant but not k copies of the same
+ * paragraph -- maximal marginal relevance (MMR) over the exact candidates of a search.
+ * Candidates: C = FlatIndex::search(query, fetch_k, metric) (src/index/flat.rs:98-119) on the whole index (filter = 0) or on
+ * the FlatIndex of a filter's rows (a token of vl_index_filter_create), n = min(fetch_k, rows) of them in that ranking;
+ * rel[i] = candidate i's score, row[i] its stored f64 row.  Candidates are rows: duplicate-id rows are distinct candidates.
+ * Selection, every operation an IEEE f64 operation rounded on its own (nothing contracted into an FMA):
+ *     one_minus = 1.0 - lambda;  sel = [0];  red[i] = -inf
+ *     while len(sel) < min(k, n):
+ *         j = sel[-1]
+ *         for every i not in sel:  s = calculate(metric, row[i], row[j]) (src/lib.rs:380-391);  if s > red[i]: red[i] = s
+ *         best = none
+ *         for i = 0 .. n-1 not in sel, ascending:
+ *             v = (lambda * rel[i]) - (one_minus * red[i]);  if best is none or v > v_best: best, v_best = i, v
+ *         sel.append(best)
+ * A NaN s never replaces red[i]; ties keep the better-ranked candidate; a NaN v never beats a standing best.
+ * Output: min(k, n, out_capacity) entries, *out_n of them: entry t = (id, rel) of candidate sel[t], the reference score
+ * bits, in SELECTION order (not sorted by score).  For fixed fetch_k and lambda the answer for a smaller k is a prefix of the
+ * answer for a larger one (out_capacity: vl_index_search_cap's rule); lambda = 1 returns the first min(k, n) results of
+ * search(query, fetch_k).
+ * Errors: vl_index_search's on the same handle, query and fetch_k (dimension check whenever len != 0, unknown metric;
+ * VL_ERR_NAN_SCORE exactly when search(query, fetch_k, metric) on the same (sub)index returns it).  lambda NaN or outside
+ * [0, 1], fetch_k < k, fetch_k > VL_MMR_MAX_FETCH, an unknown or destroyed filter: VL_ERR_INVALID_ARG (checked before any
+ * device is touched).  k = 0 or an empty (sub)index: *out_n = 0, VL_OK.
+ * Single-GPU flat handles only: HNSW and vl_flat_create_multi handles return VL_ERR_INVALID_ARG.  MMR calls never join a
+ * coalesced pass; the whole call holds the handle's shared lock (other searches run beside it, add / delete wait).
+ * vl_last_path reports the candidate search's path. */
+#define VL_MMR_MAX_FETCH 1024
+int vl_index_search_mmr(const vl_index *h, uint64_t filter, const double *query, uint64_t q_len, uint64_t k,
+                        uint64_t fetch_k, double lambda, int metric, uint64_t out_capacity, uint64_t *out_ids,
+                        double *out_scores, uint64_t *out_n);
+
 uint64_t vl_index_len(const vl_index *h);      /* len()       src/index/flat.rs:121-123 */
 int vl_index_is_empty(const vl_index *h);      /* is_empty()  src/index/flat.rs:125-127 */
 uint64_t vl_index_dimension(const vl_index *h);/* dimension() src/index/flat.rs:133-135 */

@@ -46,6 +46,7 @@ extern "C" {
     fn vl_index_filter_destroy(h: *mut vl_index, filter: u64) -> c_int;
     fn vl_index_search_filtered(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, k: u64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_range(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, min_score: f64, metric: c_int, out_ids: *mut u64, out_scores: *mut f64, out_capacity: u64, out_n: *mut u64, out_total: *mut u64) -> c_int;
+    fn vl_index_search_mmr(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, k: u64, fetch_k: u64, lambda: f64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_flat_create_multi(dim: u64, device_ids: *const c_int, n_dev: c_int, mode: c_int, out: *mut *mut vl_index) -> c_int;
     fn vl_index_len(h: *const vl_index) -> u64;
     fn vl_index_get_vector(h: *const vl_index, id: u64, out: *mut f64) -> c_int;
@@ -351,6 +352,34 @@ impl GpuFlatIndex {
                 VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
                 _ => return Err(VectorLiteError::InternalError(last_error())),
             }
+        }
+    }
+
+    /// `k` results that are relevant but not `k` copies of one paragraph (no reference counterpart): maximal marginal
+    /// relevance over the exact candidates `FlatIndex::search(query, fetch_k, metric)` -- the best one first, then the
+    /// candidate maximising `lambda * score - (1 - lambda) * (largest similarity to anything chosen)`.  Results come in
+    /// selection order with the candidates' search scores; `lambda = 1` is the plain top `k`.  `fetch_k` in `k..=1024`.
+    /// Single-GPU handles only.
+    pub fn search_mmr(&self, query: &[f64], k: usize, fetch_k: usize, lambda: f64, metric: SimilarityMetric) -> VectorLiteResult<Vec<SearchResult>> {
+        let cap = k.max(1);
+        let (mut out_ids, mut scores, mut n) = (vec![0u64; cap], vec![0f64; cap], 0u64);
+        let rc = unsafe {
+            vl_index_search_mmr(self.0.raw, 0, query.as_ptr(), query.len() as u64, k as u64, fetch_k as u64, lambda, metric_code(metric), cap as u64, out_ids.as_mut_ptr(), scores.as_mut_ptr(), &mut n)
+        };
+        match rc {
+            VL_OK => Ok((0..n as usize)
+                .map(|i| {
+                    let (text, metadata) = self.0.side.get(&out_ids[i]).cloned().unwrap_or_default();
+                    SearchResult { id: out_ids[i], score: scores[i], text, metadata }
+                })
+                .collect()),
+            VL_ERR_DIM_MISMATCH => {
+                let (mut e, mut a) = (0u64, 0u64);
+                unsafe { vl_last_dim_mismatch(&mut e, &mut a) };
+                Err(VectorLiteError::DimensionMismatch { expected: e as usize, actual: a as usize })
+            }
+            VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
+            _ => Err(VectorLiteError::InternalError(last_error())),
         }
     }
 

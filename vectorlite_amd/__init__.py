@@ -34,6 +34,7 @@ __all__ = [
 VL_OK, VL_ERR_DIM_MISMATCH, VL_ERR_DUP_ID, VL_ERR_NOT_FOUND, VL_ERR_METRIC_MISMATCH = 0, 1, 2, 3, 4
 VL_ERR_NAN_SCORE, VL_ERR_DEVICE, VL_ERR_OOM, VL_ERR_INVALID_ARG = 5, 6, 7, 8
 PATH_NONE, PATH_FAST, PATH_EXACT_SELECT, PATH_EXACT_SORT = 0, 1, 2, 3
+VL_MMR_MAX_FETCH = 1024  # most candidates a diversified search ranks (vl_index_search_mmr)
 # set_single_filter: the modes of vl_index_set_single_filter (2 = auto, what new handles start in)
 SINGLE_FILTER_MODES = {"f32": 0, "bf16": 1, "auto": 2}
 # ... and mode 3, the int8 copy first always (kept out of SINGLE_FILTER_MODES, whose three entries callers enumerate)
@@ -255,6 +256,23 @@ def _search_range(L, h, query, min_score: float, metric: int, token: int, limit)
         return ids[:m].copy(), scores[:m].copy(), int(total.value)
 
 
+def _search_mmr(L, h, query, k: int, fetch_k: int, lambda_mult: float, metric: int, token: int):
+    """vl_index_search_mmr -> (ids, scores) in selection order."""
+    q = _f64(query).ravel()
+    k = min(max(int(k), 0), 1 << 62)
+    cap = max(min(k, VL_MMR_MAX_FETCH), 1)
+    ids = np.empty(cap, dtype=np.uint64)
+    scores = np.empty(cap, dtype=np.float64)
+    n = C.c_uint64(0)
+    rc = L.vl_index_search_mmr(h, int(token), q.ctypes.data, q.size, k, max(int(fetch_k), 0), float(lambda_mult), int(metric),
+                               cap, ids.ctypes.data, scores.ctypes.data, C.byref(n))
+    if rc == VL_ERR_INVALID_ARG:
+        raise IndexOpError(_last_error())
+    _raise(rc)
+    m = int(n.value)
+    return ids[:m].copy(), scores[:m].copy()
+
+
 class FlatIndex:
     """GPU-resident counterpart of `FlatIndex` (src/index/flat.rs:60-135).
 
@@ -416,6 +434,30 @@ class FlatIndex:
     def search_range(self, query, min_score: float, similarity_metric: int = SimilarityMetric.Cosine, filter=None,
                      limit=None) -> List[SearchResult]:
         ids, scores, _ = self.search_range_arrays(query, min_score, similarity_metric, filter=filter, limit=limit)
+        out = []
+        for i, s in zip(ids.tolist(), scores.tolist()):
+            text, md = self._meta.get(i, ("", None))
+            out.append(SearchResult(id=i, score=s, text=text, metadata=md))
+        return out
+
+    # ---- diversified (MMR) search ------------------------------------------------------------
+    def search_mmr_arrays(self, query, k: int, fetch_k: int = 20, lambda_mult: float = 0.5, metric: int = 0, filter=None):
+        """(ids, scores): maximal marginal relevance over the exact candidates search(query, fetch_k, metric) (among the
+        filter's rows when `filter` is given: an IdFilter or an iterable of ids).  The best candidate first, then k - 1
+        times the one maximising lambda_mult * score - (1 - lambda_mult) * (largest similarity to anything chosen);
+        entries come in selection order, scores are the candidates' search scores.  lambda_mult = 1 is the plain top k."""
+        if filter is None:
+            return _search_mmr(self._L, self._h, query, k, fetch_k, lambda_mult, metric, 0)
+        tok, temp = self._filter_token(filter)
+        try:
+            return _search_mmr(self._L, self._h, query, k, fetch_k, lambda_mult, metric, tok)
+        finally:
+            if temp is not None:
+                temp.close()
+
+    def search_mmr(self, query, k: int, fetch_k: int = 20, lambda_mult: float = 0.5,
+                   similarity_metric: int = SimilarityMetric.Cosine, filter=None) -> List[SearchResult]:
+        ids, scores = self.search_mmr_arrays(query, k, fetch_k, lambda_mult, similarity_metric, filter=filter)
         out = []
         for i, s in zip(ids.tolist(), scores.tolist()):
             text, md = self._meta.get(i, ("", None))
@@ -877,6 +919,14 @@ class HNSWIndex:
 
     def search_range(self, query, min_score: float, similarity_metric: int = SimilarityMetric.Cosine, filter=None, limit=None):
         return self.search_range_arrays(query, min_score, similarity_metric, filter, limit)
+
+    def search_mmr_arrays(self, query, k: int, fetch_k: int = 20, lambda_mult: float = 0.5, metric: int = 0, filter=None):
+        """Diversified search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""
+        return _search_mmr(self._L, self._h, query, k, fetch_k, lambda_mult, metric, 0)
+
+    def search_mmr(self, query, k: int, fetch_k: int = 20, lambda_mult: float = 0.5,
+                   similarity_metric: int = SimilarityMetric.Cosine, filter=None):
+        return self.search_mmr_arrays(query, k, fetch_k, lambda_mult, similarity_metric, filter)
 
     def search_arrays(self, query, k: int, metric: int, ef: int = 0, filter=None):
         if filter is not None:

@@ -109,6 +109,13 @@ class Collection:
         ids = [i for i, (_text, md) in list(self.index._meta.items()) if where(md)]
         return self.index.search(embedding, k, similarity_metric, filter=ids)
 
+    def search_text_mmr(self, query_text: str, k: int, similarity_metric: SimilarityMetric, embedding_function,
+                        fetch_k: int = 20, lambda_mult: float = 0.5) -> List[SearchResult]:
+        """search_text with diversified results: maximal marginal relevance over the best fetch_k chunks (flat
+        collections; FlatIndex.search_mmr)."""
+        embedding = embedding_function.generate_embedding(query_text)
+        return self.index.search_mmr(embedding, k, fetch_k, lambda_mult, similarity_metric)
+
     def get_vector(self, id: int) -> Optional[Vector]:
         return self.index.get_vector(id)
 

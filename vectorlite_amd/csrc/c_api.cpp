@@ -378,6 +378,26 @@ int vl_index_search_range(const vl_index* h, uint64_t filter, const double* quer
     });
 }
 
+static_assert(VL_MMR_MAX_FETCH == vl::MMR_MAX_FETCH, "the header states the kernels' limit");
+
+int vl_index_search_mmr(const vl_index* h, uint64_t filter, const double* query, uint64_t q_len, uint64_t k, uint64_t fetch_k,
+                        double lambda, int metric, uint64_t out_capacity, uint64_t* out_ids, double* out_scores, uint64_t* out_n)
+{
+    return guarded([&]() -> int {
+        if (out_n) *out_n = 0;
+        const int arc = vl::mmr_check_args(k, fetch_k, lambda);  // before the handle is looked at: no device is needed
+        if (arc != VL_OK) return arc;
+        if (!h || !out_n) return VL_ERR_INVALID_ARG;
+        if (!h->flat) {
+            vl::set_last_error("diversified (MMR) search is served by single-GPU flat indexes");
+            return VL_ERR_INVALID_ARG;
+        }
+        if ((!out_ids || !out_scores) && k != 0 && out_capacity != 0) return VL_ERR_INVALID_ARG;
+        return h->flat->search_mmr(filter, query, q_len, k, fetch_k, lambda, metric, out_capacity, nullptr, out_ids, out_scores,
+                                   out_n);
+    });
+}
+
 int vl_index_search_batch_filtered(const vl_index* h, uint64_t filter, const double* queries, uint64_t nq, uint64_t q_len,
                                    uint64_t k, int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores,
                                    uint64_t* out_n)

@@ -53,6 +53,24 @@ int last_path() { return t_last_path; }
         }                                                                                        \
     } while (0)
 
+// the argument checks of a diversified search that need no handle and no device (c_api.cpp runs them first)
+int mmr_check_args(uint64_t k, uint64_t fetch_k, double lambda)
+{
+    if (!(lambda >= 0.0 && lambda <= 1.0)) {
+        set_last_error("lambda must lie in [0, 1]");
+        return ERR_INVALID_ARG;
+    }
+    if (fetch_k < k) {
+        set_last_error("fetch_k must be at least k");
+        return ERR_INVALID_ARG;
+    }
+    if (fetch_k > (uint64_t)MMR_MAX_FETCH) {
+        set_last_error("fetch_k exceeds VL_MMR_MAX_FETCH (" + std::to_string(MMR_MAX_FETCH) + ")");
+        return ERR_INVALID_ARG;
+    }
+    return OK;
+}
+
 #define VL_TRY(expr)              \
     do {                          \
         int rc_ = (expr);         \
@@ -86,7 +104,7 @@ Workspace::~Workspace()
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
     void* dev[] = {d_q64, d_partials, d_partials64, d_result, d_nan, d_scores, d_okeys,
-                   d_opos, d_out_pos, d_out_scores, d_positions, d_dists, rg_ctr, rg_cand, rg_scores, rg_keys, rg_pv};
+                   d_opos, d_out_pos, d_out_scores, d_positions, d_dists, rg_ctr, rg_cand, rg_scores, rg_keys, rg_pv, mmr_sim};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     void* host[] = {h_q64, h_result, h_nan, mf_h_q64, mf_h_result, mf_h_dom, k3_h_q64, k3_h_result, rg_h_ctr, rg_h_pos, rg_h_scores};
@@ -923,10 +941,23 @@ void GpuFlatIndex::bf16_outcome(bool certified) const
 
 int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_eff, int metric,
                                 uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
-                                bool skip_fast, bool skip_bf16) const
+                                bool skip_fast, bool skip_bf16, const MmrReq* mmr) const
 {
     const uint64_t n = ids_.size();
     hipStream_t st = ws->stream;
+    // A diversified search (mmr != nullptr, search_mmr): every stage's finalize leaves its block in DEVICE memory,
+    // unstamped, and the selection's two launches behind it write the pinned block and the stamp -- the host waits once,
+    // as before, and a stage that did not certify shows in the same flags.
+    SearchResultBlock* const fin_out = mmr ? ws->d_result : ws->h_result;
+    auto mmr_from_blocks = [&](uint32_t seq) -> int {
+        if (!mmr) return OK;
+        MmrSource src;
+        src.blocks = ws->d_result;
+        src.n = (uint32_t)k_eff;
+        src.n_block0 = (uint32_t)k_eff;
+        return mmr_tail(ws, metric, *mmr, src, seq);
+    };
+    const uint64_t n_answer = mmr ? mmr->k_out : k_eff;  // what a certified block's n_out says
 
     // stage the query in the pinned block: the f64 values, then the norm
     double qq = 0.0, qmax = 0.0;
@@ -960,6 +991,10 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
 
     // A certified answer of a filter stage: the result block's positions -> the caller's arrays.
     auto take_result = [&](const char* what) -> int {
+        if (mmr) {
+            set_last_path(PATH_FAST);
+            return mmr_take(ws, *mmr, out_pos, out_ids, out_scores, out_n);
+        }
         const SearchResultBlock& r = *ws->h_result;
         for (uint64_t i = 0; i < k_eff; ++i) {
             const uint32_t p = r.pos[i];
@@ -1002,8 +1037,9 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
         VL_HIP(launch_scan_i8(st, metric, d_slab8_, d_sr8_, d_norm8_, q8, n, (uint32_t)dim_, ws->d_partials, &grid, &variant));
         if (prof) VL_HIP(hipEventRecord(ws->ev1, st));
         // the keys are upper bounds up to their f32 evaluation (mfma_scan.hpp)
-        VL_HIP(launch_merge_finalize(st, seq, metric, ws->d_partials, grid, d_master_, ws->h_q64, ws->h_q64 + dim_,
-                                     (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_, ws->h_result, IN_EXTRA_I8_SINGLE));
+        VL_HIP(launch_merge_finalize(st, mmr ? 0u : seq, metric, ws->d_partials, grid, d_master_, ws->h_q64, ws->h_q64 + dim_,
+                                     (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_, fin_out, IN_EXTRA_I8_SINGLE));
+        VL_TRY(mmr_from_blocks(seq));
         last_scan_variant_.store(variant, std::memory_order_relaxed);
         last_scan_grid_.store(grid, std::memory_order_relaxed);
         last_scan_qarg_.store(1, std::memory_order_relaxed);
@@ -1023,7 +1059,7 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
             prof_bytes_ += n * ((uint64_t)ldb + 2 * sizeof(float) + (metric == DOT ? sizeof(float) : 0));
         }
         const SearchResultBlock& r = *ws->h_result;
-        const bool certified = !(r.flags & RESULT_NEEDS_EXACT) && r.n_out == k_eff;
+        const bool certified = !(r.flags & RESULT_NEEDS_EXACT) && r.n_out == n_answer;
         i8_outcome(certified);
         if (certified) return take_result("int8 filter");
     }
@@ -1055,8 +1091,9 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
                                 &grid, ws->q32.data(), &variant));
         if (prof) VL_HIP(hipEventRecord(ws->ev1, st));
         // rows are rounded to bf16, the query is f32 (mfma_scan.hpp)
-        VL_HIP(launch_merge_finalize(st, seq, metric, ws->d_partials, grid, d_master_, ws->h_q64, ws->h_q64 + dim_,
-                                     (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_, ws->h_result, IN_EXTRA_BF16_SINGLE));
+        VL_HIP(launch_merge_finalize(st, mmr ? 0u : seq, metric, ws->d_partials, grid, d_master_, ws->h_q64, ws->h_q64 + dim_,
+                                     (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_, fin_out, IN_EXTRA_BF16_SINGLE));
+        VL_TRY(mmr_from_blocks(seq));
         last_scan_variant_.store(variant, std::memory_order_relaxed);
         last_scan_grid_.store(grid, std::memory_order_relaxed);
         last_scan_qarg_.store(1, std::memory_order_relaxed);
@@ -1075,7 +1112,7 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
             prof_bytes_ += n * (uint64_t)ldb * 2;
         }
         const SearchResultBlock& r = *ws->h_result;
-        const bool certified = !(r.flags & RESULT_NEEDS_EXACT) && r.n_out == k_eff;
+        const bool certified = !(r.flags & RESULT_NEEDS_EXACT) && r.n_out == n_answer;
         bf16_outcome(certified);
         if (certified) return take_result("bf16 filter");
     }
@@ -1102,7 +1139,8 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
         VL_HIP(launch_scan(st, metric, d_slab_, d_inv_norm_, ws->d_q64, n, (uint32_t)dim_, ld_, ws->d_partials, &plan, q32));
         if (prof) VL_HIP(hipEventRecord(ws->ev1, st));
         VL_HIP(launch_merge_finalize(st, metric, ws->d_partials, plan.grid, 1, d_master_, fq, fq + dim_, (uint32_t)dim_, n,
-                                     (uint32_t)k_eff, max_row_norm_, ws->h_result, 0.0, seq));
+                                     (uint32_t)k_eff, max_row_norm_, fin_out, 0.0, mmr ? 0u : seq));
+        VL_TRY(mmr_from_blocks(seq));
         last_scan_variant_.store(plan.variant, std::memory_order_relaxed);
         last_scan_grid_.store(plan.grid, std::memory_order_relaxed);
         last_scan_qarg_.store(qarg ? 1 : 0, std::memory_order_relaxed);
@@ -1121,7 +1159,8 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
             prof_bytes_ += n * (uint64_t)ld_ * sizeof(float);
         }
         const SearchResultBlock& r = *ws->h_result;
-        if (!(r.flags & RESULT_NEEDS_EXACT) && r.n_out == k_eff) {
+        if (!(r.flags & RESULT_NEEDS_EXACT) && r.n_out == n_answer) {
+            if (mmr) return take_result("fast path");
             for (uint64_t i = 0; i < k_eff; ++i) {
                 const uint32_t p = r.pos[i];
                 if (p >= n) {
@@ -1151,10 +1190,12 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
         if (plan.grid % parts == 0 && plan.grid >= parts) {
             VL_HIP(launch_merge_finalize_multi(st, metric, ws->d_partials, plan.grid, parts, d_master_, ws->d_q64,
                                                ws->d_q64 + dim_, (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_,
-                                               ws->h_result));
+                                               fin_out));
+            VL_TRY(mmr_from_blocks(0));
             VL_HIP(hipStreamSynchronize(st));
             const SearchResultBlock& r0 = ws->h_result[0];
-            if (!(r0.flags & RESULT_NEEDS_EXACT) && r0.n_out == k_eff) {
+            if (!(r0.flags & RESULT_NEEDS_EXACT) && r0.n_out == n_answer) {
+                if (mmr) return take_result("multi-list fast path");
                 for (uint64_t i = 0; i < k_eff; ++i) {
                     const uint32_t p = ws->h_result[i / KP].pos[i % KP];
                     if (p >= n) {
@@ -1177,7 +1218,8 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
     std::vector<uint32_t> pos;
     std::vector<double> scores;
     VL_TRY(q_to_device());
-    VL_TRY(run_exact(ws, metric, n, k_eff, &pos, &scores));
+    VL_TRY(run_exact(ws, metric, n, k_eff, &pos, &scores, nullptr, mmr));
+    if (mmr) return mmr_take(ws, *mmr, out_pos, out_ids, out_scores, out_n);
     for (uint64_t i = 0; i < k_eff; ++i) {
         if (pos[i] >= n) {
             set_last_error("exact path returned an out-of-range position (kernel bug)");
@@ -1225,9 +1267,18 @@ int GpuFlatIndex::wait_result(Workspace* ws, uint32_t seq) const
 }
 
 int GpuFlatIndex::run_exact(Workspace* ws, int metric, uint64_t n, uint64_t k_eff, std::vector<uint32_t>* pos,
-                            std::vector<double>* scores, const uint32_t* plist) const
+                            std::vector<double>* scores, const uint32_t* plist, const MmrReq* mmr) const
 {
     hipStream_t st = ws->stream;
+    // a diversified search: the selection reads the ranked candidates where the kernels below leave them on the device
+    // (the rounds' blocks or the sort's arrays; subset indices mapped through plist there) and writes the pinned blocks
+    auto mmr_behind = [&](MmrSource src) -> int {
+        src.nan_flag = ws->d_nan;
+        src.plist = plist;
+        src.plist_len = plist ? (uint32_t)n : 0u;
+        src.n = (uint32_t)k_eff;
+        return mmr_tail(ws, metric, *mmr, src, 0);
+    };
     if (ws->scores_cap < n) {
         if (ws->d_scores) (void)hipFree(ws->d_scores);
         ws->d_scores = nullptr;
@@ -1266,7 +1317,14 @@ int GpuFlatIndex::run_exact(Workspace* ws, int metric, uint64_t n, uint64_t k_ef
             VL_HIP(launch_exact_select(st, ws->d_scores, n, kr, ws->d_partials64, ws->d_nan, ws->d_result + r,
                                        r ? ws->d_result + (r - 1) : nullptr));
         }
-        VL_HIP(hipMemcpyAsync(ws->h_result, ws->d_result, rounds * sizeof(SearchResultBlock), hipMemcpyDeviceToHost, st));
+        if (mmr) {
+            MmrSource src;
+            src.blocks = ws->d_result;
+            src.n_block0 = (uint32_t)std::min<uint64_t>(KP, k_eff);
+            VL_TRY(mmr_behind(src));
+        } else {
+            VL_HIP(hipMemcpyAsync(ws->h_result, ws->d_result, rounds * sizeof(SearchResultBlock), hipMemcpyDeviceToHost, st));
+        }
         VL_HIP(hipStreamSynchronize(st));
     } else {
         const uint64_t cap = sort_capacity_for(n);
@@ -1292,14 +1350,25 @@ int GpuFlatIndex::run_exact(Workspace* ws, int metric, uint64_t n, uint64_t k_ef
         }
         VL_HIP(launch_exact_sort(st, ws->d_scores, n, k_eff, ws->d_okeys, ws->d_opos, ws->d_out_pos,
                                  ws->d_out_scores));
-        VL_HIP(hipMemcpyAsync(pos->data(), ws->d_out_pos, k_eff * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        VL_HIP(hipMemcpyAsync(scores->data(), ws->d_out_scores, k_eff * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (mmr) {
+            MmrSource src;
+            src.pos = ws->d_out_pos;
+            src.scores = ws->d_out_scores;
+            VL_TRY(mmr_behind(src));
+        } else {
+            VL_HIP(hipMemcpyAsync(pos->data(), ws->d_out_pos, k_eff * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            VL_HIP(hipMemcpyAsync(scores->data(), ws->d_out_scores, k_eff * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
         VL_HIP(hipStreamSynchronize(st));
     }
     if (*ws->h_nan) {
         // sort_by(|a, b| b.score.partial_cmp(&a.score).unwrap()) panics on a NaN (src/index/flat.rs:116)
         set_last_error("NaN similarity score: the reference panics in partial_cmp().unwrap()");
         return ERR_NAN_SCORE;
+    }
+    if (mmr) {  // the answer stands in the pinned blocks (mmr_take)
+        set_last_path(use_select ? PATH_EXACT_SELECT : PATH_EXACT_SORT);
+        return OK;
     }
     if (use_select) {
         for (uint64_t r = 0; r < rounds; ++r) {
@@ -1506,12 +1575,14 @@ int GpuFlatIndex::search_filtered(uint64_t token, const double* query, uint64_t 
 }
 
 int GpuFlatIndex::search_subset(Workspace* ws, IdFilter* f, const double* query, uint64_t k_eff, int metric,
-                                uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n) const
+                                uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
+                                const MmrReq* mmr) const
 {
     const uint64_t n = ids_.size();
     const uint64_t m = f->m;
     const uint32_t* plist = f->d_plist;
     hipStream_t st = ws->stream;
+    const uint64_t n_answer = mmr ? mmr->k_out : k_eff;  // (search_locked's protocol for a diversified search)
 
     // the query staged as search_locked stages it: pinned f64 values, then the norm
     double qq = 0.0, qmax = 0.0;
@@ -1561,7 +1632,14 @@ int GpuFlatIndex::search_subset(Workspace* ws, IdFilter* f, const double* query,
         // n_rows = m: the bound check and the "a list of every row" rule are about the subset (every row left out of the
         // lists is a subset row with a key at or below the 64th; rows outside the subset are no part of the answer)
         VL_HIP(launch_merge_finalize(st, metric, ws->d_partials, plan.grid, 1, d_master_, fq, fq + dim_, (uint32_t)dim_, m,
-                                     (uint32_t)k_eff, max_row_norm_, ws->h_result, 0.0, seq));
+                                     (uint32_t)k_eff, max_row_norm_, mmr ? ws->d_result : ws->h_result, 0.0, mmr ? 0u : seq));
+        if (mmr) {
+            MmrSource src;
+            src.blocks = ws->d_result;
+            src.n = (uint32_t)k_eff;
+            src.n_block0 = (uint32_t)k_eff;
+            VL_TRY(mmr_tail(ws, metric, *mmr, src, seq));
+        }
         last_scan_variant_.store(plan.variant, std::memory_order_relaxed);
         last_scan_grid_.store(plan.grid, std::memory_order_relaxed);
         last_scan_qarg_.store(qarg ? 1 : 0, std::memory_order_relaxed);
@@ -1581,7 +1659,11 @@ int GpuFlatIndex::search_subset(Workspace* ws, IdFilter* f, const double* query,
             prof_bytes_ += m * ((uint64_t)ld_ * sizeof(float) + sizeof(uint32_t) + (metric == COSINE ? sizeof(float) : 0));
         }
         const SearchResultBlock& r = *ws->h_result;
-        if (!(r.flags & RESULT_NEEDS_EXACT) && r.n_out == k_eff) {
+        if (!(r.flags & RESULT_NEEDS_EXACT) && r.n_out == n_answer) {
+            if (mmr) {
+                set_last_path(PATH_FAST);
+                return mmr_take(ws, *mmr, out_pos, out_ids, out_scores, out_n);
+            }
             for (uint64_t i = 0; i < k_eff; ++i) {
                 const uint32_t p = r.pos[i];
                 if (p >= n) {
@@ -1602,7 +1684,8 @@ int GpuFlatIndex::search_subset(Workspace* ws, IdFilter* f, const double* query,
     std::vector<uint32_t> idx;
     std::vector<double> scores;
     VL_TRY(q_to_device());
-    VL_TRY(run_exact(ws, metric, m, k_eff, &idx, &scores, plist));
+    VL_TRY(run_exact(ws, metric, m, k_eff, &idx, &scores, plist, mmr));
+    if (mmr) return mmr_take(ws, *mmr, out_pos, out_ids, out_scores, out_n);  // storage positions already
     {
         std::lock_guard<std::mutex> fg(f->mu);
         if (!f->h_plist_valid) {  // one copy of the list per resolution, on the first exact answer that needs it
@@ -1624,6 +1707,113 @@ int GpuFlatIndex::search_subset(Workspace* ws, IdFilter* f, const double* query,
     }
     *out_n = k_eff;
     return OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Diversified search: maximal marginal relevance over the candidates of FlatIndex::search(q, fetch_k)
+// (src/index/flat.rs:98-119), on the whole index or on a filter's rows.  The search runs as it always does -- the ladder,
+// the multi-list route, the exact kernels -- except that its last kernel leaves the ranked candidates in device memory;
+// k_mmr_pairwise and k_mmr_select follow on the same stream and write the chosen (position, score) pairs into the pinned
+// result blocks.  Given exact candidates the selection is a deterministic function of reference scores: nothing to certify.
+// ---------------------------------------------------------------------------------------------
+int GpuFlatIndex::mmr_tail(Workspace* ws, int metric, const MmrReq& m, MmrSource src, uint32_t seq) const
+{
+    src.n_rows = (uint32_t)ids_.size();
+    VL_HIP(launch_mmr(ws->stream, metric, d_master_, (uint32_t)dim_, src, ws->mmr_sim, (uint32_t)m.k_out, m.lambda, ws->h_result,
+                      seq));
+    return OK;
+}
+
+int GpuFlatIndex::mmr_take(Workspace* ws, const MmrReq& m, uint64_t* out_pos, uint64_t* out_ids, double* out_scores,
+                           uint64_t* out_n) const
+{
+    const uint64_t n = ids_.size();
+    if (ws->h_result[0].flags != 0u || ws->h_result[0].n_out != m.k_out) {
+        set_last_error("the selection kernel did not take the search's candidates (kernel bug)");
+        return ERR_DEVICE;
+    }
+    for (uint64_t i = 0; i < m.k_out; ++i) {
+        const uint32_t p = ws->h_result[i / KP].pos[i % KP];
+        if (p >= n) {
+            set_last_error("diversified search returned an out-of-range position (kernel bug)");
+            return ERR_DEVICE;
+        }
+        if (out_pos) out_pos[i] = p;
+        if (out_ids) out_ids[i] = ids_[p];
+        out_scores[i] = ws->h_result[i / KP].score[i % KP];
+    }
+    *out_n = m.k_out;
+    return OK;
+}
+
+int GpuFlatIndex::search_mmr(uint64_t token, const double* query, uint64_t q_len, uint64_t k, uint64_t fetch_k, double lambda,
+                             int metric, uint64_t out_capacity, uint64_t* out_pos, uint64_t* out_ids, double* out_scores,
+                             uint64_t* out_n) const
+{
+    if (!out_n) return ERR_INVALID_ARG;
+    *out_n = 0;
+    const int arc = mmr_check_args(k, fetch_k, lambda);
+    if (arc != OK) return arc;
+    std::shared_ptr<IdFilter> f;
+    if (token != 0) {
+        f = find_filter(token);
+        if (!f) {
+            set_last_error("unknown or destroyed filter");
+            return ERR_INVALID_ARG;
+        }
+    }
+    if (metric < 0 || metric > 3) {
+        set_last_error("unknown metric");
+        return ERR_INVALID_ARG;
+    }
+    std::shared_lock<RwLock> lk(mu_);  // held from the search to the selection: positions cannot move in between
+    const uint64_t n = ids_.size();
+    if (n != 0 && q_len != dim_) {  // the whole index's check, as in search
+        set_dim_mismatch(dim_, q_len);
+        set_last_error("Dimension mismatch: expected " + std::to_string(dim_) + ", got " + std::to_string(q_len));
+        return ERR_DIM_MISMATCH;
+    }
+    const uint64_t k_cap = std::min<uint64_t>(k, out_capacity);  // a smaller k's answer is a prefix
+    if (n == 0 || k_cap == 0) return OK;
+    if ((!query && dim_) || !out_scores) return ERR_INVALID_ARG;
+
+    VL_HIP(hipSetDevice(device_));
+    Workspace* ws = acquire_ws();
+    if (!ws) return ERR_DEVICE;
+    int rc = OK;
+    if (f) {
+        std::lock_guard<std::mutex> fg(f->mu);
+        if (f->resolved_at != mutations_) rc = resolve_filter(ws, f.get());
+    }
+    const uint64_t rows = f ? f->m : n;
+    if (rc == OK && rows != 0) {
+        const uint64_t fetch_eff = std::min<uint64_t>(fetch_k, rows);
+        const MmrReq req{std::min<uint64_t>(k_cap, fetch_eff), lambda};
+        active_searches_.fetch_add(1, std::memory_order_relaxed);
+        if (req.k_out == 1) {
+            // sel = [0]: the best of search(q, fetch_k), whose errors are this call's
+            std::vector<uint64_t> pos(fetch_eff), ids(fetch_eff);
+            std::vector<double> scores(fetch_eff);
+            uint64_t got = 0;
+            rc = f ? search_subset(ws, f.get(), query, fetch_eff, metric, pos.data(), ids.data(), scores.data(), &got)
+                   : search_locked(ws, query, fetch_eff, metric, pos.data(), ids.data(), scores.data(), &got, false);
+            if (rc == OK && got >= 1) {
+                if (out_pos) out_pos[0] = pos[0];
+                if (out_ids) out_ids[0] = ids[0];
+                out_scores[0] = scores[0];
+                *out_n = 1;
+            }
+        } else {
+            if (!ws->mmr_sim) rc = dev_alloc(&ws->mmr_sim, (size_t)MMR_MAX_FETCH * MMR_MAX_FETCH);
+            if (rc == OK)
+                rc = f ? search_subset(ws, f.get(), query, fetch_eff, metric, out_pos, out_ids, out_scores, out_n, &req)
+                       : search_locked(ws, query, fetch_eff, metric, out_pos, out_ids, out_scores, out_n, false, false, &req);
+        }
+        active_searches_.fetch_sub(1, std::memory_order_relaxed);
+    }
+    if (rc != OK) (void)hipStreamSynchronize(ws->stream);
+    release_ws(ws);
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------------

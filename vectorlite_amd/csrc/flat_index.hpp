@@ -89,6 +89,8 @@ struct Workspace {
     size_t rg_sort_cap = 0;
     uint32_t* rg_h_pos = nullptr;    // pinned [RANGE_SMALL]
     double* rg_h_scores = nullptr;   // pinned [RANGE_SMALL]
+    // diversified search (lazy): the candidates' pairwise similarities, [MMR_MAX_FETCH][MMR_MAX_FETCH] (8 MB)
+    double* mmr_sim = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<float> q32;   // the f32 query handed to k_scan in its kernel arguments
     uint32_t seq = 0;         // stamp of the last single search issued from this workspace (h_result->seq)
@@ -140,6 +142,13 @@ struct IdFilter {
 
     ~IdFilter();
 };
+
+// A diversified search riding on a single search (search_mmr): how many candidates the selection returns, and lambda.
+struct MmrReq {
+    uint64_t k_out;
+    double lambda;
+};
+int mmr_check_args(uint64_t k, uint64_t fetch_k, double lambda);  // VL_ERR_INVALID_ARG with a message, or OK
 
 class GpuFlatIndex {
 public:
@@ -205,6 +214,12 @@ public:
     // min(total, out_capacity) entries are written (out_capacity = 0: count only, outputs may be null).
     int search_range(uint64_t token, const double* query, uint64_t q_len, double min_score, int metric, uint64_t out_capacity,
                      uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n, uint64_t* out_total) const;
+    // NEW (no reference counterpart): maximal marginal relevance over C = FlatIndex::search(q, fetch_k, metric) on the whole
+    // index (token 0) or the filter's rows: sel[0] = C[0], then greedily the candidate maximising
+    // lambda * score - (1 - lambda) * (largest reference similarity to anything chosen), ties to the better-ranked one.
+    // min(k, |C|, out_capacity) entries in selection order, scores = the candidates' reference scores.
+    int search_mmr(uint64_t token, const double* query, uint64_t q_len, uint64_t k, uint64_t fetch_k, double lambda, int metric,
+                   uint64_t out_capacity, uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;
     uint64_t len() const;
     bool is_empty() const { return len() == 0; }
     uint64_t dimension() const { return dim_; }
@@ -295,19 +310,27 @@ private:
     void run_coalesced(std::vector<CoalesceReq*>& batch) const;
     // skip_bf16: the query already failed a bf16 filter's certification (an MFMA batch straggler): neither the int8 nor the
     // bf16 stage, straight to k_scan
+    // mmr != nullptr (search_mmr): k_eff = the candidates to fetch; the outputs receive mmr->k_out selected entries
     int search_locked(Workspace* ws, const double* query, uint64_t k_eff, int metric, uint64_t* out_pos,
-                      uint64_t* out_ids, double* out_scores, uint64_t* out_n, bool skip_fast, bool skip_bf16 = false) const;
+                      uint64_t* out_ids, double* out_scores, uint64_t* out_n, bool skip_fast, bool skip_bf16 = false,
+                      const MmrReq* mmr = nullptr) const;
+    // the selection's two launches behind a search's last kernel (ws->h_result receives the answer; seq != 0: stamped)
+    int mmr_tail(Workspace* ws, int metric, const MmrReq& m, MmrSource src, uint32_t seq) const;
+    int mmr_take(Workspace* ws, const MmrReq& m, uint64_t* out_pos, uint64_t* out_ids, double* out_scores,
+                 uint64_t* out_n) const;
     bool bf16_first(uint64_t n) const;        // does this single search try the bf16 filter (after the int8 one)
     void bf16_outcome(bool certified) const;  // records one try of the bf16 filter
     bool i8_first(uint64_t n) const;          // does this single search try the int8 filter first
     void i8_outcome(bool certified) const;    // records one try of the int8 filter
     // plist != nullptr: the n rows are plist[0..n) (a filter's subset) and pos[] returns indices into that list
+    // mmr != nullptr: the selection runs behind the ranking and pos / scores stay untouched (mmr_take reads the answer)
     int run_exact(Workspace* ws, int metric, uint64_t n, uint64_t k_eff, std::vector<uint32_t>* pos,
-                  std::vector<double>* scores, const uint32_t* plist = nullptr) const;
+                  std::vector<double>* scores, const uint32_t* plist = nullptr, const MmrReq* mmr = nullptr) const;
     std::shared_ptr<IdFilter> find_filter(uint64_t token) const;
     int resolve_filter(Workspace* ws, IdFilter* f) const;  // mu_ held (shared or unique), f->mu held
     int search_subset(Workspace* ws, IdFilter* f, const double* query, uint64_t k_eff, int metric, uint64_t* out_pos,
-                      uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;  // mu_ held (shared), f resolved
+                      uint64_t* out_ids, double* out_scores, uint64_t* out_n,
+                      const MmrReq* mmr = nullptr) const;  // mu_ held (shared), f resolved
     int ensure_range_ws(Workspace* ws, uint64_t sort_cap, uint64_t out_cap) const;
     int search_range_locked(Workspace* ws, IdFilter* f, const double* query, double min_score, int metric, uint64_t out_capacity,
                             uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n,

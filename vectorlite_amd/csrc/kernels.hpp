@@ -216,6 +216,29 @@ uint64_t sort_capacity_for(uint64_t n);
 hipError_t launch_exact_sort(hipStream_t s, const double* scores, uint64_t n, uint64_t k, uint64_t* okeys,
                              uint32_t* opos, uint32_t* out_pos, double* out_scores);
 
+// Diversified (MMR) search, DESIGN.md section 16 (mmr.hip).  Where a search left its finalised candidates in device memory:
+// result blocks (entry i = blocks[i / KP].pos / .score[i % KP]: the certified finalize, the multi-list finalize, the exact
+// selection rounds) or the exact sort's (pos, scores) arrays.  The kernels take the candidates only when the device says
+// the search stands: blocks[0].n_out == n_block0 with neither NEEDS_EXACT nor HAS_NAN, and *nan_flag == 0 when given.
+constexpr uint32_t MMR_MAX_FETCH = 1024;  // VL_MMR_MAX_FETCH: one workgroup holds rel, red and the flags in LDS
+struct MmrSource {
+    const SearchResultBlock* blocks = nullptr;
+    const uint32_t* pos = nullptr;       // blocks == nullptr: [n]
+    const double* scores = nullptr;      // blocks == nullptr: [n]
+    const uint32_t* plist = nullptr;     // given: entries are indices into this id filter's position list
+    const uint32_t* nan_flag = nullptr;  // the exact scan's NaN flag
+    uint32_t plist_len = 0;
+    uint32_t n = 0;         // candidates: min(fetch_k, rows)
+    uint32_t n_block0 = 0;  // what blocks[0].n_out says when the search stands
+    uint32_t n_rows = 0;    // rows of the index (positions are clamped below it)
+};
+// k_mmr_pairwise (sim[i][j] = calculate(metric, row[i], row[j]), i != j < n, row stride MMR_MAX_FETCH) then k_mmr_select:
+// the greedy selection of min(k, n) candidates, written in selection order as (storage position, score bits) into
+// out[t / KP] entry t % KP; out[0].n_out = the count, out[0].flags = NEEDS_EXACT when the candidates were not taken;
+// seq != 0: out[0].seq = seq stored last, system-scope release (`out` pinned).  sim: MMR_MAX_FETCH^2 doubles.
+hipError_t launch_mmr(hipStream_t s, int metric, const double* master, uint32_t dim, const MmrSource& src, double* sim,
+                      uint32_t k, double lambda, SearchResultBlock* out, uint32_t seq);
+
 // HNSW distance callbacks: u64 distance of query vs the rows at positions[0..m).
 hipError_t launch_hnsw_distances(hipStream_t s, int metric, const double* master, const double* q64,
                                  uint32_t dim, const uint32_t* positions, uint32_t m, uint64_t* out);
