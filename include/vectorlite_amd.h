@@ -235,6 +235,33 @@ int vl_index_search_range(const vl_index *h, uint64_t filter, const double *quer
                           int metric, uint64_t *out_ids, double *out_scores, uint64_t out_capacity, uint64_t *out_n,
                           uint64_t *out_total);
 
+/* nq range searches against ONE index state (one hold of the reader lock): near-duplicate detection asks every row of a
+ * corpus, or a day's new rows, with one threshold.  Row i of the [nq, out_stride] outputs, out_n[i] and out_total[i] are
+ * exactly what vl_index_search_range(h, filter, queries + i * q_len, q_len, min_scores[i], metric, ..., out_capacity =
+ * out_stride, ...) returns on that state: ids, f64 score bits, counts -- so threshold ties are in, equal scores come in
+ * storage order, -inf / +inf thresholds and duplicate ids behave as there.  out_stride = 0 with NULL id / score outputs
+ * counts only.  nq = 0 is VL_OK and writes nothing.  The call returns the status the LOWEST-INDEX failing query's single
+ * call would return (dimension check, unknown metric, a NaN min_scores[i] -> VL_ERR_INVALID_ARG, VL_ERR_NAN_SCORE exactly
+ * when that query's single call returns it); outputs are unspecified on error.  HNSW and vl_flat_create_multi handles
+ * return VL_ERR_INVALID_ARG.  Never joins a coalesced pass.
+ * Route: with filter = 0, two or more queries, cosine / Euclidean / dot, a row length the batch filter has a shape for
+ * (up to 768), in-domain rows and no forced path, one bf16 MFMA pass with per-query key thresholds derived from
+ * min_scores[i] serves every query of a launch sequence, and rescore (the reference's f64 order), cut, rank and emit run on
+ * the device.  A query outside the fast-path domain, a -inf threshold, a zero query under cosine, a query whose candidate
+ * buffer (4096 rows) overflows or with more than 2048 qualifying rows is answered by the single call under the same lock.
+ * Everything else (Manhattan, other row lengths, one query, filter != 0) is a loop over the single call under the lock. */
+int vl_index_search_range_batch(const vl_index *h, uint64_t filter, const double *queries, uint64_t nq, uint64_t q_len,
+                                const double *min_scores /* [nq] */, int metric, uint64_t out_stride,
+                                uint64_t *out_ids, double *out_scores /* [nq, out_stride] */,
+                                uint64_t *out_n, uint64_t *out_total /* [nq] */);
+
+/* Diagnostics of the last successful vl_index_search_range_batch on this handle: how many of its queries were answered by
+ * the MFMA pass with the device tail, by the single-query fast route (k_scan_range), and by the exact route
+ * (VL_PATH_EXACT_SORT); the three sum to nq.  Any pointer may be NULL.  Single-GPU flat handles only. */
+int vl_index_last_range_batch(const vl_index *h, uint64_t *mfma_queries, uint64_t *single_queries, uint64_t *exact_queries);
+/* ... and the largest number of candidates the MFMA pass kept for one query it answered (0: none). */
+int vl_index_last_range_batch_candidates(const vl_index *h, uint64_t *max_candidates);
+
 /* NEW capability (the reference only answers "the best k"): k results that are relevant but not k copies of the same
  * paragraph -- maximal marginal relevance (MMR) over the exact candidates of a search.
  * Candidates: C = FlatIndex::search(query, fetch_k, metric) (src/index/flat.rs:98-119) on the whole index (filter = 0) or on

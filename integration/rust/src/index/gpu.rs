@@ -46,6 +46,9 @@ extern "C" {
     fn vl_index_filter_destroy(h: *mut vl_index, filter: u64) -> c_int;
     fn vl_index_search_filtered(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, k: u64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_range(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, min_score: f64, metric: c_int, out_ids: *mut u64, out_scores: *mut f64, out_capacity: u64, out_n: *mut u64, out_total: *mut u64) -> c_int;
+    fn vl_index_search_range_batch(h: *const vl_index, filter: u64, queries: *const f64, nq: u64, q_len: u64, min_scores: *const f64, metric: c_int, out_stride: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64, out_total: *mut u64) -> c_int;
+    fn vl_index_last_range_batch(h: *const vl_index, mfma_queries: *mut u64, single_queries: *mut u64, exact_queries: *mut u64) -> c_int;
+    fn vl_index_last_range_batch_candidates(h: *const vl_index, max_candidates: *mut u64) -> c_int;
     fn vl_index_search_mmr(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, k: u64, fetch_k: u64, lambda: f64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_flat_create_multi(dim: u64, device_ids: *const c_int, n_dev: c_int, mode: c_int, out: *mut *mut vl_index) -> c_int;
     fn vl_index_len(h: *const vl_index) -> u64;
@@ -318,6 +321,58 @@ impl GpuFlatIndex {
             VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
             _ => Err(VectorLiteError::InternalError(err)),
         }
+    }
+
+    /// `search_range` for a batch of queries against one index state (no reference counterpart): entry `i` holds at most
+    /// `limit` results of `search_range(queries[i], min_scores[i], metric, ..)` and the number of rows that qualify.
+    /// All queries must have the index's dimension.  Single-GPU handles only.
+    pub fn search_range_batch(&self, queries: &[Vec<f64>], min_scores: &[f64], metric: SimilarityMetric, limit: usize) -> VectorLiteResult<Vec<(Vec<SearchResult>, usize)>> {
+        let nq = queries.len();
+        if nq == 0 {
+            return Ok(Vec::new());
+        }
+        let q_len = queries[0].len();
+        if min_scores.len() != nq || queries.iter().any(|q| q.len() != q_len) {
+            return Err(VectorLiteError::InternalError("search_range_batch: one threshold per query, queries of one length".to_string()));
+        }
+        let flat: Vec<f64> = queries.iter().flat_map(|q| q.iter().copied()).collect();
+        let (mut out_ids, mut scores) = (vec![0u64; (nq * limit).max(1)], vec![0f64; (nq * limit).max(1)]);
+        let (mut n, mut total) = (vec![0u64; nq], vec![0u64; nq]);
+        let rc = unsafe {
+            vl_index_search_range_batch(self.0.raw, 0, flat.as_ptr(), nq as u64, q_len as u64, min_scores.as_ptr(), metric_code(metric), limit as u64, out_ids.as_mut_ptr(), scores.as_mut_ptr(), n.as_mut_ptr(), total.as_mut_ptr())
+        };
+        match rc {
+            VL_OK => Ok((0..nq)
+                .map(|qi| {
+                    let results = (0..n[qi] as usize)
+                        .map(|i| {
+                            let id = out_ids[qi * limit + i];
+                            let (text, metadata) = self.0.side.get(&id).cloned().unwrap_or_default();
+                            SearchResult { id, score: scores[qi * limit + i], text, metadata }
+                        })
+                        .collect();
+                    (results, total[qi] as usize)
+                })
+                .collect()),
+            VL_ERR_DIM_MISMATCH => {
+                let (mut e, mut a) = (0u64, 0u64);
+                unsafe { vl_last_dim_mismatch(&mut e, &mut a) };
+                Err(VectorLiteError::DimensionMismatch { expected: e as usize, actual: a as usize })
+            }
+            VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
+            _ => Err(VectorLiteError::InternalError(last_error())),
+        }
+    }
+
+    /// Routing of the last `search_range_batch`: queries answered by the MFMA pass, the single-query fast route, the exact
+    /// route, and the largest candidate count the MFMA pass kept for one query.
+    pub fn last_range_batch(&self) -> (u64, u64, u64, u64) {
+        let (mut a, mut b, mut c, mut d) = (0u64, 0u64, 0u64, 0u64);
+        unsafe {
+            vl_index_last_range_batch(self.0.raw, &mut a, &mut b, &mut c);
+            vl_index_last_range_batch_candidates(self.0.raw, &mut d);
+        }
+        (a, b, c, d)
     }
 
     /// Every row whose score is at least `min_score` (no reference counterpart): the longest prefix of

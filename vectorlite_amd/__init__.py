@@ -256,6 +256,44 @@ def _search_range(L, h, query, min_score: float, metric: int, token: int, limit)
         return ids[:m].copy(), scores[:m].copy(), int(total.value)
 
 
+def _search_range_batch(L, h, queries, min_score, metric: int, token: int, limit):
+    """vl_index_search_range_batch -> (ids_list, scores_list, totals).  limit=None: everything.  The first call's rows hold
+    64 entries; the queries whose total is larger -- only those -- are asked again as a second batch with rows sized from
+    their largest count (repeated if rows arrived in between).  That second batch's buffers are (overflowing queries) x
+    (largest total) x 16 bytes: a caller who expects many low-selectivity queries should pass a `limit`."""
+    q = np.ascontiguousarray(_f64(queries))
+    if q.ndim != 2:
+        raise ValueError("queries must be a 2-d array [nq, dim]")
+    nq, dim = q.shape
+    ms = np.ascontiguousarray(np.broadcast_to(np.asarray(min_score, dtype=np.float64), (nq,)))
+
+    def call(qs, mss, stride):
+        m = qs.shape[0]
+        ids = np.empty((m, max(stride, 1)), dtype=np.uint64)
+        scores = np.empty((m, max(stride, 1)), dtype=np.float64)
+        n = np.zeros(max(m, 1), dtype=np.uint64)
+        total = np.zeros(max(m, 1), dtype=np.uint64)
+        rc = L.vl_index_search_range_batch(h, int(token), qs.ctypes.data, m, dim, mss.ctypes.data, int(metric), stride,
+                                           ids.ctypes.data if stride else None, scores.ctypes.data if stride else None,
+                                           n.ctypes.data, total.ctypes.data)
+        if rc == VL_ERR_INVALID_ARG:
+            raise IndexOpError(_last_error())
+        _raise(rc)
+        return ([ids[i, :int(n[i])].copy() for i in range(m)], [scores[i, :int(n[i])].copy() for i in range(m)],
+                total[:m].astype(np.int64))
+
+    stride = 64 if limit is None else max(int(limit), 0)
+    ids_l, scores_l, totals = call(q, ms, stride)
+    while limit is None:
+        over = np.nonzero(totals > np.array([x.size for x in ids_l], dtype=np.int64))[0]
+        if over.size == 0:
+            break
+        i2, s2, t2 = call(np.ascontiguousarray(q[over]), np.ascontiguousarray(ms[over]), int(totals[over].max()))
+        for j, qi in enumerate(over.tolist()):
+            ids_l[qi], scores_l[qi], totals[qi] = i2[j], s2[j], t2[j]
+    return ids_l, scores_l, totals
+
+
 def _search_mmr(L, h, query, k: int, fetch_k: int, lambda_mult: float, metric: int, token: int):
     """vl_index_search_mmr -> (ids, scores) in selection order."""
     q = _f64(query).ravel()
@@ -439,6 +477,42 @@ class FlatIndex:
             text, md = self._meta.get(i, ("", None))
             out.append(SearchResult(id=i, score=s, text=text, metadata=md))
         return out
+
+    def search_range_batch_arrays(self, queries, min_score, metric: int = 0, filter=None, limit=None):
+        """(ids_list, scores_list, totals) for queries [nq, dim]: entry i is search_range_arrays(queries[i], min_score[i], ...)
+        on one index state.  `min_score` is a scalar or one value per query; `limit` caps what is returned per query
+        (0: count only), None returns every qualifying row.  With limit=None the queries with more than 64 qualifying rows
+        are asked a second time: if a writer runs between the two calls they are answered on a later index state than the
+        rest of the batch -- pass a `limit` where one state for the whole batch matters."""
+        if filter is None:
+            return _search_range_batch(self._L, self._h, queries, min_score, metric, 0, limit)
+        tok, temp = self._filter_token(filter)
+        try:
+            return _search_range_batch(self._L, self._h, queries, min_score, metric, tok, limit)
+        finally:
+            if temp is not None:
+                temp.close()
+
+    def search_range_batch(self, queries, min_score, similarity_metric: int = SimilarityMetric.Cosine, filter=None,
+                           limit=None) -> List[List[SearchResult]]:
+        ids_list, scores_list, _ = self.search_range_batch_arrays(queries, min_score, similarity_metric, filter=filter, limit=limit)
+        out = []
+        for ids, scores in zip(ids_list, scores_list):
+            row = []
+            for i, s in zip(ids.tolist(), scores.tolist()):
+                text, md = self._meta.get(i, ("", None))
+                row.append(SearchResult(id=i, score=s, text=text, metadata=md))
+            out.append(row)
+        return out
+
+    def last_range_batch(self):
+        """Routing of the last search_range_batch on this handle: queries answered by the MFMA pass, by the single-query
+        fast route, by the exact route, and the largest candidate count the MFMA pass kept for one query."""
+        a, b, c, d = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _raise(self._L.vl_index_last_range_batch(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        _raise(self._L.vl_index_last_range_batch_candidates(self._h, C.byref(d)))
+        return {"mfma_queries": int(a.value), "single_queries": int(b.value), "exact_queries": int(c.value),
+                "max_candidates": int(d.value)}
 
     # ---- diversified (MMR) search ------------------------------------------------------------
     def search_mmr_arrays(self, query, k: int, fetch_k: int = 20, lambda_mult: float = 0.5, metric: int = 0, filter=None):
@@ -919,6 +993,13 @@ class HNSWIndex:
 
     def search_range(self, query, min_score: float, similarity_metric: int = SimilarityMetric.Cosine, filter=None, limit=None):
         return self.search_range_arrays(query, min_score, similarity_metric, filter, limit)
+
+    def search_range_batch_arrays(self, queries, min_score, metric: int = 0, filter=None, limit=None):
+        """Batched range search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""
+        return _search_range_batch(self._L, self._h, queries, min_score, metric, 0, limit)
+
+    def search_range_batch(self, queries, min_score, similarity_metric: int = SimilarityMetric.Cosine, filter=None, limit=None):
+        return self.search_range_batch_arrays(queries, min_score, similarity_metric, filter, limit)
 
     def search_mmr_arrays(self, query, k: int, fetch_k: int = 20, lambda_mult: float = 0.5, metric: int = 0, filter=None):
         """Diversified search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""

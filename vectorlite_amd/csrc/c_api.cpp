@@ -378,6 +378,37 @@ int vl_index_search_range(const vl_index* h, uint64_t filter, const double* quer
     });
 }
 
+int vl_index_search_range_batch(const vl_index* h, uint64_t filter, const double* queries, uint64_t nq, uint64_t q_len,
+                                const double* min_scores, int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores,
+                                uint64_t* out_n, uint64_t* out_total)
+{
+    return guarded([&]() -> int {
+        if (!h) return VL_ERR_INVALID_ARG;
+        if (!h->flat) {
+            vl::set_last_error("range search is served by single-GPU flat indexes");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (nq != 0 && (!out_n || !out_total || !min_scores)) return VL_ERR_INVALID_ARG;
+        if (nq != 0 && (!out_ids || !out_scores) && out_stride != 0) return VL_ERR_INVALID_ARG;
+        return h->flat->search_range_batch(filter, queries, nq, q_len, min_scores, metric, out_stride, out_ids, out_scores, out_n,
+                                           out_total);
+    });
+}
+
+int vl_index_last_range_batch(const vl_index* h, uint64_t* mfma_queries, uint64_t* single_queries, uint64_t* exact_queries)
+{
+    if (!h || !h->flat) return VL_ERR_INVALID_ARG;
+    h->flat->last_range_batch(mfma_queries, single_queries, exact_queries, nullptr);
+    return VL_OK;
+}
+
+int vl_index_last_range_batch_candidates(const vl_index* h, uint64_t* max_candidates)
+{
+    if (!h || !h->flat || !max_candidates) return VL_ERR_INVALID_ARG;
+    h->flat->last_range_batch(nullptr, nullptr, nullptr, max_candidates);
+    return VL_OK;
+}
+
 static_assert(VL_MMR_MAX_FETCH == vl::MMR_MAX_FETCH, "the header states the kernels' limit");
 
 int vl_index_search_mmr(const vl_index* h, uint64_t filter, const double* query, uint64_t q_len, uint64_t k, uint64_t fetch_k,

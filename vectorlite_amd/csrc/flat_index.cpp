@@ -104,10 +104,12 @@ Workspace::~Workspace()
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
     void* dev[] = {d_q64, d_partials, d_partials64, d_result, d_nan, d_scores, d_okeys,
-                   d_opos, d_out_pos, d_out_scores, d_positions, d_dists, rg_ctr, rg_cand, rg_scores, rg_keys, rg_pv, mmr_sim};
+                   d_opos, d_out_pos, d_out_scores, d_positions, d_dists, rg_ctr, rg_cand, rg_scores, rg_keys, rg_pv, mmr_sim,
+                   rb_ctr, rb_min, rb_sv_score, rb_sv_pos};
     for (void* p : dev)
         if (p) (void)hipFree(p);
-    void* host[] = {h_q64, h_result, h_nan, mf_h_q64, mf_h_result, mf_h_dom, k3_h_q64, k3_h_result, rg_h_ctr, rg_h_pos, rg_h_scores};
+    void* host[] = {h_q64, h_result, h_nan, mf_h_q64, mf_h_result, mf_h_dom, k3_h_q64, k3_h_result, rg_h_ctr, rg_h_pos, rg_h_scores,
+                    rb_h_thr, rb_h_min, rb_h_ctr, rb_h_cnt, rb_h_pos, rb_h_scores};
     for (void* p : host)
         if (p) (void)hipHostFree(p);
     void* mfd[] = {mf.q_bf16, mf.gmax, mf.thr, mf.cand, mf.cnt, mf_d_q64, mf_lists, mf_scores, k3_d_q64};
@@ -2476,6 +2478,272 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
     }
     if (rc != OK) (void)hipStreamSynchronize(st);
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Batched range search: nq range queries against one index state.  The MFMA filter is a threshold
+// filter, and for a range query the threshold is known before the first launch: the smallest bf16 key whose bound
+// (score_bound.hpp, with the filter's in_extra) reaches min_score.  One pass of the shipped pass-1 kernel, then rescore /
+// cut / rank / emit on the device; a query leaves this route only when its candidate buffer overflows, a score is NaN or
+// more than RBATCH_SEG rows qualify -- then the single call answers it under the same lock.
+// ---------------------------------------------------------------------------------------------
+namespace {
+constexpr size_t RBATCH_SPEC = 65536;  // packed answer entries copied back with the counters (768 KB)
+uint32_t range_batch_candidate_capacity()
+{
+    // VL_RANGE_BATCH_CAND_CAP: smaller per-query candidate buffers (tests drive the overflow route with it)
+    if (const char* e = getenv("VL_RANGE_BATCH_CAND_CAP")) {
+        const long long v = atoll(e);
+        if (v >= 1 && v <= (long long)MFMA_CAND_CAP) return (uint32_t)v;
+    }
+    return (uint32_t)MFMA_CAND_CAP;
+}
+}  // namespace
+
+int GpuFlatIndex::ensure_range_batch_ws(Workspace* ws, uint64_t seq_queries) const
+{
+    if (!ws->rb_ctr) {
+        VL_TRY(dev_alloc(&ws->rb_ctr, (size_t)MFMA_MAX_BATCH * RBATCH_CTR_WORDS));
+        VL_TRY(dev_alloc(&ws->rb_min, (size_t)MFMA_MAX_BATCH));
+        VL_TRY(pinned_alloc(&ws->rb_h_thr, (size_t)MFMA_MAX_BATCH));
+        VL_TRY(pinned_alloc(&ws->rb_h_min, (size_t)MFMA_MAX_BATCH));
+        VL_TRY(pinned_alloc(&ws->rb_h_ctr, (size_t)MFMA_MAX_BATCH * RBATCH_CTR_WORDS));
+        VL_TRY(pinned_alloc(&ws->rb_h_cnt, (size_t)MFMA_MAX_BATCH));
+        VL_TRY(pinned_alloc(&ws->rb_h_pos, RBATCH_SPEC));
+        VL_TRY(pinned_alloc(&ws->rb_h_scores, RBATCH_SPEC));
+    }
+    if (ws->rb_sv_queries < seq_queries) {  // as many survivor segments as the largest sequence so far had queries
+        if (ws->rb_sv_score) (void)hipFree(ws->rb_sv_score);
+        if (ws->rb_sv_pos) (void)hipFree(ws->rb_sv_pos);
+        ws->rb_sv_score = nullptr;
+        ws->rb_sv_pos = nullptr;
+        ws->rb_sv_queries = 0;
+        VL_TRY(dev_alloc(&ws->rb_sv_score, (size_t)seq_queries * RBATCH_SEG));
+        VL_TRY(dev_alloc(&ws->rb_sv_pos, (size_t)seq_queries * RBATCH_SEG));
+        ws->rb_sv_queries = seq_queries;
+    }
+    return OK;
+}
+
+int GpuFlatIndex::search_range_batch(uint64_t token, const double* queries, uint64_t nq, uint64_t q_len, const double* min_scores,
+                                     int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
+                                     uint64_t* out_total) const
+{
+    uint64_t routes[4] = {0, 0, 0, 0};  // MFMA route, single fast route, exact route; largest kept candidate count
+    auto publish = [&]() {
+        for (int i = 0; i < 4; ++i) last_rbatch_[i].store(routes[i], std::memory_order_relaxed);
+    };
+    if (nq == 0) {
+        publish();
+        return OK;
+    }
+    if (!out_n || !out_total || !min_scores) return ERR_INVALID_ARG;
+    for (uint64_t i = 0; i < nq; ++i) {
+        out_n[i] = 0;
+        out_total[i] = 0;
+    }
+    std::shared_ptr<IdFilter> f;
+    if (token != 0) {
+        f = find_filter(token);
+        if (!f) {
+            set_last_error("unknown or destroyed filter");
+            return ERR_INVALID_ARG;
+        }
+    }
+    if (metric < 0 || metric > 3) {
+        set_last_error("unknown metric");
+        return ERR_INVALID_ARG;
+    }
+    std::shared_lock<RwLock> lk(mu_);  // one index state for the whole batch
+    const uint64_t n = ids_.size();
+    if (n != 0 && q_len != dim_) {
+        set_dim_mismatch(dim_, q_len);
+        set_last_error("Dimension mismatch: expected " + std::to_string(dim_) + ", got " + std::to_string(q_len));
+        return ERR_DIM_MISMATCH;
+    }
+    // The lowest failing query decides the status.  A NaN threshold fails its query before anything is computed, so only the
+    // queries in front of the first one can fail earlier (with a NaN score): they are answered, the rest is not.
+    uint64_t nq_run = nq;
+    for (uint64_t i = 0; i < nq; ++i)
+        if (min_scores[i] != min_scores[i]) {
+            nq_run = i;
+            break;
+        }
+    auto nan_threshold = [&]() -> int {
+        set_last_error("min_score is NaN");
+        return ERR_INVALID_ARG;
+    };
+    if (n == 0) {
+        if (nq_run < nq) return nan_threshold();
+        routes[1] = nq;
+        publish();
+        return OK;
+    }
+    if ((!queries && dim_) || (out_stride != 0 && !out_scores)) return ERR_INVALID_ARG;
+
+    VL_HIP(hipSetDevice(device_));
+    Workspace* ws = acquire_ws();
+    if (!ws) return ERR_DEVICE;
+    struct Releaser {
+        const GpuFlatIndex* self;
+        Workspace* ws;
+        ~Releaser()
+        {
+            (void)hipStreamSynchronize(ws->stream);
+            self->release_ws(ws);
+        }
+    } rel{this, ws};
+    if (f) {
+        std::lock_guard<std::mutex> fg(f->mu);
+        if (f->resolved_at != mutations_) VL_TRY(resolve_filter(ws, f.get()));
+    }
+    auto single = [&](uint64_t qi) -> int {
+        if (f && f->m == 0) {  // an empty subset: nothing qualifies (search_range's early return)
+            routes[1] += 1;
+            return OK;
+        }
+        active_searches_.fetch_add(1, std::memory_order_relaxed);
+        const int rc = search_range_locked(ws, f.get(), queries + qi * dim_, min_scores[qi], metric, out_stride, nullptr,
+                                           out_ids ? out_ids + qi * out_stride : nullptr,
+                                           out_scores ? out_scores + qi * out_stride : nullptr, out_n + qi, out_total + qi);
+        active_searches_.fetch_sub(1, std::memory_order_relaxed);
+        if (rc == OK) routes[last_path() == PATH_EXACT_SORT ? 2 : 1] += 1;
+        return rc;
+    };
+
+    std::vector<uint8_t> done(nq_run, 0);
+    const char* mf_env = getenv("VL_MFMA");
+    const char* mf_min = getenv("VL_MFMA_MIN_BATCH");
+    const uint64_t mfma_min = mf_min && *mf_min ? (uint64_t)atoi(mf_min) : (uint64_t)MFMA_MIN_BATCH;
+    // (no minimum row count: the floor of the top-k batch belongs to its sampling pass, and this route has none)
+    // The filter keeps `key >= thr`, which drops a NaN key, where the single scan's `!(key <= tau)` keeps it.  That is sound
+    // only because NaN keys cannot occur on this route: rows outside the fast-path domain (n_out_of_domain_ != 0) take the
+    // whole batch off it, and a query outside the domain is staged as zeros with thr = +inf and answered by the single call.
+    const bool fast = !f && nq_run >= mfma_min && force_path_.load() == 0 && n_out_of_domain_ == 0 && !(mf_env && mf_env[0] == '0') &&
+                      mfma_scan_supported((uint32_t)dim_, metric) && mfma_rows_kernel((uint32_t)dim_);
+    if (fast) {
+        VL_TRY(search_range_batch_mfma(ws, queries, nq_run, min_scores, metric, out_stride, out_ids, out_scores, out_n, out_total,
+                                       &done, &routes[3]));
+        for (uint64_t qi = 0; qi < nq_run; ++qi) routes[0] += done[qi] ? 1 : 0;
+    }
+    // what the MFMA route did not take (or everything), in ascending order: the first failure is the lowest failing query
+    for (uint64_t qi = 0; qi < nq_run; ++qi)
+        if (!done[qi]) VL_TRY(single(qi));
+    if (nq_run < nq) return nan_threshold();
+    set_last_path(routes[2] ? PATH_EXACT_SORT : PATH_FAST);
+    publish();
+    return OK;
+}
+
+int GpuFlatIndex::search_range_batch_mfma(Workspace* ws, const double* queries, uint64_t nq, const double* min_scores, int metric,
+                                          uint64_t out_stride, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
+                                          uint64_t* out_total, std::vector<uint8_t>* done, uint64_t* max_candidates) const
+{
+    const uint64_t n = ids_.size();
+    VL_TRY(ensure_bf16_slab(true));  // the row-stationary kernel's fragment-major slab, built as search_batch builds it
+    VL_TRY(ensure_mfma_scratch(ws));
+    const uint64_t seq = mfma_sequence_queries((uint32_t)dim_);
+    VL_TRY(ensure_range_batch_ws(ws, std::min<uint64_t>(seq, nq)));
+    hipStream_t st = ws->stream;
+    const uint32_t ldb = mfma_ldb((uint32_t)dim_);
+    const uint32_t cap = range_batch_candidate_capacity();
+    const uint32_t emit_cap = (uint32_t)std::min<uint64_t>(out_stride, RBATCH_SEG);
+    std::vector<uint8_t> staged;
+    for (uint64_t q0 = 0; q0 < nq; q0 += seq) {
+        const uint32_t g = (uint32_t)std::min<uint64_t>(seq, nq - q0);
+        const size_t packed_cap = std::max<size_t>((size_t)g * emit_cap, 1);
+        VL_TRY(ensure_range_ws(ws, 0, packed_cap));  // (allocates only while the stream is idle: every sequence ends in a sync)
+        if (ws->mf_h2d_pending) {  // a top-k batch's copies out of the pinned staging area
+            VL_HIP(hipEventSynchronize(ws->mf_ev_h2d));
+            ws->mf_h2d_pending = false;
+        }
+        // stage: the queries as the top-k batch stages them, and per query the key threshold.  (R, Q) are the conventions of
+        // that path's bound check: the index's largest row norm, the staged query norm, n = the bf16 row stride.
+        staged.assign(g, 0);
+        for (uint32_t j = 0; j < g; ++j) {
+            double norm = 0.0;
+            const bool in_domain = stage_query(queries + (q0 + j) * dim_, ws->mf_h_q64 + (size_t)j * dim_, dim_, &norm);
+            float thr = INFINITY;  // no candidates: the query is peeled off to the single call, or nothing can qualify
+            if (in_domain) {
+                const RangeKeys r = range_key_threshold(metric, ldb, max_row_norm_, norm, min_scores[q0 + j], IN_EXTRA_MFMA, &thr);
+                if (r == RANGE_KEYS_ALL) thr = INFINITY;  // every row a candidate (-inf, a zero query under cosine): not a filter's job
+                else staged[j] = 1;
+            }
+            ws->rb_h_thr[j] = thr;
+            ws->rb_h_min[j] = min_scores[q0 + j];
+        }
+        VL_HIP(hipMemcpyAsync(ws->mf_d_q64, ws->mf_h_q64, (size_t)g * dim_ * sizeof(double), hipMemcpyHostToDevice, st));
+        VL_HIP(hipMemcpyAsync(ws->mf.thr, ws->rb_h_thr, (size_t)g * sizeof(float), hipMemcpyHostToDevice, st));
+        VL_HIP(hipMemcpyAsync(ws->rb_min, ws->rb_h_min, (size_t)g * sizeof(double), hipMemcpyHostToDevice, st));
+        VL_HIP(hipMemsetAsync(ws->rb_ctr, 0, (size_t)g * RBATCH_CTR_WORDS * sizeof(uint32_t), st));
+        MfmaLaunchInfo li;
+        VL_HIP(launch_mfma_range_candidates(st, metric, d_slab16f_, d_norm16_, d_sqnorm_, ws->mf_d_q64, g, n, (uint32_t)dim_, ws->mf,
+                                            cap, &li));
+        {
+            const int v[6] = {li.ksteps, li.metric, li.chunks, li.grid_x, li.stages, li.sample_blocks};
+            for (int i = 0; i < 6; ++i) last_filter_[i].store(v[i], std::memory_order_relaxed);
+        }
+        VL_HIP(launch_range_batch_tail(st, metric, ws->mf.cand, ws->mf.cnt, cap, g, d_master_, ws->mf_d_q64, ws->rb_min, (uint32_t)dim_,
+                                       n, emit_cap, ws->rb_sv_score, ws->rb_sv_pos, ws->rb_ctr, ws->d_out_pos, ws->d_out_scores));
+        // one copy back: counters, flags and the packed prefixes (as much of them as the speculative buffer holds)
+        const size_t spec = std::min<size_t>((size_t)g * emit_cap, RBATCH_SPEC);
+        VL_HIP(hipMemcpyAsync(ws->rb_h_ctr, ws->rb_ctr, (size_t)g * RBATCH_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipMemcpyAsync(ws->rb_h_cnt, ws->mf.cnt, (size_t)g * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (spec) {
+            VL_HIP(hipMemcpyAsync(ws->rb_h_pos, ws->d_out_pos, spec * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            VL_HIP(hipMemcpyAsync(ws->rb_h_scores, ws->d_out_scores, spec * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        VL_HIP(hipStreamSynchronize(st));
+
+        // which queries the device answered, and how many packed entries that makes
+        size_t packed = 0;
+        for (uint32_t j = 0; j < g; ++j) {
+            const uint32_t* c = ws->rb_h_ctr + (size_t)j * RBATCH_CTR_WORDS;
+            const bool ok = staged[j] && ws->rb_h_cnt[j] <= cap && c[RBATCH_CTR_NAN] == 0 && c[RBATCH_CTR_TOTAL] <= RBATCH_SEG;
+            if (!ok) {
+                staged[j] = 0;
+                continue;
+            }
+            const uint32_t want = (uint32_t)std::min<uint64_t>(c[RBATCH_CTR_TOTAL], emit_cap);
+            if (c[RBATCH_CTR_TOTAL] > ws->rb_h_cnt[j] || c[RBATCH_CTR_WANT] != want || (size_t)c[RBATCH_CTR_OFF] + want > packed_cap) {
+                set_last_error("batched range tail reported inconsistent counts (kernel bug)");
+                return ERR_DEVICE;
+            }
+            packed = std::max(packed, (size_t)c[RBATCH_CTR_OFF] + want);
+            if (max_candidates && ws->rb_h_cnt[j] > *max_candidates) *max_candidates = ws->rb_h_cnt[j];
+        }
+        std::vector<uint32_t> more_pos;
+        std::vector<double> more_scores;
+        if (packed > spec) {  // long answers: the rest of the packed prefixes
+            more_pos.resize(packed - spec);
+            more_scores.resize(packed - spec);
+            VL_HIP(hipMemcpyAsync(more_pos.data(), ws->d_out_pos + spec, (packed - spec) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            VL_HIP(hipMemcpyAsync(more_scores.data(), ws->d_out_scores + spec, (packed - spec) * sizeof(double), hipMemcpyDeviceToHost,
+                                  st));
+            VL_HIP(hipStreamSynchronize(st));
+        }
+        for (uint32_t j = 0; j < g; ++j) {
+            if (!staged[j]) continue;
+            const uint64_t qi = q0 + j;
+            const uint32_t* c = ws->rb_h_ctr + (size_t)j * RBATCH_CTR_WORDS;
+            const size_t off = c[RBATCH_CTR_OFF];
+            const uint32_t want = c[RBATCH_CTR_WANT];
+            for (uint32_t i = 0; i < want; ++i) {
+                const size_t e = off + i;
+                const uint32_t p = e < spec ? ws->rb_h_pos[e] : more_pos[e - spec];
+                if (p >= n) {
+                    set_last_error("batched range search returned an out-of-range position (kernel bug)");
+                    return ERR_DEVICE;
+                }
+                if (out_ids) out_ids[qi * out_stride + i] = ids_[p];
+                out_scores[qi * out_stride + i] = e < spec ? ws->rb_h_scores[e] : more_scores[e - spec];
+            }
+            out_n[qi] = want;
+            out_total[qi] = c[RBATCH_CTR_TOTAL];
+            (*done)[qi] = 1;
+        }
+    }
+    return OK;
 }
 
 // Queries in device memory.  The MFMA batch path takes them where they are; everything else goes through the host.

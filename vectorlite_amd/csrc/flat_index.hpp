@@ -89,6 +89,18 @@ struct Workspace {
     size_t rg_sort_cap = 0;
     uint32_t* rg_h_pos = nullptr;    // pinned [RANGE_SMALL]
     double* rg_h_scores = nullptr;   // pinned [RANGE_SMALL]
+    // batched range search (lazy): per-query counters, thresholds and survivor segments of one launch sequence
+    uint32_t* rb_ctr = nullptr;      // [MFMA_MAX_BATCH, RBATCH_CTR_WORDS]
+    double* rb_min = nullptr;        // [MFMA_MAX_BATCH] min_scores
+    double* rb_sv_score = nullptr;   // [rb_sv_queries, RBATCH_SEG]
+    uint32_t* rb_sv_pos = nullptr;   // [rb_sv_queries, RBATCH_SEG]
+    size_t rb_sv_queries = 0;
+    float* rb_h_thr = nullptr;       // pinned [MFMA_MAX_BATCH]
+    double* rb_h_min = nullptr;      // pinned [MFMA_MAX_BATCH]
+    uint32_t* rb_h_ctr = nullptr;    // pinned [MFMA_MAX_BATCH, RBATCH_CTR_WORDS]
+    uint32_t* rb_h_cnt = nullptr;    // pinned [MFMA_MAX_BATCH]
+    uint32_t* rb_h_pos = nullptr;    // pinned [RBATCH_SPEC]: packed answers copied back before the host knows their number
+    double* rb_h_scores = nullptr;   // pinned [RBATCH_SPEC]
     // diversified search (lazy): the candidates' pairwise similarities, [MMR_MAX_FETCH][MMR_MAX_FETCH] (8 MB)
     double* mmr_sim = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -214,6 +226,20 @@ public:
     // min(total, out_capacity) entries are written (out_capacity = 0: count only, outputs may be null).
     int search_range(uint64_t token, const double* query, uint64_t q_len, double min_score, int metric, uint64_t out_capacity,
                      uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n, uint64_t* out_total) const;
+    // NEW (no reference counterpart): nq range searches against one index state; row i of the [nq, out_stride] outputs is
+    // exactly search_range(token, queries + i * q_len, q_len, min_scores[i], metric, out_stride, ...).  Returns the status of
+    // the lowest-index failing query.  DESIGN.md section 17.
+    int search_range_batch(uint64_t token, const double* queries, uint64_t nq, uint64_t q_len, const double* min_scores, int metric,
+                           uint64_t out_stride, uint64_t* out_ids, double* out_scores, uint64_t* out_n, uint64_t* out_total) const;
+    // the last search_range_batch on this handle: queries answered by the MFMA pass + device tail, by the single-query fast
+    // route (k_scan_range), by the exact route; and the largest candidate count the MFMA pass reported for a query it kept
+    void last_range_batch(uint64_t* mfma, uint64_t* single, uint64_t* exact, uint64_t* max_candidates) const
+    {
+        if (mfma) *mfma = last_rbatch_[0].load(std::memory_order_relaxed);
+        if (single) *single = last_rbatch_[1].load(std::memory_order_relaxed);
+        if (exact) *exact = last_rbatch_[2].load(std::memory_order_relaxed);
+        if (max_candidates) *max_candidates = last_rbatch_[3].load(std::memory_order_relaxed);
+    }
     // NEW (no reference counterpart): maximal marginal relevance over C = FlatIndex::search(q, fetch_k, metric) on the whole
     // index (token 0) or the filter's rows: sel[0] = C[0], then greedily the candidate maximising
     // lambda * score - (1 - lambda) * (largest reference similarity to anything chosen), ties to the better-ranked one.
@@ -335,6 +361,11 @@ private:
     int search_range_locked(Workspace* ws, IdFilter* f, const double* query, double min_score, int metric, uint64_t out_capacity,
                             uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
                             uint64_t* out_total) const;  // mu_ held (shared), f resolved (nullptr: the whole index)
+    int ensure_range_batch_ws(Workspace* ws, uint64_t seq_queries) const;
+    // the MFMA route of search_range_batch (mu_ held, whole index): done[qi] is set for every query answered here
+    int search_range_batch_mfma(Workspace* ws, const double* queries, uint64_t nq, const double* min_scores, int metric,
+                                uint64_t out_stride, uint64_t* out_ids, double* out_scores, uint64_t* out_n, uint64_t* out_total,
+                                std::vector<uint8_t>* done, uint64_t* max_candidates) const;
     int wait_result(Workspace* ws, uint32_t seq) const;
     int ensure_i8_slab() const;  // lazily builds the int8 copy the single-query int8 filter streams
     int ensure_bf16_slab(bool frag_major) const;  // lazily builds the bf16 slab (row-major, or MFMA fragment order) a filter streams
@@ -422,6 +453,7 @@ private:
     mutable std::atomic<int> active_searches_{0};
     mutable std::atomic<int> last_scan_variant_{0}, last_scan_grid_{0}, last_scan_qarg_{0};
     mutable std::atomic<int> last_filter_[6] = {};
+    mutable std::atomic<uint64_t> last_rbatch_[4] = {};
     mutable std::mutex prof_mu_;
     mutable uint64_t prof_n_ = 0;
     mutable double prof_ms_ = 0.0;

@@ -1430,6 +1430,149 @@ __global__ void k_range_emit(const unsigned long long* __restrict__ pv, const do
     }
 }
 
+// ---- batched range search: the segmented tail behind the MFMA filter's one pass ----------------
+// Query q's candidates are cand[q * cap + i], i < cnt[q] (the filter's per-query buffers; a counter above cap means the
+// buffer or a ring segment overflowed: the query is left alone and the host redoes it).  ctr: RBATCH_CTR_WORDS words per
+// query, zeroed by the caller in front of each launch sequence.
+//
+// Rescore + cut: workgroup (x, q) rescores tiles x, x + gridDim.x, ... of 16 candidates of query q with the batch
+// finalize's rescore_rows_par (products by all threads, one lane per row adds them in index order: the reference's
+// arithmetic, many rows and queries in flight), then cuts on score >= min_scores[q]: survivors are appended (one atomic per
+// tile) as (score, position) to the query's segment of RBATCH_SEG entries; ctr[TOTAL] counts them all.
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_rbatch_rescore_cut(const Cand32* __restrict__ cand, const uint32_t* __restrict__ cnt,
+                                                            uint32_t cap, const double* __restrict__ master,
+                                                            const double* __restrict__ q64, const double* __restrict__ min_scores,
+                                                            uint32_t dim, uint32_t n_rows, double* __restrict__ sv_score,
+                                                            uint32_t* __restrict__ sv_pos, uint32_t* __restrict__ ctr)
+{
+    const uint32_t q = blockIdx.y;
+    const uint32_t m = cnt[q];
+    if (m == 0 || m > cap) return;  // workgroup-uniform
+    __shared__ RescoreLds<METRIC, BF_ROWS, BF_NCH> rs;
+    __shared__ uint32_t sh_pos[BF_ROWS];
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
+    const Cand32* mine = cand + (size_t)q * cap;
+    q64 += (size_t)q * dim;
+    const double cut = min_scores[q];
+    uint32_t* my_ctr = ctr + (size_t)q * RBATCH_CTR_WORDS;
+    constexpr int QN = (RP_CH * BF_NCH + 255) / 256;
+    double q_first[QN];
+#pragma unroll
+    for (int j = 0; j < QN; ++j) {
+        const uint32_t c = (uint32_t)(tid + j * 256);
+        q_first[j] = q64[c < dim ? c : dim - 1];
+    }
+    for (uint32_t t0 = blockIdx.x * BF_ROWS; t0 < m; t0 += gridDim.x * BF_ROWS) {  // workgroup-uniform trip count
+        const int n_here = (int)((m - t0) < (uint32_t)BF_ROWS ? (m - t0) : (uint32_t)BF_ROWS);
+        __syncthreads();  // the previous tile's positions are consumed
+        if (tid < BF_ROWS) {
+            const uint32_t p = mine[t0 + (uint32_t)(tid < n_here ? tid : n_here - 1)].pos;
+            sh_pos[tid] = p < n_rows ? p : n_rows - 1;
+        }
+        __syncthreads();
+        Acc64<METRIC> A;
+        rescore_rows_par<METRIC, BF_ROWS, 256, BF_NCH>(master, q64, dim, sh_pos, n_here, rs, A, q_first);
+        if (wave == 0) {
+            const bool valid = lane < n_here;
+            const double sc = valid ? A.score() : 0.0;
+            if (valid && sc != sc) atomicOr(my_ctr + RBATCH_CTR_NAN, 1u);
+            const bool keep = valid && sc >= cut;
+            const unsigned long long bal = __ballot(keep);
+            if (bal != 0ull) {  // wave-uniform
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(my_ctr + RBATCH_CTR_TOTAL, (uint32_t)__popcll(bal));
+                base = __shfl(base, 0);
+                const uint32_t slot = base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+                if (keep && slot < RBATCH_SEG) {
+                    sv_score[(size_t)q * RBATCH_SEG + slot] = sc;
+                    sv_pos[(size_t)q * RBATCH_SEG + slot] = sh_pos[lane];
+                }
+            }
+        }
+    }
+}
+
+// Where each query's answer goes in the packed output: want[q] = min(total, emit_cap) for a query the device answers
+// (candidate buffer not overflowed, no NaN score, at most RBATCH_SEG survivors), 0 otherwise; off[q] = the sum of the
+// want[] in front of it.  One workgroup.
+__global__ __launch_bounds__(256) void k_rbatch_offsets(const uint32_t* __restrict__ cnt, uint32_t cap, uint32_t nq, uint32_t emit_cap,
+                                                        uint32_t* __restrict__ ctr)
+{
+    __shared__ uint32_t part[256];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t per = (nq + 255u) / 256u;
+    const uint32_t q0 = tid * per, q1 = (q0 + per) < nq ? (q0 + per) : nq;
+    uint32_t sum = 0;
+    for (uint32_t q = q0; q < q1; ++q) {
+        uint32_t* c = ctr + (size_t)q * RBATCH_CTR_WORDS;
+        const uint32_t total = c[RBATCH_CTR_TOTAL];
+        const bool ok = cnt[q] <= cap && c[RBATCH_CTR_NAN] == 0u && total <= RBATCH_SEG;
+        const uint32_t want = ok ? (total < emit_cap ? total : emit_cap) : 0u;
+        c[RBATCH_CTR_WANT] = want;
+        sum += want;
+    }
+    part[tid] = sum;
+    __syncthreads();
+    uint32_t off = 0;
+    for (uint32_t i = 0; i < tid; ++i) off += part[i];
+    for (uint32_t q = q0; q < q1; ++q) {
+        uint32_t* c = ctr + (size_t)q * RBATCH_CTR_WORDS;
+        c[RBATCH_CTR_OFF] = off;
+        off += c[RBATCH_CTR_WANT];
+    }
+}
+
+// Segmented rank + emit, one workgroup per query: the survivors go to LDS as (desc_key(score), position << 32 | slot),
+// padded to a power of two with entries that sort last; k_bitonic_local's network on pair_greater orders them by (score
+// desc with -0.0 == +0.0, position asc); the first want[q] leave as (position, the score's own bits) at off[q].
+__global__ __launch_bounds__(256) void k_rbatch_rank_emit(const double* __restrict__ sv_score, const uint32_t* __restrict__ sv_pos,
+                                                          const uint32_t* __restrict__ ctr, uint32_t* __restrict__ out_pos,
+                                                          double* __restrict__ out_scores)
+{
+    __shared__ unsigned long long sk[RBATCH_SEG];
+    __shared__ unsigned long long sp[RBATCH_SEG];
+    const uint32_t q = blockIdx.x;
+    const uint32_t* c = ctr + (size_t)q * RBATCH_CTR_WORDS;
+    const uint32_t want = c[RBATCH_CTR_WANT];
+    if (want == 0) return;  // workgroup-uniform: nothing to emit, or the host redoes this query
+    const uint32_t total = c[RBATCH_CTR_TOTAL], off = c[RBATCH_CTR_OFF];  // total <= RBATCH_SEG (k_rbatch_offsets)
+    uint32_t n2 = 2;
+    while (n2 < total) n2 <<= 1;
+    const uint32_t tid = threadIdx.x;
+    const double* my_score = sv_score + (size_t)q * RBATCH_SEG;
+    const uint32_t* my_pos = sv_pos + (size_t)q * RBATCH_SEG;
+    for (uint32_t i = tid; i < n2; i += 256) {
+        const bool real = i < total;
+        sk[i] = real ? desc_key(my_score[i]) : ~0ull;
+        sp[i] = real ? (((unsigned long long)my_pos[i] << 32) | (unsigned long long)i) : ~0ull;
+    }
+    __syncthreads();
+    for (uint32_t k = 2; k <= n2; k <<= 1) {
+        for (uint32_t j = k >> 1; j >= 1; j >>= 1) {
+            for (uint32_t t = tid; t < (n2 >> 1); t += 256) {  // pair (i, i ^ j), i the t-th index whose bit j is clear
+                const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const uint32_t l = i | j;
+                const bool up = ((i & k) == 0);
+                const unsigned long long ka = sk[i], kb = sk[l];
+                const unsigned long long pa = sp[i], pb = sp[l];
+                if (pair_greater<unsigned long long>(ka, pa, kb, pb) == up) {
+                    sk[i] = kb;
+                    sp[i] = pb;
+                    sk[l] = ka;
+                    sp[l] = pa;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (uint32_t i = tid; i < want; i += 256) {
+        const unsigned long long e = sp[i];
+        out_pos[off + i] = (uint32_t)(e >> 32);
+        out_scores[off + i] = my_score[(uint32_t)e];
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // HNSW distance callbacks
 // ---------------------------------------------------------------------------------------------
@@ -2261,6 +2404,25 @@ hipError_t launch_range_rank(hipStream_t s, uint64_t* keys, uint64_t* pv, const 
         const int egrid = (int)(((k + 255) / 256) < 4096 ? ((k + 255) / 256) : 4096);
         hipLaunchKernelGGL(k_range_emit, dim3(egrid), dim3(256), 0, s, op, scores, total_ptr, k, out_pos, out_scores);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_range_batch_tail(hipStream_t s, int metric, const Cand32* cand, const uint32_t* cnt, uint32_t cap, uint32_t nq,
+                                   const double* master, const double* q64, const double* min_scores, uint32_t dim,
+                                   uint64_t n_rows, uint32_t emit_cap, double* sv_score, uint32_t* sv_pos, uint32_t* ctr,
+                                   uint32_t* out_pos, double* out_scores)
+{
+    if (nq == 0 || cap == 0 || n_rows == 0 || n_rows >= 0xFFFFFFFFull || emit_cap > RBATCH_SEG) return hipErrorInvalidValue;
+    // 8 workgroups share a query's tiles of 16 candidates (tens of candidates: 2-3 tiles; a full buffer: 32 tiles each)
+    const hipError_t rc = dispatch_metric(metric, [&](auto M) -> hipError_t {
+        constexpr int MM = decltype(M)::value;
+        hipLaunchKernelGGL((k_rbatch_rescore_cut<MM>), dim3(8, nq), dim3(256), 0, s, cand, cnt, cap, master, q64, min_scores, dim,
+                           (uint32_t)n_rows, sv_score, sv_pos, ctr);
+        return hipGetLastError();
+    });
+    if (rc != hipSuccess) return rc;
+    hipLaunchKernelGGL(k_rbatch_offsets, dim3(1), dim3(256), 0, s, cnt, cap, nq, emit_cap, ctr);
+    if (emit_cap > 0) hipLaunchKernelGGL(k_rbatch_rank_emit, dim3(nq), dim3(256), 0, s, sv_score, sv_pos, ctr, out_pos, out_scores);
     return hipGetLastError();
 }
 

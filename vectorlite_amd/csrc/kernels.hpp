@@ -203,6 +203,20 @@ hipError_t launch_range_cut(hipStream_t s, const double* scores, const uint32_t*
 hipError_t launch_range_rank(hipStream_t s, uint64_t* keys, uint64_t* pv, const double* scores, const uint32_t* total_ptr,
                              uint64_t total, uint64_t k, uint32_t* out_pos, double* out_scores);
 
+// Batched range search: the device tail behind launch_mfma_range_candidates.  cand / cnt / cap are
+// the MFMA filter's per-query candidate buffers; ctr holds RBATCH_CTR_WORDS words per query, zeroed by the caller:
+// [TOTAL] rows of the query with score >= min_scores[q], [NAN] set when a rescored row is NaN, [WANT] entries emitted for
+// the query (0 when the host has to redo it: cnt[q] > cap, a NaN, or more than RBATCH_SEG survivors), [OFF] where they
+// start in the packed outputs.  sv_score / sv_pos: nq x RBATCH_SEG entries of scratch.  out_pos / out_scores receive, per
+// answered query, its first min(total, emit_cap) entries in (score desc, position asc) order; emit_cap <= RBATCH_SEG, so
+// nq x emit_cap entries always hold them.
+constexpr uint32_t RBATCH_SEG = 2048;  // survivors per query the segmented rank holds (one workgroup's LDS sort)
+constexpr int RBATCH_CTR_TOTAL = 0, RBATCH_CTR_NAN = 1, RBATCH_CTR_OFF = 2, RBATCH_CTR_WANT = 3, RBATCH_CTR_WORDS = 4;
+hipError_t launch_range_batch_tail(hipStream_t s, int metric, const Cand32* cand, const uint32_t* cnt, uint32_t cap, uint32_t nq,
+                                   const double* master, const double* q64, const double* min_scores, uint32_t dim,
+                                   uint64_t n_rows, uint32_t emit_cap, double* sv_score, uint32_t* sv_pos, uint32_t* ctr,
+                                   uint32_t* out_pos, double* out_scores);
+
 // Exact path, k <= KP: top-k of scores[] by (score desc, pos asc).
 int select_grid_for(uint64_t n);
 // Ranks 64 r .. 64 r + k - 1 of the exact order: `after` = the (full, k = 64) block of round r - 1, nullptr for r = 0.

@@ -1705,6 +1705,13 @@ int env_shape(uint32_t ldb)
     if (want == 81 || want == 42 || want == 41) return want;
     return 81;
 }
+// Does a pass-1 launch over `chunks` query chunks take the streaming (nontemporal) row loads?  One chunk: nobody re-reads
+// a row block.  VL_MFMA_STREAM_LOADS=0: plain loads everywhere (A/B).  One rule for the top-k filter and the range batch.
+bool pass1_streams(uint32_t chunks)
+{
+    const char* v = getenv("VL_MFMA_STREAM_LOADS");
+    return chunks == 1 && !(v && v[0] == '0');
+}
 int env_grid(uint32_t n_chunks)
 {
     const char* v = getenv("VL_MFMA_GRID");
@@ -1850,10 +1857,7 @@ hipError_t launch_mfma_candidates(hipStream_t s, int metric, const void* slab_bf
 #endif
             const uint32_t n_blk64 = (uint32_t)((n_rows + 63) / 64);
             (void)n_blk64;
-            const bool r_stream = r_chunks == 1 && []() {
-                const char* v = getenv("VL_MFMA_STREAM_LOADS");  // 0: plain loads everywhere (A/B)
-                return !(v && v[0] == '0');
-            }();  // one chunk: nobody re-reads a row block
+            const bool r_stream = pass1_streams(r_chunks);
 #ifdef RS_WIDE_SHAPES  /* stage ends are planned in 32-row blocks: halved (floor) at both ends, the last one ends the index */
 #define VL_RLAUNCH_WIDE(K, MET)                                                                                                 \
     if (wide == 1) {                                                                                                            \
@@ -2011,6 +2015,67 @@ hipError_t launch_mfma_candidates(hipStream_t s, int metric, const void* slab_bf
     if (!launched) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_select_candidates, dim3((nq + 3) / 4), dim3(256), 0, s, w.cand, w.cnt, (uint32_t)MFMA_CAND_CAP, nq,
                                (const float*)w.thr, out_lists);
+    return hipGetLastError();
+}
+
+// The filter with thresholds the caller already knows (a batch of range queries): the queries' bf16 rows, the cleared
+// counters, and ONE launch of the shipped pass-1 kernel over every 32-row block.  No sampling pass, no k_thresholds, no
+// refinement, no top-64 selection: w.thr[q] is final before the first launch.
+hipError_t launch_mfma_range_candidates(hipStream_t s, int metric, const void* slab_frag, const float* row_norm,
+                                        const float* row_sqnorm, const double* q64, uint32_t nq, uint64_t n_rows, uint32_t dim,
+                                        const MfmaScratch& w, uint32_t cand_cap, MfmaLaunchInfo* info)
+{
+    if (nq == 0 || n_rows == 0 || n_rows >= 0xFFFFFFFFull || cand_cap == 0 || cand_cap > (uint32_t)MFMA_CAND_CAP) return hipErrorInvalidValue;
+    if (!mfma_scan_supported(dim, metric) || !mfma_rows_kernel(dim) || nq > w.nq_cap) return hipErrorInvalidValue;
+    const uint32_t ldb = mfma_ldb(dim);
+    __bf16* q16 = reinterpret_cast<__bf16*>(w.q_bf16);
+    const __bf16* slab = reinterpret_cast<const __bf16*>(slab_frag);
+    const uint32_t rq = (uint32_t)rs_qpb(ldb);
+    const uint32_t nq_pad = (nq + rq - 1) / rq * rq;
+    if (nq_pad > w.nq_pad_cap) return hipErrorInvalidValue;
+    const uint32_t chunks = nq_pad / rq;
+    {
+        const size_t total = (size_t)nq_pad * ldb;
+        const int grid = (int)std::min<size_t>((total + 255) / 256, 4096);
+        hipLaunchKernelGGL(k_queries_bf16, dim3(grid), dim3(256), 0, s, q64, nq, nq_pad, dim, ldb, q16);
+        const hipError_t e = hipMemsetAsync(w.cnt, 0, (size_t)nq_pad * sizeof(uint32_t), s);
+        if (e != hipSuccess) return e;
+    }
+    const uint32_t n_blk = (uint32_t)((n_rows + 31) / 32);
+    const uint32_t wg_cap = (uint32_t)env_grid(chunks);  // co-resident workgroups per query chunk
+    const uint32_t gx = std::max<uint32_t>(1u, std::min<uint32_t>((n_blk + RS_NWAVES - 1) / RS_NWAVES, wg_cap));
+    const bool stream = pass1_streams(chunks);
+    bool launched = false;
+#define VL_RRANGE2(K, MET)                                                                                                       \
+    {                                                                                                                            \
+        if (stream)                                                                                                              \
+            hipLaunchKernelGGL((k_mfma_rows<K, 1, MET, 2, RS_NWAVES, true>), dim3(gx, chunks), dim3(RS_NWAVES * 64), 0, s, slab, \
+                               row_norm, row_sqnorm, q16, nq, 0u, n_blk, (uint32_t)n_rows, (int*)nullptr, 0u, 1u, w.thr, w.cand,  \
+                               w.cnt, cand_cap);                                                                                 \
+        else                                                                                                                     \
+            hipLaunchKernelGGL((k_mfma_rows<K, 1, MET>), dim3(gx, chunks), dim3(RS_NWAVES * 64), 0, s, slab, row_norm,           \
+                               row_sqnorm, q16, nq, 0u, n_blk, (uint32_t)n_rows, (int*)nullptr, 0u, 1u, w.thr, w.cand, w.cnt,    \
+                               cand_cap);                                                                                        \
+        launched = true;                                                                                                         \
+    }
+#define VL_RRANGE(K)                                            \
+    if (!launched && ldb == (uint32_t)(K * 16)) {               \
+        if (metric == COSINE) VL_RRANGE2(K, COSINE)             \
+        else if (metric == EUCLIDEAN) VL_RRANGE2(K, EUCLIDEAN)  \
+        else VL_RRANGE2(K, DOT)                                 \
+    }
+    VL_MFMA_KSTEPS(VL_RRANGE)
+#undef VL_RRANGE
+#undef VL_RRANGE2
+    if (!launched) return hipErrorInvalidValue;
+    if (info) {
+        info->ksteps = (int)(ldb / 16);
+        info->metric = metric;
+        info->chunks = (int)chunks;
+        info->grid_x = (int)gx;
+        info->stages = 1;
+        info->sample_blocks = 0;
+    }
     return hipGetLastError();
 }
 

@@ -113,6 +113,15 @@ hipError_t launch_mfma_candidates(hipStream_t s, int metric, const void* slab_bf
                                   const MfmaScratch& w, Cand32* out_lists, MfmaLaunchInfo* info = nullptr,
                                   bool queries_prepared = false);
 
+// A batch of range queries: the same pass-1 kernel with thresholds that are known before the first
+// launch.  w.thr[q] = the smallest key that is not provably below the query's min_score (+inf: no candidates for this
+// query), written by the caller on stream s; one launch over all rows appends every row with key >= thr[q] to
+// w.cand[q * cand_cap ..], w.cnt[q] counts them (above cand_cap <= MFMA_CAND_CAP: the buffer or a ring segment overflowed).
+// The row-stationary kernel only (mfma_rows_kernel(dim)); slab_frag is the fragment-major slab.
+hipError_t launch_mfma_range_candidates(hipStream_t s, int metric, const void* slab_frag, const float* row_norm,
+                                        const float* row_sqnorm, const double* q64, uint32_t nq, uint64_t n_rows, uint32_t dim,
+                                        const MfmaScratch& w, uint32_t cand_cap, MfmaLaunchInfo* info = nullptr);
+
 // Single-query scan of the bf16 slab (the single-query candidate filter): per-workgroup top-64 lists like launch_scan.
 // Two ways to hand over the query, as launch_scan: q32_host != nullptr is the f32 query rounded from the f64 one to
 // nearest even and zero padded to mfma_ldb(dim) floats, copied into the kernel arguments (q64 may then be null);

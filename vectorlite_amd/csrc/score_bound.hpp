@@ -79,10 +79,11 @@ inline float ordered_to_f32(uint32_t o)
 // key <= *tau, *tau = the LARGEST f32 (-inf .. +inf) whose bound is < min_score, found by bisection over the ordered bit
 // patterns (at most 34 evaluations of the bound).  Returns false when there is no such key: every row is a candidate.
 // The device tests !(key <= tau), which keeps a NaN key among the candidates.
+// `in_extra`: the bound's input-rounding term of the filter whose keys are compared (0: the f32 scan).
 template <int METRIC>
-inline bool range_tau(uint32_t n, double R, double Q, double min_score, float* tau)
+inline bool range_tau(uint32_t n, double R, double Q, double min_score, float* tau, double in_extra = 0.0)
 {
-    auto out = [&](uint32_t o) { return bound_for_key<METRIC>(ordered_to_f32(o), n, R, Q, 0.0) < min_score; };
+    auto out = [&](uint32_t o) { return bound_for_key<METRIC>(ordered_to_f32(o), n, R, Q, in_extra) < min_score; };
     uint32_t lo = f32_to_ordered(-INFINITY), hi = f32_to_ordered(INFINITY);
     if (!out(lo)) return false;
     if (out(hi)) {
@@ -98,14 +99,30 @@ inline bool range_tau(uint32_t n, double R, double Q, double min_score, float* t
     return true;
 }
 
-inline bool range_tau(int metric, uint32_t n, double R, double Q, double min_score, float* tau)
+inline bool range_tau(int metric, uint32_t n, double R, double Q, double min_score, float* tau, double in_extra = 0.0)
 {
     switch (metric) {
-    case BOUND_COSINE: return range_tau<BOUND_COSINE>(n, R, Q, min_score, tau);
-    case BOUND_EUCLIDEAN: return range_tau<BOUND_EUCLIDEAN>(n, R, Q, min_score, tau);
-    case BOUND_MANHATTAN: return range_tau<BOUND_MANHATTAN>(n, R, Q, min_score, tau);
-    default: return range_tau<BOUND_DOT>(n, R, Q, min_score, tau);
+    case BOUND_COSINE: return range_tau<BOUND_COSINE>(n, R, Q, min_score, tau, in_extra);
+    case BOUND_EUCLIDEAN: return range_tau<BOUND_EUCLIDEAN>(n, R, Q, min_score, tau, in_extra);
+    case BOUND_MANHATTAN: return range_tau<BOUND_MANHATTAN>(n, R, Q, min_score, tau, in_extra);
+    default: return range_tau<BOUND_DOT>(n, R, Q, min_score, tau, in_extra);
     }
+}
+
+// The same threshold for a filter that keeps `key >= thr` (the MFMA batch filter): *thr = the SMALLEST
+// key that is not provably out = the f32 directly above range_tau's tau, so bound(*thr) >= min_score and
+// bound(prev(*thr)) < min_score.  RANGE_KEYS_ALL: no key is provably out (a -inf threshold; cosine against a zero query)
+// -- every row is a candidate and *thr is not written.  RANGE_KEYS_NONE: every key is provably out (a +inf threshold) --
+// no row can qualify; *thr = +inf, which no finite key reaches.
+enum RangeKeys : int { RANGE_KEYS_ALL = 0, RANGE_KEYS_FROM = 1, RANGE_KEYS_NONE = 2 };
+inline RangeKeys range_key_threshold(int metric, uint32_t n, double R, double Q, double min_score, double in_extra, float* thr)
+{
+    float tau = 0.0f;
+    if (!range_tau(metric, n, R, Q, min_score, &tau, in_extra)) return RANGE_KEYS_ALL;
+    *thr = INFINITY;
+    if (tau == INFINITY) return RANGE_KEYS_NONE;
+    *thr = ordered_to_f32(f32_to_ordered(tau) + 1u);  // tau < +inf: the successor exists
+    return RANGE_KEYS_FROM;
 }
 
 }  // namespace vl
