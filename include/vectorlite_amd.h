@@ -293,6 +293,43 @@ int vl_index_search_mmr(const vl_index *h, uint64_t filter, const double *query,
                         uint64_t fetch_k, double lambda, int metric, uint64_t out_capacity, uint64_t *out_ids,
                         double *out_scores, uint64_t *out_n);
 
+/* NEW capability (the reference only answers in rows): the best k GROUPS, each shown by its best row -- "the best k
+ * documents" over an index of chunks (group_by / collapse / search-groups elsewhere).
+ * A group table maps ids to caller-chosen u64 group keys.  vl_index_groups_create: ids / group_keys [n] in any order; an id
+ * repeated with the same key is fine, an id given two different keys is VL_ERR_INVALID_ARG (checked on the host before any
+ * device is touched); ids the index does not hold are ignored; A ROW WHOSE ID IS NOT IN THE TABLE BELONGS TO NO GROUP AND
+ * TAKES NO PART; duplicate-id rows all get their id's group.  *out_groups is a token of this handle (never 0, never
+ * reused); *out_rows (may be NULL) = rows that have a group now.  Like an id filter the table is resolved on the device,
+ * resolved again on the next use after add / delete, not copied by vl_index_clone and freed by vl_index_destroy.
+ * vl_index_groups_rows: rows that have a group now (resolving again if rows changed) and, *out_distinct (may be NULL), the
+ * distinct group keys of the table.  vl_index_groups_destroy frees the token (a search using it finishes normally).
+ *
+ * vl_index_search_grouped: let S be the FlatIndex holding, in storage order, the rows of h that have a group -- with
+ * filter != 0 (a token of vl_index_filter_create) a row's id must be in the filter too -- and C = FlatIndex::search(query,
+ * len(S), metric) on S (src/index/flat.rs:98-119; score desc, storage position asc).  Walk C from the front, emit a row
+ * iff no earlier row of C has its group key, stop after k emitted rows.  Entry t = (group key, id, score) of the t-th
+ * emitted row, the reference's f64 score bits.  *out_n = min(k, distinct groups in S, out_capacity); the entries are the
+ * prefix of the k-answer (vl_index_search_cap's rule).  For a fixed table the answer for a smaller k is a prefix of the
+ * answer for a larger one.  Only the best row of a group is returned: ask for its other rows with an id filter.
+ * Errors are vl_index_search's on the WHOLE index: the dimension check runs whenever len(h) != 0, an unknown metric is
+ * VL_ERR_INVALID_ARG.  VL_ERR_NAN_SCORE exactly when search(query, len(S), metric) on S would return it (a lone row never
+ * compares).  k > VL_GROUPED_MAX_K, an unknown or destroyed groups token (0 included) or an unknown filter token:
+ * VL_ERR_INVALID_ARG.  k = 0 or an empty S: *out_n = 0, VL_OK.
+ * Single-GPU flat handles only: HNSW and vl_flat_create_multi handles return VL_ERR_INVALID_ARG.  The call never joins a
+ * coalesced pass, reads the f32 slab only, and holds the handle's shared lock throughout (other searches run beside it,
+ * add / delete wait).  vl_last_path: VL_PATH_FAST (two streaming passes: the best key per group, then a range search at the
+ * k-th best group's score, collapsed on the device), or VL_PATH_EXACT_SORT (every score, the device-wide sort, the same
+ * collapse) when k > 64, fewer than k groups have a row, a score is NaN, more rows pass the key-space threshold than the
+ * candidate buffer holds (2^20), data or query lie outside the fast-path domain, or a path is forced. */
+int vl_index_groups_create(vl_index *h, const uint64_t *ids, const uint64_t *group_keys, uint64_t n,
+                           uint64_t *out_groups, uint64_t *out_rows);
+int vl_index_groups_rows(const vl_index *h, uint64_t groups, uint64_t *out_rows, uint64_t *out_distinct);
+int vl_index_groups_destroy(vl_index *h, uint64_t groups);
+#define VL_GROUPED_MAX_K 1024
+int vl_index_search_grouped(const vl_index *h, uint64_t groups, uint64_t filter, const double *query, uint64_t q_len,
+                            uint64_t k, int metric, uint64_t out_capacity, uint64_t *out_group_keys, uint64_t *out_ids,
+                            double *out_scores, uint64_t *out_n);
+
 uint64_t vl_index_len(const vl_index *h);      /* len()       src/index/flat.rs:121-123 */
 int vl_index_is_empty(const vl_index *h);      /* is_empty()  src/index/flat.rs:125-127 */
 uint64_t vl_index_dimension(const vl_index *h);/* dimension() src/index/flat.rs:133-135 */

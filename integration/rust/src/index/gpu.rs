@@ -49,6 +49,10 @@ extern "C" {
     fn vl_index_search_range_batch(h: *const vl_index, filter: u64, queries: *const f64, nq: u64, q_len: u64, min_scores: *const f64, metric: c_int, out_stride: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64, out_total: *mut u64) -> c_int;
     fn vl_index_last_range_batch(h: *const vl_index, mfma_queries: *mut u64, single_queries: *mut u64, exact_queries: *mut u64) -> c_int;
     fn vl_index_last_range_batch_candidates(h: *const vl_index, max_candidates: *mut u64) -> c_int;
+    fn vl_index_groups_create(h: *mut vl_index, ids: *const u64, group_keys: *const u64, n: u64, out_groups: *mut u64, out_rows: *mut u64) -> c_int;
+    fn vl_index_groups_rows(h: *const vl_index, groups: u64, out_rows: *mut u64, out_distinct: *mut u64) -> c_int;
+    fn vl_index_groups_destroy(h: *mut vl_index, groups: u64) -> c_int;
+    fn vl_index_search_grouped(h: *const vl_index, groups: u64, filter: u64, query: *const f64, q_len: u64, k: u64, metric: c_int, out_capacity: u64, out_group_keys: *mut u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_mmr(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, k: u64, fetch_k: u64, lambda: f64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_flat_create_multi(dim: u64, device_ids: *const c_int, n_dev: c_int, mode: c_int, out: *mut *mut vl_index) -> c_int;
     fn vl_index_len(h: *const vl_index) -> u64;
@@ -407,6 +411,45 @@ impl GpuFlatIndex {
                 VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
                 _ => return Err(VectorLiteError::InternalError(last_error())),
             }
+        }
+    }
+
+    /// The best `k` groups, each shown by its best row (no reference counterpart): `pairs` maps ids to caller-chosen group
+    /// keys ("chunk -> document"); rows whose id is not among them take no part.  Entry `t` is the group key and the first
+    /// row of that group in `FlatIndex::search`'s order over the grouped rows.  `k <= 1024`.  Single-GPU handles only.
+    /// ONE-SHOT: every call builds the table (a host sort of the pairs), resolves it on the device (a binary search per
+    /// stored row, one synchronisation) and destroys it again, which at millions of pairs costs far more than the search.
+    /// A caller that asks more than once keeps the token: `vl_index_groups_create` once, `vl_index_search_grouped` per
+    /// query, `vl_index_groups_destroy` at the end (the table follows `add` / `delete` by itself).
+    pub fn search_grouped(&self, pairs: &[(u64, u64)], query: &[f64], k: usize, metric: SimilarityMetric) -> VectorLiteResult<Vec<(u64, SearchResult)>> {
+        let ids: Vec<u64> = pairs.iter().map(|p| p.0).collect();
+        let keys: Vec<u64> = pairs.iter().map(|p| p.1).collect();
+        let (mut token, mut rows) = (0u64, 0u64);
+        let rc = unsafe { vl_index_groups_create(self.0.raw, ids.as_ptr(), keys.as_ptr(), ids.len() as u64, &mut token, &mut rows) };
+        if rc != VL_OK {
+            return Err(VectorLiteError::InternalError(last_error()));
+        }
+        let cap = k.min(rows as usize).max(1);
+        let (mut out_keys, mut out_ids, mut scores, mut n) = (vec![0u64; cap], vec![0u64; cap], vec![0f64; cap], 0u64);
+        let rc = unsafe {
+            vl_index_search_grouped(self.0.raw, token, 0, query.as_ptr(), query.len() as u64, k as u64, metric_code(metric), cap as u64, out_keys.as_mut_ptr(), out_ids.as_mut_ptr(), scores.as_mut_ptr(), &mut n)
+        };
+        let err = if rc == VL_OK { String::new() } else { last_error() };
+        unsafe { vl_index_groups_destroy(self.0.raw, token) };
+        match rc {
+            VL_OK => Ok((0..n as usize)
+                .map(|i| {
+                    let (text, metadata) = self.0.side.get(&out_ids[i]).cloned().unwrap_or_default();
+                    (out_keys[i], SearchResult { id: out_ids[i], score: scores[i], text, metadata })
+                })
+                .collect()),
+            VL_ERR_DIM_MISMATCH => {
+                let (mut e, mut a) = (0u64, 0u64);
+                unsafe { vl_last_dim_mismatch(&mut e, &mut a) };
+                Err(VectorLiteError::DimensionMismatch { expected: e as usize, actual: a as usize })
+            }
+            VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
+            _ => Err(VectorLiteError::InternalError(err)),
         }
     }
 

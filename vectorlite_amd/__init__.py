@@ -27,7 +27,7 @@ from . import _lib
 
 __all__ = [
     "SimilarityMetric", "Vector", "SearchResult", "FlatIndex", "MultiFlatIndex", "HNSWIndex", "VectorLiteError", "DimensionMismatch",
-    "MetricMismatch", "NaNScore", "DeviceError", "IndexOpError", "IdFilter", "hnsw_score", "runtime_info",
+    "MetricMismatch", "NaNScore", "DeviceError", "IndexOpError", "IdFilter", "GroupTable", "hnsw_score", "runtime_info",
     "PATH_FAST", "PATH_EXACT_SELECT", "PATH_EXACT_SORT",
 ]
 
@@ -35,6 +35,7 @@ VL_OK, VL_ERR_DIM_MISMATCH, VL_ERR_DUP_ID, VL_ERR_NOT_FOUND, VL_ERR_METRIC_MISMA
 VL_ERR_NAN_SCORE, VL_ERR_DEVICE, VL_ERR_OOM, VL_ERR_INVALID_ARG = 5, 6, 7, 8
 PATH_NONE, PATH_FAST, PATH_EXACT_SELECT, PATH_EXACT_SORT = 0, 1, 2, 3
 VL_MMR_MAX_FETCH = 1024  # most candidates a diversified search ranks (vl_index_search_mmr)
+VL_GROUPED_MAX_K = 1024  # most groups a grouped search returns (vl_index_search_grouped)
 # set_single_filter: the modes of vl_index_set_single_filter (2 = auto, what new handles start in)
 SINGLE_FILTER_MODES = {"f32": 0, "bf16": 1, "auto": 2}
 # ... and mode 3, the int8 copy first always (kept out of SINGLE_FILTER_MODES, whose three entries callers enumerate)
@@ -232,6 +233,90 @@ def _make_filter(L, h, owner, ids) -> IdFilter:
         raise IndexOpError(_last_error())
     _raise(rc)
     return IdFilter(owner, int(tok.value))
+
+
+class GroupTable:
+    """A map id -> group key of one FlatIndex (vl_index_groups_create): `search_grouped` returns the best row of each of
+    the best k groups; rows whose id the table does not hold take no part.  It follows the index like an IdFilter: after
+    add / delete the next use resolves it against the current rows.  `rows()` = rows that have a group now, `distinct()` =
+    distinct group keys of the table; `close()` (or leaving a `with` block) frees it."""
+
+    def __init__(self, index: "FlatIndex", token: int):
+        self._index = index
+        self._token = token
+
+    @property
+    def token(self) -> int:
+        return self._token
+
+    def _counts(self) -> Tuple[int, int]:
+        if not self._token:
+            raise IndexOpError("group table is closed")
+        rows, distinct = C.c_uint64(0), C.c_uint64(0)
+        rc = self._index._L.vl_index_groups_rows(self._index._h, self._token, C.byref(rows), C.byref(distinct))
+        if rc == VL_ERR_INVALID_ARG:
+            raise IndexOpError(_last_error())
+        _raise(rc)
+        return int(rows.value), int(distinct.value)
+
+    def rows(self) -> int:
+        return self._counts()[0]
+
+    def distinct(self) -> int:
+        return self._counts()[1]
+
+    def close(self) -> None:
+        tok, self._token = self._token, 0
+        h = getattr(self._index, "_h", None)
+        if tok and h:
+            self._index._L.vl_index_groups_destroy(h, tok)
+
+    def __enter__(self) -> "GroupTable":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _u64_array(values) -> np.ndarray:
+    return np.ascontiguousarray(np.fromiter((int(i) for i in values), dtype=np.uint64)
+                                if not isinstance(values, np.ndarray) else values.astype(np.uint64, copy=False))
+
+
+def _make_groups(L, h, owner, ids, keys) -> GroupTable:
+    ids, keys = _u64_array(ids), _u64_array(keys)
+    if ids.size != keys.size:
+        raise ValueError("ids and keys must have the same length")
+    tok, rows = C.c_uint64(0), C.c_uint64(0)
+    rc = L.vl_index_groups_create(h, _pu64(ids), _pu64(keys), ids.size, C.byref(tok), C.byref(rows))
+    if rc == VL_ERR_INVALID_ARG:
+        raise IndexOpError(_last_error())
+    _raise(rc)
+    return GroupTable(owner, int(tok.value))
+
+
+def _search_grouped(L, h, query, k: int, metric: int, groups_token: int, filter_token: int):
+    """vl_index_search_grouped -> (group_keys, ids, scores), best group first."""
+    q = _f64(query).ravel()
+    k = min(max(int(k), 0), 1 << 62)
+    cap = max(min(k, VL_GROUPED_MAX_K), 1)
+    keys = np.empty(cap, dtype=np.uint64)
+    ids = np.empty(cap, dtype=np.uint64)
+    scores = np.empty(cap, dtype=np.float64)
+    n = C.c_uint64(0)
+    rc = L.vl_index_search_grouped(h, int(groups_token), int(filter_token), q.ctypes.data, q.size, k, int(metric), cap,
+                                   keys.ctypes.data, ids.ctypes.data, scores.ctypes.data, C.byref(n))
+    if rc == VL_ERR_INVALID_ARG:
+        raise IndexOpError(_last_error())
+    _raise(rc)
+    m = int(n.value)
+    return keys[:m].copy(), ids[:m].copy(), scores[:m].copy()
 
 
 def _search_range(L, h, query, min_score: float, metric: int, token: int, limit):
@@ -513,6 +598,38 @@ class FlatIndex:
         _raise(self._L.vl_index_last_range_batch_candidates(self._h, C.byref(d)))
         return {"mfma_queries": int(a.value), "single_queries": int(b.value), "exact_queries": int(c.value),
                 "max_candidates": int(d.value)}
+
+    # ---- grouped search (best row per group) --------------------------------------------------
+    def make_groups(self, ids, keys) -> GroupTable:
+        """A GroupTable mapping ids[i] -> keys[i] (u64 group keys; any order; an id repeated with the same key is fine, with
+        two different keys it is an IndexOpError; ids the index does not hold are ignored)."""
+        return _make_groups(self._L, self._h, self, ids, keys)
+
+    def search_grouped_arrays(self, query, k: int, metric: int = 0, groups=None, filter=None):
+        """(group_keys, ids, scores): the best row of each of the best k groups of `groups` (a GroupTable of this index), in
+        FlatIndex::search's order (among the filter's rows when `filter` is given: an IdFilter or an iterable of ids).
+        Rows whose id the table does not hold take no part."""
+        if not isinstance(groups, GroupTable):
+            raise ValueError("groups must be a GroupTable of this index (make_groups)")
+        if groups._index is not self:
+            raise ValueError("the group table belongs to another index")
+        if filter is None:
+            return _search_grouped(self._L, self._h, query, k, metric, groups.token, 0)
+        tok, temp = self._filter_token(filter)
+        try:
+            return _search_grouped(self._L, self._h, query, k, metric, groups.token, tok)
+        finally:
+            if temp is not None:
+                temp.close()
+
+    def search_grouped(self, query, k: int, similarity_metric: int = SimilarityMetric.Cosine, groups=None,
+                       filter=None) -> List[Tuple[int, SearchResult]]:
+        keys, ids, scores = self.search_grouped_arrays(query, k, similarity_metric, groups=groups, filter=filter)
+        out = []
+        for g, i, s in zip(keys.tolist(), ids.tolist(), scores.tolist()):
+            text, md = self._meta.get(i, ("", None))
+            out.append((g, SearchResult(id=i, score=s, text=text, metadata=md)))
+        return out
 
     # ---- diversified (MMR) search ------------------------------------------------------------
     def search_mmr_arrays(self, query, k: int, fetch_k: int = 20, lambda_mult: float = 0.5, metric: int = 0, filter=None):
@@ -1008,6 +1125,17 @@ class HNSWIndex:
     def search_mmr(self, query, k: int, fetch_k: int = 20, lambda_mult: float = 0.5,
                    similarity_metric: int = SimilarityMetric.Cosine, filter=None):
         return self.search_mmr_arrays(query, k, fetch_k, lambda_mult, similarity_metric, filter)
+
+    def make_groups(self, ids, keys) -> GroupTable:
+        """Grouped search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""
+        return _make_groups(self._L, self._h, self, ids, keys)
+
+    def search_grouped_arrays(self, query, k: int, metric: int = 0, groups=None, filter=None):
+        """Grouped search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""
+        self.make_groups([], [])  # raises: no grouped HNSW walk
+
+    def search_grouped(self, query, k: int, similarity_metric: int = SimilarityMetric.Cosine, groups=None, filter=None):
+        return self.search_grouped_arrays(query, k, similarity_metric, groups, filter)
 
     def search_arrays(self, query, k: int, metric: int, ef: int = 0, filter=None):
         if filter is not None:

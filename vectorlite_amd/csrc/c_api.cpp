@@ -429,6 +429,81 @@ int vl_index_search_mmr(const vl_index* h, uint64_t filter, const double* query,
     });
 }
 
+static_assert(VL_GROUPED_MAX_K == vl::GROUPED_MAX_K, "the header states the kernels' limit");
+
+int vl_index_groups_create(vl_index* h, const uint64_t* ids, const uint64_t* group_keys, uint64_t n, uint64_t* out_groups,
+                           uint64_t* out_rows)
+{
+    return guarded([&]() -> int {
+        if (out_groups) *out_groups = 0;
+        if (!out_groups || ((!ids || !group_keys) && n)) return VL_ERR_INVALID_ARG;
+        // the pairs are checked on the host before the handle is looked at: no device is needed
+        vl::GroupPlan plan;
+        uint64_t bad = 0;
+        if (!vl::group_plan_build(ids, group_keys, n, &plan, &bad)) {
+            vl::set_last_error(n >= (uint64_t)vl::GROUP_NONE
+                                   ? "a group table holds fewer than 2^32 - 1 pairs"
+                                   : "group table: id " + std::to_string(bad) + " is given two different group keys");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (!h) return VL_ERR_INVALID_ARG;
+        if (!h->flat) {
+            vl::set_last_error("grouped search is served by single-GPU flat indexes");
+            return VL_ERR_INVALID_ARG;
+        }
+        return h->flat->groups_create(std::move(plan), out_groups, out_rows);
+    });
+}
+
+int vl_index_groups_rows(const vl_index* h, uint64_t groups, uint64_t* out_rows, uint64_t* out_distinct)
+{
+    return guarded([&]() -> int {
+        if (!h || !out_rows) return VL_ERR_INVALID_ARG;
+        if (!h->flat) {
+            vl::set_last_error("grouped search is served by single-GPU flat indexes");
+            return VL_ERR_INVALID_ARG;
+        }
+        return h->flat->groups_rows(groups, out_rows, out_distinct);
+    });
+}
+
+int vl_index_groups_destroy(vl_index* h, uint64_t groups)
+{
+    return guarded([&]() -> int {
+        if (!h) return VL_ERR_INVALID_ARG;
+        if (!h->flat) {
+            vl::set_last_error("grouped search is served by single-GPU flat indexes");
+            return VL_ERR_INVALID_ARG;
+        }
+        return h->flat->groups_destroy(groups);
+    });
+}
+
+int vl_index_search_grouped(const vl_index* h, uint64_t groups, uint64_t filter, const double* query, uint64_t q_len, uint64_t k,
+                            int metric, uint64_t out_capacity, uint64_t* out_group_keys, uint64_t* out_ids, double* out_scores,
+                            uint64_t* out_n)
+{
+    return guarded([&]() -> int {
+        if (out_n) *out_n = 0;
+        if (k > VL_GROUPED_MAX_K) {  // before the handle is looked at: no device is needed
+            vl::set_last_error("grouped search: k exceeds VL_GROUPED_MAX_K (1024)");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (groups == 0) {
+            vl::set_last_error("unknown or destroyed group table");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (!h || !out_n) return VL_ERR_INVALID_ARG;
+        if (!h->flat) {
+            vl::set_last_error("grouped search is served by single-GPU flat indexes");
+            return VL_ERR_INVALID_ARG;
+        }
+        if ((!out_group_keys || !out_ids || !out_scores) && k != 0 && out_capacity != 0) return VL_ERR_INVALID_ARG;
+        return h->flat->search_grouped(groups, filter, query, q_len, k, metric, out_capacity, out_group_keys, nullptr, out_ids,
+                                       out_scores, out_n);
+    });
+}
+
 int vl_index_search_batch_filtered(const vl_index* h, uint64_t filter, const double* queries, uint64_t nq, uint64_t q_len,
                                    uint64_t k, int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores,
                                    uint64_t* out_n)

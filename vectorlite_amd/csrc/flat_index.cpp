@@ -12,6 +12,7 @@
 #include <chrono>
 
 #include <algorithm>
+#include <limits>
 #include <map>
 #include <type_traits>
 #include <cmath>
@@ -105,11 +106,11 @@ Workspace::~Workspace()
     if (stream) (void)hipStreamSynchronize(stream);
     void* dev[] = {d_q64, d_partials, d_partials64, d_result, d_nan, d_scores, d_okeys,
                    d_opos, d_out_pos, d_out_scores, d_positions, d_dists, rg_ctr, rg_cand, rg_scores, rg_keys, rg_pv, mmr_sim,
-                   rb_ctr, rb_min, rb_sv_score, rb_sv_pos};
+                   rb_ctr, rb_min, rb_sv_score, rb_sv_pos, gp_best, gp_first, gp_lists, gp_cand, gp_scores, gp_ctr, gp_out_keys};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     void* host[] = {h_q64, h_result, h_nan, mf_h_q64, mf_h_result, mf_h_dom, k3_h_q64, k3_h_result, rg_h_ctr, rg_h_pos, rg_h_scores,
-                    rb_h_thr, rb_h_min, rb_h_ctr, rb_h_cnt, rb_h_pos, rb_h_scores};
+                    rb_h_thr, rb_h_min, rb_h_ctr, rb_h_cnt, rb_h_pos, rb_h_scores, gp_h_ctr, gp_h_scores, gp_h_keys};
     for (void* p : host)
         if (p) (void)hipHostFree(p);
     void* mfd[] = {mf.q_bf16, mf.gmax, mf.thr, mf.cand, mf.cnt, mf_d_q64, mf_lists, mf_scores, k3_d_q64};
@@ -2080,6 +2081,414 @@ int GpuFlatIndex::search_range_locked(Workspace* ws, IdFilter* f, const double* 
     }
     set_last_path(PATH_EXACT_SORT);
     return deliver(pos.data(), scores.data(), want, total);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Grouped search (NEW): the best row of each of the best k groups.
+//
+// Pass 1 (k_scan_group_best) leaves the best f32 key of every group in best[]; the 64 largest are decoded and the first k
+// rescored in the reference's order.  L = the smallest of those k scores: k distinct groups each hold a row scoring >= L,
+// so the k-th group of the answer scores >= L, every row of the answer scores >= L, and in the ranking every row scoring
+// >= L stands in front of every row scoring less -- the first k distinct groups of the ranking are decided inside the rows
+// with score >= L.  Pass 2 is a range search at min_score = L (threshold ties in), its ranked survivors are collapsed on
+// the device.  Nothing is certified; the exact route (every score, the sort, the same collapse) is taken for k > 64, fewer
+// than k non-empty groups, a NaN, a candidate overflow, or data / query outside the fast-path domain.
+// ---------------------------------------------------------------------------------------------
+GroupTable::~GroupTable()
+{
+    (void)hipSetDevice(rows.device);
+    void* dev[] = {d_dense, d_keys, d_group_of_row};
+    for (void* p : dev)
+        if (p) (void)hipFree(p);
+}
+
+std::shared_ptr<GroupTable> GpuFlatIndex::find_groups(uint64_t token) const
+{
+    std::lock_guard<std::mutex> g(filters_mu_);
+    auto it = groups_.find(token);
+    return it == groups_.end() ? nullptr : it->second;
+}
+
+int GpuFlatIndex::groups_create(GroupPlan&& plan, uint64_t* out_token, uint64_t* out_rows)
+{
+    if (!out_token || plan.ids.size() != plan.dense.size()) return ERR_INVALID_ARG;
+    *out_token = 0;
+    auto t = std::make_shared<GroupTable>();
+    t->rows.device = device_;
+    t->rows.ids = std::move(plan.ids);
+    t->keys = std::move(plan.keys);
+    VL_HIP(hipSetDevice(device_));
+    const size_t ni = t->rows.ids.size();
+    if (ni) {
+        VL_TRY(dev_alloc(&t->rows.d_ids, ni));
+        VL_HIP(hipMemcpy(t->rows.d_ids, t->rows.ids.data(), ni * sizeof(uint64_t), hipMemcpyHostToDevice));
+        VL_TRY(dev_alloc(&t->rows.d_counts, (size_t)FILTER_COUNTS_MAX + 1));
+        VL_TRY(dev_alloc(&t->d_dense, ni));
+        VL_HIP(hipMemcpy(t->d_dense, plan.dense.data(), ni * sizeof(uint32_t), hipMemcpyHostToDevice));
+        VL_TRY(dev_alloc(&t->d_keys, t->keys.size()));
+        VL_HIP(hipMemcpy(t->d_keys, t->keys.data(), t->keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    uint64_t rows = 0;
+    {
+        std::shared_lock<RwLock> lk(mu_);
+        std::lock_guard<std::mutex> tg(t->rows.mu);
+        Workspace* ws = acquire_ws();
+        if (!ws) return ERR_DEVICE;
+        const int rc = resolve_groups(ws, t.get());
+        if (rc != OK) (void)hipStreamSynchronize(ws->stream);
+        release_ws(ws);
+        if (rc != OK) return rc;
+        rows = t->rows.m;
+    }
+    const uint64_t token = g_next_filter_token.fetch_add(1);
+    {
+        std::lock_guard<std::mutex> g(filters_mu_);
+        groups_[token] = std::move(t);
+    }
+    *out_token = token;
+    if (out_rows) *out_rows = rows;
+    return OK;
+}
+
+int GpuFlatIndex::groups_destroy(uint64_t groups)
+{
+    std::shared_ptr<GroupTable> t;  // a search still using it holds its own reference: freed when that one ends
+    {
+        std::lock_guard<std::mutex> g(filters_mu_);
+        auto it = groups_.find(groups);
+        if (it == groups_.end()) {
+            set_last_error("unknown or destroyed group table");
+            return ERR_INVALID_ARG;
+        }
+        t = std::move(it->second);
+        groups_.erase(it);
+    }
+    return OK;
+}
+
+int GpuFlatIndex::groups_rows(uint64_t groups, uint64_t* out_rows, uint64_t* out_distinct) const
+{
+    if (!out_rows) return ERR_INVALID_ARG;
+    std::shared_ptr<GroupTable> t = find_groups(groups);
+    if (!t) {
+        set_last_error("unknown or destroyed group table");
+        return ERR_INVALID_ARG;
+    }
+    std::shared_lock<RwLock> lk(mu_);
+    std::lock_guard<std::mutex> tg(t->rows.mu);
+    if (t->rows.resolved_at != mutations_) {
+        VL_HIP(hipSetDevice(device_));
+        Workspace* ws = acquire_ws();
+        if (!ws) return ERR_DEVICE;
+        const int rc = resolve_groups(ws, t.get());
+        if (rc != OK) (void)hipStreamSynchronize(ws->stream);
+        release_ws(ws);
+        if (rc != OK) return rc;
+    }
+    *out_rows = t->rows.m;
+    if (out_distinct) *out_distinct = t->keys.size();
+    return OK;
+}
+
+// The filter's resolution over the table's ids (the ascending positions of the rows that have a group), then
+// group_of_row[p] for every position.
+int GpuFlatIndex::resolve_groups(Workspace* ws, GroupTable* t) const
+{
+    const uint64_t n = ids_.size();
+    VL_TRY(resolve_filter(ws, &t->rows));
+    t->rows.resolved_at = ~0ull;
+    if (n != 0 && !t->rows.ids.empty()) {
+        if (t->gor_cap < n) {
+            if (t->d_group_of_row) (void)hipFree(t->d_group_of_row);
+            t->d_group_of_row = nullptr;
+            t->gor_cap = 0;
+            VL_TRY(dev_alloc(&t->d_group_of_row, (size_t)n));
+            t->gor_cap = n;
+        }
+        VL_HIP(launch_group_rows(ws->stream, d_ids_, n, t->rows.d_ids, t->d_dense, t->rows.ids.size(), t->d_group_of_row));
+        VL_HIP(hipStreamSynchronize(ws->stream));
+    }
+    t->rows.resolved_at = mutations_;
+    return OK;
+}
+
+int GpuFlatIndex::ensure_group_ws(Workspace* ws, uint64_t n_groups) const
+{
+    if (!ws->gp_ctr) {
+        VL_TRY(dev_alloc(&ws->gp_lists, (size_t)GROUP_TOP_LISTS * KP));
+        VL_TRY(dev_alloc(&ws->gp_cand, (size_t)KP));
+        VL_TRY(dev_alloc(&ws->gp_scores, (size_t)KP));
+        VL_TRY(dev_alloc(&ws->gp_out_keys, (size_t)GROUPED_MAX_K));
+        VL_TRY(pinned_alloc(&ws->gp_h_ctr, (size_t)RANGE_CTR_WORDS + 1));
+        VL_TRY(pinned_alloc(&ws->gp_h_scores, (size_t)KP));
+        VL_TRY(pinned_alloc(&ws->gp_h_keys, (size_t)GROUPED_MAX_K));
+        VL_TRY(dev_alloc(&ws->gp_ctr, (size_t)RANGE_CTR_WORDS + 1));
+    }
+    if (ws->gp_cap < n_groups) {
+        if (ws->gp_best) (void)hipFree(ws->gp_best);
+        if (ws->gp_first) (void)hipFree(ws->gp_first);
+        ws->gp_best = nullptr;
+        ws->gp_first = nullptr;
+        ws->gp_cap = 0;
+        VL_TRY(dev_alloc(&ws->gp_best, (size_t)n_groups));
+        VL_TRY(dev_alloc(&ws->gp_first, (size_t)n_groups));
+        ws->gp_cap = n_groups;
+    }
+    return OK;
+}
+
+int GpuFlatIndex::search_grouped(uint64_t groups, uint64_t token, const double* query, uint64_t q_len, uint64_t k, int metric,
+                                 uint64_t out_capacity, uint64_t* out_group_keys, uint64_t* out_pos, uint64_t* out_ids,
+                                 double* out_scores, uint64_t* out_n) const
+{
+    if (!out_n) return ERR_INVALID_ARG;
+    *out_n = 0;
+    set_last_path(PATH_NONE);  // an answer that needs no scan (k = 0, an empty index, an empty S) took no route
+    if (k > GROUPED_MAX_K) {
+        set_last_error("grouped search: k exceeds VL_GROUPED_MAX_K (1024)");
+        return ERR_INVALID_ARG;
+    }
+    std::shared_ptr<GroupTable> t = find_groups(groups);
+    if (!t) {
+        set_last_error("unknown or destroyed group table");
+        return ERR_INVALID_ARG;
+    }
+    std::shared_ptr<IdFilter> f;
+    if (token != 0) {
+        f = find_filter(token);
+        if (!f) {
+            set_last_error("unknown or destroyed filter");
+            return ERR_INVALID_ARG;
+        }
+    }
+    if (metric < 0 || metric > 3) {
+        set_last_error("unknown metric");
+        return ERR_INVALID_ARG;
+    }
+    std::shared_lock<RwLock> lk(mu_);  // readers share it; add / delete wait: the resolved tables cannot move under the search
+    const uint64_t n = ids_.size();
+    if (n != 0 && q_len != dim_) {  // the whole index's check, as in search
+        set_dim_mismatch(dim_, q_len);
+        set_last_error("Dimension mismatch: expected " + std::to_string(dim_) + ", got " + std::to_string(q_len));
+        return ERR_DIM_MISMATCH;
+    }
+    if (n == 0 || k == 0) return OK;
+    if ((!query && dim_) || (out_capacity != 0 && (!out_scores || !out_group_keys))) return ERR_INVALID_ARG;
+
+    VL_HIP(hipSetDevice(device_));
+    Workspace* ws = acquire_ws();
+    if (!ws) return ERR_DEVICE;
+    int rc = OK;
+    {
+        std::lock_guard<std::mutex> tg(t->rows.mu);
+        if (t->rows.resolved_at != mutations_) rc = resolve_groups(ws, t.get());
+    }
+    if (rc == OK && f) {
+        std::lock_guard<std::mutex> fg(f->mu);
+        if (f->resolved_at != mutations_) rc = resolve_filter(ws, f.get());
+    }
+    // from here on both resolutions are read only: a reader that finds them current leaves them alone, writers are shut out
+    if (rc == OK && t->rows.m != 0 && (!f || f->m != 0)) {
+        active_searches_.fetch_add(1, std::memory_order_relaxed);
+        rc = search_grouped_locked(ws, t.get(), f.get(), query, k, metric, out_capacity, out_group_keys, out_pos, out_ids, out_scores,
+                                   out_n);
+        active_searches_.fetch_sub(1, std::memory_order_relaxed);
+    }
+    if (rc != OK) (void)hipStreamSynchronize(ws->stream);
+    release_ws(ws);
+    return rc;
+}
+
+int GpuFlatIndex::search_grouped_locked(Workspace* ws, const GroupTable* t, const IdFilter* f, const double* query, uint64_t k,
+                                        int metric, uint64_t out_capacity, uint64_t* out_group_keys, uint64_t* out_pos,
+                                        uint64_t* out_ids, double* out_scores, uint64_t* out_n) const
+{
+    const uint64_t n = ids_.size();
+    // the rows scanned: the filter's list (rows without a group are dropped at the sinks and at the cut), else the table's
+    // own list of grouped rows -- or every row when all of them have a group
+    const uint32_t* plist = f ? f->d_plist : (t->rows.m == n ? nullptr : t->rows.d_plist);
+    const uint64_t m = f ? f->m : t->rows.m;
+    const uint32_t* gor = t->d_group_of_row;
+    const uint64_t ng = t->keys.size();
+    const uint32_t k32 = (uint32_t)k;
+    hipStream_t st = ws->stream;
+
+    // the query staged as search_range_locked stages it: pinned f64 values, then the norm
+    double qq = 0.0, qmax = 0.0;
+    bool q_finite = true;
+    for (uint64_t i = 0; i < dim_; ++i) {
+        const double v = query[i];
+        ws->h_q64[i] = v;
+        qq += v * v;
+        const double av = std::fabs(v);
+        if (!(av <= 1.797693134862315708e308)) q_finite = false;
+        if (av > qmax) qmax = av;
+    }
+    const double q_norm = std::sqrt(qq);
+    const bool q_in_domain = q_finite && qmax <= DOMAIN_MAX_ABS && (q_norm == 0.0 || q_norm >= DOMAIN_MIN_NORM);
+    ws->h_q64[dim_] = q_norm;
+    VL_HIP(hipMemcpyAsync(ws->d_q64, ws->h_q64, (dim_ + 1) * sizeof(double), hipMemcpyHostToDevice, st));
+
+    VL_TRY(ensure_group_ws(ws, ng));
+    VL_TRY(ensure_range_ws(ws, 0, GROUPED_MAX_K));
+
+    // the collapse of `total` ranked survivors (total_ptr: the count is still the device's) and its copy back
+    auto collapse = [&](const double* scores, const uint32_t* total_ptr, uint64_t total) -> int {
+        VL_HIP(launch_group_collapse(st, ws->rg_pv, scores, total_ptr, total, gor, n, reinterpret_cast<const uint64_t*>(t->d_keys), ng,
+                                     ws->gp_first, k32, ws->gp_out_keys, ws->d_out_pos, ws->d_out_scores,
+                                     ws->gp_ctr + RANGE_CTR_WORDS));
+        VL_HIP(hipMemcpyAsync(ws->gp_h_ctr + RANGE_CTR_WORDS, ws->gp_ctr + RANGE_CTR_WORDS, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipMemcpyAsync(ws->gp_h_keys, ws->gp_out_keys, k * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipMemcpyAsync(ws->rg_h_pos, ws->d_out_pos, k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipMemcpyAsync(ws->rg_h_scores, ws->d_out_scores, k * sizeof(double), hipMemcpyDeviceToHost, st));
+        return OK;
+    };
+    // writes the answer from the pinned copies of the collapse's output
+    auto deliver = [&](uint64_t emitted) -> int {
+        const uint64_t want = std::min<uint64_t>(emitted, out_capacity);
+        for (uint64_t i = 0; i < want; ++i) {
+            const uint32_t p = ws->rg_h_pos[i];
+            if (p >= n) {
+                set_last_error("grouped search returned an out-of-range position (kernel bug)");
+                return ERR_DEVICE;
+            }
+            out_group_keys[i] = ws->gp_h_keys[i];
+            if (out_pos) out_pos[i] = p;
+            if (out_ids) out_ids[i] = ids_[p];
+            out_scores[i] = ws->rg_h_scores[i];
+        }
+        *out_n = want;
+        return OK;
+    };
+
+    const uint32_t cap = range_candidate_capacity();
+    const bool fast_ok = force_path_.load() == 0 && n_out_of_domain_ == 0 && q_in_domain && k <= (uint64_t)KP;
+    while (fast_ok) {  // (one round: `break` leaves for the exact route)
+        VL_TRY(ensure_range_ws(ws, RANGE_CAND_MAX, GROUPED_MAX_K));
+        if (!ws->rg_cand) {
+            VL_TRY(dev_alloc(&ws->rg_cand, (size_t)RANGE_CAND_MAX));
+            VL_TRY(dev_alloc(&ws->rg_scores, (size_t)RANGE_CAND_MAX));
+        }
+        const bool qarg = scan_range_takes_qarg(ld_);
+        const float* q32 = nullptr;
+        if (qarg) {
+            if (ws->q32.size() < ld_) ws->q32.assign(ld_, 0.0f);
+            for (uint64_t i = 0; i < dim_; ++i) ws->q32[i] = (float)query[i];  // nearest even, like load_q4 on the device
+            q32 = ws->q32.data();
+        }
+        // pass 1: the best key of every group, the 64 best groups, the reference scores of the first k of them
+        const bool prof = profile_.load();
+        ScanPlan plan;
+        VL_HIP(hipMemsetAsync(ws->gp_best, 0, ng * sizeof(uint64_t), st));
+        VL_HIP(hipMemsetAsync(ws->gp_ctr, 0, (RANGE_CTR_WORDS + 1) * sizeof(uint32_t), st));
+        if (prof) VL_HIP(hipEventRecord(ws->ev0, st));
+        VL_HIP(launch_scan_group_best(st, metric, d_slab_, d_inv_norm_, plist, m, ws->d_q64, (uint32_t)dim_, ld_, gor, ws->gp_best,
+                                      &plan, q32));
+        if (prof) VL_HIP(hipEventRecord(ws->ev1, st));
+        VL_HIP(launch_group_top(st, ws->gp_best, ng, k32, ws->gp_lists, ws->gp_cand, ws->gp_ctr));
+        VL_HIP(launch_range_rescore(st, metric, d_master_, ws->d_q64, ws->gp_cand, (uint32_t)KP, (uint32_t)dim_, ws->gp_scores,
+                                    ws->gp_ctr));
+        VL_HIP(hipMemcpyAsync(ws->gp_h_ctr, ws->gp_ctr, RANGE_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipMemcpyAsync(ws->gp_h_scores, ws->gp_scores, k * sizeof(double), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipStreamSynchronize(st));
+        last_scan_variant_.store(plan.variant, std::memory_order_relaxed);
+        last_scan_grid_.store(plan.grid, std::memory_order_relaxed);
+        last_scan_qarg_.store(qarg ? 1 : 0, std::memory_order_relaxed);
+        if (prof) {
+            float ms = 0.f;
+            VL_HIP(hipEventElapsedTime(&ms, ws->ev0, ws->ev1));
+            std::lock_guard<std::mutex> g(prof_mu_);
+            prof_n_ += 1;
+            prof_ms_ += ms;
+            prof_bytes_ += m * ((uint64_t)ld_ * sizeof(float) + sizeof(uint32_t) + (plist ? sizeof(uint32_t) : 0) +
+                                (metric == COSINE ? sizeof(float) : 0));
+        }
+        if (ws->gp_h_ctr[RANGE_CTR_APPENDED] < k || ws->gp_h_ctr[RANGE_CTR_NAN] != 0) break;  // fewer than k non-empty groups; a NaN
+        double L = ws->gp_h_scores[0];
+        bool nan = false;
+        for (uint64_t i = 0; i < k; ++i) {
+            const double sc = ws->gp_h_scores[i];
+            if (sc != sc) nan = true;
+            if (sc < L) L = sc;
+        }
+        if (nan) break;
+
+        // pass 2: the range search at min_score = L, rows without a group dropped at the cut, and the collapse
+        float tau = 0.0f;
+        if (!range_tau(metric, ld_, max_row_norm_, q_norm, L, &tau)) tau = std::nanf("");
+        VL_HIP(hipMemsetAsync(ws->rg_ctr, 0, RANGE_CTR_WORDS * sizeof(uint32_t), st));
+        VL_HIP(launch_scan_range(st, metric, d_slab_, d_inv_norm_, plist, m, ws->d_q64, (uint32_t)dim_, ld_, tau, ws->rg_cand, cap,
+                                 ws->rg_ctr, nullptr, q32));
+        VL_HIP(launch_range_rescore(st, metric, d_master_, ws->d_q64, ws->rg_cand, cap, (uint32_t)dim_, ws->rg_scores, ws->rg_ctr));
+        VL_HIP(launch_range_cut(st, ws->rg_scores, ws->rg_cand, ws->rg_ctr + RANGE_CTR_APPENDED, cap, L, ws->rg_keys, ws->rg_pv, cap,
+                                ws->rg_ctr, gor, n, false));
+        // up to RANGE_SMALL survivors are ranked and collapsed before the host knows their number: one round trip
+        VL_HIP(launch_range_rank(st, ws->rg_keys, ws->rg_pv, ws->rg_scores, ws->rg_ctr + RANGE_CTR_TOTAL, 0, 0, nullptr, nullptr));
+        VL_TRY(collapse(ws->rg_scores, ws->rg_ctr + RANGE_CTR_TOTAL, RANGE_SMALL));
+        VL_HIP(hipMemcpyAsync(ws->rg_h_ctr, ws->rg_ctr, RANGE_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipStreamSynchronize(st));
+        const uint64_t appended = ws->rg_h_ctr[RANGE_CTR_APPENDED], total = ws->rg_h_ctr[RANGE_CTR_TOTAL];
+        if (appended > cap || ws->rg_h_ctr[RANGE_CTR_NAN] != 0) break;  // more candidates than the buffer holds; a NaN
+        if (appended > m || total > appended) {
+            set_last_error("range scan counted more rows than it was given (kernel bug)");
+            return ERR_DEVICE;
+        }
+        if (total > RANGE_SMALL) {
+            VL_HIP(launch_range_rank(st, ws->rg_keys, ws->rg_pv, ws->rg_scores, nullptr, total, 0, nullptr, nullptr));
+            VL_TRY(collapse(ws->rg_scores, nullptr, total));
+            VL_HIP(hipStreamSynchronize(st));
+        }
+        // the k rows behind L are among the survivors, so k groups are; should that ever fail, the exact route answers and
+        // vl_last_path shows it
+        if (ws->gp_h_ctr[RANGE_CTR_WORDS] != k) break;
+        set_last_path(PATH_FAST);
+        return deliver(k);
+    }
+
+    // the exact route: the reference score of every row, the grouped rows ranked by the device-wide sort, the collapse
+    if (ws->scores_cap < m) {
+        if (ws->d_scores) (void)hipFree(ws->d_scores);
+        ws->d_scores = nullptr;
+        ws->scores_cap = 0;
+        const size_t c = std::max<size_t>(m, 1024);
+        VL_TRY(dev_alloc(&ws->d_scores, c));
+        ws->scores_cap = c;
+    }
+    const double neg_inf = -std::numeric_limits<double>::infinity();
+    VL_HIP(hipMemsetAsync(ws->rg_ctr, 0, RANGE_CTR_WORDS * sizeof(uint32_t), st));
+    if (plist)
+        VL_HIP(launch_exact_scan_subset(st, metric, d_master_, ws->d_q64, plist, m, (uint32_t)dim_, ws->d_scores,
+                                        ws->rg_ctr + RANGE_CTR_NAN));
+    else
+        VL_HIP(launch_exact_scan(st, metric, d_master_, ws->d_q64, m, (uint32_t)dim_, ws->d_scores, ws->rg_ctr + RANGE_CTR_NAN));
+    // count only: TOTAL = |S| (NaN scores of grouped rows stay in), GROUP_NAN = how many of them are NaN.  The scan's own
+    // flag also covers filtered rows without a group, which are not rows of S.
+    VL_HIP(launch_range_cut(st, ws->d_scores, plist, nullptr, m, neg_inf, nullptr, nullptr, 0, ws->rg_ctr, gor, n, true));
+    VL_HIP(hipMemcpyAsync(ws->rg_h_ctr, ws->rg_ctr, RANGE_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    VL_HIP(hipStreamSynchronize(st));
+    const uint64_t total = ws->rg_h_ctr[RANGE_CTR_TOTAL];
+    if (total > m) {
+        set_last_error("grouped cut counted more rows than it was given (kernel bug)");
+        return ERR_DEVICE;
+    }
+    if (ws->rg_h_ctr[RANGE_CTR_GROUP_NAN] && total >= 2) {  // a 1-element sort never calls the comparator
+        set_last_error("NaN similarity score: the reference panics in partial_cmp().unwrap()");
+        return ERR_NAN_SCORE;
+    }
+    set_last_path(PATH_EXACT_SORT);
+    if (total == 0) return OK;
+    VL_TRY(ensure_range_ws(ws, sort_capacity_for(total), GROUPED_MAX_K));
+    VL_HIP(hipMemsetAsync(ws->rg_ctr, 0, RANGE_CTR_WORDS * sizeof(uint32_t), st));
+    VL_HIP(launch_range_cut(st, ws->d_scores, plist, nullptr, m, neg_inf, ws->rg_keys, ws->rg_pv, total, ws->rg_ctr, gor, n, true));
+    VL_HIP(launch_range_rank(st, ws->rg_keys, ws->rg_pv, ws->d_scores, nullptr, total, 0, nullptr, nullptr));
+    VL_TRY(collapse(ws->d_scores, nullptr, total));
+    VL_HIP(hipStreamSynchronize(st));
+    const uint64_t emitted = ws->gp_h_ctr[RANGE_CTR_WORDS];
+    if (emitted > k) {
+        set_last_error("grouped collapse emitted more rows than asked for (kernel bug)");
+        return ERR_DEVICE;
+    }
+    return deliver(emitted);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@
 
 #include "rwlock.hpp"
 #include "coalescer.hpp"
+#include "group_plan.hpp"
 #include "kernels.hpp"
 #include "mfma_scan.hpp"
 #include "single_filter.hpp"
@@ -101,6 +102,19 @@ struct Workspace {
     uint32_t* rb_h_cnt = nullptr;    // pinned [MFMA_MAX_BATCH]
     uint32_t* rb_h_pos = nullptr;    // pinned [RBATCH_SPEC]: packed answers copied back before the host knows their number
     double* rb_h_scores = nullptr;   // pinned [RBATCH_SPEC]
+    // grouped search (lazy): pass 1's per-group slots and the collapse's first-appearance table ([gp_cap] each), the top
+    // groups' positions and reference scores, its counters, the emitted group keys
+    uint64_t* gp_best = nullptr;
+    uint32_t* gp_first = nullptr;
+    size_t gp_cap = 0;
+    Cand32* gp_lists = nullptr;      // [GROUP_TOP_LISTS, KP]
+    uint32_t* gp_cand = nullptr;     // [KP]
+    double* gp_scores = nullptr;     // [KP]
+    uint32_t* gp_ctr = nullptr;      // [RANGE_CTR_WORDS] pass 1's, then [1] the collapse's count
+    uint64_t* gp_out_keys = nullptr; // [GROUPED_MAX_K]
+    uint32_t* gp_h_ctr = nullptr;    // pinned [RANGE_CTR_WORDS + 1]
+    double* gp_h_scores = nullptr;   // pinned [KP]
+    uint64_t* gp_h_keys = nullptr;   // pinned [GROUPED_MAX_K]
     // diversified search (lazy): the candidates' pairwise similarities, [MMR_MAX_FETCH][MMR_MAX_FETCH] (8 MB)
     double* mmr_sim = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -153,6 +167,20 @@ struct IdFilter {
     bool h_plist_valid = false;
 
     ~IdFilter();
+};
+
+// A group table of one single-GPU flat handle (vl_index_groups_create): the caller's (id, group key) pairs as a GroupPlan,
+// and -- resolved like an id filter, with the same staleness rule -- the ascending positions of the rows that have a group
+// (`rows`: an IdFilter over the table's ids) and group_of_row[position] for every row of the index.
+struct GroupTable {
+    IdFilter rows;                         // rows.mu guards everything here (taken after the index lock)
+    std::vector<uint64_t> keys;            // dense group number -> the caller's key
+    uint32_t* d_dense = nullptr;           // [rows.ids.size()] dense group number of each sorted id
+    unsigned long long* d_keys = nullptr;  // [keys.size()]
+    uint32_t* d_group_of_row = nullptr;    // [gor_cap] GROUP_NONE: the row has no group
+    uint64_t gor_cap = 0;
+
+    ~GroupTable();
 };
 
 // A diversified search riding on a single search (search_mmr): how many candidates the selection returns, and lambda.
@@ -246,6 +274,16 @@ public:
     // min(k, |C|, out_capacity) entries in selection order, scores = the candidates' reference scores.
     int search_mmr(uint64_t token, const double* query, uint64_t q_len, uint64_t k, uint64_t fetch_k, double lambda, int metric,
                    uint64_t out_capacity, uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;
+    // NEW (no reference counterpart): the best row of each of the best k groups.  A group table maps
+    // ids to caller-chosen u64 group keys; rows whose id it does not hold take no part.  With S = the FlatIndex of the rows
+    // that have a group (and, token != 0, pass the filter) in storage order, the answer is search(q, len(S)) on S walked from
+    // the front, a row emitted iff no earlier row has its group key, until k rows are out.
+    int groups_create(GroupPlan&& plan, uint64_t* out_token, uint64_t* out_rows);  // the caller's pairs, planned (group_plan.hpp)
+    int groups_rows(uint64_t groups, uint64_t* out_rows, uint64_t* out_distinct) const;  // resolves again if rows changed since
+    int groups_destroy(uint64_t groups);
+    int search_grouped(uint64_t groups, uint64_t token, const double* query, uint64_t q_len, uint64_t k, int metric,
+                       uint64_t out_capacity, uint64_t* out_group_keys, uint64_t* out_pos, uint64_t* out_ids, double* out_scores,
+                       uint64_t* out_n) const;
     uint64_t len() const;
     bool is_empty() const { return len() == 0; }
     uint64_t dimension() const { return dim_; }
@@ -361,6 +399,13 @@ private:
     int search_range_locked(Workspace* ws, IdFilter* f, const double* query, double min_score, int metric, uint64_t out_capacity,
                             uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
                             uint64_t* out_total) const;  // mu_ held (shared), f resolved (nullptr: the whole index)
+    std::shared_ptr<GroupTable> find_groups(uint64_t token) const;
+    int resolve_groups(Workspace* ws, GroupTable* t) const;  // mu_ held (shared or unique), t->rows.mu held
+    int ensure_group_ws(Workspace* ws, uint64_t n_groups) const;
+    // mu_ held (shared), t resolved, f resolved (nullptr: no filter)
+    int search_grouped_locked(Workspace* ws, const GroupTable* t, const IdFilter* f, const double* query, uint64_t k, int metric,
+                              uint64_t out_capacity, uint64_t* out_group_keys, uint64_t* out_pos, uint64_t* out_ids,
+                              double* out_scores, uint64_t* out_n) const;
     int ensure_range_batch_ws(Workspace* ws, uint64_t seq_queries) const;
     // the MFMA route of search_range_batch (mu_ held, whole index): done[qi] is set for every query answered here
     int search_range_batch_mfma(Workspace* ws, const double* queries, uint64_t nq, const double* min_scores, int metric,
@@ -428,6 +473,7 @@ private:
 
     mutable std::mutex filters_mu_;  // the filter table; never held while an index lock or a filter's mutex is taken
     std::unordered_map<uint64_t, std::shared_ptr<IdFilter>> filters_;
+    std::unordered_map<uint64_t, std::shared_ptr<GroupTable>> groups_;  // under filters_mu_ as well; tokens share the filters' counter
 
     std::atomic<int> force_path_{0};
     std::atomic<int> single_filter_{FILTER_AUTO};

@@ -372,6 +372,44 @@ __global__ __launch_bounds__(256) void k_scan_range_generic(const f32x4* __restr
     scan_stream_generic<METRIC, G>(slab, inv_norm, q64, dim, n, ld4, range_rows<SUBSET>(plist), RangeSink<1>(tau, cand, cap, ctr));
 }
 
+// ---------------------------------------------------------------------------------------------
+// Grouped search, pass 1: the f32 scan with GroupBestSink, over every row or (SUBSET) over
+// plist[0..n).  A row's key is bit for bit the one k_scan gives it.  The three forms of the range scan.
+// ---------------------------------------------------------------------------------------------
+template <int METRIC, int G, int VPL, int U, bool SUBSET>
+__global__ __launch_bounds__(256) void k_scan_group_best(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
+                                                         const uint32_t* __restrict__ plist, uint32_t n,
+                                                         const uint32_t* __restrict__ group_of_row,
+                                                         unsigned long long* __restrict__ best, const ScanQArg qa)
+{
+    f32x4 qv[VPL];
+    load_query<G>(qv, qa);
+    scan_stream<G, U>(F32Rows<METRIC, VPL>{slab, inv_norm}, qv, range_rows<SUBSET>(plist), n, GroupBestSink<U>(group_of_row, best));
+}
+
+template <int METRIC, int G, int VPL, int U, bool SUBSET>
+__global__ __launch_bounds__(256) void k_scan_group_best_q64(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
+                                                             const uint32_t* __restrict__ plist,
+                                                             const double* __restrict__ q64, uint32_t dim, uint32_t n,
+                                                             const uint32_t* __restrict__ group_of_row,
+                                                             unsigned long long* __restrict__ best)
+{
+    f32x4 qv[VPL];
+    load_query<G>(qv, q64, dim);
+    scan_stream<G, U>(F32Rows<METRIC, VPL>{slab, inv_norm}, qv, range_rows<SUBSET>(plist), n, GroupBestSink<U>(group_of_row, best));
+}
+
+template <int METRIC, int G, bool SUBSET>
+__global__ __launch_bounds__(256) void k_scan_group_best_generic(const f32x4* __restrict__ slab,
+                                                                 const float* __restrict__ inv_norm,
+                                                                 const uint32_t* __restrict__ plist,
+                                                                 const double* __restrict__ q64, uint32_t dim, uint32_t n,
+                                                                 uint32_t ld4, const uint32_t* __restrict__ group_of_row,
+                                                                 unsigned long long* __restrict__ best)
+{
+    scan_stream_generic<METRIC, G>(slab, inv_norm, q64, dim, n, ld4, range_rows<SUBSET>(plist), GroupBestSink<1>(group_of_row, best));
+}
+
 // K3: small-batch scan.  One pass over the slab serves QB queries: each row group is loaded ONCE into
 // registers and scored against QB queries whose f32 copies sit in LDS (lanes that share a column read
 // the same 16 bytes: an LDS broadcast).  Per wave, QB independent top-64 lists.  Still streams
@@ -1375,11 +1413,13 @@ __global__ void k_sort_emit(const uint32_t* __restrict__ opos, const double* __r
 // `store_cap` are counted and not stored (store_cap = 0: count only).  cand == nullptr: slot i IS the position (the exact
 // route's scores[] of every row); else the position is cand[i] (the fast route's candidates, or a filter's list).
 // m_ptr != nullptr: m is the range scan's counter, and nothing is done when it ran past cap_in.
+template <bool GROUPED>
 __global__ __launch_bounds__(256) void k_range_cut(const double* __restrict__ scores, const uint32_t* __restrict__ cand,
                                                    const uint32_t* __restrict__ m_ptr, uint32_t m_val, uint32_t cap_in,
                                                    double min_score, unsigned long long* __restrict__ keys,
                                                    unsigned long long* __restrict__ pv, uint32_t store_cap,
-                                                   uint32_t* __restrict__ ctr)
+                                                   uint32_t* __restrict__ ctr, const uint32_t* __restrict__ group_of_row,
+                                                   uint32_t n_rows, int keep_nan)
 {
     const uint32_t m = m_ptr ? *m_ptr : m_val;
     if (m_ptr && m > cap_in) return;
@@ -1389,7 +1429,16 @@ __global__ __launch_bounds__(256) void k_range_cut(const double* __restrict__ sc
         const uint32_t i = b0 + threadIdx.x;
         const bool valid = i < m;
         const double sc = scores[valid ? i : m - 1];
-        const bool keep = valid && sc >= min_score;
+        bool keep = valid && sc >= min_score;
+        if constexpr (GROUPED) {
+            // a grouped search's cut: rows without a group take no part; keep_nan (its exact route): NaN scores stay in and
+            // are counted, so that the host knows |S| and whether the reference's sort would have met a NaN
+            const uint32_t pos = cand ? cand[valid ? i : m - 1] : i;
+            const bool grouped = valid && pos < n_rows && group_of_row[pos] != GROUP_NONE;
+            const bool is_nan = sc != sc;
+            if (grouped && is_nan && keep_nan) atomicAdd(ctr + RANGE_CTR_GROUP_NAN, 1u);
+            keep = grouped && (keep || (is_nan && keep_nan));
+        }
         const unsigned long long bal = __ballot(keep);
         if (bal == 0ull) continue;  // wave-uniform
         uint32_t base = 0;
@@ -1948,6 +1997,14 @@ struct RangeFamily {
     template <int G> static auto generic() { return k_scan_range_generic<MM, G, SUBSET>; }
 };
 
+template <int MM, bool SUBSET>
+struct GroupBestFamily {
+    static constexpr bool ALL_SHAPES = false, Q64_AT_ANY_STRIDE = false;
+    template <int G, int VPL, int U> static auto qarg() { return k_scan_group_best<MM, G, VPL, U, SUBSET>; }
+    template <int G, int VPL, int U> static auto q64() { return k_scan_group_best_q64<MM, G, VPL, U, SUBSET>; }
+    template <int G> static auto generic() { return k_scan_group_best_generic<MM, G, SUBSET>; }
+};
+
 // does a scan of this shape and stride take its query in the kernel arguments
 bool shape_takes_qarg(const ScanShape& sh, uint32_t ld, const float* q32_host)
 {
@@ -2363,6 +2420,30 @@ hipError_t launch_scan_range(hipStream_t s, int metric, const float* slab, const
     return rc;
 }
 
+// ---- grouped search, pass 1: the range scan's shapes, GroupBestSink in RangeSink's place ------------------------------
+hipError_t launch_scan_group_best(hipStream_t s, int metric, const float* slab, const float* inv_norm, const uint32_t* plist,
+                                  uint64_t n, const double* q64, uint32_t dim, uint32_t ld, const uint32_t* group_of_row,
+                                  uint64_t* best, ScanPlan* plan, const float* q32_host)
+{
+    if (n == 0 || n >= 0xFFFFFFFFull || (ld & 3) || !group_of_row || !best) return hipErrorInvalidValue;
+    const ScanShape sh = default_scan_shape(ld / 4);
+    const f32x4* slab4 = reinterpret_cast<const f32x4*>(slab);
+    if (!shape_takes_qarg(sh, ld, q32_host) && !q64) return hipErrorInvalidValue;
+    int grid = 0;
+    hipError_t rc = dispatch_metric(metric, [&](auto M) -> hipError_t {
+        constexpr int MM = decltype(M)::value;
+        const auto head = std::make_tuple(slab4, inv_norm, plist);
+        const auto tail = std::make_tuple(group_of_row, reinterpret_cast<unsigned long long*>(best));
+        if (plist) return launch_scan_family<GroupBestFamily<MM, true>>(s, sh, n, ld, q64, dim, q32_host, head, tail, &grid);
+        return launch_scan_family<GroupBestFamily<MM, false>>(s, sh, n, ld, q64, dim, q32_host, head, tail, &grid);
+    });
+    if (plan) {
+        plan->grid = grid;
+        plan->variant = sh.special ? (GROUP_VARIANT_BASE + sh.g * 10000 + sh.vpl * 100 + sh.u) : -(GROUP_VARIANT_BASE + sh.g);
+    }
+    return rc;
+}
+
 hipError_t launch_range_rescore(hipStream_t s, int metric, const double* master, const double* q64, const uint32_t* cand,
                                 uint32_t cap, uint32_t dim, double* scores, uint32_t* ctr)
 {
@@ -2378,14 +2459,20 @@ hipError_t launch_range_rescore(hipStream_t s, int metric, const double* master,
 }
 
 hipError_t launch_range_cut(hipStream_t s, const double* scores, const uint32_t* cand, const uint32_t* m_ptr, uint64_t m_max,
-                            double min_score, uint64_t* keys, uint64_t* pv, uint64_t store_cap, uint32_t* ctr)
+                            double min_score, uint64_t* keys, uint64_t* pv, uint64_t store_cap, uint32_t* ctr,
+                            const uint32_t* group_of_row, uint64_t n_rows, bool keep_nan)
 {
-    if (m_max == 0 || m_max >= 0xFFFFFFFFull || store_cap >= 0xFFFFFFFFull) return hipErrorInvalidValue;
+    if (m_max == 0 || m_max >= 0xFFFFFFFFull || store_cap >= 0xFFFFFFFFull || n_rows >= 0xFFFFFFFFull) return hipErrorInvalidValue;
     const uint64_t blocks = (m_max + 255) / 256;
     const int grid = (int)(blocks < 2048 ? blocks : 2048);
-    hipLaunchKernelGGL(k_range_cut, dim3(grid), dim3(256), 0, s, scores, cand, m_ptr, (uint32_t)m_max, (uint32_t)m_max, min_score,
-                       reinterpret_cast<unsigned long long*>(keys), reinterpret_cast<unsigned long long*>(pv),
-                       (uint32_t)store_cap, ctr);
+    unsigned long long* k64 = reinterpret_cast<unsigned long long*>(keys);
+    unsigned long long* p64 = reinterpret_cast<unsigned long long*>(pv);
+    if (group_of_row)
+        hipLaunchKernelGGL(k_range_cut<true>, dim3(grid), dim3(256), 0, s, scores, cand, m_ptr, (uint32_t)m_max, (uint32_t)m_max,
+                           min_score, k64, p64, (uint32_t)store_cap, ctr, group_of_row, (uint32_t)n_rows, keep_nan ? 1 : 0);
+    else
+        hipLaunchKernelGGL(k_range_cut<false>, dim3(grid), dim3(256), 0, s, scores, cand, m_ptr, (uint32_t)m_max, (uint32_t)m_max,
+                           min_score, k64, p64, (uint32_t)store_cap, ctr, (const uint32_t*)nullptr, 0u, 0);
     return hipGetLastError();
 }
 

@@ -181,7 +181,7 @@ hipError_t launch_filter_compact(hipStream_t s, const unsigned long long* pos_id
 constexpr int RANGE_VARIANT_BASE = 4000000;
 constexpr uint32_t RANGE_CAND_MAX = 1u << 20;  // C: positions the candidate buffer holds (4 MB; with scores, keys and payloads 28 MB)
 constexpr uint32_t RANGE_SMALL = 2048;         // survivors ranked before the host knows their number (one workgroup's LDS sort)
-constexpr int RANGE_CTR_APPENDED = 0, RANGE_CTR_TOTAL = 1, RANGE_CTR_NAN = 2, RANGE_CTR_WORDS = 4;
+constexpr int RANGE_CTR_APPENDED = 0, RANGE_CTR_TOTAL = 1, RANGE_CTR_NAN = 2, RANGE_CTR_GROUP_NAN = 3, RANGE_CTR_WORDS = 4;
 // The scan that appends: cand[] receives the storage position of every row whose key is NOT <= tau (tau NaN: every row), up to
 // cap of them.  plist != nullptr: over the rows plist[0..n) (an id filter's list).  Keys, query forms and grid are k_scan's.
 // plan->variant = RANGE_VARIANT_BASE + G * 10000 + VPL * 100 + U, or -(RANGE_VARIANT_BASE + G) for the generic kernel.
@@ -195,13 +195,42 @@ hipError_t launch_range_rescore(hipStream_t s, int metric, const double* master,
 // The cut: slots i < m with scores[i] >= min_score are appended to (keys, pv) = (descending-order key of the score,
 // position << 32 | i), position = cand ? cand[i] : i; ctr[TOTAL] counts them, entries past store_cap are only counted.
 // m = *m_ptr when given (nothing is done when it exceeds m_max), else m_max.
+// group_of_row != nullptr (a grouped search): rows whose group_of_row[position] is GROUP_NONE are
+// dropped as well; with keep_nan, NaN scores of grouped rows stay in and ctr[GROUP_NAN] counts them.
 hipError_t launch_range_cut(hipStream_t s, const double* scores, const uint32_t* cand, const uint32_t* m_ptr, uint64_t m_max,
-                            double min_score, uint64_t* keys, uint64_t* pv, uint64_t store_cap, uint32_t* ctr);
+                            double min_score, uint64_t* keys, uint64_t* pv, uint64_t store_cap, uint32_t* ctr,
+                            const uint32_t* group_of_row = nullptr, uint64_t n_rows = 0, bool keep_nan = false);
 // Rank (keys, pv) by (score desc, position asc) and write the first min(total, k) (position, score).  total_ptr != nullptr:
 // the count is still the device's -- ranks up to RANGE_SMALL survivors (more: the output is unspecified, call again with
 // the count); else `total` entries, buffers of sort_capacity_for(total).
 hipError_t launch_range_rank(hipStream_t s, uint64_t* keys, uint64_t* pv, const double* scores, const uint32_t* total_ptr,
                              uint64_t total, uint64_t k, uint32_t* out_pos, double* out_scores);
+
+// Grouped search (best row per group).
+// The group table's resolution beside the filter's: group_of_row[p] = dense[i] when pos_ids[p] == fids[i], else GROUP_NONE.
+hipError_t launch_group_rows(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
+                             const uint32_t* dense, uint64_t nf, uint32_t* group_of_row);
+// Pass 1: every scanned row with a group raises best[group] (zeroed by the caller) to
+// ordered(key) << 32 | (0xFFFFFFFF - position).  plist != nullptr: over the rows plist[0..n).  Keys, query forms, shapes
+// and grid are the range scan's.  plan->variant = GROUP_VARIANT_BASE + G * 10000 + VPL * 100 + U, or
+// -(GROUP_VARIANT_BASE + G) for the generic kernel.
+constexpr int GROUP_VARIANT_BASE = 5000000;
+constexpr uint32_t GROUPED_MAX_K = 1024;  // VL_GROUPED_MAX_K
+hipError_t launch_scan_group_best(hipStream_t s, int metric, const float* slab, const float* inv_norm, const uint32_t* plist,
+                                  uint64_t n, const double* q64, uint32_t dim, uint32_t ld, const uint32_t* group_of_row,
+                                  uint64_t* best, ScanPlan* plan, const float* q32_host = nullptr);
+// The 64 largest values of best[0..n_groups), decoded: cand[0..c) = their positions, best first, c = min(k, non-empty
+// groups, 64) -> ctr[RANGE_CTR_APPENDED] (what launch_range_rescore reads).  lists: GROUP_TOP_LISTS * KP entries of scratch.
+constexpr int GROUP_TOP_LISTS = 64;
+hipError_t launch_group_top(hipStream_t s, const uint64_t* best, uint64_t n_groups, uint32_t k, Cand32* lists, uint32_t* cand,
+                            uint32_t* ctr);
+// The collapse of n ranked survivors pv[i] = position << 32 | slot (n = *n_ptr when given -- nothing is done when it exceeds
+// n_max -- else n_max): survivor i is kept iff no earlier one has its group; the first k kept are written as (group key,
+// position, scores[slot]) and *out_n = their number.  first: n_groups words of scratch.
+hipError_t launch_group_collapse(hipStream_t s, const uint64_t* pv, const double* scores, const uint32_t* n_ptr, uint64_t n_max,
+                                 const uint32_t* group_of_row, uint64_t n_rows, const uint64_t* group_keys, uint64_t n_groups,
+                                 uint32_t* first, uint32_t k, uint64_t* out_keys, uint32_t* out_pos, double* out_scores,
+                                 uint32_t* out_n);
 
 // Batched range search: the device tail behind launch_mfma_range_candidates.  cand / cnt / cap are
 // the MFMA filter's per-query candidate buffers; ctr holds RBATCH_CTR_WORDS words per query, zeroed by the caller:

@@ -6,12 +6,13 @@
 //     is, which per-row scalars travel with the row loads, how a chunk meets the lane's query slice, how the reduced
 //     sum becomes a key;
 //   * a ROW SOURCE (AllRows, ListedRows): which storage position step i scores;
-//   * a SINK (TopSink, RangeSink): what happens to (key, position, valid).
+//   * a SINK (TopSink, RangeSink, GroupBestSink): what happens to (key, position, valid).
 // The run-time-stride f32 kernels (k_scan_generic and its subset / range forms) share the sources and sinks through
 // the much smaller scan_stream_generic() in kernels.hip.
 #pragma once
 
 #include "device_common.hpp"
+#include "group_plan.hpp"
 
 namespace vl {
 namespace dev {
@@ -138,6 +139,48 @@ struct RangeSink {
         at[u] = pos;
     }
     __device__ __forceinline__ void step() { range_append<U>(hit, at, cand, cap, ctr); }
+    __device__ __forceinline__ void finish() {}
+};
+
+// Grouped search, pass 1: the scan that keeps the best key PER GROUP.  A row of group g raises
+// best[g] to (ordered bits of its key) << 32 | (0xFFFFFFFF - position): larger key first, lower position on ties, never 0
+// for a row that is there (best[] is zeroed in front of the launch).  A load goes in front of the atomic and the lane
+// skips the atomic when its value would not raise the slot: values only grow, so a stale read costs an atomic and never
+// loses a row.  The U group numbers of an iteration are requested together, then the U slots.  No LDS, no block merge.
+__device__ __forceinline__ uint32_t key_to_ordered(float key)
+{
+    const uint32_t b = (uint32_t)__float_as_int(key);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+template <int U>
+struct GroupBestSink {
+    const uint32_t* __restrict__ group_of_row;
+    unsigned long long* __restrict__ best;
+    bool on[U];
+    unsigned long long val[U];
+    __device__ __forceinline__ GroupBestSink(const uint32_t* __restrict__ gor, unsigned long long* __restrict__ b)
+        : group_of_row(gor), best(b)
+    {
+    }
+    __device__ __forceinline__ void offer(int u, float key, uint32_t pos, bool active)
+    {
+        on[u] = active;
+        val[u] = ((unsigned long long)key_to_ordered(key) << 32) | (unsigned long long)(0xFFFFFFFFu - pos);
+    }
+    __device__ __forceinline__ void step()
+    {
+        uint32_t g[U];
+        unsigned long long seen[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) g[u] = on[u] ? group_of_row[0xFFFFFFFFu - (uint32_t)val[u]] : GROUP_NONE;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            seen[u] = g[u] != GROUP_NONE ? __hip_atomic_load(best + g[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ~0ull;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (seen[u] < val[u]) (void)__hip_atomic_fetch_max(best + g[u], val[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     __device__ __forceinline__ void finish() {}
 };
 
