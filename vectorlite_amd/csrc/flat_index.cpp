@@ -6,6 +6,7 @@
 // positions back to ids for the k winners (the reference re-attaches text/metadata the same way,
 // src/index/flat.rs:106-114).  There is no CPU compute fallback.
 #include "flat_index.hpp"
+#include "lazy_buffers.hpp"
 #include "shard.hpp"
 #include "score_bound.hpp"
 
@@ -98,6 +99,123 @@ int pinned_alloc(T** p, size_t count)
     VL_HIP(hipHostMalloc(reinterpret_cast<void**>(p), count * sizeof(T), hipHostMallocDefault));
     return OK;
 }
+// what lazy_buffers.hpp allocates with here: device memory, or pinned host memory
+struct HipMem {
+    int alloc(void** p, size_t bytes, bool pinned) const
+    {
+        unsigned char** b = reinterpret_cast<unsigned char**>(p);
+        return pinned ? pinned_alloc(b, bytes) : dev_alloc(b, bytes);
+    }
+    void release(void* p, bool pinned) const { (void)(pinned ? hipHostFree(p) : hipFree(p)); }
+};
+
+// ---- lazily made workspace buffers (all or nothing: a failed call leaves the workspace as it found it) ----
+int ensure_scores(Workspace* ws, uint64_t rows)  // the exact scans' score of every row
+{
+    return grow(HipMem{}, ws->scores_cap, std::max<size_t>(rows, 1024), {dev_buf(ws->d_scores, std::max<size_t>(rows, 1024))});
+}
+int ensure_out(Workspace* ws, uint64_t need)  // ranked (position, score) pairs on the device: the sort's, the range routes'
+{
+    return grow(HipMem{}, ws->out_cap, need, {dev_buf(ws->d_out_pos, need), dev_buf(ws->d_out_scores, need)});
+}
+int ensure_range_ws(Workspace* ws, uint64_t sort_cap, uint64_t out_cap)
+{
+    VL_TRY(ensure_set(HipMem{}, {dev_buf(ws->rg_ctr, RANGE_CTR_WORDS), pinned_buf(ws->rg_h_ctr, RANGE_CTR_WORDS),
+                                 pinned_buf(ws->rg_h_pos, RANGE_SMALL), pinned_buf(ws->rg_h_scores, RANGE_SMALL)}));
+    VL_TRY(grow(HipMem{}, ws->rg_sort_cap, sort_cap, {dev_buf(ws->rg_keys, sort_cap), dev_buf(ws->rg_pv, sort_cap)}));
+    return ensure_out(ws, out_cap);
+}
+int ensure_range_candidates(Workspace* ws)  // the fast range scan's candidate positions and their scores
+{
+    return ensure_set(HipMem{}, {dev_buf(ws->rg_cand, RANGE_CAND_MAX), dev_buf(ws->rg_scores, RANGE_CAND_MAX)});
+}
+int ensure_group_ws(Workspace* ws, uint64_t n_groups)
+{
+    VL_TRY(ensure_set(HipMem{}, {dev_buf(ws->gp_ctr, RANGE_CTR_WORDS + 1), dev_buf(ws->gp_lists, (size_t)GROUP_TOP_LISTS * KP),
+                                 dev_buf(ws->gp_cand, KP), dev_buf(ws->gp_scores, KP), dev_buf(ws->gp_out_keys, GROUPED_MAX_K),
+                                 pinned_buf(ws->gp_h_ctr, RANGE_CTR_WORDS + 1), pinned_buf(ws->gp_h_scores, KP),
+                                 pinned_buf(ws->gp_h_keys, GROUPED_MAX_K)}));
+    return grow(HipMem{}, ws->gp_cap, n_groups, {dev_buf(ws->gp_best, n_groups), dev_buf(ws->gp_first, n_groups)});
+}
+
+// ---- the single-query protocol's small steps ----
+// the next result stamp of this workspace (never 0), the pinned block's stamp cleared for it
+uint32_t next_stamp(Workspace* ws)
+{
+    uint32_t seq = ++ws->seq;
+    if (seq == 0) seq = ++ws->seq;
+    ws->h_result->seq = 0;
+    return seq;
+}
+// the f32 query a scan takes in its kernel arguments: `width` floats, zero past dim (nearest even, like load_q4 on the device)
+const float* stage_q32(Workspace* ws, const double* query, uint64_t dim, uint32_t width)
+{
+    if (ws->q32.size() < width) ws->q32.assign(width, 0.0f);
+    for (uint64_t i = 0; i < dim; ++i) ws->q32[i] = (float)query[i];
+    return ws->q32.data();
+}
+
+// The answer's positions -> the caller's arrays, entry i from pos_at(i) / score_at(i); `what` names the route.
+template <typename PosAt, typename ScoreAt>
+int deliver(const char* what, const std::vector<uint64_t>& row_ids, uint64_t count, PosAt pos_at, ScoreAt score_at, uint64_t* out_pos,
+            uint64_t* out_ids, double* out_scores)
+{
+    const uint64_t n = row_ids.size();
+    for (uint64_t i = 0; i < count; ++i) {
+        const uint32_t p = pos_at(i);
+        if (p >= n) {
+            set_last_error(std::string(what) + " returned an out-of-range position (kernel bug)");
+            return ERR_DEVICE;
+        }
+        if (out_pos) out_pos[i] = p;
+        if (out_ids) out_ids[i] = row_ids[p];
+        out_scores[i] = score_at(i);
+    }
+    return OK;
+}
+int deliver(const char* what, const std::vector<uint64_t>& row_ids, const uint32_t* pos, const double* scores, uint64_t count,
+            uint64_t* out_pos, uint64_t* out_ids, double* out_scores)
+{
+    return deliver(what, row_ids, count, [&](uint64_t i) { return pos[i]; }, [&](uint64_t i) { return scores[i]; }, out_pos, out_ids,
+                   out_scores);
+}
+// ... from result blocks: entry i is blocks[i / KP]'s (i % KP)-th
+int deliver(const char* what, const std::vector<uint64_t>& row_ids, const SearchResultBlock* blocks, uint64_t count, uint64_t* out_pos,
+            uint64_t* out_ids, double* out_scores)
+{
+    return deliver(what, row_ids, count, [&](uint64_t i) { return blocks[i / KP].pos[i % KP]; },
+                   [&](uint64_t i) { return blocks[i / KP].score[i % KP]; }, out_pos, out_ids, out_scores);
+}
+
+// Token tables (filters, group tables).  token_find: the entry of `token`.  token_take: the same, removed from the table;
+// the caller's reference frees it outside the lock, and only once no search uses it.
+template <typename Map>
+int token_find(std::mutex& mu, const Map& table, uint64_t token, const char* unknown, typename Map::mapped_type* out)
+{
+    std::lock_guard<std::mutex> g(mu);
+    auto it = table.find(token);
+    if (it == table.end()) {
+        set_last_error(unknown);
+        return ERR_INVALID_ARG;
+    }
+    *out = it->second;
+    return OK;
+}
+template <typename Map>
+int token_take(std::mutex& mu, Map& table, uint64_t token, const char* unknown, typename Map::mapped_type* out)
+{
+    std::lock_guard<std::mutex> g(mu);
+    auto it = table.find(token);
+    if (it == table.end()) {
+        set_last_error(unknown);
+        return ERR_INVALID_ARG;
+    }
+    *out = std::move(it->second);
+    table.erase(it);
+    return OK;
+}
+constexpr const char* UNKNOWN_FILTER = "unknown or destroyed filter";
+constexpr const char* UNKNOWN_GROUPS = "unknown or destroyed group table";
 }  // namespace
 
 Workspace::~Workspace()
@@ -179,6 +297,31 @@ bool stage_query(const double* q, double* dst, uint64_t dim, double* norm_out)
         *norm_out = norm;
     }
     return in_domain;
+}
+
+// The single-query entry points stage their query here instead: ws->h_q64 = the f64 values, then the norm.  Two staging
+// functions because they differ in what the certified bounds see.  This one sums the squares sequentially -- the order the
+// filter audits restate (tests/native/filter_audit.hip) -- and keeps the raw values of a query outside the domain, which
+// the exact route reads; stage_query's four accumulators round the norm differently in the last bit, and it zeroes.
+struct StagedQuery {
+    double norm;
+    bool in_domain;
+};
+StagedQuery stage_single_query(Workspace* ws, const double* query, uint64_t dim)
+{
+    double qq = 0.0, qmax = 0.0;
+    bool finite = true;
+    for (uint64_t i = 0; i < dim; ++i) {
+        const double v = query[i];
+        ws->h_q64[i] = v;
+        qq += v * v;
+        const double av = std::fabs(v);
+        if (!(av <= 1.797693134862315708e308)) finite = false;
+        if (av > qmax) qmax = av;
+    }
+    const double norm = std::sqrt(qq);
+    ws->h_q64[dim] = norm;
+    return {norm, finite && qmax <= DOMAIN_MAX_ABS && (norm == 0.0 || norm >= DOMAIN_MIN_NORM)};
 }
 }  // namespace
 
@@ -614,6 +757,116 @@ void GpuFlatIndex::release_ws(Workspace* ws) const
     ws_pool_->free_.push_back(ws);
 }
 
+// A workspace borrowed for one call.  The caller records the call's status with done(); a call that failed may still have
+// work of its own on the stream, which is drained before the workspace goes back.  The single-query entry points must not
+// synchronise on success (their latency is a stamp poll, wait_result); the batch routes always do (sync_always), so
+// they have no status to record and return without done().
+class GpuFlatIndex::WsLease {
+public:
+    explicit WsLease(const GpuFlatIndex* self, bool sync_always = false) : self_(self), device_(self->device_), sync_always_(sync_always)
+    {
+        status_ = open();
+    }
+    ~WsLease()
+    {
+        if (!ws) return;
+        if (sync_always_ || status_ != OK) (void)hipStreamSynchronize(ws->stream);
+        self_->release_ws(ws);
+    }
+    WsLease(const WsLease&) = delete;
+    WsLease& operator=(const WsLease&) = delete;
+    int status() const { return status_; }  // of the lease itself (hipSetDevice, the pool) until done() records the call's
+    int done(int rc) { return status_ = rc; }
+
+    Workspace* ws = nullptr;
+
+private:
+    int open()
+    {
+        VL_HIP(hipSetDevice(device_));
+        ws = self_->acquire_ws();
+        return ws ? OK : ERR_DEVICE;
+    }
+    const GpuFlatIndex* self_;
+    const int device_;
+    const bool sync_always_;
+    int status_ = OK;
+};
+
+namespace {
+int check_metric(int metric)
+{
+    if (metric >= 0 && metric <= 3) return OK;
+    set_last_error("unknown metric");
+    return ERR_INVALID_ARG;
+}
+struct InFlight {  // one of the handle's single searches in flight (wait_result's spin-or-sleep choice counts them)
+    std::atomic<int>& n;
+    explicit InFlight(std::atomic<int>& counter) : n(counter) { n.fetch_add(1, std::memory_order_relaxed); }
+    ~InFlight() { n.fetch_sub(1, std::memory_order_relaxed); }
+};
+}  // namespace
+
+int GpuFlatIndex::dim_mismatch(uint64_t q_len) const
+{
+    set_dim_mismatch(dim_, q_len);
+    set_last_error("Dimension mismatch: expected " + std::to_string(dim_) + ", got " + std::to_string(q_len));
+    return ERR_DIM_MISMATCH;
+}
+
+// The checks every read-side entry point makes once its tokens are looked up, in the order callers can observe: the
+// metric, then the index lock (shared: readers share it, add / delete wait, so resolved lists and positions cannot move
+// under the search), then the query length (src/index/flat.rs:99-104: skipped while the index is empty).
+int GpuFlatIndex::lock_for_query(int metric, uint64_t q_len, std::shared_lock<RwLock>* lk) const
+{
+    VL_TRY(check_metric(metric));
+    *lk = std::shared_lock<RwLock>(mu_);
+    if (!ids_.empty() && q_len != dim_) return dim_mismatch(q_len);
+    return OK;
+}
+
+int GpuFlatIndex::resolve_if_stale(Workspace* ws, IdFilter* f) const
+{
+    std::lock_guard<std::mutex> g(f->mu);
+    return f->resolved_at != mutations_ ? resolve_filter(ws, f) : OK;
+}
+
+int GpuFlatIndex::resolve_if_stale(Workspace* ws, GroupTable* t) const
+{
+    std::lock_guard<std::mutex> g(t->rows.mu);
+    return t->rows.resolved_at != mutations_ ? resolve_groups(ws, t) : OK;
+}
+
+// From here on the resolutions are read only: a reader that finds them current leaves them alone, writers are shut out.
+template <typename Body>
+int GpuFlatIndex::run_search(GroupTable* t, IdFilter* f, Body&& body) const
+{
+    WsLease lease(this);
+    if (lease.status() != OK) return lease.status();
+    if (t) VL_TRY(lease.done(resolve_if_stale(lease.ws, t)));
+    if (f) VL_TRY(lease.done(resolve_if_stale(lease.ws, f)));
+    InFlight searching(active_searches_);
+    return lease.done(body(lease.ws));
+}
+
+// One profiled scan: the time between the workspace's event pair, the bytes it streamed.  A stamp poll can return
+// before the runtime has retired ev1, hence the retry; where the stream was synchronised it never triggers.
+int GpuFlatIndex::account_profile(Workspace* ws, uint64_t bytes, uint64_t passes) const
+{
+    float ms = 0.f;
+    hipError_t pe = hipEventElapsedTime(&ms, ws->ev0, ws->ev1);
+    if (pe == hipErrorNotReady) {
+        VL_HIP(hipEventSynchronize(ws->ev1));
+        pe = hipEventElapsedTime(&ms, ws->ev0, ws->ev1);
+    }
+    VL_HIP(pe);
+    std::lock_guard<std::mutex> g(prof_mu_);
+    prof_n_ += passes;
+    prof_ms_ += ms;
+    prof_bytes_ += bytes;
+    return OK;
+}
+
 void GpuFlatIndex::profile_enable(bool on) { profile_.store(on); }
 
 void GpuFlatIndex::profile_read(uint64_t* n, double* ms, uint64_t* bytes)
@@ -726,30 +979,14 @@ int GpuFlatIndex::search_direct(const double* query, uint64_t q_len, uint64_t k,
 {
     if (!out_n) return ERR_INVALID_ARG;
     *out_n = 0;
-    if (metric < 0 || metric > 3) {
-        set_last_error("unknown metric");
-        return ERR_INVALID_ARG;
-    }
-    std::shared_lock<RwLock> lk(mu_);
+    std::shared_lock<RwLock> lk;
+    VL_TRY(lock_for_query(metric, q_len, &lk));
     const uint64_t n = ids_.size();
-    if (n != 0 && q_len != dim_) {  // :99-104 (skipped while the index is empty)
-        set_dim_mismatch(dim_, q_len);
-        set_last_error("Dimension mismatch: expected " + std::to_string(dim_) + ", got " + std::to_string(q_len));
-        return ERR_DIM_MISMATCH;
-    }
     if (n == 0 || k == 0) return OK;  // truncate(0) / nothing stored
     if ((!query && dim_) || !out_scores) return ERR_INVALID_ARG;
-    const uint64_t k_eff = std::min<uint64_t>(k, n);
-
-    VL_HIP(hipSetDevice(device_));
-    Workspace* ws = acquire_ws();
-    if (!ws) return ERR_DEVICE;
-    active_searches_.fetch_add(1, std::memory_order_relaxed);
-    const int rc = search_locked(ws, query, k_eff, metric, out_pos, out_ids, out_scores, out_n, false);
-    active_searches_.fetch_sub(1, std::memory_order_relaxed);
-    if (rc != OK) (void)hipStreamSynchronize(ws->stream);
-    release_ws(ws);
-    return rc;
+    return run_search(nullptr, nullptr, [&](Workspace* ws) {
+        return search_locked(ws, query, std::min<uint64_t>(k, n), metric, out_pos, out_ids, out_scores, out_n, false);
+    });
 }
 
 // nq independent searches sharing slab passes: up to MFMA_MAX_BATCH queries per pass over the bf16 slab
@@ -762,10 +999,7 @@ int GpuFlatIndex::search_batch(const double* queries, uint64_t nq, uint64_t q_le
     if (nq == 0) return OK;
     if (!out_n) return ERR_INVALID_ARG;
     for (uint64_t i = 0; i < nq; ++i) out_n[i] = 0;
-    if (metric < 0 || metric > 3) {
-        set_last_error("unknown metric");
-        return ERR_INVALID_ARG;
-    }
+    VL_TRY(check_metric(metric));
     std::shared_lock<RwLock> lk(mu_);
     return search_batch_locked(queries, nq, q_len, k, metric, out_pos, out_ids, out_scores, out_n);
 }
@@ -775,27 +1009,14 @@ int GpuFlatIndex::search_batch_locked(const double* queries, uint64_t nq, uint64
                                       uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n) const
 {
     const uint64_t n = ids_.size();
-    if (n != 0 && q_len != dim_) {
-        set_dim_mismatch(dim_, q_len);
-        set_last_error("Dimension mismatch: expected " + std::to_string(dim_) + ", got " + std::to_string(q_len));
-        return ERR_DIM_MISMATCH;
-    }
+    if (n != 0 && q_len != dim_) return dim_mismatch(q_len);
     if (n == 0 || k == 0) return OK;
     if (!queries || !out_scores) return ERR_INVALID_ARG;
     const uint64_t k_eff = std::min<uint64_t>(k, n);
 
-    VL_HIP(hipSetDevice(device_));
-    Workspace* ws = acquire_ws();
-    if (!ws) return ERR_DEVICE;
-    struct Releaser {
-        const GpuFlatIndex* self;
-        Workspace* ws;
-        ~Releaser()
-        {
-            (void)hipStreamSynchronize(ws->stream);
-            self->release_ws(ws);
-        }
-    } rel{this, ws};
+    WsLease lease(this, /*sync_always=*/true);
+    if (lease.status() != OK) return lease.status();
+    Workspace* const ws = lease.ws;
     hipStream_t st = ws->stream;
 
     // row lengths without an 8-query f32 shape can still take the MFMA filter (its bf16 slab is padded to 128)
@@ -848,12 +1069,9 @@ int GpuFlatIndex::search_batch_locked(const double* queries, uint64_t nq, uint64
     // blockIdx.y, each group one pass over the slab -- and ONE finalize launch, then one stream sync: staged, launched and
     // synchronised pass by pass a 50 000-row index answered 70-100 k Manhattan queries per second where cosine batches
     // reach millions (round 3's verdict, item 8).
-    if (!ws->k3_d_q64) {
-        const size_t words = (size_t)K3_PIPE_QUERIES * (dim_ + 1);
-        VL_TRY(dev_alloc(&ws->k3_d_q64, words));
-        VL_TRY(pinned_alloc(&ws->k3_h_q64, words));
-        VL_TRY(pinned_alloc(&ws->k3_h_result, (size_t)K3_PIPE_QUERIES));
-    }
+    const size_t k3_words = (size_t)K3_PIPE_QUERIES * (dim_ + 1);
+    VL_TRY(ensure_set(HipMem{}, {dev_buf(ws->k3_d_q64, k3_words), pinned_buf(ws->k3_h_q64, k3_words),
+                                 pinned_buf(ws->k3_h_result, K3_PIPE_QUERIES)}));
     std::vector<uint8_t> in_domain((size_t)K3_PIPE_QUERIES);
     for (uint64_t base = 0; base < nt; base += K3_PIPE_QUERIES) {
         const uint32_t cnt = (uint32_t)std::min<uint64_t>(K3_PIPE_QUERIES, nt - base);
@@ -872,29 +1090,14 @@ int GpuFlatIndex::search_batch_locked(const double* queries, uint64_t nq, uint64
                                          (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_, ws->k3_h_result));
         }
         VL_HIP(hipStreamSynchronize(st));
-        if (prof) {  // (the events bracket the one scan launch: `passes` slab passes side by side)
-            float ms = 0.f;
-            VL_HIP(hipEventElapsedTime(&ms, ws->ev0, ws->ev1));
-            std::lock_guard<std::mutex> gl(prof_mu_);
-            prof_n_ += passes;
-            prof_ms_ += ms;
-            prof_bytes_ += (uint64_t)passes * n * (uint64_t)ld_ * sizeof(float);
-        }
+        // (the events bracket the one scan launch: `passes` slab passes side by side)
+        if (prof) VL_TRY(account_profile(ws, (uint64_t)passes * n * (uint64_t)ld_ * sizeof(float), passes));
         for (uint32_t j = 0; j < cnt; ++j) {
             const uint64_t qi = todo[base + j];
             const SearchResultBlock& r = ws->k3_h_result[j];  // (a fallback below uses the workspace's other buffers, not these)
             const bool ok = in_domain[j] && !(r.flags & RESULT_NEEDS_EXACT) && r.n_out == k_eff;
             if (ok) {
-                for (uint64_t i = 0; i < k_eff; ++i) {
-                    const uint32_t p = r.pos[i];
-                    if (p >= n) {
-                        set_last_error("batch fast path returned an out-of-range position (kernel bug)");
-                        return ERR_DEVICE;
-                    }
-                    if (out_pos) out_pos[qi * k + i] = p;
-                    if (out_ids) out_ids[qi * k + i] = ids_[p];
-                    out_scores[qi * k + i] = r.score[i];
-                }
+                VL_TRY(deliver("batch fast path", ids_, &r, k_eff, out_at(out_pos, qi), out_at(out_ids, qi), out_scores + qi * k));
                 out_n[qi] = k_eff;
             } else {
                 VL_TRY(single(qi, true));
@@ -962,20 +1165,7 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
     };
     const uint64_t n_answer = mmr ? mmr->k_out : k_eff;  // what a certified block's n_out says
 
-    // stage the query in the pinned block: the f64 values, then the norm
-    double qq = 0.0, qmax = 0.0;
-    bool q_finite = true;
-    for (uint64_t i = 0; i < dim_; ++i) {
-        const double v = query[i];
-        ws->h_q64[i] = v;
-        qq += v * v;
-        const double av = std::fabs(v);
-        if (!(av <= 1.797693134862315708e308)) q_finite = false;
-        if (av > qmax) qmax = av;
-    }
-    const double q_norm = std::sqrt(qq);
-    const bool q_in_domain = q_finite && qmax <= DOMAIN_MAX_ABS && (q_norm == 0.0 || q_norm >= DOMAIN_MIN_NORM);
-    ws->h_q64[dim_] = q_norm;
+    const bool q_in_domain = stage_single_query(ws, query, dim_).in_domain;
     // The f32 scan takes its query in the kernel arguments and the finalize kernel reads the pinned block itself,
     // so the common case needs NO copy in front of the kernels.  Every other kernel (bf16 filter, the k > 60 lists,
     // the exact scan: all workgroups read the query) wants it in device memory: copied on first use.
@@ -998,17 +1188,7 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
             set_last_path(PATH_FAST);
             return mmr_take(ws, *mmr, out_pos, out_ids, out_scores, out_n);
         }
-        const SearchResultBlock& r = *ws->h_result;
-        for (uint64_t i = 0; i < k_eff; ++i) {
-            const uint32_t p = r.pos[i];
-            if (p >= n) {
-                set_last_error(std::string(what) + " returned an out-of-range position (kernel bug)");
-                return ERR_DEVICE;
-            }
-            if (out_pos) out_pos[i] = p;
-            if (out_ids) out_ids[i] = ids_[p];
-            out_scores[i] = r.score[i];
-        }
+        VL_TRY(deliver(what, ids_, ws->h_result, k_eff, out_pos, out_ids, out_scores));
         *out_n = k_eff;
         set_last_path(PATH_FAST);
         return OK;
@@ -1032,9 +1212,7 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
         const uint32_t ldb = mfma_ldb((uint32_t)dim_);
         I8Query q8;
         prepare_i8_query(query, (uint32_t)dim_, &q8);
-        uint32_t seq = ++ws->seq;
-        if (seq == 0) seq = ++ws->seq;
-        ws->h_result->seq = 0;
+        const uint32_t seq = next_stamp(ws);
         int grid = 0, variant = 0;
         if (prof) VL_HIP(hipEventRecord(ws->ev0, st));
         VL_HIP(launch_scan_i8(st, metric, d_slab8_, d_sr8_, d_norm8_, q8, n, (uint32_t)dim_, ws->d_partials, &grid, &variant));
@@ -1043,24 +1221,10 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
         VL_HIP(launch_merge_finalize(st, mmr ? 0u : seq, metric, ws->d_partials, grid, d_master_, ws->h_q64, ws->h_q64 + dim_,
                                      (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_, fin_out, IN_EXTRA_I8_SINGLE));
         VL_TRY(mmr_from_blocks(seq));
-        last_scan_variant_.store(variant, std::memory_order_relaxed);
-        last_scan_grid_.store(grid, std::memory_order_relaxed);
-        last_scan_qarg_.store(1, std::memory_order_relaxed);
+        note_scan(variant, grid, true);
         VL_TRY(wait_result(ws, seq));
-        if (prof) {
-            float ms = 0.f;
-            hipError_t pe = hipEventElapsedTime(&ms, ws->ev0, ws->ev1);
-            if (pe == hipErrorNotReady) {
-                VL_HIP(hipEventSynchronize(ws->ev1));
-                pe = hipEventElapsedTime(&ms, ws->ev0, ws->ev1);
-            }
-            VL_HIP(pe);
-            std::lock_guard<std::mutex> g(prof_mu_);
-            prof_n_ += 1;
-            prof_ms_ += ms;
-            // the rows plus the per-row (s, r) pair, and |row| for dot
-            prof_bytes_ += n * ((uint64_t)ldb + 2 * sizeof(float) + (metric == DOT ? sizeof(float) : 0));
-        }
+        // the rows plus the per-row (s, r) pair, and |row| for dot
+        if (prof) VL_TRY(account_profile(ws, n * ((uint64_t)ldb + 2 * sizeof(float) + (metric == DOT ? sizeof(float) : 0))));
         const SearchResultBlock& r = *ws->h_result;
         const bool certified = !(r.flags & RESULT_NEEDS_EXACT) && r.n_out == n_answer;
         i8_outcome(certified);
@@ -1083,37 +1247,20 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
     if (bf16_stage) {
         const bool prof = profile_.load();
         const uint32_t ldb = mfma_ldb((uint32_t)dim_);
-        if (ws->q32.size() < ldb) ws->q32.assign(ldb, 0.0f);  // columns past dim_ stay zero
-        for (uint64_t i = 0; i < dim_; ++i) ws->q32[i] = (float)query[i];  // nearest even, like the kernel's own rounding
-        uint32_t seq = ++ws->seq;
-        if (seq == 0) seq = ++ws->seq;
-        ws->h_result->seq = 0;
+        const float* q32 = stage_q32(ws, query, dim_, ldb);  // (nearest even is the kernel's own rounding too)
+        const uint32_t seq = next_stamp(ws);
         int grid = 0, variant = 0;
         if (prof) VL_HIP(hipEventRecord(ws->ev0, st));
         VL_HIP(launch_scan_bf16(st, metric, d_slab16_, d_norm16_, d_sqnorm_, nullptr, n, (uint32_t)dim_, ws->d_partials,
-                                &grid, ws->q32.data(), &variant));
+                                &grid, q32, &variant));
         if (prof) VL_HIP(hipEventRecord(ws->ev1, st));
         // rows are rounded to bf16, the query is f32 (mfma_scan.hpp)
         VL_HIP(launch_merge_finalize(st, mmr ? 0u : seq, metric, ws->d_partials, grid, d_master_, ws->h_q64, ws->h_q64 + dim_,
                                      (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_, fin_out, IN_EXTRA_BF16_SINGLE));
         VL_TRY(mmr_from_blocks(seq));
-        last_scan_variant_.store(variant, std::memory_order_relaxed);
-        last_scan_grid_.store(grid, std::memory_order_relaxed);
-        last_scan_qarg_.store(1, std::memory_order_relaxed);
+        note_scan(variant, grid, true);
         VL_TRY(wait_result(ws, seq));
-        if (prof) {
-            float ms = 0.f;
-            hipError_t pe = hipEventElapsedTime(&ms, ws->ev0, ws->ev1);
-            if (pe == hipErrorNotReady) {
-                VL_HIP(hipEventSynchronize(ws->ev1));
-                pe = hipEventElapsedTime(&ms, ws->ev0, ws->ev1);
-            }
-            VL_HIP(pe);
-            std::lock_guard<std::mutex> g(prof_mu_);
-            prof_n_ += 1;
-            prof_ms_ += ms;
-            prof_bytes_ += n * (uint64_t)ldb * 2;
-        }
+        if (prof) VL_TRY(account_profile(ws, n * (uint64_t)ldb * 2));
         const SearchResultBlock& r = *ws->h_result;
         const bool certified = !(r.flags & RESULT_NEEDS_EXACT) && r.n_out == n_answer;
         bf16_outcome(certified);
@@ -1126,58 +1273,21 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
         // the f64 query from the pinned block, writes the result block into pinned memory and stamps it; the host
         // waits for the stamp, not for the stream
         const bool qarg = scan_takes_qarg(ld_);
-        const float* q32 = nullptr;
-        if (qarg) {
-            if (ws->q32.size() < ld_) ws->q32.assign(ld_, 0.0f);
-            for (uint64_t i = 0; i < dim_; ++i) ws->q32[i] = (float)query[i];  // nearest even, like load_q4 on the device
-            q32 = ws->q32.data();
-        } else {
-            VL_TRY(q_to_device());
-        }
+        const float* q32 = qarg ? stage_q32(ws, query, dim_, ld_) : nullptr;
+        if (!qarg) VL_TRY(q_to_device());
         const double* fq = q_on_device ? ws->d_q64 : ws->h_q64;
-        uint32_t seq = ++ws->seq;
-        if (seq == 0) seq = ++ws->seq;
-        ws->h_result->seq = 0;
+        const uint32_t seq = next_stamp(ws);
         if (prof) VL_HIP(hipEventRecord(ws->ev0, st));
         VL_HIP(launch_scan(st, metric, d_slab_, d_inv_norm_, ws->d_q64, n, (uint32_t)dim_, ld_, ws->d_partials, &plan, q32));
         if (prof) VL_HIP(hipEventRecord(ws->ev1, st));
         VL_HIP(launch_merge_finalize(st, metric, ws->d_partials, plan.grid, 1, d_master_, fq, fq + dim_, (uint32_t)dim_, n,
                                      (uint32_t)k_eff, max_row_norm_, fin_out, 0.0, mmr ? 0u : seq));
         VL_TRY(mmr_from_blocks(seq));
-        last_scan_variant_.store(plan.variant, std::memory_order_relaxed);
-        last_scan_grid_.store(plan.grid, std::memory_order_relaxed);
-        last_scan_qarg_.store(qarg ? 1 : 0, std::memory_order_relaxed);
+        note_scan(plan.variant, plan.grid, qarg);
         VL_TRY(wait_result(ws, seq));
-        if (prof) {
-            float ms = 0.f;
-            hipError_t pe = hipEventElapsedTime(&ms, ws->ev0, ws->ev1);
-            if (pe == hipErrorNotReady) {
-                VL_HIP(hipEventSynchronize(ws->ev1));
-                pe = hipEventElapsedTime(&ms, ws->ev0, ws->ev1);
-            }
-            VL_HIP(pe);
-            std::lock_guard<std::mutex> g(prof_mu_);
-            prof_n_ += 1;
-            prof_ms_ += ms;
-            prof_bytes_ += n * (uint64_t)ld_ * sizeof(float);
-        }
+        if (prof) VL_TRY(account_profile(ws, n * (uint64_t)ld_ * sizeof(float)));
         const SearchResultBlock& r = *ws->h_result;
-        if (!(r.flags & RESULT_NEEDS_EXACT) && r.n_out == n_answer) {
-            if (mmr) return take_result("fast path");
-            for (uint64_t i = 0; i < k_eff; ++i) {
-                const uint32_t p = r.pos[i];
-                if (p >= n) {
-                    set_last_error("fast path returned an out-of-range position (kernel bug)");
-                    return ERR_DEVICE;
-                }
-                if (out_pos) out_pos[i] = p;
-                if (out_ids) out_ids[i] = ids_[p];
-                out_scores[i] = r.score[i];
-            }
-            *out_n = k_eff;
-            set_last_path(PATH_FAST);
-            return OK;
-        }
+        if (!(r.flags & RESULT_NEEDS_EXACT) && r.n_out == n_answer) return take_result("fast path");
         // ties at the cut or a failed bound: fall through to the exact kernels
     }
 
@@ -1197,22 +1307,7 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
             VL_TRY(mmr_from_blocks(0));
             VL_HIP(hipStreamSynchronize(st));
             const SearchResultBlock& r0 = ws->h_result[0];
-            if (!(r0.flags & RESULT_NEEDS_EXACT) && r0.n_out == n_answer) {
-                if (mmr) return take_result("multi-list fast path");
-                for (uint64_t i = 0; i < k_eff; ++i) {
-                    const uint32_t p = ws->h_result[i / KP].pos[i % KP];
-                    if (p >= n) {
-                        set_last_error("multi-list fast path returned an out-of-range position (kernel bug)");
-                        return ERR_DEVICE;
-                    }
-                    if (out_pos) out_pos[i] = p;
-                    if (out_ids) out_ids[i] = ids_[p];
-                    out_scores[i] = ws->h_result[i / KP].score[i % KP];
-                }
-                *out_n = k_eff;
-                set_last_path(PATH_FAST);
-                return OK;
-            }
+            if (!(r0.flags & RESULT_NEEDS_EXACT) && r0.n_out == n_answer) return take_result("multi-list fast path");
         } else {
             VL_HIP(hipStreamSynchronize(st));
         }
@@ -1223,15 +1318,7 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
     VL_TRY(q_to_device());
     VL_TRY(run_exact(ws, metric, n, k_eff, &pos, &scores, nullptr, mmr));
     if (mmr) return mmr_take(ws, *mmr, out_pos, out_ids, out_scores, out_n);
-    for (uint64_t i = 0; i < k_eff; ++i) {
-        if (pos[i] >= n) {
-            set_last_error("exact path returned an out-of-range position (kernel bug)");
-            return ERR_DEVICE;
-        }
-        if (out_pos) out_pos[i] = pos[i];
-        if (out_ids) out_ids[i] = ids_[pos[i]];
-        out_scores[i] = scores[i];
-    }
+    VL_TRY(deliver("exact path", ids_, pos.data(), scores.data(), k_eff, out_pos, out_ids, out_scores));
     *out_n = k_eff;
     return OK;
 }
@@ -1282,14 +1369,7 @@ int GpuFlatIndex::run_exact(Workspace* ws, int metric, uint64_t n, uint64_t k_ef
         src.n = (uint32_t)k_eff;
         return mmr_tail(ws, metric, *mmr, src, 0);
     };
-    if (ws->scores_cap < n) {
-        if (ws->d_scores) (void)hipFree(ws->d_scores);
-        ws->d_scores = nullptr;
-        ws->scores_cap = 0;
-        const size_t cap = std::max<size_t>(n, 1024);
-        VL_TRY(dev_alloc(&ws->d_scores, cap));
-        ws->scores_cap = cap;
-    }
+    VL_TRY(ensure_scores(ws, n));
     VL_HIP(hipMemsetAsync(ws->d_nan, 0, sizeof(uint32_t), st));
     if (plist)
         VL_HIP(launch_exact_scan_subset(st, metric, d_master_, ws->d_q64, plist, n, (uint32_t)dim_, ws->d_scores, ws->d_nan));
@@ -1331,26 +1411,8 @@ int GpuFlatIndex::run_exact(Workspace* ws, int metric, uint64_t n, uint64_t k_ef
         VL_HIP(hipStreamSynchronize(st));
     } else {
         const uint64_t cap = sort_capacity_for(n);
-        if (ws->sort_cap < cap) {
-            if (ws->d_okeys) (void)hipFree(ws->d_okeys);
-            if (ws->d_opos) (void)hipFree(ws->d_opos);
-            ws->d_okeys = nullptr;
-            ws->d_opos = nullptr;
-            ws->sort_cap = 0;
-            VL_TRY(dev_alloc(&ws->d_okeys, cap));
-            VL_TRY(dev_alloc(&ws->d_opos, cap));
-            ws->sort_cap = cap;
-        }
-        if (ws->out_cap < k_eff) {
-            if (ws->d_out_pos) (void)hipFree(ws->d_out_pos);
-            if (ws->d_out_scores) (void)hipFree(ws->d_out_scores);
-            ws->d_out_pos = nullptr;
-            ws->d_out_scores = nullptr;
-            ws->out_cap = 0;
-            VL_TRY(dev_alloc(&ws->d_out_pos, k_eff));
-            VL_TRY(dev_alloc(&ws->d_out_scores, k_eff));
-            ws->out_cap = k_eff;
-        }
+        VL_TRY(grow(HipMem{}, ws->sort_cap, cap, {dev_buf(ws->d_okeys, cap), dev_buf(ws->d_opos, cap)}));
+        VL_TRY(ensure_out(ws, k_eff));
         VL_HIP(launch_exact_sort(st, ws->d_scores, n, k_eff, ws->d_okeys, ws->d_opos, ws->d_out_pos,
                                  ws->d_out_scores));
         if (mmr) {
@@ -1411,11 +1473,9 @@ namespace {
 std::atomic<uint64_t> g_next_filter_token{1};  // process-wide: a token is never 0 and never handed out twice
 }  // namespace
 
-std::shared_ptr<IdFilter> GpuFlatIndex::find_filter(uint64_t token) const
+int GpuFlatIndex::find_filter(uint64_t token, std::shared_ptr<IdFilter>* out) const
 {
-    std::lock_guard<std::mutex> g(filters_mu_);
-    auto it = filters_.find(token);
-    return it == filters_.end() ? nullptr : it->second;
+    return token_find(filters_mu_, filters_, token, UNKNOWN_FILTER, out);
 }
 
 int GpuFlatIndex::filter_create(const uint64_t* ids, uint64_t n_ids, uint64_t* out_token, uint64_t* out_rows)
@@ -1441,12 +1501,9 @@ int GpuFlatIndex::filter_create(const uint64_t* ids, uint64_t n_ids, uint64_t* o
     {
         std::shared_lock<RwLock> lk(mu_);
         std::lock_guard<std::mutex> fg(f->mu);
-        Workspace* ws = acquire_ws();
-        if (!ws) return ERR_DEVICE;
-        const int rc = resolve_filter(ws, f.get());
-        if (rc != OK) (void)hipStreamSynchronize(ws->stream);
-        release_ws(ws);
-        if (rc != OK) return rc;
+        WsLease lease(this);
+        if (lease.status() != OK) return lease.status();
+        VL_TRY(lease.done(resolve_filter(lease.ws, f.get())));
         rows = f->m;
     }
     const uint64_t token = g_next_filter_token.fetch_add(1);
@@ -1462,37 +1519,20 @@ int GpuFlatIndex::filter_create(const uint64_t* ids, uint64_t n_ids, uint64_t* o
 int GpuFlatIndex::filter_destroy(uint64_t token)
 {
     std::shared_ptr<IdFilter> f;  // a search still using it holds its own reference: freed when that one ends
-    {
-        std::lock_guard<std::mutex> g(filters_mu_);
-        auto it = filters_.find(token);
-        if (it == filters_.end()) {
-            set_last_error("unknown or destroyed filter");
-            return ERR_INVALID_ARG;
-        }
-        f = std::move(it->second);
-        filters_.erase(it);
-    }
-    return OK;
+    return token_take(filters_mu_, filters_, token, UNKNOWN_FILTER, &f);
 }
 
 int GpuFlatIndex::filter_rows(uint64_t token, uint64_t* out_rows) const
 {
     if (!out_rows) return ERR_INVALID_ARG;
-    std::shared_ptr<IdFilter> f = find_filter(token);
-    if (!f) {
-        set_last_error("unknown or destroyed filter");
-        return ERR_INVALID_ARG;
-    }
+    std::shared_ptr<IdFilter> f;
+    VL_TRY(find_filter(token, &f));
     std::shared_lock<RwLock> lk(mu_);
     std::lock_guard<std::mutex> fg(f->mu);
     if (f->resolved_at != mutations_) {
-        VL_HIP(hipSetDevice(device_));
-        Workspace* ws = acquire_ws();
-        if (!ws) return ERR_DEVICE;
-        const int rc = resolve_filter(ws, f.get());
-        if (rc != OK) (void)hipStreamSynchronize(ws->stream);
-        release_ws(ws);
-        if (rc != OK) return rc;
+        WsLease lease(this);
+        if (lease.status() != OK) return lease.status();
+        VL_TRY(lease.done(resolve_filter(lease.ws, f.get())));
     }
     *out_rows = f->m;
     return OK;
@@ -1517,13 +1557,7 @@ int GpuFlatIndex::resolve_filter(Workspace* ws, IdFilter* f) const
             set_last_error("filter resolution counted more rows than the index holds (kernel bug)");
             return ERR_DEVICE;
         }
-        if (m > f->plist_cap) {
-            if (f->d_plist) (void)hipFree(f->d_plist);
-            f->d_plist = nullptr;
-            f->plist_cap = 0;
-            VL_TRY(dev_alloc(&f->d_plist, m));
-            f->plist_cap = m;
-        }
+        VL_TRY(grow(HipMem{}, f->plist_cap, m, {dev_buf(f->d_plist, m)}));
         if (m) {
             VL_HIP(launch_filter_compact(st, d_ids_, n, f->d_ids, f->ids.size(), f->d_counts, m, f->d_plist));
             VL_HIP(hipStreamSynchronize(st));
@@ -1539,68 +1573,28 @@ int GpuFlatIndex::search_filtered(uint64_t token, const double* query, uint64_t 
 {
     if (!out_n) return ERR_INVALID_ARG;
     *out_n = 0;
-    std::shared_ptr<IdFilter> f = find_filter(token);
-    if (!f) {
-        set_last_error("unknown or destroyed filter");
-        return ERR_INVALID_ARG;
-    }
-    if (metric < 0 || metric > 3) {
-        set_last_error("unknown metric");
-        return ERR_INVALID_ARG;
-    }
-    std::shared_lock<RwLock> lk(mu_);  // readers share it; every writer waits: the resolved list cannot move under the search
-    const uint64_t n = ids_.size();
-    if (n != 0 && q_len != dim_) {  // the whole index's check, even when the subset is empty
-        set_dim_mismatch(dim_, q_len);
-        set_last_error("Dimension mismatch: expected " + std::to_string(dim_) + ", got " + std::to_string(q_len));
-        return ERR_DIM_MISMATCH;
-    }
-    if (n == 0 || k == 0) return OK;
+    std::shared_ptr<IdFilter> f;
+    VL_TRY(find_filter(token, &f));
+    std::shared_lock<RwLock> lk;
+    VL_TRY(lock_for_query(metric, q_len, &lk));  // the whole index's length check, even when the subset is empty
+    if (ids_.empty() || k == 0) return OK;
     if ((!query && dim_) || !out_scores) return ERR_INVALID_ARG;
-
-    VL_HIP(hipSetDevice(device_));
-    Workspace* ws = acquire_ws();
-    if (!ws) return ERR_DEVICE;
-    int rc = OK;
-    {
-        std::lock_guard<std::mutex> fg(f->mu);
-        if (f->resolved_at != mutations_) rc = resolve_filter(ws, f.get());
-    }
-    // from here on the list is read only: a reader that finds it current leaves it alone, and writers are shut out
-    if (rc == OK && f->m != 0) {
-        active_searches_.fetch_add(1, std::memory_order_relaxed);
-        rc = search_subset(ws, f.get(), query, std::min<uint64_t>(k, f->m), metric, out_pos, out_ids, out_scores, out_n);
-        active_searches_.fetch_sub(1, std::memory_order_relaxed);
-    }
-    if (rc != OK) (void)hipStreamSynchronize(ws->stream);
-    release_ws(ws);
-    return rc;
+    return run_search(nullptr, f.get(), [&](Workspace* ws) -> int {
+        if (f->m == 0) return OK;
+        return search_subset(ws, f.get(), query, std::min<uint64_t>(k, f->m), metric, out_pos, out_ids, out_scores, out_n);
+    });
 }
 
 int GpuFlatIndex::search_subset(Workspace* ws, IdFilter* f, const double* query, uint64_t k_eff, int metric,
                                 uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
                                 const MmrReq* mmr) const
 {
-    const uint64_t n = ids_.size();
     const uint64_t m = f->m;
     const uint32_t* plist = f->d_plist;
     hipStream_t st = ws->stream;
     const uint64_t n_answer = mmr ? mmr->k_out : k_eff;  // (search_locked's protocol for a diversified search)
 
-    // the query staged as search_locked stages it: pinned f64 values, then the norm
-    double qq = 0.0, qmax = 0.0;
-    bool q_finite = true;
-    for (uint64_t i = 0; i < dim_; ++i) {
-        const double v = query[i];
-        ws->h_q64[i] = v;
-        qq += v * v;
-        const double av = std::fabs(v);
-        if (!(av <= 1.797693134862315708e308)) q_finite = false;
-        if (av > qmax) qmax = av;
-    }
-    const double q_norm = std::sqrt(qq);
-    const bool q_in_domain = q_finite && qmax <= DOMAIN_MAX_ABS && (q_norm == 0.0 || q_norm >= DOMAIN_MIN_NORM);
-    ws->h_q64[dim_] = q_norm;
+    const bool q_in_domain = stage_single_query(ws, query, dim_).in_domain;
     bool q_on_device = false;
     auto q_to_device = [&]() -> int {
         if (!q_on_device) {
@@ -1616,18 +1610,10 @@ int GpuFlatIndex::search_subset(Workspace* ws, IdFilter* f, const double* query,
         const bool prof = profile_.load();
         ScanPlan plan;
         const bool qarg = scan_subset_takes_qarg(ld_);
-        const float* q32 = nullptr;
-        if (qarg) {
-            if (ws->q32.size() < ld_) ws->q32.assign(ld_, 0.0f);
-            for (uint64_t i = 0; i < dim_; ++i) ws->q32[i] = (float)query[i];  // nearest even, like load_q4 on the device
-            q32 = ws->q32.data();
-        } else {
-            VL_TRY(q_to_device());
-        }
+        const float* q32 = qarg ? stage_q32(ws, query, dim_, ld_) : nullptr;
+        if (!qarg) VL_TRY(q_to_device());
         const double* fq = q_on_device ? ws->d_q64 : ws->h_q64;
-        uint32_t seq = ++ws->seq;
-        if (seq == 0) seq = ++ws->seq;
-        ws->h_result->seq = 0;
+        const uint32_t seq = next_stamp(ws);
         if (prof) VL_HIP(hipEventRecord(ws->ev0, st));
         VL_HIP(launch_scan_subset(st, metric, d_slab_, d_inv_norm_, plist, m, ws->d_q64, (uint32_t)dim_, ld_, ws->d_partials,
                                   &plan, q32));
@@ -1643,40 +1629,17 @@ int GpuFlatIndex::search_subset(Workspace* ws, IdFilter* f, const double* query,
             src.n_block0 = (uint32_t)k_eff;
             VL_TRY(mmr_tail(ws, metric, *mmr, src, seq));
         }
-        last_scan_variant_.store(plan.variant, std::memory_order_relaxed);
-        last_scan_grid_.store(plan.grid, std::memory_order_relaxed);
-        last_scan_qarg_.store(qarg ? 1 : 0, std::memory_order_relaxed);
+        note_scan(plan.variant, plan.grid, qarg);
         VL_TRY(wait_result(ws, seq));
-        if (prof) {
-            float ms = 0.f;
-            hipError_t pe = hipEventElapsedTime(&ms, ws->ev0, ws->ev1);
-            if (pe == hipErrorNotReady) {
-                VL_HIP(hipEventSynchronize(ws->ev1));
-                pe = hipEventElapsedTime(&ms, ws->ev0, ws->ev1);
-            }
-            VL_HIP(pe);
-            std::lock_guard<std::mutex> g(prof_mu_);
-            prof_n_ += 1;
-            prof_ms_ += ms;
-            // the rows read, the position list, and 1/|row| for cosine
-            prof_bytes_ += m * ((uint64_t)ld_ * sizeof(float) + sizeof(uint32_t) + (metric == COSINE ? sizeof(float) : 0));
-        }
+        // the rows read, the position list, and 1/|row| for cosine
+        if (prof) VL_TRY(account_profile(ws, m * ((uint64_t)ld_ * sizeof(float) + sizeof(uint32_t) + (metric == COSINE ? sizeof(float) : 0))));
         const SearchResultBlock& r = *ws->h_result;
         if (!(r.flags & RESULT_NEEDS_EXACT) && r.n_out == n_answer) {
             if (mmr) {
                 set_last_path(PATH_FAST);
                 return mmr_take(ws, *mmr, out_pos, out_ids, out_scores, out_n);
             }
-            for (uint64_t i = 0; i < k_eff; ++i) {
-                const uint32_t p = r.pos[i];
-                if (p >= n) {
-                    set_last_error("filtered fast path returned an out-of-range position (kernel bug)");
-                    return ERR_DEVICE;
-                }
-                if (out_pos) out_pos[i] = p;
-                if (out_ids) out_ids[i] = ids_[p];
-                out_scores[i] = r.score[i];
-            }
+            VL_TRY(deliver("filtered fast path", ids_, &r, k_eff, out_pos, out_ids, out_scores));
             *out_n = k_eff;
             set_last_path(PATH_FAST);
             return OK;
@@ -1698,16 +1661,8 @@ int GpuFlatIndex::search_subset(Workspace* ws, IdFilter* f, const double* query,
             f->h_plist_valid = true;
         }
     }
-    for (uint64_t i = 0; i < k_eff; ++i) {
-        const uint32_t p = idx[i] < m ? f->h_plist[idx[i]] : POS_SENTINEL;
-        if (p >= n) {
-            set_last_error("filtered exact path returned an out-of-range position (kernel bug)");
-            return ERR_DEVICE;
-        }
-        if (out_pos) out_pos[i] = p;
-        if (out_ids) out_ids[i] = ids_[p];
-        out_scores[i] = scores[i];
-    }
+    auto storage_pos = [&](uint64_t i) { return idx[i] < m ? f->h_plist[idx[i]] : POS_SENTINEL; };
+    VL_TRY(deliver("filtered exact path", ids_, k_eff, storage_pos, [&](uint64_t i) { return scores[i]; }, out_pos, out_ids, out_scores));
     *out_n = k_eff;
     return OK;
 }
@@ -1730,21 +1685,11 @@ int GpuFlatIndex::mmr_tail(Workspace* ws, int metric, const MmrReq& m, MmrSource
 int GpuFlatIndex::mmr_take(Workspace* ws, const MmrReq& m, uint64_t* out_pos, uint64_t* out_ids, double* out_scores,
                            uint64_t* out_n) const
 {
-    const uint64_t n = ids_.size();
     if (ws->h_result[0].flags != 0u || ws->h_result[0].n_out != m.k_out) {
         set_last_error("the selection kernel did not take the search's candidates (kernel bug)");
         return ERR_DEVICE;
     }
-    for (uint64_t i = 0; i < m.k_out; ++i) {
-        const uint32_t p = ws->h_result[i / KP].pos[i % KP];
-        if (p >= n) {
-            set_last_error("diversified search returned an out-of-range position (kernel bug)");
-            return ERR_DEVICE;
-        }
-        if (out_pos) out_pos[i] = p;
-        if (out_ids) out_ids[i] = ids_[p];
-        out_scores[i] = ws->h_result[i / KP].score[i % KP];
-    }
+    VL_TRY(deliver("diversified search", ids_, ws->h_result, m.k_out, out_pos, out_ids, out_scores));
     *out_n = m.k_out;
     return OK;
 }
@@ -1755,68 +1700,39 @@ int GpuFlatIndex::search_mmr(uint64_t token, const double* query, uint64_t q_len
 {
     if (!out_n) return ERR_INVALID_ARG;
     *out_n = 0;
-    const int arc = mmr_check_args(k, fetch_k, lambda);
-    if (arc != OK) return arc;
+    VL_TRY(mmr_check_args(k, fetch_k, lambda));
     std::shared_ptr<IdFilter> f;
-    if (token != 0) {
-        f = find_filter(token);
-        if (!f) {
-            set_last_error("unknown or destroyed filter");
-            return ERR_INVALID_ARG;
-        }
-    }
-    if (metric < 0 || metric > 3) {
-        set_last_error("unknown metric");
-        return ERR_INVALID_ARG;
-    }
-    std::shared_lock<RwLock> lk(mu_);  // held from the search to the selection: positions cannot move in between
+    if (token != 0) VL_TRY(find_filter(token, &f));
+    std::shared_lock<RwLock> lk;  // held from the search to the selection: positions cannot move in between
+    VL_TRY(lock_for_query(metric, q_len, &lk));
     const uint64_t n = ids_.size();
-    if (n != 0 && q_len != dim_) {  // the whole index's check, as in search
-        set_dim_mismatch(dim_, q_len);
-        set_last_error("Dimension mismatch: expected " + std::to_string(dim_) + ", got " + std::to_string(q_len));
-        return ERR_DIM_MISMATCH;
-    }
     const uint64_t k_cap = std::min<uint64_t>(k, out_capacity);  // a smaller k's answer is a prefix
     if (n == 0 || k_cap == 0) return OK;
     if ((!query && dim_) || !out_scores) return ERR_INVALID_ARG;
-
-    VL_HIP(hipSetDevice(device_));
-    Workspace* ws = acquire_ws();
-    if (!ws) return ERR_DEVICE;
-    int rc = OK;
-    if (f) {
-        std::lock_guard<std::mutex> fg(f->mu);
-        if (f->resolved_at != mutations_) rc = resolve_filter(ws, f.get());
-    }
-    const uint64_t rows = f ? f->m : n;
-    if (rc == OK && rows != 0) {
+    return run_search(nullptr, f.get(), [&](Workspace* ws) -> int {
+        const uint64_t rows = f ? f->m : n;
+        if (rows == 0) return OK;
         const uint64_t fetch_eff = std::min<uint64_t>(fetch_k, rows);
         const MmrReq req{std::min<uint64_t>(k_cap, fetch_eff), lambda};
-        active_searches_.fetch_add(1, std::memory_order_relaxed);
         if (req.k_out == 1) {
             // sel = [0]: the best of search(q, fetch_k), whose errors are this call's
             std::vector<uint64_t> pos(fetch_eff), ids(fetch_eff);
             std::vector<double> scores(fetch_eff);
             uint64_t got = 0;
-            rc = f ? search_subset(ws, f.get(), query, fetch_eff, metric, pos.data(), ids.data(), scores.data(), &got)
-                   : search_locked(ws, query, fetch_eff, metric, pos.data(), ids.data(), scores.data(), &got, false);
-            if (rc == OK && got >= 1) {
+            VL_TRY(f ? search_subset(ws, f.get(), query, fetch_eff, metric, pos.data(), ids.data(), scores.data(), &got)
+                     : search_locked(ws, query, fetch_eff, metric, pos.data(), ids.data(), scores.data(), &got, false));
+            if (got >= 1) {
                 if (out_pos) out_pos[0] = pos[0];
                 if (out_ids) out_ids[0] = ids[0];
                 out_scores[0] = scores[0];
                 *out_n = 1;
             }
-        } else {
-            if (!ws->mmr_sim) rc = dev_alloc(&ws->mmr_sim, (size_t)MMR_MAX_FETCH * MMR_MAX_FETCH);
-            if (rc == OK)
-                rc = f ? search_subset(ws, f.get(), query, fetch_eff, metric, out_pos, out_ids, out_scores, out_n, &req)
-                       : search_locked(ws, query, fetch_eff, metric, out_pos, out_ids, out_scores, out_n, false, false, &req);
+            return OK;
         }
-        active_searches_.fetch_sub(1, std::memory_order_relaxed);
-    }
-    if (rc != OK) (void)hipStreamSynchronize(ws->stream);
-    release_ws(ws);
-    return rc;
+        if (!ws->mmr_sim) VL_TRY(dev_alloc(&ws->mmr_sim, (size_t)MMR_MAX_FETCH * MMR_MAX_FETCH));
+        return f ? search_subset(ws, f.get(), query, fetch_eff, metric, out_pos, out_ids, out_scores, out_n, &req)
+                 : search_locked(ws, query, fetch_eff, metric, out_pos, out_ids, out_scores, out_n, false, false, &req);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1839,37 +1755,6 @@ uint32_t range_candidate_capacity()
 }
 }  // namespace
 
-int GpuFlatIndex::ensure_range_ws(Workspace* ws, uint64_t sort_cap, uint64_t out_cap) const
-{
-    if (!ws->rg_ctr) {
-        VL_TRY(dev_alloc(&ws->rg_ctr, (size_t)RANGE_CTR_WORDS));
-        VL_TRY(pinned_alloc(&ws->rg_h_ctr, (size_t)RANGE_CTR_WORDS));
-        VL_TRY(pinned_alloc(&ws->rg_h_pos, (size_t)RANGE_SMALL));
-        VL_TRY(pinned_alloc(&ws->rg_h_scores, (size_t)RANGE_SMALL));
-    }
-    if (ws->rg_sort_cap < sort_cap) {
-        if (ws->rg_keys) (void)hipFree(ws->rg_keys);
-        if (ws->rg_pv) (void)hipFree(ws->rg_pv);
-        ws->rg_keys = nullptr;
-        ws->rg_pv = nullptr;
-        ws->rg_sort_cap = 0;
-        VL_TRY(dev_alloc(&ws->rg_keys, sort_cap));
-        VL_TRY(dev_alloc(&ws->rg_pv, sort_cap));
-        ws->rg_sort_cap = sort_cap;
-    }
-    if (ws->out_cap < out_cap) {
-        if (ws->d_out_pos) (void)hipFree(ws->d_out_pos);
-        if (ws->d_out_scores) (void)hipFree(ws->d_out_scores);
-        ws->d_out_pos = nullptr;
-        ws->d_out_scores = nullptr;
-        ws->out_cap = 0;
-        VL_TRY(dev_alloc(&ws->d_out_pos, out_cap));
-        VL_TRY(dev_alloc(&ws->d_out_scores, out_cap));
-        ws->out_cap = out_cap;
-    }
-    return OK;
-}
-
 int GpuFlatIndex::search_range(uint64_t token, const double* query, uint64_t q_len, double min_score, int metric,
                                uint64_t out_capacity, uint64_t* out_pos, uint64_t* out_ids, double* out_scores,
                                uint64_t* out_n, uint64_t* out_total) const
@@ -1878,48 +1763,19 @@ int GpuFlatIndex::search_range(uint64_t token, const double* query, uint64_t q_l
     *out_n = 0;
     *out_total = 0;
     std::shared_ptr<IdFilter> f;
-    if (token != 0) {
-        f = find_filter(token);
-        if (!f) {
-            set_last_error("unknown or destroyed filter");
-            return ERR_INVALID_ARG;
-        }
-    }
-    if (metric < 0 || metric > 3) {
-        set_last_error("unknown metric");
-        return ERR_INVALID_ARG;
-    }
-    std::shared_lock<RwLock> lk(mu_);  // readers share it; add / delete wait
-    const uint64_t n = ids_.size();
-    if (n != 0 && q_len != dim_) {  // the whole index's check, as in search
-        set_dim_mismatch(dim_, q_len);
-        set_last_error("Dimension mismatch: expected " + std::to_string(dim_) + ", got " + std::to_string(q_len));
-        return ERR_DIM_MISMATCH;
-    }
+    if (token != 0) VL_TRY(find_filter(token, &f));
+    std::shared_lock<RwLock> lk;
+    VL_TRY(lock_for_query(metric, q_len, &lk));
     if (min_score != min_score) {
         set_last_error("min_score is NaN");
         return ERR_INVALID_ARG;
     }
-    if (n == 0) return OK;
+    if (ids_.empty()) return OK;
     if ((!query && dim_) || (out_capacity != 0 && !out_scores)) return ERR_INVALID_ARG;
-
-    VL_HIP(hipSetDevice(device_));
-    Workspace* ws = acquire_ws();
-    if (!ws) return ERR_DEVICE;
-    int rc = OK;
-    if (f) {
-        std::lock_guard<std::mutex> fg(f->mu);
-        if (f->resolved_at != mutations_) rc = resolve_filter(ws, f.get());
-    }
-    if (rc == OK && (!f || f->m != 0)) {
-        active_searches_.fetch_add(1, std::memory_order_relaxed);
-        rc = search_range_locked(ws, f.get(), query, min_score, metric, out_capacity, out_pos, out_ids, out_scores, out_n,
-                                 out_total);
-        active_searches_.fetch_sub(1, std::memory_order_relaxed);
-    }
-    if (rc != OK) (void)hipStreamSynchronize(ws->stream);
-    release_ws(ws);
-    return rc;
+    return run_search(nullptr, f.get(), [&](Workspace* ws) -> int {
+        if (f && f->m == 0) return OK;
+        return search_range_locked(ws, f.get(), query, min_score, metric, out_capacity, out_pos, out_ids, out_scores, out_n, out_total);
+    });
 }
 
 int GpuFlatIndex::search_range_locked(Workspace* ws, IdFilter* f, const double* query, double min_score, int metric,
@@ -1931,58 +1787,28 @@ int GpuFlatIndex::search_range_locked(Workspace* ws, IdFilter* f, const double* 
     const uint32_t* plist = f ? f->d_plist : nullptr;
     hipStream_t st = ws->stream;
 
-    // the query staged as search_subset stages it: pinned f64 values, then the norm
-    double qq = 0.0, qmax = 0.0;
-    bool q_finite = true;
-    for (uint64_t i = 0; i < dim_; ++i) {
-        const double v = query[i];
-        ws->h_q64[i] = v;
-        qq += v * v;
-        const double av = std::fabs(v);
-        if (!(av <= 1.797693134862315708e308)) q_finite = false;
-        if (av > qmax) qmax = av;
-    }
-    const double q_norm = std::sqrt(qq);
-    const bool q_in_domain = q_finite && qmax <= DOMAIN_MAX_ABS && (q_norm == 0.0 || q_norm >= DOMAIN_MIN_NORM);
-    ws->h_q64[dim_] = q_norm;
+    const StagedQuery sq = stage_single_query(ws, query, dim_);
     VL_HIP(hipMemcpyAsync(ws->d_q64, ws->h_q64, (dim_ + 1) * sizeof(double), hipMemcpyHostToDevice, st));
 
     // writes the answer's first `want` entries from (positions, scores) on the host
-    auto deliver = [&](const uint32_t* pos, const double* scores, uint64_t want, uint64_t total) -> int {
-        for (uint64_t i = 0; i < want; ++i) {
-            const uint32_t p = pos[i];
-            if (p >= n) {
-                set_last_error("range search returned an out-of-range position (kernel bug)");
-                return ERR_DEVICE;
-            }
-            if (out_pos) out_pos[i] = p;
-            if (out_ids) out_ids[i] = ids_[p];
-            out_scores[i] = scores[i];
-        }
+    auto answer = [&](const uint32_t* pos, const double* scores, uint64_t want, uint64_t total) -> int {
+        VL_TRY(deliver("range search", ids_, pos, scores, want, out_pos, out_ids, out_scores));
         *out_n = want;
         *out_total = total;
         return OK;
     };
 
     const uint32_t cap = range_candidate_capacity();
-    const bool fast_ok = force_path_.load() == 0 && n_out_of_domain_ == 0 && q_in_domain;
+    const bool fast_ok = force_path_.load() == 0 && n_out_of_domain_ == 0 && sq.in_domain;
     if (fast_ok) {
         VL_TRY(ensure_range_ws(ws, RANGE_CAND_MAX, RANGE_SMALL));
-        if (!ws->rg_cand) {
-            VL_TRY(dev_alloc(&ws->rg_cand, (size_t)RANGE_CAND_MAX));
-            VL_TRY(dev_alloc(&ws->rg_scores, (size_t)RANGE_CAND_MAX));
-        }
+        VL_TRY(ensure_range_candidates(ws));
         // the score threshold in key space: rows with key <= tau are provably below min_score (R over the whole index
         // bounds a filter's rows too); no such key: every row is a candidate (NaN fails the device's comparison)
         float tau = 0.0f;
-        if (!range_tau(metric, ld_, max_row_norm_, q_norm, min_score, &tau)) tau = std::nanf("");
+        if (!range_tau(metric, ld_, max_row_norm_, sq.norm, min_score, &tau)) tau = std::nanf("");
         const bool qarg = scan_range_takes_qarg(ld_);
-        const float* q32 = nullptr;
-        if (qarg) {
-            if (ws->q32.size() < ld_) ws->q32.assign(ld_, 0.0f);
-            for (uint64_t i = 0; i < dim_; ++i) ws->q32[i] = (float)query[i];  // nearest even, like load_q4 on the device
-            q32 = ws->q32.data();
-        }
+        const float* q32 = qarg ? stage_q32(ws, query, dim_, ld_) : nullptr;
         const bool prof = profile_.load();
         ScanPlan plan;
         VL_HIP(hipMemsetAsync(ws->rg_ctr, 0, RANGE_CTR_WORDS * sizeof(uint32_t), st));
@@ -2003,17 +1829,10 @@ int GpuFlatIndex::search_range_locked(Workspace* ws, IdFilter* f, const double* 
             VL_HIP(hipMemcpyAsync(ws->rg_h_scores, ws->d_out_scores, k_spec * sizeof(double), hipMemcpyDeviceToHost, st));
         }
         VL_HIP(hipStreamSynchronize(st));
-        last_scan_variant_.store(plan.variant, std::memory_order_relaxed);
-        last_scan_grid_.store(plan.grid, std::memory_order_relaxed);
-        last_scan_qarg_.store(qarg ? 1 : 0, std::memory_order_relaxed);
-        if (prof) {
-            float ms = 0.f;
-            VL_HIP(hipEventElapsedTime(&ms, ws->ev0, ws->ev1));
-            std::lock_guard<std::mutex> g(prof_mu_);
-            prof_n_ += 1;
-            prof_ms_ += ms;
-            prof_bytes_ += m * ((uint64_t)ld_ * sizeof(float) + (plist ? sizeof(uint32_t) : 0) + (metric == COSINE ? sizeof(float) : 0));
-        }
+        note_scan(plan.variant, plan.grid, qarg);
+        if (prof)
+            VL_TRY(account_profile(ws, m * ((uint64_t)ld_ * sizeof(float) + (plist ? sizeof(uint32_t) : 0) +
+                                            (metric == COSINE ? sizeof(float) : 0))));
         const uint64_t appended = ws->rg_h_ctr[RANGE_CTR_APPENDED], total = ws->rg_h_ctr[RANGE_CTR_TOTAL];
         // in-domain rows cannot score NaN; a raised flag sends the call to the exact route, which decides the status
         if (appended <= cap && ws->rg_h_ctr[RANGE_CTR_NAN] == 0) {
@@ -2023,7 +1842,7 @@ int GpuFlatIndex::search_range_locked(Workspace* ws, IdFilter* f, const double* 
             }
             const uint64_t want = std::min<uint64_t>(total, out_capacity);
             set_last_path(PATH_FAST);
-            if (total <= RANGE_SMALL) return deliver(ws->rg_h_pos, ws->rg_h_scores, want, total);
+            if (total <= RANGE_SMALL) return answer(ws->rg_h_pos, ws->rg_h_scores, want, total);
             std::vector<uint32_t> pos(want);
             std::vector<double> scores(want);
             if (want) {
@@ -2034,21 +1853,14 @@ int GpuFlatIndex::search_range_locked(Workspace* ws, IdFilter* f, const double* 
                 VL_HIP(hipMemcpyAsync(scores.data(), ws->d_out_scores, want * sizeof(double), hipMemcpyDeviceToHost, st));
                 VL_HIP(hipStreamSynchronize(st));
             }
-            return deliver(pos.data(), scores.data(), want, total);
+            return answer(pos.data(), scores.data(), want, total);
         }
         // more candidates than the buffer holds: every score, then the cut
     }
 
     // the exact route: the reference score of every row, the cut, the sort on (score desc, position asc)
     VL_TRY(ensure_range_ws(ws, 0, 0));
-    if (ws->scores_cap < m) {
-        if (ws->d_scores) (void)hipFree(ws->d_scores);
-        ws->d_scores = nullptr;
-        ws->scores_cap = 0;
-        const size_t c = std::max<size_t>(m, 1024);
-        VL_TRY(dev_alloc(&ws->d_scores, c));
-        ws->scores_cap = c;
-    }
+    VL_TRY(ensure_scores(ws, m));
     VL_HIP(hipMemsetAsync(ws->rg_ctr, 0, RANGE_CTR_WORDS * sizeof(uint32_t), st));
     if (plist)
         VL_HIP(launch_exact_scan_subset(st, metric, d_master_, ws->d_q64, plist, m, (uint32_t)dim_, ws->d_scores,
@@ -2080,7 +1892,7 @@ int GpuFlatIndex::search_range_locked(Workspace* ws, IdFilter* f, const double* 
         VL_HIP(hipStreamSynchronize(st));
     }
     set_last_path(PATH_EXACT_SORT);
-    return deliver(pos.data(), scores.data(), want, total);
+    return answer(pos.data(), scores.data(), want, total);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2102,11 +1914,9 @@ GroupTable::~GroupTable()
         if (p) (void)hipFree(p);
 }
 
-std::shared_ptr<GroupTable> GpuFlatIndex::find_groups(uint64_t token) const
+int GpuFlatIndex::find_groups(uint64_t token, std::shared_ptr<GroupTable>* out) const
 {
-    std::lock_guard<std::mutex> g(filters_mu_);
-    auto it = groups_.find(token);
-    return it == groups_.end() ? nullptr : it->second;
+    return token_find(filters_mu_, groups_, token, UNKNOWN_GROUPS, out);
 }
 
 int GpuFlatIndex::groups_create(GroupPlan&& plan, uint64_t* out_token, uint64_t* out_rows)
@@ -2132,12 +1942,9 @@ int GpuFlatIndex::groups_create(GroupPlan&& plan, uint64_t* out_token, uint64_t*
     {
         std::shared_lock<RwLock> lk(mu_);
         std::lock_guard<std::mutex> tg(t->rows.mu);
-        Workspace* ws = acquire_ws();
-        if (!ws) return ERR_DEVICE;
-        const int rc = resolve_groups(ws, t.get());
-        if (rc != OK) (void)hipStreamSynchronize(ws->stream);
-        release_ws(ws);
-        if (rc != OK) return rc;
+        WsLease lease(this);
+        if (lease.status() != OK) return lease.status();
+        VL_TRY(lease.done(resolve_groups(lease.ws, t.get())));
         rows = t->rows.m;
     }
     const uint64_t token = g_next_filter_token.fetch_add(1);
@@ -2153,37 +1960,20 @@ int GpuFlatIndex::groups_create(GroupPlan&& plan, uint64_t* out_token, uint64_t*
 int GpuFlatIndex::groups_destroy(uint64_t groups)
 {
     std::shared_ptr<GroupTable> t;  // a search still using it holds its own reference: freed when that one ends
-    {
-        std::lock_guard<std::mutex> g(filters_mu_);
-        auto it = groups_.find(groups);
-        if (it == groups_.end()) {
-            set_last_error("unknown or destroyed group table");
-            return ERR_INVALID_ARG;
-        }
-        t = std::move(it->second);
-        groups_.erase(it);
-    }
-    return OK;
+    return token_take(filters_mu_, groups_, groups, UNKNOWN_GROUPS, &t);
 }
 
 int GpuFlatIndex::groups_rows(uint64_t groups, uint64_t* out_rows, uint64_t* out_distinct) const
 {
     if (!out_rows) return ERR_INVALID_ARG;
-    std::shared_ptr<GroupTable> t = find_groups(groups);
-    if (!t) {
-        set_last_error("unknown or destroyed group table");
-        return ERR_INVALID_ARG;
-    }
+    std::shared_ptr<GroupTable> t;
+    VL_TRY(find_groups(groups, &t));
     std::shared_lock<RwLock> lk(mu_);
     std::lock_guard<std::mutex> tg(t->rows.mu);
     if (t->rows.resolved_at != mutations_) {
-        VL_HIP(hipSetDevice(device_));
-        Workspace* ws = acquire_ws();
-        if (!ws) return ERR_DEVICE;
-        const int rc = resolve_groups(ws, t.get());
-        if (rc != OK) (void)hipStreamSynchronize(ws->stream);
-        release_ws(ws);
-        if (rc != OK) return rc;
+        WsLease lease(this);
+        if (lease.status() != OK) return lease.status();
+        VL_TRY(lease.done(resolve_groups(lease.ws, t.get())));
     }
     *out_rows = t->rows.m;
     if (out_distinct) *out_distinct = t->keys.size();
@@ -2198,42 +1988,11 @@ int GpuFlatIndex::resolve_groups(Workspace* ws, GroupTable* t) const
     VL_TRY(resolve_filter(ws, &t->rows));
     t->rows.resolved_at = ~0ull;
     if (n != 0 && !t->rows.ids.empty()) {
-        if (t->gor_cap < n) {
-            if (t->d_group_of_row) (void)hipFree(t->d_group_of_row);
-            t->d_group_of_row = nullptr;
-            t->gor_cap = 0;
-            VL_TRY(dev_alloc(&t->d_group_of_row, (size_t)n));
-            t->gor_cap = n;
-        }
+        VL_TRY(grow(HipMem{}, t->gor_cap, n, {dev_buf(t->d_group_of_row, n)}));
         VL_HIP(launch_group_rows(ws->stream, d_ids_, n, t->rows.d_ids, t->d_dense, t->rows.ids.size(), t->d_group_of_row));
         VL_HIP(hipStreamSynchronize(ws->stream));
     }
     t->rows.resolved_at = mutations_;
-    return OK;
-}
-
-int GpuFlatIndex::ensure_group_ws(Workspace* ws, uint64_t n_groups) const
-{
-    if (!ws->gp_ctr) {
-        VL_TRY(dev_alloc(&ws->gp_lists, (size_t)GROUP_TOP_LISTS * KP));
-        VL_TRY(dev_alloc(&ws->gp_cand, (size_t)KP));
-        VL_TRY(dev_alloc(&ws->gp_scores, (size_t)KP));
-        VL_TRY(dev_alloc(&ws->gp_out_keys, (size_t)GROUPED_MAX_K));
-        VL_TRY(pinned_alloc(&ws->gp_h_ctr, (size_t)RANGE_CTR_WORDS + 1));
-        VL_TRY(pinned_alloc(&ws->gp_h_scores, (size_t)KP));
-        VL_TRY(pinned_alloc(&ws->gp_h_keys, (size_t)GROUPED_MAX_K));
-        VL_TRY(dev_alloc(&ws->gp_ctr, (size_t)RANGE_CTR_WORDS + 1));
-    }
-    if (ws->gp_cap < n_groups) {
-        if (ws->gp_best) (void)hipFree(ws->gp_best);
-        if (ws->gp_first) (void)hipFree(ws->gp_first);
-        ws->gp_best = nullptr;
-        ws->gp_first = nullptr;
-        ws->gp_cap = 0;
-        VL_TRY(dev_alloc(&ws->gp_best, (size_t)n_groups));
-        VL_TRY(dev_alloc(&ws->gp_first, (size_t)n_groups));
-        ws->gp_cap = n_groups;
-    }
     return OK;
 }
 
@@ -2248,55 +2007,19 @@ int GpuFlatIndex::search_grouped(uint64_t groups, uint64_t token, const double* 
         set_last_error("grouped search: k exceeds VL_GROUPED_MAX_K (1024)");
         return ERR_INVALID_ARG;
     }
-    std::shared_ptr<GroupTable> t = find_groups(groups);
-    if (!t) {
-        set_last_error("unknown or destroyed group table");
-        return ERR_INVALID_ARG;
-    }
+    std::shared_ptr<GroupTable> t;
+    VL_TRY(find_groups(groups, &t));
     std::shared_ptr<IdFilter> f;
-    if (token != 0) {
-        f = find_filter(token);
-        if (!f) {
-            set_last_error("unknown or destroyed filter");
-            return ERR_INVALID_ARG;
-        }
-    }
-    if (metric < 0 || metric > 3) {
-        set_last_error("unknown metric");
-        return ERR_INVALID_ARG;
-    }
-    std::shared_lock<RwLock> lk(mu_);  // readers share it; add / delete wait: the resolved tables cannot move under the search
-    const uint64_t n = ids_.size();
-    if (n != 0 && q_len != dim_) {  // the whole index's check, as in search
-        set_dim_mismatch(dim_, q_len);
-        set_last_error("Dimension mismatch: expected " + std::to_string(dim_) + ", got " + std::to_string(q_len));
-        return ERR_DIM_MISMATCH;
-    }
-    if (n == 0 || k == 0) return OK;
+    if (token != 0) VL_TRY(find_filter(token, &f));
+    std::shared_lock<RwLock> lk;
+    VL_TRY(lock_for_query(metric, q_len, &lk));
+    if (ids_.empty() || k == 0) return OK;
     if ((!query && dim_) || (out_capacity != 0 && (!out_scores || !out_group_keys))) return ERR_INVALID_ARG;
-
-    VL_HIP(hipSetDevice(device_));
-    Workspace* ws = acquire_ws();
-    if (!ws) return ERR_DEVICE;
-    int rc = OK;
-    {
-        std::lock_guard<std::mutex> tg(t->rows.mu);
-        if (t->rows.resolved_at != mutations_) rc = resolve_groups(ws, t.get());
-    }
-    if (rc == OK && f) {
-        std::lock_guard<std::mutex> fg(f->mu);
-        if (f->resolved_at != mutations_) rc = resolve_filter(ws, f.get());
-    }
-    // from here on both resolutions are read only: a reader that finds them current leaves them alone, writers are shut out
-    if (rc == OK && t->rows.m != 0 && (!f || f->m != 0)) {
-        active_searches_.fetch_add(1, std::memory_order_relaxed);
-        rc = search_grouped_locked(ws, t.get(), f.get(), query, k, metric, out_capacity, out_group_keys, out_pos, out_ids, out_scores,
-                                   out_n);
-        active_searches_.fetch_sub(1, std::memory_order_relaxed);
-    }
-    if (rc != OK) (void)hipStreamSynchronize(ws->stream);
-    release_ws(ws);
-    return rc;
+    return run_search(t.get(), f.get(), [&](Workspace* ws) -> int {
+        if (t->rows.m == 0 || (f && f->m == 0)) return OK;
+        return search_grouped_locked(ws, t.get(), f.get(), query, k, metric, out_capacity, out_group_keys, out_pos, out_ids, out_scores,
+                                     out_n);
+    });
 }
 
 int GpuFlatIndex::search_grouped_locked(Workspace* ws, const GroupTable* t, const IdFilter* f, const double* query, uint64_t k,
@@ -2313,20 +2036,7 @@ int GpuFlatIndex::search_grouped_locked(Workspace* ws, const GroupTable* t, cons
     const uint32_t k32 = (uint32_t)k;
     hipStream_t st = ws->stream;
 
-    // the query staged as search_range_locked stages it: pinned f64 values, then the norm
-    double qq = 0.0, qmax = 0.0;
-    bool q_finite = true;
-    for (uint64_t i = 0; i < dim_; ++i) {
-        const double v = query[i];
-        ws->h_q64[i] = v;
-        qq += v * v;
-        const double av = std::fabs(v);
-        if (!(av <= 1.797693134862315708e308)) q_finite = false;
-        if (av > qmax) qmax = av;
-    }
-    const double q_norm = std::sqrt(qq);
-    const bool q_in_domain = q_finite && qmax <= DOMAIN_MAX_ABS && (q_norm == 0.0 || q_norm >= DOMAIN_MIN_NORM);
-    ws->h_q64[dim_] = q_norm;
+    const StagedQuery sq = stage_single_query(ws, query, dim_);
     VL_HIP(hipMemcpyAsync(ws->d_q64, ws->h_q64, (dim_ + 1) * sizeof(double), hipMemcpyHostToDevice, st));
 
     VL_TRY(ensure_group_ws(ws, ng));
@@ -2344,38 +2054,21 @@ int GpuFlatIndex::search_grouped_locked(Workspace* ws, const GroupTable* t, cons
         return OK;
     };
     // writes the answer from the pinned copies of the collapse's output
-    auto deliver = [&](uint64_t emitted) -> int {
+    auto answer = [&](uint64_t emitted) -> int {
         const uint64_t want = std::min<uint64_t>(emitted, out_capacity);
-        for (uint64_t i = 0; i < want; ++i) {
-            const uint32_t p = ws->rg_h_pos[i];
-            if (p >= n) {
-                set_last_error("grouped search returned an out-of-range position (kernel bug)");
-                return ERR_DEVICE;
-            }
-            out_group_keys[i] = ws->gp_h_keys[i];
-            if (out_pos) out_pos[i] = p;
-            if (out_ids) out_ids[i] = ids_[p];
-            out_scores[i] = ws->rg_h_scores[i];
-        }
+        VL_TRY(deliver("grouped search", ids_, ws->rg_h_pos, ws->rg_h_scores, want, out_pos, out_ids, out_scores));
+        for (uint64_t i = 0; i < want; ++i) out_group_keys[i] = ws->gp_h_keys[i];
         *out_n = want;
         return OK;
     };
 
     const uint32_t cap = range_candidate_capacity();
-    const bool fast_ok = force_path_.load() == 0 && n_out_of_domain_ == 0 && q_in_domain && k <= (uint64_t)KP;
+    const bool fast_ok = force_path_.load() == 0 && n_out_of_domain_ == 0 && sq.in_domain && k <= (uint64_t)KP;
     while (fast_ok) {  // (one round: `break` leaves for the exact route)
         VL_TRY(ensure_range_ws(ws, RANGE_CAND_MAX, GROUPED_MAX_K));
-        if (!ws->rg_cand) {
-            VL_TRY(dev_alloc(&ws->rg_cand, (size_t)RANGE_CAND_MAX));
-            VL_TRY(dev_alloc(&ws->rg_scores, (size_t)RANGE_CAND_MAX));
-        }
+        VL_TRY(ensure_range_candidates(ws));
         const bool qarg = scan_range_takes_qarg(ld_);
-        const float* q32 = nullptr;
-        if (qarg) {
-            if (ws->q32.size() < ld_) ws->q32.assign(ld_, 0.0f);
-            for (uint64_t i = 0; i < dim_; ++i) ws->q32[i] = (float)query[i];  // nearest even, like load_q4 on the device
-            q32 = ws->q32.data();
-        }
+        const float* q32 = qarg ? stage_q32(ws, query, dim_, ld_) : nullptr;
         // pass 1: the best key of every group, the 64 best groups, the reference scores of the first k of them
         const bool prof = profile_.load();
         ScanPlan plan;
@@ -2391,18 +2084,10 @@ int GpuFlatIndex::search_grouped_locked(Workspace* ws, const GroupTable* t, cons
         VL_HIP(hipMemcpyAsync(ws->gp_h_ctr, ws->gp_ctr, RANGE_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         VL_HIP(hipMemcpyAsync(ws->gp_h_scores, ws->gp_scores, k * sizeof(double), hipMemcpyDeviceToHost, st));
         VL_HIP(hipStreamSynchronize(st));
-        last_scan_variant_.store(plan.variant, std::memory_order_relaxed);
-        last_scan_grid_.store(plan.grid, std::memory_order_relaxed);
-        last_scan_qarg_.store(qarg ? 1 : 0, std::memory_order_relaxed);
-        if (prof) {
-            float ms = 0.f;
-            VL_HIP(hipEventElapsedTime(&ms, ws->ev0, ws->ev1));
-            std::lock_guard<std::mutex> g(prof_mu_);
-            prof_n_ += 1;
-            prof_ms_ += ms;
-            prof_bytes_ += m * ((uint64_t)ld_ * sizeof(float) + sizeof(uint32_t) + (plist ? sizeof(uint32_t) : 0) +
-                                (metric == COSINE ? sizeof(float) : 0));
-        }
+        note_scan(plan.variant, plan.grid, qarg);
+        if (prof)
+            VL_TRY(account_profile(ws, m * ((uint64_t)ld_ * sizeof(float) + sizeof(uint32_t) + (plist ? sizeof(uint32_t) : 0) +
+                                            (metric == COSINE ? sizeof(float) : 0))));
         if (ws->gp_h_ctr[RANGE_CTR_APPENDED] < k || ws->gp_h_ctr[RANGE_CTR_NAN] != 0) break;  // fewer than k non-empty groups; a NaN
         double L = ws->gp_h_scores[0];
         bool nan = false;
@@ -2415,7 +2100,7 @@ int GpuFlatIndex::search_grouped_locked(Workspace* ws, const GroupTable* t, cons
 
         // pass 2: the range search at min_score = L, rows without a group dropped at the cut, and the collapse
         float tau = 0.0f;
-        if (!range_tau(metric, ld_, max_row_norm_, q_norm, L, &tau)) tau = std::nanf("");
+        if (!range_tau(metric, ld_, max_row_norm_, sq.norm, L, &tau)) tau = std::nanf("");
         VL_HIP(hipMemsetAsync(ws->rg_ctr, 0, RANGE_CTR_WORDS * sizeof(uint32_t), st));
         VL_HIP(launch_scan_range(st, metric, d_slab_, d_inv_norm_, plist, m, ws->d_q64, (uint32_t)dim_, ld_, tau, ws->rg_cand, cap,
                                  ws->rg_ctr, nullptr, q32));
@@ -2442,18 +2127,11 @@ int GpuFlatIndex::search_grouped_locked(Workspace* ws, const GroupTable* t, cons
         // vl_last_path shows it
         if (ws->gp_h_ctr[RANGE_CTR_WORDS] != k) break;
         set_last_path(PATH_FAST);
-        return deliver(k);
+        return answer(k);
     }
 
     // the exact route: the reference score of every row, the grouped rows ranked by the device-wide sort, the collapse
-    if (ws->scores_cap < m) {
-        if (ws->d_scores) (void)hipFree(ws->d_scores);
-        ws->d_scores = nullptr;
-        ws->scores_cap = 0;
-        const size_t c = std::max<size_t>(m, 1024);
-        VL_TRY(dev_alloc(&ws->d_scores, c));
-        ws->scores_cap = c;
-    }
+    VL_TRY(ensure_scores(ws, m));
     const double neg_inf = -std::numeric_limits<double>::infinity();
     VL_HIP(hipMemsetAsync(ws->rg_ctr, 0, RANGE_CTR_WORDS * sizeof(uint32_t), st));
     if (plist)
@@ -2488,7 +2166,7 @@ int GpuFlatIndex::search_grouped_locked(Workspace* ws, const GroupTable* t, cons
         set_last_error("grouped collapse emitted more rows than asked for (kernel bug)");
         return ERR_DEVICE;
     }
-    return deliver(emitted);
+    return answer(emitted);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2648,18 +2326,9 @@ int GpuFlatIndex::search_batch_to_record(const double* queries, bool queries_on_
         return ERR_OOM;
     }
     {
-        Workspace* ws = acquire_ws();
-        if (!ws) return ERR_DEVICE;
-        struct Releaser {
-            const GpuFlatIndex* self;
-            Workspace* ws;
-            ~Releaser()
-            {
-                (void)hipStreamSynchronize(ws->stream);
-                self->release_ws(ws);
-            }
-        } rel{this, ws};
-        VL_TRY(search_batch_mfma(ws, queries_on_device ? nullptr : queries, queries_on_device ? queries : nullptr, nq, ks, k_eff, metric,
+        WsLease lease(this, /*sync_always=*/true);
+        if (lease.status() != OK) return lease.status();
+        VL_TRY(search_batch_mfma(lease.ws, queries_on_device ? nullptr : queries, queries_on_device ? queries : nullptr, nq, ks, k_eff, metric,
                                  pos.data(), ids.data(), sc.data(), cnt.data(), &done, &sink));
     }
     set_last_path(PATH_FAST);
@@ -2839,14 +2508,7 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
         if (d_queries)
             for (uint32_t j = 0; j < g; ++j) S.in_domain[j] = dom[j];
         const auto t_3 = now();
-        if (prof) {
-            float ms = 0.f;
-            VL_HIP(hipEventElapsedTime(&ms, ws->ev0, ws->ev1));
-            std::lock_guard<std::mutex> gl(prof_mu_);
-            prof_n_ += 1;
-            prof_ms_ += ms;
-            prof_bytes_ += n * (uint64_t)mfma_ldb((uint32_t)dim_) * 2;
-        }
+        if (prof) VL_TRY(account_profile(ws, n * (uint64_t)mfma_ldb((uint32_t)dim_) * 2));
         for (uint32_t j = 0; j < g; ++j) {
             const uint64_t qi = S.q0 + j;
             const SearchResultBlock& r = res[j];
@@ -2907,32 +2569,18 @@ uint32_t range_batch_candidate_capacity()
     }
     return (uint32_t)MFMA_CAND_CAP;
 }
-}  // namespace
-
-int GpuFlatIndex::ensure_range_batch_ws(Workspace* ws, uint64_t seq_queries) const
+int ensure_range_batch_ws(Workspace* ws, uint64_t seq_queries)
 {
-    if (!ws->rb_ctr) {
-        VL_TRY(dev_alloc(&ws->rb_ctr, (size_t)MFMA_MAX_BATCH * RBATCH_CTR_WORDS));
-        VL_TRY(dev_alloc(&ws->rb_min, (size_t)MFMA_MAX_BATCH));
-        VL_TRY(pinned_alloc(&ws->rb_h_thr, (size_t)MFMA_MAX_BATCH));
-        VL_TRY(pinned_alloc(&ws->rb_h_min, (size_t)MFMA_MAX_BATCH));
-        VL_TRY(pinned_alloc(&ws->rb_h_ctr, (size_t)MFMA_MAX_BATCH * RBATCH_CTR_WORDS));
-        VL_TRY(pinned_alloc(&ws->rb_h_cnt, (size_t)MFMA_MAX_BATCH));
-        VL_TRY(pinned_alloc(&ws->rb_h_pos, RBATCH_SPEC));
-        VL_TRY(pinned_alloc(&ws->rb_h_scores, RBATCH_SPEC));
-    }
-    if (ws->rb_sv_queries < seq_queries) {  // as many survivor segments as the largest sequence so far had queries
-        if (ws->rb_sv_score) (void)hipFree(ws->rb_sv_score);
-        if (ws->rb_sv_pos) (void)hipFree(ws->rb_sv_pos);
-        ws->rb_sv_score = nullptr;
-        ws->rb_sv_pos = nullptr;
-        ws->rb_sv_queries = 0;
-        VL_TRY(dev_alloc(&ws->rb_sv_score, (size_t)seq_queries * RBATCH_SEG));
-        VL_TRY(dev_alloc(&ws->rb_sv_pos, (size_t)seq_queries * RBATCH_SEG));
-        ws->rb_sv_queries = seq_queries;
-    }
-    return OK;
+    const size_t nq = MFMA_MAX_BATCH;
+    VL_TRY(ensure_set(HipMem{}, {dev_buf(ws->rb_ctr, nq * RBATCH_CTR_WORDS), dev_buf(ws->rb_min, nq), pinned_buf(ws->rb_h_thr, nq),
+                                 pinned_buf(ws->rb_h_min, nq), pinned_buf(ws->rb_h_ctr, nq * RBATCH_CTR_WORDS),
+                                 pinned_buf(ws->rb_h_cnt, nq), pinned_buf(ws->rb_h_pos, RBATCH_SPEC),
+                                 pinned_buf(ws->rb_h_scores, RBATCH_SPEC)}));
+    // as many survivor segments as the largest sequence so far had queries
+    return grow(HipMem{}, ws->rb_sv_queries, seq_queries,
+                {dev_buf(ws->rb_sv_score, (size_t)seq_queries * RBATCH_SEG), dev_buf(ws->rb_sv_pos, (size_t)seq_queries * RBATCH_SEG)});
 }
+}  // namespace
 
 int GpuFlatIndex::search_range_batch(uint64_t token, const double* queries, uint64_t nq, uint64_t q_len, const double* min_scores,
                                      int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
@@ -2952,24 +2600,10 @@ int GpuFlatIndex::search_range_batch(uint64_t token, const double* queries, uint
         out_total[i] = 0;
     }
     std::shared_ptr<IdFilter> f;
-    if (token != 0) {
-        f = find_filter(token);
-        if (!f) {
-            set_last_error("unknown or destroyed filter");
-            return ERR_INVALID_ARG;
-        }
-    }
-    if (metric < 0 || metric > 3) {
-        set_last_error("unknown metric");
-        return ERR_INVALID_ARG;
-    }
-    std::shared_lock<RwLock> lk(mu_);  // one index state for the whole batch
+    if (token != 0) VL_TRY(find_filter(token, &f));
+    std::shared_lock<RwLock> lk;  // one index state for the whole batch
+    VL_TRY(lock_for_query(metric, q_len, &lk));
     const uint64_t n = ids_.size();
-    if (n != 0 && q_len != dim_) {
-        set_dim_mismatch(dim_, q_len);
-        set_last_error("Dimension mismatch: expected " + std::to_string(dim_) + ", got " + std::to_string(q_len));
-        return ERR_DIM_MISMATCH;
-    }
     // The lowest failing query decides the status.  A NaN threshold fails its query before anything is computed, so only the
     // queries in front of the first one can fail earlier (with a NaN score): they are answered, the rest is not.
     uint64_t nq_run = nq;
@@ -2990,32 +2624,19 @@ int GpuFlatIndex::search_range_batch(uint64_t token, const double* queries, uint
     }
     if ((!queries && dim_) || (out_stride != 0 && !out_scores)) return ERR_INVALID_ARG;
 
-    VL_HIP(hipSetDevice(device_));
-    Workspace* ws = acquire_ws();
-    if (!ws) return ERR_DEVICE;
-    struct Releaser {
-        const GpuFlatIndex* self;
-        Workspace* ws;
-        ~Releaser()
-        {
-            (void)hipStreamSynchronize(ws->stream);
-            self->release_ws(ws);
-        }
-    } rel{this, ws};
-    if (f) {
-        std::lock_guard<std::mutex> fg(f->mu);
-        if (f->resolved_at != mutations_) VL_TRY(resolve_filter(ws, f.get()));
-    }
+    WsLease lease(this, /*sync_always=*/true);
+    if (lease.status() != OK) return lease.status();
+    Workspace* const ws = lease.ws;
+    if (f) VL_TRY(resolve_if_stale(ws, f.get()));
     auto single = [&](uint64_t qi) -> int {
         if (f && f->m == 0) {  // an empty subset: nothing qualifies (search_range's early return)
             routes[1] += 1;
             return OK;
         }
-        active_searches_.fetch_add(1, std::memory_order_relaxed);
+        InFlight searching(active_searches_);
         const int rc = search_range_locked(ws, f.get(), queries + qi * dim_, min_scores[qi], metric, out_stride, nullptr,
                                            out_ids ? out_ids + qi * out_stride : nullptr,
                                            out_scores ? out_scores + qi * out_stride : nullptr, out_n + qi, out_total + qi);
-        active_searches_.fetch_sub(1, std::memory_order_relaxed);
         if (rc == OK) routes[last_path() == PATH_EXACT_SORT ? 2 : 1] += 1;
         return rc;
     };
@@ -3137,16 +2758,12 @@ int GpuFlatIndex::search_range_batch_mfma(Workspace* ws, const double* queries, 
             const uint32_t* c = ws->rb_h_ctr + (size_t)j * RBATCH_CTR_WORDS;
             const size_t off = c[RBATCH_CTR_OFF];
             const uint32_t want = c[RBATCH_CTR_WANT];
-            for (uint32_t i = 0; i < want; ++i) {
-                const size_t e = off + i;
-                const uint32_t p = e < spec ? ws->rb_h_pos[e] : more_pos[e - spec];
-                if (p >= n) {
-                    set_last_error("batched range search returned an out-of-range position (kernel bug)");
-                    return ERR_DEVICE;
-                }
-                if (out_ids) out_ids[qi * out_stride + i] = ids_[p];
-                out_scores[qi * out_stride + i] = e < spec ? ws->rb_h_scores[e] : more_scores[e - spec];
-            }
+            // packed entry e: in the speculative copy, or in the rest fetched behind it
+            VL_TRY(deliver(
+                "batched range search", ids_, want,
+                [&](uint64_t i) { return off + i < spec ? ws->rb_h_pos[off + i] : more_pos[off + i - spec]; },
+                [&](uint64_t i) { return off + i < spec ? ws->rb_h_scores[off + i] : more_scores[off + i - spec]; }, nullptr,
+                out_ids ? out_ids + qi * out_stride : nullptr, out_scores + qi * out_stride));
             out_n[qi] = want;
             out_total[qi] = c[RBATCH_CTR_TOTAL];
             (*done)[qi] = 1;
@@ -3162,10 +2779,7 @@ int GpuFlatIndex::search_batch_device(const double* d_queries, uint64_t nq, uint
     if (nq == 0) return OK;
     if (!out_n) return ERR_INVALID_ARG;
     for (uint64_t i = 0; i < nq; ++i) out_n[i] = 0;
-    if (metric < 0 || metric > 3) {
-        set_last_error("unknown metric");
-        return ERR_INVALID_ARG;
-    }
+    VL_TRY(check_metric(metric));
     VL_HIP(hipSetDevice(device_));
     auto via_host = [&]() -> int {  // the reference's surface with host queries: every check and path of search_batch()
         std::vector<double> h;
@@ -3184,11 +2798,7 @@ int GpuFlatIndex::search_batch_device(const double* d_queries, uint64_t nq, uint
     const uint64_t n = ids_.size();
     // the checks of search_batch(), before any byte of the queries is touched (src/index/flat.rs:99-104: an empty index
     // accepts any query length)
-    if (n != 0 && q_len != dim_) {
-        set_dim_mismatch(dim_, q_len);
-        set_last_error("Dimension mismatch: expected " + std::to_string(dim_) + ", got " + std::to_string(q_len));
-        return ERR_DIM_MISMATCH;
-    }
+    if (n != 0 && q_len != dim_) return dim_mismatch(q_len);
     if (n == 0 || k == 0) return OK;
     if (!d_queries || !out_scores) return ERR_INVALID_ARG;
     const uint64_t k_eff = std::min<uint64_t>(k, n);
@@ -3204,18 +2814,9 @@ int GpuFlatIndex::search_batch_device(const double* d_queries, uint64_t nq, uint
     }
     std::vector<uint8_t> done(nq, 0);
     {
-        Workspace* ws = acquire_ws();
-        if (!ws) return ERR_DEVICE;
-        struct Releaser {
-            const GpuFlatIndex* self;
-            Workspace* ws;
-            ~Releaser()
-            {
-                (void)hipStreamSynchronize(ws->stream);
-                self->release_ws(ws);
-            }
-        } rel{this, ws};
-        VL_TRY(search_batch_mfma(ws, nullptr, d_queries, nq, k, k_eff, metric, out_pos, out_ids, out_scores, out_n, &done));
+        WsLease lease(this, /*sync_always=*/true);
+        if (lease.status() != OK) return lease.status();
+        VL_TRY(search_batch_mfma(lease.ws, nullptr, d_queries, nq, k, k_eff, metric, out_pos, out_ids, out_scores, out_n, &done));
     }
     set_last_path(PATH_FAST);
     // what the filter could not certify (ties, candidate overflow, a query outside the fast-path domain): those queries
@@ -3316,11 +2917,7 @@ int GpuFlatIndex::hnsw_distances(const double* query, uint64_t q_len, int metric
 {
     if (metric < 0 || metric > 3) return ERR_INVALID_ARG;
     std::shared_lock<RwLock> lk(mu_);
-    if (q_len != dim_) {
-        set_dim_mismatch(dim_, q_len);
-        set_last_error("Dimension mismatch: expected " + std::to_string(dim_) + ", got " + std::to_string(q_len));
-        return ERR_DIM_MISMATCH;
-    }
+    if (q_len != dim_) return dim_mismatch(q_len);
     if (m == 0) return OK;
     if (!positions || !out || (!query && dim_)) return ERR_INVALID_ARG;
     const uint64_t n = ids_.size();
@@ -3332,30 +2929,12 @@ int GpuFlatIndex::hnsw_distances(const double* query, uint64_t q_len, int metric
         }
         p32[i] = (uint32_t)positions[i];
     }
-    VL_HIP(hipSetDevice(device_));
-    Workspace* ws = acquire_ws();
-    if (!ws) return ERR_DEVICE;
-    struct Releaser {
-        const GpuFlatIndex* self;
-        Workspace* ws;
-        ~Releaser()
-        {
-            (void)hipStreamSynchronize(ws->stream);
-            self->release_ws(ws);
-        }
-    } rel{this, ws};
+    WsLease lease(this, /*sync_always=*/true);
+    if (lease.status() != OK) return lease.status();
+    Workspace* const ws = lease.ws;
     hipStream_t st = ws->stream;
-    if (ws->hn_cap < m) {
-        if (ws->d_positions) (void)hipFree(ws->d_positions);
-        if (ws->d_dists) (void)hipFree(ws->d_dists);
-        ws->d_positions = nullptr;
-        ws->d_dists = nullptr;
-        ws->hn_cap = 0;
-        const size_t cap = std::max<size_t>(m, 256);
-        VL_TRY(dev_alloc(&ws->d_positions, cap));
-        VL_TRY(dev_alloc(&ws->d_dists, cap));
-        ws->hn_cap = cap;
-    }
+    const size_t cap = std::max<size_t>(m, 256);
+    VL_TRY(grow(HipMem{}, ws->hn_cap, cap, {dev_buf(ws->d_positions, cap), dev_buf(ws->d_dists, cap)}));
     for (uint64_t i = 0; i < dim_; ++i) ws->h_q64[i] = query[i];
     if (dim_) VL_HIP(hipMemcpyAsync(ws->d_q64, ws->h_q64, dim_ * sizeof(double), hipMemcpyHostToDevice, st));
     VL_HIP(hipMemcpyAsync(ws->d_positions, p32.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -3459,22 +3038,10 @@ int search_embeddings_f32(int device, uint64_t dim, const float* emb, uint64_t n
     } ret{scp};
     Scratch& sc = *scp;
     const size_t need = (size_t)nq * dim;
-    if (sc.rows_cap < need) {
-        if (sc.rows) (void)hipFree(sc.rows);
-        sc.rows = nullptr;
-        sc.rows_cap = 0;
-        VL_HIP(hipMalloc(&sc.rows, need * sizeof(double)));
-        sc.rows_cap = need;
-    }
+    VL_TRY(grow(HipMem{}, sc.rows_cap, need, {dev_buf(sc.rows, need)}));
     const float* src = emb;
     if (!emb_on_device) {
-        if (sc.staged_cap < need) {
-            if (sc.staged) (void)hipFree(sc.staged);
-            sc.staged = nullptr;
-            sc.staged_cap = 0;
-            VL_HIP(hipMalloc(&sc.staged, need * sizeof(float)));
-            sc.staged_cap = need;
-        }
+        VL_TRY(grow(HipMem{}, sc.staged_cap, need, {dev_buf(sc.staged, need)}));
         VL_HIP(hipMemcpyAsync(sc.staged, emb, need * sizeof(float), hipMemcpyHostToDevice, sc.st));
         src = sc.staged;
     }

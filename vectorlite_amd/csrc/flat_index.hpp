@@ -367,6 +367,24 @@ private:
     Workspace* acquire_ws() const;
     void release_ws(Workspace* ws) const;
     int prepare_ws(Workspace* ws) const;
+    // What every read-side entry point shares.  A new search mode writes its argument rules and its
+    // *_locked body, nothing else.
+    class WsLease;  // a borrowed workspace: hipSetDevice + acquire_ws; drains the stream if the call failed, then gives it back
+    int lock_for_query(int metric, uint64_t q_len, std::shared_lock<RwLock>* lk) const;  // the metric, then mu_ shared, then the length
+    int dim_mismatch(uint64_t q_len) const;  // records it; VL_ERR_DIM_MISMATCH
+    // mu_ held (shared): leases a workspace, resolves t and f (either may be null) if rows changed since, runs body(ws) as one
+    // of the handle's searches in flight
+    template <typename Body>
+    int run_search(GroupTable* t, IdFilter* f, Body&& body) const;
+    int resolve_if_stale(Workspace* ws, IdFilter* f) const;    // takes f->mu
+    int resolve_if_stale(Workspace* ws, GroupTable* t) const;  // takes t->rows.mu
+    int account_profile(Workspace* ws, uint64_t bytes, uint64_t passes = 1) const;  // the scan between ws->ev0 and ws->ev1
+    void note_scan(int variant, int grid, bool qarg) const
+    {
+        last_scan_variant_.store(variant, std::memory_order_relaxed);
+        last_scan_grid_.store(grid, std::memory_order_relaxed);
+        last_scan_qarg_.store(qarg ? 1 : 0, std::memory_order_relaxed);
+    }
     int search_direct(const double* query, uint64_t q_len, uint64_t k, int metric, uint64_t* out_pos, uint64_t* out_ids,
                       double* out_scores, uint64_t* out_n) const;
     int search_coalesced(const double* query, uint64_t q_len, uint64_t k, int metric, uint64_t* out_pos,
@@ -390,23 +408,20 @@ private:
     // mmr != nullptr: the selection runs behind the ranking and pos / scores stay untouched (mmr_take reads the answer)
     int run_exact(Workspace* ws, int metric, uint64_t n, uint64_t k_eff, std::vector<uint32_t>* pos,
                   std::vector<double>* scores, const uint32_t* plist = nullptr, const MmrReq* mmr = nullptr) const;
-    std::shared_ptr<IdFilter> find_filter(uint64_t token) const;
+    int find_filter(uint64_t token, std::shared_ptr<IdFilter>* out) const;  // VL_ERR_INVALID_ARG with a message: no such token
     int resolve_filter(Workspace* ws, IdFilter* f) const;  // mu_ held (shared or unique), f->mu held
     int search_subset(Workspace* ws, IdFilter* f, const double* query, uint64_t k_eff, int metric, uint64_t* out_pos,
                       uint64_t* out_ids, double* out_scores, uint64_t* out_n,
                       const MmrReq* mmr = nullptr) const;  // mu_ held (shared), f resolved
-    int ensure_range_ws(Workspace* ws, uint64_t sort_cap, uint64_t out_cap) const;
     int search_range_locked(Workspace* ws, IdFilter* f, const double* query, double min_score, int metric, uint64_t out_capacity,
                             uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
                             uint64_t* out_total) const;  // mu_ held (shared), f resolved (nullptr: the whole index)
-    std::shared_ptr<GroupTable> find_groups(uint64_t token) const;
+    int find_groups(uint64_t token, std::shared_ptr<GroupTable>* out) const;
     int resolve_groups(Workspace* ws, GroupTable* t) const;  // mu_ held (shared or unique), t->rows.mu held
-    int ensure_group_ws(Workspace* ws, uint64_t n_groups) const;
     // mu_ held (shared), t resolved, f resolved (nullptr: no filter)
     int search_grouped_locked(Workspace* ws, const GroupTable* t, const IdFilter* f, const double* query, uint64_t k, int metric,
                               uint64_t out_capacity, uint64_t* out_group_keys, uint64_t* out_pos, uint64_t* out_ids,
                               double* out_scores, uint64_t* out_n) const;
-    int ensure_range_batch_ws(Workspace* ws, uint64_t seq_queries) const;
     // the MFMA route of search_range_batch (mu_ held, whole index): done[qi] is set for every query answered here
     int search_range_batch_mfma(Workspace* ws, const double* queries, uint64_t nq, const double* min_scores, int metric,
                                 uint64_t out_stride, uint64_t* out_ids, double* out_scores, uint64_t* out_n, uint64_t* out_total,
