@@ -879,10 +879,15 @@ def test_seeded_fuzz_adversarial_values(V, O):
             assert bi[j, : bn[j]].tolist() == want[0].tolist() and bs[j, : bn[j]].tolist() == want[1].tolist(), (case, kind, j)
 
 
-def test_stateful_fuzz_large_index_all_filters(V, O):
-    """An index big enough for every candidate filter (f32 scan, bf16 single-query filter, bf16 MFMA batch
+def test_stateful_fuzz_large_index_all_filters(V, O, monkeypatch):
+    """An index big enough for every candidate filter (f32 scan, int8 and bf16 single-query filters, bf16 MFMA batch
     filter) under a random stream of adds, bulk adds, deletes (present, absent, duplicated ids), failed adds
-    and clones; every search is compared with the oracle that received the same stream."""
+    and clones; every search is compared with the oracle that received the same stream.  The size floors of the
+    single-query ladder are off, so a handle in its starting mode (the first one, and every clone) scans the int8 copy
+    first, then the bf16 one; the mode switch picks the int8 stage, the bf16 stage or neither."""
+    monkeypatch.setenv("VL_SINGLE_FILTER_MIN_MB", "0")  # read at create
+    monkeypatch.setenv("VL_SINGLE_FILTER_I8_MIN_MB", "0")
+    monkeypatch.delenv("VL_SINGLE_FILTER", raising=False)
     rng = np.random.default_rng(424242)
     dim, n0 = 128, 9000
     rows = unit_rows(rng, n0, dim)
@@ -921,7 +926,7 @@ def test_stateful_fuzz_large_index_all_filters(V, O):
         elif op == 6:  # the clone takes over (src/persistence.rs:118 clones the index)
             gpu = gpu.clone()
         else:
-            gpu.set_single_filter("bf16" if rng.random() < 0.5 else "f32")
+            gpu.set_single_filter(("i8", "bf16", "f32")[int(rng.random() * 3.0)])
         assert len(gpu) == len(ref) == len(live)
         m = int(rng.integers(0, 4))
         k = int(rng.choice([1, 10, 48, 70]))

@@ -190,7 +190,13 @@ struct MmrReq {
 };
 int mmr_check_args(uint64_t k, uint64_t fetch_k, double lambda);  // VL_ERR_INVALID_ARG with a message, or OK
 
+// Defined only by tests/native/derived_copies_audit.hip: reads the device copies, their watermarks and the host bookkeeping
+// below to compare them with a from-scratch conversion after every mutation.  The library has no code of it.
+class DerivedCopiesProbe;
+
 class GpuFlatIndex {
+    friend class DerivedCopiesProbe;
+
 public:
     struct CoalesceReq {  // one caller waiting in search_coalesced()
         const double* query;
