@@ -898,17 +898,33 @@ __global__ __launch_bounds__(256) void k_hnsw_insert_link(HnswGraphView g, uint3
             const uint32_t cap = layer == 0 ? g.m0 : g.m;
             const uint32_t* pnb;
             const unsigned long long* pnd;
-            uint32_t pcnt;
+            const uint32_t* pc;
             if (layer == 0) {
                 pnb = g.nbr0 + (size_t)p * g.m0;
                 pnd = g.dist0 + (size_t)p * g.m0;
-                pcnt = g.cnt0[p];
+                pc = g.cnt0 + p;
             } else {
                 const uint32_t us = g.upper_off[p] + (uint32_t)(layer - 1);
                 pnb = g.nbrU + (size_t)us * g.m;
                 pnd = g.distU + (size_t)us * g.m;
-                pcnt = g.cntU[us];
+                pc = g.cntU + us;
             }
+            // p's own list, read ONCE and under p's lock (lane t keeps entry t; lists hold <= 64): the later nodes of this
+            // batch that chose p (same-batch predecessors) append to it and evict from it while this wave runs.  Read
+            // entry by entry without the lock, an entry could already be such a node q -- p then linked itself into q's
+            // list, which names p already -- or the id of one edge with the distance of another.  Entries above p are
+            // exactly those back-links (phase A picks among the nodes below p), so they are left out.  The lock is
+            // released before the first link_into: no wave ever holds two locks.
+            if (lane == 0) {
+                while (atomicCAS(&g.lock[p], 0u, 1u) != 0u) __builtin_amdgcn_s_sleep(4);
+            }
+            __threadfence();
+            const uint32_t pcnt = __hip_atomic_load(pc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t own_v = (uint32_t)lane < pcnt ? __hip_atomic_load(pnb + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : HNSW_NONE;
+            const unsigned long long own_d = (uint32_t)lane < pcnt ? __hip_atomic_load(pnd + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+            __threadfence();  // the loads have returned before the lock opens
+            if (lane == 0) atomicExch(&g.lock[p], 0u);
+            const unsigned long long own = __ballot(own_v < p);  // HNSW_NONE is above every node
             // returns whether p entered qn's list (wave-uniform)
             auto link_into = [&](uint32_t qn, unsigned long long d, bool force) -> bool {
                 bool entered = false;
@@ -985,10 +1001,17 @@ __global__ __launch_bounds__(256) void k_hnsw_insert_link(HnswGraphView g, uint3
                 return entered;
             };
             bool any = false;
-            for (uint32_t t = 0; t < pcnt; ++t) any = link_into(pnb[t], pnd[t], false) || any;
+            for (unsigned long long todo = own; todo != 0ull; todo &= todo - 1) {
+                const int t = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
+                any = link_into(read_lane(own_v, t), read_lane(own_d, t), false) || any;
+            }
             // every chosen neighbour had a full list of closer entries: p would have no incoming edge at all and could
             // never be found (seen on a 40-node index with M0 = 32) -- its nearest neighbour takes it regardless
-            if (!any && pcnt > 0) (void)link_into(pnb[0], pnd[0], true);
+            // (nearest first; a list whose every entry is some node's last incoming edge cannot take it, then the next does)
+            for (unsigned long long todo = own; !any && todo != 0ull; todo &= todo - 1) {
+                const int t = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
+                any = link_into(read_lane(own_v, t), read_lane(own_d, t), true);
+            }
         }
     }
 }

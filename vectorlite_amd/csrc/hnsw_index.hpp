@@ -49,6 +49,8 @@ struct WalkScratch {
     ~WalkScratch();
 };
 
+struct HnswGraphProbe;  // tests/native/hnsw_graph_audit.hip: reads the graph arrays and the scratch pool
+
 class HnswIndex {
 public:
     struct CoalesceReq {  // one caller waiting in search() while coalescing is on
@@ -117,6 +119,7 @@ public:
                      uint64_t* node_ids, uint8_t* live, double* rows) const;
 
 private:
+    friend struct HnswGraphProbe;
     HnswIndex(uint64_t dim, int metric, const HnswParams& p, int device);
     int ensure_graph(uint64_t nodes, uint64_t upper_slots);
     HnswGraphView view() const;
