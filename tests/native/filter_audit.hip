@@ -213,6 +213,11 @@ int main(int argc, char** argv)
             CK(launch_scan_batch(s, metric, d_slab, d_inv, d_q, nq, n, dim, ld, d_part, &plan));
             merge_to_one(s, d_part, plan.grid, (size_t)plan.grid * KP, (int)nq, d_m0, d_m1, d_lists);
             info[0] = (uint32_t)plan.grid;
+            // lanes per row of the shape that ran: the first one of the library's list whose G * VPL is the stride
+#define VL_AUDIT_G(G, VPL) \
+    if (info[1] == 0 && (uint32_t)(G * VPL) == ld / 4) info[1] = G;
+            VL_BATCH_SHAPES(VL_AUDIT_G)
+#undef VL_AUDIT_G
         } else if (filter == BF16_SINGLE) {
             if (!scan_bf16_supported(dim, metric)) {
                 printf("FAIL no bf16 scan for dim %u metric %d\n", dim, metric);

@@ -8,8 +8,12 @@ Here, for every query, with u = 2^-24 and n = the padded row length:
   (b) completeness: no row outside the list has a host key above the list's 64th key t64 (plus the same allowance);
   (c) certificate: every row outside the list has reference score <= B(t64), every listed row <= B(its key);
   (d) ordering: (key desc, pos asc), no duplicate positions, none >= n.
+  (e) lattice cases only: the list IS the host's top 64 by (key desc, pos asc), positions and key bits, at zero tolerance.
 End-to-end answers would only notice a wrong key or a dropped row if it landed in the final top k; these checks look at
-the filter output itself.
+the filter output itself.  For the 8-query f32 batch scan (k_scan_batch) nothing else can: a query whose list fails the
+bound check is redone on the exact path and still answers like the oracle, so a list that lost rows in a mid-stream flush
+of the lazy insertion buffer is invisible from outside.  The `ordered` and `lattice` cases run that kernel under
+VL_BATCH_GRID, so that one workgroup streams the whole index and every wave flushes its buffers many times.
 """
 import os
 import struct
@@ -177,6 +181,39 @@ def family(name, rng, n, dim, nq):
         q[0::2] *= 2.0 ** -12
         q[1::2] *= 2.0 ** 12
         return rows, q
+    if name == "ordered":  # cosine / dot / Euclidean keys of query 0 rise with the storage position, those of query 1 fall
+        q0 = unit(rng, 1, dim)[0]
+        x = unit(rng, n, dim)
+        x = x[np.argsort(x @ q0, kind="stable")]
+        # The sorted gaussian projections have gaps far below one f32 rounding of a key somewhere among n rows, so the
+        # component along q0 is respaced evenly (gap 1.8 / n, thousands of roundings); the part across q0 stays and the
+        # rows stay unit: x.q0 = t, cos = t, -|x - q0|^2 = 2t - 2 all rise with t, and -q0 turns every one of them round.
+        across = x - (x @ q0)[:, None] * q0[None, :]
+        across /= np.linalg.norm(across, axis=1, keepdims=True)
+        t = np.linspace(-0.9, 0.9, n)
+        rows = t[:, None] * q0[None, :] + np.sqrt(1.0 - t * t)[:, None] * across
+        q = rng.standard_normal((nq, dim))
+        q[0] = q0
+        q[1] = -q0
+        return rows, q
+    if name in ("ordered-l1", "ordered-l1r"):  # Manhattan keys of query 0 rise (-l1r: fall) with the storage position
+        q0 = unit(rng, 1, dim)[0]
+        d = unit(rng, n, dim) - q0[None, :]
+        l1 = np.abs(d).sum(axis=1)
+        order = np.argsort(-l1, kind="stable")  # farthest first
+        d, l1 = d[order], l1[order]
+        # respaced like `ordered`: every row's offset from q0 is scaled to an evenly spaced L1 distance
+        target = np.linspace(1.25 * l1[0], 0.75 * l1[-1], n)
+        rows = q0[None, :] + d * (target / l1)[:, None]
+        q = rng.standard_normal((nq, dim))
+        q[0] = q0
+        return (rows[::-1].copy() if name == "ordered-l1r" else rows), q
+    if name == "lattice":  # small integers: every f32 partial sum is exact in any order, and the keys tie massively
+        rows = rng.integers(-4, 5, size=(n, dim)).astype(np.float64)
+        rows[~rows.any(axis=1), 0] = 1.0
+        q = rng.integers(-4, 5, size=(nq, dim)).astype(np.float64)
+        q[~q.any(axis=1), 0] = 1.0
+        return rows, q
     raise ValueError(name)
 
 
@@ -190,6 +227,8 @@ class Case:
     metrics: tuple
     env: dict = field(default_factory=dict)
     tag: str = ""
+    grid: int = 0        # f32 batch: the grid the launcher must arrive at under the case's VL_BATCH_GRID (0: not checked)
+    loops: bool = False  # f32 batch: every wave must stream at least LOOP_ROWS rows
 
     @property
     def id(self):
@@ -198,6 +237,40 @@ class Case:
 
 N1 = 8192 + 37    # not a multiple of 16 / 32 / 64: the last block is masked
 NM = 8192 + 45
+NW = 4133         # rows longer than 768 columns (the case file stays near 50 MB)
+NG = 2048 + 37    # the 512-query cases: 64 reference scans per metric
+# A wave of k_scan_batch parks the rows that beat its list's (stale) threshold in a 64-entry buffer and folds the buffer
+# in once more than 64 - RPS entries wait.  On the rising query of an `ordered` case every row beats all rows before it,
+# so a wave that streams 256 rows flushes in mid-stream at least three times however stale the threshold is.
+LOOP_ROWS = 256
+
+
+def k3_looping(fam, dim, nq, metrics, cap, tag=None, n=None, grid=1):
+    """An f32 batch case under VL_BATCH_GRID = cap that leaves `grid` workgroups to stream the whole index."""
+    n = n or (N1 if dim <= 768 else NW)
+    return Case(F32_BATCH, fam, dim, n, nq, metrics, {"VL_BATCH_GRID": str(cap)}, tag or f"grid{cap}", grid,
+                n // (4 * grid) >= LOOP_ROWS)
+
+
+# one dim per stride of VL_BATCH_SHAPES; 190, 637 and 1021 only pad to theirs (192, 640, 1024)
+K3_DIMS = (32, 64, 96, 128, 190, 256, 320, 384, 512, 637, 768, 1021, 1536)
+K3_FAMILIES = (("ordered", (COS, EUC, DOT)), ("ordered-l1", (MAN,)), ("ordered-l1r", (MAN,)), ("lattice", ALL4))
+K3_EDGE_FAMILIES = (K3_FAMILIES[0], K3_FAMILIES[3])
+K3_CASES = (
+    # every stride, all four metrics: 11 queries = two groups, which halve the cap of 2 -- one workgroup, four waves
+    [k3_looping(f, d, 11, m, 2) for d in K3_DIMS for f, m in K3_FAMILIES]
+    # grid boundaries, one group of 8 (the cap is not divided): 65 lists per query give the merge a second level whose
+    # second block holds a single list
+    + [k3_looping(f, 128, 8, m, g, grid=g) for g in (1, 64, 65) for f, m in K3_EDGE_FAMILIES]
+    # group boundaries at four lanes per row: 8 and 9 queries, and 512 = SCAN_BATCH_MAX_QUERIES (64 groups as blockIdx.y:
+    # a cap of 64 leaves each group one workgroup; the largest cap leaves 32, which fills the partial-list buffer)
+    + [k3_looping(f, 64, 8, m, 2, grid=2) for f, m in K3_EDGE_FAMILIES]
+    + [k3_looping(f, 64, 9, m, 2) for f, m in K3_EDGE_FAMILIES]
+    + [k3_looping("ordered", 64, 512, (COS, EUC, DOT), 64, n=NG), k3_looping("lattice", 64, 512, ALL4, 64, n=NG),
+       k3_looping("lattice", 64, 512, ALL4, 4096, n=NG, grid=32)]
+    # the older families once each at a wide stride, looping
+    + [k3_looping("gauss", 640, 11, ALL4, 2), k3_looping("cancel", 1024, 11, ALL4, 2), k3_looping("scales", 1021, 11, ALL4, 2)]
+)
 CASES = (
     # f32 single query: the query in the kernel arguments (k_scan), from device memory (k_scan_q64), k_scan_generic
     [Case(F32_QARG, "gauss", d, N1, 4, ALL4) for d in (128, 384, 512, 768)]
@@ -226,6 +299,7 @@ CASES = (
        for st in (2, 3, 4)]
     + [Case(MFMA_BATCH, f, d, NM, 40, BF16_METRICS) for f, d in
        (("bf16edge", 384), ("scales", 256), ("cancel", 512), ("underflow", 768), ("gemm", 384))]
+    + K3_CASES
 )
 
 
@@ -398,17 +472,57 @@ def audit_block(case, h, queries, b):
     return audited
 
 
-@pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
-def test_filter_list_against_its_bound(audit_exe, case, tmp_path):
-    rows, queries, buf = run_case(audit_exe, case, tmp_path)
+def check_ordered_construction(case, h, queries, b):
+    """The host keys of query 0 rise strictly with the storage position over the whole index (fall for `ordered-l1r`), those
+    of query 1 of `ordered` fall: asserted before the device is judged."""
+    kh, _ = host_keys(h, queries[0], case.filt, b["metric"], b["ld"])
+    step = np.diff(kh)
+    ctx = (case.id, METRIC_NAME[b["metric"]], "construction")
+    assert (step < 0.0).all() if case.fam == "ordered-l1r" else (step > 0.0).all(), ctx
+    if case.fam == "ordered":
+        kh, _ = host_keys(h, queries[1], case.filt, b["metric"], b["ld"])
+        assert (np.diff(kh) < 0.0).all(), ctx
+
+
+def check_lattice_exact(case, h, queries, b):
+    """(e): integer inputs make every f32 partial sum exact in any order (dim <= 1536: |dot| <= 24 576, squared distance
+    <= 98 304, L1 <= 12 288, all below 2^24) and the cosine key one f32 product with the device's own 1/norm, so the host
+    key is the device's bit for bit and the list has to be the host's top 64 by (key desc, pos asc)."""
+    n, metric = b["n"], b["metric"]
+    for qi in range(b["nq"]):
+        kh, _ = host_keys(h, queries[qi], case.filt, metric, b["ld"])
+        if metric != COS:
+            assert (kh == np.round(kh)).all() and np.abs(kh).max() < 2.0 ** 24
+        kh = f32(kh)
+        want = np.lexsort((np.arange(n), -kh))[:KP]
+        ctx = (case.id, METRIC_NAME[metric], qi)
+        got = b["pos"][qi].astype(np.int64)
+        assert got.tolist() == want.tolist(), (ctx, "(e) positions", np.nonzero(got != want)[0][:4], got[:4], want[:4])
+        assert (b["key"][qi] == kh[want]).all(), (ctx, "(e) key bits")
+
+
+def check_case(exe, case, tmp_path):
+    rows, queries, buf = run_case(exe, case, tmp_path)
     blocks = parse_blocks(buf, len(case.metrics))
     h = HostRows(rows)
     R = float(np.sqrt(dev_sumsq(rows)).max())
     for b in blocks:
         assert b["R"] == R, (case.id, "IngestStats max norm", b["R"], R)
+        if case.fam.startswith("ordered"):
+            check_ordered_construction(case, h, queries, b)
         audited = audit_block(case, h, queries, b)
         # an MFMA list may be empty (overflow -> exact path), but the audit must not be vacuous
         assert audited >= (b["nq"] + 1) // 2, (case.id, METRIC_NAME[b["metric"]], audited, b["nq"])
+        if case.filt == F32_BATCH:
+            grid, lanes = b["info"][0], b["info"][1]
+            assert audited == b["nq"], (case.id, "an f32 batch list was skipped", audited)
+            assert lanes == (4 if b["ld"] <= 64 else 8 if b["ld"] <= 512 else 16), (case.id, "lanes per row", b["ld"], lanes)
+            if case.grid:
+                assert grid == case.grid, (case.id, "grid", grid)
+            if case.loops:  # rows per wave: the case is there for the mid-stream flushes
+                assert b["n"] // (4 * grid) >= LOOP_ROWS, (case.id, "waves do not loop", b["n"], grid)
+            if case.fam == "lattice":
+                check_lattice_exact(case, h, queries, b)
         if case.filt == MFMA_BATCH:
             assert b["info"][3] == (0 if case.env.get("VL_MFMA_KERNEL") == "tile" else 1), b["info"]
             if "chunks" in case.tag:
@@ -416,3 +530,7 @@ def test_filter_list_against_its_bound(audit_exe, case, tmp_path):
             if "stages" in case.tag:
                 assert b["info"][2] == int(case.env["VL_MFMA_STAGES"]), b["info"]
 
+
+@pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
+def test_filter_list_against_its_bound(audit_exe, case, tmp_path):
+    check_case(audit_exe, case, tmp_path)

@@ -1,5 +1,6 @@
-"""Hardware unit test of the wave-level top-64 list (insert / offer) against a host model:
-tests/native/toplist_test.hip is compiled with hipcc and run on the GPU."""
+"""Hardware unit test of the wave-level top-64 list (insert / offer, and the f32 batch scan's flush: sort64_reversed of
+partly filled buffers and merge_reversed into an empty, half full or full list, ties across the 64th place, the threshold
+copy) against a host model: tests/native/toplist_test.hip is compiled with hipcc and run on the GPU."""
 import os
 import subprocess
 

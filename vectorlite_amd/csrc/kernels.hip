@@ -432,6 +432,10 @@ __global__ __launch_bounds__(256) void k_scan_batch(const f32x4* __restrict__ sl
     // against is a little stale in between (more rows pass than would one by one); nothing that belongs is ever dropped, and
     // the list after a merge is the top 64 of everything the wave has seen: the same lists as before, bit for bit.
     __shared__ Cand32 cbuf[4][QB][WAVE];
+    // qs + sh + cbuf, static: 67 584 B for the widest shape (16 lanes x 24 chunks, stride 1536).  That is past the 64 KB a
+    // workgroup gets on every CDNA part before gfx950 (160 KB): this build is gfx950-only.
+    static_assert(sizeof(f32x4) * QB * LD4 + sizeof(Cand32) * 4 * WAVE + sizeof(Cand32) * 4 * QB * WAVE <= 160u * 1024u,
+                  "k_scan_batch: static LDS of this shape exceeds a gfx950 workgroup's 160 KB");
 
     const int lane = lane_id();
     const int wave = threadIdx.x >> 6;
@@ -2096,7 +2100,7 @@ hipError_t launch_scan(hipStream_t s, int metric, const float* slab, const float
 // The first shape whose G * VPL matches the stride runs.  Strides 32 and 64 take FOUR lanes per row (16 rows per wave step):
 // at such lengths a (row, query) pair is ~35 instructions of which 19 are the cross-lane reduction, the key compare, the
 // ballot and the branch -- per ROW costs that 16 rows per step halve (round 4, `tools/manhattan_probe.py`).
-#define VL_BATCH_SHAPES(X) X(4, 2) X(4, 4) X(8, 1) X(8, 2) X(8, 3) X(8, 4) X(8, 6) X(8, 8) X(8, 10) X(8, 12) X(8, 16) X(16, 10) X(16, 12) X(16, 16) X(16, 24)
+#define VL_BATCH_SHAPES(X) X(4, 2) X(4, 4) X(8, 3) X(8, 4) X(8, 6) X(8, 8) X(8, 10) X(8, 12) X(8, 16) X(16, 10) X(16, 12) X(16, 16) X(16, 24)
 
 bool scan_batch_supported(uint32_t ld)
 {
