@@ -380,6 +380,30 @@ int vl_index_hnsw_graph_info(const vl_index *h, uint64_t *n_nodes, uint32_t *ent
 int vl_index_hnsw_graph_export(const vl_index *h, uint8_t *level, uint32_t *upper_off, uint32_t *cnt0, uint32_t *nbr0,
                                uint32_t *cntU, uint32_t *nbrU, uint64_t *node_ids, uint8_t *live, double *rows);
 
+/* HNSW handle: the inverse of vl_index_hnsw_graph_export, on an EMPTY handle (no node yet) created with the dim, metric,
+ * m, m0 and seed the graph belongs to.  Node i becomes storage position i with row rows[i * dim ..] (rows_on_device as
+ * vl_index_add_bulk's values_on_device), id node_ids[i] and live[i] (0 = tombstoned, 1 = live); its lists are taken as
+ * given, entry order included.  level[] and upper_off[] are NOT inputs: they follow from the level law (vl_hnsw_level)
+ * and its prefix sum, n_upper must be their total, and entry / max_level are the first node of the top level.  Before
+ * any device work the lists are validated on the host: counts within m0 / m, every neighbour < n, not the list's owner,
+ * of a level >= the list's layer (G3), none named twice in a list (G4); a violation is VL_ERR_INVALID_ARG with the graph
+ * audit's "G3: ..." / "G4: ..." text.  An id carried by two LIVE nodes is VL_ERR_DUP_ID ("Vector ID {} already exists");
+ * a tombstoned node may carry any id.  What the export does not carry -- the f32 distance stored with every edge and the
+ * layer-0 in-degree counter -- is recomputed on the device, bit for bit what the build stores.  *out_orphans (may be
+ * NULL): nodes without an incoming layer-0 edge (reported, never refused; 0 when n < 2).  A handle that is not HNSW or
+ * not empty is VL_ERR_INVALID_ARG.  Every refusal and every failure leaves the handle empty and accepting adds.  After
+ * VL_OK the handle answers, exports, clones and grows like the handle the arrays were exported from. */
+int vl_index_hnsw_graph_import(vl_index *h, uint64_t n, const uint64_t *node_ids, const uint8_t *live, const double *rows,
+                               int rows_on_device, const uint32_t *cnt0, const uint32_t *nbr0, uint64_t n_upper,
+                               const uint32_t *cntU, const uint32_t *nbrU, uint64_t *out_orphans);
+/* Milliseconds of the handle's last import: out_ms[0] host validation, [1] row ingest, [2] uploads, [3] the edge-key
+ * kernel, [4] the in-degree kernel (HIP events around the kernels, the host clock around the rest). */
+int vl_index_hnsw_import_times(const vl_index *h, double *out_ms5);
+/* HNSW handle: the four build parameters (vl_hnsw_create_ex); any pointer may be NULL. */
+int vl_index_hnsw_params(const vl_index *h, uint32_t *m, uint32_t *m0, uint32_t *ef_construction, uint64_t *seed);
+/* The level law: the top layer (0 .. 15) of the node at insertion position `node` in an index of that seed and m. */
+int vl_hnsw_level(uint64_t seed, uint64_t node, uint32_t m);
+
 /* get_vector(id) (src/index/flat.rs:129-131): first row with that id -> out[dim];
  * VL_ERR_NOT_FOUND stands for None. */
 int vl_index_get_vector(const vl_index *h, uint64_t id, double *out_values);

@@ -17,6 +17,8 @@ from __future__ import annotations
 
 import ctypes as C
 import enum
+import json
+import os
 import threading
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional, Sequence, Tuple
@@ -27,7 +29,7 @@ from . import _lib
 
 __all__ = [
     "SimilarityMetric", "Vector", "SearchResult", "FlatIndex", "MultiFlatIndex", "HNSWIndex", "VectorLiteError", "DimensionMismatch",
-    "MetricMismatch", "NaNScore", "DeviceError", "IndexOpError", "IdFilter", "GroupTable", "hnsw_score", "runtime_info",
+    "MetricMismatch", "NaNScore", "DeviceError", "IndexOpError", "IdFilter", "GroupTable", "hnsw_score", "hnsw_level", "runtime_info",
     "PATH_FAST", "PATH_EXACT_SELECT", "PATH_EXACT_SORT",
 ]
 
@@ -135,6 +137,31 @@ def runtime_info() -> Tuple[int, int]:
 def hnsw_score(d_u64: int, metric: int) -> float:
     """convert_distance_to_similarity(d as f64 / 1000.0, metric) (src/index/hnsw.rs:51-75, :478-479)."""
     return _lib.load().vl_hnsw_score(int(d_u64), int(metric))
+
+
+def hnsw_level(seed: int, node: int, m: int) -> int:
+    """The level law (vl_hnsw_level): the top layer, 0 .. 15, of the node at insertion position `node` in an HNSW index
+    created with that seed and m.  A builder outside the library lays out its upper lists by it."""
+    return int(_lib.load().vl_hnsw_level(int(seed), int(node), int(m)))
+
+
+def hnsw_levels(seed: int, n: int, m: int) -> np.ndarray:
+    """hnsw_level for the nodes 0 .. n - 1 as a uint8 array.  The hash is restated in numpy (exact integer arithmetic);
+    a level is taken from numpy's logarithm only where it sits clear of a boundary, otherwise from the library."""
+    if n == 0 or m < 2:
+        return np.zeros(n, np.uint8)
+    with np.errstate(over="ignore"):
+        x = np.uint64(seed) * np.uint64(0x100000001B3) + np.arange(n, dtype=np.uint64)
+        x = x + np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        x = x ^ (x >> np.uint64(31))
+    u = ((x >> np.uint64(11)).astype(np.float64) + 1.0) * (1.0 / 9007199254740992.0)
+    t = -np.log(u) / np.log(float(m))
+    lv = np.clip(np.floor(t), 0, 15).astype(np.uint8)
+    for i in np.nonzero(np.abs(t - np.rint(t)) < 1e-9)[0]:  # a last-place difference between two logarithms could move these
+        lv[i] = hnsw_level(seed, int(i), m)
+    return lv
 
 
 def last_path() -> int:
@@ -991,6 +1018,136 @@ class HNSWIndex:
             g[key] = g[key][:nn]
         g["cntU"], g["nbrU"] = g["cntU"][:ns], g["nbrU"][:ns]
         return g
+
+    def params(self) -> Dict[str, int]:
+        """The four build parameters: {"m", "m0", "ef_construction", "seed"} (vl_index_hnsw_params)."""
+        m, m0, efc, seed = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        _raise(self._L.vl_index_hnsw_params(self._h, C.byref(m), C.byref(m0), C.byref(efc), C.byref(seed)))
+        return {"m": int(m.value), "m0": int(m0.value), "ef_construction": int(efc.value), "seed": int(seed.value)}
+
+    _GRAPH_ARRAYS = (("cnt0", np.uint32, 1), ("nbr0", np.uint32, 2), ("cntU", np.uint32, 1), ("nbrU", np.uint32, 2),
+                     ("node_ids", np.uint64, 1), ("live", np.uint8, 1), ("rows", np.float64, 2))
+
+    def _import_graph(self, g) -> int:
+        """vl_index_hnsw_graph_import of the dict graph(with_rows=True) returns into this (empty) index; returns the
+        number of nodes without an incoming layer-0 edge.  Shapes, dtypes and -- where the dict carries them -- level[]
+        and upper_off[] against the level law of this index's (seed, m) are checked here, the lists by the library."""
+        p, dim = self.params(), self.dimension()
+        for key in ("m", "m0") + tuple(k for k, _, _ in self._GRAPH_ARRAYS):
+            if key not in g:
+                raise IndexOpError(f"graph import: the graph has no '{key}'")
+        if int(g["m"]) != p["m"] or int(g["m0"]) != p["m0"]:
+            raise IndexOpError(f"graph import: the graph has m = {int(g['m'])}, m0 = {int(g['m0'])}, the index m = {p['m']}, m0 = {p['m0']}")
+        a = {}
+        for key, dtype, ndim in self._GRAPH_ARRAYS:
+            x = np.asarray(g[key])
+            if x.dtype != dtype or x.ndim != ndim:
+                raise IndexOpError(f"graph import: '{key}' must be a {ndim}-d {np.dtype(dtype).name} array, got {x.ndim}-d {x.dtype.name}")
+            a[key] = np.ascontiguousarray(x)
+        n, ns = a["cnt0"].shape[0], a["cntU"].shape[0]
+        if "n" in g and int(g["n"]) != n:
+            raise IndexOpError(f"graph import: n = {int(g['n'])} but cnt0 holds {n} entries")
+        want = {"nbr0": (n, p["m0"]), "nbrU": (ns, p["m"]), "node_ids": (n,), "live": (n,), "rows": (n, dim)}
+        for key, shape in want.items():
+            if a[key].shape != shape:
+                raise IndexOpError(f"graph import: '{key}' has shape {a[key].shape}, expected {shape}")
+        if "level" in g or "upper_off" in g:
+            law = hnsw_levels(p["seed"], n, p["m"])
+            off = np.cumsum(law, dtype=np.uint64) - law
+            for key, ref in (("level", law), ("upper_off", off)):
+                if key not in g:
+                    continue
+                x = np.asarray(g[key])
+                if x.shape != (n,) or not np.array_equal(x.astype(np.uint64), ref.astype(np.uint64)):
+                    raise IndexOpError(f"graph import: '{key}' is not the level law of seed {p['seed']}, m {p['m']}: "
+                                       "the graph was exported from an index with another seed or m")
+        vp = lambda x: C.c_void_p(x.ctypes.data) if x.size else C.c_void_p()  # noqa: E731
+        orphans = C.c_uint64(0)
+        rc = self._L.vl_index_hnsw_graph_import(self._h, n, vp(a["node_ids"]), vp(a["live"]), vp(a["rows"]), 0, vp(a["cnt0"]),
+                                                vp(a["nbr0"]), ns, vp(a["cntU"]), vp(a["nbrU"]), C.byref(orphans))
+        if rc in (VL_ERR_INVALID_ARG, VL_ERR_DUP_ID):
+            raise IndexOpError(_last_error())
+        _raise(rc)
+        return int(orphans.value)
+
+    def import_times(self) -> Dict[str, float]:
+        """Milliseconds of the last import: host validation, row ingest, uploads, edge-key kernel, in-degree kernel."""
+        ms = (C.c_double * 5)()
+        _raise(self._L.vl_index_hnsw_import_times(self._h, ms))
+        return dict(zip(("validate_ms", "ingest_ms", "upload_ms", "edge_key_kernel_ms", "indegree_kernel_ms"), (float(x) for x in ms)))
+
+    @classmethod
+    def from_graph(cls, g, dim: int, metric: int, device: int = 0, ef_construction: int = 400, seed: int = 0,
+                   m: Optional[int] = None, m0: Optional[int] = None) -> "HNSWIndex":
+        """An index from the dict graph(with_rows=True) returns, without rebuilding: the lists are taken as given, the
+        levels follow from (seed, m), and what the dict does not carry is recomputed on the device.  m and m0 are read
+        from the dict (if named they must agree); pass the exporter's params().  IndexOpError with the library's text
+        for a list that breaks the graph's invariants, a duplicate live id or a graph of another seed.  _meta starts
+        empty."""
+        for key, given in (("m", m), ("m0", m0)):
+            if key not in g:
+                raise IndexOpError(f"graph import: the graph has no '{key}'")
+            if given is not None and int(given) != int(g[key]):
+                raise IndexOpError(f"graph import: {key} = {int(given)} was asked for, the graph has {int(g[key])}")
+        idx = cls(dim, metric, device=device, m=int(g["m"]), m0=int(g["m0"]), ef_construction=ef_construction, seed=seed)
+        idx._import_graph(g)
+        return idx
+
+    def save_snapshot(self, path: str) -> None:
+        """The whole index -- graph, rows, tombstones, parameters and _meta -- as one .npz file (written under a
+        temporary name and renamed).  load_snapshot() brings it back without rebuilding."""
+        g, p = self.graph(with_rows=True), self.params()
+        meta = json.dumps([[int(i), t, md] for i, (t, md) in self._meta.items()])
+        tmp = f"{path}.tmp.{os.getpid()}"
+        try:
+            with open(tmp, "wb") as f:
+                np.savez(f, format=np.array(self._SNAPSHOT_FORMAT), dim=np.uint64(self.dimension()), metric=np.int32(int(self.metric())),
+                         m=np.uint32(p["m"]), m0=np.uint32(p["m0"]), ef_construction=np.uint32(p["ef_construction"]),
+                         seed=np.uint64(p["seed"]), entry=np.uint32(g["entry"]), max_level=np.int32(g["max_level"]),
+                         meta=np.array(meta), **{k: g[k] for k in self._SNAPSHOT_ARRAYS})
+            os.replace(tmp, path)
+        finally:
+            if os.path.exists(tmp):
+                os.unlink(tmp)
+
+    _SNAPSHOT_FORMAT = "vectorlite-hnsw-snapshot-1"
+    _SNAPSHOT_ARRAYS = ("level", "upper_off", "cnt0", "nbr0", "cntU", "nbrU", "node_ids", "live", "rows")
+
+    @classmethod
+    def load_snapshot(cls, path: str, device: int = 0) -> "HNSWIndex":
+        """The index save_snapshot() wrote.  PersistenceError for a file that is missing, cut short, lacks a member, has
+        a member of the wrong shape or type, or holds a list the import refuses."""
+        from .persistence import FileNotFound, PersistenceError
+        if not os.path.exists(path):
+            raise FileNotFound(f"File not found: {path}")
+        try:
+            with np.load(path, allow_pickle=False) as z:
+                if str(z["format"][()]) != cls._SNAPSHOT_FORMAT:
+                    raise PersistenceError(f"Expected format '{cls._SNAPSHOT_FORMAT}', got '{z['format'][()]}'")
+                s = {k: z[k][()] for k in ("dim", "metric", "m", "m0", "ef_construction", "seed", "entry", "max_level")}
+                for k, v in s.items():
+                    if np.ndim(v) != 0 or not np.issubdtype(np.asarray(v).dtype, np.integer):
+                        raise PersistenceError(f"snapshot member '{k}' is not an integer scalar")
+                g = {k: z[k] for k in cls._SNAPSHOT_ARRAYS}
+                meta = json.loads(str(z["meta"][()]))
+        except PersistenceError:
+            raise
+        except Exception as e:  # a cut-short or foreign file: zipfile, numpy and json each have their own error types
+            raise PersistenceError(f"cannot read HNSW snapshot {path}: {type(e).__name__}: {e}") from e
+        g["m"], g["m0"] = int(s["m"]), int(s["m0"])
+        try:
+            idx = cls.from_graph(g, int(s["dim"]), int(s["metric"]), device=device, ef_construction=int(s["ef_construction"]),
+                                 seed=int(s["seed"]))
+        except (IndexOpError, ValueError) as e:
+            raise PersistenceError(f"HNSW snapshot {path} refused: {e}") from e
+        got = idx.graph()
+        if g["cnt0"].shape[0] and (got["entry"], got["max_level"]) != (int(s["entry"]), int(s["max_level"])):
+            raise PersistenceError(f"HNSW snapshot {path} refused: entry / max_level do not follow from its levels")
+        try:
+            idx._meta = {int(i): (t, md) for i, t, md in meta}
+        except Exception as e:
+            raise PersistenceError(f"HNSW snapshot {path}: malformed meta: {e}") from e
+        return idx
 
     def set_min_beam(self, min_beam: int) -> None:
         """Opt-in beam floor of searches that name no ef; default 0 = the reference's strict ef = min(k, len)."""

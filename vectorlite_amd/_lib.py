@@ -28,6 +28,7 @@ SYMBOLS = [
     "vl_index_profile_enable", "vl_index_profile_read", "vl_index_last_scan", "vl_index_last_filter", "vl_runtime_info",
     "vl_comm_unique_id", "vl_comm_create", "vl_comm_destroy", "vl_comm_world", "vl_comm_rank", "vl_comm_profile_enable", "vl_comm_profile_read", "vl_comm_record_paths",
     "vl_index_hnsw_set_min_beam", "vl_index_hnsw_set_navigation", "vl_index_hnsw_graph_info", "vl_index_hnsw_graph_export",
+    "vl_index_hnsw_graph_import", "vl_index_hnsw_import_times", "vl_index_hnsw_params", "vl_hnsw_level",
     "vl_shard_sync", "vl_shard_search_batch", "vl_shard_packed_words", "vl_shard_search_local", "vl_shard_merge", "vl_shard_search_batch_dev", "vl_shard_search_local_dev",
 ]
 
@@ -127,6 +128,10 @@ def load() -> C.CDLL:
     p_u32 = C.POINTER(C.c_uint32)
     sig("vl_index_hnsw_graph_info", i32, [vp, p_u64, p_u32, p_i32, p_u32, p_u32, p_u64])
     sig("vl_index_hnsw_graph_export", i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    sig("vl_index_hnsw_graph_import", i32, [vp, u64, vp, vp, vp, i32, vp, vp, u64, vp, vp, p_u64])
+    sig("vl_index_hnsw_import_times", i32, [vp, p_f64])
+    sig("vl_index_hnsw_params", i32, [vp, p_u32, p_u32, p_u32, p_u64])
+    sig("vl_hnsw_level", i32, [u64, u64, C.c_uint32])
     sig("vl_index_profile_enable", i32, [vp, i32])
     sig("vl_index_profile_read", i32, [vp, p_u64, p_f64, p_u64])
     sig("vl_index_last_scan", i32, [vp, p_i32, p_i32, p_i32])

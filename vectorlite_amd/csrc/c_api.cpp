@@ -1036,6 +1036,45 @@ int vl_index_hnsw_graph_export(const vl_index* h, uint8_t* level, uint32_t* uppe
     });
 }
 
+int vl_index_hnsw_graph_import(vl_index* h, uint64_t n, const uint64_t* node_ids, const uint8_t* live, const double* rows,
+                               int rows_on_device, const uint32_t* cnt0, const uint32_t* nbr0, uint64_t n_upper,
+                               const uint32_t* cntU, const uint32_t* nbrU, uint64_t* out_orphans)
+{
+    return guarded([&]() -> int {
+        if (!h || !h->hnsw) {
+            vl::set_last_error("this entry point needs an HNSW index handle");
+            return VL_ERR_INVALID_ARG;
+        }
+        return h->hnsw->graph_import(n, node_ids, live, rows, rows_on_device != 0, cnt0, nbr0, n_upper, cntU, nbrU, out_orphans);
+    });
+}
+
+int vl_index_hnsw_import_times(const vl_index* h, double* out_ms5)
+{
+    if (!h || !h->hnsw || !out_ms5) {
+        vl::set_last_error("this entry point needs an HNSW index handle");
+        return VL_ERR_INVALID_ARG;
+    }
+    h->hnsw->last_import_ms(out_ms5);
+    return VL_OK;
+}
+
+int vl_index_hnsw_params(const vl_index* h, uint32_t* m, uint32_t* m0, uint32_t* ef_construction, uint64_t* seed)
+{
+    if (!h || !h->hnsw) {
+        vl::set_last_error("this entry point needs an HNSW index handle");
+        return VL_ERR_INVALID_ARG;
+    }
+    const vl::HnswParams& p = h->hnsw->params();
+    if (m) *m = p.m;
+    if (m0) *m0 = p.m0;
+    if (ef_construction) *ef_construction = p.ef_construction;
+    if (seed) *seed = p.seed;
+    return VL_OK;
+}
+
+int vl_hnsw_level(uint64_t seed, uint64_t node, uint32_t m) { return vl::hnsw_level(seed, node, m); }
+
 int vl_index_hnsw_set_min_beam(vl_index* h, uint32_t min_beam)
 {
     if (!h || !h->hnsw) {

@@ -1016,6 +1016,62 @@ __global__ __launch_bounds__(256) void k_hnsw_insert_link(HnswGraphView g, uint3
     }
 }
 
+// Import: the edge keys of lists that came from outside (HnswIndex::graph_import).  The build stores with every edge
+// (i, v) the f32 key of the LARGER index as the query against the smaller as the candidate -- the new node p walked with
+// its own row and kept `dc`, and the link phase handed the same value to the neighbour's list -- so that is recomputed
+// here with the same routine: row_distance_f32, its query pointer at the owner's or the neighbour's slab row in global
+// memory.  One wave per node, a lane pair per entry (rounds of 32 when a list is longer), layer 0 and then the node's
+// upper lists.  The lists passed hnsw_import_plan.hpp before the launch: counts within the capacity, entries below n,
+// upper slots within the node's own; the clamps below only restate that.
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_hnsw_import_keys(HnswGraphView g, uint32_t n)
+{
+    const int lane = lane_id();
+    const int half = lane >> 5, nl = lane & 31;
+    for (uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += gridDim.x * 4) {
+        const int lp = g.level[i] < HNSW_MAX_LEVEL ? g.level[i] : HNSW_MAX_LEVEL;
+        for (int layer = 0; layer <= lp; ++layer) {
+            const uint32_t cap = layer == 0 ? g.m0 : g.m;
+            const uint32_t* nb;
+            unsigned long long* nd;
+            uint32_t cnt;
+            if (layer == 0) {
+                nb = g.nbr0 + (size_t)i * g.m0;
+                nd = g.dist0 + (size_t)i * g.m0;
+                cnt = g.cnt0[i];
+            } else {
+                const uint32_t us = g.upper_off[i] + (uint32_t)(layer - 1);
+                nb = g.nbrU + (size_t)us * g.m;
+                nd = g.distU + (size_t)us * g.m;
+                cnt = g.cntU[us];
+            }
+            cnt = cnt < cap ? cnt : cap;
+            for (uint32_t base = 0; base < cnt; base += 32) {
+                const uint32_t t = base + (uint32_t)nl;
+                const uint32_t v = t < cnt ? nb[t] : HNSW_NONE;
+                if (v < n) {  // lanes l and l + 32 read the same entry: both halves of a pair are in or out together
+                    const uint32_t a = i > v ? i : v, b = i > v ? v : i;
+                    const unsigned long long key = row_distance_f32<METRIC>(g, b, g.slab + (size_t)a * g.ld, g.inv_norm[a], half);
+                    if (half == 0) nd[t] = key;
+                }
+            }
+        }
+    }
+}
+
+// indeg0[v] = number of layer-0 entries naming v (zeroed by the caller): one atomic per entry
+__global__ __launch_bounds__(256) void k_hnsw_import_indeg(HnswGraphView g, uint32_t n)
+{
+    const size_t total = (size_t)n * g.m0;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t i = (uint32_t)(e / g.m0), t = (uint32_t)(e % g.m0);
+        if (t < g.cnt0[i]) {
+            const uint32_t v = g.nbr0[e];
+            if (v < n) atomicAdd(&g.indeg0[v], 1u);
+        }
+    }
+}
+
 template <typename F>
 hipError_t dispatch_metric(int metric, F&& f)
 {
@@ -1151,6 +1207,28 @@ hipError_t launch_hnsw_insert_link(hipStream_t s, const HnswGraphView& g, uint32
     const uint32_t blocks = (n + 3) / 4;
     const int grid = (int)(blocks < 4096 ? blocks : 4096);
     hipLaunchKernelGGL(k_hnsw_insert_link, dim3(grid), dim3(256), 0, s, g, first, n, max_level);
+    return hipGetLastError();
+}
+
+hipError_t launch_hnsw_import_keys(hipStream_t s, int metric, const HnswGraphView& g, uint32_t n)
+{
+    if (n == 0) return hipSuccess;
+    if (g.m0 > 64 || g.m > 64 || g.m0 == 0 || g.m == 0 || (uint64_t)n > g.cap) return hipErrorInvalidValue;
+    const uint32_t blocks = (n + 3) / 4;
+    const int grid = (int)(blocks < 8192 ? blocks : 8192);
+    return dispatch_metric(metric, [&](auto M) -> hipError_t {
+        hipLaunchKernelGGL(k_hnsw_import_keys<decltype(M)::value>, dim3(grid), dim3(256), 0, s, g, n);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_hnsw_import_indeg(hipStream_t s, const HnswGraphView& g, uint32_t n)
+{
+    if (n == 0) return hipSuccess;
+    if (g.m0 == 0 || (uint64_t)n > g.cap) return hipErrorInvalidValue;
+    const uint64_t blocks = ((uint64_t)n * g.m0 + 255) / 256;
+    const int grid = (int)(blocks < 8192 ? blocks : 8192);
+    hipLaunchKernelGGL(k_hnsw_import_indeg, dim3(grid), dim3(256), 0, s, g, n);
     return hipGetLastError();
 }
 

@@ -83,4 +83,12 @@ hipError_t launch_hnsw_insert_search(hipStream_t s, int metric, const HnswGraphV
                                      uint32_t ef_construction, uint32_t entry, int max_level, uint32_t flags);
 hipError_t launch_hnsw_insert_link(hipStream_t s, const HnswGraphView& g, uint32_t first, uint32_t n, int max_level);
 
+// Import (HnswIndex::graph_import): what an exported graph does not carry, recomputed for the nodes [0, n) whose lists,
+// levels and upper offsets are already on the device and passed hnsw_import_plan.hpp.
+// _keys fills dist0 / distU for every stored edge with the build's f32 key, bit for bit (the larger node index as the
+// query row, the smaller as the candidate); _indeg counts the layer-0 entries naming each node into indeg0, which the
+// caller has zeroed.
+hipError_t launch_hnsw_import_keys(hipStream_t s, int metric, const HnswGraphView& g, uint32_t n);
+hipError_t launch_hnsw_import_indeg(hipStream_t s, const HnswGraphView& g, uint32_t n);
+
 }  // namespace vl

@@ -7,8 +7,11 @@
 #include "hnsw_index.hpp"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
+
+#include "hnsw_import_plan.hpp"
 
 namespace vl {
 
@@ -78,6 +81,8 @@ int regrow(T** p, uint64_t old_count, uint64_t new_count, hipStream_t s, bool ze
     return OK;
 }
 }  // namespace
+
+int hnsw_level(uint64_t seed, uint64_t node, uint32_t m) { return m < 2 ? 0 : draw_level(seed, node, m); }
 
 HnswIndex::HnswIndex(uint64_t dim, int metric, const HnswParams& p, int device)
     : dim_(dim), metric_(metric), params_(p), device_(device)
@@ -605,6 +610,184 @@ int HnswIndex::graph_export(uint8_t* level, uint32_t* upper_off, uint32_t* cnt0,
     if (cntU && n_upper_) VL_HIP(hipMemcpy(cntU, d_cntU_, n_upper_ * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (nbrU && n_upper_) VL_HIP(hipMemcpy(nbrU, d_nbrU_, n_upper_ * params_.m * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (rows) VL_HIP(hipMemcpy(rows, store_->device_master(), n * dim_ * sizeof(double), hipMemcpyDeviceToHost));
+    return OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// import (the inverse of graph_export; DESIGN.md "Importing a graph")
+// ---------------------------------------------------------------------------------------------
+void HnswIndex::last_import_ms(double out[5]) const
+{
+    std::shared_lock<RwLock> lk(mu_);
+    for (int i = 0; i < 5; ++i) out[i] = import_ms_[i];
+}
+
+int HnswIndex::graph_import(uint64_t n, const uint64_t* node_ids, const uint8_t* live, const double* rows, bool rows_on_device,
+                            const uint32_t* cnt0, const uint32_t* nbr0, uint64_t n_upper, const uint32_t* cntU,
+                            const uint32_t* nbrU, uint64_t* out_orphans)
+{
+    using clock = std::chrono::steady_clock;
+    auto ms_since = [](clock::time_point t) { return std::chrono::duration<double, std::milli>(clock::now() - t).count(); };
+    std::unique_lock<RwLock> lk(mu_);
+    if (n_nodes_ != 0 || store_->len() != 0) {
+        set_last_error("HNSW graph import needs an empty index: this one holds " + std::to_string(n_nodes_) + " nodes");
+        return ERR_INVALID_ARG;
+    }
+    if (out_orphans) *out_orphans = 0;
+    if (n == 0) {
+        if (n_upper != 0) {
+            set_last_error("G1: n_upper " + std::to_string(n_upper) + " != total of the levels 0");
+            return ERR_INVALID_ARG;
+        }
+        return OK;
+    }
+    if (n >= 0x7FFFFFF0ull) {
+        set_last_error("HNSW node count exceeds 2^31");
+        return ERR_INVALID_ARG;
+    }
+    if (!node_ids || !live || !rows || !cnt0 || !nbr0 || (n_upper && (!cntU || !nbrU))) {
+        set_last_error("HNSW graph import: a required array is null");
+        return ERR_INVALID_ARG;
+    }
+
+    // ---- host: levels from the level law, the structural pass, the id map.  Nothing on the device has been touched.
+    clock::time_point t0 = clock::now();
+    std::vector<uint8_t> lv(n);
+    std::vector<uint32_t> off(n);
+    uint64_t upper = 0;
+    int top = -1;
+    uint32_t first_top = HNSW_NONE;
+    for (uint64_t i = 0; i < n; ++i) {
+        const int l = hnsw_level(params_.seed, i, params_.m);
+        lv[i] = (uint8_t)l;
+        off[i] = (uint32_t)upper;
+        upper += (uint64_t)l;
+        if (l > top) {  // G2: the first node of the top level
+            top = l;
+            first_top = (uint32_t)i;
+        }
+    }
+    if (upper != n_upper) {
+        set_last_error("G1: n_upper " + std::to_string(n_upper) + " != total of the levels " + std::to_string(upper) +
+                       " (level law of seed " + std::to_string(params_.seed) + ", m " + std::to_string(params_.m) + ")");
+        return ERR_INVALID_ARG;
+    }
+    {
+        const std::string v = hnsw_import_check(n, params_.m, params_.m0, lv.data(), off.data(), cnt0, nbr0, cntU, nbrU);
+        if (!v.empty()) {
+            set_last_error(v);
+            return ERR_INVALID_ARG;
+        }
+    }
+    std::unordered_map<uint64_t, uint32_t> ids;
+    uint64_t alive = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (live[i] > 1) {
+            set_last_error("G8: live flag " + std::to_string(live[i]) + " is neither 0 nor 1 (node " + std::to_string(i) + ")");
+            return ERR_INVALID_ARG;
+        }
+        if (!live[i]) continue;  // a tombstoned node may carry an id a later live node has
+        if (!ids.emplace(node_ids[i], (uint32_t)i).second) {
+            set_last_error("Vector ID " + std::to_string(node_ids[i]) + " already exists");
+            return ERR_DUP_ID;
+        }
+        ++alive;
+    }
+    std::vector<uint64_t> h_ids(node_ids, node_ids + n);  // every host allocation of the commit is made before the device work
+    std::vector<uint8_t> h_live(live, live + n);
+    std::vector<uint32_t> h_indeg(out_orphans ? n : 0);
+    double t_ms[5] = {ms_since(t0), 0, 0, 0, 0};
+
+    // ---- device.  From here on a failure takes the rows back and re-zeroes what the build expects to find zero.
+    VL_HIP(hipSetDevice(device_));
+    struct Undo {
+        HnswIndex* h;
+        bool armed = true;
+        ~Undo()
+        {
+            if (!armed) return;
+            h->store_->truncate(0);
+            h->zero_graph_counters();
+        }
+    } undo{this};
+    VL_TRY(ensure_graph(n, n_upper));
+    VL_TRY(zero_graph_counters());  // an earlier refused import may have left counts behind (G7: tails are zero)
+    t0 = clock::now();
+    VL_TRY(store_->reserve(n));
+    VL_TRY(store_->add_bulk(node_ids, rows, n, /*validate=*/false, rows_on_device));
+    t_ms[1] = ms_since(t0);
+    t0 = clock::now();
+    auto up = [&](void* dst, const void* src, size_t bytes) -> int {
+        if (bytes) VL_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream_));
+        return OK;
+    };
+    VL_TRY(up(d_level_, lv.data(), n));
+    VL_TRY(up(d_upper_off_, off.data(), n * sizeof(uint32_t)));
+    VL_TRY(up(d_cnt0_, cnt0, n * sizeof(uint32_t)));
+    VL_TRY(up(d_nbr0_, nbr0, n * params_.m0 * sizeof(uint32_t)));
+    VL_TRY(up(d_cntU_, cntU, n_upper * sizeof(uint32_t)));
+    VL_TRY(up(d_nbrU_, nbrU, n_upper * params_.m * sizeof(uint32_t)));
+    VL_TRY(up(d_node_id_, node_ids, n * sizeof(uint64_t)));
+    VL_TRY(up(d_live_, live, n));
+    VL_HIP(hipStreamSynchronize(stream_));
+    t_ms[2] = ms_since(t0);
+    {
+        struct Events {
+            hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+            ~Events()
+            {
+                for (hipEvent_t x : e)
+                    if (x) (void)hipEventDestroy(x);
+            }
+        } ev;
+        for (hipEvent_t& x : ev.e) VL_HIP(hipEventCreate(&x));
+        const HnswGraphView g = view(nullptr);
+        VL_HIP(hipEventRecord(ev.e[0], stream_));
+        VL_HIP(launch_hnsw_import_keys(stream_, metric_, g, (uint32_t)n));
+        VL_HIP(hipEventRecord(ev.e[1], stream_));
+        VL_HIP(launch_hnsw_import_indeg(stream_, g, (uint32_t)n));
+        VL_HIP(hipEventRecord(ev.e[2], stream_));
+        if (out_orphans) VL_HIP(hipMemcpyAsync(h_indeg.data(), d_indeg0_, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+        VL_HIP(hipStreamSynchronize(stream_));
+        float a = 0.f, b = 0.f;
+        VL_HIP(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
+        VL_HIP(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
+        t_ms[3] = a;
+        t_ms[4] = b;
+    }
+
+    // ---- commit (moves and swaps only: nothing below can fail)
+    undo.armed = false;
+    if (out_orphans && n >= 2) {
+        uint64_t orphans = 0;
+        for (uint64_t i = 0; i < n; ++i) orphans += h_indeg[i] == 0 ? 1 : 0;
+        *out_orphans = orphans;
+    }
+    level_ = std::move(lv);
+    upper_off_ = std::move(off);
+    n_upper_ = n_upper;
+    entry_ = first_top;
+    max_level_ = top;
+    n_nodes_ = n;
+    id_to_node_ = std::move(ids);
+    node_id_ = std::move(h_ids);
+    live_ = std::move(h_live);
+    live_count_ = alive;
+    for (int i = 0; i < 5; ++i) import_ms_[i] = t_ms[i];
+    return OK;
+}
+
+// cnt0 / indeg0 / lock over the node capacity and cntU over the slot capacity back to zero (the state ensure_graph
+// leaves them in): only for an index without nodes
+int HnswIndex::zero_graph_counters()
+{
+    if (g_cap_) {
+        VL_HIP(hipMemsetAsync(d_cnt0_, 0, g_cap_ * sizeof(uint32_t), stream_));
+        VL_HIP(hipMemsetAsync(d_indeg0_, 0, g_cap_ * sizeof(uint32_t), stream_));
+        VL_HIP(hipMemsetAsync(d_lock_, 0, g_cap_ * sizeof(uint32_t), stream_));
+    }
+    if (u_cap_) VL_HIP(hipMemsetAsync(d_cntU_, 0, u_cap_ * sizeof(uint32_t), stream_));
+    VL_HIP(hipStreamSynchronize(stream_));
     return OK;
 }
 

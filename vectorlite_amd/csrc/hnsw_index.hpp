@@ -20,6 +20,8 @@ namespace vl {
 
 // convert_distance_to_similarity(d as f64 / 1000.0, metric) (src/index/hnsw.rs:51-75, :478-479)
 double hnsw_score(uint64_t d_u64, int metric);
+// the level law: the level of node `node` (insertion position) in an index created with `seed` and `m`, 0 .. HNSW_MAX_LEVEL
+int hnsw_level(uint64_t seed, uint64_t node, uint32_t m);
 
 struct HnswParams {
     uint32_t m = 16;                // MAXIMUM_NUMBER_CONNECTIONS   (src/index/hnsw.rs:95-101, default profile)
@@ -117,11 +119,26 @@ public:
     void graph_info(uint64_t* n_nodes, uint32_t* entry, int* max_level, uint32_t* m, uint32_t* m0, uint64_t* upper_slots) const;
     int graph_export(uint8_t* level, uint32_t* upper_off, uint32_t* cnt0, uint32_t* nbr0, uint32_t* cntU, uint32_t* nbrU,
                      uint64_t* node_ids, uint8_t* live, double* rows) const;
+    const HnswParams& params() const { return params_; }
+    // The inverse of graph_export on an EMPTY index (no node yet, created with the graph's dim, metric, m, m0 and seed):
+    // node i is storage position i, its lists are taken as given (entry order included), levels and upper offsets are
+    // derived from the level law (n_upper must be their total), entry / max_level follow.  The lists are validated on
+    // the host first (hnsw_import_plan.hpp: G3, G4); the edge distances and the in-degree counter are recomputed on the
+    // device.  Among LIVE nodes an id may appear once (ERR_DUP_ID).  *out_orphans (optional): nodes without an incoming
+    // layer-0 edge, counted as the audit counts them (none when n < 2).  Every refusal and every failure leaves the
+    // index as empty as it was and still accepting adds.
+    int graph_import(uint64_t n, const uint64_t* node_ids, const uint8_t* live, const double* rows, bool rows_on_device,
+                     const uint32_t* cnt0, const uint32_t* nbr0, uint64_t n_upper, const uint32_t* cntU, const uint32_t* nbrU,
+                     uint64_t* out_orphans);
+    // milliseconds of the last graph_import: host validation, row ingest, uploads, edge-key kernel, in-degree kernel
+    // (HIP events around the kernels, the host clock around the rest); zeros before the first import
+    void last_import_ms(double out[5]) const;
 
 private:
     friend struct HnswGraphProbe;
     HnswIndex(uint64_t dim, int metric, const HnswParams& p, int device);
     int ensure_graph(uint64_t nodes, uint64_t upper_slots);
+    int zero_graph_counters();  // graph_import, on an index without nodes
     HnswGraphView view() const;
     HnswGraphView view(const WalkScratch* ws) const;
     WalkScratch* acquire_scratch(uint64_t walks) const;  // nullptr + last_error on failure
@@ -169,6 +186,7 @@ private:
     std::vector<uint64_t> node_id_;
     std::vector<uint8_t> live_;
     uint64_t live_count_ = 0;
+    double import_ms_[5] = {0, 0, 0, 0, 0};  // last graph_import, see last_import_ms()
 
     std::atomic<uint32_t> min_beam_{0};  // 0 = the reference's strict ef = min(k, len); a wider floor is opt-in
     std::atomic<int> nav_{NAV_F32};      // walk navigation; the reference's u64 order is opt-in
