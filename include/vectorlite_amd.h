@@ -369,6 +369,33 @@ int vl_index_hnsw_set_min_beam(vl_index *h, uint32_t min_beam);
 #define VL_HNSW_NAV_REFERENCE 1
 int vl_index_hnsw_set_navigation(vl_index *h, int mode);
 
+/* HNSW handle, NEW (no reference counterpart): graph walks restricted to the nodes whose id is in a set (DESIGN.md
+ * section 21).  A node PASSES iff it is live and its id is in the set.  The walk navigates through every node but only
+ * passing ones count: layer 0 keeps one sorted list that is cut, after every insertion, to its first `cap` entries and
+ * then to the shortest prefix holding ef_walk passing entries; the answer is the passing entries of the final list, at
+ * most min(k, passing nodes).  ef_walk = max(min(k, passing), ef), or the handle's beam floor when ef = 0.  Where the
+ * filter is too selective for a walk (ef_walk * nodes > 256 * passing), where ef_walk > 512, or where nothing passes,
+ * the answer comes from the exact scan of the passing rows instead: the true nearest passing rows in Metric::distance
+ * order, post-processed like a walk's result.  With a filter every live node passes and no tombstones, a call returns
+ * exactly what vl_index_search_ef returns, in either navigation mode.
+ * A filter is a token of the handle that made it: never 0, never reused, not cloned, freed with the handle.  ids may be
+ * unsorted and repeat; ids the index does not hold are ignored until a row with such an id is added.  Rows added or
+ * deleted later are seen by the next call.  *out_nodes (may be NULL) / _filter_nodes: the nodes that pass now.
+ * vl_index_filter_create still refuses HNSW handles; these tokens are no use to the flat entry points.
+ * _search_ef_filtered: arguments as vl_index_search_ef plus out_stride (0 = k: entries per query the output rows hold);
+ * one filter serves every query of the batch; errors are vl_index_search_ef's in the same order, then an unknown token.
+ * An unknown token or a non-HNSW handle is VL_ERR_INVALID_ARG.
+ * _last_filtered (any argument may be NULL): the last filtered search on the handle -- route (0 walk, 1 exact), the
+ * walk's list capacity (0 on the exact route), the passing nodes, and the walks in which the capacity dropped a list
+ * entry (their results may miss a passing node a wider list would have kept). */
+int vl_index_hnsw_filter_create(vl_index *h, const uint64_t *ids, uint64_t n_ids, uint64_t *out_filter, uint64_t *out_nodes);
+int vl_index_hnsw_filter_nodes(const vl_index *h, uint64_t filter, uint64_t *out_nodes);
+int vl_index_hnsw_filter_destroy(vl_index *h, uint64_t filter);
+int vl_index_search_ef_filtered(const vl_index *h, uint64_t filter, const double *queries, uint64_t nq, uint64_t q_len,
+                                uint64_t k, uint32_t ef, int metric, uint64_t out_stride,
+                                uint64_t *out_ids, double *out_scores, uint64_t *out_n);
+int vl_index_hnsw_last_filtered(const vl_index *h, int *route, uint32_t *cap, uint64_t *pass_nodes, uint64_t *cap_cut_walks);
+
 /* HNSW handle: the graph as it stands, every node (tombstoned ones included; node = insertion position).  level[n]
  * = top layer of each node; layer 0: cnt0[n] neighbours of node i at nbr0[i * m0 ..]; layer L >= 1 of node i: slot
  * upper_off[i] + L - 1 with cntU[slot] neighbours at nbrU[slot * m ..]; node_ids[n] the caller's ids, live[n] 0 for

@@ -63,6 +63,11 @@ extern "C" {
     fn vl_index_search_batch(h: *const vl_index, queries: *const f64, nq: u64, q_len: u64, k: u64, metric: c_int, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_hnsw_set_navigation(h: *mut vl_index, mode: c_int) -> c_int;
     fn vl_index_search_ef(h: *const vl_index, queries: *const f64, nq: u64, q_len: u64, k: u64, ef: u32, metric: c_int, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
+    fn vl_index_hnsw_filter_create(h: *mut vl_index, ids: *const u64, n_ids: u64, out_filter: *mut u64, out_nodes: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn vl_index_hnsw_filter_nodes(h: *const vl_index, filter: u64, out_nodes: *mut u64) -> c_int;
+    fn vl_index_hnsw_filter_destroy(h: *mut vl_index, filter: u64) -> c_int;
+    fn vl_index_search_ef_filtered(h: *const vl_index, filter: u64, queries: *const f64, nq: u64, q_len: u64, k: u64, ef: u32, metric: c_int, out_stride: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_vlc_open(path: *const c_char, out: *mut *mut vl_vlc_doc) -> c_int;
     fn vl_vlc_close(doc: *mut vl_vlc_doc);
     fn vl_vlc_build_index(doc: *const vl_vlc_doc, device: c_int, out: *mut *mut vl_index) -> c_int;
@@ -688,6 +693,38 @@ impl GpuHnswIndex {
         match unsafe { vl_index_hnsw_set_navigation(self.h.raw, if on { VL_HNSW_NAV_REFERENCE } else { VL_HNSW_NAV_F32 }) } {
             VL_OK => Ok(()),
             _ => Err(last_error()),
+        }
+    }
+    /// Graph walk among the nodes whose id is in `ids` only (no reference counterpart): the walk navigates through every
+    /// node but only live nodes with such an id count towards the beam of `max(ef, min(k, passing))` entries.  Filters that
+    /// are too selective for a walk are answered by the exact scan of the passing rows (`vl_index_hnsw_last_filtered` tells the route).
+    /// `ef = 0`: the beam `search` uses.  The query's metric must be the index's.
+    pub fn search_filtered(&self, ids: &[u64], query: &[f64], k: usize, ef: u32, metric: SimilarityMetric) -> VectorLiteResult<Vec<SearchResult>> {
+        let (mut token, mut nodes) = (0u64, 0u64);
+        let rc = unsafe { vl_index_hnsw_filter_create(self.h.raw, ids.as_ptr(), ids.len() as u64, &mut token, &mut nodes) };
+        if rc != VL_OK {
+            return Err(VectorLiteError::InternalError(last_error()));
+        }
+        let cap = k.min(nodes as usize).max(1);
+        let (mut out_ids, mut scores, mut n) = (vec![0u64; cap], vec![0f64; cap], 0u64);
+        let rc = unsafe {
+            vl_index_search_ef_filtered(self.h.raw, token, query.as_ptr(), 1, query.len() as u64, k.min(cap) as u64, ef, metric_code(metric), cap as u64, out_ids.as_mut_ptr(), scores.as_mut_ptr(), &mut n)
+        };
+        let err = if rc == VL_OK { String::new() } else { last_error() };
+        unsafe { vl_index_hnsw_filter_destroy(self.h.raw, token) };
+        match rc {
+            VL_OK => Ok((0..n as usize)
+                .map(|i| {
+                    let (text, metadata) = self.h.side.get(&out_ids[i]).cloned().unwrap_or_default();
+                    SearchResult { id: out_ids[i], score: scores[i], text, metadata }
+                })
+                .collect()),
+            VL_ERR_DIM_MISMATCH => {
+                let (mut e, mut a) = (0u64, 0u64);
+                unsafe { vl_last_dim_mismatch(&mut e, &mut a) };
+                Err(VectorLiteError::DimensionMismatch { expected: e as usize, actual: a as usize })
+            }
+            _ => Err(VectorLiteError::InternalError(err)),
         }
     }
     /// Bulk insert (one batched graph build on the device) for the custom Deserialize.

@@ -29,7 +29,7 @@ from . import _lib
 
 __all__ = [
     "SimilarityMetric", "Vector", "SearchResult", "FlatIndex", "MultiFlatIndex", "HNSWIndex", "VectorLiteError", "DimensionMismatch",
-    "MetricMismatch", "NaNScore", "DeviceError", "IndexOpError", "IdFilter", "GroupTable", "hnsw_score", "hnsw_level", "runtime_info",
+    "MetricMismatch", "NaNScore", "DeviceError", "IndexOpError", "IdFilter", "WalkFilter", "GroupTable", "hnsw_score", "hnsw_level", "runtime_info",
     "PATH_FAST", "PATH_EXACT_SELECT", "PATH_EXACT_SORT",
 ]
 
@@ -260,6 +260,48 @@ def _make_filter(L, h, owner, ids) -> IdFilter:
         raise IndexOpError(_last_error())
     _raise(rc)
     return IdFilter(owner, int(tok.value))
+
+
+class WalkFilter:
+    """A set of ids of one HNSWIndex (vl_index_hnsw_filter_create): graph walks given it navigate through every node
+    but count only the live nodes whose id is in the set.  It follows the index: after add / delete the next use sees
+    the current nodes.  `nodes()` = nodes that pass now; `close()` (or leaving a `with` block) frees it."""
+
+    def __init__(self, index: "HNSWIndex", token: int):
+        self._index = index
+        self._token = token
+
+    @property
+    def token(self) -> int:
+        return self._token
+
+    def nodes(self) -> int:
+        if not self._token:
+            raise IndexOpError("filter is closed")
+        out = C.c_uint64(0)
+        rc = self._index._L.vl_index_hnsw_filter_nodes(self._index._h, self._token, C.byref(out))
+        if rc == VL_ERR_INVALID_ARG:
+            raise IndexOpError(_last_error())
+        _raise(rc)
+        return int(out.value)
+
+    def close(self) -> None:
+        tok, self._token = self._token, 0
+        h = getattr(self._index, "_h", None)
+        if tok and h:
+            self._index._L.vl_index_hnsw_filter_destroy(h, tok)
+
+    def __enter__(self) -> "WalkFilter":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class GroupTable:
@@ -1239,8 +1281,9 @@ class HNSWIndex:
             raise MetricMismatch(SimilarityMetric(int(requested)), self.metric())
         _raise(rc)
 
-    def search_batch(self, queries, k: int, metric: int, ef: int = 0):
-        """(ids [nq, k], scores [nq, k], n [nq]); ef = 0 is the reference's ef = min(k, len)."""
+    def search_batch(self, queries, k: int, metric: int, ef: int = 0, filter=None):
+        """(ids [nq, k], scores [nq, k], n [nq]); ef = 0 is the reference's ef = min(k, len).  filter: a WalkFilter of
+        this index or an iterable of ids (a temporary filter) -- one filter for every query of the batch."""
         Q = _f64(queries)
         if Q.ndim == 1:
             Q = Q[None, :]
@@ -1252,10 +1295,47 @@ class HNSWIndex:
         ids = np.zeros((nq, kk), dtype=np.uint64)
         scores = np.zeros((nq, kk), dtype=np.float64)
         n = np.zeros(max(nq, 1), dtype=np.uint64)
-        rc = self._L.vl_index_search_ef(self._h, _pf64(Q), nq, qlen, kc, int(ef), int(metric), _pu64(ids),
-                                        _pf64(scores), _pu64(n))
+        if filter is None:
+            rc = self._L.vl_index_search_ef(self._h, _pf64(Q), nq, qlen, kc, int(ef), int(metric), _pu64(ids),
+                                            _pf64(scores), _pu64(n))
+        else:
+            wf, temporary = self._walk_filter(filter)
+            try:
+                rc = self._L.vl_index_search_ef_filtered(self._h, wf.token, _pf64(Q), nq, qlen, kc, int(ef), int(metric), kk,
+                                                         _pu64(ids), _pf64(scores), _pu64(n))
+            finally:
+                if temporary:
+                    wf.close()
         self._raise_search(rc, metric)
         return ids[:, :kc], scores[:, :kc], n[:nq]
+
+    def make_walk_filter(self, ids) -> WalkFilter:
+        """A WalkFilter over `ids` (any iterable of ints; unsorted, repeats and ids the index does not hold are fine)."""
+        ids = np.ascontiguousarray(np.fromiter((int(i) for i in ids), dtype=np.uint64)
+                                   if not isinstance(ids, np.ndarray) else ids.astype(np.uint64, copy=False))
+        tok, nodes = C.c_uint64(0), C.c_uint64(0)
+        rc = self._L.vl_index_hnsw_filter_create(self._h, _pu64(ids), ids.size, C.byref(tok), C.byref(nodes))
+        if rc == VL_ERR_INVALID_ARG:
+            raise IndexOpError(_last_error())
+        _raise(rc)
+        return WalkFilter(self, int(tok.value))
+
+    def _walk_filter(self, filter):
+        """(WalkFilter, whether it is a temporary one the caller closes).  An IdFilter raises as make_filter does."""
+        if isinstance(filter, WalkFilter):
+            if filter._index is not self or not filter.token:
+                raise IndexOpError("the filter is closed or belongs to another index")
+            return filter, False
+        if isinstance(filter, IdFilter):
+            self.make_filter([])  # raises: flat filters do not serve HNSW handles
+        return self.make_walk_filter(filter), True
+
+    def last_filtered(self) -> Dict[str, int]:
+        """The last filtered search on this index: route (0 walk, 1 exact), the walk's list capacity, the nodes that
+        passed, and the walks in which the capacity dropped a list entry."""
+        route, cap, nodes, cut = C.c_int(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        _raise(self._L.vl_index_hnsw_last_filtered(self._h, C.byref(route), C.byref(cap), C.byref(nodes), C.byref(cut)))
+        return {"route": int(route.value), "cap": int(cap.value), "pass_nodes": int(nodes.value), "cap_cut_walks": int(cut.value)}
 
     def make_filter(self, ids) -> IdFilter:
         """Filtered search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""
@@ -1295,15 +1375,18 @@ class HNSWIndex:
         return self.search_grouped_arrays(query, k, similarity_metric, groups, filter)
 
     def search_arrays(self, query, k: int, metric: int, ef: int = 0, filter=None):
-        if filter is not None:
-            self.make_filter(filter if not isinstance(filter, IdFilter) else [])  # raises: no filtered HNSW walk
-        ids, scores, n = self.search_batch(_f64(query).ravel()[None, :], k, metric, ef)
+        ids, scores, n = self.search_batch(_f64(query).ravel()[None, :], k, metric, ef, filter=filter)
         m = int(n[0])
         return ids[0, :m].copy(), scores[0, :m].copy()
 
     def search(self, query, k: int, similarity_metric: int, filter=None) -> List[SearchResult]:
         if filter is not None:
-            self.make_filter(filter if not isinstance(filter, IdFilter) else [])  # raises: no filtered HNSW walk
+            ids, scores = self.search_arrays(query, k, similarity_metric, 0, filter)
+            out = []
+            for i, s in zip(ids.tolist(), scores.tolist()):
+                text, md = self._meta.get(i, ("", None))
+                out.append(SearchResult(id=i, score=s, text=text, metadata=md))
+            return out
         q = _f64(query).ravel()
         kk = max(min(int(k), self.len()), 1)
         ids = np.zeros(kk, dtype=np.uint64)

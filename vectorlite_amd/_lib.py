@@ -28,7 +28,8 @@ SYMBOLS = [
     "vl_index_profile_enable", "vl_index_profile_read", "vl_index_last_scan", "vl_index_last_filter", "vl_runtime_info",
     "vl_comm_unique_id", "vl_comm_create", "vl_comm_destroy", "vl_comm_world", "vl_comm_rank", "vl_comm_profile_enable", "vl_comm_profile_read", "vl_comm_record_paths",
     "vl_index_hnsw_set_min_beam", "vl_index_hnsw_set_navigation", "vl_index_hnsw_graph_info", "vl_index_hnsw_graph_export",
-    "vl_index_hnsw_graph_import", "vl_index_hnsw_import_times", "vl_index_hnsw_params", "vl_hnsw_level",
+    "vl_index_hnsw_graph_import", "vl_index_hnsw_import_times",
+    "vl_index_hnsw_filter_create", "vl_index_hnsw_filter_nodes", "vl_index_hnsw_filter_destroy", "vl_index_search_ef_filtered", "vl_index_hnsw_last_filtered", "vl_index_hnsw_params", "vl_hnsw_level",
     "vl_shard_sync", "vl_shard_search_batch", "vl_shard_packed_words", "vl_shard_search_local", "vl_shard_merge", "vl_shard_search_batch_dev", "vl_shard_search_local_dev",
 ]
 
@@ -126,6 +127,11 @@ def load() -> C.CDLL:
     sig("vl_index_hnsw_set_min_beam", i32, [vp, C.c_uint32])
     sig("vl_index_hnsw_set_navigation", i32, [vp, i32])
     p_u32 = C.POINTER(C.c_uint32)
+    sig("vl_index_hnsw_filter_create", i32, [vp, p_u64, u64, p_u64, p_u64])
+    sig("vl_index_hnsw_filter_nodes", i32, [vp, u64, p_u64])
+    sig("vl_index_hnsw_filter_destroy", i32, [vp, u64])
+    sig("vl_index_search_ef_filtered", i32, [vp, u64, p_f64, u64, u64, u64, C.c_uint32, i32, u64, p_u64, p_f64, p_u64])
+    sig("vl_index_hnsw_last_filtered", i32, [vp, p_i32, p_u32, p_u64, p_u64])
     sig("vl_index_hnsw_graph_info", i32, [vp, p_u64, p_u32, p_i32, p_u32, p_u32, p_u64])
     sig("vl_index_hnsw_graph_export", i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     sig("vl_index_hnsw_graph_import", i32, [vp, u64, vp, vp, vp, i32, vp, vp, u64, vp, vp, p_u64])

@@ -1099,6 +1099,56 @@ int vl_index_hnsw_set_navigation(vl_index* h, int mode)
     return VL_OK;
 }
 
+#define VL_HNSW_HANDLE(h)                                                          \
+    do {                                                                           \
+        if (!(h) || !(h)->hnsw) {                                                  \
+            vl::set_last_error("this entry point needs an HNSW index handle");     \
+            return VL_ERR_INVALID_ARG;                                             \
+        }                                                                          \
+    } while (0)
+
+int vl_index_hnsw_filter_create(vl_index* h, const uint64_t* ids, uint64_t n_ids, uint64_t* out_filter, uint64_t* out_nodes)
+{
+    return guarded([&]() -> int {
+        VL_HNSW_HANDLE(h);
+        if (!out_filter) return VL_ERR_INVALID_ARG;
+        return h->hnsw->filter_create(ids, n_ids, out_filter, out_nodes);
+    });
+}
+
+int vl_index_hnsw_filter_nodes(const vl_index* h, uint64_t filter, uint64_t* out_nodes)
+{
+    return guarded([&]() -> int {
+        VL_HNSW_HANDLE(h);
+        if (!out_nodes) return VL_ERR_INVALID_ARG;
+        return h->hnsw->filter_nodes(filter, out_nodes);
+    });
+}
+
+int vl_index_hnsw_filter_destroy(vl_index* h, uint64_t filter)
+{
+    return guarded([&]() -> int {
+        VL_HNSW_HANDLE(h);
+        return h->hnsw->filter_destroy(filter);
+    });
+}
+
+int vl_index_search_ef_filtered(const vl_index* h, uint64_t filter, const double* queries, uint64_t nq, uint64_t q_len, uint64_t k,
+                                uint32_t ef, int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores, uint64_t* out_n)
+{
+    return guarded([&]() -> int {
+        VL_HNSW_HANDLE(h);
+        return h->hnsw->search_filtered(filter, queries, nq, q_len, k, metric, ef, out_ids, out_scores, out_n, out_stride);
+    });
+}
+
+int vl_index_hnsw_last_filtered(const vl_index* h, int* route, uint32_t* cap, uint64_t* pass_nodes, uint64_t* cap_cut_walks)
+{
+    if (!h || !h->hnsw) return VL_ERR_INVALID_ARG;
+    h->hnsw->last_filtered(route, cap, pass_nodes, cap_cut_walks);
+    return VL_OK;
+}
+
 int vl_index_hnsw_walk_stats(const vl_index* h, uint64_t* queries, uint64_t* distance_evals)
 {
     if (!h || !h->hnsw) return VL_ERR_INVALID_ARG;

@@ -1538,6 +1538,24 @@ int GpuFlatIndex::filter_rows(uint64_t token, uint64_t* out_rows) const
     return OK;
 }
 
+int GpuFlatIndex::filter_positions(uint64_t token, std::shared_ptr<IdFilter>* keep, const uint32_t** d_plist, uint64_t* m) const
+{
+    if (!keep || !d_plist || !m) return ERR_INVALID_ARG;
+    std::shared_ptr<IdFilter> f;
+    VL_TRY(find_filter(token, &f));
+    std::shared_lock<RwLock> lk(mu_);
+    std::lock_guard<std::mutex> fg(f->mu);
+    if (f->resolved_at != mutations_) {
+        WsLease lease(this);
+        if (lease.status() != OK) return lease.status();
+        VL_TRY(lease.done(resolve_filter(lease.ws, f.get())));
+    }
+    *d_plist = f->d_plist;
+    *m = f->m;
+    *keep = std::move(f);
+    return OK;
+}
+
 // positions p < len() whose ids_[p] is in f->ids -> f->d_plist[0..m), ascending.  Two launches, one 4-byte read-back (m, which
 // sizes the list and the scan's grid), one launch; nothing per row crosses PCIe.
 int GpuFlatIndex::resolve_filter(Workspace* ws, IdFilter* f) const

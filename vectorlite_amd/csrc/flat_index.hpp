@@ -253,6 +253,9 @@ public:
     int filter_create(const uint64_t* ids, uint64_t n_ids, uint64_t* out_token, uint64_t* out_rows);
     int filter_rows(uint64_t token, uint64_t* out_rows) const;  // resolves the filter again if rows changed since
     int filter_destroy(uint64_t token);
+    // for the HNSW graph layered on this row store (hnsw_index.cpp): the filter's ascending position list on the device,
+    // resolved again first if rows changed since.  Valid while the caller holds *keep and keeps rows from being added.
+    int filter_positions(uint64_t token, std::shared_ptr<IdFilter>* keep, const uint32_t** d_plist, uint64_t* m) const;
     int search_filtered(uint64_t token, const double* query, uint64_t q_len, uint64_t k, int metric, uint64_t* out_pos,
                         uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;
     // NEW (no reference counterpart): every row whose score is >= min_score -- the longest prefix of FlatIndex::search(q, len,

@@ -719,6 +719,423 @@ __global__ __launch_bounds__(256) void k_hnsw_search_ref(HnswGraphView g, const 
     }
 }
 
+// ---- id-filtered walks (vl_index_search_ef_filtered) ------------------------------------------
+// A node PASSES iff its bit is set in the filter's pass bitmap (k_hnsw_filter_bits: position in the filter's list AND
+// live).  The walk navigates through every node but only passing ones count towards ef: layer 0 keeps one sorted list B
+// of (key, tie-break, node | EXPANDED | PASS) entries, and after every insertion B is cut to its first `cap` entries and
+// then to its WINDOW -- the shortest prefix holding ef passing entries, all of B while it holds fewer.  The upper layers
+// are the unfiltered greedy descent (pass == nullptr below: every node counts).  Both navigations share the list; the
+// tie-break word is the node (f32 navigation, BeamList's order) or the first-seen sequence number (reference
+// navigation, RefBeam's order).  Separate kernels: the unfiltered instantiations above are not touched.
+
+constexpr uint32_t PASSING = 0x40000000u;  // flag bit in the node word next to EXPANDED (the launcher refuses cap >= 2^30 nodes)
+constexpr uint32_t NODE_BITS = ~(EXPANDED | PASSING);
+
+template <int S>
+struct FilterBeam {
+    unsigned long long d[S];
+    uint32_t t[S];  // tie-break: node (f32 navigation) or sequence number (reference navigation)
+    uint32_t v[S];  // node | EXPANDED | PASSING; HNSW_NONE = empty
+    int len;        // real entries (wave-uniform)
+    int lim;        // where a candidate must rank in front of to enter: len when the window holds ef passing entries, cap otherwise
+    bool cut;       // `cap` dropped an entry the window would have kept, at least once
+
+    __device__ __forceinline__ void init(int cap)
+    {
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            d[s] = ~0ull;
+            t[s] = ~0u;
+            v[s] = HNSW_NONE;
+        }
+        len = 0;
+        lim = cap;
+        cut = false;
+    }
+    __device__ __forceinline__ int rank_of(unsigned long long dist, uint32_t tie) const
+    {
+        int c = 0;
+#pragma unroll
+        for (int s = 0; s < S; ++s) c += __popcll(__ballot(d[s] < dist || (d[s] == dist && t[s] < tie)));
+        return c;
+    }
+    // index one past the ef-th passing entry, or -1 while there are fewer than ef
+    __device__ __forceinline__ int window_end(int ef) const
+    {
+        int before = 0;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const bool p = v[s] != HNSW_NONE && (v[s] & PASSING) != 0u;
+            const unsigned long long mk = __ballot(p);
+            const int c = __popcll(mk);
+            if (before + c >= ef) {  // wave-uniform
+                const int mine = before + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+                const unsigned long long at = __ballot(p && mine + 1 == ef);
+                return s * 64 + __ffsll((long long)at);
+            }
+            before += c;
+        }
+        return -1;
+    }
+    __device__ __forceinline__ void truncate(int n)
+    {
+        const int lane = lane_id();
+#pragma unroll
+        for (int s = 0; s < S; ++s)
+            if (s * 64 + lane >= n) {
+                d[s] = ~0ull;
+                t[s] = ~0u;
+                v[s] = HNSW_NONE;
+            }
+    }
+    // insert at the sorted position, cut to cap, cut to the window.  A candidate that ranks at or behind `lim` would be
+    // cut again at once (behind a full window, or behind cap entries), so it is rejected before anything moves.
+    __device__ __forceinline__ void insert(unsigned long long dist, uint32_t tie, uint32_t word, int ef, int cap)
+    {
+        const int idx = rank_of(dist, tie);
+        if (idx >= lim) return;  // wave-uniform
+        const int lane = lane_id();
+#pragma unroll
+        for (int s = S - 1; s >= 0; --s) {  // top slot first: it reads the slot below before that moves
+            if ((s + 1) * 64 <= idx) break;
+            const int j = s * 64 + lane;
+            unsigned long long pd = wave_shr1(d[s]);
+            uint32_t pt = wave_shr1(t[s]);
+            uint32_t pv = wave_shr1(v[s]);
+            if (s > 0) {
+                const unsigned long long cd = read_lane(d[s > 0 ? s - 1 : 0], 63);
+                const uint32_t ct = read_lane(t[s > 0 ? s - 1 : 0], 63);
+                const uint32_t cv = read_lane(v[s > 0 ? s - 1 : 0], 63);
+                if (lane == 0) {
+                    pd = cd;
+                    pt = ct;
+                    pv = cv;
+                }
+            }
+            if (j == idx) {
+                d[s] = dist;
+                t[s] = tie;
+                v[s] = word;
+            } else if (j > idx) {
+                d[s] = pd;
+                t[s] = pt;
+                v[s] = pv;
+            }
+            if (j >= cap) {
+                d[s] = ~0ull;
+                t[s] = ~0u;
+                v[s] = HNSW_NONE;
+            }
+        }
+        const bool dropped = len == cap;  // the last entry fell off the end
+        if (!dropped) ++len;
+        const int w = window_end(ef);
+        if (w >= 0) {
+            if (w < len) truncate(w);
+            len = w;
+            lim = w;
+        } else {
+            lim = cap;
+            if (dropped) cut = true;  // ... and the window would have kept it: fewer than ef passing entries in front of it
+        }
+    }
+    __device__ __forceinline__ void get(int idx, unsigned long long& dist, uint32_t& word) const
+    {
+        const int si = idx >> 6, l = idx & 63;  // idx is wave-uniform
+        dist = read_lane(d[0], l);
+        word = read_lane(v[0], l);
+#pragma unroll
+        for (int s = 1; s < S; ++s)
+            if (si == s) {
+                dist = read_lane(d[s], l);
+                word = read_lane(v[s], l);
+            }
+    }
+    __device__ __forceinline__ int next_unexpanded() const
+    {
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const unsigned long long m = __ballot((v[s] & EXPANDED) == 0u);
+            if (m) return s * 64 + __ffsll((long long)m) - 1;
+        }
+        return -1;
+    }
+    __device__ __forceinline__ void mark_expanded(int idx)
+    {
+        const int lane = lane_id();
+#pragma unroll
+        for (int s = 0; s < S; ++s)
+            if (s * 64 + lane == idx) v[s] |= EXPANDED;
+    }
+    // the survivor of a greedy layer becomes the unexpanded entry point of the next one; pass != nullptr (entering layer 0):
+    // its flag now says whether it really passes
+    __device__ __forceinline__ void reopen(const uint32_t* __restrict__ pass)
+    {
+#pragma unroll
+        for (int s = 0; s < S; ++s)
+            if (v[s] != HNSW_NONE) {
+                const uint32_t node = v[s] & NODE_BITS;
+                const bool p = pass == nullptr || ((pass[node >> 5] >> (node & 31u)) & 1u) != 0u;
+                v[s] = node | (p ? PASSING : 0u);
+            }
+    }
+};
+
+// One layer of a filtered walk.  REF: reference navigation (u64 keys on the f64 rows, one lane per neighbour, ties by
+// sequence number); otherwise f32 navigation (a lane pair per neighbour, rounds of 32, ties by node).  pass == nullptr:
+// every node counts (the greedy upper layers).
+template <int METRIC, int S, bool REF>
+__device__ __forceinline__ void filter_layer(const HnswGraphView& g, const double* q, const float* q32, float q_inv, int layer,
+                                             Visited& vis, FilterBeam<S>& L, int ef, int cap, const uint32_t* __restrict__ pass,
+                                             uint32_t& seq, uint32_t& evals)
+{
+    const int lane = lane_id();
+    const int half = REF ? 0 : lane >> 5, nl = REF ? lane : lane & 31;
+    constexpr uint32_t ROUND = REF ? 64u : 32u;
+    for (;;) {
+        const int idx = L.next_unexpanded();
+        if (idx < 0) break;
+        unsigned long long dc;
+        uint32_t c;
+        L.get(idx, dc, c);
+        L.mark_expanded(idx);
+        const LayerView lv = layer_of(g, c & NODE_BITS, layer);
+        for (uint32_t base = 0; base < lv.cnt; base += ROUND) {  // one round under reference navigation (lists hold <= 64)
+            const uint32_t e = base + (uint32_t)nl < lv.cnt ? lv.nbr[base + nl] : HNSW_NONE;
+            bool act;
+            uint32_t tie;
+            unsigned long long de = ~0ull;
+            if (REF) {
+                // a list that names a node twice: see beam_layer_ref
+                bool first = e != HNSW_NONE;
+                for (uint32_t j = 0; j + 1 < lv.cnt; ++j) first = first && !((uint32_t)lane > j && e == read_lane(e, (int)j));
+                act = vis.mark(e, first);
+                const unsigned long long mk = __ballot(act);
+                tie = seq + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+                seq += (uint32_t)__popcll(mk);
+                evals += (uint32_t)__popcll(mk);
+                if (act) de = row_distance_u64<METRIC>(g, e, q);
+            } else {
+                act = vis.mark(e, e != HNSW_NONE && half == 0);
+                act = __shfl((int)act, nl) != 0;  // the upper half-wave follows its partner's visited check
+                if (act) de = row_distance_f32<METRIC>(g, e, q32, q_inv, half);
+                evals += (uint32_t)__popcll(__ballot(act && half == 0));
+                act = act && half == 0;
+                tie = e;
+            }
+            uint32_t word = e;
+            if (act && (pass == nullptr || ((pass[e >> 5] >> (e & 31u)) & 1u) != 0u)) word |= PASSING;
+            // the entry a candidate must beat only moves forward while this round inserts; insert() re-checks the rank
+            unsigned long long w = ~0ull;
+            uint32_t wn = HNSW_NONE;
+            if (L.lim > 0) L.get(L.lim - 1, w, wn);
+            unsigned long long m = __ballot(act && (wn == HNSW_NONE || (REF ? de < w : de <= w)));
+            while (m) {
+                const int src = __builtin_amdgcn_readfirstlane(__ffsll((long long)m) - 1);
+                m &= m - 1;
+                L.insert(read_lane(de, src), read_lane(tie, src), read_lane(word, src), ef, cap);
+            }
+        }
+    }
+}
+
+template <int S>
+__device__ __forceinline__ void next_layer(FilterBeam<S>& L, Visited& vis, const uint32_t* __restrict__ pass)
+{
+    vis.clear();
+    L.reopen(pass);
+#pragma unroll
+    for (int s = 0; s < S; ++s) (void)vis.mark(L.v[s] & NODE_BITS, L.v[s] != HNSW_NONE);
+}
+
+// The filtered walk, both navigations.  Arguments as k_hnsw_search, plus cap (<= 64 S), the pass bitmap and the counter of
+// walks whose list was cut at cap.  LDS as the unfiltered kernel of the same navigation.
+// Results: REF -- the passing entries of the final list in list order, scores from their u64 keys; f32 -- the passing
+// entries get the exact callback value (one evaluation each) and are ranked by (that value, node) like k_hnsw_search's
+// steps 1-3, over the list's length instead of ef.  A passing node is live, so nothing is dropped afterwards.
+template <int METRIC, int S, bool REF>
+__device__ __forceinline__ void filtered_search_body(const HnswGraphView& g, const double* __restrict__ queries, uint32_t nq,
+                                                     uint32_t ef, uint32_t cap, uint32_t entry, int max_level,
+                                                     uint32_t max_candidates, uint32_t k_stride,
+                                                     const uint32_t* __restrict__ pass, unsigned long long* __restrict__ out_ids,
+                                                     double* __restrict__ out_scores, unsigned long long* __restrict__ out_n,
+                                                     unsigned long long* __restrict__ stat_evals,
+                                                     unsigned long long* __restrict__ cut_walks)
+{
+    extern __shared__ double q_lds[];
+    const int lane = lane_id();
+    const int wave = threadIdx.x >> 6;
+    const uint32_t slot = blockIdx.x * 4 + wave;
+    if (slot >= g.n_slots) return;
+    constexpr uint32_t CAP = 64u * (uint32_t)S;
+    const size_t q_words = REF ? (((size_t)g.dim + 1) & ~(size_t)1) : (((size_t)g.ld / 2 + g.dim + 1) & ~(size_t)1);
+    const size_t per_wave = REF ? q_words : q_words + 3 * (size_t)CAP;
+    double* base = q_lds + (size_t)wave * per_wave;
+    float* q32 = reinterpret_cast<float*>(base);
+    double* q = REF ? base : base + g.ld / 2;
+    unsigned long long* t_key = reinterpret_cast<unsigned long long*>(base + q_words);  // [2][CAP], f32 navigation only
+    uint32_t* t_node = reinterpret_cast<uint32_t*>(t_key + 2 * CAP);                     // [2][CAP]
+    Visited vis;
+    vis.attach(g, slot);
+
+    for (uint32_t qi = slot; qi < nq; qi += gridDim.x * 4) {
+        float q_inv = 0.f;
+        if (REF) {
+            for (uint32_t i = lane; i < g.dim; i += 64) q[i] = queries[(size_t)qi * g.dim + i];
+        } else {
+            float qq = 0.f;
+            for (uint32_t i = lane; i < g.ld; i += 64) {
+                const double v = i < g.dim ? queries[(size_t)qi * g.dim + i] : 0.0;
+                if (i < g.dim) q[i] = v;
+                q32[i] = (float)v;
+                qq = fmaf((float)v, (float)v, qq);
+            }
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) qq += __shfl_xor(qq, o);
+            q_inv = qq > 0.f ? 1.0f / sqrtf(qq) : 0.f;
+        }
+        __builtin_amdgcn_wave_barrier();
+        FilterBeam<S> L;
+        L.init(1);
+        uint32_t evals = 1, seq = 1;  // the entry point: one evaluation, sequence number 0
+        {
+            unsigned long long d0;
+            if (REF) d0 = row_distance_u64<METRIC>(g, entry, q);
+            else d0 = row_distance_f32<METRIC>(g, entry, q32, q_inv, lane >> 5);
+            d0 = read_lane(d0, 0);
+            L.insert(d0, REF ? 0u : entry, entry | PASSING, 1, 1);
+            (void)vis.mark(entry, lane == 0);
+        }
+        for (int layer = max_level; layer >= 1; --layer) {
+            filter_layer<METRIC, S, REF>(g, q, q32, q_inv, layer, vis, L, 1, 1, nullptr, seq, evals);
+            next_layer(L, vis, layer == 1 ? pass : nullptr);
+        }
+        if (max_level < 1) L.reopen(pass);  // a one-layer graph: the entry's flag was a placeholder
+        // layer 0 starts from the single entry the descent landed on, whether it passes or not
+        {
+            const int w0 = L.window_end((int)ef);  // 1 when ef == 1 and it passes
+            L.lim = w0 >= 0 ? w0 : (int)cap;
+            L.cut = false;
+        }
+        filter_layer<METRIC, S, REF>(g, q, q32, q_inv, 0, vis, L, (int)ef, (int)cap, pass, seq, evals);
+        vis.clear();
+
+        uint32_t kept = 0;
+        if (REF) {
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                const bool p = L.v[s] != HNSW_NONE && (L.v[s] & PASSING) != 0u;
+                const unsigned long long mk = __ballot(p);
+                const uint32_t pos = kept + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+                if (p && pos < max_candidates) {
+                    out_ids[(size_t)qi * k_stride + pos] = g.node_id[L.v[s] & NODE_BITS];
+                    out_scores[(size_t)qi * k_stride + pos] = hnsw_score_dev<METRIC>(L.d[s]);
+                }
+                kept += (uint32_t)__popcll(mk);
+            }
+        } else {
+            const uint32_t len = (uint32_t)L.len;
+            // (1) the exact callback value of the passing entries; the others leave the ranking
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                const uint32_t j = s * 64 + lane;
+                const bool p = L.v[s] != HNSW_NONE && (L.v[s] & PASSING) != 0u;
+                const uint32_t node = p ? (L.v[s] & NODE_BITS) : HNSW_NONE;
+                unsigned long long exact = ~0ull;
+                if (p) exact = row_distance<METRIC>(g.master + (size_t)node * g.dim, q, g.dim);
+                kept += (uint32_t)__popcll(__ballot(p));
+                t_key[j] = exact;  // j < CAP by construction
+                t_node[j] = node;
+            }
+            evals += kept;
+            __builtin_amdgcn_wave_barrier();
+            // (2) (exact value, node) order among them
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                const uint32_t j = s * 64 + lane;
+                const unsigned long long kj = t_key[j];
+                const uint32_t nj = t_node[j];
+                if (j < len && nj != HNSW_NONE) {
+                    uint32_t rank = 0;
+                    for (uint32_t i = 0; i < len; ++i) {
+                        const unsigned long long ki = t_key[i];
+                        const uint32_t ni = t_node[i];
+                        rank += (ni != HNSW_NONE && (ki < kj || (ki == kj && ni < nj))) ? 1u : 0u;
+                    }
+                    t_key[CAP + rank] = kj;
+                    t_node[CAP + rank] = nj;
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            // (3) the closest max_candidates of them
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                const uint32_t r = s * 64 + lane;
+                if (r < kept && r < max_candidates) {
+                    const double scaled = __longlong_as_double((long long)t_key[CAP + r]);
+                    out_ids[(size_t)qi * k_stride + r] = g.node_id[t_node[CAP + r]];
+                    out_scores[(size_t)qi * k_stride + r] = hnsw_score_dev<METRIC>(rust_as_u64(scaled));
+                }
+            }
+        }
+        if (lane == 0) {
+            out_n[qi] = kept < max_candidates ? kept : max_candidates;
+            if (stat_evals) atomicAdd(stat_evals, (unsigned long long)evals);
+            if (L.cut) atomicAdd(cut_walks, 1ull);
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+template <int METRIC, int S>
+__global__ __launch_bounds__(256) void k_hnsw_search_filt(HnswGraphView g, const double* __restrict__ queries, uint32_t nq,
+                                                          uint32_t ef, uint32_t cap, uint32_t entry, int max_level,
+                                                          uint32_t max_candidates, uint32_t k_stride,
+                                                          const uint32_t* __restrict__ pass, unsigned long long* __restrict__ out_ids,
+                                                          double* __restrict__ out_scores, unsigned long long* __restrict__ out_n,
+                                                          unsigned long long* __restrict__ stat_evals,
+                                                          unsigned long long* __restrict__ cut_walks)
+{
+    filtered_search_body<METRIC, S, false>(g, queries, nq, ef, cap, entry, max_level, max_candidates, k_stride, pass, out_ids,
+                                           out_scores, out_n, stat_evals, cut_walks);
+}
+
+template <int METRIC, int S>
+__global__ __launch_bounds__(256) void k_hnsw_search_ref_filt(HnswGraphView g, const double* __restrict__ queries, uint32_t nq,
+                                                              uint32_t ef, uint32_t cap, uint32_t entry, int max_level,
+                                                              uint32_t max_candidates, uint32_t k_stride,
+                                                              const uint32_t* __restrict__ pass,
+                                                              unsigned long long* __restrict__ out_ids,
+                                                              double* __restrict__ out_scores, unsigned long long* __restrict__ out_n,
+                                                              unsigned long long* __restrict__ stat_evals,
+                                                              unsigned long long* __restrict__ cut_walks)
+{
+    filtered_search_body<METRIC, S, true>(g, queries, nq, ef, cap, entry, max_level, max_candidates, k_stride, pass, out_ids,
+                                          out_scores, out_n, stat_evals, cut_walks);
+}
+
+// Pass bitmap of a filter: bit p of bits[] is set iff p is in the filter's ascending position list and live[p] != 0.
+// bits[] is zeroed by the caller; *n_pass (zeroed too) receives the number of bits set.
+__global__ __launch_bounds__(256) void k_hnsw_filter_bits(const uint32_t* __restrict__ plist, uint64_t m, uint64_t n_nodes,
+                                                          const uint8_t* __restrict__ live, uint32_t* __restrict__ bits,
+                                                          unsigned long long* __restrict__ n_pass)
+{
+    unsigned long long mine = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t p = plist[i];
+        if ((uint64_t)p < n_nodes && live[p] != 0) {  // positions are unique: every bit is set once
+            atomicOr(&bits[p >> 5], 1u << (p & 31u));
+            ++mine;
+        }
+    }
+    const unsigned long long any = __ballot(mine != 0);
+    if (any != 0ull) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
+        if (lane_id() == 0) atomicAdd(n_pass, mine);
+    }
+}
+
 // Build phase A: node p = first + i searches the graph of the nodes < first and fills its own lists.
 template <int METRIC, int S>
 __global__ __launch_bounds__(256) void k_hnsw_insert_search(HnswGraphView g, uint32_t first, uint32_t n, uint32_t efc,
@@ -1173,6 +1590,59 @@ hipError_t launch_hnsw_search_ref(hipStream_t s, int metric, const HnswGraphView
         default: return launch(k_hnsw_search_ref<MM, 8>);
         }
     });
+}
+
+hipError_t launch_hnsw_search_filtered(hipStream_t s, int metric, bool reference_nav, const HnswGraphView& g,
+                                       const double* queries, uint32_t nq, uint32_t ef, uint32_t cap, uint32_t entry,
+                                       int max_level, uint32_t max_candidates, uint32_t k_stride, const uint32_t* pass_bits,
+                                       unsigned long long* out_ids, double* out_scores, unsigned long long* out_n,
+                                       unsigned long long* stat_evals, unsigned long long* cut_walks)
+{
+    if (nq == 0) return hipSuccess;
+    if (ef == 0 || ef > cap || (cap != 64 && cap != 128 && cap != 256 && cap != 512) || g.m0 > 64 || g.m > 64 ||
+        max_candidates > k_stride || max_candidates > cap || !pass_bits || !cut_walks || g.cap >= (uint64_t)PASSING ||
+        (uint64_t)entry >= g.cap)
+        return hipErrorInvalidValue;
+    const uint32_t slots = cap / 64;
+    const size_t q_words = reference_nav ? (((size_t)g.dim + 1) & ~(size_t)1) : (((size_t)g.ld / 2 + g.dim + 1) & ~(size_t)1);
+    const size_t lds = (size_t)4 * (reference_nav ? q_words : q_words + 3 * (size_t)64 * slots) * sizeof(double);
+    if (lds > HNSW_LDS_MAX) return hipErrorInvalidValue;
+    const int grid = grid_for(g, nq);
+    return dispatch_metric(metric, [&](auto M) -> hipError_t {
+        constexpr int MM = decltype(M)::value;
+        auto launch = [&](auto kern) -> hipError_t {
+            const hipError_t e = allow_big_lds(kern, lds);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, g, queries, nq, ef, cap, entry, max_level, max_candidates,
+                               k_stride, pass_bits, out_ids, out_scores, out_n, stat_evals, cut_walks);
+            return hipGetLastError();
+        };
+        if (reference_nav) {
+            switch (slots) {
+            case 1: return launch(k_hnsw_search_ref_filt<MM, 1>);
+            case 2: return launch(k_hnsw_search_ref_filt<MM, 2>);
+            case 4: return launch(k_hnsw_search_ref_filt<MM, 4>);
+            default: return launch(k_hnsw_search_ref_filt<MM, 8>);
+            }
+        }
+        switch (slots) {
+        case 1: return launch(k_hnsw_search_filt<MM, 1>);
+        case 2: return launch(k_hnsw_search_filt<MM, 2>);
+        case 4: return launch(k_hnsw_search_filt<MM, 4>);
+        default: return launch(k_hnsw_search_filt<MM, 8>);
+        }
+    });
+}
+
+hipError_t launch_hnsw_filter_bits(hipStream_t s, const uint32_t* plist, uint64_t m, uint64_t n_nodes, const uint8_t* live,
+                                   uint32_t* bits, unsigned long long* n_pass)
+{
+    if (m == 0) return hipSuccess;
+    if (!plist || !live || !bits || !n_pass) return hipErrorInvalidValue;
+    const uint64_t blocks = (m + 255) / 256;
+    hipLaunchKernelGGL(k_hnsw_filter_bits, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, plist, m, n_nodes,
+                       live, bits, n_pass);
+    return hipGetLastError();
 }
 
 hipError_t launch_hnsw_insert_search(hipStream_t s, int metric, const HnswGraphView& g, uint32_t first, uint32_t n,

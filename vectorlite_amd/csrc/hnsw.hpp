@@ -74,6 +74,22 @@ hipError_t launch_hnsw_search_ref(hipStream_t s, int metric, const HnswGraphView
                                   uint32_t k_stride, unsigned long long* out_ids, double* out_scores, unsigned long long* out_n,
                                   unsigned long long* stat_evals);
 
+// The id-filtered walk, either navigation.  pass_bits: [ceil(g.cap / 32)] u32, bit v set iff node v
+// passes (launch_hnsw_filter_bits).  The upper layers descend unfiltered; layer 0 keeps one sorted list that is cut, after
+// every insertion, to its first `cap` entries (64 / 128 / 256 / 512, >= ef) and then to the shortest prefix holding ef
+// passing entries.  Results: the passing entries of the final list, at most max_candidates -- in (u64, first seen) order
+// under reference navigation, re-scored with the exact callback and ranked by (value, node) under f32 navigation.
+// *cut_walks (device, not zeroed here) counts the walks in which `cap` dropped a list entry.  Refuses graphs of 2^30
+// nodes or more: the pass flag rides in bit 30 of the beam's node word.
+hipError_t launch_hnsw_search_filtered(hipStream_t s, int metric, bool reference_nav, const HnswGraphView& g,
+                                       const double* queries, uint32_t nq, uint32_t ef, uint32_t cap, uint32_t entry,
+                                       int max_level, uint32_t max_candidates, uint32_t k_stride, const uint32_t* pass_bits,
+                                       unsigned long long* out_ids, double* out_scores, unsigned long long* out_n,
+                                       unsigned long long* stat_evals, unsigned long long* cut_walks);
+// bits (zeroed by the caller) |= the positions plist[0..m) that are below n_nodes and live; *n_pass (zeroed too) += bits set
+hipError_t launch_hnsw_filter_bits(hipStream_t s, const uint32_t* plist, uint64_t m, uint64_t n_nodes, const uint8_t* live,
+                                   uint32_t* bits, unsigned long long* n_pass);
+
 // Build phase A: the rows [first, first+n) are new nodes; each walks the graph that holds the
 // nodes < first (entry/max_level describe it) with beam width ef_construction and writes its own
 // neighbour lists.  Phase B links them back into their neighbours' lists.

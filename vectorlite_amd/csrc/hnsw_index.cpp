@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "hnsw_filter_plan.hpp"
 #include "hnsw_import_plan.hpp"
 
 namespace vl {
@@ -369,6 +370,7 @@ int HnswIndex::add_bulk(const uint64_t* ids, const double* values, uint64_t n, b
     if (n == 0) return OK;
     if (!ids || !values) return ERR_INVALID_ARG;
     std::unique_lock<RwLock> lk(mu_);
+    ++mutations_;  // walk filters build their pass bitmaps again
     VL_HIP(hipSetDevice(device_));
 
     // n sequential add() calls: stop at the first id that already exists (:368-370)
@@ -476,6 +478,7 @@ int HnswIndex::add_bulk(const uint64_t* ids, const double* values, uint64_t n, b
 int HnswIndex::remove(uint64_t id)
 {
     std::unique_lock<RwLock> lk(mu_);
+    ++mutations_;  // walk filters build their pass bitmaps again
     auto it = id_to_node_.find(id);
     if (it == id_to_node_.end()) {  // :401-403
         set_last_error("Vector ID " + std::to_string(id) + " does not exist");
@@ -629,6 +632,7 @@ int HnswIndex::graph_import(uint64_t n, const uint64_t* node_ids, const uint8_t*
     using clock = std::chrono::steady_clock;
     auto ms_since = [](clock::time_point t) { return std::chrono::duration<double, std::milli>(clock::now() - t).count(); };
     std::unique_lock<RwLock> lk(mu_);
+    ++mutations_;  // walk filters build their pass bitmaps again
     if (n_nodes_ != 0 || store_->len() != 0) {
         set_last_error("HNSW graph import needs an empty index: this one holds " + std::to_string(n_nodes_) + " nodes");
         return ERR_INVALID_ARG;
@@ -1000,6 +1004,264 @@ int HnswIndex::search_batch(const double* queries, uint64_t nq, uint64_t q_len, 
     }
     stat_queries_.fetch_add(nq, std::memory_order_relaxed);
     const unsigned long long* h_n = ws->h_out + 2 * nq * kd;
+    for (uint64_t qi = 0; qi < nq; ++qi) {
+        const uint64_t m = std::min<uint64_t>({(uint64_t)h_n[qi], kd, os});
+        std::memcpy(out_ids + qi * os, ws->h_out + qi * kd, m * sizeof(uint64_t));
+        std::memcpy(out_scores + qi * os, ws->h_out + nq * kd + qi * kd, m * sizeof(double));
+        out_n[qi] = m;
+    }
+    return OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// id-filtered search (no reference counterpart)
+// ---------------------------------------------------------------------------------------------
+WalkFilter::~WalkFilter()
+{
+    (void)hipSetDevice(device);
+    if (d_bits) (void)hipFree(d_bits);
+    if (d_count) (void)hipFree(d_count);
+}
+
+int HnswIndex::find_walk_filter(uint64_t token, std::shared_ptr<WalkFilter>* out) const
+{
+    std::lock_guard<std::mutex> g(wfilters_mu_);
+    auto it = wfilters_.find(token);
+    if (token == 0 || it == wfilters_.end()) {
+        set_last_error("unknown HNSW walk filter token " + std::to_string(token) + " (a token belongs to the handle that made it)");
+        return ERR_INVALID_ARG;
+    }
+    *out = it->second;
+    return OK;
+}
+
+int HnswIndex::refresh_walk_filter(WalkFilter* f) const
+{
+    if (f->built_at == mutations_) return OK;
+    f->built_at = ~0ull;
+    VL_HIP(hipSetDevice(device_));
+    std::shared_ptr<IdFilter> keep;
+    const uint32_t* plist = nullptr;
+    uint64_t m = 0;
+    VL_TRY(store_->filter_positions(f->store_token, &keep, &plist, &m));
+    const uint64_t words = std::max<uint64_t>((g_cap_ + 31) / 32, 1);  // the walk reads bits of nodes < n_nodes_ <= g_cap_
+    if (words > f->words) {
+        if (f->d_bits) (void)hipFree(f->d_bits);
+        f->d_bits = nullptr;
+        f->words = 0;
+        VL_HIP(hipMalloc(reinterpret_cast<void**>(&f->d_bits), words * sizeof(uint32_t)));
+        f->words = words;
+    }
+    if (!f->d_count) VL_HIP(hipMalloc(reinterpret_cast<void**>(&f->d_count), sizeof(unsigned long long)));
+    // a stream of its own: filters of different callers are built side by side under the shared lock
+    hipStream_t st = nullptr;
+    VL_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    hipError_t e = hipMemsetAsync(f->d_bits, 0, f->words * sizeof(uint32_t), st);
+    if (e == hipSuccess) e = hipMemsetAsync(f->d_count, 0, sizeof(unsigned long long), st);
+    if (e == hipSuccess) e = launch_hnsw_filter_bits(st, plist, m, n_nodes_, d_live_, f->d_bits, f->d_count);
+    unsigned long long count = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&count, f->d_count, sizeof count, hipMemcpyDeviceToHost, st);
+    const hipError_t se = hipStreamSynchronize(st);
+    (void)hipStreamDestroy(st);
+    if (e == hipSuccess) e = se;
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_last_error(std::string("HNSW walk filter: ") + hipGetErrorString(e));
+        return ERR_DEVICE;
+    }
+    if (count > m || count > live_count_) {
+        set_last_error("the pass bitmap counts more nodes than can pass (kernel bug)");
+        return ERR_DEVICE;
+    }
+    f->n_pass = count;
+    f->subset_rows = m;
+    f->built_at = mutations_;
+    return OK;
+}
+
+int HnswIndex::filter_create(const uint64_t* ids, uint64_t n_ids, uint64_t* out_token, uint64_t* out_nodes)
+{
+    if (!out_token || (!ids && n_ids)) return ERR_INVALID_ARG;
+    *out_token = 0;
+    auto f = std::make_shared<WalkFilter>();
+    f->device = device_;
+    uint64_t rows = 0;
+    VL_TRY(store_->filter_create(ids, n_ids, &f->store_token, &rows));
+    int rc;
+    {
+        std::shared_lock<RwLock> lk(mu_);
+        std::lock_guard<std::mutex> fg(f->mu);
+        rc = refresh_walk_filter(f.get());
+    }
+    if (rc != OK) {
+        const std::string why = last_error();
+        (void)store_->filter_destroy(f->store_token);
+        set_last_error(why);
+        return rc;
+    }
+    const uint64_t token = f->store_token;  // the store's tokens are never 0 and never handed out twice in this process
+    if (out_nodes) *out_nodes = f->n_pass;
+    {
+        std::lock_guard<std::mutex> g(wfilters_mu_);
+        wfilters_[token] = std::move(f);
+    }
+    *out_token = token;
+    return OK;
+}
+
+int HnswIndex::filter_nodes(uint64_t token, uint64_t* out_nodes) const
+{
+    if (!out_nodes) return ERR_INVALID_ARG;
+    std::shared_ptr<WalkFilter> f;
+    VL_TRY(find_walk_filter(token, &f));
+    std::shared_lock<RwLock> lk(mu_);
+    std::lock_guard<std::mutex> fg(f->mu);
+    VL_TRY(refresh_walk_filter(f.get()));
+    *out_nodes = f->n_pass;
+    return OK;
+}
+
+int HnswIndex::filter_destroy(uint64_t token)
+{
+    std::shared_ptr<WalkFilter> f;  // a search still using it holds its own reference: freed when that one ends
+    {
+        std::lock_guard<std::mutex> g(wfilters_mu_);
+        auto it = wfilters_.find(token);
+        if (token == 0 || it == wfilters_.end()) {
+            set_last_error("unknown HNSW walk filter token " + std::to_string(token) + " (a token belongs to the handle that made it)");
+            return ERR_INVALID_ARG;
+        }
+        f = std::move(it->second);
+        wfilters_.erase(it);
+    }
+    return store_->filter_destroy(f->store_token);
+}
+
+// search_exact_fallback's recipe over the filter's subset: the row store's filtered search, asked for k plus the
+// subset's tombstoned rows (each could sit in front of a live one); hnsw_distances on the winners; non-live rows
+// dropped; scores from hnsw_score; stable sort by score; the first min(k, n_pass).
+int HnswIndex::search_filtered_exact(const WalkFilter* f, uint64_t tombs, const double* query, uint64_t k, uint64_t* out_ids,
+                                     double* out_scores, uint64_t* out_n, uint64_t out_limit) const
+{
+    *out_n = 0;
+    const uint64_t want = k > f->subset_rows ? f->subset_rows : std::min<uint64_t>(f->subset_rows, k + tombs);
+    if (want == 0) return OK;
+    std::vector<uint64_t> pos(want);
+    std::vector<double> flat_scores(want);
+    uint64_t got = 0;
+    VL_TRY(store_->search_filtered(f->store_token, query, dim_, want, metric_, pos.data(), nullptr, flat_scores.data(), &got));
+    std::vector<uint64_t> dist(got);
+    VL_TRY(store_->hnsw_distances(query, dim_, metric_, pos.data(), got, dist.data()));
+    struct Res {
+        uint64_t id;
+        double score;
+    };
+    std::vector<Res> res;
+    stat_queries_.fetch_add(1, std::memory_order_relaxed);
+    stat_evals_.fetch_add(f->subset_rows + got, std::memory_order_relaxed);
+    const uint64_t max_candidates = std::min<uint64_t>(k, f->n_pass);
+    for (uint64_t i = 0; i < got && res.size() < max_candidates; ++i) {
+        if (pos[i] >= n_nodes_ || !live_[pos[i]]) continue;
+        res.push_back({node_id_[pos[i]], hnsw_score(dist[i], metric_)});
+    }
+    std::stable_sort(res.begin(), res.end(), [](const Res& a, const Res& b) { return a.score > b.score; });
+    const uint64_t n_out = std::min<uint64_t>(res.size(), out_limit);
+    for (uint64_t i = 0; i < n_out; ++i) {
+        out_ids[i] = res[i].id;
+        out_scores[i] = res[i].score;
+    }
+    *out_n = n_out;
+    return OK;
+}
+
+int HnswIndex::search_filtered(uint64_t token, const double* queries, uint64_t nq, uint64_t q_len, uint64_t k, int metric,
+                               uint32_t ef, uint64_t* out_ids, double* out_scores, uint64_t* out_n, uint64_t out_stride) const
+{
+    const uint64_t os = out_stride ? out_stride : k;
+    if (!out_n && nq) return ERR_INVALID_ARG;
+    for (uint64_t i = 0; i < nq; ++i) out_n[i] = 0;
+    // search_batch's checks, in its order
+    if (metric < 0 || metric > 3) return ERR_INVALID_ARG;
+    if (ef > (uint32_t)HNSW_MAX_EF) {
+        set_last_error("HNSW search: ef = " + std::to_string(ef) + " exceeds the walk's beam ceiling of " + std::to_string(HNSW_MAX_EF));
+        return ERR_INVALID_ARG;
+    }
+    std::shared_lock<RwLock> lk(mu_);
+    if (q_len != dim_) {
+        set_dim_mismatch(dim_, q_len);
+        set_last_error("Dimension mismatch: expected " + std::to_string(dim_) + ", got " + std::to_string(q_len));
+        return ERR_DIM_MISMATCH;
+    }
+    if (metric != metric_) {
+        set_last_error("Metric mismatch: the HNSW index was built for metric " + std::to_string(metric_) +
+                       ", search requested " + std::to_string(metric));
+        return ERR_METRIC_MISMATCH;
+    }
+    std::shared_ptr<WalkFilter> f;
+    VL_TRY(find_walk_filter(token, &f));
+    if (nq == 0 || k == 0) return OK;
+    if (!queries || !out_ids || !out_scores) return ERR_INVALID_ARG;
+    {
+        std::lock_guard<std::mutex> fg(f->mu);
+        VL_TRY(refresh_walk_filter(f.get()));
+    }
+    // current until mu_ is released: the bitmap changes only after a mutation, and those take mu_ exclusively
+    const uint64_t n_pass = f->n_pass;
+    HnswFilterPlan plan = hnsw_filter_plan(k, ef, min_beam_.load(), n_nodes_, n_pass);
+    if (plan.route == 0 && g_cap_ >= (1ull << 30)) plan.route = 1;  // the walk keeps the pass flag in bit 30 of the node word
+    last_filt_route_.store(plan.route, std::memory_order_relaxed);
+    last_filt_cap_.store(plan.route == 0 ? plan.cap : 0u, std::memory_order_relaxed);
+    last_filt_pass_.store(n_pass, std::memory_order_relaxed);
+    last_filt_cut_.store(0, std::memory_order_relaxed);
+    if (n_pass == 0) return OK;
+    if (plan.route == 1) {
+        const uint64_t tombs = f->subset_rows - n_pass;
+        for (uint64_t qi = 0; qi < nq; ++qi)
+            VL_TRY(search_filtered_exact(f.get(), tombs, queries + qi * dim_, k, out_ids + qi * os, out_scores + qi * os,
+                                         out_n + qi, os));
+        return OK;
+    }
+
+    VL_HIP(hipSetDevice(device_));
+    const uint64_t kd = plan.max_candidates;  // <= ef_walk <= cap <= HNSW_MAX_EF
+    WalkScratch* ws = acquire_scratch(nq);
+    if (!ws) return ERR_OOM;
+    struct Back {
+        const HnswIndex* h;
+        WalkScratch* w;
+        ~Back()
+        {
+            (void)hipStreamSynchronize(w->stream);
+            h->release_scratch(w);
+        }
+    } back{this, ws};
+    hipStream_t st = ws->stream;
+    {
+        const int rc = ensure_io(ws, nq + 1, kd);  // one query's worth more: the cut-walk counter sits behind the counts
+        if (rc != OK) return rc;
+    }
+    VL_HIP(hipMemcpyAsync(ws->d_q, queries, nq * dim_ * sizeof(double), hipMemcpyHostToDevice, st));
+    const HnswGraphView g = view(ws);
+    unsigned long long* d_ids = ws->d_out;
+    double* d_scores = reinterpret_cast<double*>(ws->d_out + nq * kd);
+    unsigned long long* d_n = ws->d_out + 2 * nq * kd;
+    unsigned long long* d_cut = d_n + nq;
+    const uint64_t out_words = nq * (2 * kd + 1) + 1;
+    hipError_t le = hipMemsetAsync(d_cut, 0, sizeof(unsigned long long), st);
+    if (le == hipSuccess)
+        le = launch_hnsw_search_filtered(st, metric_, nav_.load() == NAV_REFERENCE, g, ws->d_q, (uint32_t)nq, (uint32_t)plan.ef_walk,
+                                         plan.cap, entry_, max_level_, (uint32_t)plan.max_candidates, (uint32_t)kd, f->d_bits, d_ids,
+                                         d_scores, d_n, d_stat_evals_, d_cut);
+    if (le == hipSuccess) le = hipMemcpyAsync(ws->h_out, ws->d_out, out_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+    const hipError_t se = hipStreamSynchronize(st);
+    if (le == hipSuccess) le = se;
+    if (le != hipSuccess) {
+        set_last_error(std::string("filtered HNSW walk: ") + hipGetErrorString(le));
+        return ERR_DEVICE;
+    }
+    stat_queries_.fetch_add(nq, std::memory_order_relaxed);
+    const unsigned long long* h_n = ws->h_out + 2 * nq * kd;
+    last_filt_cut_.store(h_n[nq], std::memory_order_relaxed);
     for (uint64_t qi = 0; qi < nq; ++qi) {
         const uint64_t m = std::min<uint64_t>({(uint64_t)h_n[qi], kd, os});
         std::memcpy(out_ids + qi * os, ws->h_out + qi * kd, m * sizeof(uint64_t));

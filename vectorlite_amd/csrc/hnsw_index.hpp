@@ -51,6 +51,22 @@ struct WalkScratch {
     ~WalkScratch();
 };
 
+// A walk filter of one HNSW handle (vl_index_hnsw_filter_create): an id filter of the row store (its ascending position
+// list; node index = storage position) and the pass bitmap built from it -- bit v set iff node v is in the list AND live.
+// The bitmap belongs to the handle's mutation count `built_at`; a call that finds the count moved on builds it again.
+struct WalkFilter {
+    std::mutex mu;                        // guards everything below (taken after the index lock)
+    int device = 0;
+    uint64_t store_token = 0;             // the row store's IdFilter; also this filter's token
+    uint32_t* d_bits = nullptr;           // [words]
+    uint64_t words = 0;
+    unsigned long long* d_count = nullptr;
+    uint64_t n_pass = 0;                  // bits set
+    uint64_t subset_rows = 0;             // rows of the store's list, tombstoned ones included
+    uint64_t built_at = ~0ull;
+    ~WalkFilter();
+};
+
 struct HnswGraphProbe;  // tests/native/hnsw_graph_audit.hip: reads the graph arrays and the scratch pool
 
 class HnswIndex {
@@ -90,6 +106,26 @@ public:
                double* out_scores, uint64_t* out_n, uint64_t out_stride = 0) const;
     int search_batch(const double* queries, uint64_t nq, uint64_t q_len, uint64_t k, int metric, uint32_t ef,
                      uint64_t* out_ids, double* out_scores, uint64_t* out_n, uint64_t out_stride = 0) const;
+    // NEW (no reference counterpart): walks restricted to the nodes whose id is in a set.  A filter
+    // is a token of this handle (never 0, never reused, not cloned, freed with the handle); ids may be unsorted and repeat,
+    // ids the index does not hold are ignored.  *out_nodes / filter_nodes: the nodes that pass now (in the set and live).
+    int filter_create(const uint64_t* ids, uint64_t n_ids, uint64_t* out_token, uint64_t* out_nodes);
+    int filter_nodes(uint64_t token, uint64_t* out_nodes) const;
+    int filter_destroy(uint64_t token);
+    // search_batch's arguments, errors and outputs; one filter serves every query of the batch.  Returns per query the
+    // passing nodes a walk of width ef_walk finds (hnsw_filter_plan.hpp: walk route), or the exact nearest passing rows
+    // (exact route).  Never joins a coalesced pass.
+    int search_filtered(uint64_t token, const double* queries, uint64_t nq, uint64_t q_len, uint64_t k, int metric, uint32_t ef,
+                        uint64_t* out_ids, double* out_scores, uint64_t* out_n, uint64_t out_stride = 0) const;
+    // the last search_filtered on this handle that reached the plan: route (0 walk, 1 exact), the walk's list capacity
+    // (0 on the exact route), the passing nodes, and the walks whose list was cut at that capacity
+    void last_filtered(int* route, uint32_t* cap, uint64_t* pass_nodes, uint64_t* cap_cut_walks) const
+    {
+        if (route) *route = last_filt_route_.load(std::memory_order_relaxed);
+        if (cap) *cap = last_filt_cap_.load(std::memory_order_relaxed);
+        if (pass_nodes) *pass_nodes = last_filt_pass_.load(std::memory_order_relaxed);
+        if (cap_cut_walks) *cap_cut_walks = last_filt_cut_.load(std::memory_order_relaxed);
+    }
     uint64_t len() const;
     uint64_t dimension() const { return dim_; }
     int device() const { return device_; }
@@ -147,6 +183,11 @@ private:
     int ensure_io(WalkScratch* ws, uint64_t nq, uint64_t k) const;
     int search_exact_fallback(const double* query, uint64_t k, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
                               uint64_t out_limit) const;
+    int find_walk_filter(uint64_t token, std::shared_ptr<WalkFilter>* out) const;
+    int refresh_walk_filter(WalkFilter* f) const;  // mu_ held (shared or unique), f->mu held: builds the bitmap if stale
+    // the exact route of one query; mu_ held (shared), n_pass > 0, tombs = tombstoned rows of the filter's subset
+    int search_filtered_exact(const WalkFilter* f, uint64_t tombs, const double* query, uint64_t k, uint64_t* out_ids,
+                              double* out_scores, uint64_t* out_n, uint64_t out_limit) const;
 
     const uint64_t dim_;
     const int metric_;
@@ -187,6 +228,12 @@ private:
     std::vector<uint8_t> live_;
     uint64_t live_count_ = 0;
     double import_ms_[5] = {0, 0, 0, 0, 0};  // last graph_import, see last_import_ms()
+    uint64_t mutations_ = 0;  // add / delete / import calls so far (a walk filter's staleness test: tombstoning counts)
+    mutable std::mutex wfilters_mu_;  // the filter table; never held while mu_ or a filter's mutex is taken
+    std::unordered_map<uint64_t, std::shared_ptr<WalkFilter>> wfilters_;
+    mutable std::atomic<int> last_filt_route_{0};
+    mutable std::atomic<uint32_t> last_filt_cap_{0};
+    mutable std::atomic<uint64_t> last_filt_pass_{0}, last_filt_cut_{0};
 
     std::atomic<uint32_t> min_beam_{0};  // 0 = the reference's strict ef = min(k, len); a wider floor is opt-in
     std::atomic<int> nav_{NAV_F32};      // walk navigation; the reference's u64 order is opt-in
