@@ -215,6 +215,26 @@ int vl_index_search_batch_filtered(const vl_index *h, uint64_t filter, const dou
                                    uint64_t k, int metric, uint64_t out_stride, uint64_t *out_ids, double *out_scores,
                                    uint64_t *out_n);
 
+/* nq filtered searches, each with its own filter -- a server's batch of requests from different users.
+ * row i = vl_index_search_filtered(h, filters[n_filters == 1 ? 0 : i], queries + i*q_len, q_len, k, metric, ...)
+ * n_filters is 1 (one filter for the batch: vl_index_search_batch_filtered) or nq (one per query); rows out_stride apart,
+ * capped at out_stride.  The same token may appear many times, filters may overlap, be empty or stale (every distinct
+ * stale filter is resolved once per call).  The jobs share scan launches: one launch, one finalize and one
+ * synchronisation for up to 512 (query, filter) pairs, the keys and the certificate of the single filtered search.
+ * Checks are the single call's in its order: n_filters other than 1 or nq is VL_ERR_INVALID_ARG; then every token of the
+ * array (0, unknown, destroyed: VL_ERR_INVALID_ARG); the metric; the dimension whenever len(h) != 0; k = 0 or nq = 0
+ * is VL_OK with nothing written.  If a query fails (a NaN score inside its subset) the call returns the status of the
+ * lowest-numbered failing query; rows in front of it hold their answers and out_n is 0 from that query on. */
+int vl_index_search_batch_filters(const vl_index *h, const uint64_t *filters, uint64_t n_filters,
+                                  const double *queries, uint64_t nq, uint64_t q_len, uint64_t k, int metric,
+                                  uint64_t out_stride, uint64_t *out_ids, double *out_scores, uint64_t *out_n);
+/* Of the last such call on this handle (either entry point; any argument may be NULL): batched = jobs answered by a
+ * batched launch; single = jobs handed to the single filtered search before any launch (k beyond the fast path, a forced
+ * path, a query or rows outside the f32 domain, a job alone in its launch); exact = jobs a batched launch could not
+ * certify (redone on the exact kernels); launches = batched scan launches.  Jobs with an empty subset count nowhere. */
+int vl_index_last_filtered_batch(const vl_index *h, uint64_t *batched, uint64_t *single, uint64_t *exact,
+                                 uint64_t *launches);
+
 /* NEW capability (the reference only answers "the best k"): every row that is at least this similar.  min_score is a
  * score in the reference's sense (higher is better for all four metrics, src/lib.rs:425-572; Euclidean and Manhattan are
  * 1 / (1 + d)).  The answer is the LONGEST PREFIX of FlatIndex::search(q, len, metric) (src/index/flat.rs:98-119) whose

@@ -45,6 +45,8 @@ extern "C" {
     fn vl_index_filter_create(h: *mut vl_index, ids: *const u64, n_ids: u64, out_filter: *mut u64, out_rows: *mut u64) -> c_int;
     fn vl_index_filter_destroy(h: *mut vl_index, filter: u64) -> c_int;
     fn vl_index_search_filtered(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, k: u64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
+    fn vl_index_search_batch_filters(h: *const vl_index, filters: *const u64, n_filters: u64, queries: *const f64, nq: u64, q_len: u64, k: u64, metric: c_int, out_stride: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
+    fn vl_index_last_filtered_batch(h: *const vl_index, batched: *mut u64, single: *mut u64, exact: *mut u64, launches: *mut u64) -> c_int;
     fn vl_index_search_range(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, min_score: f64, metric: c_int, out_ids: *mut u64, out_scores: *mut f64, out_capacity: u64, out_n: *mut u64, out_total: *mut u64) -> c_int;
     fn vl_index_search_range_batch(h: *const vl_index, filter: u64, queries: *const f64, nq: u64, q_len: u64, min_scores: *const f64, metric: c_int, out_stride: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64, out_total: *mut u64) -> c_int;
     fn vl_index_last_range_batch(h: *const vl_index, mfma_queries: *mut u64, single_queries: *mut u64, exact_queries: *mut u64) -> c_int;
@@ -330,6 +332,74 @@ impl GpuFlatIndex {
             VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
             _ => Err(VectorLiteError::InternalError(err)),
         }
+    }
+
+    /// A batch of filtered searches, one id set per query (no reference counterpart): entry `i` is exactly
+    /// `search_filtered(filters[i], &queries[i], k, metric)`.  The (query, filter) pairs share scan launches -- a server's
+    /// batch of requests from different users.  All queries must have one length.  Single-GPU handles only.
+    pub fn search_batch_filtered(&self, filters: &[&[u64]], queries: &[Vec<f64>], k: usize, metric: SimilarityMetric) -> VectorLiteResult<Vec<Vec<SearchResult>>> {
+        let nq = queries.len();
+        if nq == 0 {
+            return Ok(Vec::new());
+        }
+        let q_len = queries[0].len();
+        if filters.len() != nq || queries.iter().any(|q| q.len() != q_len) {
+            return Err(VectorLiteError::InternalError("search_batch_filtered: one id set per query, queries of one length".to_string()));
+        }
+        let mut tokens: Vec<u64> = Vec::with_capacity(nq);
+        let destroy = |tokens: &[u64]| {
+            for &t in tokens {
+                unsafe { vl_index_filter_destroy(self.0.raw, t) };
+            }
+        };
+        let mut most_rows = 0u64;
+        for ids in filters {
+            let (mut token, mut rows) = (0u64, 0u64);
+            let rc = unsafe { vl_index_filter_create(self.0.raw, ids.as_ptr(), ids.len() as u64, &mut token, &mut rows) };
+            if rc != VL_OK {
+                let err = last_error();
+                destroy(&tokens);
+                return Err(VectorLiteError::InternalError(err));
+            }
+            tokens.push(token);
+            most_rows = most_rows.max(rows);
+        }
+        let stride = k.min(most_rows as usize).max(1);
+        let flat: Vec<f64> = queries.iter().flat_map(|q| q.iter().copied()).collect();
+        let (mut out_ids, mut scores, mut n) = (vec![0u64; nq * stride], vec![0f64; nq * stride], vec![0u64; nq]);
+        let rc = unsafe {
+            vl_index_search_batch_filters(self.0.raw, tokens.as_ptr(), nq as u64, flat.as_ptr(), nq as u64, q_len as u64, k as u64, metric_code(metric), stride as u64, out_ids.as_mut_ptr(), scores.as_mut_ptr(), n.as_mut_ptr())
+        };
+        let err = if rc == VL_OK { String::new() } else { last_error() };
+        destroy(&tokens);
+        match rc {
+            VL_OK => Ok((0..nq)
+                .map(|qi| {
+                    (0..n[qi] as usize)
+                        .map(|i| {
+                            let id = out_ids[qi * stride + i];
+                            let (text, metadata) = self.0.side.get(&id).cloned().unwrap_or_default();
+                            SearchResult { id, score: scores[qi * stride + i], text, metadata }
+                        })
+                        .collect()
+                })
+                .collect()),
+            VL_ERR_DIM_MISMATCH => {
+                let (mut e, mut a) = (0u64, 0u64);
+                unsafe { vl_last_dim_mismatch(&mut e, &mut a) };
+                Err(VectorLiteError::DimensionMismatch { expected: e as usize, actual: a as usize })
+            }
+            VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
+            _ => Err(VectorLiteError::InternalError(err)),
+        }
+    }
+
+    /// Routing of the last filtered batch: jobs answered by a batched launch, jobs handed to the single filtered search,
+    /// jobs a batched launch could not certify (redone exactly), and the batched scan launches.
+    pub fn last_filtered_batch(&self) -> (u64, u64, u64, u64) {
+        let (mut a, mut b, mut c, mut d) = (0u64, 0u64, 0u64, 0u64);
+        unsafe { vl_index_last_filtered_batch(self.0.raw, &mut a, &mut b, &mut c, &mut d) };
+        (a, b, c, d)
     }
 
     /// `search_range` for a batch of queries against one index state (no reference counterpart): entry `i` holds at most

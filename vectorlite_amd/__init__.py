@@ -736,19 +736,45 @@ class FlatIndex:
                                                  _pu64(ids), _pf64(scores), C.byref(n)))
         return pos[: n.value].copy(), ids[: n.value].copy(), scores[: n.value].copy()
 
-    def search_batch(self, queries, k: int, metric: int = 0, filter=None):
+    def search_batch(self, queries, k: int, metric: int = 0, filter=None, filters=None):
         """New capability (no reference counterpart): nq independent searches.
         Returns (ids [nq, k], scores [nq, k], n [nq]); row i is exactly search(queries[i]) (with `filter`: exactly
-        search(queries[i], filter=filter))."""
+        search(queries[i], filter=filter); with `filters`, a sequence of nq items each an IdFilter of this index or an
+        iterable of ids: exactly search(queries[i], filter=filters[i])).  The filtered forms share scan launches
+        (last_filtered_batch() tells how the jobs were routed)."""
+        if filter is not None and filters is not None:
+            raise ValueError("give `filter` (one for the batch) or `filters` (one per query), not both")
         Q = _f64(queries)
         if Q.ndim != 2:
             raise ValueError("queries must be [nq, dim]")
         nq, qlen = Q.shape
+        if filters is not None:
+            filters = list(filters)
+            if len(filters) != nq:
+                raise ValueError("`filters` must hold one filter per query (%d queries, %d filters)" % (nq, len(filters)))
         kk = max(min(int(k), self.len()), 1)   # min(k, len) results at most; k is clamped to the buffers
         kc = min(int(k), kk)
         ids = np.zeros((nq, kk), dtype=np.uint64)
         scores = np.zeros((nq, kk), dtype=np.float64)
         n = np.zeros(max(nq, 1), dtype=np.uint64)
+        if filters is not None:
+            temps = []
+            try:
+                toks = np.zeros(max(nq, 1), dtype=np.uint64)
+                for i, f in enumerate(filters):
+                    tok, temp = self._filter_token(f)
+                    if temp is not None:
+                        temps.append(temp)
+                    toks[i] = tok
+                rc = self._L.vl_index_search_batch_filters(self._h, _pu64(toks), nq, _pf64(Q), nq, qlen, kc, int(metric), kk,
+                                                           _pu64(ids), _pf64(scores), _pu64(n))
+            finally:
+                for temp in temps:
+                    temp.close()
+            if rc == VL_ERR_INVALID_ARG:
+                raise IndexOpError(_last_error())
+            _raise(rc)
+            return ids[:, :kc], scores[:, :kc], n[:nq]
         if filter is not None:
             tok, temp = self._filter_token(filter)
             try:
@@ -764,6 +790,14 @@ class FlatIndex:
         _raise(self._L.vl_index_search_batch(self._h, _pf64(Q), nq, qlen, kc, int(metric), _pu64(ids),
                                              _pf64(scores), _pu64(n)))
         return ids[:, :kc], scores[:, :kc], n[:nq]
+
+    def last_filtered_batch(self) -> Dict[str, int]:
+        """Routing of the last filtered search_batch on this handle: jobs (query, filter pairs) answered by a batched
+        launch, jobs handed to the single filtered search before any launch, jobs a batched launch could not certify
+        (redone on the exact kernels), and the batched scan launches.  Jobs with an empty subset count nowhere."""
+        a, b, c, d = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _raise(self._L.vl_index_last_filtered_batch(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return {"batched": int(a.value), "single": int(b.value), "exact": int(c.value), "launches": int(d.value)}
 
     def search_batch_device(self, queries, k: int, metric: int = 0, with_positions: bool = False):
         """search_batch for queries that are already on this index's GPU: `queries` is a contiguous float64 torch tensor

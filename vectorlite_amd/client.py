@@ -14,7 +14,7 @@ import enum
 import itertools
 import threading
 from dataclasses import dataclass
-from typing import Any, Callable, Dict, List, Optional
+from typing import Any, Callable, Dict, List, Optional, Sequence
 
 from . import (DimensionMismatch, FlatIndex, HNSWIndex, IndexOpError, SearchResult, SimilarityMetric, Vector,
                VectorLiteError)
@@ -109,6 +109,49 @@ class Collection:
         ids = [i for i, (_text, md) in list(self.index._meta.items()) if where(md)]
         return self.index.search(embedding, k, similarity_metric, filter=ids)
 
+    def search_texts(self, texts: Sequence[str], k: int, similarity_metric: SimilarityMetric, embedding_function,
+                     wheres: Optional[Sequence[Optional[Callable[[Any], bool]]]] = None) -> List[List[SearchResult]]:
+        """search_text for a batch of requests, each with its own optional predicate (`wheres[i]`, None: no filter) -- what
+        a server does with the requests of different users that arrive together.  Entry i is exactly
+        search_text(texts[i], ..., where=wheres[i]).  Predicates that select the same id set share one filter; the
+        filtered queries go through one FlatIndex.search_batch(filters=...), the others through one search_batch."""
+        texts = list(texts)
+        wheres = [None] * len(texts) if wheres is None else list(wheres)
+        if len(wheres) != len(texts):
+            raise ValueError("`wheres` must hold one predicate (or None) per text")
+        embeddings = [embedding_function.generate_embedding(t) for t in texts]
+        if not isinstance(self.index, FlatIndex):  # no batched filters there: one by one
+            return [self.index.search(e, k, similarity_metric) if w is None else
+                    self.index.search(e, k, similarity_metric, filter=[i for i, (_t, md) in list(self.index._meta.items()) if w(md)])
+                    for e, w in zip(embeddings, wheres)]
+        out: List[List[SearchResult]] = [[] for _ in texts]
+
+        def fill(rows, ids, scores, n):
+            for r, qi in enumerate(rows):
+                for i, s in zip(ids[r, :int(n[r])].tolist(), scores[r, :int(n[r])].tolist()):
+                    text, md = self.index._meta.get(i, ("", None))
+                    out[qi].append(SearchResult(id=i, score=s, text=text, metadata=md))
+
+        plain = [qi for qi, w in enumerate(wheres) if w is None]
+        if plain:
+            fill(plain, *self.index.search_batch([embeddings[qi] for qi in plain], k, similarity_metric))
+        picky = [qi for qi, w in enumerate(wheres) if w is not None]
+        if picky:
+            meta = list(self.index._meta.items())
+            by_ids: Dict[tuple, Any] = {}  # id set -> its filter
+            try:
+                filters = []
+                for qi in picky:
+                    key = tuple(sorted(i for i, (_text, md) in meta if wheres[qi](md)))
+                    if key not in by_ids:
+                        by_ids[key] = self.index.make_filter(key)
+                    filters.append(by_ids[key])
+                fill(picky, *self.index.search_batch([embeddings[qi] for qi in picky], k, similarity_metric, filters=filters))
+            finally:
+                for f in by_ids.values():
+                    f.close()
+        return out
+
     def search_text_mmr(self, query_text: str, k: int, similarity_metric: SimilarityMetric, embedding_function,
                         fetch_k: int = 20, lambda_mult: float = 0.5) -> List[SearchResult]:
         """search_text with diversified results: maximal marginal relevance over the best fetch_k chunks (flat
@@ -185,6 +228,15 @@ class VectorLiteClient:
         if similarity_metric is None:  # src/client.rs:143-155
             similarity_metric = c.index.metric() if isinstance(c.index, HNSWIndex) else SimilarityMetric.Cosine
         return c.search_text(query_text, k, similarity_metric, self.embedding_function, where=where)
+
+    def search_texts_in_collection(self, collection_name: str, query_texts: Sequence[str], k: int,
+                                   similarity_metric: Optional[SimilarityMetric] = None,
+                                   wheres: Optional[Sequence[Optional[Callable[[Any], bool]]]] = None) -> List[List[SearchResult]]:
+        """search_text_in_collection for a batch of requests, each with its own optional `where` (Collection.search_texts)."""
+        c = self._get(collection_name)
+        if similarity_metric is None:
+            similarity_metric = c.index.metric() if isinstance(c.index, HNSWIndex) else SimilarityMetric.Cosine
+        return c.search_texts(query_texts, k, similarity_metric, self.embedding_function, wheres=wheres)
 
     def delete_from_collection(self, collection_name: str, id: int) -> None:
         self._get(collection_name).delete(id)

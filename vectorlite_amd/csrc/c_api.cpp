@@ -504,9 +504,9 @@ int vl_index_search_grouped(const vl_index* h, uint64_t groups, uint64_t filter,
     });
 }
 
-int vl_index_search_batch_filtered(const vl_index* h, uint64_t filter, const double* queries, uint64_t nq, uint64_t q_len,
-                                   uint64_t k, int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores,
-                                   uint64_t* out_n)
+int vl_index_search_batch_filters(const vl_index* h, const uint64_t* filters, uint64_t n_filters, const double* queries,
+                                  uint64_t nq, uint64_t q_len, uint64_t k, int metric, uint64_t out_stride, uint64_t* out_ids,
+                                  double* out_scores, uint64_t* out_n)
 {
     return guarded([&]() -> int {
         if (!h || (!out_n && nq)) return VL_ERR_INVALID_ARG;
@@ -514,17 +514,25 @@ int vl_index_search_batch_filtered(const vl_index* h, uint64_t filter, const dou
         VL_FILTER_HANDLE(h);
         if (nq == 0) return VL_OK;
         if (!queries && q_len) return VL_ERR_INVALID_ARG;
-        const uint64_t kk = k < out_stride ? k : out_stride;
+        const uint64_t kk = k < out_stride ? k : out_stride;  // a smaller k's answer is a prefix (vl_index_search_cap)
         if ((!out_ids || !out_scores) && kk != 0) return VL_ERR_INVALID_ARG;
         // each row is the single filtered search's answer, rows out_stride apart
-        for (uint64_t q = 0; q < nq; ++q) {
-            const int rc = h->flat->search_filtered(filter, queries + q * q_len, q_len, kk, metric, nullptr,
-                                                    kk ? out_ids + q * out_stride : nullptr,
-                                                    kk ? out_scores + q * out_stride : nullptr, out_n + q);
-            if (rc != VL_OK) return rc;
-        }
-        return VL_OK;
+        return h->flat->search_batch_filters(filters, n_filters, queries, nq, q_len, kk, metric, out_stride, out_ids, out_scores, out_n);
     });
+}
+
+int vl_index_search_batch_filtered(const vl_index* h, uint64_t filter, const double* queries, uint64_t nq, uint64_t q_len,
+                                   uint64_t k, int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores,
+                                   uint64_t* out_n)
+{
+    return vl_index_search_batch_filters(h, &filter, 1, queries, nq, q_len, k, metric, out_stride, out_ids, out_scores, out_n);
+}
+
+int vl_index_last_filtered_batch(const vl_index* h, uint64_t* batched, uint64_t* single, uint64_t* exact, uint64_t* launches)
+{
+    if (!h || !h->flat) return VL_ERR_INVALID_ARG;
+    h->flat->last_filtered_batch(batched, single, exact, launches);
+    return VL_OK;
 }
 
 int vl_index_search_batch_cap(const vl_index* h, const double* queries, uint64_t nq, uint64_t q_len, uint64_t k,

@@ -9,6 +9,7 @@
 #include "lazy_buffers.hpp"
 #include "shard.hpp"
 #include "score_bound.hpp"
+#include "subset_batch_plan.hpp"
 
 #include <chrono>
 
@@ -297,6 +298,38 @@ bool stage_query(const double* q, double* dst, uint64_t dim, double* norm_out)
         *norm_out = norm;
     }
     return in_domain;
+}
+
+// stage_query's verdict without the copy (the same sums in the same order): a filtered batch plans its launches before it
+// stages any query, and the plan has to know which jobs may take the fast path.
+bool query_in_domain(const double* q, uint64_t dim)
+{
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0;
+    uint64_t i = 0;
+    for (; i + 4 <= dim; i += 4) {
+        const double a = q[i], b = q[i + 1], c = q[i + 2], d = q[i + 3];
+        s0 += a * a;
+        s1 += b * b;
+        s2 += c * c;
+        s3 += d * d;
+        const double fa = std::fabs(a), fb = std::fabs(b), fc = std::fabs(c), fd = std::fabs(d);
+        m0 = fa > m0 ? fa : m0;
+        m1 = fb > m1 ? fb : m1;
+        m2 = fc > m2 ? fc : m2;
+        m3 = fd > m3 ? fd : m3;
+    }
+    for (; i < dim; ++i) {
+        const double a = q[i];
+        s0 += a * a;
+        const double fa = std::fabs(a);
+        m0 = fa > m0 ? fa : m0;
+    }
+    const double qq = (s0 + s1) + (s2 + s3);
+    const double m01 = m0 > m1 ? m0 : m1, m23 = m2 > m3 ? m2 : m3;
+    const double qmax = m01 > m23 ? m01 : m23;
+    const double norm = std::sqrt(qq);
+    const bool finite = qq == qq && qmax <= 1.797693134862315708e308 && norm <= 1.797693134862315708e308;
+    return finite && qmax <= DOMAIN_MAX_ABS && (norm == 0.0 || norm >= DOMAIN_MIN_NORM);
 }
 
 // The single-query entry points stage their query here instead: ws->h_q64 = the f64 values, then the norm.  Two staging
@@ -1069,7 +1102,7 @@ int GpuFlatIndex::search_batch_locked(const double* queries, uint64_t nq, uint64
     // blockIdx.y, each group one pass over the slab -- and ONE finalize launch, then one stream sync: staged, launched and
     // synchronised pass by pass a 50 000-row index answered 70-100 k Manhattan queries per second where cosine batches
     // reach millions (round 3's verdict, item 8).
-    const size_t k3_words = (size_t)K3_PIPE_QUERIES * (dim_ + 1);
+    const size_t k3_words = k3_stage_words(dim_);
     VL_TRY(ensure_set(HipMem{}, {dev_buf(ws->k3_d_q64, k3_words), pinned_buf(ws->k3_h_q64, k3_words),
                                  pinned_buf(ws->k3_h_result, K3_PIPE_QUERIES)}));
     std::vector<uint8_t> in_domain((size_t)K3_PIPE_QUERIES);
@@ -1605,7 +1638,7 @@ int GpuFlatIndex::search_filtered(uint64_t token, const double* query, uint64_t 
 
 int GpuFlatIndex::search_subset(Workspace* ws, IdFilter* f, const double* query, uint64_t k_eff, int metric,
                                 uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
-                                const MmrReq* mmr) const
+                                const MmrReq* mmr, bool exact_only) const
 {
     const uint64_t m = f->m;
     const uint32_t* plist = f->d_plist;
@@ -1623,7 +1656,7 @@ int GpuFlatIndex::search_subset(Workspace* ws, IdFilter* f, const double* query,
     };
 
     // the fast path's conditions are search_locked's; the out-of-domain count is the whole index's (conservative)
-    const bool fast_ok = force_path_.load() == 0 && k_eff <= (uint64_t)KFAST_MAX && n_out_of_domain_ == 0 && q_in_domain;
+    const bool fast_ok = !exact_only && force_path_.load() == 0 && k_eff <= (uint64_t)KFAST_MAX && n_out_of_domain_ == 0 && q_in_domain;
     if (fast_ok) {
         const bool prof = profile_.load();
         ScanPlan plan;
@@ -1682,6 +1715,142 @@ int GpuFlatIndex::search_subset(Workspace* ws, IdFilter* f, const double* query,
     auto storage_pos = [&](uint64_t i) { return idx[i] < m ? f->h_plist[idx[i]] : POS_SENTINEL; };
     VL_TRY(deliver("filtered exact path", ids_, k_eff, storage_pos, [&](uint64_t i) { return scores[i]; }, out_pos, out_ids, out_scores));
     *out_n = k_eff;
+    return OK;
+}
+
+// A batch of filtered searches, one filter for all queries or one per query.  Every (query, filter)
+// pair is a job.  The jobs that may take the fast path are planned into launches (subset_batch_plan.hpp); a launch is one
+// H2D copy of its queries, norms and job table, one k_scan_subset_jobs, one finalize into the pinned K3 result blocks and
+// one stream sync -- search_batch's K3 pipeline, where the single path pays a launch pair and a stamp wait per query.
+// The certificate is the single path's, per job (n_rows = m, k = min(k, m)); what it refuses goes to the exact kernels,
+// what the plan left out to search_subset.
+static_assert(sizeof(SubsetJobDev) == 2 * sizeof(double), "k3_stage_words() counts two words per job table entry");
+
+int GpuFlatIndex::search_batch_filters(const uint64_t* tokens, uint64_t n_filters, const double* queries, uint64_t nq,
+                                       uint64_t q_len, uint64_t k, int metric, uint64_t out_stride, uint64_t* out_ids,
+                                       double* out_scores, uint64_t* out_n) const
+{
+    if (nq == 0) return OK;
+    if (!out_n) return ERR_INVALID_ARG;
+    for (uint64_t i = 0; i < nq; ++i) out_n[i] = 0;
+    if (n_filters != 1 && n_filters != nq) {
+        set_last_error("a filtered batch takes one filter, or one filter per query");
+        return ERR_INVALID_ARG;
+    }
+    if (!tokens) return ERR_INVALID_ARG;
+    // every distinct token is looked up once; the references keep the filters alive until the call ends
+    std::vector<std::shared_ptr<IdFilter>> filters;
+    std::vector<uint32_t> filter_of(n_filters);
+    {
+        std::unordered_map<uint64_t, uint32_t> slot;
+        for (uint64_t i = 0; i < n_filters; ++i) {
+            auto it = slot.find(tokens[i]);
+            if (it == slot.end()) {
+                std::shared_ptr<IdFilter> f;
+                VL_TRY(find_filter(tokens[i], &f));
+                it = slot.emplace(tokens[i], (uint32_t)filters.size()).first;
+                filters.push_back(std::move(f));
+            }
+            filter_of[i] = it->second;
+        }
+    }
+    std::shared_lock<RwLock> lk;
+    VL_TRY(lock_for_query(metric, q_len, &lk));  // the whole index's length check, even when every subset is empty
+    if (ids_.empty() || k == 0) return OK;
+    if ((!queries && dim_) || !out_ids || !out_scores || k > out_stride) return ERR_INVALID_ARG;
+
+    WsLease lease(this, /*sync_always=*/true);
+    if (lease.status() != OK) return lease.status();
+    Workspace* const ws = lease.ws;
+    hipStream_t st = ws->stream;
+    for (const auto& f : filters) VL_TRY(resolve_if_stale(ws, f.get()));  // each stale filter once, whatever its number of jobs
+    InFlight searching(active_searches_);
+
+    auto filter_at = [&](uint64_t qi) { return filters[filter_of[n_filters == 1 ? 0 : qi]].get(); };
+    const bool may_batch = force_path_.load() == 0 && n_out_of_domain_ == 0 && dim_ != 0;
+    int shape_g = 1, shape_u = 1, resident = 1;
+    if (may_batch) VL_HIP(scan_subset_jobs_shape(metric, ld_, &shape_g, &shape_u, &resident));
+    std::vector<SubsetJob> jobs(nq);
+    for (uint64_t qi = 0; qi < nq; ++qi) {
+        const uint64_t m = filter_at(qi)->m;
+        jobs[qi].m = m;
+        jobs[qi].need = subset_job_need(m, shape_g, shape_u);
+        jobs[qi].fast = may_batch && m > 0 && std::min<uint64_t>(k, m) <= (uint64_t)KFAST_MAX && query_in_domain(queries + qi * dim_, dim_);
+    }
+    const SubsetBatchPlan plan = subset_batch_plan(
+        jobs, {(uint32_t)resident, (uint32_t)K3_PIPE_QUERIES, (uint64_t)PARTIALS32_LISTS, (uint32_t)SCAN_BATCH_QB, (uint32_t)SCAN_BATCH_MAX_GRID});
+
+    enum : uint8_t { DONE = 0, SINGLE = 1, EXACT = 2 };  // DONE: answered (an empty subset, or a certified batched job)
+    std::vector<uint8_t> todo(nq, DONE);
+    for (uint32_t qi : plan.single) todo[qi] = SINGLE;
+    uint64_t n_batched = 0, n_exact = 0;
+
+    if (!plan.launches.empty()) {
+        const size_t k3_words = k3_stage_words(dim_);
+        VL_TRY(ensure_set(HipMem{}, {dev_buf(ws->k3_d_q64, k3_words), pinned_buf(ws->k3_h_q64, k3_words),
+                                     pinned_buf(ws->k3_h_result, K3_PIPE_QUERIES)}));
+    }
+    const bool prof = profile_.load();
+    std::vector<uint8_t> in_domain((size_t)K3_PIPE_QUERIES);
+    for (const SubsetLaunch& L : plan.launches) {
+        const uint32_t cnt = (uint32_t)L.jobs.size();
+        // the launch's pinned block: cnt queries, cnt norms, cnt job table entries -- one H2D copy
+        double* norms = ws->k3_h_q64 + (size_t)cnt * dim_;
+        SubsetJobDev* h_jobs = reinterpret_cast<SubsetJobDev*>(norms + cnt);
+        uint64_t bytes = 0;
+        for (uint32_t j = 0; j < cnt; ++j) {
+            const uint64_t qi = L.jobs[j];
+            const IdFilter* f = filter_at(qi);
+            in_domain[j] = stage_query(queries + qi * dim_, ws->k3_h_q64 + (size_t)j * dim_, dim_, &norms[j]) ? 1 : 0;
+            h_jobs[j].plist = f->d_plist;
+            h_jobs[j].m = (uint32_t)f->m;
+            h_jobs[j].k = (uint32_t)std::min<uint64_t>(k, f->m);
+            bytes += f->m * ((uint64_t)ld_ * sizeof(float) + sizeof(uint32_t) + (metric == COSINE ? sizeof(float) : 0));
+        }
+        VL_HIP(hipMemcpyAsync(ws->k3_d_q64, ws->k3_h_q64, ((size_t)cnt * dim_ + 3 * (size_t)cnt) * sizeof(double), hipMemcpyHostToDevice, st));
+        const double* d_norms = ws->k3_d_q64 + (size_t)cnt * dim_;
+        const SubsetJobDev* d_jobs = reinterpret_cast<const SubsetJobDev*>(d_norms + cnt);
+        ScanPlan sp;
+        if (prof) VL_HIP(hipEventRecord(ws->ev0, st));
+        VL_HIP(launch_scan_subset_jobs(st, metric, d_slab_, d_inv_norm_, d_jobs, cnt, L.gx, ws->k3_d_q64, (uint32_t)dim_, ld_,
+                                       ws->d_partials, &sp));
+        if (prof) VL_HIP(hipEventRecord(ws->ev1, st));
+        VL_HIP(launch_merge_finalize_jobs(st, metric, ws->d_partials, (int)L.gx, d_jobs, cnt, d_master_, ws->k3_d_q64, d_norms,
+                                          (uint32_t)dim_, max_row_norm_, ws->k3_h_result));
+        VL_HIP(hipStreamSynchronize(st));
+        note_scan(sp.variant, sp.grid, false);
+        if (prof) VL_TRY(account_profile(ws, bytes));
+        for (uint32_t j = 0; j < cnt; ++j) {
+            const uint64_t qi = L.jobs[j];
+            const uint64_t k_eff = h_jobs[j].k;
+            const SearchResultBlock& r = ws->k3_h_result[j];  // (a fallback below uses the workspace's other buffers, not these)
+            if (in_domain[j] && !(r.flags & RESULT_NEEDS_EXACT) && r.n_out == k_eff) {
+                VL_TRY(deliver("filtered batch fast path", ids_, &r, k_eff, nullptr, out_ids + qi * out_stride, out_scores + qi * out_stride));
+                out_n[qi] = k_eff;
+                ++n_batched;
+            } else {
+                todo[qi] = EXACT;
+                ++n_exact;
+            }
+        }
+        set_last_path(PATH_FAST);
+    }
+    last_fbatch_[0].store(n_batched, std::memory_order_relaxed);
+    last_fbatch_[1].store(plan.single.size(), std::memory_order_relaxed);
+    last_fbatch_[2].store(n_exact, std::memory_order_relaxed);
+    last_fbatch_[3].store(plan.launches.size(), std::memory_order_relaxed);
+
+    // what is left, in query order; the first failure ends the call (rows in front of it keep their answers)
+    for (uint64_t qi = 0; qi < nq; ++qi) {
+        if (todo[qi] == DONE) continue;
+        IdFilter* f = filter_at(qi);
+        const int rc = search_subset(ws, f, queries + qi * dim_, std::min<uint64_t>(k, f->m), metric, nullptr, out_ids + qi * out_stride,
+                                     out_scores + qi * out_stride, out_n + qi, nullptr, todo[qi] == EXACT);
+        if (rc != OK) {
+            for (uint64_t q = qi; q < nq; ++q) out_n[q] = 0;
+            return rc;
+        }
+    }
     return OK;
 }
 

@@ -121,7 +121,8 @@ struct Workspace {
     std::vector<float> q32;   // the f32 query handed to k_scan in its kernel arguments
     uint32_t seq = 0;         // stamp of the last single search issued from this workspace (h_result->seq)
     // f32 batch path (K3), several passes in flight: staging for K3_PIPE_QUERIES queries and their result blocks (lazy)
-    double* k3_d_q64 = nullptr;                // [K3_PIPE_QUERIES, dim] queries, then their norms
+    double* k3_d_q64 = nullptr;                // [K3_PIPE_QUERIES, dim] queries, then their norms, then (a filtered batch) the
+                                               // launch's SubsetJobDev table: k3_stage_words(dim) words
     double* k3_h_q64 = nullptr;                // pinned
     SearchResultBlock* k3_h_result = nullptr;  // pinned [K3_PIPE_QUERIES]
     // large-batch MFMA path (lazy)
@@ -138,6 +139,9 @@ struct Workspace {
 
     ~Workspace();
 };
+
+// words of the K3 staging buffers: per query its values and its norm, and the 16 bytes of a filtered batch's job table entry
+inline size_t k3_stage_words(uint64_t dim) { return (size_t)K3_PIPE_QUERIES * (dim + 3); }
 
 // Search scratch (streams, partial-list buffers, the batch filter's buffers: ~10 MB, 80+ MB once a large batch ran) is
 // shared by every handle of one (device, dimension): the reference keeps a HashMap of collections (src/client.rs:243-247),
@@ -258,6 +262,23 @@ public:
     int filter_positions(uint64_t token, std::shared_ptr<IdFilter>* keep, const uint32_t** d_plist, uint64_t* m) const;
     int search_filtered(uint64_t token, const double* query, uint64_t q_len, uint64_t k, int metric, uint64_t* out_pos,
                         uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;
+    // NEW: nq filtered searches against one index state, one filter for all of them (n_filters == 1) or one per query
+    // (n_filters == nq; tokens may repeat).  Row i of the [nq, out_stride] outputs is exactly search_filtered(tokens[i], queries
+    // + i * q_len, ..., k)'s answer; k <= out_stride.  The jobs that may take the fast path share launches of
+    // k_scan_subset_jobs (subset_batch_plan.hpp) and one finalize launch each; the rest, and what a launch could not certify,
+    // go through search_subset.  Returns the status of the lowest-numbered failing query; out_n is 0 from that query on.
+    int search_batch_filters(const uint64_t* tokens, uint64_t n_filters, const double* queries, uint64_t nq, uint64_t q_len,
+                             uint64_t k, int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores,
+                             uint64_t* out_n) const;
+    // the last search_batch_filters on this handle: jobs answered by a batched launch, jobs handed to the single filtered
+    // search before any launch, jobs a batched launch could not certify (redone on the exact kernels), batched scan launches
+    void last_filtered_batch(uint64_t* batched, uint64_t* single, uint64_t* exact, uint64_t* launches) const
+    {
+        if (batched) *batched = last_fbatch_[0].load(std::memory_order_relaxed);
+        if (single) *single = last_fbatch_[1].load(std::memory_order_relaxed);
+        if (exact) *exact = last_fbatch_[2].load(std::memory_order_relaxed);
+        if (launches) *launches = last_fbatch_[3].load(std::memory_order_relaxed);
+    }
     // NEW (no reference counterpart): every row whose score is >= min_score -- the longest prefix of FlatIndex::search(q, len,
     // metric) with score >= min_score, over the filter's rows when token != 0.  *out_total = rows that qualify, always;
     // min(total, out_capacity) entries are written (out_capacity = 0: count only, outputs may be null).
@@ -419,9 +440,10 @@ private:
                   std::vector<double>* scores, const uint32_t* plist = nullptr, const MmrReq* mmr = nullptr) const;
     int find_filter(uint64_t token, std::shared_ptr<IdFilter>* out) const;  // VL_ERR_INVALID_ARG with a message: no such token
     int resolve_filter(Workspace* ws, IdFilter* f) const;  // mu_ held (shared or unique), f->mu held
+    // exact_only: the fast path already failed to certify this (query, filter) in a batched launch: straight to the exact kernels
     int search_subset(Workspace* ws, IdFilter* f, const double* query, uint64_t k_eff, int metric, uint64_t* out_pos,
-                      uint64_t* out_ids, double* out_scores, uint64_t* out_n,
-                      const MmrReq* mmr = nullptr) const;  // mu_ held (shared), f resolved
+                      uint64_t* out_ids, double* out_scores, uint64_t* out_n, const MmrReq* mmr = nullptr,
+                      bool exact_only = false) const;  // mu_ held (shared), f resolved
     int search_range_locked(Workspace* ws, IdFilter* f, const double* query, double min_score, int metric, uint64_t out_capacity,
                             uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
                             uint64_t* out_total) const;  // mu_ held (shared), f resolved (nullptr: the whole index)
@@ -524,6 +546,7 @@ private:
     mutable std::atomic<int> last_scan_variant_{0}, last_scan_grid_{0}, last_scan_qarg_{0};
     mutable std::atomic<int> last_filter_[6] = {};
     mutable std::atomic<uint64_t> last_rbatch_[4] = {};
+    mutable std::atomic<uint64_t> last_fbatch_[4] = {};
     mutable std::mutex prof_mu_;
     mutable uint64_t prof_n_ = 0;
     mutable double prof_ms_ = 0.0;

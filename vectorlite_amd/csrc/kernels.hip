@@ -249,6 +249,34 @@ __global__ __launch_bounds__(256) void k_scan_subset_generic(const f32x4* __rest
     scan_stream_generic<METRIC, G>(slab, inv_norm, q64, dim, m, ld4, ListedRows{plist}, TopSink(out));
 }
 
+// K1 over MANY subsets in one launch: blockIdx.y is the job, jobs[job] names its list, its f64 query is row `job` of q64
+// (load_query's device form: the rounding of the kernel-argument form, so a row's key is k_scan_subset's bit for bit).
+// Every job has gridDim.x workgroups; scan_stream strides by gridDim.x and TopSink writes list blockIdx.x of the job's
+// gridDim.x lists, so the skeleton is k_scan_subset's.  A workgroup with no step for its job writes the empty list.
+template <int METRIC, int G, int VPL, int U>
+__global__ __launch_bounds__(256) void k_scan_subset_jobs(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
+                                                          const SubsetJobDev* __restrict__ jobs, const double* __restrict__ q64,
+                                                          uint32_t dim, Cand32* __restrict__ out)
+{
+    const SubsetJobDev job = jobs[blockIdx.y];
+    f32x4 qv[VPL];
+    load_query<G>(qv, q64 + (size_t)blockIdx.y * dim, dim);
+    scan_stream<G, U>(F32Rows<METRIC, VPL>{slab, inv_norm}, qv, ListedRows{job.plist}, job.m,
+                      TopSink(out + (size_t)blockIdx.y * gridDim.x * KP));
+}
+
+template <int METRIC, int G>
+__global__ __launch_bounds__(256) void k_scan_subset_jobs_generic(const f32x4* __restrict__ slab,
+                                                                  const float* __restrict__ inv_norm,
+                                                                  const SubsetJobDev* __restrict__ jobs,
+                                                                  const double* __restrict__ q64, uint32_t dim, uint32_t ld4,
+                                                                  Cand32* __restrict__ out)
+{
+    const SubsetJobDev job = jobs[blockIdx.y];
+    scan_stream_generic<METRIC, G>(slab, inv_norm, q64 + (size_t)blockIdx.y * dim, dim, job.m, ld4, ListedRows{job.plist},
+                                   TopSink(out + (size_t)blockIdx.y * gridDim.x * KP));
+}
+
 // Resolution of an id filter: which storage positions hold an id of the sorted, deduplicated set fids[0..nf).  Workgroup b
 // owns positions [b chunk, (b+1) chunk); pass 1 counts its matches, one workgroup turns the counts into offsets (and m), pass 2
 // writes the matching positions of each chunk in ascending order at its offset: the list comes out ascending.
@@ -964,6 +992,70 @@ __global__ __launch_bounds__(1024) void k_merge_finalize(const Cand32* __restric
         const bool valid = lane < n_cand;
         const double sc = valid ? A.score() : 0.0;
         rank_check_emit<METRIC>(sc, sh_pos[lane], sh_key[KP - 1], n_cand, k, n_rows, ld, R, Q, in_extra, out, seq, sink, blockIdx.x);
+    }
+}
+
+// K2 per job of a filtered batch (k_scan_subset_jobs' lists): k_merge_finalize, phase by phase, except that the rows the
+// bound check and the "a list of at most 64 rows must hold every row" rule refer to are the job's m and k is the job's
+// min(k, m), both read from the job table.  Its own kernel, not a flag or a shared body of k_merge_finalize: folding the
+// two changed the address arithmetic hipcc emits for k_merge_finalize's result block, and the kernels the unfiltered
+// paths launch stay as they are.
+template <int METRIC>
+__global__ __launch_bounds__(1024) void k_merge_finalize_jobs(const Cand32* __restrict__ partials, int n_lists,
+                                                              size_t list_stride_q, const double* __restrict__ master,
+                                                              const double* __restrict__ q64,
+                                                              const double* __restrict__ q_norms, uint32_t dim, uint32_t ld,
+                                                              const SubsetJobDev* __restrict__ jobs, double R,
+                                                              SearchResultBlock* __restrict__ out)
+{
+    // one workgroup per job of the launch
+    partials += (size_t)blockIdx.x * list_stride_q;
+    q64 += (size_t)blockIdx.x * dim;
+    out += blockIdx.x;
+    const double Q = q_norms[blockIdx.x];
+    const SubsetJobDev job = jobs[blockIdx.x];
+    constexpr int NW = 16;
+    __shared__ Cand32 sh_lists[NW * WAVE];
+    __shared__ RescoreLds<METRIC> rs;
+    __shared__ uint32_t sh_pos[KP];
+    __shared__ float sh_key[KP];
+    __shared__ int sh_ncand;
+
+    const int lane = lane_id();
+    const int wave = threadIdx.x >> 6;
+
+    // phase 1: n_lists <= 64 sorted lists: up to 16 waves x 4 bitonic folds, then a tree merge over the waves that hold one
+    TopList<float> L;
+    double q_first[1] = {0.0};
+    {
+        const int first = wave * 4;
+        int count = n_lists - first;
+        count = count < 0 ? 0 : (count > 4 ? 4 : count);
+        Cand32 e[4];
+        fold_lists4_load<Cand32>(e, partials, first, count);
+        if (threadIdx.x < RP_BW) q_first[0] = q64[threadIdx.x < dim ? threadIdx.x : dim - 1];  // behind the list loads
+        fold_lists4_merge<float, Cand32>(L, e, count);
+    }
+    block_merge_n<float, Cand32>(L, sh_lists, (n_lists + 3) / 4);
+    if (wave == 0) {
+        sh_pos[lane] = L.pos;
+        sh_key[lane] = L.key;
+        const unsigned long long real = __ballot(L.pos != POS_SENTINEL);
+        if (lane == 0) sh_ncand = __popcll(real);
+    }
+    __syncthreads();
+    const int n_cand = sh_ncand;
+
+    // phase 2: exact f64 rescoring of the candidates
+    Acc64<METRIC> A;
+    rescore_rows_par<METRIC, KP, 1024>(master, q64, dim, sh_pos, n_cand, rs, A, q_first);
+
+    // phase 3: rank by (score desc, pos asc), bound check against the job's rows, emit
+    if (wave == 0) {
+        const bool valid = lane < n_cand;
+        const double sc = valid ? A.score() : 0.0;
+        rank_check_emit<METRIC>(sc, sh_pos[lane], sh_key[KP - 1], n_cand, job.k, (uint64_t)job.m, ld, R, Q, 0.0, out, 0u,
+                                ShardRecordSink{}, blockIdx.x);
     }
 }
 
@@ -2284,6 +2376,101 @@ hipError_t launch_scan_subset(hipStream_t s, int metric, const float* slab, cons
         plan->variant = sh.special ? (SUBSET_VARIANT_BASE + sh.g * 10000 + sh.vpl * 100 + sh.u) : -(SUBSET_VARIANT_BASE + sh.g);
     }
     return rc;
+}
+
+namespace {
+// The jobs scan of a shape: fn(kernel, std::true_type) for the stride's default shape, fn(kernel, std::false_type) for the
+// generic kernel (which takes ld4 as well).
+template <int MM, class Fn>
+hipError_t with_subset_jobs_kernel(const ScanShape& sh, Fn&& fn)
+{
+    if (sh.special) {
+#define VL_TRY_VARIANT(G, VPL, U, BPC)                                                                                  \
+    if constexpr (is_default_scan_shape(G, VPL, U)) {                                                                   \
+        if (sh.g == G && sh.vpl == VPL && sh.u == U) return fn(k_scan_subset_jobs<MM, G, VPL, U>, std::true_type{});    \
+    }
+        VL_SCAN_VARIANTS(VL_TRY_VARIANT)
+#undef VL_TRY_VARIANT
+        return hipErrorInvalidValue;
+    }
+#define VL_SCAN_GEN(G) \
+    case G: return fn(k_scan_subset_jobs_generic<MM, G>, std::false_type{});
+    switch (sh.g) {
+        VL_SCAN_GEN(1)
+        VL_SCAN_GEN(2)
+        VL_SCAN_GEN(4)
+        VL_SCAN_GEN(8)
+        VL_SCAN_GEN(16)
+        VL_SCAN_GEN(32)
+        VL_SCAN_GEN(64)
+    default: return hipErrorInvalidValue;
+    }
+#undef VL_SCAN_GEN
+}
+}  // namespace
+
+hipError_t scan_subset_jobs_shape(int metric, uint32_t ld, int* g, int* u, int* resident)
+{
+    if ((ld & 3) || ld == 0) return hipErrorInvalidValue;
+    const ScanShape sh = default_scan_shape(ld / 4);
+    *g = sh.g;
+    *u = sh.u;
+    return dispatch_metric(metric, [&](auto M) -> hipError_t {
+        return with_subset_jobs_kernel<decltype(M)::value>(sh, [&](auto kern, auto) -> hipError_t {
+            // scan_grid's cap for this kernel
+            uint64_t cap = (uint64_t)env_int("VL_SCAN_GRID", 0);
+            if (cap == 0) {
+                int cus = 0;
+                const uint64_t res = (uint64_t)resident_blocks(reinterpret_cast<const void*>(kern), &cus);
+                cap = std::min<uint64_t>((uint64_t)sh.bpc * (uint64_t)cus, res);
+            }
+            *resident = (int)std::max<uint64_t>(1, std::min<uint64_t>(cap, (uint64_t)SCAN_MAX_GRID));
+            return hipSuccess;
+        });
+    });
+}
+
+hipError_t launch_scan_subset_jobs(hipStream_t s, int metric, const float* slab, const float* inv_norm, const SubsetJobDev* jobs,
+                                   uint32_t n_jobs, uint32_t gx, const double* q64, uint32_t dim, uint32_t ld, Cand32* partials,
+                                   ScanPlan* plan)
+{
+    if (n_jobs == 0 || n_jobs > (uint32_t)SCAN_BATCH_MAX_QUERIES || gx == 0 || (uint64_t)gx * n_jobs > PARTIALS32_LISTS ||
+        (ld & 3) || ld == 0 || !jobs || !q64)
+        return hipErrorInvalidValue;
+    const ScanShape sh = default_scan_shape(ld / 4);
+    const f32x4* slab4 = reinterpret_cast<const f32x4*>(slab);
+    const hipError_t rc = dispatch_metric(metric, [&](auto M) -> hipError_t {
+        return with_subset_jobs_kernel<decltype(M)::value>(sh, [&](auto kern, auto special) -> hipError_t {
+            if constexpr (decltype(special)::value)
+                hipLaunchKernelGGL(kern, dim3(gx, n_jobs), dim3(256), 0, s, slab4, inv_norm, jobs, q64, dim, partials);
+            else
+                hipLaunchKernelGGL(kern, dim3(gx, n_jobs), dim3(256), 0, s, slab4, inv_norm, jobs, q64, dim, ld / 4, partials);
+            return hipGetLastError();
+        });
+    });
+    if (plan) {
+        plan->grid = (int)gx;
+        plan->variant = sh.special ? (SUBSET_JOBS_VARIANT_BASE + sh.g * 10000 + sh.vpl * 100 + sh.u) : -(SUBSET_JOBS_VARIANT_BASE + sh.g);
+    }
+    return rc;
+}
+
+hipError_t launch_merge_finalize_jobs(hipStream_t s, int metric, Cand32* partials, int n_lists, const SubsetJobDev* jobs,
+                                      uint32_t n_jobs, const double* master, const double* q64, const double* q_norms,
+                                      uint32_t dim, double max_row_norm, SearchResultBlock* out)
+{
+    if (n_jobs == 0 || n_lists <= 0 || (n_jobs > (uint32_t)SCAN_BATCH_QB && n_lists > 64) ||
+        (uint64_t)n_lists * n_jobs > PARTIALS32_LISTS)
+        return hipErrorInvalidValue;
+    const uint32_t ld = (dim + 3u) & ~3u;
+    size_t stride = (size_t)n_lists * KP;
+    const Cand32* lists = reduce_lists<float, Cand32>(s, partials, &n_lists, &stride, (int)n_jobs, partials + PARTIALS32_LISTS * KP);
+    return dispatch_metric(metric, [&](auto M) -> hipError_t {
+        constexpr int MM = decltype(M)::value;
+        hipLaunchKernelGGL((k_merge_finalize_jobs<MM>), dim3(n_jobs), dim3(1024), 0, s, lists, n_lists, stride, master, q64,
+                           q_norms, dim, ld, jobs, max_row_norm, out);
+        return hipGetLastError();
+    });
 }
 
 int filter_grid_for(uint64_t n, uint32_t* chunk)

@@ -163,6 +163,29 @@ bool scan_subset_takes_qarg(uint32_t ld);
 hipError_t launch_scan_subset(hipStream_t s, int metric, const float* slab, const float* inv_norm, const uint32_t* plist,
                               uint64_t m, const double* q64, uint32_t dim, uint32_t ld, Cand32* partials, ScanPlan* plan,
                               const float* q32_host = nullptr);
+// Many (query, subset) jobs in one launch (batches).  A job is one row of a device table; its f64
+// query is row `job` of q64 [n_jobs, dim].  The grid is (gx, n_jobs): every job writes gx lists (job-major) with
+// k_scan_subset's keys and positions.  gx and the launch's membership are subset_batch_plan.hpp's; gx * n_jobs <=
+// PARTIALS32_LISTS, n_jobs <= SCAN_BATCH_MAX_QUERIES, every m > 0.  No allocation, no synchronisation.
+// plan->variant = SUBSET_JOBS_VARIANT_BASE + G * 10000 + VPL * 100 + U, or -(SUBSET_JOBS_VARIANT_BASE + G) for the generic kernel.
+struct SubsetJobDev {
+    const uint32_t* plist;  // ascending storage positions of the job's filter
+    uint32_t m;             // their number, > 0
+    uint32_t k;             // min(k, m)
+};
+constexpr int SUBSET_JOBS_VARIANT_BASE = 6000000;
+hipError_t launch_scan_subset_jobs(hipStream_t s, int metric, const float* slab, const float* inv_norm, const SubsetJobDev* jobs,
+                                   uint32_t n_jobs, uint32_t gx, const double* q64, uint32_t dim, uint32_t ld, Cand32* partials,
+                                   ScanPlan* plan);
+// launch_merge_finalize for those lists: n_rows and k of each query are its job's m and k.  More than SCAN_BATCH_QB jobs:
+// n_lists <= 64 (the merge scratch behind the lists holds SCAN_BATCH_QB queries).
+hipError_t launch_merge_finalize_jobs(hipStream_t s, int metric, Cand32* partials, int n_lists, const SubsetJobDev* jobs,
+                                      uint32_t n_jobs, const double* master, const double* q64, const double* q_norms,
+                                      uint32_t dim, double max_row_norm, SearchResultBlock* out);
+// What the plan needs to know about the scan: lanes per row and row groups in flight of the stride's shape (the default
+// one, or the generic kernel's), and the workgroups of that kernel resident at once (what launch_scan_subset's grid is
+// capped at).
+hipError_t scan_subset_jobs_shape(int metric, uint32_t ld, int* g, int* u, int* resident);
 // Exact path over the subset: scores[i] = reference f64 score of row plist[i].
 hipError_t launch_exact_scan_subset(hipStream_t s, int metric, const double* master, const double* q64, const uint32_t* plist,
                                     uint64_t m, uint32_t dim, double* scores, uint32_t* nan_flag);
