@@ -153,6 +153,26 @@ int vl_index_add_embeddings_f32(vl_index *h, const uint64_t *ids, const float *e
  * the id is absent (src/index/flat.rs:93-96). */
 int vl_index_delete(vl_index *h, uint64_t id);
 
+/* NEW capability: n deletes in one call.  The index is left in exactly the state `for (i < n_ids) vl_index_delete(h, ids[i])`
+ * leaves it in -- length, row order, exported ids and f64 bits, every later search, filter, group table and clone -- but the
+ * flat index finds the rows with one walk over its ids and compacts each device array in one pass (a row-move kernel over
+ * the plan of DESIGN.md section 22), however many ids go, where n single deletes move the rows behind each id in turn.
+ * Flat (also over several GPUs): absent ids are Ok, a repeated id is a no-op the second time, every row an id has goes;
+ * always VL_OK short of a device error; *out_removed (may be null) = rows removed.  HNSW: the loop of tombstones under one
+ * lock; stops at the first id that does not exist with VL_ERR_NOT_FOUND ("Vector ID {id} does not exist"), the ids before
+ * it stay deleted (vl_index_add_bulk's prefix rule); *out_removed = nodes tombstoned. */
+int vl_index_delete_bulk(vl_index *h, const uint64_t *ids, uint64_t n_ids, uint64_t *out_removed);
+
+/* Bytes of the buffer a flat index's deletes compact through (it holds what a launch cannot move in place); 0 = the default
+ * of 64 MB; never less than one row.  An existing smaller buffer is freed.  Diagnostic: small values make small indexes
+ * exercise every kind of segment of the bulk delete's plan.  No effect on HNSW handles. */
+int vl_index_set_delete_bounce(vl_index *h, uint64_t bytes);
+
+/* Diagnostic (single-GPU flat handles): the last vl_index_delete_bulk (all zero if it removed nothing).  out6 = rows removed, rows moved
+ * (those behind the first hole that stayed), launches that moved a segment in place, segments that went through the
+ * bounce buffer, bytes written to device memory, microseconds from the first launch to the end of the synchronisation. */
+int vl_index_last_delete(const vl_index *h, uint64_t *out6);
+
 /* search(query, k, metric) (src/index/flat.rs:98-119): writes min(k, len) results, best first,
  * ties in insertion order.  out_ids/out_scores must hold min(k, len) entries; a caller that sized its
  * buffers from an earlier vl_index_len() passes k = min(k, capacity) -- results for a smaller k are a prefix

@@ -59,6 +59,8 @@ int main(void)
     CHECK(vl_index_delete(idx, 2));
     CHECK(vl_index_delete(idx, 2)); /* absent id: still Ok for the flat index (src/index/flat.rs:93-96) */
     if (vl_index_len(idx) != 2) return 1;
+    CHECK(vl_index_delete_bulk(idx, (const uint64_t[]){3, 3, 99}, 3, &n)); /* n deletes in one pass: a repeat and an absent id are no-ops */
+    if (n != 1 || vl_index_len(idx) != 1) return 1;
 
     /* the same index over two GPUs of the node in this one process (here: the same card twice), rows sharded:
      * identical answers, no rank processes, no id handshake */

@@ -39,6 +39,9 @@ extern "C" {
     fn vl_index_add_bulk(h: *mut vl_index, ids: *const u64, values: *const f64, n: u64, validate: c_int, values_on_device: c_int) -> c_int;
     fn vl_index_add_embeddings_f32(h: *mut vl_index, ids: *const u64, embeddings: *const f32, n: u64, normalize: c_int, validate: c_int, embeddings_on_device: c_int) -> c_int;
     fn vl_index_delete(h: *mut vl_index, id: u64) -> c_int;
+    fn vl_index_delete_bulk(h: *mut vl_index, ids: *const u64, n_ids: u64, out_removed: *mut u64) -> c_int;
+    fn vl_index_set_delete_bounce(h: *mut vl_index, bytes: u64) -> c_int;
+    fn vl_index_last_delete(h: *const vl_index, out6: *mut u64) -> c_int;
     fn vl_index_search(h: *const vl_index, query: *const f64, q_len: u64, k: u64, metric: c_int, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_cap(h: *const vl_index, query: *const f64, q_len: u64, k: u64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_batch_cap(h: *const vl_index, queries: *const f64, nq: u64, q_len: u64, k: u64, metric: c_int, out_stride: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
@@ -268,6 +271,35 @@ impl GpuFlatIndex {
         }
         // coalescing is on by default, one queue per replica
         GpuFlatIndex(Handle { raw, dim, side })
+    }
+}
+
+impl GpuFlatIndex {
+    /// `for id in ids { self.delete(*id) }` in one call (`vl_index_delete_bulk`): the rows are found with one walk over the
+    /// index's ids and each device array is compacted in one pass, however many ids go.  Absent and repeated ids are
+    /// no-ops, as `retain` makes them (src/index/flat.rs:93-96).  Returns the rows removed.
+    pub fn delete_many(&mut self, ids: &[u64]) -> Result<u64, String> {
+        let mut removed = 0u64;
+        match unsafe { vl_index_delete_bulk(self.0.raw, ids.as_ptr(), ids.len() as u64, &mut removed) } {
+            VL_OK => {
+                for id in ids {
+                    self.0.side.remove(id);
+                }
+                Ok(removed)
+            }
+            _ => Err(last_error()),
+        }
+    }
+    /// The last `delete_many`: rows removed, rows moved, launches that moved a segment in place, segments that went
+    /// through the bounce buffer, bytes written to device memory, microseconds on the device (`vl_index_last_delete`).
+    pub fn last_delete(&self) -> [u64; 6] {
+        let mut out = [0u64; 6];
+        unsafe { vl_index_last_delete(self.0.raw, out.as_mut_ptr()) };
+        out
+    }
+    /// Bytes of the buffer deletes compact through; 0 = the default 64 MB (`vl_index_set_delete_bounce`, a diagnostic knob).
+    pub fn set_delete_bounce(&mut self, bytes: u64) {
+        unsafe { vl_index_set_delete_bounce(self.0.raw, bytes) };
     }
 }
 
@@ -756,6 +788,20 @@ impl GpuHnswIndex {
     }
     pub fn metric(&self) -> SimilarityMetric {
         self.metric
+    }
+    /// `for id in ids { self.delete(*id)? }` under one lock (`vl_index_delete_bulk`): stops at the first id that does not
+    /// exist with the reference's error (src/index/hnsw.rs:401-403); the ids before it stay deleted.  Ok: nodes tombstoned.
+    pub fn delete_many(&mut self, ids: &[u64]) -> Result<u64, String> {
+        let mut removed = 0u64;
+        let rc = unsafe { vl_index_delete_bulk(self.h.raw, ids.as_ptr(), ids.len() as u64, &mut removed) };
+        for id in &ids[..removed as usize] {
+            self.h.side.remove(id);
+        }
+        match rc {
+            VL_OK => Ok(removed),
+            VL_ERR_NOT_FOUND => Err(format!("Vector ID {} does not exist", ids[removed as usize])),
+            _ => Err(last_error()),
+        }
     }
     /// Opt-in: walks navigate by the reference's own u64 distances with ties in first-seen order
     /// (`VL_HNSW_NAV_REFERENCE`); `false` returns to the default f32 navigation.  A clone starts in the default.

@@ -514,6 +514,28 @@ class FlatIndex:
         _raise(self._L.vl_index_delete(self._h, int(id)))
         self._meta.pop(int(id), None)
 
+    def delete_many(self, ids) -> int:
+        """`for id in ids: delete(id)` in one call (vl_index_delete_bulk): one walk over the ids and one compaction pass
+        over the device arrays, however many ids go.  Absent and repeated ids are ignored.  Returns the rows removed."""
+        arr = _u64_array(ids)
+        removed = C.c_uint64(0)
+        _raise(self._L.vl_index_delete_bulk(self._h, _pu64(arr), arr.size, C.byref(removed)))
+        if self._meta:
+            for i in arr.tolist():
+                self._meta.pop(i, None)
+        return int(removed.value)
+
+    def set_delete_bounce(self, nbytes: int) -> None:
+        """Bytes of the buffer deletes compact through (0: the default 64 MB); a diagnostic knob (vl_index_set_delete_bounce)."""
+        _raise(self._L.vl_index_set_delete_bounce(self._h, int(nbytes)))
+
+    def last_delete(self) -> Dict[str, int]:
+        """The last delete_many on this (single-GPU) handle: rows removed and moved, launches that moved a segment in
+        place, segments that went through the bounce buffer, bytes written, microseconds on the device."""
+        out = (C.c_uint64 * 6)()
+        _raise(self._L.vl_index_last_delete(self._h, out))
+        return dict(zip(("removed", "moved", "direct_launches", "bounced_segments", "bytes_written", "micros"), (int(v) for v in out)))
+
     def search(self, query, k: int, similarity_metric: int = SimilarityMetric.Cosine, filter=None) -> List[SearchResult]:
         """`filter`: None, an IdFilter of this index, or an iterable of ids (a one-shot filter): the top k among the rows
         whose id is in the set."""
@@ -1309,6 +1331,19 @@ class HNSWIndex:
             raise IndexOpError(_last_error())  # "Vector ID {id} does not exist" (:401-403)
         _raise(rc)
         self._meta.pop(int(id), None)
+
+    def delete_many(self, ids) -> int:
+        """`for id in ids: delete(id)` under one lock (vl_index_delete_bulk): stops at the first id that does not exist and
+        raises its error; the ids before it stay deleted.  Returns the nodes tombstoned."""
+        arr = _u64_array(ids)
+        removed = C.c_uint64(0)
+        rc = self._L.vl_index_delete_bulk(self._h, _pu64(arr), arr.size, C.byref(removed))
+        for i in arr[: int(removed.value)].tolist():
+            self._meta.pop(i, None)
+        if rc == VL_ERR_NOT_FOUND:
+            raise IndexOpError(_last_error())  # "Vector ID {id} does not exist" (:401-403)
+        _raise(rc)
+        return int(removed.value)
 
     def _raise_search(self, rc: int, requested: int):
         if rc == VL_ERR_METRIC_MISMATCH:

@@ -99,6 +99,16 @@ class Collection:
                 raise VectorNotFound(f"Vector ID {id} not found") from e
             raise VectorLiteError(str(e)) from e
 
+    def delete_many(self, ids) -> int:
+        """`for id in ids: delete(id)` in one index call (a document's chunks, a tombstone list); returns the rows removed.
+        An HNSW collection stops at the first id it does not hold, as the loop would."""
+        try:
+            return self.index.delete_many(ids)
+        except IndexOpError as e:
+            if "does not exist" in str(e):
+                raise VectorNotFound(str(e).replace("does not exist", "not found")) from e
+            raise VectorLiteError(str(e)) from e
+
     def search_text(self, query_text: str, k: int, similarity_metric: SimilarityMetric, embedding_function,
                     where: Optional[Callable[[Any], bool]] = None) -> List[SearchResult]:
         """`where`: a predicate on a row's metadata; only rows for which it holds are ranked (an exact filtered search

@@ -281,6 +281,33 @@ int vl_index_delete(vl_index* h, uint64_t id)
     });
 }
 
+int vl_index_delete_bulk(vl_index* h, const uint64_t* ids, uint64_t n_ids, uint64_t* out_removed)
+{
+    return guarded([&]() -> int {
+        if (out_removed) *out_removed = 0;
+        if (!h || (!ids && n_ids)) return VL_ERR_INVALID_ARG;
+        if (h->hnsw) return h->hnsw->remove_bulk(ids, n_ids, out_removed);
+        if (h->multi) return h->multi->remove_bulk(ids, n_ids, out_removed);
+        return h->flat->remove_bulk(ids, n_ids, nullptr, out_removed);
+    });
+}
+
+int vl_index_set_delete_bounce(vl_index* h, uint64_t bytes)
+{
+    return guarded([&]() -> int {
+        if (!h) return VL_ERR_INVALID_ARG;
+        if (h->hnsw) return VL_OK;  // tombstones move nothing
+        return on_flat(h, [&](auto* f) { return f->set_delete_bounce(bytes); });
+    });
+}
+
+int vl_index_last_delete(const vl_index* h, uint64_t* out6)
+{
+    if (!h || !h->flat || !out6) return VL_ERR_INVALID_ARG;
+    h->flat->last_delete(out6);
+    return VL_OK;
+}
+
 int vl_index_search(const vl_index* h, const double* query, uint64_t q_len, uint64_t k, int metric,
                     uint64_t* out_ids, double* out_scores, uint64_t* out_n)
 {

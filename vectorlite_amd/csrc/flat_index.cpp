@@ -6,6 +6,7 @@
 // positions back to ids for the k winners (the reference re-attaches text/metadata the same way,
 // src/index/flat.rs:106-114).  There is no CPU compute fallback.
 #include "flat_index.hpp"
+#include "delete_plan.hpp"
 #include "lazy_buffers.hpp"
 #include "shard.hpp"
 #include "score_bound.hpp"
@@ -740,6 +741,163 @@ int GpuFlatIndex::remove_report(uint64_t id, std::vector<uint64_t>* removed_posi
         }
     }
     return OK;  // absent id is Ok(()) (src/index/flat.rs:93-96)
+}
+
+int GpuFlatIndex::set_delete_bounce(uint64_t bytes)
+{
+    std::unique_lock<RwLock> lk(mu_);
+    const size_t widest = std::max<size_t>({dim_ * sizeof(double), ld_ * sizeof(float), 1});
+    bounce_want_ = bytes ? std::max<size_t>((size_t)bytes, widest) : 0;
+    const size_t want = bounce_want_ ? bounce_want_ : BOUNCE_BYTES;
+    if (d_bounce_ && bounce_bytes_ < want) {  // allocated again, large enough, by the next delete
+        VL_HIP(hipSetDevice(device_));
+        (void)hipFree(d_bounce_);
+        d_bounce_ = nullptr;
+        bounce_bytes_ = 0;
+    }
+    return OK;
+}
+
+// n deletes at once: Vec::retain (src/index/flat.rs:93-96) applied n times is one order-preserving compaction.  One walk over
+// ids_ finds the rows, delete_plan.hpp cuts each device array's moved part into segments, k_move_rows moves them; the host
+// bookkeeping follows once the device work is known to have completed.
+int GpuFlatIndex::remove_bulk(const uint64_t* ids, uint64_t n, std::vector<uint64_t>* removed_positions, uint64_t* out_rows)
+{
+    if (out_rows) *out_rows = 0;
+    if (removed_positions) removed_positions->clear();
+    if (n && !ids) return ERR_INVALID_ARG;
+    std::unique_lock<RwLock> lk(mu_);
+    for (auto& v : last_delete_) v.store(0, std::memory_order_relaxed);  // a call that removes nothing reads as all zero
+    if (n == 0) return OK;
+    VL_HIP(hipSetDevice(device_));
+
+    const uint64_t rows_before = ids_.size();
+    if (rows_before >= 0xFFFFFFF0ull) {  // the plan's keys and the kernel's row numbers are u32 (ensure_capacity's limit)
+        set_last_error("row count exceeds the u32 position space");
+        return ERR_INVALID_ARG;
+    }
+    std::vector<uint64_t> gone;  // ascending
+    {
+        // The listed ids as an open-addressing table (a power of two of slots, at most half full, linear probing; the id
+        // ~0 is the empty slot's mark and is remembered beside it), behind a bitmap of the same hash's top bits -- 8 bits
+        // per listed id at least -- that answers for most of the rows that stay without a probe of the table.
+        constexpr uint64_t EMPTY = ~0ull;
+        int log2_slots = 4, log2_bits = 10;
+        while ((1ull << log2_slots) < 2 * n) ++log2_slots;
+        while (log2_bits < 30 && (1ull << log2_bits) < 8 * n) ++log2_bits;
+        std::vector<uint64_t> table((size_t)1 << log2_slots, EMPTY), maybe((size_t)1 << (log2_bits - 6), 0);
+        const uint64_t mask = table.size() - 1;
+        bool want_empty_mark = false;
+        const auto hash = [](uint64_t id) { return id * 0x9E3779B97F4A7C15ull; };
+        for (uint64_t i = 0; i < n; ++i) {
+            if (ids[i] == EMPTY) {
+                want_empty_mark = true;
+                continue;
+            }
+            const uint64_t h = hash(ids[i]), b = h >> (64 - log2_bits);
+            maybe[b >> 6] |= 1ull << (b & 63);
+            uint64_t s = h >> (64 - log2_slots);
+            while (table[s] != EMPTY && table[s] != ids[i]) s = (s + 1) & mask;
+            table[s] = ids[i];
+        }
+        for (uint64_t p = 0; p < rows_before; ++p) {
+            const uint64_t id = ids_[p];
+            if (id == EMPTY) {
+                if (want_empty_mark) gone.push_back(p);
+                continue;
+            }
+            const uint64_t h = hash(id), b = h >> (64 - log2_bits);
+            if (!((maybe[b >> 6] >> (b & 63)) & 1)) continue;
+            uint64_t s = h >> (64 - log2_slots);
+            while (table[s] != EMPTY && table[s] != id) s = (s + 1) & mask;
+            if (table[s] == id) gone.push_back(p);
+        }
+    }
+    const uint64_t m = gone.size();
+    if (m == 0) return OK;  // absent ids are Ok(()), and nothing changed
+    const uint64_t rows_after = rows_before - m, first = gone[0];
+
+    uint64_t launches = 0, bounced = 0, bytes_written = 0, micros = 0;
+    if (first < rows_after) {  // rows behind a hole survive: they move up
+        const size_t want_bytes = bounce_want_ ? bounce_want_ : BOUNCE_BYTES;
+        if (d_bounce_ && bounce_bytes_ < want_bytes) {
+            (void)hipFree(d_bounce_);
+            d_bounce_ = nullptr;
+            bounce_bytes_ = 0;
+        }
+        if (!d_bounce_) {
+            VL_HIP(hipMalloc(&d_bounce_, want_bytes));
+            bounce_bytes_ = want_bytes;
+        }
+        const std::vector<uint32_t> keys = delete_keys(gone);
+        struct DevKeys {  // the removed list on the device for the length of this call
+            uint32_t* p = nullptr;
+            ~DevKeys()
+            {
+                if (p) (void)hipFree(p);
+            }
+        } d_keys;
+        VL_TRY(dev_alloc(&d_keys.p, keys.size()));
+        VL_HIP(hipMemcpyAsync(d_keys.p, keys.data(), keys.size() * sizeof(uint32_t), hipMemcpyHostToDevice, mut_stream_));
+        struct Buf {
+            char* base;
+            size_t row_bytes;
+        } bufs[] = {{reinterpret_cast<char*>(d_master_), dim_ * sizeof(double)},
+                    {reinterpret_cast<char*>(d_slab_), ld_ * sizeof(float)},
+                    {reinterpret_cast<char*>(d_inv_norm_), sizeof(float)},
+                    {reinterpret_cast<char*>(d_flags_), 1}};
+        const auto t0 = std::chrono::steady_clock::now();
+        for (const Buf& b : bufs) {
+            if (b.row_bytes == 0) continue;
+            for (const DeleteSegment& sg : delete_plan(rows_before, keys, want_bytes / b.row_bytes)) {
+                const uint64_t cnt = sg.dst_end - sg.dst_begin;
+                char* place = b.base + sg.dst_begin * b.row_bytes;
+                VL_HIP(launch_move_rows(mut_stream_, b.base, sg.direct ? place : static_cast<char*>(d_bounce_), b.row_bytes, d_keys.p,
+                                        (uint32_t)sg.shift_begin, (uint32_t)sg.shift_end, sg.dst_begin, cnt));
+                if (sg.direct) {
+                    ++launches;
+                } else {
+                    VL_HIP(hipMemcpyAsync(place, d_bounce_, cnt * b.row_bytes, hipMemcpyDeviceToDevice, mut_stream_));
+                    ++bounced;
+                }
+                bytes_written += cnt * b.row_bytes * (sg.direct ? 1 : 2);
+            }
+        }
+        VL_HIP(hipStreamSynchronize(mut_stream_));
+        micros = (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    }
+
+    // the device arrays are compacted: now the host's
+    {
+        // the runs of kept rows between the holes move up as blocks
+        uint64_t w = first;
+        for (size_t gi = 0; gi < gone.size(); ++gi) {
+            const uint64_t p = gone[gi];
+            if (row_flags_[p] & ROW_OUT_OF_DOMAIN) --n_out_of_domain_;
+            if (id_counts_valid_) {
+                auto it = id_counts_.find(ids_[p]);
+                if (it != id_counts_.end() && it->second > 0) --it->second;
+            }
+            const uint64_t run_end = gi + 1 < gone.size() ? gone[gi + 1] : rows_before, run = run_end - (p + 1);
+            if (run) {
+                std::memmove(&ids_[w], &ids_[p + 1], run * sizeof(uint64_t));
+                std::memmove(&row_flags_[w], &row_flags_[p + 1], run);
+                w += run;
+            }
+        }
+        ids_.resize(rows_after);
+        row_flags_.resize(rows_after);
+    }
+    if (slab16_rows_ > first) slab16_rows_ = first;  // rows behind the first hole are re-converted on demand
+    if (slab16f_rows_ > first) slab16f_rows_ = first;
+    if (slab8_rows_ > first) slab8_rows_ = first;
+    if (d_ids_rows_ > first) d_ids_rows_ = first;
+    ++mutations_;
+    const uint64_t st[6] = {m, rows_after - first, launches, bounced, bytes_written, micros};
+    for (int i = 0; i < 6; ++i) last_delete_[i].store(st[i], std::memory_order_relaxed);
+    if (out_rows) *out_rows = m;
+    if (removed_positions) *removed_positions = std::move(gone);
+    return OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -229,6 +229,20 @@ public:
     int remove(uint64_t id);  // `delete`
     // the same, reporting which storage positions went (descending) -- a sharded handle keeps a per-row table beside this index
     int remove_report(uint64_t id, std::vector<uint64_t>* removed_positions);
+    // NEW (no reference counterpart): the state `for id in ids: delete(id)` leaves -- every row whose id is in the list goes,
+    // the others keep their order -- reached with one walk over the ids and one pass over each device array (delete_plan.hpp,
+    // k_move_rows), whatever n is.  Absent and repeated ids are no-ops.  removed_positions (may be null) receives the
+    // positions that went, ascending; *out_rows their number.  DESIGN.md section 22.
+    int remove_bulk(const uint64_t* ids, uint64_t n, std::vector<uint64_t>* removed_positions, uint64_t* out_rows);
+    // bytes of the delete compaction buffer from now on (0: the default 64 MB; at least one row of the widest array); a
+    // smaller buffer that exists is freed.  Small values make small indexes cross the plan's segment boundaries (tests).
+    int set_delete_bounce(uint64_t bytes);
+    // the last remove_bulk on this handle: rows removed, rows moved, direct launches, bounced segments, bytes written to
+    // device memory, microseconds from the first launch to the end of the synchronisation
+    void last_delete(uint64_t out[6]) const
+    {
+        for (int i = 0; i < 6; ++i) out[i] = last_delete_[i].load(std::memory_order_relaxed);
+    }
     bool contains(uint64_t id) const;                       // O(1) after the first call (the duplicate-id table)
     int find_first(uint64_t id, uint64_t* out_pos) const;   // first row with that id (get_vector's rule); ERR_NOT_FOUND
     int get_row_at(uint64_t pos, double* out) const;
@@ -500,6 +514,7 @@ private:
     hipStream_t mut_stream_ = nullptr;
     void* d_bounce_ = nullptr;  // delete compaction buffer
     size_t bounce_bytes_ = 0;
+    size_t bounce_want_ = 0;    // set_delete_bounce: what remove_bulk plans with and allocates (0: BOUNCE_BYTES)
 
     // host bookkeeping
     std::vector<uint64_t> ids_;        // position -> id (insertion order)
@@ -547,6 +562,7 @@ private:
     mutable std::atomic<int> last_filter_[6] = {};
     mutable std::atomic<uint64_t> last_rbatch_[4] = {};
     mutable std::atomic<uint64_t> last_fbatch_[4] = {};
+    std::atomic<uint64_t> last_delete_[6] = {};
     mutable std::mutex prof_mu_;
     mutable uint64_t prof_n_ = 0;
     mutable double prof_ms_ = 0.0;

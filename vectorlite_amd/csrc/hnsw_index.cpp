@@ -10,6 +10,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <unordered_set>
 
 #include "hnsw_filter_plan.hpp"
 #include "hnsw_import_plan.hpp"
@@ -491,6 +492,43 @@ int HnswIndex::remove(uint64_t id)
     live_[it->second] = 0;
     id_to_node_.erase(it);
     --live_count_;
+    return OK;
+}
+
+int HnswIndex::remove_bulk(const uint64_t* ids, uint64_t n, uint64_t* out_nodes)
+{
+    if (out_nodes) *out_nodes = 0;
+    if (n == 0) return OK;
+    if (!ids) return ERR_INVALID_ARG;
+    std::unique_lock<RwLock> lk(mu_);
+    ++mutations_;  // walk filters build their pass bitmaps again
+    // the prefix the loop of remove() would get through: an id that is absent, or was named earlier in the list, ends it
+    std::vector<uint32_t> nodes;
+    std::unordered_set<uint64_t> seen;
+    uint64_t n_take = n;
+    for (uint64_t i = 0; i < n; ++i) {
+        auto it = id_to_node_.find(ids[i]);
+        if (it == id_to_node_.end() || !seen.insert(ids[i]).second) {
+            n_take = i;
+            break;
+        }
+        nodes.push_back(it->second);
+    }
+    if (!nodes.empty()) {  // tombstones: host state follows the device's
+        VL_HIP(hipSetDevice(device_));
+        for (uint32_t node : nodes) VL_HIP(hipMemsetAsync(d_live_ + node, 0, 1, stream_));
+        VL_HIP(hipStreamSynchronize(stream_));
+        for (uint64_t i = 0; i < n_take; ++i) {
+            live_[nodes[i]] = 0;
+            id_to_node_.erase(ids[i]);
+        }
+        live_count_ -= n_take;
+    }
+    if (out_nodes) *out_nodes = n_take;
+    if (n_take < n) {  // :401-403
+        set_last_error("Vector ID " + std::to_string(ids[n_take]) + " does not exist");
+        return ERR_NOT_FOUND;
+    }
     return OK;
 }
 

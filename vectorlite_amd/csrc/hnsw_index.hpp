@@ -98,6 +98,9 @@ public:
     int add(uint64_t id, const double* values, uint64_t len);
     int add_bulk(const uint64_t* ids, const double* values, uint64_t n, bool values_on_device);
     int remove(uint64_t id);
+    // n remove() calls under one lock: stops at the first id that does not exist (ERR_NOT_FOUND, the reference's message),
+    // the ids before it stay tombstoned -- add_bulk's prefix rule.  *out_nodes = nodes tombstoned.
+    int remove_bulk(const uint64_t* ids, uint64_t n, uint64_t* out_nodes);
     // ef == 0: the reference's rule ef = min(k, len) (src/index/hnsw.rs:437,454); ef > 0: own extension
     // out_stride (0 = k): the caller's buffers hold out_stride entries per query -- rows are out_stride apart and at most
     // out_stride results are written per row, while the WALK still runs with the caller's k (ef = min(k, len)): the

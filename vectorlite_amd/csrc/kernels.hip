@@ -1878,6 +1878,81 @@ __global__ __launch_bounds__(256) void k_embed_f32_rows(const float* __restrict_
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Bulk delete (delete_plan.hpp): one launch moves the kept rows of one segment of destination rows up to their place in
+// one device array, or gathers them into the bounce buffer.  A pure copy in units of V bytes (16 where the row pitch
+// allows, 8 for f64 rows of odd dimension, 4 and 1 for the two per-row arrays): nothing is converted, a slab row's
+// padding columns travel with it.
+// Destination row d reads source row d + shift(d), shift(d) = #{i : keys[i] <= d} with keys[i] = r_i - i over the
+// ascending removed positions; the segment's shifts lie in [c_lo, c_hi], so only keys[c_lo, c_hi) is searched.  A wave
+// takes MOVE_U groups of rows per trip (a group = the rows 64 lanes cover at lpr lanes per row) and first searches for
+// the trip's first and last row with wave-uniform (scalar) loads: holes are rare against rows, the two shifts are mostly
+// equal and are then every lane's; otherwise each lane searches the few keys between them.  All loads of a trip's
+// column step are issued before its stores (MOVE_U in flight per lane).
+// src_base and dst may be the same array (a direct segment): the plan guarantees that the launch's destinations end
+// before its sources begin, so no __restrict__ on them and nothing else is needed.
+// ---------------------------------------------------------------------------------------------
+constexpr int MOVE_U = 4;
+
+template <int V> struct MoveUnit;
+template <> struct MoveUnit<16> { typedef uint32_t type __attribute__((ext_vector_type(4))); };
+template <> struct MoveUnit<8> { typedef uint32_t type __attribute__((ext_vector_type(2))); };
+template <> struct MoveUnit<4> { using type = uint32_t; };
+template <> struct MoveUnit<1> { using type = uint8_t; };
+
+// lo + #{i in [lo, hi) : keys[i] <= d}
+__device__ __forceinline__ uint32_t move_shift(const uint32_t* __restrict__ keys, uint32_t lo, uint32_t hi, uint32_t d)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] <= d) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void k_move_rows(const char* src_base, char* dst, const uint32_t* __restrict__ keys,
+                                                   uint32_t c_lo, uint32_t c_hi, uint32_t dst_begin, uint32_t rows,
+                                                   uint32_t upr, uint32_t lpr_log2)
+{
+    using T = typename MoveUnit<V>::type;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint32_t lpr = 1u << lpr_log2, rpg = (uint32_t)WAVE >> lpr_log2;  // lanes per row, rows per group
+    const uint32_t sub = lane >> lpr_log2, col0 = lane & (lpr - 1);
+    const size_t pitch = (size_t)upr * V;
+    const uint64_t n_groups = ((uint64_t)rows + rpg - 1) >> (6 - lpr_log2);
+    const uint64_t wave = (uint64_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    const uint64_t step = (uint64_t)gridDim.x * 4 * MOVE_U;
+    for (uint64_t g0 = wave * MOVE_U; g0 < n_groups; g0 += step) {
+        const uint64_t r_first = g0 * rpg;
+        const uint64_t r_end = (g0 + MOVE_U) * rpg;
+        const uint32_t r_last = (uint32_t)(r_end < rows ? r_end : rows) - 1;
+        const uint32_t cf = move_shift(keys, c_lo, c_hi, dst_begin + (uint32_t)r_first);
+        const uint32_t cl = move_shift(keys, cf, c_hi, dst_begin + r_last);
+        const T* sp[MOVE_U];
+        T* dp[MOVE_U];
+#pragma unroll
+        for (int j = 0; j < MOVE_U; ++j) {
+            // past the segment's end: the lane moves the last row once more (the same bytes to the same place, and that
+            // place is no source of this launch), which keeps every load and store of the trip unpredicated
+            const uint64_t r_lane = (g0 + j) * rpg + sub;
+            const uint64_t r = r_lane < rows ? r_lane : r_last;
+            const uint32_t d = dst_begin + (uint32_t)r;
+            const uint32_t c = cf == cl ? cf : move_shift(keys, cf, cl, d);
+            sp[j] = reinterpret_cast<const T*>(src_base + ((size_t)d + c) * pitch);
+            dp[j] = reinterpret_cast<T*>(dst + (size_t)r * pitch);
+        }
+        for (uint32_t col = col0; col < upr; col += lpr) {
+            T v[MOVE_U];
+#pragma unroll
+            for (int j = 0; j < MOVE_U; ++j) v[j] = sp[j][col];
+#pragma unroll
+            for (int j = 0; j < MOVE_U; ++j) dp[j][col] = v[j];
+        }
+    }
+}
+
 template <typename F>
 hipError_t dispatch_metric(int metric, F&& f)
 {
@@ -1921,6 +1996,30 @@ hipError_t launch_ingest(hipStream_t s, const double* master, float* slab, float
     const uint64_t blocks = (n + 3) / 4;
     const int grid = (int)(blocks < 8192 ? blocks : 8192);
     hipLaunchKernelGGL(k_ingest, dim3(grid), dim3(256), 0, s, master, slab, inv_norm, flags, stats, n, dim, ld);
+    return hipGetLastError();
+}
+
+hipError_t launch_move_rows(hipStream_t s, const void* src_base, void* dst, uint64_t pitch, const uint32_t* keys, uint32_t c_lo,
+                            uint32_t c_hi, uint64_t dst_begin, uint64_t rows)
+{
+    if (rows == 0 || pitch == 0) return hipSuccess;
+    if (dst_begin + rows + c_hi > 0xFFFFFFFFull || pitch > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    const uintptr_t both = reinterpret_cast<uintptr_t>(src_base) | reinterpret_cast<uintptr_t>(dst) | (uintptr_t)pitch;
+    const int v = both % 16 == 0 ? 16 : both % 8 == 0 ? 8 : both % 4 == 0 ? 4 : 1;
+    const uint32_t upr = (uint32_t)(pitch / (uint64_t)v);
+    uint32_t lpr_log2 = 0;  // lanes per row: the power of two that covers a row's units, a whole wave at most
+    while (lpr_log2 < 6 && (1u << lpr_log2) < upr) ++lpr_log2;
+    const uint64_t n_groups = (rows + (64u >> lpr_log2) - 1) >> (6 - lpr_log2);
+    const uint64_t blocks = ((n_groups + MOVE_U - 1) / MOVE_U + 3) / 4;
+    const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096));
+    const char* sb = static_cast<const char*>(src_base);
+    char* db = static_cast<char*>(dst);
+    switch (v) {
+    case 16: hipLaunchKernelGGL(k_move_rows<16>, grid, dim3(256), 0, s, sb, db, keys, c_lo, c_hi, (uint32_t)dst_begin, (uint32_t)rows, upr, lpr_log2); break;
+    case 8: hipLaunchKernelGGL(k_move_rows<8>, grid, dim3(256), 0, s, sb, db, keys, c_lo, c_hi, (uint32_t)dst_begin, (uint32_t)rows, upr, lpr_log2); break;
+    case 4: hipLaunchKernelGGL(k_move_rows<4>, grid, dim3(256), 0, s, sb, db, keys, c_lo, c_hi, (uint32_t)dst_begin, (uint32_t)rows, upr, lpr_log2); break;
+    default: hipLaunchKernelGGL(k_move_rows<1>, grid, dim3(256), 0, s, sb, db, keys, c_lo, c_hi, (uint32_t)dst_begin, (uint32_t)rows, upr, lpr_log2); break;
+    }
     return hipGetLastError();
 }
 

@@ -82,6 +82,14 @@ hipError_t launch_embed_f32(hipStream_t s, const float* emb, uint64_t n, uint32_
 hipError_t launch_ingest(hipStream_t s, const double* master, float* slab, float* inv_norm, uint8_t* flags,
                          IngestStats* stats, uint64_t n, uint32_t dim, uint32_t ld);
 
+// Bulk delete (delete_plan.hpp): copies `rows` rows of `pitch` bytes to dst + r * pitch, r = 0 .. rows - 1, destination
+// row dst_begin + r reading source row d + #{i : keys[i] <= d} of src_base (d = dst_begin + r; keys[i] = r_i - i over the
+// ascending removed positions, on the device).  [c_lo, c_hi] = the shifts of the segment's first and last row.  dst is the
+// destination's place in the same array (a direct segment: the plan keeps the launch's destinations below its sources) or
+// the bounce buffer.  16 bytes per lane where pitch and both addresses allow, else 8, 4 or 1.
+hipError_t launch_move_rows(hipStream_t s, const void* src_base, void* dst, uint64_t pitch, const uint32_t* keys, uint32_t c_lo,
+                            uint32_t c_hi, uint64_t dst_begin, uint64_t rows);
+
 // Upper bound on the workgroups launch_scan uses (partials must hold SCAN_MAX_GRID*KP entries).
 constexpr int SCAN_MAX_GRID = 4096;
 constexpr int SELECT_MAX_GRID = 1024;

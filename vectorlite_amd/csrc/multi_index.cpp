@@ -367,6 +367,48 @@ int MultiFlatIndex::remove(uint64_t id)
     return publish_first_error(oc);  // an absent id is Ok(()) (src/index/flat.rs:93-96)
 }
 
+int MultiFlatIndex::remove_bulk(const uint64_t* ids, uint64_t n, uint64_t* out_rows)
+{
+    if (out_rows) *out_rows = 0;
+    if (n == 0) return OK;
+    if (!ids) return ERR_INVALID_ARG;
+    std::unique_lock<RwLock> lk(mu_);
+    if (const int brc = refuse_if_broken()) return brc;
+    const int P = (int)parts_.size();
+    std::vector<PartOutcome> oc((size_t)P);
+    std::vector<std::vector<uint64_t>> gone((size_t)P);
+    std::vector<uint64_t> rows((size_t)P, 0);
+    run_parts([&](int i) {
+        guarded(oc[(size_t)i], [&]() { return parts_[(size_t)i]->remove_bulk(ids, n, &gone[(size_t)i], &rows[(size_t)i]); });
+    });
+    for (int p = 0; p < P; ++p)
+        if (oc[(size_t)p].rc != OK) broken_.store(true);  // a compaction died half way on that part: nothing to roll back to
+    uint64_t total = 0;
+    for (int p = 0; p < P; ++p) {
+        total = mode_ == ROW_SHARDS ? total + rows[(size_t)p] : rows[0];
+        if (mode_ != ROW_SHARDS || gone[(size_t)p].empty()) continue;
+        std::vector<uint64_t>& sq = seq_[(size_t)p];  // one pass: the ascending positions drop out
+        size_t gi = 0, w = (size_t)gone[(size_t)p][0];
+        for (size_t r = w; r < sq.size(); ++r) {
+            if (gi < gone[(size_t)p].size() && gone[(size_t)p][gi] == r) ++gi;
+            else sq[w++] = sq[r];
+        }
+        if (w < sq.size()) sq.resize(w);
+    }
+    if (out_rows) *out_rows = total;
+    return publish_first_error(oc);
+}
+
+int MultiFlatIndex::set_delete_bounce(uint64_t bytes)
+{
+    std::unique_lock<RwLock> lk(mu_);
+    for (auto& p : parts_) {
+        const int rc = p->set_delete_bounce(bytes);
+        if (rc != OK) return rc;
+    }
+    return OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // search
 // ---------------------------------------------------------------------------------------------

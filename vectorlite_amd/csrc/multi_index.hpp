@@ -49,6 +49,9 @@ public:
     int add_bulk(const uint64_t* ids, const double* values, uint64_t n, bool validate, bool values_on_device,
                  int src_device = -1);
     int remove(uint64_t id);
+    // every part's GpuFlatIndex::remove_bulk; *out_rows = rows the index lost (a replica's count / the shards' sum)
+    int remove_bulk(const uint64_t* ids, uint64_t n, uint64_t* out_rows);
+    int set_delete_bounce(uint64_t bytes);  // on every part
     // out_pos: global insertion numbers (ROW_SHARDS) / storage positions (REPLICAS: every replica stores alike)
     int search(const double* query, uint64_t q_len, uint64_t k, int metric, uint64_t* out_pos, uint64_t* out_ids,
                double* out_scores, uint64_t* out_n) const;
