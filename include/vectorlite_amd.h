@@ -221,6 +221,17 @@ int vl_index_search_batch_cap(const vl_index *h, const double *queries, uint64_t
  * vl_index_filter_destroy: frees the token (a search using it at that moment finishes normally).
  * An unknown or destroyed token is VL_ERR_INVALID_ARG. */
 int vl_index_filter_create(vl_index *h, const uint64_t *ids, uint64_t n_ids, uint64_t *out_filter, uint64_t *out_rows);
+/* The opposite question -- "the best k, EXCEPT these ids" (rows already seen, the query document itself, soft-deleted rows):
+ * a token of the same token space (never 0, never reused, not cloned, freed by vl_index_filter_destroy / vl_index_destroy,
+ * resolved again on the first use after any add or delete) under which a row qualifies iff its id is NOT in the set.  ids in
+ * any order, repeats allowed; n_ids = 0 keeps every row; an id the index does not hold is ignored until a row with that id is
+ * added, which is then excluded; every row carrying an excluded id is excluded.  *out_rows and vl_index_filter_rows = len -
+ * excluded rows.  Every flat entry point that takes a filter token takes this one, with its semantics read over "the
+ * FlatIndex holding only the qualifying rows in storage order" (vl_index_search_batch_filters may mix both kinds); errors
+ * are the include filter's, VL_ERR_NAN_SCORE only when a QUALIFYING row scores NaN.  The token costs a bitmap of len / 8
+ * bytes; a single vl_index_search_filtered streams the unfiltered search's ladder (int8 / bf16 / f32 copies) under that
+ * bitmap, the other calls build the position list (4 bytes per qualifying row) on first use.  DESIGN.md section 23. */
+int vl_index_filter_create_excluding(vl_index *h, const uint64_t *ids, uint64_t n_ids, uint64_t *out_filter, uint64_t *out_rows);
 int vl_index_filter_rows(const vl_index *h, uint64_t filter, uint64_t *out_rows);
 int vl_index_filter_destroy(vl_index *h, uint64_t filter);
 

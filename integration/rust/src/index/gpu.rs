@@ -46,6 +46,7 @@ extern "C" {
     fn vl_index_search_cap(h: *const vl_index, query: *const f64, q_len: u64, k: u64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_batch_cap(h: *const vl_index, queries: *const f64, nq: u64, q_len: u64, k: u64, metric: c_int, out_stride: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_filter_create(h: *mut vl_index, ids: *const u64, n_ids: u64, out_filter: *mut u64, out_rows: *mut u64) -> c_int;
+    fn vl_index_filter_create_excluding(h: *mut vl_index, ids: *const u64, n_ids: u64, out_filter: *mut u64, out_rows: *mut u64) -> c_int;
     fn vl_index_filter_destroy(h: *mut vl_index, filter: u64) -> c_int;
     fn vl_index_search_filtered(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, k: u64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_batch_filters(h: *const vl_index, filters: *const u64, n_filters: u64, queries: *const f64, nq: u64, q_len: u64, k: u64, metric: c_int, out_stride: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
@@ -339,6 +340,39 @@ impl GpuFlatIndex {
     pub fn search_filtered(&self, ids: &[u64], query: &[f64], k: usize, metric: SimilarityMetric) -> VectorLiteResult<Vec<SearchResult>> {
         let (mut token, mut rows) = (0u64, 0u64);
         let rc = unsafe { vl_index_filter_create(self.0.raw, ids.as_ptr(), ids.len() as u64, &mut token, &mut rows) };
+        if rc != VL_OK {
+            return Err(VectorLiteError::InternalError(last_error()));
+        }
+        let cap = k.min(rows as usize).max(1);
+        let (mut out_ids, mut scores, mut n) = (vec![0u64; cap], vec![0f64; cap], 0u64);
+        let rc = unsafe {
+            vl_index_search_filtered(self.0.raw, token, query.as_ptr(), query.len() as u64, k as u64, metric_code(metric), cap as u64, out_ids.as_mut_ptr(), scores.as_mut_ptr(), &mut n)
+        };
+        let err = if rc == VL_OK { String::new() } else { last_error() };
+        unsafe { vl_index_filter_destroy(self.0.raw, token) };
+        match rc {
+            VL_OK => Ok((0..n as usize)
+                .map(|i| {
+                    let (text, metadata) = self.0.side.get(&out_ids[i]).cloned().unwrap_or_default();
+                    SearchResult { id: out_ids[i], score: scores[i], text, metadata }
+                })
+                .collect()),
+            VL_ERR_DIM_MISMATCH => {
+                let (mut e, mut a) = (0u64, 0u64);
+                unsafe { vl_last_dim_mismatch(&mut e, &mut a) };
+                Err(VectorLiteError::DimensionMismatch { expected: e as usize, actual: a as usize })
+            }
+            VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
+            _ => Err(VectorLiteError::InternalError(err)),
+        }
+    }
+
+    /// `search` among the rows whose id is NOT in `ids` (no reference counterpart): exactly what `FlatIndex::search` returns
+    /// on a FlatIndex holding just the other rows in their storage order -- rows already shown, the query document itself,
+    /// soft-deleted rows.  Single-GPU handles only (a multi-GPU handle returns an error).
+    pub fn search_excluding(&self, ids: &[u64], query: &[f64], k: usize, metric: SimilarityMetric) -> VectorLiteResult<Vec<SearchResult>> {
+        let (mut token, mut rows) = (0u64, 0u64);
+        let rc = unsafe { vl_index_filter_create_excluding(self.0.raw, ids.as_ptr(), ids.len() as u64, &mut token, &mut rows) };
         if rc != VL_OK {
             return Err(VectorLiteError::InternalError(last_error()));
         }

@@ -212,15 +212,21 @@ class IdFilter:
     """A set of ids of one FlatIndex (vl_index_filter_create): searches given it rank only the rows whose id is in the set,
     exactly as FlatIndex::search would on an index holding just those rows in their storage order.  It follows the index:
     after add / delete the next use resolves it against the current rows.  `rows()` = rows that qualify now; `close()`
-    (or leaving a `with` block) frees it."""
+    (or leaving a `with` block) frees it.  An exclusion filter (`make_filter(ids, exclude=True)`,
+    vl_index_filter_create_excluding; `exclude` is True) is the opposite set: the rows whose id is NOT in `ids` qualify."""
 
-    def __init__(self, index: "FlatIndex", token: int):
+    def __init__(self, index: "FlatIndex", token: int, exclude: bool = False):
         self._index = index
         self._token = token
+        self._exclude = bool(exclude)
 
     @property
     def token(self) -> int:
         return self._token
+
+    @property
+    def exclude(self) -> bool:
+        return self._exclude
 
     def rows(self) -> int:
         if not self._token:
@@ -251,15 +257,36 @@ class IdFilter:
             pass
 
 
-def _make_filter(L, h, owner, ids) -> IdFilter:
+def _make_filter(L, h, owner, ids, exclude: bool = False) -> IdFilter:
     ids = np.ascontiguousarray(np.fromiter((int(i) for i in ids), dtype=np.uint64)
                                if not isinstance(ids, np.ndarray) else ids.astype(np.uint64, copy=False))
     tok, rows = C.c_uint64(0), C.c_uint64(0)
-    rc = L.vl_index_filter_create(h, _pu64(ids), ids.size, C.byref(tok), C.byref(rows))
+    create = L.vl_index_filter_create_excluding if exclude else L.vl_index_filter_create
+    rc = create(h, _pu64(ids), ids.size, C.byref(tok), C.byref(rows))
     if rc == VL_ERR_INVALID_ARG:
         raise IndexOpError(_last_error())
     _raise(rc)
-    return IdFilter(owner, int(tok.value))
+    return IdFilter(owner, int(tok.value), exclude)
+
+
+class _ExcludeIds:
+    """`exclude=` given as an iterable of ids: a one-shot exclusion filter is made of it where the token is needed."""
+
+    def __init__(self, ids):
+        self.ids = ids
+
+
+def _one_filter(filter, exclude):
+    """What a search's `filter=` / `exclude=` pair asks for, as the one value _filter_token takes."""
+    if exclude is None:
+        return filter
+    if filter is not None:
+        raise ValueError("pass one of filter / exclude")
+    if isinstance(exclude, IdFilter):
+        if not exclude.exclude:
+            raise ValueError("`exclude` takes ids or an exclusion IdFilter (make_filter(ids, exclude=True))")
+        return exclude
+    return _ExcludeIds(exclude)
 
 
 class WalkFilter:
@@ -536,10 +563,12 @@ class FlatIndex:
         _raise(self._L.vl_index_last_delete(self._h, out))
         return dict(zip(("removed", "moved", "direct_launches", "bounced_segments", "bytes_written", "micros"), (int(v) for v in out)))
 
-    def search(self, query, k: int, similarity_metric: int = SimilarityMetric.Cosine, filter=None) -> List[SearchResult]:
+    def search(self, query, k: int, similarity_metric: int = SimilarityMetric.Cosine, filter=None,
+               exclude=None) -> List[SearchResult]:
         """`filter`: None, an IdFilter of this index, or an iterable of ids (a one-shot filter): the top k among the rows
-        whose id is in the set."""
-        ids, scores = self.search_arrays(query, k, similarity_metric, filter=filter)
+        whose id is in the set.  `exclude`: an iterable of ids or an exclusion IdFilter: the top k among the rows whose id
+        is NOT in the set.  One of the two at most."""
+        ids, scores = self.search_arrays(query, k, similarity_metric, filter=filter, exclude=exclude)
         out = []
         for i, s in zip(ids.tolist(), scores.tolist()):
             text, md = self._meta.get(i, ("", None))
@@ -590,7 +619,9 @@ class FlatIndex:
             tl.buf = buf
         return buf
 
-    def search_arrays(self, query, k: int, metric: int = 0, filter=None) -> Tuple[np.ndarray, np.ndarray]:
+    def search_arrays(self, query, k: int, metric: int = 0, filter=None, exclude=None) -> Tuple[np.ndarray, np.ndarray]:
+        if exclude is not None:
+            filter = _one_filter(filter, exclude)
         q = query
         if not (type(q) is np.ndarray and q.dtype == np.float64 and q.ndim == 1 and q.flags.c_contiguous):
             q = _f64(query).ravel()
@@ -605,9 +636,11 @@ class FlatIndex:
         return ids[:m].copy(), scores[:m].copy()
 
     # ---- id filters -------------------------------------------------------------------------
-    def make_filter(self, ids) -> IdFilter:
-        """An IdFilter over `ids` (any order, repeats allowed; ids the index does not hold are ignored)."""
-        return _make_filter(self._L, self._h, self, ids)
+    def make_filter(self, ids, exclude: bool = False) -> IdFilter:
+        """An IdFilter over `ids` (any order, repeats allowed; ids the index does not hold are ignored).  exclude=True: the
+        rows whose id is NOT in `ids` qualify (an empty `ids` keeps every row; a row added later under one of the ids is
+        excluded from then on)."""
+        return _make_filter(self._L, self._h, self, ids, exclude)
 
     def _filter_token(self, filter):
         """(token, one-shot filter to close afterwards or None)"""
@@ -615,7 +648,7 @@ class FlatIndex:
             if filter._index is not self:
                 raise ValueError("the filter belongs to another index")
             return filter.token, None
-        f = self.make_filter(filter)
+        f = self.make_filter(filter.ids, exclude=True) if isinstance(filter, _ExcludeIds) else self.make_filter(filter)
         return f.token, f
 
     def _search_filtered(self, q, k, metric, filter, cap, ids, scores, n, p_ids, p_scores, p_n):
@@ -632,10 +665,11 @@ class FlatIndex:
         return ids[:m].copy(), scores[:m].copy()
 
     # ---- range search -----------------------------------------------------------------------
-    def search_range_arrays(self, query, min_score: float, metric: int = 0, filter=None, limit=None):
+    def search_range_arrays(self, query, min_score: float, metric: int = 0, filter=None, limit=None, exclude=None):
         """(ids, scores, total): every row whose score is >= min_score -- the longest prefix of search(query, len, metric)
         with score >= min_score (among the filter's rows when `filter` is given: an IdFilter or an iterable of ids).
         `total` = rows that qualify; `limit` caps what is returned (0: count only), None returns all of them."""
+        filter = _one_filter(filter, exclude)
         if filter is None:
             return _search_range(self._L, self._h, query, min_score, metric, 0, limit)
         tok, temp = self._filter_token(filter)
@@ -646,20 +680,21 @@ class FlatIndex:
                 temp.close()
 
     def search_range(self, query, min_score: float, similarity_metric: int = SimilarityMetric.Cosine, filter=None,
-                     limit=None) -> List[SearchResult]:
-        ids, scores, _ = self.search_range_arrays(query, min_score, similarity_metric, filter=filter, limit=limit)
+                     limit=None, exclude=None) -> List[SearchResult]:
+        ids, scores, _ = self.search_range_arrays(query, min_score, similarity_metric, filter=filter, limit=limit, exclude=exclude)
         out = []
         for i, s in zip(ids.tolist(), scores.tolist()):
             text, md = self._meta.get(i, ("", None))
             out.append(SearchResult(id=i, score=s, text=text, metadata=md))
         return out
 
-    def search_range_batch_arrays(self, queries, min_score, metric: int = 0, filter=None, limit=None):
+    def search_range_batch_arrays(self, queries, min_score, metric: int = 0, filter=None, limit=None, exclude=None):
         """(ids_list, scores_list, totals) for queries [nq, dim]: entry i is search_range_arrays(queries[i], min_score[i], ...)
         on one index state.  `min_score` is a scalar or one value per query; `limit` caps what is returned per query
         (0: count only), None returns every qualifying row.  With limit=None the queries with more than 64 qualifying rows
         are asked a second time: if a writer runs between the two calls they are answered on a later index state than the
         rest of the batch -- pass a `limit` where one state for the whole batch matters."""
+        filter = _one_filter(filter, exclude)
         if filter is None:
             return _search_range_batch(self._L, self._h, queries, min_score, metric, 0, limit)
         tok, temp = self._filter_token(filter)
@@ -670,8 +705,9 @@ class FlatIndex:
                 temp.close()
 
     def search_range_batch(self, queries, min_score, similarity_metric: int = SimilarityMetric.Cosine, filter=None,
-                           limit=None) -> List[List[SearchResult]]:
-        ids_list, scores_list, _ = self.search_range_batch_arrays(queries, min_score, similarity_metric, filter=filter, limit=limit)
+                           limit=None, exclude=None) -> List[List[SearchResult]]:
+        ids_list, scores_list, _ = self.search_range_batch_arrays(queries, min_score, similarity_metric, filter=filter, limit=limit,
+                                                                  exclude=exclude)
         out = []
         for ids, scores in zip(ids_list, scores_list):
             row = []
@@ -696,10 +732,11 @@ class FlatIndex:
         two different keys it is an IndexOpError; ids the index does not hold are ignored)."""
         return _make_groups(self._L, self._h, self, ids, keys)
 
-    def search_grouped_arrays(self, query, k: int, metric: int = 0, groups=None, filter=None):
+    def search_grouped_arrays(self, query, k: int, metric: int = 0, groups=None, filter=None, exclude=None):
         """(group_keys, ids, scores): the best row of each of the best k groups of `groups` (a GroupTable of this index), in
         FlatIndex::search's order (among the filter's rows when `filter` is given: an IdFilter or an iterable of ids).
         Rows whose id the table does not hold take no part."""
+        filter = _one_filter(filter, exclude)
         if not isinstance(groups, GroupTable):
             raise ValueError("groups must be a GroupTable of this index (make_groups)")
         if groups._index is not self:
@@ -714,8 +751,8 @@ class FlatIndex:
                 temp.close()
 
     def search_grouped(self, query, k: int, similarity_metric: int = SimilarityMetric.Cosine, groups=None,
-                       filter=None) -> List[Tuple[int, SearchResult]]:
-        keys, ids, scores = self.search_grouped_arrays(query, k, similarity_metric, groups=groups, filter=filter)
+                       filter=None, exclude=None) -> List[Tuple[int, SearchResult]]:
+        keys, ids, scores = self.search_grouped_arrays(query, k, similarity_metric, groups=groups, filter=filter, exclude=exclude)
         out = []
         for g, i, s in zip(keys.tolist(), ids.tolist(), scores.tolist()):
             text, md = self._meta.get(i, ("", None))
@@ -723,11 +760,12 @@ class FlatIndex:
         return out
 
     # ---- diversified (MMR) search ------------------------------------------------------------
-    def search_mmr_arrays(self, query, k: int, fetch_k: int = 20, lambda_mult: float = 0.5, metric: int = 0, filter=None):
+    def search_mmr_arrays(self, query, k: int, fetch_k: int = 20, lambda_mult: float = 0.5, metric: int = 0, filter=None, exclude=None):
         """(ids, scores): maximal marginal relevance over the exact candidates search(query, fetch_k, metric) (among the
         filter's rows when `filter` is given: an IdFilter or an iterable of ids).  The best candidate first, then k - 1
         times the one maximising lambda_mult * score - (1 - lambda_mult) * (largest similarity to anything chosen);
         entries come in selection order, scores are the candidates' search scores.  lambda_mult = 1 is the plain top k."""
+        filter = _one_filter(filter, exclude)
         if filter is None:
             return _search_mmr(self._L, self._h, query, k, fetch_k, lambda_mult, metric, 0)
         tok, temp = self._filter_token(filter)
@@ -738,8 +776,8 @@ class FlatIndex:
                 temp.close()
 
     def search_mmr(self, query, k: int, fetch_k: int = 20, lambda_mult: float = 0.5,
-                   similarity_metric: int = SimilarityMetric.Cosine, filter=None) -> List[SearchResult]:
-        ids, scores = self.search_mmr_arrays(query, k, fetch_k, lambda_mult, similarity_metric, filter=filter)
+                   similarity_metric: int = SimilarityMetric.Cosine, filter=None, exclude=None) -> List[SearchResult]:
+        ids, scores = self.search_mmr_arrays(query, k, fetch_k, lambda_mult, similarity_metric, filter=filter, exclude=exclude)
         out = []
         for i, s in zip(ids.tolist(), scores.tolist()):
             text, md = self._meta.get(i, ("", None))
@@ -758,12 +796,14 @@ class FlatIndex:
                                                  _pu64(ids), _pf64(scores), C.byref(n)))
         return pos[: n.value].copy(), ids[: n.value].copy(), scores[: n.value].copy()
 
-    def search_batch(self, queries, k: int, metric: int = 0, filter=None, filters=None):
-        """New capability (no reference counterpart): nq independent searches.
+    def search_batch(self, queries, k: int, metric: int = 0, filter=None, filters=None, exclude=None):
+        """New capability (no reference counterpart): nq independent searches.  `exclude` (ids or an exclusion IdFilter)
+        stands where `filter` does; the items of `filters` may be IdFilters of either kind.
         Returns (ids [nq, k], scores [nq, k], n [nq]); row i is exactly search(queries[i]) (with `filter`: exactly
         search(queries[i], filter=filter); with `filters`, a sequence of nq items each an IdFilter of this index or an
         iterable of ids: exactly search(queries[i], filter=filters[i])).  The filtered forms share scan launches
         (last_filtered_batch() tells how the jobs were routed)."""
+        filter = _one_filter(filter, exclude)
         if filter is not None and filters is not None:
             raise ValueError("give `filter` (one for the batch) or `filters` (one per query), not both")
         Q = _f64(queries)
@@ -1406,9 +1446,9 @@ class HNSWIndex:
         _raise(self._L.vl_index_hnsw_last_filtered(self._h, C.byref(route), C.byref(cap), C.byref(nodes), C.byref(cut)))
         return {"route": int(route.value), "cap": int(cap.value), "pass_nodes": int(nodes.value), "cap_cut_walks": int(cut.value)}
 
-    def make_filter(self, ids) -> IdFilter:
+    def make_filter(self, ids, exclude: bool = False) -> IdFilter:
         """Filtered search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""
-        return _make_filter(self._L, self._h, self, ids)
+        return _make_filter(self._L, self._h, self, ids, exclude)
 
     def search_range_arrays(self, query, min_score: float, metric: int = 0, filter=None, limit=None):
         """Range search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""
@@ -1443,14 +1483,16 @@ class HNSWIndex:
     def search_grouped(self, query, k: int, similarity_metric: int = SimilarityMetric.Cosine, groups=None, filter=None):
         return self.search_grouped_arrays(query, k, similarity_metric, groups, filter)
 
-    def search_arrays(self, query, k: int, metric: int, ef: int = 0, filter=None):
+    def search_arrays(self, query, k: int, metric: int, ef: int = 0, filter=None, exclude=None):
+        if exclude is not None:
+            self.make_filter([], exclude=True)  # raises: exclusion filters do not serve HNSW handles
         ids, scores, n = self.search_batch(_f64(query).ravel()[None, :], k, metric, ef, filter=filter)
         m = int(n[0])
         return ids[0, :m].copy(), scores[0, :m].copy()
 
-    def search(self, query, k: int, similarity_metric: int, filter=None) -> List[SearchResult]:
-        if filter is not None:
-            ids, scores = self.search_arrays(query, k, similarity_metric, 0, filter)
+    def search(self, query, k: int, similarity_metric: int, filter=None, exclude=None) -> List[SearchResult]:
+        if filter is not None or exclude is not None:
+            ids, scores = self.search_arrays(query, k, similarity_metric, 0, filter, exclude)
             out = []
             for i, s in zip(ids.tolist(), scores.tolist()):
                 text, md = self._meta.get(i, ("", None))

@@ -358,6 +358,15 @@ int vl_index_filter_create(vl_index* h, const uint64_t* ids, uint64_t n_ids, uin
     });
 }
 
+int vl_index_filter_create_excluding(vl_index* h, const uint64_t* ids, uint64_t n_ids, uint64_t* out_filter, uint64_t* out_rows)
+{
+    return guarded([&]() -> int {
+        VL_FILTER_HANDLE(h);
+        if (!out_filter) return VL_ERR_INVALID_ARG;
+        return h->flat->filter_create(ids, n_ids, out_filter, out_rows, /*exclude=*/true);
+    });
+}
+
 int vl_index_filter_rows(const vl_index* h, uint64_t filter, uint64_t* out_rows)
 {
     return guarded([&]() -> int {

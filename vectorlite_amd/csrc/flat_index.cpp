@@ -1016,10 +1016,11 @@ int GpuFlatIndex::lock_for_query(int metric, uint64_t q_len, std::shared_lock<Rw
     return OK;
 }
 
-int GpuFlatIndex::resolve_if_stale(Workspace* ws, IdFilter* f) const
+int GpuFlatIndex::resolve_if_stale(Workspace* ws, IdFilter* f, bool need_list) const
 {
     std::lock_guard<std::mutex> g(f->mu);
-    return f->resolved_at != mutations_ ? resolve_filter(ws, f) : OK;
+    if (f->resolved_at != mutations_) VL_TRY(resolve_filter(ws, f));
+    return need_list ? ensure_plist(ws, f) : OK;
 }
 
 int GpuFlatIndex::resolve_if_stale(Workspace* ws, GroupTable* t) const
@@ -1030,12 +1031,12 @@ int GpuFlatIndex::resolve_if_stale(Workspace* ws, GroupTable* t) const
 
 // From here on the resolutions are read only: a reader that finds them current leaves them alone, writers are shut out.
 template <typename Body>
-int GpuFlatIndex::run_search(GroupTable* t, IdFilter* f, Body&& body) const
+int GpuFlatIndex::run_search(GroupTable* t, IdFilter* f, Body&& body, bool need_list) const
 {
     WsLease lease(this);
     if (lease.status() != OK) return lease.status();
     if (t) VL_TRY(lease.done(resolve_if_stale(lease.ws, t)));
-    if (f) VL_TRY(lease.done(resolve_if_stale(lease.ws, f)));
+    if (f) VL_TRY(lease.done(resolve_if_stale(lease.ws, f, need_list)));
     InFlight searching(active_searches_);
     return lease.done(body(lease.ws));
 }
@@ -1302,46 +1303,59 @@ int GpuFlatIndex::search_batch_locked(const double* queries, uint64_t nq, uint64
 // Single-query filter choice (set_single_filter, single_filter.hpp's ladder_stage).  Modes 1 and 3 keep their one-way
 // switch-off; auto applies each stage's recent-outcome window, so a bad streak pauses it and the periodic probes bring
 // it back.
-bool GpuFlatIndex::bf16_first(uint64_t n) const
+bool GpuFlatIndex::bf16_first(uint64_t n, bool masked) const
 {
     const int mode = single_filter_.load(std::memory_order_relaxed);
     const bool ok = !(mode == FILTER_AUTO && auto_unavailable_.load(std::memory_order_relaxed));
     return ladder_stage(
         FILTER_BF16, mode, ok, n * (uint64_t)ld_ * sizeof(float), auto_min_bytes_,
-        [&] { return forced_stage_on(bf16_tries_.load(std::memory_order_relaxed), bf16_fails_.load(std::memory_order_relaxed)); },
-        [&] { return auto_window_.want(); });
+        [&] {
+            return forced_stage_on((masked ? mask_bf16_tries_ : bf16_tries_).load(std::memory_order_relaxed),
+                                   (masked ? mask_bf16_fails_ : bf16_fails_).load(std::memory_order_relaxed));
+        },
+        [&] { return (masked ? mask_bf16_window_ : auto_window_).want(); });
 }
 
-bool GpuFlatIndex::i8_first(uint64_t n) const
+bool GpuFlatIndex::i8_first(uint64_t n, bool masked) const
 {
     const int mode = single_filter_.load(std::memory_order_relaxed);
     const bool ok = !(mode == FILTER_AUTO && i8_unavailable_.load(std::memory_order_relaxed));
     return ladder_stage(
         FILTER_I8, mode, ok, n * (uint64_t)ld_ * sizeof(float), i8_min_bytes_,
-        [&] { return forced_stage_on(i8_tries_.load(std::memory_order_relaxed), i8_fails_.load(std::memory_order_relaxed)); },
-        [&] { return i8_window_.want(); });
+        [&] {
+            return forced_stage_on((masked ? mask_i8_tries_ : i8_tries_).load(std::memory_order_relaxed),
+                                   (masked ? mask_i8_fails_ : i8_fails_).load(std::memory_order_relaxed));
+        },
+        [&] { return (masked ? mask_i8_window_ : i8_window_).want(); });
 }
 
-void GpuFlatIndex::i8_outcome(bool certified) const
+void GpuFlatIndex::i8_outcome(bool certified, bool masked) const
 {
-    i8_tries_.fetch_add(1, std::memory_order_relaxed);
-    if (!certified) i8_fails_.fetch_add(1, std::memory_order_relaxed);
-    i8_window_.record(certified);
+    (masked ? mask_i8_tries_ : i8_tries_).fetch_add(1, std::memory_order_relaxed);
+    if (!certified) (masked ? mask_i8_fails_ : i8_fails_).fetch_add(1, std::memory_order_relaxed);
+    (masked ? mask_i8_window_ : i8_window_).record(certified);
 }
 
-void GpuFlatIndex::bf16_outcome(bool certified) const
+void GpuFlatIndex::bf16_outcome(bool certified, bool masked) const
 {
-    bf16_tries_.fetch_add(1, std::memory_order_relaxed);
-    if (!certified) bf16_fails_.fetch_add(1, std::memory_order_relaxed);
-    auto_window_.record(certified);
+    (masked ? mask_bf16_tries_ : bf16_tries_).fetch_add(1, std::memory_order_relaxed);
+    if (!certified) (masked ? mask_bf16_fails_ : bf16_fails_).fetch_add(1, std::memory_order_relaxed);
+    (masked ? mask_bf16_window_ : auto_window_).record(certified);
 }
 
 int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_eff, int metric,
                                 uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
-                                bool skip_fast, bool skip_bf16, const MmrReq* mmr) const
+                                bool skip_fast, bool skip_bf16, const MmrReq* mmr, const IdFilter* mask) const
 {
     const uint64_t n = ids_.size();
     hipStream_t st = ws->stream;
+    // Under a mask every stage streams all n rows and drops the excluded ones at the sink: its lists hold kept rows only,
+    // so the finalize's bound check and its "a list of every row" rule are about the mask's m rows (search_subset's
+    // argument), and a profiled stage read the keep bitmap on top of its rows.
+    const bool masked = mask != nullptr;
+    const unsigned long long* keep = masked ? mask->d_keep : nullptr;
+    const uint64_t n_cert = masked ? mask->m : n;
+    const uint64_t keep_bytes = masked ? n / 8 : 0;
     // A diversified search (mmr != nullptr, search_mmr): every stage's finalize leaves its block in DEVICE memory,
     // unstamped, and the selection's two launches behind it write the pinned block and the stamp -- the host waits once,
     // as before, and a stage that did not certify shows in the same flags.
@@ -1389,7 +1403,7 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
     // bytes).  Its keys bound the score from above, so the same exact f64 rescoring and bound check (with the int8 key's
     // evaluation term) certify the answer or hand the query on: to the bf16 stage when that one is on, else to the f32
     // scan.  Same protocol as below: the query in the kernel arguments, the finalize reading the pinned f64 query.
-    bool i8_stage = fast_ok && !skip_bf16 && scan_i8_supported((uint32_t)dim_, metric) && i8_first(n);
+    bool i8_stage = fast_ok && !skip_bf16 && scan_i8_supported((uint32_t)dim_, metric) && i8_first(n, masked);
     if (i8_stage) {
         const int irc = ensure_i8_slab();
         if (irc != OK) {
@@ -1406,19 +1420,24 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
         const uint32_t seq = next_stamp(ws);
         int grid = 0, variant = 0;
         if (prof) VL_HIP(hipEventRecord(ws->ev0, st));
-        VL_HIP(launch_scan_i8(st, metric, d_slab8_, d_sr8_, d_norm8_, q8, n, (uint32_t)dim_, ws->d_partials, &grid, &variant));
+        if (masked)
+            VL_HIP(launch_scan_i8_masked(st, metric, d_slab8_, d_sr8_, d_norm8_, keep, q8, n, (uint32_t)dim_, ws->d_partials, &grid,
+                                         &variant));
+        else
+            VL_HIP(launch_scan_i8(st, metric, d_slab8_, d_sr8_, d_norm8_, q8, n, (uint32_t)dim_, ws->d_partials, &grid, &variant));
         if (prof) VL_HIP(hipEventRecord(ws->ev1, st));
         // the keys are upper bounds up to their f32 evaluation (mfma_scan.hpp)
         VL_HIP(launch_merge_finalize(st, mmr ? 0u : seq, metric, ws->d_partials, grid, d_master_, ws->h_q64, ws->h_q64 + dim_,
-                                     (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_, fin_out, IN_EXTRA_I8_SINGLE));
+                                     (uint32_t)dim_, n_cert, (uint32_t)k_eff, max_row_norm_, fin_out, IN_EXTRA_I8_SINGLE));
         VL_TRY(mmr_from_blocks(seq));
         note_scan(variant, grid, true);
         VL_TRY(wait_result(ws, seq));
         // the rows plus the per-row (s, r) pair, and |row| for dot
-        if (prof) VL_TRY(account_profile(ws, n * ((uint64_t)ldb + 2 * sizeof(float) + (metric == DOT ? sizeof(float) : 0))));
+        if (prof)
+            VL_TRY(account_profile(ws, n * ((uint64_t)ldb + 2 * sizeof(float) + (metric == DOT ? sizeof(float) : 0)) + keep_bytes));
         const SearchResultBlock& r = *ws->h_result;
         const bool certified = !(r.flags & RESULT_NEEDS_EXACT) && r.n_out == n_answer;
-        i8_outcome(certified);
+        i8_outcome(certified, masked);
         if (certified) return take_result("int8 filter");
     }
 
@@ -1426,7 +1445,7 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
     // Its candidates get the same exact f64 rescoring and a bound with the bf16 row-rounding term; if that cannot
     // certify the answer the f32 scan below runs as before.  Same protocol as the f32 scan: the f32 query in the kernel
     // arguments, the finalize reading the pinned f64 query, a stamped result block -- nothing is copied to the device.
-    bool bf16_stage = fast_ok && !skip_bf16 && scan_bf16_supported((uint32_t)dim_, metric) && bf16_first(n);
+    bool bf16_stage = fast_ok && !skip_bf16 && scan_bf16_supported((uint32_t)dim_, metric) && bf16_first(n, masked);
     if (bf16_stage) {
         const int brc = ensure_bf16_slab(false);
         if (brc != OK) {
@@ -1442,19 +1461,23 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
         const uint32_t seq = next_stamp(ws);
         int grid = 0, variant = 0;
         if (prof) VL_HIP(hipEventRecord(ws->ev0, st));
-        VL_HIP(launch_scan_bf16(st, metric, d_slab16_, d_norm16_, d_sqnorm_, nullptr, n, (uint32_t)dim_, ws->d_partials,
-                                &grid, q32, &variant));
+        if (masked)
+            VL_HIP(launch_scan_bf16_masked(st, metric, d_slab16_, d_norm16_, d_sqnorm_, keep, n, (uint32_t)dim_, ws->d_partials,
+                                           &grid, q32, &variant));
+        else
+            VL_HIP(launch_scan_bf16(st, metric, d_slab16_, d_norm16_, d_sqnorm_, nullptr, n, (uint32_t)dim_, ws->d_partials,
+                                    &grid, q32, &variant));
         if (prof) VL_HIP(hipEventRecord(ws->ev1, st));
         // rows are rounded to bf16, the query is f32 (mfma_scan.hpp)
         VL_HIP(launch_merge_finalize(st, mmr ? 0u : seq, metric, ws->d_partials, grid, d_master_, ws->h_q64, ws->h_q64 + dim_,
-                                     (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_, fin_out, IN_EXTRA_BF16_SINGLE));
+                                     (uint32_t)dim_, n_cert, (uint32_t)k_eff, max_row_norm_, fin_out, IN_EXTRA_BF16_SINGLE));
         VL_TRY(mmr_from_blocks(seq));
         note_scan(variant, grid, true);
         VL_TRY(wait_result(ws, seq));
-        if (prof) VL_TRY(account_profile(ws, n * (uint64_t)ldb * 2));
+        if (prof) VL_TRY(account_profile(ws, n * (uint64_t)ldb * 2 + keep_bytes));
         const SearchResultBlock& r = *ws->h_result;
         const bool certified = !(r.flags & RESULT_NEEDS_EXACT) && r.n_out == n_answer;
-        bf16_outcome(certified);
+        bf16_outcome(certified, masked);
         if (certified) return take_result("bf16 filter");
     }
     if (fast_ok) {
@@ -1469,18 +1492,22 @@ int GpuFlatIndex::search_locked(Workspace* ws, const double* query, uint64_t k_e
         const double* fq = q_on_device ? ws->d_q64 : ws->h_q64;
         const uint32_t seq = next_stamp(ws);
         if (prof) VL_HIP(hipEventRecord(ws->ev0, st));
-        VL_HIP(launch_scan(st, metric, d_slab_, d_inv_norm_, ws->d_q64, n, (uint32_t)dim_, ld_, ws->d_partials, &plan, q32));
+        if (masked)
+            VL_HIP(launch_scan_masked(st, metric, d_slab_, d_inv_norm_, keep, n, ws->d_q64, (uint32_t)dim_, ld_, ws->d_partials, &plan, q32));
+        else
+            VL_HIP(launch_scan(st, metric, d_slab_, d_inv_norm_, ws->d_q64, n, (uint32_t)dim_, ld_, ws->d_partials, &plan, q32));
         if (prof) VL_HIP(hipEventRecord(ws->ev1, st));
-        VL_HIP(launch_merge_finalize(st, metric, ws->d_partials, plan.grid, 1, d_master_, fq, fq + dim_, (uint32_t)dim_, n,
+        VL_HIP(launch_merge_finalize(st, metric, ws->d_partials, plan.grid, 1, d_master_, fq, fq + dim_, (uint32_t)dim_, n_cert,
                                      (uint32_t)k_eff, max_row_norm_, fin_out, 0.0, mmr ? 0u : seq));
         VL_TRY(mmr_from_blocks(seq));
         note_scan(plan.variant, plan.grid, qarg);
         VL_TRY(wait_result(ws, seq));
-        if (prof) VL_TRY(account_profile(ws, n * (uint64_t)ld_ * sizeof(float)));
+        if (prof) VL_TRY(account_profile(ws, n * (uint64_t)ld_ * sizeof(float) + keep_bytes));
         const SearchResultBlock& r = *ws->h_result;
         if (!(r.flags & RESULT_NEEDS_EXACT) && r.n_out == n_answer) return take_result("fast path");
         // ties at the cut or a failed bound: fall through to the exact kernels
     }
+    if (masked) return MASK_UNCERTIFIED;  // the exact kernels want the position list: the caller's route
 
     // 60 < k <= 220: several 64-entry candidate lists (one per partition of the scan's workgroups) rescored and
     // ranked together; still one f32 scan (2.3 ms at N = 10 M) instead of the exact f64 scan + selection rounds
@@ -1655,7 +1682,7 @@ int GpuFlatIndex::run_exact(Workspace* ws, int metric, uint64_t n, uint64_t k_ef
 IdFilter::~IdFilter()
 {
     (void)hipSetDevice(device);
-    void* dev[] = {d_ids, d_counts, d_plist};
+    void* dev[] = {d_ids, d_counts, d_plist, d_keep};
     for (void* p : dev)
         if (p) (void)hipFree(p);
 }
@@ -1669,7 +1696,7 @@ int GpuFlatIndex::find_filter(uint64_t token, std::shared_ptr<IdFilter>* out) co
     return token_find(filters_mu_, filters_, token, UNKNOWN_FILTER, out);
 }
 
-int GpuFlatIndex::filter_create(const uint64_t* ids, uint64_t n_ids, uint64_t* out_token, uint64_t* out_rows)
+int GpuFlatIndex::filter_create(const uint64_t* ids, uint64_t n_ids, uint64_t* out_token, uint64_t* out_rows, bool exclude)
 {
     if (!out_token || (!ids && n_ids)) return ERR_INVALID_ARG;
     *out_token = 0;
@@ -1679,6 +1706,7 @@ int GpuFlatIndex::filter_create(const uint64_t* ids, uint64_t n_ids, uint64_t* o
     }
     auto f = std::make_shared<IdFilter>();
     f->device = device_;
+    f->exclude = exclude;
     f->ids.assign(ids, ids + n_ids);
     std::sort(f->ids.begin(), f->ids.end());
     f->ids.erase(std::unique(f->ids.begin(), f->ids.end()), f->ids.end());
@@ -1686,8 +1714,9 @@ int GpuFlatIndex::filter_create(const uint64_t* ids, uint64_t n_ids, uint64_t* o
     if (!f->ids.empty()) {
         VL_TRY(dev_alloc(&f->d_ids, f->ids.size()));
         VL_HIP(hipMemcpy(f->d_ids, f->ids.data(), f->ids.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-        VL_TRY(dev_alloc(&f->d_counts, (size_t)FILTER_COUNTS_MAX + 1));
     }
+    // (an empty exclusion set still resolves on the device: every row qualifies, and rows come and go)
+    if (!f->ids.empty() || exclude) VL_TRY(dev_alloc(&f->d_counts, (size_t)FILTER_COUNTS_MAX + 1));
     uint64_t rows = 0;
     {
         std::shared_lock<RwLock> lk(mu_);
@@ -1741,6 +1770,11 @@ int GpuFlatIndex::filter_positions(uint64_t token, std::shared_ptr<IdFilter>* ke
         if (lease.status() != OK) return lease.status();
         VL_TRY(lease.done(resolve_filter(lease.ws, f.get())));
     }
+    if (!f->plist_built) {
+        WsLease lease(this);
+        if (lease.status() != OK) return lease.status();
+        VL_TRY(lease.done(ensure_plist(lease.ws, f.get())));
+    }
     *d_plist = f->d_plist;
     *m = f->m;
     *keep = std::move(f);
@@ -1749,16 +1783,19 @@ int GpuFlatIndex::filter_positions(uint64_t token, std::shared_ptr<IdFilter>* ke
 
 // positions p < len() whose ids_[p] is in f->ids -> f->d_plist[0..m), ascending.  Two launches, one 4-byte read-back (m, which
 // sizes the list and the scan's grid), one launch; nothing per row crosses PCIe.
+// An exclusion filter: the same count with the predicate inverted, then the keep bitmap (k_filter_bits); the list waits for
+// ensure_plist.  Its empty id set resolves like any other: nf = 0 never reads the set.
 int GpuFlatIndex::resolve_filter(Workspace* ws, IdFilter* f) const
 {
     const uint64_t n = ids_.size();
     f->m = 0;
     f->h_plist_valid = false;
+    f->plist_built = !f->exclude;
     f->resolved_at = ~0ull;
-    if (n != 0 && !f->ids.empty()) {
+    if (n != 0 && (!f->ids.empty() || f->exclude)) {
         hipStream_t st = ws->stream;
         VL_TRY(ensure_device_ids());
-        VL_HIP(launch_filter_count(st, d_ids_, n, f->d_ids, f->ids.size(), f->d_counts, f->d_counts + FILTER_COUNTS_MAX));
+        VL_HIP(launch_filter_count(st, d_ids_, n, f->d_ids, f->ids.size(), f->d_counts, f->d_counts + FILTER_COUNTS_MAX, f->exclude));
         uint32_t m = 0;
         VL_HIP(hipMemcpyAsync(&m, f->d_counts + FILTER_COUNTS_MAX, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         VL_HIP(hipStreamSynchronize(st));
@@ -1766,14 +1803,36 @@ int GpuFlatIndex::resolve_filter(Workspace* ws, IdFilter* f) const
             set_last_error("filter resolution counted more rows than the index holds (kernel bug)");
             return ERR_DEVICE;
         }
-        VL_TRY(grow(HipMem{}, f->plist_cap, m, {dev_buf(f->d_plist, m)}));
-        if (m) {
-            VL_HIP(launch_filter_compact(st, d_ids_, n, f->d_ids, f->ids.size(), f->d_counts, m, f->d_plist));
+        if (f->exclude) {
+            const uint64_t words = (n + 63) / 64;
+            VL_TRY(grow(HipMem{}, f->keep_cap, words, {dev_buf(f->d_keep, words)}));
+            VL_HIP(launch_filter_bits(st, d_ids_, n, f->d_ids, f->ids.size(), f->d_keep));
             VL_HIP(hipStreamSynchronize(st));
+        } else {
+            VL_TRY(grow(HipMem{}, f->plist_cap, m, {dev_buf(f->d_plist, m)}));
+            if (m) {
+                VL_HIP(launch_filter_compact(st, d_ids_, n, f->d_ids, f->ids.size(), f->d_counts, m, f->d_plist));
+                VL_HIP(hipStreamSynchronize(st));
+            }
         }
         f->m = m;
     }
     f->resolved_at = mutations_;
+    return OK;
+}
+
+// The position list of an exclusion filter, on the first call that needs one after a resolution: k_filter_compact with the
+// inverted predicate, at the offsets the resolution's count left in d_counts.
+int GpuFlatIndex::ensure_plist(Workspace* ws, IdFilter* f) const
+{
+    if (f->plist_built) return OK;
+    const uint64_t n = ids_.size(), m = f->m;
+    VL_TRY(grow(HipMem{}, f->plist_cap, m, {dev_buf(f->d_plist, m)}));
+    if (n != 0 && m != 0) {
+        VL_HIP(launch_filter_compact(ws->stream, d_ids_, n, f->d_ids, f->ids.size(), f->d_counts, m, f->d_plist, true));
+        VL_HIP(hipStreamSynchronize(ws->stream));
+    }
+    f->plist_built = true;
     return OK;
 }
 
@@ -1788,10 +1847,24 @@ int GpuFlatIndex::search_filtered(uint64_t token, const double* query, uint64_t 
     VL_TRY(lock_for_query(metric, q_len, &lk));  // the whole index's length check, even when the subset is empty
     if (ids_.empty() || k == 0) return OK;
     if ((!query && dim_) || !out_scores) return ERR_INVALID_ARG;
+    // An exclusion filter leaves almost every row in play: where the single-query ladder's conditions hold (and the f32
+    // stride is one the masked scan is compiled for) it runs that ladder under the keep bitmap and needs no list.
+    const bool ladder = f->exclude && force_path_.load() == 0 && n_out_of_domain_ == 0 && scan_masked_supported(ld_);
     return run_search(nullptr, f.get(), [&](Workspace* ws) -> int {
         if (f->m == 0) return OK;
-        return search_subset(ws, f.get(), query, std::min<uint64_t>(k, f->m), metric, out_pos, out_ids, out_scores, out_n);
-    });
+        const uint64_t k_eff = std::min<uint64_t>(k, f->m);
+        bool uncertified = false;
+        if (ladder && k_eff <= (uint64_t)KFAST_MAX) {
+            const int rc = search_locked(ws, query, k_eff, metric, out_pos, out_ids, out_scores, out_n, false, false, nullptr, f.get());
+            if (rc != MASK_UNCERTIFIED) return rc;
+            uncertified = true;  // no masked stage certified it (or the query is out of the domain): the exact kernels
+        }
+        if (f->exclude) {
+            std::lock_guard<std::mutex> fg(f->mu);
+            VL_TRY(ensure_plist(ws, f.get()));
+        }
+        return search_subset(ws, f.get(), query, k_eff, metric, out_pos, out_ids, out_scores, out_n, nullptr, uncertified);
+    }, /*need_list=*/!f->exclude);
 }
 
 int GpuFlatIndex::search_subset(Workspace* ws, IdFilter* f, const double* query, uint64_t k_eff, int metric,

@@ -157,14 +157,21 @@ struct WorkspacePool {
 // An id filter of one single-GPU flat handle (vl_index_filter_create): the caller's ids, sorted and deduplicated, and -- resolved
 // against the rows as they stood when the handle's mutation count was `resolved_at` -- the ascending storage positions of
 // every row whose id is in the set.  A search that finds the count moved on resolves it again first.
+// An EXCLUSION filter (vl_index_filter_create_excluding) qualifies the rows whose id is NOT in the set.
+// Its resolution is the count m and a keep bitmap over storage positions; the position list is built by the first call
+// that needs one after a resolution (ensure_plist), the masked single-query ladder never does.
 struct IdFilter {
     std::mutex mu;                         // guards everything below (taken after the index lock)
     int device = 0;
+    bool exclude = false;                  // the kind: set at creation, never changes
     std::vector<uint64_t> ids;             // sorted, unique
     unsigned long long* d_ids = nullptr;   // the same on the device
     uint32_t* d_counts = nullptr;          // [FILTER_COUNTS_MAX + 1] resolution scratch: per-chunk offsets, then m
     uint32_t* d_plist = nullptr;           // [plist_cap] positions of the qualifying rows, ascending
     uint64_t plist_cap = 0;
+    bool plist_built = true;               // d_plist[0..m) belongs to this resolution (an exclusion filter: false until asked for)
+    unsigned long long* d_keep = nullptr;  // exclusion only: [keep_cap] words, bit p & 63 of word p >> 6 set iff row p qualifies
+    uint64_t keep_cap = 0;
     uint64_t m = 0;                        // qualifying rows
     uint64_t resolved_at = ~0ull;          // the handle's mutation count the list belongs to (none yet)
     std::vector<uint32_t> h_plist;         // host copy of the list (the exact path maps its winners back), made on demand
@@ -268,7 +275,8 @@ public:
     // NEW (no reference counterpart): search restricted to the rows whose id is in a set.  The answer is exactly what
     // FlatIndex::search returns on a FlatIndex holding only those rows, in their storage order.  A filter is a token of this
     // handle (never 0, never reused); ids may be unsorted and repeat; ids the index does not hold are ignored.
-    int filter_create(const uint64_t* ids, uint64_t n_ids, uint64_t* out_token, uint64_t* out_rows);
+    // exclude: the rows whose id is NOT in the set qualify (n_ids = 0 keeps every row; an id added later is excluded then)
+    int filter_create(const uint64_t* ids, uint64_t n_ids, uint64_t* out_token, uint64_t* out_rows, bool exclude = false);
     int filter_rows(uint64_t token, uint64_t* out_rows) const;  // resolves the filter again if rows changed since
     int filter_destroy(uint64_t token);
     // for the HNSW graph layered on this row store (hnsw_index.cpp): the filter's ascending position list on the device,
@@ -366,6 +374,9 @@ public:
         i8_fails_.store(0);
         auto_window_.reset();
         i8_window_.reset();
+        for (auto* c : {&mask_bf16_tries_, &mask_bf16_fails_, &mask_i8_tries_, &mask_i8_fails_}) c->store(0);
+        mask_bf16_window_.reset();
+        mask_i8_window_.reset();
         auto_unavailable_.store(false);
         i8_unavailable_.store(false);
     }
@@ -419,8 +430,10 @@ private:
     // mu_ held (shared): leases a workspace, resolves t and f (either may be null) if rows changed since, runs body(ws) as one
     // of the handle's searches in flight
     template <typename Body>
-    int run_search(GroupTable* t, IdFilter* f, Body&& body) const;
-    int resolve_if_stale(Workspace* ws, IdFilter* f) const;    // takes f->mu
+    int run_search(GroupTable* t, IdFilter* f, Body&& body, bool need_list = true) const;
+    // takes f->mu; need_list: the caller reads f->d_plist (an exclusion filter builds it then, once per resolution)
+    int resolve_if_stale(Workspace* ws, IdFilter* f, bool need_list = true) const;
+    int ensure_plist(Workspace* ws, IdFilter* f) const;  // mu_ held, f->mu held, f resolved
     int resolve_if_stale(Workspace* ws, GroupTable* t) const;  // takes t->rows.mu
     int account_profile(Workspace* ws, uint64_t bytes, uint64_t passes = 1) const;  // the scan between ws->ev0 and ws->ev1
     void note_scan(int variant, int grid, bool qarg) const
@@ -437,17 +450,22 @@ private:
     // skip_bf16: the query already failed a bf16 filter's certification (an MFMA batch straggler): neither the int8 nor the
     // bf16 stage, straight to k_scan
     // mmr != nullptr (search_mmr): k_eff = the candidates to fetch; the outputs receive mmr->k_out selected entries
+    // mask != nullptr (search_filtered with an exclusion filter): the ladder runs its masked launchers over the whole slab,
+    // certifies against the mask's m rows with switches and counters of its own, and returns MASK_UNCERTIFIED -- with
+    // nothing written -- where no stage certified: the caller then takes the list route.  k_eff <= mask->m.
+    static constexpr int MASK_UNCERTIFIED = -1000;  // never leaves flat_index.cpp
     int search_locked(Workspace* ws, const double* query, uint64_t k_eff, int metric, uint64_t* out_pos,
                       uint64_t* out_ids, double* out_scores, uint64_t* out_n, bool skip_fast, bool skip_bf16 = false,
-                      const MmrReq* mmr = nullptr) const;
+                      const MmrReq* mmr = nullptr, const IdFilter* mask = nullptr) const;
     // the selection's two launches behind a search's last kernel (ws->h_result receives the answer; seq != 0: stamped)
     int mmr_tail(Workspace* ws, int metric, const MmrReq& m, MmrSource src, uint32_t seq) const;
     int mmr_take(Workspace* ws, const MmrReq& m, uint64_t* out_pos, uint64_t* out_ids, double* out_scores,
                  uint64_t* out_n) const;
-    bool bf16_first(uint64_t n) const;        // does this single search try the bf16 filter (after the int8 one)
-    void bf16_outcome(bool certified) const;  // records one try of the bf16 filter
-    bool i8_first(uint64_t n) const;          // does this single search try the int8 filter first
-    void i8_outcome(bool certified) const;    // records one try of the int8 filter
+    // masked: the masked ladder's own windows and counters (the mode and the floors are shared)
+    bool bf16_first(uint64_t n, bool masked = false) const;        // does this single search try the bf16 filter (after the int8 one)
+    void bf16_outcome(bool certified, bool masked = false) const;  // records one try of the bf16 filter
+    bool i8_first(uint64_t n, bool masked = false) const;          // does this single search try the int8 filter first
+    void i8_outcome(bool certified, bool masked = false) const;    // records one try of the int8 filter
     // plist != nullptr: the n rows are plist[0..n) (a filter's subset) and pos[] returns indices into that list
     // mmr != nullptr: the selection runs behind the ranking and pos / scores stay untouched (mmr_take reads the answer)
     int run_exact(Workspace* ws, int metric, uint64_t n, uint64_t k_eff, std::vector<uint32_t>* pos,
@@ -552,6 +570,10 @@ private:
     uint64_t i8_min_bytes_ = SINGLE_FILTER_I8_MIN_BYTES;
     mutable AutoFilterWindow i8_window_;
     mutable std::atomic<bool> i8_unavailable_{false};  // the int8 copy could not be allocated: auto goes on to bf16
+    // the masked ladder's (an exclusion filter's single searches) windows and mode-1 / mode-3 counters: what it certifies
+    // depends on what was excluded, so it neither reads nor feeds the unfiltered ladder's
+    mutable AutoFilterWindow mask_bf16_window_, mask_i8_window_;
+    mutable std::atomic<uint64_t> mask_bf16_tries_{0}, mask_bf16_fails_{0}, mask_i8_tries_{0}, mask_i8_fails_{0};
     std::atomic<bool> profile_{false};
     // single searches in flight on this handle: up to SPIN_MAX_SEARCHERS of them poll their result stamp,
     // more than that sleep in hipStreamSynchronize (wait_result)

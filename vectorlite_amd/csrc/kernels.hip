@@ -168,6 +168,30 @@ __global__ __launch_bounds__(256) void k_scan_q64(const f32x4* __restrict__ slab
     scan_stream<G, U>(F32Rows<METRIC, VPL>{slab, inv_norm}, qv, AllRows{}, n, TopSink(out));
 }
 
+// K1 under an exclusion filter's keep bitmap: every row is streamed and scored as in k_scan, a row
+// whose bit is 0 is never offered.  Compiled for the default shape of each stride (k_scan_subset's rule): the query in the
+// kernel arguments, or -- strides past the kernel-argument query -- the f64 query in device memory (k_scan_q64's form).
+template <int METRIC, int G, int VPL, int U>
+__global__ __launch_bounds__(256) void k_scan_masked(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
+                                                     const unsigned long long* __restrict__ keep, uint32_t n,
+                                                     Cand32* __restrict__ out, const ScanQArg qa)
+{
+    f32x4 qv[VPL];
+    load_query<G>(qv, qa);
+    scan_stream<G, U>(F32Rows<METRIC, VPL>{slab, inv_norm}, qv, MaskedRows{keep}, n, TopSink(out));
+}
+
+template <int METRIC, int G, int VPL, int U>
+__global__ __launch_bounds__(256) void k_scan_masked_q64(const f32x4* __restrict__ slab, const float* __restrict__ inv_norm,
+                                                         const unsigned long long* __restrict__ keep,
+                                                         const double* __restrict__ q64, uint32_t dim, uint32_t n,
+                                                         Cand32* __restrict__ out)
+{
+    f32x4 qv[VPL];
+    load_query<G>(qv, q64, dim);
+    scan_stream<G, U>(F32Rows<METRIC, VPL>{slab, inv_norm}, qv, MaskedRows{keep}, n, TopSink(out));
+}
+
 // Generic: any ld4 (float4 per row), G = lanes per row (power of two <= 64), one row group per step, the query read
 // as it is needed.  scan_stream()'s row sources and sinks; the same acc4 column order, group_reduce and scan_key, so a
 // row's key does not depend on which of the three families scores it.  A listed row's entry for the NEXT step is
@@ -280,6 +304,7 @@ __global__ __launch_bounds__(256) void k_scan_subset_jobs_generic(const f32x4* _
 // Resolution of an id filter: which storage positions hold an id of the sorted, deduplicated set fids[0..nf).  Workgroup b
 // owns positions [b chunk, (b+1) chunk); pass 1 counts its matches, one workgroup turns the counts into offsets (and m), pass 2
 // writes the matching positions of each chunk in ascending order at its offset: the list comes out ascending.
+// `invert` (an exclusion filter): a position qualifies iff its id is NOT in the set; nf may then be 0 (fids is not read).
 __device__ __forceinline__ bool id_in_set(unsigned long long id, const unsigned long long* __restrict__ fids, uint32_t nf)
 {
     uint32_t lo = 0, hi = nf;  // lower_bound
@@ -295,13 +320,13 @@ constexpr int FILTER_MAX_GRID = FILTER_COUNTS_MAX;
 
 __global__ __launch_bounds__(256) void k_filter_count(const unsigned long long* __restrict__ pos_ids, uint32_t n,
                                                       const unsigned long long* __restrict__ fids, uint32_t nf,
-                                                      uint32_t chunk, uint32_t* __restrict__ counts)
+                                                      uint32_t chunk, uint32_t* __restrict__ counts, uint32_t invert)
 {
     __shared__ uint32_t sh_cnt[4];
     const uint32_t lo = blockIdx.x * chunk;
     const uint32_t hi = (uint64_t)lo + chunk < n ? lo + chunk : n;
     uint32_t cnt = 0;
-    for (uint32_t p = lo + threadIdx.x; p < hi; p += 256) cnt += id_in_set(pos_ids[p], fids, nf) ? 1u : 0u;
+    for (uint32_t p = lo + threadIdx.x; p < hi; p += 256) cnt += (id_in_set(pos_ids[p], fids, nf) != (invert != 0)) ? 1u : 0u;
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
     if (lane_id() == 0) sh_cnt[threadIdx.x >> 6] = cnt;
@@ -330,7 +355,7 @@ __global__ __launch_bounds__(FILTER_MAX_GRID) void k_filter_scan(uint32_t* __res
 __global__ __launch_bounds__(256) void k_filter_compact(const unsigned long long* __restrict__ pos_ids, uint32_t n,
                                                         const unsigned long long* __restrict__ fids, uint32_t nf,
                                                         uint32_t chunk, const uint32_t* __restrict__ offsets,
-                                                        uint32_t m_cap, uint32_t* __restrict__ plist)
+                                                        uint32_t m_cap, uint32_t* __restrict__ plist, uint32_t invert)
 {
     __shared__ uint32_t sh_cnt[4];
     const int lane = lane_id(), wave = threadIdx.x >> 6;
@@ -339,7 +364,7 @@ __global__ __launch_bounds__(256) void k_filter_compact(const unsigned long long
     uint32_t base = offsets[blockIdx.x];
     for (uint32_t t0 = lo; t0 < hi; t0 += 256) {  // block-uniform trip count
         const uint32_t p = t0 + threadIdx.x;
-        const bool hit = p < hi && id_in_set(pos_ids[p], fids, nf);
+        const bool hit = p < hi && (id_in_set(pos_ids[p], fids, nf) != (invert != 0));
         const unsigned long long bal = __ballot(hit);
         if (lane == 0) sh_cnt[wave] = (uint32_t)__popcll(bal);
         __syncthreads();
@@ -350,6 +375,23 @@ __global__ __launch_bounds__(256) void k_filter_compact(const unsigned long long
         if (hit && base + rank < m_cap) plist[base + rank] = p;
         base += total;
         __syncthreads();  // sh_cnt is rewritten by the next tile
+    }
+}
+
+// The keep bitmap of an exclusion filter: bit p & 63 of keep[p >> 6] is set iff p < n and ids[p] is NOT in the set.  One
+// wave per word: the 64 lanes ballot their rows' membership, lane 0 stores the inverted word (bits at or past n are 0).
+__global__ __launch_bounds__(256) void k_filter_bits(const unsigned long long* __restrict__ pos_ids, uint32_t n,
+                                                     const unsigned long long* __restrict__ fids, uint32_t nf,
+                                                     uint32_t n_words, unsigned long long* __restrict__ keep)
+{
+    const int lane = lane_id();
+    const uint32_t n_waves = gridDim.x * 4;
+    for (uint32_t w = blockIdx.x * 4 + (threadIdx.x >> 6); w < n_words; w += n_waves) {  // wave-uniform trip count
+        const uint32_t p = w * 64u + (uint32_t)lane;
+        const bool there = p < n;
+        const bool in_set = there && id_in_set(pos_ids[p], fids, nf);
+        const unsigned long long word = __ballot(there) & ~__ballot(in_set);
+        if (lane == 0) keep[w] = word;
     }
 }
 
@@ -2477,6 +2519,51 @@ hipError_t launch_scan_subset(hipStream_t s, int metric, const float* slab, cons
     return rc;
 }
 
+// The masked scan: the default shape of a stride VL_SCAN_VARIANTS specialises (scan_masked_supported(ld)), the query as
+// launch_scan_subset takes it; the grid is k_scan's, sized from n.
+bool scan_masked_supported(uint32_t ld) { return !(ld & 3) && default_scan_shape(ld / 4).special; }
+
+hipError_t launch_scan_masked(hipStream_t s, int metric, const float* slab, const float* inv_norm, const unsigned long long* keep,
+                              uint64_t n, const double* q64, uint32_t dim, uint32_t ld, Cand32* partials, ScanPlan* plan,
+                              const float* q32_host)
+{
+    if (n == 0 || n >= 0xFFFFFFFFull || !keep || !scan_masked_supported(ld)) return hipErrorInvalidValue;
+    const ScanShape sh = default_scan_shape(ld / 4);
+    const f32x4* slab4 = reinterpret_cast<const f32x4*>(slab);
+    const bool qarg = shape_takes_qarg(sh, ld, q32_host);
+    if (!qarg && (!q64 || ld <= (uint32_t)SCAN_QARG_FLOATS)) return hipErrorInvalidValue;
+    int grid = 0;
+    hipError_t rc = dispatch_metric(metric, [&](auto M) -> hipError_t {
+        constexpr int MM = decltype(M)::value;
+        bool launched = false;
+#define VL_TRY_VARIANT(G, VPL, U, BPC)                                                                                   \
+    if constexpr (is_default_scan_shape(G, VPL, U)) {                                                                    \
+        if (!launched && sh.g == G && sh.vpl == VPL && sh.u == U) {                                                      \
+            if constexpr (G * VPL * 4 <= SCAN_QARG_FLOATS) {                                                             \
+                ScanQArg qa;                                                                                             \
+                memcpy(qa.v, q32_host, (size_t)ld * sizeof(float));                                                      \
+                grid = scan_grid(n, sh, reinterpret_cast<const void*>(k_scan_masked<MM, G, VPL, U>));                    \
+                hipLaunchKernelGGL((k_scan_masked<MM, G, VPL, U>), dim3(grid), dim3(256), 0, s, slab4, inv_norm, keep,   \
+                                   (uint32_t)n, partials, qa);                                                           \
+            } else {                                                                                                     \
+                grid = scan_grid(n, sh, reinterpret_cast<const void*>(k_scan_masked_q64<MM, G, VPL, U>));                \
+                hipLaunchKernelGGL((k_scan_masked_q64<MM, G, VPL, U>), dim3(grid), dim3(256), 0, s, slab4, inv_norm,     \
+                                   keep, q64, dim, (uint32_t)n, partials);                                               \
+            }                                                                                                            \
+            launched = true;                                                                                             \
+        }                                                                                                                \
+    }
+        VL_SCAN_VARIANTS(VL_TRY_VARIANT)
+#undef VL_TRY_VARIANT
+        return launched ? hipGetLastError() : hipErrorInvalidValue;
+    });
+    if (plan) {
+        plan->grid = grid;
+        plan->variant = MASK_VARIANT_BASE + sh.g * 10000 + sh.vpl * 100 + sh.u;
+    }
+    return rc;
+}
+
 namespace {
 // The jobs scan of a shape: fn(kernel, std::true_type) for the stride's default shape, fn(kernel, std::false_type) for the
 // generic kernel (which takes ld4 as well).
@@ -2582,24 +2669,35 @@ int filter_grid_for(uint64_t n, uint32_t* chunk)
 }
 
 hipError_t launch_filter_count(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
-                               uint64_t nf, uint32_t* counts, uint32_t* m_out)
+                               uint64_t nf, uint32_t* counts, uint32_t* m_out, bool invert)
 {
-    if (n == 0 || n >= 0xFFFFFFFFull || nf == 0 || nf >= 0xFFFFFFFFull) return hipErrorInvalidValue;
+    if (n == 0 || n >= 0xFFFFFFFFull || (nf == 0 && !invert) || nf >= 0xFFFFFFFFull) return hipErrorInvalidValue;
     uint32_t chunk = 0;
     const int grid = filter_grid_for(n, &chunk);
-    hipLaunchKernelGGL(k_filter_count, dim3(grid), dim3(256), 0, s, pos_ids, (uint32_t)n, fids, (uint32_t)nf, chunk, counts);
+    hipLaunchKernelGGL(k_filter_count, dim3(grid), dim3(256), 0, s, pos_ids, (uint32_t)n, fids, (uint32_t)nf, chunk, counts,
+                       invert ? 1u : 0u);
     hipLaunchKernelGGL(k_filter_scan, dim3(1), dim3(FILTER_MAX_GRID), 0, s, counts, (uint32_t)grid, m_out);
     return hipGetLastError();
 }
 
 hipError_t launch_filter_compact(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
-                                 uint64_t nf, const uint32_t* offsets, uint64_t m, uint32_t* plist)
+                                 uint64_t nf, const uint32_t* offsets, uint64_t m, uint32_t* plist, bool invert)
 {
-    if (n == 0 || n >= 0xFFFFFFFFull || nf == 0 || nf >= 0xFFFFFFFFull || m == 0) return hipErrorInvalidValue;
+    if (n == 0 || n >= 0xFFFFFFFFull || (nf == 0 && !invert) || nf >= 0xFFFFFFFFull || m == 0) return hipErrorInvalidValue;
     uint32_t chunk = 0;
     const int grid = filter_grid_for(n, &chunk);
     hipLaunchKernelGGL(k_filter_compact, dim3(grid), dim3(256), 0, s, pos_ids, (uint32_t)n, fids, (uint32_t)nf, chunk, offsets,
-                       (uint32_t)m, plist);
+                       (uint32_t)m, plist, invert ? 1u : 0u);
+    return hipGetLastError();
+}
+
+hipError_t launch_filter_bits(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
+                              uint64_t nf, unsigned long long* keep)
+{
+    if (n == 0 || n >= 0xFFFFFFFFull || nf >= 0xFFFFFFFFull) return hipErrorInvalidValue;
+    const uint64_t n_words = (n + 63) / 64;
+    const int grid = (int)std::min<uint64_t>((n_words + 3) / 4, FILTER_MAX_GRID);
+    hipLaunchKernelGGL(k_filter_bits, dim3(grid), dim3(256), 0, s, pos_ids, (uint32_t)n, fids, (uint32_t)nf, (uint32_t)n_words, keep);
     return hipGetLastError();
 }
 

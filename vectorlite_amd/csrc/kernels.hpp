@@ -201,10 +201,24 @@ hipError_t launch_exact_scan_subset(hipStream_t s, int metric, const double* mas
 // matches per chunk of positions and turns the counts into offsets, *m_out = total (counts: FILTER_COUNTS_MAX words); step 2
 // writes the m matching positions in ascending order into plist[0..m).
 constexpr int FILTER_COUNTS_MAX = 1024;
+// invert (an exclusion filter): a position matches iff its id is NOT in the set; nf may then be 0.
 hipError_t launch_filter_count(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
-                               uint64_t nf, uint32_t* counts, uint32_t* m_out);
+                               uint64_t nf, uint32_t* counts, uint32_t* m_out, bool invert = false);
 hipError_t launch_filter_compact(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
-                                 uint64_t nf, const uint32_t* offsets, uint64_t m, uint32_t* plist);
+                                 uint64_t nf, const uint32_t* offsets, uint64_t m, uint32_t* plist, bool invert = false);
+// An exclusion filter's keep bitmap: keep[0..(n + 63) / 64), bit p & 63 of word p >> 6 set iff p < n
+// and pos_ids[p] is not in the set (nf may be 0: every row kept).
+hipError_t launch_filter_bits(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
+                              uint64_t nf, unsigned long long* keep);
+// K1 under a keep bitmap: launch_scan's partial lists without the rows whose bit is 0, on launch_scan's grid (sized from n).
+// Only at the strides VL_SCAN_VARIANTS specialises (scan_masked_supported(ld)), the stride's default shape; the query as
+// launch_scan_subset takes it (q32_host where scan_takes_qarg(ld), else q64 in device memory).
+// plan->variant = MASK_VARIANT_BASE + G * 10000 + VPL * 100 + U.
+constexpr int MASK_VARIANT_BASE = 7000000;
+bool scan_masked_supported(uint32_t ld);
+hipError_t launch_scan_masked(hipStream_t s, int metric, const float* slab, const float* inv_norm, const unsigned long long* keep,
+                              uint64_t n, const double* q64, uint32_t dim, uint32_t ld, Cand32* partials, ScanPlan* plan,
+                              const float* q32_host = nullptr);
 
 // Range search (score >= min_score).  ctr: RANGE_CTR_WORDS words of device memory, zeroed by the
 // caller in front of each sequence: [APPENDED] rows the scan appended (it keeps counting past the buffer), [TOTAL] rows

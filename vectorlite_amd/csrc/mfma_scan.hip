@@ -1059,6 +1059,24 @@ __global__ __launch_bounds__(256) void k_scan_bf16_qarg(const u32x4* __restrict_
     scan_stream<G, U>(Bf16Rows<METRIC, VPL>{slab16, row_nrm, row_sqn}, qv, AllRows{}, n, TopSink(out));
 }
 
+// The same under an exclusion filter's keep bitmap (MaskedRows): the stride's first listed shape only.
+template <int METRIC, int G, int VPL, int U>
+__global__ __launch_bounds__(256) void k_scan_bf16_masked(const u32x4* __restrict__ slab16, const float* __restrict__ row_nrm,
+                                                          const float* __restrict__ row_sqn,
+                                                          const unsigned long long* __restrict__ keep, uint32_t n,
+                                                          Cand32* __restrict__ out, const Scan16QArg qa)
+{
+    static_assert(G * VPL * 8 <= SCAN16_QARG_FLOATS, "row too long for the kernarg query");
+    const int c = lane_id() % G;
+    f32x4 qv[VPL][2];
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+        qv[j][0] = *reinterpret_cast<const f32x4*>(&qa.v[8 * (c + G * j)]);
+        qv[j][1] = *reinterpret_cast<const f32x4*>(&qa.v[8 * (c + G * j) + 4]);
+    }
+    scan_stream<G, U>(Bf16Rows<METRIC, VPL>{slab16, row_nrm, row_sqn}, qv, MaskedRows{keep}, n, TopSink(out));
+}
+
 // ---------------------------------------------------------------------------------------------
 // Single-query scan of the int8 copy (the first stage of the single-query ladder: a quarter of the f32 slab's bytes):
 // scan_stream() over rows of 16 bytes per chunk.
@@ -1145,6 +1163,24 @@ __global__ __launch_bounds__(256) void k_scan_i8_qarg(const u32x4* __restrict__ 
         qv[j][1] = *reinterpret_cast<const u32x4*>(&qa.h[8 * (c + G * j) + 4]);
     }
     scan_stream<G, U>(I8Rows<METRIC, VPL>{slab8, row_sr, row_nrm, qa.inv_scale, qa.qd, qa.d}, qv, AllRows{}, n, TopSink(out));
+}
+
+// The same under an exclusion filter's keep bitmap (MaskedRows): the stride's first listed shape only.
+template <int METRIC, int G, int VPL, int U>
+__global__ __launch_bounds__(256) void k_scan_i8_masked(const u32x4* __restrict__ slab8, const float2* __restrict__ row_sr,
+                                                        const float* __restrict__ row_nrm,
+                                                        const unsigned long long* __restrict__ keep, uint32_t n,
+                                                        Cand32* __restrict__ out, const Scan8QArg qa)
+{
+    static_assert(G * VPL * 16 <= SCAN8_QARG_HALVES, "row too long for the kernarg query");
+    const int c = lane_id() % G;
+    u32x4 qv[VPL][2];
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+        qv[j][0] = *reinterpret_cast<const u32x4*>(&qa.h[8 * (c + G * j)]);
+        qv[j][1] = *reinterpret_cast<const u32x4*>(&qa.h[8 * (c + G * j) + 4]);
+    }
+    scan_stream<G, U>(I8Rows<METRIC, VPL>{slab8, row_sr, row_nrm, qa.inv_scale, qa.qd, qa.d}, qv, MaskedRows{keep}, n, TopSink(out));
 }
 
 // T_q = the 64th largest group maximum (a lower bound of the query's 64th best key); -inf when fewer
@@ -2093,7 +2129,7 @@ RowScanPlan plan_row_scan(const int (*shapes)[3], int n_shapes, uint32_t ldc, ui
                           const char* bpc_env, int bpc_default, int variant_base)
 {
     int want[3] = {0, 0, 0};
-    if (const char* se = getenv(shape_env)) {
+    if (const char* se = shape_env ? getenv(shape_env) : nullptr) {  // (no variable: the stride's first listed shape)
         if (sscanf(se, "%d,%d,%d", &want[0], &want[1], &want[2]) != 3) want[0] = 0;
     }
     int pick = -1;
@@ -2117,6 +2153,15 @@ RowScanPlan plan_row_scan(const int (*shapes)[3], int n_shapes, uint32_t ldc, ui
     if (blocks > (uint64_t)(cus * bpc)) blocks = (uint64_t)(cus * bpc);
     if (blocks > (uint64_t)SCAN_MAX_GRID) blocks = SCAN_MAX_GRID;
     return {g, vpl, u, (int)(blocks < 1 ? 1 : blocks), variant_base + g * 10000 + vpl * 100 + u};
+}
+
+// is (g, vpl, u) the first listed shape of its stride (what the masked scans compile)
+template <int N>
+constexpr bool first_listed_shape(const int (&shapes)[N][3], int g, int vpl, int u)
+{
+    for (int i = 0; i < N; ++i)
+        if (shapes[i][0] * shapes[i][1] == g * vpl) return shapes[i][0] == g && shapes[i][1] == vpl && shapes[i][2] == u;
+    return false;
 }
 
 bool row_scan_listed(const int (*shapes)[3], int n_shapes, uint32_t ldc)
@@ -2185,6 +2230,42 @@ hipError_t launch_scan_bf16(hipStream_t s, int metric, const void* slab_bf16, co
         if (metric == COSINE) VL_L3(COSINE, G, VPL, U)                                              \
         else if (metric == EUCLIDEAN) VL_L3(EUCLIDEAN, G, VPL, U)                                   \
         else VL_L3(DOT, G, VPL, U)                                                                  \
+    }
+    VL_BF16_SCAN_SHAPES(VL_L)
+#undef VL_L
+#undef VL_L3
+    if (!launched) return hipErrorInvalidValue;
+    if (grid_out) *grid_out = p.grid;
+    if (variant_out) *variant_out = p.variant;
+    return hipGetLastError();
+}
+
+hipError_t launch_scan_bf16_masked(hipStream_t s, int metric, const void* slab_bf16, const float* row_norm,
+                                   const float* row_sqnorm, const unsigned long long* keep, uint64_t n, uint32_t dim,
+                                   Cand32* partials, int* grid_out, const float* q32_host, int* variant_out)
+{
+    if (n == 0 || n >= 0xFFFFFFFFull || !keep || !q32_host || !scan_bf16_supported(dim, metric)) return hipErrorInvalidValue;
+    const uint32_t ldb = mfma_ldb(dim), ld8 = ldb / 8;
+    if (ldb > (uint32_t)SCAN16_QARG_FLOATS) return hipErrorInvalidValue;
+    const u32x4* slab = reinterpret_cast<const u32x4*>(slab_bf16);
+    const RowScanPlan p = plan_row_scan(BF16_SCAN_SHAPES, N_BF16_SCAN_SHAPES, ld8, n, nullptr, "VL_SCAN16_BPC",
+                                        ld8 >= 96 ? SCAN16_BPC_LONG : SCAN16_BPC, MASK16_VARIANT_BASE);
+    bool launched = false;
+    Scan16QArg qa;
+    memcpy(qa.v, q32_host, (size_t)ldb * sizeof(float));
+#define VL_L3(MET, G, VPL, U)                                                                                          \
+    {                                                                                                                  \
+        hipLaunchKernelGGL((k_scan_bf16_masked<MET, G, VPL, U>), dim3(p.grid), dim3(256), 0, s, slab, row_norm,        \
+                           row_sqnorm, keep, (uint32_t)n, partials, qa);                                               \
+        launched = true;                                                                                               \
+    }
+#define VL_L(G, VPL, U)                                                                             \
+    if constexpr (first_listed_shape(BF16_SCAN_SHAPES, G, VPL, U)) {                                \
+        if (!launched && p.g == G && p.vpl == VPL && p.u == U) {                                    \
+            if (metric == COSINE) VL_L3(COSINE, G, VPL, U)                                          \
+            else if (metric == EUCLIDEAN) VL_L3(EUCLIDEAN, G, VPL, U)                               \
+            else VL_L3(DOT, G, VPL, U)                                                              \
+        }                                                                                           \
     }
     VL_BF16_SCAN_SHAPES(VL_L)
 #undef VL_L
@@ -2289,6 +2370,45 @@ hipError_t launch_scan_i8(hipStream_t s, int metric, const void* slab_i8, const 
     if (!launched && p.g == G && p.vpl == VPL && p.u == U) {                                        \
         if (metric == COSINE) VL_L3(COSINE, G, VPL, U)                                              \
         else VL_L3(DOT, G, VPL, U)                                                                  \
+    }
+    VL_I8_SCAN_SHAPES(VL_L)
+#undef VL_L
+#undef VL_L3
+    if (!launched) return hipErrorInvalidValue;
+    if (grid_out) *grid_out = p.grid;
+    if (variant_out) *variant_out = p.variant;
+    return hipGetLastError();
+}
+
+hipError_t launch_scan_i8_masked(hipStream_t s, int metric, const void* slab_i8, const float* row_sr, const float* row_norm,
+                                 const unsigned long long* keep, const I8Query& q, uint64_t n, uint32_t dim, Cand32* partials,
+                                 int* grid_out, int* variant_out)
+{
+    if (n == 0 || n >= 0xFFFFFFFFull || !keep || !scan_i8_supported(dim, metric)) return hipErrorInvalidValue;
+    const uint32_t ldb = mfma_ldb(dim), ld16 = ldb / 16;
+    const u32x4* slab = reinterpret_cast<const u32x4*>(slab_i8);
+    const float2* sr = reinterpret_cast<const float2*>(row_sr);
+    const RowScanPlan p = plan_row_scan(I8_SCAN_SHAPES, N_I8_SCAN_SHAPES, ld16, n, nullptr, "VL_SCAN8_BPC", SCAN8_BPC,
+                                        MASK8_VARIANT_BASE);
+    bool launched = false;
+    Scan8QArg qa;
+    memset(&qa, 0, sizeof(qa));
+    memcpy(qa.h, q.h, (size_t)ldb * sizeof(uint16_t));
+    qa.inv_scale = q.inv_scale;
+    qa.qd = q.qd;
+    qa.d = q.d;
+#define VL_L3(MET, G, VPL, U)                                                                                       \
+    {                                                                                                               \
+        hipLaunchKernelGGL((k_scan_i8_masked<MET, G, VPL, U>), dim3(p.grid), dim3(256), 0, s, slab, sr, row_norm,   \
+                           keep, (uint32_t)n, partials, qa);                                                        \
+        launched = true;                                                                                            \
+    }
+#define VL_L(G, VPL, U)                                                                             \
+    if constexpr (first_listed_shape(I8_SCAN_SHAPES, G, VPL, U)) {                                  \
+        if (!launched && p.g == G && p.vpl == VPL && p.u == U) {                                    \
+            if (metric == COSINE) VL_L3(COSINE, G, VPL, U)                                          \
+            else VL_L3(DOT, G, VPL, U)                                                              \
+        }                                                                                           \
     }
     VL_I8_SCAN_SHAPES(VL_L)
 #undef VL_L

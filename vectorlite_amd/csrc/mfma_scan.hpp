@@ -160,4 +160,17 @@ hipError_t launch_scan_i8(hipStream_t s, int metric, const void* slab_i8, const 
                           const I8Query& q, uint64_t n, uint32_t dim, Cand32* partials, int* grid_out,
                           int* variant_out = nullptr);
 
+// The two scans under an exclusion filter's keep bitmap (kernels.hpp's launch_filter_bits): the same
+// lists without the rows whose bit is 0, on the same grids (sized from n).  The query in the kernel arguments, the first
+// listed shape of the stride (VL_SCAN16_SHAPE / VL_SCAN8_SHAPE do not apply).  variant_out: MASK16_VARIANT_BASE /
+// MASK8_VARIANT_BASE + G * 10000 + VPL * 100 + U.
+constexpr int MASK16_VARIANT_BASE = 8000000;
+constexpr int MASK8_VARIANT_BASE = 9000000;
+hipError_t launch_scan_bf16_masked(hipStream_t s, int metric, const void* slab_bf16, const float* row_norm,
+                                   const float* row_sqnorm, const unsigned long long* keep, uint64_t n, uint32_t dim,
+                                   Cand32* partials, int* grid_out, const float* q32_host, int* variant_out = nullptr);
+hipError_t launch_scan_i8_masked(hipStream_t s, int metric, const void* slab_i8, const float* row_sr, const float* row_norm,
+                                 const unsigned long long* keep, const I8Query& q, uint64_t n, uint32_t dim, Cand32* partials,
+                                 int* grid_out, int* variant_out = nullptr);
+
 }  // namespace vl

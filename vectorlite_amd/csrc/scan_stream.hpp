@@ -5,7 +5,7 @@
 //   * a ROW FORMAT (F32Rows, Bf16Rows, I8Rows: next to their arithmetic in the two .hip files): what a 16-byte chunk
 //     is, which per-row scalars travel with the row loads, how a chunk meets the lane's query slice, how the reduced
 //     sum becomes a key;
-//   * a ROW SOURCE (AllRows, ListedRows): which storage position step i scores;
+//   * a ROW SOURCE (AllRows, ListedRows, MaskedRows): which storage position step i scores, and whether it may be offered;
 //   * a SINK (TopSink, RangeSink, GroupBestSink): what happens to (key, position, valid).
 // The run-time-stride f32 kernels (k_scan_generic and its subset / range forms) share the sources and sinks through
 // the much smaller scan_stream_generic() in kernels.hip.
@@ -50,9 +50,12 @@ __device__ __forceinline__ f32x4 load_q4(const double* __restrict__ q64, uint32_
 // load_row(): the row whose bytes are loaded for it.  Loads are clamped into bounds and never predicated: a row that
 // is not there is loaded from a row that is, and dropped at the sink.
 
+// MASKED: the source drops rows at the sink (MaskedRows).  For the other sources it is a compile-time false and every
+// line it guards is gone: their kernels are the code they were before the hook existed.
+
 // Every row of the slab, in storage order.
 struct AllRows {
-    static constexpr bool INDIRECT = false;
+    static constexpr bool INDIRECT = false, MASKED = false;
     __device__ __forceinline__ uint32_t at(uint32_t i, uint32_t) const { return i; }
     __device__ __forceinline__ uint32_t load_row(uint32_t pos, bool valid, uint32_t n) const { return valid ? pos : n - 1; }
 };
@@ -60,10 +63,25 @@ struct AllRows {
 // The rows plist[0..n): ascending storage positions (an id filter's resolution).  The position is one dependent read
 // away from the row loads, so the scans request it one iteration ahead (INDIRECT).
 struct ListedRows {
-    static constexpr bool INDIRECT = true;
+    static constexpr bool INDIRECT = true, MASKED = false;
     const uint32_t* __restrict__ plist;
     __device__ __forceinline__ uint32_t at(uint32_t i, uint32_t n) const { return plist[i < n ? i : n - 1]; }
     __device__ __forceinline__ uint32_t load_row(uint32_t pos, bool, uint32_t) const { return pos; }
+};
+
+// Every row of the slab like AllRows, minus the rows whose bit in `keep` is 0 (an exclusion filter's resolution: bit p & 63
+// of word p >> 6 is set iff row p qualifies; bits at or past n are 0).  The rows are all loaded and scored -- an exclusion
+// set leaves almost every row in play -- and an excluded one is dropped where it would be offered.  The WAVE / G rows of
+// one wave step are consecutive and start at a multiple of WAVE / G, a divisor of 64: their keep bits are one shifted
+// field of ONE aligned 64-bit word at a wave-uniform address, so the read is a scalar load (no VGPR per row group) that
+// goes out together with the step's row loads.
+struct MaskedRows {
+    static constexpr bool INDIRECT = false, MASKED = true;
+    const unsigned long long* __restrict__ keep;
+    __device__ __forceinline__ uint32_t at(uint32_t i, uint32_t) const { return i; }
+    __device__ __forceinline__ uint32_t load_row(uint32_t pos, bool valid, uint32_t n) const { return valid ? pos : n - 1; }
+    // first_row: wave-uniform (the caller passes it through readfirstlane)
+    __device__ __forceinline__ unsigned long long keep_word(uint32_t first_row) const { return keep[first_row >> 6]; }
 };
 
 // ---- sinks -------------------------------------------------------------------------------------------------------
@@ -242,6 +260,8 @@ __device__ __forceinline__ void scan_stream(const Fmt fmt, const typename Fmt::Q
         }
         typename Fmt::Chunk x[U][VPL];
         typename Fmt::Scalars sc[U];
+        [[maybe_unused]] unsigned long long kw[U];  // MaskedRows: the keep word of each step in flight
+        [[maybe_unused]] uint32_t first[U];         // and the step's first row (wave-uniform)
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint32_t r = rows.load_row(pos[u], valid[u], n);
@@ -249,17 +269,39 @@ __device__ __forceinline__ void scan_stream(const Fmt fmt, const typename Fmt::Q
 #pragma unroll
             for (int j = 0; j < VPL; ++j) x[u][j] = __builtin_nontemporal_load(p + G * j);
             sc[u] = fmt.load_scalars(r);
+            if constexpr (Rows::MASKED) {
+                // s0 is the same in every lane of the wave; readfirstlane tells the compiler so
+                const uint32_t s = (uint32_t)__builtin_amdgcn_readfirstlane((int)s0) + (uint32_t)u * n_waves;
+                first[u] = s < n_steps ? s * RPS : 0u;  // a step past the end reads word 0 and offers nothing
+                kw[u] = rows.keep_word(first[u]);
+            }
         }
         // every load of this iteration is issued before the first arithmetic instruction: left alone, the scheduler
         // trades memory-level parallelism for registers and serialises the loads two at a time
         __builtin_amdgcn_sched_barrier(0);
+        [[maybe_unused]] unsigned long long kept[U];
+        if constexpr (Rows::MASKED) {
+            // The step's RPS keep bits, spread to the wave's lanes with scalar instructions only: bit r of the field goes
+            // to lane r * G, the lane that offers row r.  The lane mask waits for the offer in scalar registers and becomes
+            // the lanes' flag there (inverse ballot): no VGPR, neither across the loop nor on top of the arithmetic's peak.
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const unsigned long long field = kw[u] >> (first[u] & 63u);  // wave-uniform: a scalar shift
+                unsigned long long m = 0;
+#pragma unroll
+                for (int r = 0; r < RPS; ++r) m |= ((field >> r) & 1ull) << (r * G);
+                kept[u] = m;
+            }
+        }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             float a = 0.0f;
 #pragma unroll
             for (int j = 0; j < VPL; ++j) a = Fmt::accumulate(a, x[u][j], qv[j]);
             a = group_reduce<G>(a);
-            sink.offer(u, fmt.key(a, sc[u]), pos[u], valid[u] && c == 0);
+            bool keep = true;
+            if constexpr (Rows::MASKED) keep = __builtin_amdgcn_inverse_ballot_w64(kept[u]);
+            sink.offer(u, fmt.key(a, sc[u]), pos[u], valid[u] && keep && c == 0);
         }
         sink.step();
     }
