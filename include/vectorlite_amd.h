@@ -265,6 +265,23 @@ int vl_index_search_batch_filters(const vl_index *h, const uint64_t *filters, ui
  * certify (redone on the exact kernels); launches = batched scan launches.  Jobs with an empty subset count nowhere. */
 int vl_index_last_filtered_batch(const vl_index *h, uint64_t *batched, uint64_t *single, uint64_t *exact,
                                  uint64_t *launches);
+/* How the two calls above answer queries under EXCLUSION tokens (vl_index_filter_create_excluding).  mode 0: with the
+ * jobs launches, like include tokens.  1: every eligible query with the mask-aware MFMA batch pass -- one pass over the
+ * bf16 rows per launch sequence whatever the number of queries, each query reading its own token's keep bitmap; no
+ * position list is built for a token whose queries are all answered there.  2 (what new handles start in; a clone keeps
+ * its source's mode): the pass when its estimated time is below the jobs launches'.  A query is eligible when the handle
+ * has no forced path and no row outside the f32 domain, the metric is cosine, dot or Euclidean with a row length the MFMA
+ * filter has a shape for, the index holds at least 8192 rows, min(k, rows kept) <= 60, at least one row is kept, and the
+ * call holds at least two such queries.  The answers are the same bits in every mode: a query the pass cannot certify
+ * joins the jobs like any other.  Flat single-GPU handles; others: VL_ERR_INVALID_ARG, as is a mode outside 0..2. */
+int vl_index_set_masked_batch(vl_index *h, int mode);
+/* Of the last vl_index_search_batch_filters / _filtered on this handle (any argument may be NULL): routed = queries sent
+ * to the mask-aware pass; certified = those it answered; redone = those it handed back (counted by
+ * vl_index_last_filtered_batch like any other job; queries answered by the pass are counted in none of its numbers);
+ * sequences = launch sequences of the pass; lists_built = position lists of exclusion tokens the call had to build (0
+ * when the pass answered every query of those tokens). */
+int vl_index_last_masked_batch(const vl_index *h, uint64_t *routed, uint64_t *certified, uint64_t *redone,
+                               uint64_t *sequences, uint64_t *lists_built);
 
 /* NEW capability (the reference only answers "the best k"): every row that is at least this similar.  min_score is a
  * score in the reference's sense (higher is better for all four metrics, src/lib.rs:425-572; Euclidean and Manhattan are

@@ -51,6 +51,8 @@ extern "C" {
     fn vl_index_search_filtered(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, k: u64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_batch_filters(h: *const vl_index, filters: *const u64, n_filters: u64, queries: *const f64, nq: u64, q_len: u64, k: u64, metric: c_int, out_stride: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_last_filtered_batch(h: *const vl_index, batched: *mut u64, single: *mut u64, exact: *mut u64, launches: *mut u64) -> c_int;
+    fn vl_index_set_masked_batch(h: *mut vl_index, mode: c_int) -> c_int;
+    fn vl_index_last_masked_batch(h: *const vl_index, routed: *mut u64, certified: *mut u64, redone: *mut u64, sequences: *mut u64, lists_built: *mut u64) -> c_int;
     fn vl_index_search_range(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, min_score: f64, metric: c_int, out_ids: *mut u64, out_scores: *mut f64, out_capacity: u64, out_n: *mut u64, out_total: *mut u64) -> c_int;
     fn vl_index_search_range_batch(h: *const vl_index, filter: u64, queries: *const f64, nq: u64, q_len: u64, min_scores: *const f64, metric: c_int, out_stride: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64, out_total: *mut u64) -> c_int;
     fn vl_index_last_range_batch(h: *const vl_index, mfma_queries: *mut u64, single_queries: *mut u64, exact_queries: *mut u64) -> c_int;
@@ -466,6 +468,24 @@ impl GpuFlatIndex {
         let (mut a, mut b, mut c, mut d) = (0u64, 0u64, 0u64, 0u64);
         unsafe { vl_index_last_filtered_batch(self.0.raw, &mut a, &mut b, &mut c, &mut d) };
         (a, b, c, d)
+    }
+
+    /// How filtered batches answer queries under exclusion tokens: 0 = with the jobs launches, 1 = every eligible query with
+    /// the mask-aware MFMA batch pass, 2 = the pass when it is estimated to be faster (what new handles start in).  The
+    /// answers are the same in every mode.  Single-GPU flat handles only.
+    pub fn set_masked_batch(&self, mode: i32) -> VectorLiteResult<()> {
+        match unsafe { vl_index_set_masked_batch(self.0.raw, mode as c_int) } {
+            VL_OK => Ok(()),
+            _ => Err(VectorLiteError::InternalError(last_error())),
+        }
+    }
+
+    /// Of the last filtered batch: queries sent to the mask-aware MFMA pass, those it answered, those it handed back to the
+    /// jobs, its launch sequences, and the position lists of exclusion tokens the call had to build.
+    pub fn last_masked_batch(&self) -> (u64, u64, u64, u64, u64) {
+        let (mut a, mut b, mut c, mut d, mut e) = (0u64, 0u64, 0u64, 0u64, 0u64);
+        unsafe { vl_index_last_masked_batch(self.0.raw, &mut a, &mut b, &mut c, &mut d, &mut e) };
+        (a, b, c, d, e)
     }
 
     /// `search_range` for a batch of queries against one index state (no reference counterpart): entry `i` holds at most

@@ -42,6 +42,8 @@ VL_GROUPED_MAX_K = 1024  # most groups a grouped search returns (vl_index_search
 SINGLE_FILTER_MODES = {"f32": 0, "bf16": 1, "auto": 2}
 # ... and mode 3, the int8 copy first always (kept out of SINGLE_FILTER_MODES, whose three entries callers enumerate)
 SINGLE_FILTER_I8 = 3
+# set_masked_batch: the modes of vl_index_set_masked_batch (2 = auto, what new handles start in)
+MASKED_BATCH_MODES = {"off": 0, "on": 1, "auto": 2}
 
 
 class SimilarityMetric(enum.IntEnum):
@@ -860,6 +862,21 @@ class FlatIndex:
         a, b, c, d = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         _raise(self._L.vl_index_last_filtered_batch(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return {"batched": int(a.value), "single": int(b.value), "exact": int(c.value), "launches": int(d.value)}
+
+    def set_masked_batch(self, mode: str) -> None:
+        """How a filtered search_batch answers queries under exclusion tokens: "off" (with the jobs launches, like
+        include tokens), "on" (every eligible query with the mask-aware MFMA batch pass: one pass over the bf16 rows per
+        launch sequence, each query under its own token's keep bitmap, no position list) or "auto" (new handles: the
+        pass when its estimated time is below the jobs launches').  Answers are identical in every mode."""
+        _raise(self._L.vl_index_set_masked_batch(self._h, MASKED_BATCH_MODES[mode]))
+
+    def last_masked_batch(self) -> Dict[str, int]:
+        """Of the last filtered search_batch on this handle: queries sent to the mask-aware MFMA pass, those it answered,
+        those it handed back to the jobs (last_filtered_batch() counts them; it counts none of the answered ones), the
+        pass's launch sequences, and the position lists of exclusion tokens the call had to build."""
+        v = [C.c_uint64(0) for _ in range(5)]
+        _raise(self._L.vl_index_last_masked_batch(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("routed", "certified", "redone", "sequences", "lists_built"), (int(x.value) for x in v)))
 
     def search_batch_device(self, queries, k: int, metric: int = 0, with_positions: bool = False):
         """search_batch for queries that are already on this index's GPU: `queries` is a contiguous float64 torch tensor

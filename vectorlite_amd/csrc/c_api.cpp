@@ -571,6 +571,21 @@ int vl_index_last_filtered_batch(const vl_index* h, uint64_t* batched, uint64_t*
     return VL_OK;
 }
 
+int vl_index_set_masked_batch(vl_index* h, int mode)
+{
+    if (!h || !h->flat || mode < 0 || mode > 2) return VL_ERR_INVALID_ARG;
+    h->flat->set_masked_batch(mode);
+    return VL_OK;
+}
+
+int vl_index_last_masked_batch(const vl_index* h, uint64_t* routed, uint64_t* certified, uint64_t* redone, uint64_t* sequences,
+                               uint64_t* lists_built)
+{
+    if (!h || !h->flat) return VL_ERR_INVALID_ARG;
+    h->flat->last_masked_batch(routed, certified, redone, sequences, lists_built);
+    return VL_OK;
+}
+
 int vl_index_search_batch_cap(const vl_index* h, const double* queries, uint64_t nq, uint64_t q_len, uint64_t k,
                               int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores, uint64_t* out_n)
 {

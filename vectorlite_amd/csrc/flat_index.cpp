@@ -11,6 +11,7 @@
 #include "shard.hpp"
 #include "score_bound.hpp"
 #include "subset_batch_plan.hpp"
+#include "masked_batch_plan.hpp"
 
 #include <chrono>
 
@@ -1994,16 +1995,98 @@ int GpuFlatIndex::search_batch_filters(const uint64_t* tokens, uint64_t n_filter
     if (lease.status() != OK) return lease.status();
     Workspace* const ws = lease.ws;
     hipStream_t st = ws->stream;
-    for (const auto& f : filters) VL_TRY(resolve_if_stale(ws, f.get()));  // each stale filter once, whatever its number of jobs
+    // each stale filter once, whatever its number of jobs; an exclusion token's position list waits until one of its
+    // queries needs it (need_list below): the masked MFMA pass reads the keep bitmap
+    for (const auto& f : filters) VL_TRY(resolve_if_stale(ws, f.get(), /*need_list=*/!f->exclude));
     InFlight searching(active_searches_);
 
     auto filter_at = [&](uint64_t qi) { return filters[filter_of[n_filters == 1 ? 0 : qi]].get(); };
     const bool may_batch = force_path_.load() == 0 && n_out_of_domain_ == 0 && dim_ != 0;
+    uint64_t mb[5] = {0, 0, 0, 0, 0};  // last_masked_batch: routed, certified, handed back, sequences, lists built
+    auto publish_masked = [&]() {
+        for (int i = 0; i < 5; ++i) last_mbatch_[i].store(mb[i], std::memory_order_relaxed);
+    };
+    auto need_list = [&](IdFilter* f) -> int {
+        std::lock_guard<std::mutex> g(f->mu);
+        if (f->plist_built) return OK;
+        ++mb[4];
+        return ensure_plist(ws, f);
+    };
+
+    // ---- exclusion tokens: the mask-aware MFMA pass answers the eligible queries it may take
+    //      (masked_batch_plan.hpp); what it does not certify joins the jobs below like any other query ----
+    std::vector<uint8_t> answered(nq, 0);
+    {
+        const uint64_t n = ids_.size();
+        const char* mf_env = getenv("VL_MFMA");
+        const char* mf_min = getenv("VL_MFMA_MIN_BATCH");
+        const MaskedBatchShape shp{may_batch && !(mf_env && mf_env[0] == '0') && mfma_scan_supported((uint32_t)dim_, metric) &&
+                                       mfma_rows_kernel((uint32_t)dim_),
+                                   n, (uint32_t)dim_, ld_, mfma_ldb((uint32_t)dim_)};
+        const MaskedBatchLimits lim{MFMA_MIN_ROWS, mf_min && *mf_min ? (uint64_t)atoi(mf_min) : (uint64_t)MFMA_MIN_BATCH,
+                                    (uint64_t)KFAST_MAX, mfma_sequence_queries((uint32_t)dim_)};
+        const int mode = masked_batch_.load();
+        std::vector<uint32_t> elig;
+        uint64_t sum_m = 0;
+        if (mode != MASKED_BATCH_OFF && shp.index_ok)
+            for (uint64_t qi = 0; qi < nq; ++qi) {
+                const IdFilter* f = filter_at(qi);
+                if (f->exclude && masked_query_eligible(shp, lim, f->m, k)) {
+                    elig.push_back((uint32_t)qi);
+                    sum_m += f->m;
+                }
+            }
+        if (masked_batch_route(mode, shp, lim, elig.size(), sum_m)) {
+            const uint64_t ne = elig.size();
+            std::vector<const unsigned long long*> keep(ne);
+            std::vector<uint32_t> mq(ne), kq(ne);
+            for (uint64_t j = 0; j < ne; ++j) {
+                const IdFilter* f = filter_at(elig[j]);
+                keep[j] = f->d_keep;
+                mq[j] = (uint32_t)f->m;
+                kq[j] = (uint32_t)std::min<uint64_t>(k, f->m);
+            }
+            const MaskedQueries desc{elig.data(), keep.data(), mq.data(), kq.data()};
+            std::vector<uint64_t> t_ids(ne * k), t_n(ne, 0);
+            std::vector<double> t_scores(ne * k);
+            std::vector<uint8_t> done(ne, 0);
+            const int rc = search_batch_mfma(ws, queries, nullptr, ne, k, k, metric, nullptr, t_ids.data(), t_scores.data(), t_n.data(),
+                                             &done, nullptr, &desc, &mb[3]);
+            if (rc != OK) {
+                publish_masked();
+                return rc;
+            }
+            mb[0] = ne;
+            for (uint64_t j = 0; j < ne; ++j) {
+                if (!done[j]) continue;
+                const uint64_t qi = elig[j];
+                std::copy_n(t_ids.data() + j * k, t_n[j], out_ids + qi * out_stride);
+                std::copy_n(t_scores.data() + j * k, t_n[j], out_scores + qi * out_stride);
+                out_n[qi] = t_n[j];
+                answered[qi] = 1;
+                ++mb[1];
+            }
+            mb[2] = mb[0] - mb[1];
+            if (mb[1]) set_last_path(PATH_FAST);
+        }
+    }
+    // the position lists the jobs kernel and search_subset read: every token with a query left (one that keeps no row
+    // is answered empty without a list)
+    for (uint64_t qi = 0; qi < nq; ++qi)
+        if (!answered[qi] && filter_at(qi)->exclude && filter_at(qi)->m > 0) {
+            const int rc = need_list(filter_at(qi));
+            if (rc != OK) {
+                publish_masked();
+                for (uint64_t q = 0; q < nq; ++q) out_n[q] = 0;
+                return rc;
+            }
+        }
+    publish_masked();
     int shape_g = 1, shape_u = 1, resident = 1;
     if (may_batch) VL_HIP(scan_subset_jobs_shape(metric, ld_, &shape_g, &shape_u, &resident));
     std::vector<SubsetJob> jobs(nq);
     for (uint64_t qi = 0; qi < nq; ++qi) {
-        const uint64_t m = filter_at(qi)->m;
+        const uint64_t m = answered[qi] ? 0 : filter_at(qi)->m;  // (m = 0: the plan leaves the query alone)
         jobs[qi].m = m;
         jobs[qi].need = subset_job_need(m, shape_g, shape_u);
         jobs[qi].fast = may_batch && m > 0 && std::min<uint64_t>(k, m) <= (uint64_t)KFAST_MAX && query_in_domain(queries + qi * dim_, dim_);
@@ -2797,8 +2880,9 @@ int GpuFlatIndex::ensure_mfma_scratch(Workspace* ws) const
     VL_TRY(dev_alloc(&ws->mf.thr, nqc));
     VL_TRY(dev_alloc(&ws->mf.cand, nqc * MFMA_CAND_CAP));
     VL_TRY(dev_alloc(&ws->mf.cnt, nqp));
-    VL_TRY(dev_alloc(&ws->mf_d_q64, nqc * (dim_ + 1)));
-    VL_TRY(pinned_alloc(&ws->mf_h_q64, nqc * (dim_ + 1)));
+    // per query: the f64 query, its norm, and (a masked batch) a bitmap pointer and the two words m, k
+    VL_TRY(dev_alloc(&ws->mf_d_q64, nqc * (dim_ + 3)));
+    VL_TRY(pinned_alloc(&ws->mf_h_q64, nqc * (dim_ + 3)));
     VL_TRY(dev_alloc(&ws->mf_lists, nqc * KP));
     VL_TRY(dev_alloc(&ws->mf_scores, nqc * KP));
     VL_TRY(pinned_alloc(&ws->mf_h_result, 2 * nqc));  // two launch sequences in flight: one being unpacked, one on the GPU
@@ -2815,8 +2899,12 @@ int GpuFlatIndex::ensure_mfma_scratch(Workspace* ws) const
 int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const double* d_queries, uint64_t nq,
                                     uint64_t k, uint64_t k_eff, int metric, uint64_t* out_pos, uint64_t* out_ids,
                                     double* out_scores, uint64_t* out_n, std::vector<uint8_t>* done,
-                                    const ShardRecordSink* sink) const
+                                    const ShardRecordSink* sink, const MaskedQueries* masked, uint64_t* n_sequences) const
 {
+    static_assert(sizeof(const unsigned long long*) == sizeof(double) && 2 * sizeof(uint32_t) == sizeof(double),
+                  "the masked descriptor is staged as two words per query behind the norms");
+    if (masked && (d_queries || sink || !mfma_rows_kernel((uint32_t)dim_))) return ERR_INVALID_ARG;
+    if (n_sequences) *n_sequences = 0;
     const uint64_t n = ids_.size();
     const bool frag = mfma_rows_kernel((uint32_t)dim_);  // which kernel, hence which slab layout
     VL_TRY(ensure_bf16_slab(frag));
@@ -2824,6 +2912,7 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
     VL_TRY(ensure_mfma_scratch(ws));
     hipStream_t st = ws->stream;
     const double in_extra = IN_EXTRA_MFMA;  // bf16 rows and queries (mfma_scan.hpp)
+    const uint64_t k_eff_all = k_eff;       // (a masked batch has its own per query)
     const bool prof = profile_.load();
     static const bool trace = getenv("VL_TRACE_BATCH") != nullptr;  // diagnostic: host-side phases of a sequence on stderr
     auto now = [] { return std::chrono::steady_clock::now(); };
@@ -2876,21 +2965,42 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
             const uint32_t piece = (uint32_t)std::max<uint64_t>(16, (1u << 20) / (dim_ * sizeof(double)));  // ~1 MB
             for (uint32_t j0 = 0; j0 < g; j0 += piece) {
                 const uint32_t j1 = std::min<uint32_t>(g, j0 + piece);
-                for (uint32_t j = j0; j < j1; ++j)
-                    S.in_domain[j] = stage_query(queries + (q0 + j) * dim_, ws->mf_h_q64 + (size_t)j * dim_, dim_, &norms[j]) ? 1 : 0;
+                for (uint32_t j = j0; j < j1; ++j) {
+                    const uint64_t src = masked ? masked->qidx[q0 + j] : q0 + j;
+                    S.in_domain[j] = stage_query(queries + src * dim_, ws->mf_h_q64 + (size_t)j * dim_, dim_, &norms[j]) ? 1 : 0;
+                }
                 VL_HIP(hipMemcpyAsync(ws->mf_d_q64 + (size_t)j0 * dim_, ws->mf_h_q64 + (size_t)j0 * dim_,
                                       (size_t)(j1 - j0) * dim_ * sizeof(double), hipMemcpyHostToDevice, st));
             }
-            VL_HIP(hipMemcpyAsync(ws->mf_d_q64 + (size_t)g * dim_, norms, (size_t)g * sizeof(double), hipMemcpyHostToDevice, st));
+            // a masked batch: the sequence's bitmap table and its (m, k) words travel with the norms, in stream order with
+            // the queries -- the two-deep pipeline shares the device copy like every other staging buffer
+            if (masked) {
+                const unsigned long long** h_keep = reinterpret_cast<const unsigned long long**>(norms + g);
+                uint32_t* h_m = reinterpret_cast<uint32_t*>(norms + 2 * (size_t)g);
+                for (uint32_t j = 0; j < g; ++j) {
+                    h_keep[j] = masked->keep[q0 + j];
+                    h_m[j] = masked->m[q0 + j];
+                    h_m[g + j] = masked->k[q0 + j];
+                }
+            }
+            VL_HIP(hipMemcpyAsync(ws->mf_d_q64 + (size_t)g * dim_, norms, (size_t)g * (masked ? 3 : 1) * sizeof(double),
+                                  hipMemcpyHostToDevice, st));
             VL_HIP(hipEventRecord(ws->mf_ev_h2d, st));
             ws->mf_h2d_pending = true;
         }
         S.t1 = now();
         if (prof) VL_HIP(hipEventRecord(ws->ev0, st));
         MfmaLaunchInfo li;
-        VL_HIP(launch_mfma_candidates(st, metric, slab16, d_norm16_, d_sqnorm_, ws->mf_d_q64, g, n, (uint32_t)dim_,
-                                      ws->mf, ws->mf_lists, &li, prepared));
-        {
+        const double* d_norms = ws->mf_d_q64 + (size_t)g * dim_;
+        const unsigned long long* const* d_keep_of = reinterpret_cast<const unsigned long long* const*>(d_norms + g);
+        const uint32_t* d_m = reinterpret_cast<const uint32_t*>(d_norms + 2 * (size_t)g);
+        if (masked)
+            VL_HIP(launch_mfma_candidates_masked(st, metric, slab16, d_norm16_, d_sqnorm_, ws->mf_d_q64, g, n, (uint32_t)dim_,
+                                                 ws->mf, d_keep_of, ws->mf_lists, &li));
+        else
+            VL_HIP(launch_mfma_candidates(st, metric, slab16, d_norm16_, d_sqnorm_, ws->mf_d_q64, g, n, (uint32_t)dim_,
+                                          ws->mf, ws->mf_lists, &li, prepared));
+        if (!masked) {
             const int v[6] = {li.ksteps, li.metric, li.chunks, li.grid_x, li.stages, li.sample_blocks};
             for (int i = 0; i < 6; ++i) last_filter_[i].store(v[i], std::memory_order_relaxed);
         }
@@ -2903,7 +3013,10 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
         // batches: the rescoring split over four workgroups per query + a rank / emit launch (launch_batch_finalize); a handful
         // of queries keeps the one-workgroup-per-query kernel (one launch less)
         static const bool split_off = []() { const char* v = getenv("VL_BATCH_FINALIZE"); return v && v[0] == '0'; }();
-        if (g >= 8 && !split_off)
+        if (masked)  // the certificate per query: n_rows = m_q, k = min(k, m_q) (DESIGN.md sections 23, 24)
+            VL_HIP(launch_batch_finalize_rows(st, metric, ws->mf_lists, (int)g, d_master_, ws->mf_d_q64, d_norms, (uint32_t)dim_,
+                                              d_m, d_m + g, max_row_norm_, res, in_extra, ws->mf_scores));
+        else if (g >= 8 && !split_off)
             VL_HIP(launch_batch_finalize(st, metric, ws->mf_lists, (int)g, d_master_, ws->mf_d_q64, ws->mf_d_q64 + (size_t)g * dim_,
                                          (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_, res, in_extra, ws->mf_scores,
                                          sink ? &seq_sink : nullptr));
@@ -2912,6 +3025,7 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
                                          ws->mf_d_q64 + (size_t)g * dim_, (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_,
                                          res, in_extra, 0, sink ? &seq_sink : nullptr));
         VL_HIP(hipEventRecord(ws->mf_ev_done[slot], st));
+        if (n_sequences) ++*n_sequences;
         S.t2 = now();
         return OK;
     };
@@ -2926,10 +3040,19 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
         if (d_queries)
             for (uint32_t j = 0; j < g; ++j) S.in_domain[j] = dom[j];
         const auto t_3 = now();
-        if (prof) VL_TRY(account_profile(ws, n * (uint64_t)mfma_ldb((uint32_t)dim_) * 2));
+        if (prof) {
+            uint64_t bytes = n * (uint64_t)mfma_ldb((uint32_t)dim_) * 2;
+            if (masked) {  // and every distinct bitmap of the sequence once
+                std::vector<const unsigned long long*> maps(masked->keep + S.q0, masked->keep + S.q0 + g);
+                std::sort(maps.begin(), maps.end());
+                bytes += (uint64_t)(std::unique(maps.begin(), maps.end()) - maps.begin()) * (n / 8);
+            }
+            VL_TRY(account_profile(ws, bytes));
+        }
         for (uint32_t j = 0; j < g; ++j) {
             const uint64_t qi = S.q0 + j;
             const SearchResultBlock& r = res[j];
+            const uint64_t k_eff = masked ? masked->k[qi] : k_eff_all;
             if (!S.in_domain[j] || (r.flags & RESULT_NEEDS_EXACT) || r.n_out != k_eff) continue;
             bool ok = true;
             for (uint64_t i = 0; i < k_eff; ++i) ok = ok && r.pos[i] < n;
@@ -3323,6 +3446,7 @@ int GpuFlatIndex::clone(GpuFlatIndex** out) const
     if (!ids_.empty())
         VL_TRY(c->add_bulk(ids_.data(), d_master_, ids_.size(), /*validate=*/false, /*values_on_device=*/true));
     c->force_path_.store(force_path_.load());
+    c->masked_batch_.store(masked_batch_.load());
     *out = guard.release();
     return OK;
 }

@@ -301,6 +301,20 @@ public:
         if (exact) *exact = last_fbatch_[2].load(std::memory_order_relaxed);
         if (launches) *launches = last_fbatch_[3].load(std::memory_order_relaxed);
     }
+    // How search_batch_filters answers queries under EXCLUSION tokens (masked_batch_plan.hpp).  0: with
+    // the jobs kernel, like include tokens.  1: the eligible ones with the mask-aware MFMA pass.  2 ("auto", the default):
+    // the pass when its estimated time is below the jobs kernel's.
+    void set_masked_batch(int mode) { masked_batch_.store(mode); }
+    int masked_batch() const { return masked_batch_.load(); }
+    // the last search_batch_filters on this handle: queries sent to the masked MFMA pass, those it certified, those it
+    // handed back (they are counted by last_filtered_batch like any other job), its launch sequences, and the position
+    // lists of exclusion tokens the call had to build (0: the pass answered every query of those tokens)
+    void last_masked_batch(uint64_t* routed, uint64_t* certified, uint64_t* redone, uint64_t* sequences, uint64_t* lists_built) const
+    {
+        uint64_t* out[5] = {routed, certified, redone, sequences, lists_built};
+        for (int i = 0; i < 5; ++i)
+            if (out[i]) *out[i] = last_mbatch_[i].load(std::memory_order_relaxed);
+    }
     // NEW (no reference counterpart): every row whose score is >= min_score -- the longest prefix of FlatIndex::search(q, len,
     // metric) with score >= min_score, over the filter's rows when token != 0.  *out_total = rows that qualify, always;
     // min(total, out_capacity) entries are written (out_capacity = 0: count only, outputs may be null).
@@ -495,10 +509,20 @@ private:
     int ensure_mfma_scratch(Workspace* ws) const;
     int search_batch_locked(const double* queries, uint64_t nq, uint64_t q_len, uint64_t k, int metric, uint64_t* out_pos,
                             uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;  // mu_ held (shared)
+    // Per-query descriptor of a masked batch (exclusion tokens): sequence query j is the caller's
+    // query qidx[j] (host queries only) under the keep bitmap keep[j] (a device pointer), which keeps m[j] > 0 rows; it asks
+    // for k[j] = min(k, m[j]) rows.  Outputs and `done` are indexed by j, at stride k.
+    struct MaskedQueries {
+        const uint32_t* qidx;
+        const unsigned long long* const* keep;
+        const uint32_t* m;
+        const uint32_t* k;
+    };
     int search_batch_mfma(Workspace* ws, const double* queries, const double* d_queries, uint64_t nq, uint64_t k,
                           uint64_t k_eff, int metric, uint64_t* out_pos, uint64_t* out_ids, double* out_scores,
                           uint64_t* out_n, std::vector<uint8_t>* done,
-                          const ShardRecordSink* sink = nullptr) const;  // queries on the host, or d_queries on the device
+                          const ShardRecordSink* sink = nullptr,  // queries on the host, or d_queries on the device
+                          const MaskedQueries* masked = nullptr, uint64_t* n_sequences = nullptr) const;
     int ensure_device_ids() const;  // lazily uploads the position -> id table (what a device-written exchange record needs)
 
     const uint64_t dim_;
@@ -584,6 +608,8 @@ private:
     mutable std::atomic<int> last_filter_[6] = {};
     mutable std::atomic<uint64_t> last_rbatch_[4] = {};
     mutable std::atomic<uint64_t> last_fbatch_[4] = {};
+    mutable std::atomic<uint64_t> last_mbatch_[5] = {};
+    std::atomic<int> masked_batch_{2};  // MASKED_BATCH_AUTO
     std::atomic<uint64_t> last_delete_[6] = {};
     mutable std::mutex prof_mu_;
     mutable uint64_t prof_n_ = 0;

@@ -971,6 +971,26 @@ __global__ __launch_bounds__(256) void k_batch_rank_emit(const Cand32* __restric
     rank_check_emit<METRIC>(sc, e.pos, read_lane(e.key, KP - 1), n_cand, k, n_rows, ld, R, q_norms[q], in_extra, out + q, 0u, sink, q);
 }
 
+// k_batch_rank_emit for lists that hold only the rows each query's filter keeps (the masked MFMA filter, DESIGN.md section
+// 24): the rows the bound check and the "a list of at most 64 rows must hold every row" rule refer to are the query's own
+// m_of[q], and k is k_of[q] = min(k, m_of[q]) -- k_merge_finalize_jobs' arithmetic, read from two arrays.  Its own kernel,
+// for the reason given there.
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_batch_rank_emit_rows(const Cand32* __restrict__ lists, const double* __restrict__ scores,
+                                                              const double* __restrict__ q_norms, uint32_t nq, uint32_t ld,
+                                                              const uint32_t* __restrict__ m_of, const uint32_t* __restrict__ k_of,
+                                                              double R, double in_extra, SearchResultBlock* __restrict__ out)
+{
+    const int lane = lane_id();
+    const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= nq) return;
+    const Cand32 e = lists[(size_t)q * KP + lane];
+    const int n_cand = __popcll(__ballot(e.pos != POS_SENTINEL));
+    const double sc = lane < n_cand ? scores[(size_t)q * KP + lane] : 0.0;
+    rank_check_emit<METRIC>(sc, e.pos, read_lane(e.key, KP - 1), n_cand, k_of[q], (uint64_t)m_of[q], ld, R, q_norms[q], in_extra,
+                            out + q, 0u, ShardRecordSink{}, q);
+}
+
 // K2: merge partial lists, rescore, rank, bound-check.  One workgroup of 1024 threads.
 template <int METRIC>
 __global__ __launch_bounds__(1024) void k_merge_finalize(const Cand32* __restrict__ partials, int n_lists,
@@ -2447,6 +2467,22 @@ hipError_t launch_batch_finalize(hipStream_t s, int metric, const Cand32* lists,
         hipLaunchKernelGGL((k_batch_rescore<MM>), dim3((unsigned)nq * 4u), dim3(256), 0, s, lists, master, q64, dim, score_scratch);
         hipLaunchKernelGGL((k_batch_rank_emit<MM>), dim3(((unsigned)nq + 3u) / 4u), dim3(256), 0, s, lists, (const double*)score_scratch,
                            q_norms, (uint32_t)nq, ld, n_rows, k, max_row_norm, in_extra, out, sk);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_batch_finalize_rows(hipStream_t s, int metric, const Cand32* lists, int nq, const double* master,
+                                      const double* q64, const double* q_norms, uint32_t dim, const uint32_t* m_of,
+                                      const uint32_t* k_of, double max_row_norm, SearchResultBlock* out, double in_extra,
+                                      double* score_scratch)
+{
+    if (nq <= 0 || !score_scratch || !m_of || !k_of) return hipErrorInvalidValue;
+    const uint32_t ld = (dim + 3u) & ~3u;
+    return dispatch_metric(metric, [&](auto M) -> hipError_t {
+        constexpr int MM = decltype(M)::value;
+        hipLaunchKernelGGL((k_batch_rescore<MM>), dim3((unsigned)nq * 4u), dim3(256), 0, s, lists, master, q64, dim, score_scratch);
+        hipLaunchKernelGGL((k_batch_rank_emit_rows<MM>), dim3(((unsigned)nq + 3u) / 4u), dim3(256), 0, s, lists,
+                           (const double*)score_scratch, q_norms, (uint32_t)nq, ld, m_of, k_of, max_row_norm, in_extra, out);
         return hipGetLastError();
     });
 }

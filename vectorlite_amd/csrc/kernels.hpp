@@ -152,6 +152,14 @@ hipError_t launch_batch_finalize(hipStream_t s, int metric, const Cand32* lists,
                                  SearchResultBlock* out, double in_extra, double* score_scratch,
                                  const ShardRecordSink* sink = nullptr);
 
+// launch_batch_finalize for lists of kept rows only (the masked MFMA filter): n_rows and k of query q
+// are m_of[q] (its filter's rows, > 0) and k_of[q] = min(k, m_of[q]), two device arrays of nq words -- what
+// launch_merge_finalize_jobs reads from its job table.  Any nq >= 1; no shard record.
+hipError_t launch_batch_finalize_rows(hipStream_t s, int metric, const Cand32* lists, int nq, const double* master,
+                                      const double* q64, const double* q_norms, uint32_t dim, const uint32_t* m_of,
+                                      const uint32_t* k_of, double max_row_norm, SearchResultBlock* out, double in_extra,
+                                      double* score_scratch);
+
 // K3: one launch for nq <= SCAN_BATCH_MAX_QUERIES queries (q64 is [nq, dim]) in groups of SCAN_BATCH_QB -- every group is one
 // pass over the slab (blockIdx.y = group); lists are written query-major, plan->grid of them per query (<= 64 when there is
 // more than one group, so that the finalize kernel takes them without a merge level).

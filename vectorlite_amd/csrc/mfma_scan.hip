@@ -539,17 +539,27 @@ constexpr int rs_seg(uint32_t ldb) { return (size_t)rs_qpb(ldb) * (ldb * 2 + 32)
 // (6.05 -> 6.6 TB/s of bf16 rows).  With several chunks the other chunks of the XCD re-read a block from L2 and the same
 // hint costs 15-25 % (256 queries: 1.82 -> 2.15 ms), so only single-chunk launches of pass 1 take it.
 #define RS_LOAD_FRAG(ptr) (STREAM ? __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(ptr)) : *reinterpret_cast<const bf16x8*>(ptr))
-template <int KSTEPS, int MODE, int METRIC, int RBN = 2, int NW = RS_NWAVES, bool STREAM = false>
-__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(1, (NW == 4 ? 1 : 2))))
-void k_mfma_rows(const __bf16* __restrict__ slab16,
+// One body, two kernels (below): k_mfma_rows (MASKED = false) and k_mfma_rows_masked, which answers a batch of queries
+// that each exclude rows.  keep_of[q] is query q's keep bitmap (bit p & 63 of word p >> 6 set iff
+// row p qualifies; a shared filter is nq equal pointers).  A wave's 32-row block is one 32-bit half of one word:
+//   MODE 0  an excluded row's key becomes -inf in front of the max tree, like a row past n_rows: the group maxima are
+//           maxima over kept rows, and T_q (k_thresholds, unchanged) a lower bound of the 64th best KEPT key;
+//   MODE 1  the common path (max tree, one threshold test, one branch) is the unmasked one's code; the candidate code
+//           fetches the field on demand (keep_bits below) and appends kept rows only.  Nothing of the mask lives across
+//           the main loop.
+// Padding queries (index >= nq) have no table slot: it is never read.
+template <int KSTEPS, int MODE, int METRIC, int RBN, int NW, bool STREAM, bool MASKED>
+__device__ __forceinline__ void rs_rows_body(const __bf16* __restrict__ slab16,
                                                               const float* __restrict__ row_nrm,
                                                               const float* __restrict__ row_sqn,
                                                               const __bf16* __restrict__ q16, uint32_t nq,
                                                               uint32_t blk_begin, uint32_t blk_end, uint32_t n_rows,
                                                               int* __restrict__ gmax, uint32_t n_groups, uint32_t gpw,
                                                               const float* __restrict__ thr, Cand32* __restrict__ cand,
-                                                              uint32_t* __restrict__ cnt, uint32_t cap)
+                                                              uint32_t* __restrict__ cnt, uint32_t cap,
+                                                              const unsigned long long* const* __restrict__ keep_of)
 {
+    static_assert(!MASKED || RBN == 2, "the masked form reads one 32-bit keep field per 32-row block");
     constexpr int LDB = KSTEPS * 16;
     constexpr int ROW_BYTES = LDB * 2;
     constexpr int LDS_ROW = ROW_BYTES + 32;   // same padding as k_mfma_scan's row tiles: conflict-free ds_read_b128
@@ -607,6 +617,7 @@ void k_mfma_rows(const __bf16* __restrict__ slab16,
     constexpr bool THR_LDS = (MODE == 1 && METRIC == EUCLIDEAN && PH == 1 && RBN == 2);
 #endif
     __shared__ float thr_lds[THR_LDS ? QPB : 1];
+    constexpr bool MASK0 = MASKED && MODE == 0;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -657,6 +668,33 @@ void k_mfma_rows(const __bf16* __restrict__ slab16,
     // this lane's threshold for query block qb: a register, or (THR_LDS) one ds_read_b32 per use
     auto thr_of = [&](int qb) -> float { return THR_LDS ? thr_lds[qb * 16 + c16] : thr_q[THR_LDS ? 0 : qb]; };
     uint32_t my_cnt = 0;
+    // masked forms: the keep bits of this lane's query of query block qb for the rows of 32-row block blk, shifted so that
+    // row (rb, jj) of the lane is bit 16 rb + jj.  The 16 queries of a query block are wave-uniform numbers and so is blk:
+    // the table and the fields come through SCALAR loads (the constant address space: both were written before the launch)
+    // and one select per query picks the lane's own -- no vector register besides the result, nothing kept between calls.
+    // A padding query (>= nq) reads the last real query's field; its keys never count (T = +inf, maxima never written).
+    auto keep_bits = [&](int qb, uint32_t blk) -> uint32_t {
+        typedef __attribute__((address_space(4))) const unsigned long long cu64;
+        typedef __attribute__((address_space(4))) const uint32_t cu32;
+        const cu64* tab = (const cu64*)(uintptr_t)keep_of;
+        const uint32_t ublk = (uint32_t)__builtin_amdgcn_readfirstlane((int)blk);
+        uint32_t f = 0u;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const uint32_t qq = chunk_base + (uint32_t)(qb * 16 + i);
+            uint32_t uq = (uint32_t)__builtin_amdgcn_readfirstlane((int)(qq < nq ? qq : nq - 1));
+            // the table reads stay here: they do not depend on the row block, and hoisted out of the main loop the
+            // pointers of every query of the workgroup would live (in spilled scalar registers) across it
+            asm volatile("" : "+s"(uq));
+            const cu32* kp = (const cu32*)(uintptr_t)tab[uq];
+            const uint32_t fi = kp[ublk];
+            f = (c16 == i) ? fi : f;
+            // eight queries' loads in flight at a time (24 scalar registers): all sixteen, or several query blocks'
+            // interleaved, spill scalar registers
+            if (i % 8 == 7) __builtin_amdgcn_sched_barrier(0);
+        }
+        return f >> (4 * kg);
+    };
 
     // block schedule: neighbouring WORKGROUPS stream neighbouring BR-row blocks (block = begin + x + gridDim.x * (wave + NW i)),
     // so in MODE 0 every workgroup (= group) owns rows as soon as there are gridDim.x blocks
@@ -852,6 +890,13 @@ void k_mfma_rows(const __bf16* __restrict__ slab16,
             // masking them costs a compare and two selects per key -- in every block, if it is written as a predicate.
             auto epilogue = [&](auto partial_tag) {
                 constexpr bool PARTIAL = decltype(partial_tag)::value;
+                // masked sampling pass: this lane's keep bits of block b, one 32-bit field per query block of the
+                // sub-iteration.  Fetched here, behind the MFMAs: no register of the mask lives across them.
+                uint32_t kfld[MASK0 ? HQB : 1];
+                if (MASK0) {
+#pragma unroll
+                    for (int j = 0; j < HQB; ++j) kfld[j] = keep_bits(half * HQB + j, b);
+                }
                 // key of row (rb, jj) for query block j, from the finished sums.  The common path only needs each query
                 // block's maximum; the rare candidate path recomputes the keys it looks at (the same arithmetic on the same
                 // registers: the accumulators stay live until the next block zeroes them), so no key array stays live across
@@ -861,6 +906,7 @@ void k_mfma_rows(const __bf16* __restrict__ slab16,
                     if (METRIC == DOT) key *= aux_c[rb][jj];                                      // x.q
                     if (METRIC == EUCLIDEAN) key = 2.0f * key * aux_c[rb][jj] - aux2_c[rb][jj];   // |q|^2 - |x - q|^2
                     if (PARTIAL && row0 + (uint32_t)(16 * rb + 4 * kg + jj) >= n_rows) key = -INFINITY;
+                    if (MASK0 && !((kfld[MASK0 ? j : 0] >> (16 * rb + jj)) & 1u)) key = -INFINITY;
                     return key;
                 };
                 float mj[HQB];
@@ -906,6 +952,9 @@ void k_mfma_rows(const __bf16* __restrict__ slab16,
                     const int qb = half * HQB + j;
                     const float tq = thr_of(qb);
                     if (__builtin_amdgcn_ballot_w64(mj[j] >= tq) == 0ull) continue;  // wave-uniform
+                    // masked pass 1: the keep field of this lane's query for block b, fetched here and nowhere else
+                    uint32_t kbits = 0xFFFFFFFFu;
+                    if (MASKED) kbits = keep_bits(qb, b);
 #pragma unroll
                     for (int rb = 0; rb < RBN; ++rb) {
                         const float k0 = key_of(rb, j, 0), k1 = key_of(rb, j, 1), k2 = key_of(rb, j, 2), k3 = key_of(rb, j, 3);
@@ -914,7 +963,8 @@ void k_mfma_rows(const __bf16* __restrict__ slab16,
 #pragma unroll
                         for (int jj = 0; jj < 4; ++jj) {
                             const float key = jj == 0 ? k0 : (jj == 1 ? k1 : (jj == 2 ? k2 : k3));
-                            const bool is_cand = key >= tq && key > -INFINITY;  // masked rows are -inf; T_q may be too
+                            // rows past n_rows are -inf; T_q may be too; an excluded row never enters a buffer
+                            const bool is_cand = key >= tq && key > -INFINITY && (!MASKED || ((kbits >> (16 * rb + jj)) & 1u));
                             const unsigned long long mk = __builtin_amdgcn_ballot_w64(is_cand);
                             if (mk != 0ull) {  // wave-uniform
                                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32),
@@ -967,6 +1017,30 @@ void k_mfma_rows(const __bf16* __restrict__ slab16,
             if (chunk_base + ql < nq && gidx < n_groups) gmax[(size_t)(chunk_base + ql) * n_groups + gidx] = gmax_lds[c];
         }
     }
+}
+
+template <int KSTEPS, int MODE, int METRIC, int RBN = 2, int NW = RS_NWAVES, bool STREAM = false>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(1, (NW == 4 ? 1 : 2))))
+void k_mfma_rows(const __bf16* __restrict__ slab16, const float* __restrict__ row_nrm, const float* __restrict__ row_sqn,
+                 const __bf16* __restrict__ q16, uint32_t nq, uint32_t blk_begin, uint32_t blk_end, uint32_t n_rows,
+                 int* __restrict__ gmax, uint32_t n_groups, uint32_t gpw, const float* __restrict__ thr,
+                 Cand32* __restrict__ cand, uint32_t* __restrict__ cnt, uint32_t cap)
+{
+    rs_rows_body<KSTEPS, MODE, METRIC, RBN, NW, STREAM, false>(slab16, row_nrm, row_sqn, q16, nq, blk_begin, blk_end, n_rows, gmax,
+                                                               n_groups, gpw, thr, cand, cnt, cap, nullptr);
+}
+
+// The masked form: the same arguments and keep_of (the shipped shape only: RBN = 2, NW = 8).
+template <int KSTEPS, int MODE, int METRIC, bool STREAM = false>
+__global__ __launch_bounds__(RS_NWAVES * 64) __attribute__((amdgpu_waves_per_eu(1, 2)))
+void k_mfma_rows_masked(const __bf16* __restrict__ slab16, const float* __restrict__ row_nrm, const float* __restrict__ row_sqn,
+                        const __bf16* __restrict__ q16, uint32_t nq, uint32_t blk_begin, uint32_t blk_end, uint32_t n_rows,
+                        int* __restrict__ gmax, uint32_t n_groups, uint32_t gpw, const float* __restrict__ thr,
+                        Cand32* __restrict__ cand, uint32_t* __restrict__ cnt, uint32_t cap,
+                        const unsigned long long* const* __restrict__ keep_of)
+{
+    rs_rows_body<KSTEPS, MODE, METRIC, 2, RS_NWAVES, STREAM, true>(slab16, row_nrm, row_sqn, q16, nq, blk_begin, blk_end, n_rows,
+                                                                  gmax, n_groups, gpw, thr, cand, cnt, cap, keep_of);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1833,11 +1907,14 @@ hipError_t launch_rows_bf16_frag(hipStream_t s, const double* master_rows, uint6
     return hipGetLastError();
 }
 
-hipError_t launch_mfma_candidates(hipStream_t s, int metric, const void* slab_bf16, const float* row_norm,
-                                  const float* row_sqnorm,
-                                  const double* q64, uint32_t nq, uint64_t n_rows, uint32_t dim,
-                                  const MfmaScratch& w, Cand32* out_lists, MfmaLaunchInfo* info, bool queries_prepared)
+namespace {
+// launch_mfma_candidates and launch_mfma_candidates_masked: one launch plan (filter_plan, the stage loop, refine, select).
+// keep_of != nullptr launches the masked kernels of the row-stationary filter with it; the LDS-tile kernel has no masked form.
+hipError_t mfma_candidates(hipStream_t s, int metric, const void* slab_bf16, const float* row_norm, const float* row_sqnorm,
+                           const double* q64, uint32_t nq, uint64_t n_rows, uint32_t dim, const MfmaScratch& w, Cand32* out_lists,
+                           MfmaLaunchInfo* info, bool queries_prepared, const unsigned long long* const* keep_of)
 {
+    if (keep_of && !mfma_rows_kernel(dim)) return hipErrorInvalidValue;
     if (nq == 0 || n_rows == 0 || n_rows >= 0xFFFFFFFFull) return hipErrorInvalidValue;
     if (!mfma_scan_supported(dim, metric) || nq > w.nq_cap) return hipErrorInvalidValue;
     const uint32_t ldb = mfma_ldb(dim);
@@ -1896,7 +1973,7 @@ hipError_t launch_mfma_candidates(hipStream_t s, int metric, const void* slab_bf
             const bool r_stream = pass1_streams(r_chunks);
 #ifdef RS_WIDE_SHAPES  /* stage ends are planned in 32-row blocks: halved (floor) at both ends, the last one ends the index */
 #define VL_RLAUNCH_WIDE(K, MET)                                                                                                 \
-    if (wide == 1) {                                                                                                            \
+    if (wide == 1 && !keep_of) {                                                                                                \
         const uint32_t tb = st_end[st] / 2, te = (st + 1 == r_stages) ? n_blk64 : st_end[st + 1] / 2;                            \
         const uint32_t gx = std::max<uint32_t>(1u, std::min<uint32_t>((te - tb + 3) / 4, wg_cap));                               \
         hipLaunchKernelGGL((k_mfma_rows<K, 1, MET, 4, 4>), dim3(gx, r_chunks), dim3(4 * 64), 0, s, slab, row_norm,               \
@@ -1906,11 +1983,19 @@ hipError_t launch_mfma_candidates(hipStream_t s, int metric, const void* slab_bf
 #else
 #define VL_RLAUNCH_WIDE(K, MET)
 #endif
+/* the unmasked kernel, or (keep_of given) the masked one with the table as its last argument */
+#define VL_ROWS_GO(PLAIN, MASKED_K, GRID, ...)                                                           \
+    {                                                                                                    \
+        if (keep_of)                                                                                     \
+            hipLaunchKernelGGL(MASKED_K, GRID, dim3(RS_NWAVES * 64), 0, s, __VA_ARGS__, keep_of);        \
+        else                                                                                             \
+            hipLaunchKernelGGL(PLAIN, GRID, dim3(RS_NWAVES * 64), 0, s, __VA_ARGS__);                    \
+    }
 #define VL_RLAUNCH2(K, MET)                                                                                                     \
     {                                                                                                                           \
-        hipLaunchKernelGGL((k_mfma_rows<K, 0, MET>), dim3(gx0, r_chunks), dim3(RS_NWAVES * 64), 0, s, slab, row_norm,           \
-                           row_sqnorm, q16, nq, 0u, sample_blocks, (uint32_t)r_sample_rows, w.gmax, r_groups, r_gpw,            \
-                           (const float*)nullptr, (Cand32*)nullptr, (uint32_t*)nullptr, 0u);                                    \
+        VL_ROWS_GO((k_mfma_rows<K, 0, MET>), (k_mfma_rows_masked<K, 0, MET>), dim3(gx0, r_chunks), slab, row_norm,              \
+                   row_sqnorm, q16, nq, 0u, sample_blocks, (uint32_t)r_sample_rows, w.gmax, r_groups, r_gpw,                    \
+                   (const float*)nullptr, (Cand32*)nullptr, (uint32_t*)nullptr, 0u)                                             \
         hipLaunchKernelGGL(k_thresholds, dim3((nq + 3) / 4), dim3(256), 0, s, w.gmax, r_groups, nq, q64 + (size_t)nq * dim,     \
                            w.thr);                                                                                              \
         for (int st = 0; st < r_stages; ++st) {                                                                                 \
@@ -1919,13 +2004,13 @@ hipError_t launch_mfma_candidates(hipStream_t s, int metric, const void* slab_bf
                 const uint32_t tb = st_end[st], te = st_end[st + 1];                                                            \
                 const uint32_t gx = std::max<uint32_t>(1u, std::min<uint32_t>((te - tb + RS_NWAVES - 1) / RS_NWAVES, wg_cap));  \
                 if (r_stream)                                                                                                   \
-                    hipLaunchKernelGGL((k_mfma_rows<K, 1, MET, 2, RS_NWAVES, true>), dim3(gx, r_chunks), dim3(RS_NWAVES * 64),  \
-                                       0, s, slab, row_norm, row_sqnorm, q16, nq, tb, te, (uint32_t)n_rows, (int*)nullptr, 0u,  \
-                                       1u, w.thr, w.cand, w.cnt, (uint32_t)MFMA_CAND_CAP);                                      \
+                    VL_ROWS_GO((k_mfma_rows<K, 1, MET, 2, RS_NWAVES, true>), (k_mfma_rows_masked<K, 1, MET, true>),             \
+                               dim3(gx, r_chunks), slab, row_norm, row_sqnorm, q16, nq, tb, te, (uint32_t)n_rows, (int*)nullptr, \
+                               0u, 1u, w.thr, w.cand, w.cnt, (uint32_t)MFMA_CAND_CAP)                                           \
                 else                                                                                                            \
-                hipLaunchKernelGGL((k_mfma_rows<K, 1, MET>), dim3(gx, r_chunks), dim3(RS_NWAVES * 64), 0, s, slab, row_norm,    \
-                                   row_sqnorm, q16, nq, tb, te, (uint32_t)n_rows, (int*)nullptr, 0u, 1u, w.thr, w.cand, w.cnt,  \
-                                   (uint32_t)MFMA_CAND_CAP);                                                                    \
+                    VL_ROWS_GO((k_mfma_rows<K, 1, MET>), (k_mfma_rows_masked<K, 1, MET>), dim3(gx, r_chunks), slab, row_norm,   \
+                               row_sqnorm, q16, nq, tb, te, (uint32_t)n_rows, (int*)nullptr, 0u, 1u, w.thr, w.cand, w.cnt,      \
+                               (uint32_t)MFMA_CAND_CAP)                                                                         \
             }                                                                                                                   \
             if (st + 1 < r_stages)                                                                                              \
                 hipLaunchKernelGGL(k_refine_thresholds, dim3((nq + 3) / 4), dim3(256), 0, s, w.cand, w.cnt,                     \
@@ -1942,6 +2027,7 @@ hipError_t launch_mfma_candidates(hipStream_t s, int metric, const void* slab_bf
             VL_RLAUNCH(8) VL_RLAUNCH(16) VL_RLAUNCH(24) VL_RLAUNCH(32) VL_RLAUNCH(48)
 #undef VL_RLAUNCH
 #undef VL_RLAUNCH2
+#undef VL_ROWS_GO
             if (!r_launched) return hipErrorInvalidValue;
             if (info) {
                 info->ksteps = (int)(ldb / 16);
@@ -2052,6 +2138,26 @@ hipError_t launch_mfma_candidates(hipStream_t s, int metric, const void* slab_bf
     hipLaunchKernelGGL(k_select_candidates, dim3((nq + 3) / 4), dim3(256), 0, s, w.cand, w.cnt, (uint32_t)MFMA_CAND_CAP, nq,
                                (const float*)w.thr, out_lists);
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_mfma_candidates(hipStream_t s, int metric, const void* slab_bf16, const float* row_norm,
+                                  const float* row_sqnorm,
+                                  const double* q64, uint32_t nq, uint64_t n_rows, uint32_t dim,
+                                  const MfmaScratch& w, Cand32* out_lists, MfmaLaunchInfo* info, bool queries_prepared)
+{
+    return mfma_candidates(s, metric, slab_bf16, row_norm, row_sqnorm, q64, nq, n_rows, dim, w, out_lists, info, queries_prepared,
+                           nullptr);
+}
+
+hipError_t launch_mfma_candidates_masked(hipStream_t s, int metric, const void* slab_frag, const float* row_norm,
+                                         const float* row_sqnorm, const double* q64, uint32_t nq, uint64_t n_rows, uint32_t dim,
+                                         const MfmaScratch& w, const unsigned long long* const* keep_of, Cand32* out_lists,
+                                         MfmaLaunchInfo* info)
+{
+    if (!keep_of) return hipErrorInvalidValue;
+    return mfma_candidates(s, metric, slab_frag, row_norm, row_sqnorm, q64, nq, n_rows, dim, w, out_lists, info, false, keep_of);
 }
 
 // The filter with thresholds the caller already knows (a batch of range queries): the queries' bf16 rows, the cleared

@@ -113,6 +113,16 @@ hipError_t launch_mfma_candidates(hipStream_t s, int metric, const void* slab_bf
                                   const MfmaScratch& w, Cand32* out_lists, MfmaLaunchInfo* info = nullptr,
                                   bool queries_prepared = false);
 
+// launch_mfma_candidates for queries that each exclude rows: keep_of is a DEVICE table of nq
+// pointers, keep_of[q] = query q's keep bitmap (bit p & 63 of word p >> 6 set iff row p qualifies, no bit at or past
+// n_rows, at least ceil(n_rows / 64) words); one shared filter is nq equal pointers.  The table must be written on
+// stream s before this call.  A list holds kept rows only: min(64, kept rows of q) entries unless cnt[q] overflowed.
+// The row-stationary kernel only (mfma_rows_kernel(dim)); slab_frag is the fragment-major slab.
+hipError_t launch_mfma_candidates_masked(hipStream_t s, int metric, const void* slab_frag, const float* row_norm,
+                                         const float* row_sqnorm, const double* q64, uint32_t nq, uint64_t n_rows, uint32_t dim,
+                                         const MfmaScratch& w, const unsigned long long* const* keep_of, Cand32* out_lists,
+                                         MfmaLaunchInfo* info = nullptr);
+
 // A batch of range queries: the same pass-1 kernel with thresholds that are known before the first
 // launch.  w.thr[q] = the smallest key that is not provably below the query's min_score (+inf: no candidates for this
 // query), written by the caller on stream s; one launch over all rows appends every row with key >= thr[q] to
