@@ -173,6 +173,30 @@ int vl_index_set_delete_bounce(vl_index *h, uint64_t bytes);
  * bounce buffer, bytes written to device memory, microseconds from the first launch to the end of the synchronisation. */
 int vl_index_last_delete(const vl_index *h, uint64_t *out6);
 
+/* NEW capability (single-GPU flat handles): replace the values of a stored row in place.  update(id, v) rewrites the FIRST row
+ * carrying `id` (vl_index_get_vector's rule; afterwards get_vector(id) returns v bit for bit) and, on the device, every copy
+ * derived from it that exists for the row.  Length, row order, every other row, the ids, every filter / exclusion / group
+ * token and its resolved state, and clones made earlier stay as they are; where delete + add would move the row to the end
+ * and compact everything behind it, nothing moves.  Afterwards the handle answers every entry point as a flat index built
+ * from the same (id, values) list in the same order.  VL_ERR_DIM_MISMATCH if len != dim, VL_ERR_NOT_FOUND ("Vector ID {id}
+ * does not exist") if no row carries the id, VL_ERR_INVALID_ARG (the message says which) on HNSW and multi-GPU handles. */
+int vl_index_update(vl_index *h, uint64_t id, const double *values, uint64_t len);
+
+/* n updates in one call; `values` is [n, dim] f64 on the host.  The index is left in exactly the state of the loop
+ * `for (i < n) contains(ids[i]) ? update(ids[i], values_i) : (insert_missing ? add(ids[i], values_i) : fail)`: a repeated id
+ * keeps its last values; with insert_missing != 0 an absent id is appended once (where its first occurrence falls among the
+ * appended rows, holding its last values) through the add path.  All or nothing: VL_ERR_NOT_FOUND (an absent id with
+ * insert_missing == 0; "Vector ID {id} does not exist") and VL_ERR_INVALID_ARG (null pointers with n > 0; HNSW and
+ * multi-GPU handles) are decided before any device write, and then nothing has changed.  n == 0 is VL_OK.  *out_updated =
+ * distinct rows rewritten, *out_inserted = rows appended (either may be null).  DESIGN.md section 25. */
+int vl_index_update_bulk(vl_index *h, const uint64_t *ids, const double *values, uint64_t n, int insert_missing,
+                         uint64_t *out_updated, uint64_t *out_inserted);
+
+/* Diagnostic (single-GPU flat handles): the last vl_index_update / vl_index_update_bulk (all zero if it did nothing).  out7 =
+ * rows rewritten, rows appended, rows rewritten in the row-major bf16 copy, in the fragment-major bf16 copy, in the int8
+ * copy, staging chunks, microseconds from the first launch to the end of the synchronisation. */
+int vl_index_last_update(const vl_index *h, uint64_t *out7);
+
 /* search(query, k, metric) (src/index/flat.rs:98-119): writes min(k, len) results, best first,
  * ties in insertion order.  out_ids/out_scores must hold min(k, len) entries; a caller that sized its
  * buffers from an earlier vl_index_len() passes k = min(k, capacity) -- results for a smaller k are a prefix

@@ -61,6 +61,7 @@ int main(void)
     if (vl_index_len(idx) != 2) return 1;
     CHECK(vl_index_delete_bulk(idx, (const uint64_t[]){3, 3, 99}, 3, &n)); /* n deletes in one pass: a repeat and an absent id are no-ops */
     if (n != 1 || vl_index_len(idx) != 1) return 1;
+    if (vl_index_update(idx, 1, rows[1], 3) != VL_OK || vl_index_update(idx, 2, rows[0], 3) != VL_ERR_NOT_FOUND) return 1; /* new values in place; "Vector ID 2 does not exist" */
 
     /* the same index over two GPUs of the node in this one process (here: the same card twice), rows sharded:
      * identical answers, no rank processes, no id handshake */

@@ -42,6 +42,9 @@ extern "C" {
     fn vl_index_delete_bulk(h: *mut vl_index, ids: *const u64, n_ids: u64, out_removed: *mut u64) -> c_int;
     fn vl_index_set_delete_bounce(h: *mut vl_index, bytes: u64) -> c_int;
     fn vl_index_last_delete(h: *const vl_index, out6: *mut u64) -> c_int;
+    fn vl_index_update(h: *mut vl_index, id: u64, values: *const f64, len: u64) -> c_int;
+    fn vl_index_update_bulk(h: *mut vl_index, ids: *const u64, values: *const f64, n: u64, insert_missing: c_int, out_updated: *mut u64, out_inserted: *mut u64) -> c_int;
+    fn vl_index_last_update(h: *const vl_index, out7: *mut u64) -> c_int;
     fn vl_index_search(h: *const vl_index, query: *const f64, q_len: u64, k: u64, metric: c_int, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_cap(h: *const vl_index, query: *const f64, q_len: u64, k: u64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_batch_cap(h: *const vl_index, queries: *const f64, nq: u64, q_len: u64, k: u64, metric: c_int, out_stride: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
@@ -303,6 +306,40 @@ impl GpuFlatIndex {
     /// Bytes of the buffer deletes compact through; 0 = the default 64 MB (`vl_index_set_delete_bounce`, a diagnostic knob).
     pub fn set_delete_bounce(&mut self, bytes: u64) {
         unsafe { vl_index_set_delete_bounce(self.0.raw, bytes) };
+    }
+    /// Replace, in place, the values (and text / metadata) of the first row carrying `vector.id` (`vl_index_update`): the
+    /// row keeps its position, every filter and group token its resolved state.  `Err("Vector ID {id} does not exist")`
+    /// if no row carries the id; `Err("Vector dimension mismatch")` for a row of another length.
+    pub fn update(&mut self, vector: Vector) -> Result<(), String> {
+        match unsafe { vl_index_update(self.0.raw, vector.id, vector.values.as_ptr(), vector.values.len() as u64) } {
+            VL_OK => {
+                self.0.side.insert(vector.id, (vector.text, vector.metadata));
+                Ok(())
+            }
+            _ => Err(last_error()),
+        }
+    }
+    /// `for (id, row) in ids.zip(rows) { if contains(id) { update } else if insert_missing { add } else { fail } }` in one
+    /// call, all or nothing (`vl_index_update_bulk`): `values` is `[ids.len(), dim]` row-major; a repeated id keeps its last
+    /// values, an absent id is appended once.  Returns (rows rewritten, rows appended).
+    pub fn update_many(&mut self, ids: &[u64], values: &[f64], insert_missing: bool) -> Result<(u64, u64), String> {
+        if values.len() != ids.len() * self.0.dim {
+            return Err("Vector dimension mismatch".to_string());
+        }
+        let (mut updated, mut inserted) = (0u64, 0u64);
+        match unsafe {
+            vl_index_update_bulk(self.0.raw, ids.as_ptr(), values.as_ptr(), ids.len() as u64, insert_missing as c_int, &mut updated, &mut inserted)
+        } {
+            VL_OK => Ok((updated, inserted)),
+            _ => Err(last_error()),
+        }
+    }
+    /// The last `update` / `update_many`: rows rewritten, rows appended, rows rewritten in the row-major bf16, the
+    /// fragment-major bf16 and the int8 copy, staging chunks, microseconds on the device (`vl_index_last_update`).
+    pub fn last_update(&self) -> [u64; 7] {
+        let mut out = [0u64; 7];
+        unsafe { vl_index_last_update(self.0.raw, out.as_mut_ptr()) };
+        out
     }
 }
 

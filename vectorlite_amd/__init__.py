@@ -494,6 +494,21 @@ def _search_mmr(L, h, query, k: int, fetch_k: int, lambda_mult: float, metric: i
     return ids[:m].copy(), scores[:m].copy()
 
 
+def _update_rows(L, h, dim: int, ids, values, insert_missing: bool) -> Tuple[int, int]:
+    """vl_index_update_bulk -> (rows rewritten, rows appended); the library's refusals as IndexOpError."""
+    ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64)).ravel()
+    vals = _f64(values)
+    if vals.size != ids.size * dim:
+        raise ValueError("values must be [n, dim]")
+    upd, ins = C.c_uint64(0), C.c_uint64(0)
+    rc = L.vl_index_update_bulk(h, _pu64(ids), C.c_void_p(vals.ctypes.data), ids.size, 1 if insert_missing else 0,
+                                C.byref(upd), C.byref(ins))
+    if rc in (VL_ERR_NOT_FOUND, VL_ERR_INVALID_ARG):
+        raise IndexOpError(_last_error())
+    _raise(rc)
+    return int(upd.value), int(ins.value)
+
+
 class FlatIndex:
     """GPU-resident counterpart of `FlatIndex` (src/index/flat.rs:60-135).
 
@@ -564,6 +579,34 @@ class FlatIndex:
         out = (C.c_uint64 * 6)()
         _raise(self._L.vl_index_last_delete(self._h, out))
         return dict(zip(("removed", "moved", "direct_launches", "bounced_segments", "bytes_written", "micros"), (int(v) for v in out)))
+
+    def update(self, vector: Vector) -> None:
+        """Replace, in place, the values (and text / metadata) of the first row carrying vector.id (vl_index_update): the row
+        keeps its position, every filter / group token its resolved state.  IndexOpError("Vector ID {id} does not exist")
+        if no row carries the id; single-GPU flat handles only."""
+        vals = _f64(vector.values).ravel()
+        rc = self._L.vl_index_update(self._h, int(vector.id), _pf64(vals), vals.size)
+        if rc in (VL_ERR_NOT_FOUND, VL_ERR_INVALID_ARG):
+            raise IndexOpError(_last_error())
+        _raise(rc)
+        self._meta[int(vector.id)] = (vector.text, vector.metadata)
+
+    def update_rows(self, ids, values, insert_missing: bool = False) -> Tuple[int, int]:
+        """`for id, v in zip(ids, values): update(id, v) if id in index else (add(id, v) if insert_missing else fail)` in
+        one call (vl_index_update_bulk), all or nothing: a repeated id keeps its last values, an absent id is appended
+        once.  `values`: [n, dim] f64 on the host.  Returns (rows rewritten, rows appended)."""
+        return _update_rows(self._L, self._h, self.dimension(), ids, values, insert_missing)
+
+    def upsert_rows(self, ids, values) -> Tuple[int, int]:
+        """update_rows(ids, values, insert_missing=True)."""
+        return self.update_rows(ids, values, insert_missing=True)
+
+    def last_update(self) -> Dict[str, int]:
+        """The last update / update_rows on this (single-GPU) handle: rows rewritten and appended, rows rewritten in the
+        row-major bf16, fragment-major bf16 and int8 copies, staging chunks, microseconds on the device."""
+        out = (C.c_uint64 * 7)()
+        _raise(self._L.vl_index_last_update(self._h, out))
+        return dict(zip(("updated", "inserted", "bf16_rows", "bf16_frag_rows", "int8_rows", "chunks", "micros"), (int(v) for v in out)))
 
     def search(self, query, k: int, similarity_metric: int = SimilarityMetric.Cosine, filter=None,
                exclude=None) -> List[SearchResult]:
@@ -1401,6 +1444,21 @@ class HNSWIndex:
             raise IndexOpError(_last_error())  # "Vector ID {id} does not exist" (:401-403)
         _raise(rc)
         return int(removed.value)
+
+    def update(self, vector: Vector) -> None:
+        """Not served on HNSW handles (the graph's edge keys are distances of the old values): the library's error."""
+        vals = _f64(vector.values).ravel()
+        rc = self._L.vl_index_update(self._h, int(vector.id), _pf64(vals), vals.size)
+        if rc in (VL_ERR_NOT_FOUND, VL_ERR_INVALID_ARG):
+            raise IndexOpError(_last_error())
+        _raise(rc)
+
+    def update_rows(self, ids, values, insert_missing: bool = False) -> Tuple[int, int]:
+        """Not served on HNSW handles: the library's error."""
+        return _update_rows(self._L, self._h, self.dimension(), ids, values, insert_missing)
+
+    def upsert_rows(self, ids, values) -> Tuple[int, int]:
+        return self.update_rows(ids, values, insert_missing=True)
 
     def _raise_search(self, rc: int, requested: int):
         if rc == VL_ERR_METRIC_MISMATCH:

@@ -16,7 +16,7 @@ SO_PATH = os.environ.get("VL_LIB_PATH") or os.path.join(_HERE, "libvectorlite_am
 # every symbol include/vectorlite_amd.h declares
 SYMBOLS = [
     "vl_flat_create", "vl_flat_from_rows", "vl_flat_create_multi", "vl_index_parts", "vl_hnsw_create", "vl_hnsw_create_ex", "vl_index_type", "vl_index_metric", "vl_index_search_ef", "vl_index_clone", "vl_index_destroy", "vl_index_reserve",
-    "vl_index_add", "vl_index_add_bulk", "vl_index_add_embeddings_f32", "vl_index_delete", "vl_index_delete_bulk", "vl_index_set_delete_bounce", "vl_index_last_delete", "vl_index_search", "vl_index_search_batch", "vl_index_search_cap", "vl_index_search_batch_cap",
+    "vl_index_add", "vl_index_add_bulk", "vl_index_add_embeddings_f32", "vl_index_delete", "vl_index_delete_bulk", "vl_index_set_delete_bounce", "vl_index_last_delete", "vl_index_update", "vl_index_update_bulk", "vl_index_last_update", "vl_index_search", "vl_index_search_batch", "vl_index_search_cap", "vl_index_search_batch_cap",
     "vl_index_filter_create", "vl_index_filter_create_excluding", "vl_index_filter_rows", "vl_index_filter_destroy", "vl_index_search_filtered", "vl_index_search_batch_filtered", "vl_index_search_batch_filters", "vl_index_last_filtered_batch", "vl_index_set_masked_batch", "vl_index_last_masked_batch","vl_index_search_range", "vl_index_search_range_batch", "vl_index_last_range_batch",
     "vl_index_last_range_batch_candidates", "vl_index_search_mmr",
     "vl_index_groups_create", "vl_index_groups_rows", "vl_index_groups_destroy", "vl_index_search_grouped",
@@ -80,6 +80,9 @@ def load() -> C.CDLL:
     sig("vl_index_delete_bulk", i32, [vp, p_u64, u64, p_u64])
     sig("vl_index_set_delete_bounce", i32, [vp, u64])
     sig("vl_index_last_delete", i32, [vp, p_u64])
+    sig("vl_index_update", i32, [vp, u64, p_f64, u64])
+    sig("vl_index_update_bulk", i32, [vp, p_u64, vp, u64, i32, p_u64, p_u64])
+    sig("vl_index_last_update", i32, [vp, p_u64])
     sig("vl_index_search", i32, [vp, p_f64, u64, u64, i32, p_u64, p_f64, p_u64])
     sig("vl_index_search_batch", i32, [vp, p_f64, u64, u64, u64, i32, p_u64, p_f64, p_u64])
     # the hot single-query entry takes raw addresses (no ctypes pointer objects made per call)

@@ -109,6 +109,19 @@ class Collection:
                 raise VectorNotFound(str(e).replace("does not exist", "not found")) from e
             raise VectorLiteError(str(e)) from e
 
+    def update_text(self, id: int, text: str, metadata: Optional[Any], embedding_function) -> None:
+        """Re-embed a stored chunk in place (a changed text, a corrected vector): the row keeps its id and its position, and
+        filters made earlier stay resolved (FlatIndex.update).  Flat collections only.  The index row and the side table of
+        text and metadata change under one lock: two updates of one id leave the values and the text of the same call."""
+        embedding = embedding_function.generate_embedding(text)  # outside any lock
+        try:
+            with self._lock:
+                self.index.update(Vector(id=id, values=embedding, text=text, metadata=metadata))
+        except IndexOpError as e:
+            if "does not exist" in str(e):
+                raise VectorNotFound(f"Vector ID {id} not found") from e
+            raise VectorLiteError(str(e)) from e
+
     def search_text(self, query_text: str, k: int, similarity_metric: SimilarityMetric, embedding_function,
                     where: Optional[Callable[[Any], bool]] = None) -> List[SearchResult]:
         """`where`: a predicate on a row's metadata; only rows for which it holds are ranked (an exact filtered search
@@ -250,6 +263,9 @@ class VectorLiteClient:
 
     def delete_from_collection(self, collection_name: str, id: int) -> None:
         self._get(collection_name).delete(id)
+
+    def update_text_in_collection(self, collection_name: str, id: int, text: str, metadata: Optional[Any] = None) -> None:
+        self._get(collection_name).update_text(id, text, metadata, self.embedding_function)
 
     def get_vector_from_collection(self, collection_name: str, id: int) -> Optional[Vector]:
         return self._get(collection_name).get_vector(id)

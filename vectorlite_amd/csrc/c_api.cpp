@@ -308,6 +308,56 @@ int vl_index_last_delete(const vl_index* h, uint64_t* out6)
     return VL_OK;
 }
 
+namespace {
+// in-place updates serve single-GPU flat handles only; says which other kind the handle is
+int update_refused(const vl_index* h)
+{
+    if (h->hnsw) {
+        vl::set_last_error("update needs a single-GPU flat index handle: this is an HNSW handle (its graph's edge keys are distances "
+                           "of the stored values)");
+        return VL_ERR_INVALID_ARG;
+    }
+    if (h->multi) {
+        vl::set_last_error("update needs a single-GPU flat index handle: this is a multi-GPU handle (its replicas and shards are "
+                           "not updated in place)");
+        return VL_ERR_INVALID_ARG;
+    }
+    return VL_OK;
+}
+}  // namespace
+
+int vl_index_update(vl_index* h, uint64_t id, const double* values, uint64_t len)
+{
+    return guarded([&]() -> int {
+        if (!h) return VL_ERR_INVALID_ARG;
+        if (!h->flat) return update_refused(h);
+        return h->flat->update(id, values, len);
+    });
+}
+
+int vl_index_update_bulk(vl_index* h, const uint64_t* ids, const double* values, uint64_t n, int insert_missing,
+                         uint64_t* out_updated, uint64_t* out_inserted)
+{
+    return guarded([&]() -> int {
+        if (out_updated) *out_updated = 0;
+        if (out_inserted) *out_inserted = 0;
+        if (!h) return VL_ERR_INVALID_ARG;
+        if (!h->flat) return update_refused(h);
+        if (n && (!ids || (!values && h->flat->dimension()))) {
+            vl::set_last_error("update_bulk: null ids or values with n > 0");
+            return VL_ERR_INVALID_ARG;
+        }
+        return h->flat->update_bulk(ids, values, n, insert_missing != 0, out_updated, out_inserted);
+    });
+}
+
+int vl_index_last_update(const vl_index* h, uint64_t* out7)
+{
+    if (!h || !h->flat || !out7) return VL_ERR_INVALID_ARG;
+    h->flat->last_update(out7);
+    return VL_OK;
+}
+
 int vl_index_search(const vl_index* h, const double* query, uint64_t q_len, uint64_t k, int metric,
                     uint64_t* out_ids, double* out_scores, uint64_t* out_n)
 {

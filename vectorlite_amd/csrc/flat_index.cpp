@@ -7,6 +7,7 @@
 // src/index/flat.rs:106-114).  There is no CPU compute fallback.
 #include "flat_index.hpp"
 #include "delete_plan.hpp"
+#include "update_plan.hpp"
 #include "lazy_buffers.hpp"
 #include "shard.hpp"
 #include "score_bound.hpp"
@@ -607,7 +608,12 @@ int GpuFlatIndex::add_bulk(const uint64_t* ids, const double* values, uint64_t n
     if (!ids || (!values && dim_)) return ERR_INVALID_ARG;
     std::unique_lock<RwLock> lk(mu_);
     VL_HIP(hipSetDevice(device_));
+    return add_bulk_locked(ids, values, n, validate, values_on_device, src_device);
+}
 
+int GpuFlatIndex::add_bulk_locked(const uint64_t* ids, const double* values, uint64_t n, bool validate, bool values_on_device,
+                                  int src_device)
+{
     uint64_t n_take = n;
     int rc_after = OK;
     if (validate) {  // n sequential add() calls: stop at the first duplicate id (src/index/flat.rs:86-88)
@@ -651,6 +657,123 @@ int GpuFlatIndex::add_bulk(const uint64_t* ids, const double* values, uint64_t n
     ids_.insert(ids_.end(), ids, ids + n_take);
     ++mutations_;
     return rc_after;
+}
+
+// In-place update / upsert.  Nothing moves: ids_, the row order, mutations_ and the watermarks of the
+// lazy copies stay as they are; what changes is the f64 master row and every copy derived from it that exists for the row.
+int GpuFlatIndex::update(uint64_t id, const double* values, uint64_t len)
+{
+    if (len != dim_ || (!values && dim_)) {
+        for (auto& v : last_update_) v.store(0, std::memory_order_relaxed);  // a refused call did nothing
+        if (len == dim_) return ERR_INVALID_ARG;
+        set_dim_mismatch(dim_, len);
+        set_last_error("Vector dimension mismatch");
+        return ERR_DIM_MISMATCH;
+    }
+    return update_bulk(&id, values, 1, /*insert_missing=*/false, nullptr, nullptr);
+}
+
+int GpuFlatIndex::update_bulk(const uint64_t* ids, const double* values, uint64_t n, bool insert_missing, uint64_t* out_updated,
+                              uint64_t* out_inserted)
+{
+    if (out_updated) *out_updated = 0;
+    if (out_inserted) *out_inserted = 0;
+    std::unique_lock<RwLock> lk(mu_);
+    for (auto& v : last_update_) v.store(0, std::memory_order_relaxed);  // a call that does nothing reads as all zero
+    if (n && (!ids || (!values && dim_))) {
+        set_last_error("update_bulk: null ids or values with n > 0");
+        return ERR_INVALID_ARG;
+    }
+    if (n == 0) return OK;
+
+    // every refusal is decided here, before the device is touched
+    const UpdatePlan plan = update_plan(ids_.data(), ids_.size(), ids, n, insert_missing);
+    if (plan.refused) {
+        set_last_error("Vector ID " + std::to_string(plan.missing_id) + " does not exist");
+        return ERR_NOT_FOUND;
+    }
+    VL_HIP(hipSetDevice(device_));
+    const uint64_t m = plan.pos.size(), n_add = plan.append_ids.size();
+    // room for the appended rows first: growth is the one step that can run out of memory, and it changes no row
+    if (n_add) VL_TRY(ensure_capacity(ids_.size() + n_add));
+
+    uint64_t in_copy[3] = {0, 0, 0}, chunks = 0, micros = 0;
+    if (m && dim_) {
+        const size_t want_bytes = bounce_want_ ? bounce_want_ : BOUNCE_BYTES;
+        const uint64_t stage_rows = std::min<uint64_t>(update_stage_rows(want_bytes, dim_), m);
+        const size_t need_bytes = std::max<size_t>(want_bytes, update_stage_bytes(stage_rows, dim_));
+        if (d_bounce_ && bounce_bytes_ < need_bytes) {
+            (void)hipFree(d_bounce_);
+            d_bounce_ = nullptr;
+            bounce_bytes_ = 0;
+        }
+        if (!d_bounce_) {
+            VL_HIP(hipMalloc(&d_bounce_, need_bytes));
+            bounce_bytes_ = need_bytes;
+        }
+        char* stage = static_cast<char*>(d_bounce_);
+        double* d_rows = reinterpret_cast<double*>(stage);
+        uint32_t* d_pos = reinterpret_cast<uint32_t*>(stage + update_stage_pos_offset(stage_rows, dim_));
+        uint8_t* d_newfl = reinterpret_cast<uint8_t*>(stage + update_stage_flag_offset(stage_rows, dim_));
+        std::vector<double> h_rows(stage_rows * dim_);
+        std::vector<uint32_t> h_pos(stage_rows);
+        std::vector<uint8_t> h_fl(stage_rows);
+        // the lazy copies as they stand (mu_ is held exclusively: no search is converting rows)
+        struct Copy {
+            int kind;
+            void* base;
+            float *a, *b;
+            uint64_t rows_done;
+        } const copies[3] = {{UPDATE_COPY_BF16, d_slab16_, d_norm16_, d_sqnorm_, d_slab16_ ? slab16_rows_ : 0},
+                             {UPDATE_COPY_BF16_FRAG, d_slab16f_, d_norm16_, d_sqnorm_, d_slab16f_ ? slab16f_rows_ : 0},
+                             {UPDATE_COPY_I8, d_slab8_, d_sr8_, d_norm8_, d_slab8_ ? slab8_rows_ : 0}};
+        const auto t0 = std::chrono::steady_clock::now();
+        for (const auto& cut : update_chunks(m, stage_rows)) {
+            const uint64_t c = cut.second - cut.first;
+            for (uint64_t j = 0; j < c; ++j) {
+                std::memcpy(&h_rows[j * dim_], values + plan.src[cut.first + j] * dim_, dim_ * sizeof(double));
+                h_pos[j] = (uint32_t)plan.pos[cut.first + j];
+            }
+            VL_HIP(hipMemcpyAsync(d_rows, h_rows.data(), c * dim_ * sizeof(double), hipMemcpyHostToDevice, mut_stream_));
+            VL_HIP(hipMemcpyAsync(d_pos, h_pos.data(), c * sizeof(uint32_t), hipMemcpyHostToDevice, mut_stream_));
+            VL_HIP(launch_update_rows(mut_stream_, d_rows, d_pos, (uint32_t)c, d_master_, d_slab_, d_inv_norm_, d_flags_, d_newfl,
+                                      d_stats_, (uint32_t)dim_, ld_));
+            for (const Copy& cp : copies)
+                if (cp.base && cp.rows_done)
+                    VL_HIP(launch_update_copies(mut_stream_, cp.kind, d_rows, d_pos, (uint32_t)c, cp.rows_done, (uint32_t)dim_, cp.base,
+                                                cp.a, cp.b));
+            VL_HIP(hipMemcpyAsync(h_fl.data(), d_newfl, c, hipMemcpyDeviceToHost, mut_stream_));
+            VL_HIP(hipStreamSynchronize(mut_stream_));  // the host buffers are reused by the next chunk
+            for (uint64_t j = 0; j < c; ++j) {
+                const uint64_t p = h_pos[j];
+                const bool was = row_flags_[p] & ROW_OUT_OF_DOMAIN, is = h_fl[j] & ROW_OUT_OF_DOMAIN;
+                if (was && !is) --n_out_of_domain_;
+                if (!was && is) ++n_out_of_domain_;
+                row_flags_[p] = h_fl[j];
+                for (int k = 0; k < 3; ++k)
+                    if (copies[k].base && p < copies[k].rows_done) ++in_copy[k];
+            }
+            ++chunks;
+        }
+        IngestStats st;
+        VL_HIP(hipMemcpyAsync(&st, d_stats_, sizeof(st), hipMemcpyDeviceToHost, mut_stream_));
+        VL_HIP(hipStreamSynchronize(mut_stream_));
+        micros = (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+        double mn;
+        std::memcpy(&mn, &st.max_norm_bits, sizeof(mn));
+        if (mn > max_row_norm_) max_row_norm_ = mn;  // an upper bound over rows ever stored: only ever raised
+    }
+    if (n_add) {  // the absent ids, once each, through the add path (ids_ grows, mutations_ is bumped once)
+        std::vector<double> rows(n_add * dim_);
+        for (uint64_t j = 0; j < n_add; ++j)
+            if (dim_) std::memcpy(&rows[j * dim_], values + plan.append_src[j] * dim_, dim_ * sizeof(double));
+        VL_TRY(add_bulk_locked(plan.append_ids.data(), rows.data(), n_add, /*validate=*/true, /*values_on_device=*/false, -1));
+    }
+    const uint64_t st7[7] = {m, n_add, in_copy[0], in_copy[1], in_copy[2], chunks, micros};
+    for (int i = 0; i < 7; ++i) last_update_[i].store(st7[i], std::memory_order_relaxed);
+    if (out_updated) *out_updated = m;
+    if (out_inserted) *out_inserted = n_add;
+    return OK;
 }
 
 // Order-preserving removal of one row (Vec::retain, src/index/flat.rs:94): rows behind it move up

@@ -250,6 +250,24 @@ public:
     {
         for (int i = 0; i < 6; ++i) out[i] = last_delete_[i].load(std::memory_order_relaxed);
     }
+    // NEW (no reference counterpart): replaces the values of the FIRST row carrying `id` (get_vector's rule) in place:
+    // length, row order, ids_, mutations_ and every token's resolved state stay as they are.  ERR_NOT_FOUND: no such row.
+    int update(uint64_t id, const double* values, uint64_t len);
+    // the state the loop `contains(ids[i]) ? update(ids[i], values_i) : (insert_missing ? add(ids[i], values_i) : fail)`
+    // leaves (update_plan.hpp): a repeated id keeps its last values, an absent id is appended once.  A refusal
+    // (ERR_NOT_FOUND: an absent id without insert_missing) is decided before any device write.  The rewritten rows go up in
+    // position-sorted chunks through the bounce buffer (set_delete_bounce sizes it), k_update_rows rewrites master, slab,
+    // inv_norm and flags, k_update_copies the rows of each lazy copy below its watermark; appended rows take the add
+    // path.  *out_updated = distinct rows rewritten, *out_inserted = rows appended (either may be null).  DESIGN.md section 25.
+    int update_bulk(const uint64_t* ids, const double* values, uint64_t n, bool insert_missing, uint64_t* out_updated,
+                    uint64_t* out_inserted);
+    // the last update / update_bulk on this handle (all zero if it did nothing): rows rewritten, rows appended, rows
+    // rewritten in the row-major bf16 copy, in the fragment-major one, in the int8 copy, staging chunks, microseconds from
+    // the first launch to the end of the last synchronisation
+    void last_update(uint64_t out[7]) const
+    {
+        for (int i = 0; i < 7; ++i) out[i] = last_update_[i].load(std::memory_order_relaxed);
+    }
     bool contains(uint64_t id) const;                       // O(1) after the first call (the duplicate-id table)
     int find_first(uint64_t id, uint64_t* out_pos) const;   // first row with that id (get_vector's rule); ERR_NOT_FOUND
     int get_row_at(uint64_t pos, double* out) const;
@@ -431,6 +449,8 @@ private:
     GpuFlatIndex(uint64_t dim, int device);
     int ensure_capacity(uint64_t rows);  // caller holds the unique lock
     int ingest_range(uint64_t first, uint64_t n);
+    // add_bulk's body; the caller holds the unique lock and has set the device
+    int add_bulk_locked(const uint64_t* ids, const double* values, uint64_t n, bool validate, bool values_on_device, int src_device);
     int remove_position(uint64_t pos);
     void rebuild_id_counts() const;
     Workspace* acquire_ws() const;
@@ -554,7 +574,7 @@ private:
     uint64_t cap_ = 0;  // rows every array holds (the minimum of the four below)
     uint64_t cap_master_ = 0, cap_slab_ = 0, cap_inv_ = 0, cap_flags_ = 0;
     hipStream_t mut_stream_ = nullptr;
-    void* d_bounce_ = nullptr;  // delete compaction buffer
+    void* d_bounce_ = nullptr;  // delete compaction buffer; an update's staging buffer
     size_t bounce_bytes_ = 0;
     size_t bounce_want_ = 0;    // set_delete_bounce: what remove_bulk plans with and allocates (0: BOUNCE_BYTES)
 
@@ -611,6 +631,7 @@ private:
     mutable std::atomic<uint64_t> last_mbatch_[5] = {};
     std::atomic<int> masked_batch_{2};  // MASKED_BATCH_AUTO
     std::atomic<uint64_t> last_delete_[6] = {};
+    std::atomic<uint64_t> last_update_[7] = {};
     mutable std::mutex prof_mu_;
     mutable uint64_t prof_n_ = 0;
     mutable double prof_ms_ = 0.0;

@@ -1806,6 +1806,47 @@ __global__ __launch_bounds__(256) void k_hnsw_dist(const double* __restrict__ ma
 // ---------------------------------------------------------------------------------------------
 // Ingest: f64 master rows -> f32 slab + 1/|row| cache + domain flags
 // ---------------------------------------------------------------------------------------------
+// One row, one wave: `src` is the row's f64 values (the master row itself, or an update's staged copy of it), `row` the
+// position whose slab row, inv_norm and flag it writes.  Lane 0 returns the flag it stored.
+__device__ __forceinline__ uint8_t ingest_row(const double* __restrict__ src, uint64_t row, float* __restrict__ slab,
+                                              float* __restrict__ inv_norm, uint8_t* __restrict__ flags,
+                                              IngestStats* __restrict__ stats, uint32_t dim, uint32_t ld, int lane)
+{
+    float* dst = slab + row * ld;
+    double ss = 0.0, mx = 0.0;
+    bool bad = false;
+    for (uint32_t c = lane; c < ld; c += WAVE) {
+        const double v = c < dim ? src[c] : 0.0;
+        dst[c] = (float)v;  // round to nearest even
+        ss += v * v;
+        const double av = fabs(v);
+        mx = av > mx ? av : mx;
+        bad |= !(av <= 1.797693134862315708e308);  // inf or NaN
+    }
+#pragma unroll
+    for (int o = WAVE / 2; o >= 1; o >>= 1) {
+        ss += __shfl_xor(ss, o);
+        const double m2 = __shfl_xor(mx, o);
+        mx = m2 > mx ? m2 : mx;
+    }
+    const bool any_bad = __ballot(bad) != 0ull;
+    uint8_t flag = 0;
+    if (lane == 0) {
+        const double norm = sqrt(ss);
+        const bool ood = any_bad || !(mx <= 1099511627776.0 /* 2^40 */) || !(norm <= 1.0e300) ||
+                         (norm != 0.0 && norm < 9.094947017729282e-13 /* 2^-40 */);
+        inv_norm[row] = (norm > 0.0 && !ood) ? (float)(1.0 / norm) : 0.0f;
+        flag = ood ? ROW_OUT_OF_DOMAIN : 0;
+        flags[row] = flag;
+        if (ood) {
+            atomicAdd(&stats->n_out_of_domain, 1u);
+        } else {
+            atomicMax(&stats->max_norm_bits, (unsigned long long)__double_as_longlong(norm));
+        }
+    }
+    return flag;
+}
+
 __global__ __launch_bounds__(256) void k_ingest(const double* __restrict__ master, float* __restrict__ slab,
                                                 float* __restrict__ inv_norm, uint8_t* __restrict__ flags,
                                                 IngestStats* __restrict__ stats, uint64_t n, uint32_t dim,
@@ -1813,38 +1854,37 @@ __global__ __launch_bounds__(256) void k_ingest(const double* __restrict__ maste
 {
     const int lane = lane_id();
     const uint64_t n_waves = (uint64_t)gridDim.x * 4;
-    for (uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += n_waves) {
-        const double* src = master + row * dim;
-        float* dst = slab + row * ld;
-        double ss = 0.0, mx = 0.0;
-        bool bad = false;
-        for (uint32_t c = lane; c < ld; c += WAVE) {
-            const double v = c < dim ? src[c] : 0.0;
-            dst[c] = (float)v;  // round to nearest even
-            ss += v * v;
-            const double av = fabs(v);
-            mx = av > mx ? av : mx;
-            bad |= !(av <= 1.797693134862315708e308);  // inf or NaN
+    for (uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += n_waves)
+        (void)ingest_row(master + row * dim, row, slab, inv_norm, flags, stats, dim, ld, lane);
+}
+
+// In-place update (GpuFlatIndex::update_bulk): staged row i (f64, [m, dim]) replaces the row at
+// position pos[i] -- its master row, copied in 16-byte pieces where V == 16 (dim even: every row of both arrays starts on
+// a 16-byte boundary), and what k_ingest derives from it, by k_ingest's own row body (same lanes, same order of sums: the
+// bits a from-scratch ingest of the new master would write).  out_flags[i] = the row's new flag, for the host's
+// bookkeeping.  Positions are distinct: no two waves write one row.  One wave per row.
+template <int V>
+__global__ __launch_bounds__(256) void k_update_rows(const double* __restrict__ staged, const uint32_t* __restrict__ pos,
+                                                     uint32_t m, double* __restrict__ master, float* __restrict__ slab,
+                                                     float* __restrict__ inv_norm, uint8_t* __restrict__ flags,
+                                                     uint8_t* __restrict__ out_flags, IngestStats* __restrict__ stats,
+                                                     uint32_t dim, uint32_t ld)
+{
+    const int lane = lane_id();
+    const uint32_t n_waves = gridDim.x * 4;
+    for (uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6); i < m; i += n_waves) {
+        const double* src = staged + (uint64_t)i * dim;
+        const uint64_t row = pos[i];
+        double* mrow = master + row * dim;
+        if (V == 16) {
+            const double2* s2 = reinterpret_cast<const double2*>(src);
+            double2* m2 = reinterpret_cast<double2*>(mrow);
+            for (uint32_t c = lane; c < dim / 2; c += WAVE) m2[c] = s2[c];
+        } else {
+            for (uint32_t c = lane; c < dim; c += WAVE) mrow[c] = src[c];
         }
-#pragma unroll
-        for (int o = WAVE / 2; o >= 1; o >>= 1) {
-            ss += __shfl_xor(ss, o);
-            const double m2 = __shfl_xor(mx, o);
-            mx = m2 > mx ? m2 : mx;
-        }
-        const bool any_bad = __ballot(bad) != 0ull;
-        if (lane == 0) {
-            const double norm = sqrt(ss);
-            const bool ood = any_bad || !(mx <= 1099511627776.0 /* 2^40 */) || !(norm <= 1.0e300) ||
-                             (norm != 0.0 && norm < 9.094947017729282e-13 /* 2^-40 */);
-            inv_norm[row] = (norm > 0.0 && !ood) ? (float)(1.0 / norm) : 0.0f;
-            flags[row] = ood ? ROW_OUT_OF_DOMAIN : 0;
-            if (ood) {
-                atomicAdd(&stats->n_out_of_domain, 1u);
-            } else {
-                atomicMax(&stats->max_norm_bits, (unsigned long long)__double_as_longlong(norm));
-            }
-        }
+        const uint8_t flag = ingest_row(src, row, slab, inv_norm, flags, stats, dim, ld, lane);
+        if (lane == 0) out_flags[i] = flag;
     }
 }
 
@@ -2058,6 +2098,22 @@ hipError_t launch_ingest(hipStream_t s, const double* master, float* slab, float
     const uint64_t blocks = (n + 3) / 4;
     const int grid = (int)(blocks < 8192 ? blocks : 8192);
     hipLaunchKernelGGL(k_ingest, dim3(grid), dim3(256), 0, s, master, slab, inv_norm, flags, stats, n, dim, ld);
+    return hipGetLastError();
+}
+
+hipError_t launch_update_rows(hipStream_t s, const double* staged, const uint32_t* pos, uint32_t m, double* master, float* slab,
+                              float* inv_norm, uint8_t* flags, uint8_t* out_flags, IngestStats* stats, uint32_t dim, uint32_t ld)
+{
+    if (m == 0) return hipSuccess;
+    const uint32_t blocks = (m + 3) / 4;
+    const dim3 grid(blocks < 8192 ? blocks : 8192);
+    const uintptr_t both = reinterpret_cast<uintptr_t>(staged) | reinterpret_cast<uintptr_t>(master);
+    if (dim % 2 == 0 && both % 16 == 0)
+        hipLaunchKernelGGL(k_update_rows<16>, grid, dim3(256), 0, s, staged, pos, m, master, slab, inv_norm, flags, out_flags, stats,
+                           dim, ld);
+    else
+        hipLaunchKernelGGL(k_update_rows<8>, grid, dim3(256), 0, s, staged, pos, m, master, slab, inv_norm, flags, out_flags, stats,
+                           dim, ld);
     return hipGetLastError();
 }
 

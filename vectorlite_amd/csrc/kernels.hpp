@@ -82,6 +82,12 @@ hipError_t launch_embed_f32(hipStream_t s, const float* emb, uint64_t n, uint32_
 hipError_t launch_ingest(hipStream_t s, const double* master, float* slab, float* inv_norm, uint8_t* flags,
                          IngestStats* stats, uint64_t n, uint32_t dim, uint32_t ld);
 
+// In-place update: staged f64 rows [m, dim] replace the master rows at the DISTINCT positions pos[0..m) (device memory), and
+// their slab rows, inv_norm and flags are derived as launch_ingest derives them; out_flags[i] = the new flag of pos[i];
+// stats->max_norm_bits is raised.  16-byte copies of the master row when dim is even and both arrays are 16-byte aligned.
+hipError_t launch_update_rows(hipStream_t s, const double* staged, const uint32_t* pos, uint32_t m, double* master, float* slab,
+                              float* inv_norm, uint8_t* flags, uint8_t* out_flags, IngestStats* stats, uint32_t dim, uint32_t ld);
+
 // Bulk delete (delete_plan.hpp): copies `rows` rows of `pitch` bytes to dst + r * pitch, r = 0 .. rows - 1, destination
 // row dst_begin + r reading source row d + #{i : keys[i] <= d} of src_base (d = dst_begin + r; keys[i] = r_i - i over the
 // ascending removed positions, on the device).  [c_lo, c_hi] = the shifts of the segment's first and last row.  dst is the

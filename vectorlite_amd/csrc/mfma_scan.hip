@@ -1671,36 +1671,74 @@ __global__ __launch_bounds__(256) void k_prepare_queries(const double* __restric
 
 // f64 master rows -> UNIT-NORMALISED bf16 slab rows [n, ldb] (x/|x| in f64, then f32, then bf16 RNE;
 // zero rows stay zero), plus |row| and |row|^2 rounded once to f32.  One wave per row.
+// The row bodies of the three converters below take the row's f64 values (`src`: the master row, or an update's staged copy
+// of it) and the row number they write, so that k_update_copies rewrites single rows with the converters' own arithmetic.
+__device__ __forceinline__ void rows_bf16_row(const double* __restrict__ src, uint64_t row, uint32_t dim, uint32_t ldb,
+                                              __bf16* __restrict__ out, float* __restrict__ out_nrm,
+                                              float* __restrict__ out_sqn, int lane)
+{
+    double ss = 0.0;
+    for (uint32_t c = lane; c < dim; c += 64) {
+        const double v = src[c];
+        ss += v * v;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
+    const double nrm = sqrt(ss);
+    const double inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
+    for (uint32_t c = lane; c < ldb; c += 64) {
+        const float v = c < dim ? (float)(src[c] * inv) : 0.0f;
+        out[row * ldb + c] = (__bf16)v;
+    }
+    if (lane == 0) {
+        out_nrm[row] = (float)nrm;
+        out_sqn[row] = (float)ss;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_rows_bf16(const double* __restrict__ master, uint64_t n, uint32_t dim,
                                                    uint32_t ldb, __bf16* __restrict__ out, float* __restrict__ out_nrm,
                                                    float* __restrict__ out_sqn)
 {
     const int lane = threadIdx.x & 63;
     const uint64_t n_waves = (uint64_t)gridDim.x * 4;
-    for (uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += n_waves) {
-        double ss = 0.0;
-        for (uint32_t c = lane; c < dim; c += 64) {
-            const double v = master[row * dim + c];
-            ss += v * v;
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
-        const double nrm = sqrt(ss);
-        const double inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
-        for (uint32_t c = lane; c < ldb; c += 64) {
-            const float v = c < dim ? (float)(master[row * dim + c] * inv) : 0.0f;
-            out[row * ldb + c] = (__bf16)v;
-        }
-        if (lane == 0) {
-            out_nrm[row] = (float)nrm;
-            out_sqn[row] = (float)ss;
-        }
-    }
+    for (uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += n_waves)
+        rows_bf16_row(master + row * dim, row, dim, ldb, out, out_nrm, out_sqn, lane);
 }
 
 // The same rows in FRAGMENT-MAJOR order for k_mfma_rows: row r, 16-byte piece p (8 bf16: columns 8 p .. 8 p + 7) goes to
 // byte (((r / 16) * (ldb / 32) + p / 4) * 64 + (p % 4) * 16 + r % 16) * 16 -- per 16-row group and 32-column K-step
 // one 1 KB chunk whose 64 pieces are in MFMA lane order (lane = 16 * (p % 4) + r % 16).  One wave per row.
+// (a row writes only its own 16-byte pieces of each chunk: rewriting row r touches no neighbour's bytes)
+__device__ __forceinline__ void rows_bf16_frag_row(const double* __restrict__ src, uint64_t r, uint32_t dim, uint32_t ldb,
+                                                   uint32_t ks32, unsigned char* __restrict__ out,
+                                                   float* __restrict__ out_nrm, float* __restrict__ out_sqn, int lane)
+{
+    double ss = 0.0;
+    for (uint32_t c = lane; c < dim; c += 64) {
+        const double v = src[c];
+        ss += v * v;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
+    const double nrm = sqrt(ss);
+    const double inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
+    for (uint32_t p = lane; p < ldb / 8; p += 64) {
+        bf16x8 v;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const uint32_t c = 8 * p + e;
+            v[e] = (__bf16)(c < dim ? (float)(src[c] * inv) : 0.0f);
+        }
+        const size_t off = ((((size_t)(r >> 4) * ks32 + (p >> 2)) * 64) + (size_t)((p & 3) * 16 + (uint32_t)(r & 15))) * 16;
+        *reinterpret_cast<bf16x8*>(out + off) = v;
+    }
+    if (lane == 0) {
+        out_nrm[r] = (float)nrm;
+        out_sqn[r] = (float)ss;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_rows_bf16_frag(const double* __restrict__ master, uint64_t row0, uint64_t n,
                                                         uint32_t dim, uint32_t ldb, unsigned char* __restrict__ out,
                                                         float* __restrict__ out_nrm, float* __restrict__ out_sqn)
@@ -1708,33 +1746,8 @@ __global__ __launch_bounds__(256) void k_rows_bf16_frag(const double* __restrict
     const int lane = threadIdx.x & 63;
     const uint64_t n_waves = (uint64_t)gridDim.x * 4;
     const uint32_t ks32 = ldb / 32;
-    for (uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += n_waves) {
-        const double* src = master + i * dim;
-        double ss = 0.0;
-        for (uint32_t c = lane; c < dim; c += 64) {
-            const double v = src[c];
-            ss += v * v;
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
-        const double nrm = sqrt(ss);
-        const double inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
-        const uint64_t r = row0 + i;
-        for (uint32_t p = lane; p < ldb / 8; p += 64) {
-            bf16x8 v;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const uint32_t c = 8 * p + e;
-                v[e] = (__bf16)(c < dim ? (float)(src[c] * inv) : 0.0f);
-            }
-            const size_t off = ((((size_t)(r >> 4) * ks32 + (p >> 2)) * 64) + (size_t)((p & 3) * 16 + (uint32_t)(r & 15))) * 16;
-            *reinterpret_cast<bf16x8*>(out + off) = v;
-        }
-        if (lane == 0) {
-            out_nrm[r] = (float)nrm;
-            out_sqn[r] = (float)ss;
-        }
-    }
+    for (uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += n_waves)
+        rows_bf16_frag_row(master + i * dim, row0 + i, dim, ldb, ks32, out, out_nrm, out_sqn, lane);
 }
 
 // x > 0 in f64 -> the smallest f32 >= x (x below FLT_MAX)
@@ -1750,51 +1763,82 @@ __device__ __forceinline__ float f32_up(double x)
 // f32, so k_i = rint(x^_i / s) stays in [-127, 127] without clamping; r >= |x/|x| - s k| in real arithmetic: the f64
 // residual inflated for its own rounding and for x^'s error against the exact unit row ((dim + 8) 2^-52 each, far
 // above the worst case), rounded up to f32.  Zero rows: s = r = 0, k = 0.  One wave per row.
+__device__ __forceinline__ void rows_i8_row(const double* __restrict__ src, uint64_t row, uint32_t dim, uint32_t ldb,
+                                            uint32_t* __restrict__ out, float2* __restrict__ out_sr,
+                                            float* __restrict__ out_nrm, int lane)
+{
+    double ss = 0.0, mx = 0.0;
+    for (uint32_t c = lane; c < dim; c += 64) {
+        const double v = src[c];
+        ss += v * v;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
+    const double nrm = sqrt(ss);
+    const double inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
+    for (uint32_t c = lane; c < dim; c += 64) mx = fmax(mx, fabs(src[c] * inv));
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+    const float s = mx > 0.0 ? f32_up(mx / 127.0) : 0.0f;
+    const double sd = (double)s, rs = s > 0.0f ? 1.0 / sd : 0.0;
+    double res = 0.0;
+    for (uint32_t p = lane; p < ldb / 4; p += 64) {
+        uint32_t w = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const uint32_t c = 4 * p + e;
+            const double xh = c < dim ? src[c] * inv : 0.0;
+            double k = rint(xh * rs);
+            k = fmin(127.0, fmax(-127.0, k));  // a no-op (s is rounded up); kept so a byte can never wrap
+            const double d = xh - sd * k;       // s k is exact in f64
+            res += d * d;
+            w |= (uint32_t)((int)k + 128) << (8 * e);
+        }
+        out[(row * ldb) / 4 + p] = w;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) res += __shfl_xor(res, o);
+    if (lane == 0) {
+        const double slack = (double)(dim + 8) * 2.220446049250313e-16;  // (dim + 8) 2^-52
+        const double r = sqrt(res) * (1.0 + slack) + slack;
+        out_sr[row] = make_float2(s, s > 0.0f ? f32_up(r) : 0.0f);
+        out_nrm[row] = (float)nrm;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_rows_i8(const double* __restrict__ master, uint64_t n, uint32_t dim, uint32_t ldb,
                                                  uint32_t* __restrict__ out, float2* __restrict__ out_sr,
                                                  float* __restrict__ out_nrm)
 {
     const int lane = threadIdx.x & 63;
     const uint64_t n_waves = (uint64_t)gridDim.x * 4;
-    for (uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += n_waves) {
-        const double* src = master + row * dim;
-        double ss = 0.0, mx = 0.0;
-        for (uint32_t c = lane; c < dim; c += 64) {
-            const double v = src[c];
-            ss += v * v;
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
-        const double nrm = sqrt(ss);
-        const double inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
-        for (uint32_t c = lane; c < dim; c += 64) mx = fmax(mx, fabs(src[c] * inv));
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-        const float s = mx > 0.0 ? f32_up(mx / 127.0) : 0.0f;
-        const double sd = (double)s, rs = s > 0.0f ? 1.0 / sd : 0.0;
-        double res = 0.0;
-        for (uint32_t p = lane; p < ldb / 4; p += 64) {
-            uint32_t w = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const uint32_t c = 4 * p + e;
-                const double xh = c < dim ? src[c] * inv : 0.0;
-                double k = rint(xh * rs);
-                k = fmin(127.0, fmax(-127.0, k));  // a no-op (s is rounded up); kept so a byte can never wrap
-                const double d = xh - sd * k;       // s k is exact in f64
-                res += d * d;
-                w |= (uint32_t)((int)k + 128) << (8 * e);
-            }
-            out[(row * ldb) / 4 + p] = w;
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) res += __shfl_xor(res, o);
-        if (lane == 0) {
-            const double slack = (double)(dim + 8) * 2.220446049250313e-16;  // (dim + 8) 2^-52
-            const double r = sqrt(res) * (1.0 + slack) + slack;
-            out_sr[row] = make_float2(s, s > 0.0f ? f32_up(r) : 0.0f);
-            out_nrm[row] = (float)nrm;
-        }
+    for (uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += n_waves)
+        rows_i8_row(master + row * dim, row, dim, ldb, out, out_sr, out_nrm, lane);
+}
+
+// In-place update (GpuFlatIndex::update_bulk): the lazy copies of the rows at the distinct positions
+// pos[0..m), rewritten from the staged f64 rows [m, dim] with the converters' own row bodies.  COPY 0: the row-major bf16
+// copy, 1: the fragment-major one, 2: the int8 copy.  A row at or above the copy's watermark `rows_done` is left alone (the
+// next ensure_* converts it from the updated master); norm16 / sqnorm are written with each bf16 copy that covers the row,
+// as the converters write them (both write the same bits).  One wave per row.
+template <int COPY>
+__global__ __launch_bounds__(256) void k_update_copies(const double* __restrict__ staged, const uint32_t* __restrict__ pos,
+                                                       uint32_t m, uint64_t rows_done, uint32_t dim, uint32_t ldb,
+                                                       void* __restrict__ out, float* __restrict__ out_a,
+                                                       float* __restrict__ out_b)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t n_waves = gridDim.x * 4;
+    for (uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6); i < m; i += n_waves) {
+        const uint64_t row = pos[i];
+        if (row >= rows_done) continue;
+        const double* src = staged + (uint64_t)i * dim;
+        if (COPY == 0)
+            rows_bf16_row(src, row, dim, ldb, reinterpret_cast<__bf16*>(out), out_a, out_b, lane);
+        else if (COPY == 1)
+            rows_bf16_frag_row(src, row, dim, ldb, ldb / 32, reinterpret_cast<unsigned char*>(out), out_a, out_b, lane);
+        else
+            rows_i8_row(src, row, dim, ldb, reinterpret_cast<uint32_t*>(out), reinterpret_cast<float2*>(out_a), out_b, lane);
     }
 }
 
@@ -1904,6 +1948,23 @@ hipError_t launch_rows_bf16_frag(hipStream_t s, const double* master_rows, uint6
     const int grid = (int)std::min<uint64_t>((n + 3) / 4, 16384);
     hipLaunchKernelGGL(k_rows_bf16_frag, dim3(grid), dim3(256), 0, s, master_rows, row0, n, dim, ldb,
                        reinterpret_cast<unsigned char*>(slab_frag_base), norm_base, sqnorm_base);
+    return hipGetLastError();
+}
+
+hipError_t launch_update_copies(hipStream_t s, int copy, const double* staged, const uint32_t* pos, uint32_t m, uint64_t rows_done,
+                                uint32_t dim, void* out_base, float* out_a, float* out_b)
+{
+    if (m == 0 || rows_done == 0) return hipSuccess;
+    if (!out_base || !out_a || !out_b || copy < UPDATE_COPY_BF16 || copy > UPDATE_COPY_I8) return hipErrorInvalidValue;
+    const uint32_t ldb = mfma_ldb(dim);
+    if (copy == UPDATE_COPY_BF16_FRAG && ldb % 32 != 0) return hipErrorInvalidValue;
+    const dim3 grid(std::min<uint32_t>((m + 3) / 4, 16384u));
+    if (copy == UPDATE_COPY_BF16)
+        hipLaunchKernelGGL(k_update_copies<0>, grid, dim3(256), 0, s, staged, pos, m, rows_done, dim, ldb, out_base, out_a, out_b);
+    else if (copy == UPDATE_COPY_BF16_FRAG)
+        hipLaunchKernelGGL(k_update_copies<1>, grid, dim3(256), 0, s, staged, pos, m, rows_done, dim, ldb, out_base, out_a, out_b);
+    else
+        hipLaunchKernelGGL(k_update_copies<2>, grid, dim3(256), 0, s, staged, pos, m, rows_done, dim, ldb, out_base, out_a, out_b);
     return hipGetLastError();
 }
 

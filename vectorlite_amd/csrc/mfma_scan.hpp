@@ -88,6 +88,15 @@ bool mfma_rows_kernel(uint32_t dim);
 hipError_t launch_rows_bf16_frag(hipStream_t s, const double* master_rows, uint64_t row0, uint64_t n, uint32_t dim,
                                  void* slab_frag_base, float* norm_base, float* sqnorm_base);
 
+// In-place update: rewrites, from staged f64 rows [m, dim] on the device, the rows of ONE lazy copy at the distinct positions
+// pos[0..m) that lie below the copy's watermark rows_done; rows at or above it are left to the next conversion.  All arrays
+// are addressed from their base (row 0).  UPDATE_COPY_BF16: out_base = the row-major bf16 slab, out_a / out_b = norm16 /
+// sqnorm.  UPDATE_COPY_BF16_FRAG: the fragment-major slab and the same two arrays.  UPDATE_COPY_I8: the int8 slab, out_a =
+// the (s, r) pairs, out_b = |row|.  The arithmetic is the converters' own (the same row bodies).
+constexpr int UPDATE_COPY_BF16 = 0, UPDATE_COPY_BF16_FRAG = 1, UPDATE_COPY_I8 = 2;
+hipError_t launch_update_copies(hipStream_t s, int copy, const double* staged, const uint32_t* pos, uint32_t m, uint64_t rows_done,
+                                uint32_t dim, void* out_base, float* out_a, float* out_b);
+
 // rows per k_mfma_scan tile (its largest shape).  The bf16 slab and the two per-row arrays must be ALLOCATED in whole tiles
 // (ceil(n_rows / MFMA_TILE_ROWS) * MFMA_TILE_ROWS rows): the kernel fetches a tile as one contiguous block and masks
 // the rows past n_rows afterwards, whatever they hold.
