@@ -422,6 +422,38 @@ int vl_index_search_grouped(const vl_index *h, uint64_t groups, uint64_t filter,
                             uint64_t k, int metric, uint64_t out_capacity, uint64_t *out_group_keys, uint64_t *out_ids,
                             double *out_scores, uint64_t *out_n);
 
+/* nq grouped searches against ONE index state (one hold of the reader lock): "the best k documents for each of these
+ * questions" over an index of chunks.  Row i of the [nq, out_stride] outputs and out_n[i] are exactly what
+ * vl_index_search_grouped(h, groups, filter, queries + i * q_len, q_len, k, metric, out_capacity = out_stride, ...) returns
+ * on that state: group keys, ids and f64 score bits -- so ties come out in storage order, the answer for a smaller k is a
+ * prefix of the answer for a larger one, and duplicate-id rows behave as there.  filter is 0, an include token or an
+ * exclusion token, as in the single call.
+ * nq = 0 is VL_OK and writes nothing.  The argument checks are the single call's, in its order and with its texts:
+ * k > VL_GROUPED_MAX_K, the groups token (0 included), the filter token, the metric, the dimension (whenever len != 0);
+ * then k > out_stride: VL_ERR_INVALID_ARG.  k = 0 or an empty S: every out_n[i] = 0, VL_OK.  A failing query
+ * (VL_ERR_NAN_SCORE) makes the call return the status of the LOWEST-INDEX failing query; outputs are unspecified on error.
+ * HNSW and vl_flat_create_multi handles return VL_ERR_INVALID_ARG.  Never joins a coalesced pass.
+ * Route: with two or more queries, k <= 60, cosine / Euclidean / dot, a row length the batch filter has a shape for (up
+ * to 768), at least 8192 rows, in-domain rows, a non-empty S and no forced path, the queries of a launch sequence share
+ * ONE pass of the bf16 MFMA batch filter -- over every row when the table covers the index and filter = 0, else under one
+ * keep bitmap of S, built on the device without a position list -- and each query's 64 candidates are rescored in the
+ * reference's order, ranked, and collapsed to one row per group as far as the exactness bound certifies the ranking.  A
+ * query is settled there when its certified prefix holds k groups (or S has at most 64 rows); otherwise (a NaN, a query
+ * outside the fast-path domain, a zero query under cosine, too few groups in the prefix) the single call's body answers
+ * it under the same lock.  Everything else is a loop over the single call's body under the lock.
+ * vl_last_path is VL_PATH_FAST when the pass settled any query, else the last single call's.
+ * vl_index_set_grouped_batch: 0 = always the loop, 1 = the pass whenever the batch is eligible, 2 = auto (the default):
+ * the pass when its estimated time is below the loop's (csrc/grouped_batch_plan.hpp; both estimates are derived).
+ * vl_index_last_grouped_batch: of the last call on this handle, the queries sent to the pass, those it settled, those it
+ * handed back (routed = settled + handed_back) and its launch sequences; all zero when the call looped.  Any pointer may
+ * be NULL.  Single-GPU flat handles only. */
+int vl_index_search_grouped_batch(const vl_index *h, uint64_t groups, uint64_t filter, const double *queries, uint64_t nq,
+                                  uint64_t q_len, uint64_t k, int metric, uint64_t out_stride, uint64_t *out_group_keys,
+                                  uint64_t *out_ids, double *out_scores /* [nq, out_stride] */, uint64_t *out_n /* [nq] */);
+int vl_index_set_grouped_batch(vl_index *h, int mode);
+int vl_index_last_grouped_batch(const vl_index *h, uint64_t *routed, uint64_t *settled, uint64_t *handed_back,
+                                uint64_t *sequences);
+
 uint64_t vl_index_len(const vl_index *h);      /* len()       src/index/flat.rs:121-123 */
 int vl_index_is_empty(const vl_index *h);      /* is_empty()  src/index/flat.rs:125-127 */
 uint64_t vl_index_dimension(const vl_index *h);/* dimension() src/index/flat.rs:133-135 */

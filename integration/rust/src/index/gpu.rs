@@ -64,6 +64,7 @@ extern "C" {
     fn vl_index_groups_rows(h: *const vl_index, groups: u64, out_rows: *mut u64, out_distinct: *mut u64) -> c_int;
     fn vl_index_groups_destroy(h: *mut vl_index, groups: u64) -> c_int;
     fn vl_index_search_grouped(h: *const vl_index, groups: u64, filter: u64, query: *const f64, q_len: u64, k: u64, metric: c_int, out_capacity: u64, out_group_keys: *mut u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
+    fn vl_index_search_grouped_batch(h: *const vl_index, groups: u64, filter: u64, queries: *const f64, nq: u64, q_len: u64, k: u64, metric: c_int, out_stride: u64, out_group_keys: *mut u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_mmr(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, k: u64, fetch_k: u64, lambda: f64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_flat_create_multi(dim: u64, device_ids: *const c_int, n_dev: c_int, mode: c_int, out: *mut *mut vl_index) -> c_int;
     fn vl_index_len(h: *const vl_index) -> u64;
@@ -639,6 +640,57 @@ impl GpuFlatIndex {
                 .map(|i| {
                     let (text, metadata) = self.0.side.get(&out_ids[i]).cloned().unwrap_or_default();
                     (out_keys[i], SearchResult { id: out_ids[i], score: scores[i], text, metadata })
+                })
+                .collect()),
+            VL_ERR_DIM_MISMATCH => {
+                let (mut e, mut a) = (0u64, 0u64);
+                unsafe { vl_last_dim_mismatch(&mut e, &mut a) };
+                Err(VectorLiteError::DimensionMismatch { expected: e as usize, actual: a as usize })
+            }
+            VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
+            _ => Err(VectorLiteError::InternalError(err)),
+        }
+    }
+
+    /// `search_grouped` for a batch of queries against one index state (no reference counterpart): entry `i` is
+    /// `search_grouped(pairs, queries[i], k, metric)`.  The table is built once for the whole batch; eligible batches share
+    /// passes of the bf16 MFMA batch filter (`vl_index_set_grouped_batch`), every other one loops under one lock.  All
+    /// queries must have the index's dimension.  `k <= 1024`.  Single-GPU handles only.
+    pub fn search_grouped_batch(&self, pairs: &[(u64, u64)], queries: &[Vec<f64>], k: usize, metric: SimilarityMetric) -> VectorLiteResult<Vec<Vec<(u64, SearchResult)>>> {
+        let nq = queries.len();
+        if nq == 0 {
+            return Ok(Vec::new());
+        }
+        let q_len = queries[0].len();
+        if queries.iter().any(|q| q.len() != q_len) {
+            return Err(VectorLiteError::InternalError("search_grouped_batch: queries of one length".to_string()));
+        }
+        let ids: Vec<u64> = pairs.iter().map(|p| p.0).collect();
+        let keys: Vec<u64> = pairs.iter().map(|p| p.1).collect();
+        let (mut token, mut rows) = (0u64, 0u64);
+        let rc = unsafe { vl_index_groups_create(self.0.raw, ids.as_ptr(), keys.as_ptr(), ids.len() as u64, &mut token, &mut rows) };
+        if rc != VL_OK {
+            return Err(VectorLiteError::InternalError(last_error()));
+        }
+        let flat: Vec<f64> = queries.iter().flat_map(|q| q.iter().copied()).collect();
+        let stride = k.min(1024);
+        let len = (nq * stride).max(1);
+        let (mut out_keys, mut out_ids, mut scores, mut n) = (vec![0u64; len], vec![0u64; len], vec![0f64; len], vec![0u64; nq]);
+        let rc = unsafe {
+            vl_index_search_grouped_batch(self.0.raw, token, 0, flat.as_ptr(), nq as u64, q_len as u64, k as u64, metric_code(metric), stride as u64, out_keys.as_mut_ptr(), out_ids.as_mut_ptr(), scores.as_mut_ptr(), n.as_mut_ptr())
+        };
+        let err = if rc == VL_OK { String::new() } else { last_error() };
+        unsafe { vl_index_groups_destroy(self.0.raw, token) };
+        match rc {
+            VL_OK => Ok((0..nq)
+                .map(|qi| {
+                    (0..n[qi] as usize)
+                        .map(|i| {
+                            let id = out_ids[qi * stride + i];
+                            let (text, metadata) = self.0.side.get(&id).cloned().unwrap_or_default();
+                            (out_keys[qi * stride + i], SearchResult { id, score: scores[qi * stride + i], text, metadata })
+                        })
+                        .collect()
                 })
                 .collect()),
             VL_ERR_DIM_MISMATCH => {

@@ -417,6 +417,29 @@ def _search_grouped(L, h, query, k: int, metric: int, groups_token: int, filter_
     return keys[:m].copy(), ids[:m].copy(), scores[:m].copy()
 
 
+GROUPED_BATCH_MODES = {"off": 0, "on": 1, "auto": 2}
+
+
+def _search_grouped_batch(L, h, queries, k: int, metric: int, groups_token: int, filter_token: int):
+    """vl_index_search_grouped_batch -> (group_keys [nq, k], ids [nq, k], scores [nq, k], n [nq]); row i holds n[i] entries."""
+    Q = np.ascontiguousarray(_f64(queries))
+    if Q.ndim != 2:
+        raise ValueError("queries must be [nq, dim]")
+    nq, q_len = Q.shape
+    k = min(max(int(k), 0), 1 << 62)
+    stride = min(k, VL_GROUPED_MAX_K)
+    keys = np.zeros((nq, stride), dtype=np.uint64)
+    ids = np.zeros((nq, stride), dtype=np.uint64)
+    scores = np.zeros((nq, stride), dtype=np.float64)
+    n = np.zeros(nq, dtype=np.uint64)
+    rc = L.vl_index_search_grouped_batch(h, int(groups_token), int(filter_token), Q.ctypes.data, nq, q_len, k, int(metric), stride,
+                                         keys.ctypes.data, ids.ctypes.data, scores.ctypes.data, n.ctypes.data)
+    if rc == VL_ERR_INVALID_ARG:
+        raise IndexOpError(_last_error())
+    _raise(rc)
+    return keys, ids, scores, n
+
+
 def _search_range(L, h, query, min_score: float, metric: int, token: int, limit):
     """vl_index_search_range -> (ids, scores, total).  limit=None: everything (the first call's buffers hold 1024 entries;
     a larger total is fetched by a second call sized from the first one's count, repeated if rows arrived in between)."""
@@ -803,6 +826,52 @@ class FlatIndex:
             text, md = self._meta.get(i, ("", None))
             out.append((g, SearchResult(id=i, score=s, text=text, metadata=md)))
         return out
+
+    def search_grouped_batch_arrays(self, queries, k: int, metric: int = 0, groups=None, filter=None, exclude=None):
+        """(group_keys [nq, k], ids [nq, k], scores [nq, k], n [nq]) for queries [nq, dim]: the first n[i] entries of row i
+        are search_grouped_arrays(queries[i], k, ...), all rows on one index state.  Eligible batches share passes of the
+        bf16 MFMA batch filter (set_grouped_batch); answers are identical on every route."""
+        filter = _one_filter(filter, exclude)
+        if not isinstance(groups, GroupTable):
+            raise ValueError("groups must be a GroupTable of this index (make_groups)")
+        if groups._index is not self:
+            raise ValueError("the group table belongs to another index")
+        if filter is None:
+            return _search_grouped_batch(self._L, self._h, queries, k, metric, groups.token, 0)
+        tok, temp = self._filter_token(filter)
+        try:
+            return _search_grouped_batch(self._L, self._h, queries, k, metric, groups.token, tok)
+        finally:
+            if temp is not None:
+                temp.close()
+
+    def search_grouped_batch(self, queries, k: int, similarity_metric: int = SimilarityMetric.Cosine, groups=None,
+                             filter=None, exclude=None) -> List[List[Tuple[int, SearchResult]]]:
+        keys, ids, scores, n = self.search_grouped_batch_arrays(queries, k, similarity_metric, groups=groups, filter=filter,
+                                                                exclude=exclude)
+        out = []
+        for r in range(len(n)):
+            m = int(n[r])
+            row = []
+            for g, i, s in zip(keys[r, :m].tolist(), ids[r, :m].tolist(), scores[r, :m].tolist()):
+                text, md = self._meta.get(i, ("", None))
+                row.append((g, SearchResult(id=i, score=s, text=text, metadata=md)))
+            out.append(row)
+        return out
+
+    def set_grouped_batch(self, mode: str) -> None:
+        """How search_grouped_batch answers an eligible batch: "off" (a loop over the single grouped search under one
+        lock), "on" (one bf16 MFMA pass per launch sequence, each query's candidates ranked and collapsed to one row per
+        group on the device; what the pass does not settle goes to the single search) or "auto" (new handles: the pass
+        when its estimated time is below the loop's).  Answers are identical in every mode."""
+        _raise(self._L.vl_index_set_grouped_batch(self._h, GROUPED_BATCH_MODES[mode]))
+
+    def last_grouped_batch(self) -> Dict[str, int]:
+        """Of the last search_grouped_batch on this handle: queries sent to the MFMA pass, those it settled, those it handed
+        back to the single search, and its launch sequences; all zero when the call looped."""
+        v = [C.c_uint64(0) for _ in range(4)]
+        _raise(self._L.vl_index_last_grouped_batch(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("routed", "settled", "handed_back", "sequences"), (int(x.value) for x in v)))
 
     # ---- diversified (MMR) search ------------------------------------------------------------
     def search_mmr_arrays(self, query, k: int, fetch_k: int = 20, lambda_mult: float = 0.5, metric: int = 0, filter=None, exclude=None):
@@ -1557,6 +1626,13 @@ class HNSWIndex:
 
     def search_grouped(self, query, k: int, similarity_metric: int = SimilarityMetric.Cosine, groups=None, filter=None):
         return self.search_grouped_arrays(query, k, similarity_metric, groups, filter)
+
+    def search_grouped_batch_arrays(self, queries, k: int, metric: int = 0, groups=None, filter=None):
+        """Grouped search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""
+        self.make_groups([], [])  # raises: no grouped HNSW walk
+
+    def search_grouped_batch(self, queries, k: int, similarity_metric: int = SimilarityMetric.Cosine, groups=None, filter=None):
+        return self.search_grouped_batch_arrays(queries, k, similarity_metric, groups, filter)
 
     def search_arrays(self, query, k: int, metric: int, ef: int = 0, filter=None, exclude=None):
         if exclude is not None:

@@ -590,6 +590,47 @@ int vl_index_search_grouped(const vl_index* h, uint64_t groups, uint64_t filter,
     });
 }
 
+int vl_index_search_grouped_batch(const vl_index* h, uint64_t groups, uint64_t filter, const double* queries, uint64_t nq,
+                                  uint64_t q_len, uint64_t k, int metric, uint64_t out_stride, uint64_t* out_group_keys,
+                                  uint64_t* out_ids, double* out_scores, uint64_t* out_n)
+{
+    return guarded([&]() -> int {
+        if (k > VL_GROUPED_MAX_K) {  // the single call's checks, in its order: before the handle is looked at
+            vl::set_last_error("grouped search: k exceeds VL_GROUPED_MAX_K (1024)");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (groups == 0) {
+            vl::set_last_error("unknown or destroyed group table");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (!h) return VL_ERR_INVALID_ARG;
+        if (!h->flat) {
+            vl::set_last_error("grouped search is served by single-GPU flat indexes");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (nq == 0) return h->flat->search_grouped_batch(groups, filter, queries, 0, q_len, k, metric, out_stride, nullptr, nullptr,
+                                                          nullptr, nullptr);
+        if (!out_n) return VL_ERR_INVALID_ARG;
+        if ((!out_group_keys || !out_ids || !out_scores) && k != 0 && out_stride != 0) return VL_ERR_INVALID_ARG;
+        return h->flat->search_grouped_batch(groups, filter, queries, nq, q_len, k, metric, out_stride, out_group_keys, out_ids,
+                                             out_scores, out_n);
+    });
+}
+
+int vl_index_set_grouped_batch(vl_index* h, int mode)
+{
+    if (!h || !h->flat || mode < 0 || mode > 2) return VL_ERR_INVALID_ARG;
+    h->flat->set_grouped_batch(mode);
+    return VL_OK;
+}
+
+int vl_index_last_grouped_batch(const vl_index* h, uint64_t* routed, uint64_t* settled, uint64_t* handed_back, uint64_t* sequences)
+{
+    if (!h || !h->flat) return VL_ERR_INVALID_ARG;
+    h->flat->last_grouped_batch(routed, settled, handed_back, sequences);
+    return VL_OK;
+}
+
 int vl_index_search_batch_filters(const vl_index* h, const uint64_t* filters, uint64_t n_filters, const double* queries,
                                   uint64_t nq, uint64_t q_len, uint64_t k, int metric, uint64_t out_stride, uint64_t* out_ids,
                                   double* out_scores, uint64_t* out_n)

@@ -13,6 +13,7 @@
 #include "score_bound.hpp"
 #include "subset_batch_plan.hpp"
 #include "masked_batch_plan.hpp"
+#include "grouped_batch_plan.hpp"
 
 #include <chrono>
 
@@ -228,11 +229,13 @@ Workspace::~Workspace()
     if (stream) (void)hipStreamSynchronize(stream);
     void* dev[] = {d_q64, d_partials, d_partials64, d_result, d_nan, d_scores, d_okeys,
                    d_opos, d_out_pos, d_out_scores, d_positions, d_dists, rg_ctr, rg_cand, rg_scores, rg_keys, rg_pv, mmr_sim,
-                   rb_ctr, rb_min, rb_sv_score, rb_sv_pos, gp_best, gp_first, gp_lists, gp_cand, gp_scores, gp_ctr, gp_out_keys};
+                   rb_ctr, rb_min, rb_sv_score, rb_sv_pos, gp_best, gp_first, gp_lists, gp_cand, gp_scores, gp_ctr, gp_out_keys,
+                   gb_keep, gb_m};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     void* host[] = {h_q64, h_result, h_nan, mf_h_q64, mf_h_result, mf_h_dom, k3_h_q64, k3_h_result, rg_h_ctr, rg_h_pos, rg_h_scores,
-                    rb_h_thr, rb_h_min, rb_h_ctr, rb_h_cnt, rb_h_pos, rb_h_scores, gp_h_ctr, gp_h_scores, gp_h_keys};
+                    rb_h_thr, rb_h_min, rb_h_ctr, rb_h_cnt, rb_h_pos, rb_h_scores, gp_h_ctr, gp_h_scores, gp_h_keys,
+                    gb_h_result};
     for (void* p : host)
         if (p) (void)hipHostFree(p);
     void* mfd[] = {mf.q_bf16, mf.gmax, mf.thr, mf.cand, mf.cnt, mf_d_q64, mf_lists, mf_scores, k3_d_q64};
@@ -2533,7 +2536,7 @@ int GpuFlatIndex::search_range_locked(Workspace* ws, IdFilter* f, const double* 
 GroupTable::~GroupTable()
 {
     (void)hipSetDevice(rows.device);
-    void* dev[] = {d_dense, d_keys, d_group_of_row};
+    void* dev[] = {d_dense, d_keys, d_group_of_row, d_keep};
     for (void* p : dev)
         if (p) (void)hipFree(p);
 }
@@ -2794,6 +2797,160 @@ int GpuFlatIndex::search_grouped_locked(Workspace* ws, const GroupTable* t, cons
 }
 
 // ---------------------------------------------------------------------------------------------
+// Batched grouped search: nq grouped queries against one index state.  The MFMA batch filter already
+// leaves, per query, the 64 best rows of S rescored in the reference's order; k_batch_rank_collapse certifies as long a
+// prefix of that ranking as the bound allows and collapses it to one row per group.  A query whose prefix holds k groups
+// (or whose S fits the list) is settled without any per-group atomic; every other query runs the single search's body
+// under the same lock, so each row is the single call's answer bit for bit.
+// ---------------------------------------------------------------------------------------------
+int GpuFlatIndex::grouped_keep_bits(Workspace* ws, GroupTable* t, IdFilter* f, const unsigned long long** keep, uint64_t* m) const
+{
+    const uint64_t n = ids_.size(), words = (n + 63) / 64;
+    hipStream_t st = ws->stream;
+    VL_TRY(ensure_set(HipMem{}, {dev_buf(ws->gb_m, 1)}));
+    uint32_t m32 = 0;
+    auto count = [&]() -> int {
+        VL_HIP(hipMemcpyAsync(&m32, ws->gb_m, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipStreamSynchronize(st));
+        return OK;
+    };
+    if (!f) {  // the table alone: cached on the table until rows are added or deleted
+        std::lock_guard<std::mutex> g(t->rows.mu);
+        if (t->keep_at != mutations_) {
+            t->keep_at = ~0ull;
+            VL_TRY(grow(HipMem{}, t->keep_cap, words, {dev_buf(t->d_keep, words)}));
+            VL_HIP(launch_group_keep_bits(st, t->d_group_of_row, n, nullptr, nullptr, nullptr, 0, t->d_keep, ws->gb_m));
+            VL_TRY(count());
+            if (m32 != t->rows.m) {
+                set_last_error("the group table's keep bitmap and its row list disagree (kernel bug)");
+                return ERR_DEVICE;
+            }
+            t->keep_at = mutations_;
+        }
+        *keep = t->d_keep;
+        *m = t->rows.m;
+        return OK;
+    }
+    VL_TRY(grow(HipMem{}, ws->gb_keep_cap, words, {dev_buf(ws->gb_keep, words)}));
+    if (f->exclude) {
+        VL_HIP(launch_group_keep_bits(st, t->d_group_of_row, n, f->d_keep, nullptr, nullptr, 0, ws->gb_keep, ws->gb_m));
+    } else {
+        VL_TRY(ensure_device_ids());
+        VL_HIP(launch_group_keep_bits(st, t->d_group_of_row, n, nullptr, d_ids_, f->d_ids, f->ids.size(), ws->gb_keep, ws->gb_m));
+    }
+    VL_TRY(count());
+    if (m32 > t->rows.m || m32 > f->m) {
+        set_last_error("the keep bitmap of a grouped batch holds more rows than its table or its filter (kernel bug)");
+        return ERR_DEVICE;
+    }
+    *keep = ws->gb_keep;
+    *m = m32;
+    return OK;
+}
+
+int GpuFlatIndex::search_grouped_batch(uint64_t groups, uint64_t token, const double* queries, uint64_t nq, uint64_t q_len,
+                                       uint64_t k, int metric, uint64_t out_stride, uint64_t* out_group_keys, uint64_t* out_ids,
+                                       double* out_scores, uint64_t* out_n) const
+{
+    uint64_t gb[4] = {0, 0, 0, 0};  // last_grouped_batch: routed, settled, handed back, sequences
+    auto publish = [&]() {
+        for (int i = 0; i < 4; ++i) last_gbatch_[i].store(gb[i], std::memory_order_relaxed);
+    };
+    if (nq == 0) {
+        publish();
+        return OK;
+    }
+    if (!out_n) return ERR_INVALID_ARG;
+    for (uint64_t i = 0; i < nq; ++i) out_n[i] = 0;
+    set_last_path(PATH_NONE);
+    if (k > GROUPED_MAX_K) {
+        set_last_error("grouped search: k exceeds VL_GROUPED_MAX_K (1024)");
+        return ERR_INVALID_ARG;
+    }
+    std::shared_ptr<GroupTable> t;
+    VL_TRY(find_groups(groups, &t));
+    std::shared_ptr<IdFilter> f;
+    if (token != 0) VL_TRY(find_filter(token, &f));
+    std::shared_lock<RwLock> lk;  // one index state for the whole batch
+    VL_TRY(lock_for_query(metric, q_len, &lk));
+    if (k > out_stride) {
+        set_last_error("grouped batch: k exceeds out_stride");
+        return ERR_INVALID_ARG;
+    }
+    publish();
+    if (ids_.empty() || k == 0) return OK;
+    if ((!queries && dim_) || !out_scores || !out_group_keys || !out_ids) return ERR_INVALID_ARG;
+
+    WsLease lease(this, /*sync_always=*/true);
+    if (lease.status() != OK) return lease.status();
+    Workspace* const ws = lease.ws;
+    VL_TRY(resolve_if_stale(ws, t.get()));
+    // an exclusion token's position list waits until a query is left to the single search: the pass reads a bitmap
+    if (f) VL_TRY(resolve_if_stale(ws, f.get(), /*need_list=*/false));
+    InFlight searching(active_searches_);
+    if (t->rows.m == 0 || (f && f->m == 0)) return OK;  // an empty S (search_grouped's early return)
+
+    const uint64_t n = ids_.size();
+    std::vector<uint8_t> done(nq, 0);
+    {
+        const char* mf_env = getenv("VL_MFMA");
+        const char* mf_min = getenv("VL_MFMA_MIN_BATCH");
+        const MaskedBatchLimits lim{MFMA_MIN_ROWS, mf_min && *mf_min ? (uint64_t)atoi(mf_min) : (uint64_t)MFMA_MIN_BATCH,
+                                    (uint64_t)KFAST_MAX, mfma_sequence_queries((uint32_t)dim_)};
+        GroupedBatchShape shp;
+        shp.index = {force_path_.load() == 0 && n_out_of_domain_ == 0 && dim_ != 0 && !(mf_env && mf_env[0] == '0') &&
+                         mfma_scan_supported((uint32_t)dim_, metric),
+                     n, (uint32_t)dim_, ld_, mfma_ldb((uint32_t)dim_)};
+        shp.rows_kernel = mfma_rows_kernel((uint32_t)dim_);
+        shp.needs_bitmap = f != nullptr || t->rows.m != n;
+        shp.m = f ? std::min<uint64_t>(t->rows.m, f->m) : t->rows.m;  // an upper bound until the bitmap is counted
+        const int mode = grouped_batch_.load();
+        // (the loop's estimate grows with m: a batch that loops at the upper bound loops at the counted m as well)
+        if (grouped_batch_route(mode, shp, lim, nq, k)) {
+            const unsigned long long* keep = nullptr;
+            if (shp.needs_bitmap) {
+                VL_TRY(grouped_keep_bits(ws, t.get(), f.get(), &keep, &shp.m));
+                if (shp.m == 0) return OK;  // the filter keeps no grouped row
+            }
+            if (grouped_batch_route(mode, shp, lim, nq, k)) {
+                std::vector<uint32_t> qidx, mq, kq;
+                std::vector<const unsigned long long*> keep_of;
+                MaskedQueries desc{nullptr, nullptr, nullptr, nullptr};
+                if (keep) {  // every query of every sequence under the ONE bitmap of S
+                    qidx.resize(nq);
+                    for (uint64_t i = 0; i < nq; ++i) qidx[i] = (uint32_t)i;
+                    mq.assign(nq, (uint32_t)shp.m);
+                    kq.assign(nq, (uint32_t)k);
+                    keep_of.assign(nq, keep);
+                    desc = {qidx.data(), keep_of.data(), mq.data(), kq.data()};
+                }
+                const GroupedReq req{t.get(), shp.m, out_stride, out_group_keys};
+                VL_TRY(search_batch_mfma(ws, queries, nullptr, nq, out_stride, k, metric, nullptr, out_ids, out_scores, out_n, &done,
+                                         nullptr, keep ? &desc : nullptr, &gb[3], &req));
+                gb[0] = nq;
+                for (uint64_t qi = 0; qi < nq; ++qi) gb[1] += done[qi] ? 1 : 0;
+                gb[2] = gb[0] - gb[1];
+            }
+        }
+    }
+    // what the pass did not settle (or everything), in ascending order: the first failure is the lowest failing query
+    bool list_ready = !(f && f->exclude);
+    for (uint64_t qi = 0; qi < nq; ++qi) {
+        if (done[qi]) continue;
+        if (!list_ready) {
+            std::lock_guard<std::mutex> fg(f->mu);
+            VL_TRY(ensure_plist(ws, f.get()));
+            list_ready = true;
+        }
+        VL_TRY(search_grouped_locked(ws, t.get(), f.get(), queries + qi * dim_, k, metric, out_stride, out_group_keys + qi * out_stride,
+                                     nullptr, out_ids + qi * out_stride, out_scores + qi * out_stride, out_n + qi));
+    }
+    if (gb[1]) set_last_path(PATH_FAST);
+    publish();
+    return OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // large batches: bf16 MFMA candidate filter (mfma_scan.hip) + the same exact finalize
 // ---------------------------------------------------------------------------------------------
 int GpuFlatIndex::ensure_bf16_slab(bool frag_major) const
@@ -3022,17 +3179,21 @@ int GpuFlatIndex::ensure_mfma_scratch(Workspace* ws) const
 int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const double* d_queries, uint64_t nq,
                                     uint64_t k, uint64_t k_eff, int metric, uint64_t* out_pos, uint64_t* out_ids,
                                     double* out_scores, uint64_t* out_n, std::vector<uint8_t>* done,
-                                    const ShardRecordSink* sink, const MaskedQueries* masked, uint64_t* n_sequences) const
+                                    const ShardRecordSink* sink, const MaskedQueries* masked, uint64_t* n_sequences,
+                                    const GroupedReq* grouped) const
 {
     static_assert(sizeof(const unsigned long long*) == sizeof(double) && 2 * sizeof(uint32_t) == sizeof(double),
                   "the masked descriptor is staged as two words per query behind the norms");
     if (masked && (d_queries || sink || !mfma_rows_kernel((uint32_t)dim_))) return ERR_INVALID_ARG;
+    if (grouped && (d_queries || sink || !out_ids || !grouped->out_keys || k_eff == 0 || k_eff > (uint64_t)KFAST_MAX))
+        return ERR_INVALID_ARG;
     if (n_sequences) *n_sequences = 0;
     const uint64_t n = ids_.size();
     const bool frag = mfma_rows_kernel((uint32_t)dim_);  // which kernel, hence which slab layout
     VL_TRY(ensure_bf16_slab(frag));
     const void* slab16 = frag ? d_slab16f_ : d_slab16_;
     VL_TRY(ensure_mfma_scratch(ws));
+    if (grouped) VL_TRY(ensure_set(HipMem{}, {pinned_buf(ws->gb_h_result, 2 * (size_t)MFMA_MAX_BATCH)}));
     hipStream_t st = ws->stream;
     const double in_extra = IN_EXTRA_MFMA;  // bf16 rows and queries (mfma_scan.hpp)
     const uint64_t k_eff_all = k_eff;       // (a masked batch has its own per query)
@@ -3136,7 +3297,11 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
         // batches: the rescoring split over four workgroups per query + a rank / emit launch (launch_batch_finalize); a handful
         // of queries keeps the one-workgroup-per-query kernel (one launch less)
         static const bool split_off = []() { const char* v = getenv("VL_BATCH_FINALIZE"); return v && v[0] == '0'; }();
-        if (masked)  // the certificate per query: n_rows = m_q, k = min(k, m_q) (DESIGN.md sections 23, 24)
+        if (grouped)  // the certified prefix of each list, collapsed to one row per group
+            VL_HIP(launch_batch_finalize_grouped(st, metric, ws->mf_lists, (int)g, d_master_, ws->mf_d_q64, d_norms, (uint32_t)dim_,
+                                                 grouped->m, (uint32_t)k_eff, max_row_norm_, grouped->table->d_group_of_row, n,
+                                                 ws->gb_h_result + (size_t)slot * MFMA_MAX_BATCH, in_extra, ws->mf_scores));
+        else if (masked)  // the certificate per query: n_rows = m_q, k = min(k, m_q) (DESIGN.md sections 23, 24)
             VL_HIP(launch_batch_finalize_rows(st, metric, ws->mf_lists, (int)g, d_master_, ws->mf_d_q64, d_norms, (uint32_t)dim_,
                                               d_m, d_m + g, max_row_norm_, res, in_extra, ws->mf_scores));
         else if (g >= 8 && !split_off)
@@ -3172,7 +3337,29 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
             }
             VL_TRY(account_profile(ws, bytes));
         }
-        for (uint32_t j = 0; j < g; ++j) {
+        for (uint32_t j = 0; grouped && j < g; ++j) {  // settled queries: position -> id, group number -> key
+            const uint64_t qi = S.q0 + j;
+            const GroupedResultBlock& r = ws->gb_h_result[(size_t)slot * MFMA_MAX_BATCH + j];
+            if (!S.in_domain[j] || r.flags != 0u) continue;
+            const std::vector<uint64_t>& keys = grouped->table->keys;
+            bool ok = r.n_out <= k_eff_all;
+            for (uint64_t i = 0; ok && i < r.n_out; ++i) ok = r.pos[i] < n && r.group[i] < keys.size();
+            if (!ok) {
+                set_last_error("grouped MFMA path returned an out-of-range entry (kernel bug)");
+                return ERR_DEVICE;
+            }
+            const uint64_t want = std::min<uint64_t>(r.n_out, grouped->out_stride);
+            for (uint64_t i = 0; i < want; ++i) {
+                const size_t o = qi * grouped->out_stride + i;
+                grouped->out_keys[o] = keys[r.group[i]];
+                if (out_pos) out_pos[o] = r.pos[i];
+                out_ids[o] = ids_[r.pos[i]];
+                out_scores[o] = r.score[i];
+            }
+            out_n[qi] = want;
+            (*done)[qi] = 1;
+        }
+        for (uint32_t j = 0; !grouped && j < g; ++j) {
             const uint64_t qi = S.q0 + j;
             const SearchResultBlock& r = res[j];
             const uint64_t k_eff = masked ? masked->k[qi] : k_eff_all;

@@ -115,6 +115,12 @@ struct Workspace {
     uint32_t* gp_h_ctr = nullptr;    // pinned [RANGE_CTR_WORDS + 1]
     double* gp_h_scores = nullptr;   // pinned [KP]
     uint64_t* gp_h_keys = nullptr;   // pinned [GROUPED_MAX_K]
+    // batched grouped search (lazy): the result blocks of two launch sequences in flight, the keep bitmap of S when a filter
+    // is involved (the table's own bitmap is cached on the table), the device's count of its bits
+    GroupedResultBlock* gb_h_result = nullptr;  // pinned [2][MFMA_MAX_BATCH]
+    unsigned long long* gb_keep = nullptr;      // [gb_keep_cap] words
+    size_t gb_keep_cap = 0;
+    uint32_t* gb_m = nullptr;                   // [1]
     // diversified search (lazy): the candidates' pairwise similarities, [MMR_MAX_FETCH][MMR_MAX_FETCH] (8 MB)
     double* mmr_sim = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -190,6 +196,11 @@ struct GroupTable {
     unsigned long long* d_keys = nullptr;  // [keys.size()]
     uint32_t* d_group_of_row = nullptr;    // [gor_cap] GROUP_NONE: the row has no group
     uint64_t gor_cap = 0;
+    // the batched grouped search's keep bitmap of the table alone (bit p set iff row p has a group; section 26), built by the
+    // first batch that needs it after a resolution
+    unsigned long long* d_keep = nullptr;  // [keep_cap] words
+    uint64_t keep_cap = 0;
+    uint64_t keep_at = ~0ull;              // the mutation count the bitmap belongs to (none yet)
 
     ~GroupTable();
 };
@@ -368,6 +379,25 @@ public:
     int search_grouped(uint64_t groups, uint64_t token, const double* query, uint64_t q_len, uint64_t k, int metric,
                        uint64_t out_capacity, uint64_t* out_group_keys, uint64_t* out_pos, uint64_t* out_ids, double* out_scores,
                        uint64_t* out_n) const;
+    // NEW (no reference counterpart): nq grouped searches against one index state; row i of the [nq, out_stride] outputs and
+    // out_n[i] are exactly search_grouped(groups, token, queries + i * q_len, q_len, k, metric, out_stride, ...).  Eligible
+    // batches (grouped_batch_plan.hpp) share passes of the bf16 MFMA filter, followed per query by the rescoring and the
+    // rank-and-collapse stage; whatever a pass does not settle, and every batch that is not eligible, runs the single
+    // search's body under the same lock.  Returns the status of the lowest-index failing query.  DESIGN.md section 26.
+    int search_grouped_batch(uint64_t groups, uint64_t token, const double* queries, uint64_t nq, uint64_t q_len, uint64_t k,
+                             int metric, uint64_t out_stride, uint64_t* out_group_keys, uint64_t* out_ids, double* out_scores,
+                             uint64_t* out_n) const;
+    // 0: always the loop.  1: the pass whenever the batch is eligible.  2 ("auto", the default): when its estimate is lower.
+    void set_grouped_batch(int mode) { grouped_batch_.store(mode); }
+    int grouped_batch() const { return grouped_batch_.load(); }
+    // the last search_grouped_batch on this handle: queries sent to the pass, those it settled, those it handed back to the
+    // single search, its launch sequences; all zero when the call looped
+    void last_grouped_batch(uint64_t* routed, uint64_t* settled, uint64_t* handed_back, uint64_t* sequences) const
+    {
+        uint64_t* out[4] = {routed, settled, handed_back, sequences};
+        for (int i = 0; i < 4; ++i)
+            if (out[i]) *out[i] = last_gbatch_[i].load(std::memory_order_relaxed);
+    }
     uint64_t len() const;
     bool is_empty() const { return len() == 0; }
     uint64_t dimension() const { return dim_; }
@@ -538,11 +568,25 @@ private:
         const uint32_t* m;
         const uint32_t* k;
     };
+    // A batched grouped search riding on the sequence pipeline: k_batch_rank_collapse takes the
+    // rank / emit launch's place and settled queries are unpacked as (group key, id, score) rows, out_stride apart.  S has m
+    // rows: every row of the index (masked == nullptr) or the rows under the one bitmap every query of `masked` names.
+    // Host queries only; out_pos / out_n / done as ever, out_ids and out_scores at stride out_stride like out_keys.
+    struct GroupedReq {
+        const GroupTable* table;
+        uint64_t m;
+        uint64_t out_stride;
+        uint64_t* out_keys;
+    };
     int search_batch_mfma(Workspace* ws, const double* queries, const double* d_queries, uint64_t nq, uint64_t k,
                           uint64_t k_eff, int metric, uint64_t* out_pos, uint64_t* out_ids, double* out_scores,
                           uint64_t* out_n, std::vector<uint8_t>* done,
                           const ShardRecordSink* sink = nullptr,  // queries on the host, or d_queries on the device
-                          const MaskedQueries* masked = nullptr, uint64_t* n_sequences = nullptr) const;
+                          const MaskedQueries* masked = nullptr, uint64_t* n_sequences = nullptr,
+                          const GroupedReq* grouped = nullptr) const;
+    // the keep bitmap of S = the table's rows under f (nullptr: the table alone, cached on the table) and |S|; mu_ held,
+    // t and f resolved.  No position list is built.
+    int grouped_keep_bits(Workspace* ws, GroupTable* t, IdFilter* f, const unsigned long long** keep, uint64_t* m) const;
     int ensure_device_ids() const;  // lazily uploads the position -> id table (what a device-written exchange record needs)
 
     const uint64_t dim_;
@@ -630,6 +674,8 @@ private:
     mutable std::atomic<uint64_t> last_fbatch_[4] = {};
     mutable std::atomic<uint64_t> last_mbatch_[5] = {};
     std::atomic<int> masked_batch_{2};  // MASKED_BATCH_AUTO
+    mutable std::atomic<uint64_t> last_gbatch_[4] = {};
+    std::atomic<int> grouped_batch_{2};  // GROUPED_BATCH_AUTO
     std::atomic<uint64_t> last_delete_[6] = {};
     std::atomic<uint64_t> last_update_[7] = {};
     mutable std::mutex prof_mu_;

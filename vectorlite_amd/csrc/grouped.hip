@@ -3,6 +3,7 @@
 //   k_group_rows       the group table's resolution: storage position -> dense group number
 //   k_group_top(_final) the 64 largest values of pass 1's best[] (TopList / block_merge / the list merge), decoded
 //   k_group_first, k_group_collapse   the collapse of the ranked survivors to one row per group
+//   k_group_keep_bits  the keep bitmap of S for the batched form (section 26)
 #include <hip/hip_runtime.h>
 
 #include "device_common.hpp"
@@ -146,7 +147,62 @@ __global__ __launch_bounds__(1024) void k_group_collapse(const unsigned long lon
     if (threadIdx.x == 0) *out_n = base < k ? base : k;
 }
 
+// The keep bitmap of S for the batched grouped search, in k_filter_bits' layout: one wave per 64-bit
+// word, lane p & 63 tests p < n && group_of_row[p] != GROUP_NONE and, with a filter, the filter -- an exclusion token's own
+// keep word (filter_keep), or membership of the row's id in an include token's sorted ids (fids; the lower bound of
+// k_filter_bits' id_in_set).  Lane 0 stores the ballot (bits at or past n are 0) and adds its popcount to *m_out.
+__global__ __launch_bounds__(256) void k_group_keep_bits(const uint32_t* __restrict__ group_of_row, uint32_t n,
+                                                         const unsigned long long* __restrict__ filter_keep,
+                                                         const unsigned long long* __restrict__ pos_ids,
+                                                         const unsigned long long* __restrict__ fids, uint32_t nf, uint32_t by_ids,
+                                                         uint32_t n_words, unsigned long long* __restrict__ keep,
+                                                         uint32_t* __restrict__ m_out)
+{
+    const int lane = lane_id();
+    const uint32_t n_waves = gridDim.x * 4;
+    uint32_t mine = 0;  // lane 0: bits set in this wave's words
+    for (uint32_t w = blockIdx.x * 4 + (threadIdx.x >> 6); w < n_words; w += n_waves) {  // wave-uniform trip count
+        const uint32_t p = w * 64u + (uint32_t)lane;
+        bool on = p < n && group_of_row[p] != GROUP_NONE;
+        if (filter_keep) {
+            on = on && ((filter_keep[w] >> lane) & 1ull) != 0ull;
+        } else if (by_ids && on) {
+            const unsigned long long id = pos_ids[p];
+            uint32_t lo = 0, hi = nf;
+            while (lo < hi) {
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                if (fids[mid] < id) lo = mid + 1;
+                else hi = mid;
+            }
+            on = lo < nf && fids[lo] == id;
+        }
+        const unsigned long long word = __ballot(on);
+        if (lane == 0) {
+            keep[w] = word;
+            mine += (uint32_t)__popcll(word);
+        }
+    }
+    if (lane == 0 && mine) atomicAdd(m_out, mine);
+}
+
 }  // namespace
+
+hipError_t launch_group_keep_bits(hipStream_t s, const uint32_t* group_of_row, uint64_t n, const unsigned long long* filter_keep,
+                                  const unsigned long long* pos_ids, const unsigned long long* fids, uint64_t nf,
+                                  unsigned long long* keep, uint32_t* m_out)
+{
+    const bool by_ids = !filter_keep && pos_ids != nullptr;  // an include token (nf == 0: it keeps no row, fids is not read)
+    if (n == 0 || n >= 0xFFFFFFFFull || nf >= 0xFFFFFFFFull || !group_of_row || !keep || !m_out || (by_ids && nf != 0 && !fids))
+        return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(m_out, 0, sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    const uint64_t n_words = (n + 63) / 64;
+    const uint64_t blocks = (n_words + 3) / 4;
+    const int grid = (int)(blocks < 4096 ? blocks : 4096);
+    hipLaunchKernelGGL(k_group_keep_bits, dim3(grid), dim3(256), 0, s, group_of_row, (uint32_t)n, filter_keep, pos_ids, fids,
+                       (uint32_t)nf, by_ids ? 1u : 0u, (uint32_t)n_words, keep, m_out);
+    return hipGetLastError();
+}
 
 hipError_t launch_group_rows(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
                              const uint32_t* dense, uint64_t nf, uint32_t* group_of_row)

@@ -991,6 +991,82 @@ __global__ __launch_bounds__(256) void k_batch_rank_emit_rows(const Cand32* __re
                             out + q, 0u, ShardRecordSink{}, q);
 }
 
+// The batched grouped search's stage behind k_batch_rescore: rank_check_emit's ranking and bound,
+// then the collapse to one row per group, one WAVE per query, no LDS.  The lists hold rows of S only and n_rows = |S|.
+// A candidate is CERTIFIED iff its score is > B = bound_for_key(the list's 64th key), strictly: no row outside the list
+// scores above B, so it outranks all of them, and the certified candidates are a prefix of S's ranking.  (A list that
+// holds all n_rows <= 64 rows has no row outside it: every candidate is certified.)  Inside the prefix a candidate is the
+// first of its group iff no candidate of smaller rank has its group; its slot is the number of such candidates ranked
+// before it.  Settled (flags == 0): k groups came out, or the whole of S was ranked and holds no NaN.
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_batch_rank_collapse(const Cand32* __restrict__ lists, const double* __restrict__ scores,
+                                                             const double* __restrict__ q_norms, uint32_t nq, uint32_t ld,
+                                                             uint64_t n_rows, uint32_t k, double R, double in_extra,
+                                                             const uint32_t* __restrict__ group_of_row, uint32_t index_rows,
+                                                             GroupedResultBlock* __restrict__ out)
+{
+    const int lane = lane_id();
+    const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= nq) return;
+    const Cand32 e = lists[(size_t)q * KP + lane];
+    const int n_cand = __popcll(__ballot(e.pos != POS_SENTINEL));
+    const bool valid = lane < n_cand;
+    const double sc = valid ? scores[(size_t)q * KP + lane] : 0.0;
+    const uint32_t my_pos = e.pos;
+    const bool any_nan = __ballot(valid && sc != sc) != 0ull;
+    int rank = 0;  // (score desc, position asc), as rank_check_emit ranks
+    for (int j = 0; j < n_cand; ++j) {
+        const double sj = read_lane(sc, j);
+        const uint32_t pj = read_lane(my_pos, j);
+        rank += (sj > sc || (sj == sc && pj < my_pos)) ? 1 : 0;
+    }
+    uint32_t flags = 0;
+    if (any_nan) flags |= RESULT_HAS_NAN | RESULT_NEEDS_EXACT;
+    bool certified = false;
+    bool complete = false;  // the list is the whole of S
+    if (n_rows <= (uint64_t)KP) {
+        complete = (uint64_t)n_cand >= n_rows;
+        if (!complete) flags |= RESULT_NEEDS_EXACT;
+        certified = valid && complete && !any_nan;
+    } else if (n_cand < KP) {
+        flags |= RESULT_NEEDS_EXACT;  // keys were not finite, or the candidate stage dropped rows
+    } else {
+        const double B = bound_for_key<METRIC>(read_lane(e.key, KP - 1), ld, R, q_norms[q], in_extra);
+        certified = !any_nan && sc > B;
+    }
+    uint32_t g = GROUP_NONE;
+    if (certified && my_pos < index_rows) g = group_of_row[my_pos];
+    if (__ballot(certified && g == GROUP_NONE) != 0ull) {  // a row of S without a group: the bitmap and the table disagree
+        flags |= RESULT_NEEDS_EXACT;
+        certified = false;
+    }
+    uint32_t dup = 0;
+    for (int j = 0; j < n_cand; ++j) {
+        const uint32_t gj = read_lane(g, j);
+        const uint32_t rj = read_lane((uint32_t)rank, j);
+        dup |= (gj == g && rj < (uint32_t)rank) ? 1u : 0u;  // (an uncertified lane holds GROUP_NONE and is never `first`)
+    }
+    const uint32_t first = (certified && !dup) ? 1u : 0u;
+    uint32_t slot = 0;
+    for (int j = 0; j < n_cand; ++j) {
+        const uint32_t fj = read_lane(first, j);
+        const uint32_t rj = read_lane((uint32_t)rank, j);
+        slot += (fj && rj < (uint32_t)rank) ? 1u : 0u;
+    }
+    const uint32_t n_first = (uint32_t)__popcll(__ballot(first != 0u));
+    if (n_first < k && !(complete && !any_nan)) flags |= RESULT_NEEDS_EXACT;
+    GroupedResultBlock* o = out + q;
+    if (first && slot < k) {
+        o->pos[slot] = my_pos;
+        o->group[slot] = g;
+        o->score[slot] = sc;
+    }
+    if (lane == 0) {  // the count and the flags last
+        o->n_out = n_first < k ? n_first : k;
+        o->flags = flags;
+    }
+}
+
 // K2: merge partial lists, rescore, rank, bound-check.  One workgroup of 1024 threads.
 template <int METRIC>
 __global__ __launch_bounds__(1024) void k_merge_finalize(const Cand32* __restrict__ partials, int n_lists,
@@ -2541,6 +2617,52 @@ hipError_t launch_batch_finalize_rows(hipStream_t s, int metric, const Cand32* l
                            (const double*)score_scratch, q_norms, (uint32_t)nq, ld, m_of, k_of, max_row_norm, in_extra, out);
         return hipGetLastError();
     });
+}
+
+namespace {
+// the MFMA filter's metrics: the collapse stage has no Manhattan form
+template <typename F>
+hipError_t dispatch_mfma_metric(int metric, F&& f)
+{
+    switch (metric) {
+    case COSINE: return f(std::integral_constant<int, COSINE>{});
+    case EUCLIDEAN: return f(std::integral_constant<int, EUCLIDEAN>{});
+    case DOT: return f(std::integral_constant<int, DOT>{});
+    default: return hipErrorInvalidValue;
+    }
+}
+}  // namespace
+
+hipError_t launch_batch_rank_collapse(hipStream_t s, int metric, const Cand32* lists, const double* scores, int nq,
+                                      const double* q_norms, uint32_t ld, uint64_t n_rows, uint32_t k, double max_row_norm,
+                                      const uint32_t* group_of_row, uint64_t index_rows, GroupedResultBlock* out, double in_extra)
+{
+    if (nq <= 0 || !lists || !scores || !q_norms || !group_of_row || !out || n_rows == 0 || k == 0 || k > (uint32_t)KFAST_MAX ||
+        index_rows >= 0xFFFFFFFFull)
+        return hipErrorInvalidValue;
+    return dispatch_mfma_metric(metric, [&](auto M) -> hipError_t {
+        constexpr int MM = decltype(M)::value;
+        hipLaunchKernelGGL((k_batch_rank_collapse<MM>), dim3(((unsigned)nq + 3u) / 4u), dim3(256), 0, s, lists, scores, q_norms,
+                           (uint32_t)nq, ld, n_rows, k, max_row_norm, in_extra, group_of_row, (uint32_t)index_rows, out);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_batch_finalize_grouped(hipStream_t s, int metric, const Cand32* lists, int nq, const double* master,
+                                         const double* q64, const double* q_norms, uint32_t dim, uint64_t n_rows, uint32_t k,
+                                         double max_row_norm, const uint32_t* group_of_row, uint64_t index_rows,
+                                         GroupedResultBlock* out, double in_extra, double* score_scratch)
+{
+    if (nq <= 0 || !score_scratch) return hipErrorInvalidValue;
+    const uint32_t ld = (dim + 3u) & ~3u;
+    const hipError_t e = dispatch_mfma_metric(metric, [&](auto M) -> hipError_t {
+        constexpr int MM = decltype(M)::value;
+        hipLaunchKernelGGL((k_batch_rescore<MM>), dim3((unsigned)nq * 4u), dim3(256), 0, s, lists, master, q64, dim, score_scratch);
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return e;
+    return launch_batch_rank_collapse(s, metric, lists, score_scratch, nq, q_norms, ld, n_rows, k, max_row_norm, group_of_row,
+                                      index_rows, out, in_extra);
 }
 
 hipError_t launch_merge_finalize_multi(hipStream_t s, int metric, Cand32* partials, int n_lists_total, int n_parts,

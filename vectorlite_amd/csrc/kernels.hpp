@@ -291,6 +291,38 @@ hipError_t launch_group_collapse(hipStream_t s, const uint64_t* pv, const double
                                  uint32_t* first, uint32_t k, uint64_t* out_keys, uint32_t* out_pos, double* out_scores,
                                  uint32_t* out_n);
 
+// Batched grouped search.  Device -> host block of one query of a launch sequence: entry t < n_out is
+// the t-th group of the answer as (dense group number, storage position, reference score).  flags == 0: the query is
+// settled and the block is its answer; RESULT_NEEDS_EXACT: the host hands the query to the single call.
+struct GroupedResultBlock {
+    uint32_t n_out;
+    uint32_t flags;  // RESULT_* bits
+    uint32_t pos[KP];
+    uint32_t group[KP];
+    double score[KP];
+};
+// launch_batch_finalize with a rank-and-collapse stage in k_batch_rank_emit's place: lists hold rows of S only (every row
+// that has a group, or the rows under the sequence's one keep bitmap), n_rows = |S| > 0, 1 <= k <= KFAST_MAX.  A candidate
+// is certified iff its score is > bound_for_key(the list's 64th key) -- or the list holds all n_rows <= 64 rows; the
+// certified ones are collapsed to the first row of each group and the first k of those emitted.  Settled iff k groups came
+// out, or the whole of S was ranked without a NaN.  group_of_row: index_rows words.
+hipError_t launch_batch_finalize_grouped(hipStream_t s, int metric, const Cand32* lists, int nq, const double* master,
+                                         const double* q64, const double* q_norms, uint32_t dim, uint64_t n_rows, uint32_t k,
+                                         double max_row_norm, const uint32_t* group_of_row, uint64_t index_rows,
+                                         GroupedResultBlock* out, double in_extra, double* score_scratch);
+// The stage behind the rescoring alone, on scores the caller supplies (tests/native/grouped_batch_audit.hip).
+hipError_t launch_batch_rank_collapse(hipStream_t s, int metric, const Cand32* lists, const double* scores, int nq,
+                                      const double* q_norms, uint32_t ld, uint64_t n_rows, uint32_t k, double max_row_norm,
+                                      const uint32_t* group_of_row, uint64_t index_rows, GroupedResultBlock* out,
+                                      double in_extra);
+// The keep bitmap of S (grouped.hip): bit p & 63 of keep[p >> 6] is set iff p < n, group_of_row[p] != GROUP_NONE and the
+// filter keeps row p -- filter_keep (an exclusion token's own bitmap) when given, else pos_ids[p] in fids[0..nf) when
+// fids != nullptr (an include token's sorted ids; nf may be 0), else every row.  *m_out (zeroed here) receives the
+// number of bits set.  keep: (n + 63) / 64 words.
+hipError_t launch_group_keep_bits(hipStream_t s, const uint32_t* group_of_row, uint64_t n, const unsigned long long* filter_keep,
+                                  const unsigned long long* pos_ids, const unsigned long long* fids, uint64_t nf,
+                                  unsigned long long* keep, uint32_t* m_out);
+
 // Batched range search: the device tail behind launch_mfma_range_candidates.  cand / cnt / cap are
 // the MFMA filter's per-query candidate buffers; ctr holds RBATCH_CTR_WORDS words per query, zeroed by the caller:
 // [TOTAL] rows of the query with score >= min_scores[q], [NAN] set when a rescored row is NaN, [WANT] entries emitted for
