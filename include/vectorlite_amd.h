@@ -385,6 +385,42 @@ int vl_index_search_mmr(const vl_index *h, uint64_t filter, const double *query,
                         uint64_t fetch_k, double lambda, int metric, uint64_t out_capacity, uint64_t *out_ids,
                         double *out_scores, uint64_t *out_n);
 
+/* nq diversified searches against ONE index state (one hold of the reader lock): what a retrieval pipeline issues per
+ * batch, fetch_k = 20 by convention.  Row i of the [nq, out_stride] outputs and out_n[i] are exactly what
+ * vl_index_search_mmr(h, filter, queries + i * q_len, q_len, k, fetch_k, lambda, metric, out_capacity = out_stride, ...)
+ * returns on that state: ids and f64 score bits in selection order.  out_stride acts as the single call's capacity: with
+ * m = the rows the filter keeps (len without one) and n = min(fetch_k, m), a row holds min(k, n, out_stride) entries, and
+ * nothing is written beyond out_n[i] entries of a row.  filter is 0, an include token or an exclusion token.
+ * The argument checks are the single call's, in its order and with its texts: lambda, fetch_k < k,
+ * fetch_k > VL_MMR_MAX_FETCH, the filter token, the metric, the dimension (whenever len != 0).  A NULL out_n is
+ * VL_ERR_INVALID_ARG.  nq = 0 is VL_OK and writes nothing.  k = 0, out_stride = 0 or an empty (sub)index: every
+ * out_n[i] = 0, VL_OK.  A failing query (VL_ERR_NAN_SCORE) makes the call return the status of the LOWEST-INDEX failing
+ * query; outputs are unspecified on error.  HNSW and vl_flat_create_multi handles return VL_ERR_INVALID_ARG.  Never joins a
+ * coalesced pass.
+ * Route: with two or more queries, n <= 60, cosine / Euclidean / dot, a row length the batch filter has a shape for (up to
+ * 768), at least 8192 rows, in-domain rows, m > 0 and no forced path, the queries of a launch sequence share ONE pass of the
+ * bf16 MFMA batch filter -- over every row when filter = 0, under an exclusion token's own keep bitmap, or under a bitmap of
+ * an include token's rows built on the device; no position list is read (an exclusion token's is not even built; an
+ * include token's exists since its resolution) -- and each query's 64 candidates are rescored in the reference's order
+ * and ranked.  The candidates scoring strictly above the exactness bound of the list's 64th key are a
+ * prefix of the exact ranking; a query whose prefix holds n candidates (or whose m <= 64 rows all sit in the list) is
+ * settled on the device: the pairwise similarities of those n rows and the greedy selection, in the single call's
+ * arithmetic.  Otherwise (a NaN score, fewer than 64 candidates while m > 64, a query outside the fast-path domain, a zero
+ * query under cosine, a shorter prefix) the single call's body answers it under the same lock, in ascending query order.
+ * Everything else is a loop over the single call's body under the lock.
+ * vl_last_path is VL_PATH_FAST when the pass settled any query, else the last single call's.
+ * vl_index_set_mmr_batch: 0 = always the loop, 1 = the pass whenever the batch is eligible, 2 = auto (the default): the pass
+ * when its estimated time is below the loop's (csrc/mmr_batch_plan.hpp; both estimates are derived).
+ * vl_index_last_mmr_batch: of the last call on this handle, the queries sent to the pass, those it settled, those it handed
+ * back (routed = settled + handed_back) and its launch sequences; all zero when the call looped.  Any pointer may be NULL.
+ * Single-GPU flat handles only. */
+int vl_index_search_mmr_batch(const vl_index *h, uint64_t filter, const double *queries, uint64_t nq, uint64_t q_len,
+                              uint64_t k, uint64_t fetch_k, double lambda, int metric, uint64_t out_stride,
+                              uint64_t *out_ids, double *out_scores /* [nq, out_stride] */, uint64_t *out_n /* [nq] */);
+int vl_index_set_mmr_batch(vl_index *h, int mode);
+int vl_index_last_mmr_batch(const vl_index *h, uint64_t *routed, uint64_t *settled, uint64_t *handed_back,
+                            uint64_t *sequences);
+
 /* NEW capability (the reference only answers in rows): the best k GROUPS, each shown by its best row -- "the best k
  * documents" over an index of chunks (group_by / collapse / search-groups elsewhere).
  * A group table maps ids to caller-chosen u64 group keys.  vl_index_groups_create: ids / group_keys [n] in any order; an id

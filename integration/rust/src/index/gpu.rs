@@ -66,6 +66,9 @@ extern "C" {
     fn vl_index_search_grouped(h: *const vl_index, groups: u64, filter: u64, query: *const f64, q_len: u64, k: u64, metric: c_int, out_capacity: u64, out_group_keys: *mut u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_grouped_batch(h: *const vl_index, groups: u64, filter: u64, queries: *const f64, nq: u64, q_len: u64, k: u64, metric: c_int, out_stride: u64, out_group_keys: *mut u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_mmr(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, k: u64, fetch_k: u64, lambda: f64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
+    fn vl_index_search_mmr_batch(h: *const vl_index, filter: u64, queries: *const f64, nq: u64, q_len: u64, k: u64, fetch_k: u64, lambda: f64, metric: c_int, out_stride: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
+    fn vl_index_set_mmr_batch(h: *mut vl_index, mode: c_int) -> c_int;
+    fn vl_index_last_mmr_batch(h: *const vl_index, routed: *mut u64, settled: *mut u64, handed_back: *mut u64, sequences: *mut u64) -> c_int;
     fn vl_flat_create_multi(dim: u64, device_ids: *const c_int, n_dev: c_int, mode: c_int, out: *mut *mut vl_index) -> c_int;
     fn vl_index_len(h: *const vl_index) -> u64;
     fn vl_index_get_vector(h: *const vl_index, id: u64, out: *mut f64) -> c_int;
@@ -729,6 +732,63 @@ impl GpuFlatIndex {
             VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
             _ => Err(VectorLiteError::InternalError(last_error())),
         }
+    }
+
+    /// `search_mmr` for a batch of queries against one index state (no reference counterpart): entry `i` is
+    /// `search_mmr(queries[i], k, fetch_k, lambda, metric)`.  Eligible batches share passes of the bf16 MFMA batch filter
+    /// (`vl_index_set_mmr_batch`), every other one loops under one lock.  All queries must have the index's dimension.
+    /// Single-GPU handles only.
+    pub fn search_mmr_batch(&self, queries: &[Vec<f64>], k: usize, fetch_k: usize, lambda: f64, metric: SimilarityMetric) -> VectorLiteResult<Vec<Vec<SearchResult>>> {
+        let nq = queries.len();
+        if nq == 0 {
+            return Ok(Vec::new());
+        }
+        let q_len = queries[0].len();
+        if queries.iter().any(|q| q.len() != q_len) {
+            return Err(VectorLiteError::InternalError("search_mmr_batch: queries of one length".to_string()));
+        }
+        let flat: Vec<f64> = queries.iter().flat_map(|q| q.iter().copied()).collect();
+        let stride = k.min(1024);
+        let len = (nq * stride).max(1);
+        let (mut out_ids, mut scores, mut n) = (vec![0u64; len], vec![0f64; len], vec![0u64; nq]);
+        let rc = unsafe {
+            vl_index_search_mmr_batch(self.0.raw, 0, flat.as_ptr(), nq as u64, q_len as u64, k as u64, fetch_k as u64, lambda, metric_code(metric), stride as u64, out_ids.as_mut_ptr(), scores.as_mut_ptr(), n.as_mut_ptr())
+        };
+        match rc {
+            VL_OK => Ok((0..nq)
+                .map(|qi| {
+                    (0..n[qi] as usize)
+                        .map(|i| {
+                            let id = out_ids[qi * stride + i];
+                            let (text, metadata) = self.0.side.get(&id).cloned().unwrap_or_default();
+                            SearchResult { id, score: scores[qi * stride + i], text, metadata }
+                        })
+                        .collect()
+                })
+                .collect()),
+            VL_ERR_DIM_MISMATCH => {
+                let (mut e, mut a) = (0u64, 0u64);
+                unsafe { vl_last_dim_mismatch(&mut e, &mut a) };
+                Err(VectorLiteError::DimensionMismatch { expected: e as usize, actual: a as usize })
+            }
+            VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
+            _ => Err(VectorLiteError::InternalError(last_error())),
+        }
+    }
+
+    /// How `search_mmr_batch` answers an eligible batch: 0 = the loop, 1 = the MFMA pass, 2 = auto (the default).
+    pub fn set_mmr_batch(&self, mode: i32) -> VectorLiteResult<()> {
+        match unsafe { vl_index_set_mmr_batch(self.0.raw, mode as c_int) } {
+            VL_OK => Ok(()),
+            _ => Err(VectorLiteError::InternalError(last_error())),
+        }
+    }
+
+    /// Of the last `search_mmr_batch`: (queries sent to the pass, settled there, handed back, launch sequences).
+    pub fn last_mmr_batch(&self) -> (u64, u64, u64, u64) {
+        let (mut r, mut s, mut hb, mut q) = (0u64, 0u64, 0u64, 0u64);
+        unsafe { vl_index_last_mmr_batch(self.0.raw, &mut r, &mut s, &mut hb, &mut q) };
+        (r, s, hb, q)
     }
 
     /// The embed -> search step of `Collection::search_text` (src/client.rs:393-401) for a batch: `embeddings` is `[nq, dim]`

@@ -517,6 +517,28 @@ def _search_mmr(L, h, query, k: int, fetch_k: int, lambda_mult: float, metric: i
     return ids[:m].copy(), scores[:m].copy()
 
 
+MMR_BATCH_MODES = {"off": 0, "on": 1, "auto": 2}
+
+
+def _search_mmr_batch(L, h, queries, k: int, fetch_k: int, lambda_mult: float, metric: int, token: int):
+    """vl_index_search_mmr_batch -> (ids [nq, stride], scores [nq, stride], n [nq]); row i holds n[i] entries in selection order."""
+    Q = np.ascontiguousarray(_f64(queries))
+    if Q.ndim != 2:
+        raise ValueError("queries must be [nq, dim]")
+    nq, q_len = Q.shape
+    k = min(max(int(k), 0), 1 << 62)
+    stride = min(k, VL_MMR_MAX_FETCH)
+    ids = np.zeros((nq, stride), dtype=np.uint64)
+    scores = np.zeros((nq, stride), dtype=np.float64)
+    n = np.zeros(nq, dtype=np.uint64)
+    rc = L.vl_index_search_mmr_batch(h, int(token), Q.ctypes.data, nq, q_len, k, max(int(fetch_k), 0), float(lambda_mult),
+                                     int(metric), stride, ids.ctypes.data, scores.ctypes.data, n.ctypes.data)
+    if rc == VL_ERR_INVALID_ARG:
+        raise IndexOpError(_last_error())
+    _raise(rc)
+    return ids, scores, n
+
+
 def _update_rows(L, h, dim: int, ids, values, insert_missing: bool) -> Tuple[int, int]:
     """vl_index_update_bulk -> (rows rewritten, rows appended); the library's refusals as IndexOpError."""
     ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64)).ravel()
@@ -897,6 +919,49 @@ class FlatIndex:
             text, md = self._meta.get(i, ("", None))
             out.append(SearchResult(id=i, score=s, text=text, metadata=md))
         return out
+
+    def search_mmr_batch_arrays(self, queries, k: int, fetch_k: int = 20, lambda_mult: float = 0.5, metric: int = 0, filter=None,
+                                exclude=None):
+        """(ids [nq, k], scores [nq, k], n [nq]) for queries [nq, dim]: the first n[i] entries of row i are
+        search_mmr_arrays(queries[i], k, fetch_k, lambda_mult, ...), all rows on one index state.  Eligible batches share
+        passes of the bf16 MFMA batch filter (set_mmr_batch); answers are identical on every route."""
+        filter = _one_filter(filter, exclude)
+        if filter is None:
+            return _search_mmr_batch(self._L, self._h, queries, k, fetch_k, lambda_mult, metric, 0)
+        tok, temp = self._filter_token(filter)
+        try:
+            return _search_mmr_batch(self._L, self._h, queries, k, fetch_k, lambda_mult, metric, tok)
+        finally:
+            if temp is not None:
+                temp.close()
+
+    def search_mmr_batch(self, queries, k: int, fetch_k: int = 20, lambda_mult: float = 0.5,
+                         similarity_metric: int = SimilarityMetric.Cosine, filter=None, exclude=None) -> List[List[SearchResult]]:
+        ids, scores, n = self.search_mmr_batch_arrays(queries, k, fetch_k, lambda_mult, similarity_metric, filter=filter,
+                                                      exclude=exclude)
+        out = []
+        for r in range(len(n)):
+            m = int(n[r])
+            row = []
+            for i, s in zip(ids[r, :m].tolist(), scores[r, :m].tolist()):
+                text, md = self._meta.get(i, ("", None))
+                row.append(SearchResult(id=i, score=s, text=text, metadata=md))
+            out.append(row)
+        return out
+
+    def set_mmr_batch(self, mode: str) -> None:
+        """How search_mmr_batch answers an eligible batch: "off" (a loop over the single diversified search under one
+        lock), "on" (one bf16 MFMA pass per launch sequence, each query's certified candidates compared and selected on the
+        device; what the pass does not settle goes to the single search) or "auto" (new handles: the pass when its
+        estimated time is below the loop's).  Answers are identical in every mode."""
+        _raise(self._L.vl_index_set_mmr_batch(self._h, MMR_BATCH_MODES[mode]))
+
+    def last_mmr_batch(self) -> Dict[str, int]:
+        """Of the last search_mmr_batch on this handle: queries sent to the MFMA pass, those it settled, those it handed
+        back to the single search, and its launch sequences; all zero when the call looped."""
+        v = [C.c_uint64(0) for _ in range(4)]
+        _raise(self._L.vl_index_last_mmr_batch(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("routed", "settled", "handed_back", "sequences"), (int(x.value) for x in v)))
 
     def search_positions(self, query, k: int, metric: int = 0):
         """(positions, ids, scores): positions are storage positions, for row-shard merging."""
@@ -1615,6 +1680,14 @@ class HNSWIndex:
     def search_mmr(self, query, k: int, fetch_k: int = 20, lambda_mult: float = 0.5,
                    similarity_metric: int = SimilarityMetric.Cosine, filter=None):
         return self.search_mmr_arrays(query, k, fetch_k, lambda_mult, similarity_metric, filter)
+
+    def search_mmr_batch_arrays(self, queries, k: int, fetch_k: int = 20, lambda_mult: float = 0.5, metric: int = 0, filter=None):
+        """Diversified search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""
+        return _search_mmr_batch(self._L, self._h, queries, k, fetch_k, lambda_mult, metric, 0)
+
+    def search_mmr_batch(self, queries, k: int, fetch_k: int = 20, lambda_mult: float = 0.5,
+                         similarity_metric: int = SimilarityMetric.Cosine, filter=None):
+        return self.search_mmr_batch_arrays(queries, k, fetch_k, lambda_mult, similarity_metric, filter)
 
     def make_groups(self, ids, keys) -> GroupTable:
         """Grouped search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""

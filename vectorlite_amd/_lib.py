@@ -21,6 +21,7 @@ SYMBOLS = [
     "vl_index_last_range_batch_candidates", "vl_index_search_mmr",
     "vl_index_groups_create", "vl_index_groups_rows", "vl_index_groups_destroy", "vl_index_search_grouped",
     "vl_index_search_grouped_batch", "vl_index_set_grouped_batch", "vl_index_last_grouped_batch",
+    "vl_index_search_mmr_batch", "vl_index_set_mmr_batch", "vl_index_last_mmr_batch",
     "vl_index_len", "vl_index_is_empty", "vl_index_dimension", "vl_index_get_vector", "vl_index_max_id",
     "vl_index_export", "vl_index_search_positions", "vl_index_search_batch_positions", "vl_index_search_batch_dev", "vl_index_search_batch_embeddings_f32", "vl_index_hnsw_distances", "vl_hnsw_score",
     "vl_last_error", "vl_last_dim_mismatch", "vl_last_path", "vl_index_force_path", "vl_index_set_single_filter",
@@ -111,6 +112,9 @@ def load() -> C.CDLL:
     sig("vl_index_search_grouped_batch", i32, [vp, u64, u64, vp, u64, u64, u64, i32, u64, vp, vp, vp, vp])
     sig("vl_index_set_grouped_batch", i32, [vp, i32])
     sig("vl_index_last_grouped_batch", i32, [vp, p_u64, p_u64, p_u64, p_u64])
+    sig("vl_index_search_mmr_batch", i32, [vp, u64, vp, u64, u64, u64, u64, f64, i32, u64, vp, vp, vp])
+    sig("vl_index_set_mmr_batch", i32, [vp, i32])
+    sig("vl_index_last_mmr_batch", i32, [vp, p_u64, p_u64, p_u64, p_u64])
     sig("vl_index_len", u64, [vp])
     sig("vl_index_is_empty", i32, [vp])
     sig("vl_index_dimension", u64, [vp])

@@ -515,6 +515,41 @@ int vl_index_search_mmr(const vl_index* h, uint64_t filter, const double* query,
     });
 }
 
+int vl_index_search_mmr_batch(const vl_index* h, uint64_t filter, const double* queries, uint64_t nq, uint64_t q_len, uint64_t k,
+                              uint64_t fetch_k, double lambda, int metric, uint64_t out_stride, uint64_t* out_ids,
+                              double* out_scores, uint64_t* out_n)
+{
+    return guarded([&]() -> int {
+        const int arc = vl::mmr_check_args(k, fetch_k, lambda);  // the single call's checks, in its order: no device is needed
+        if (arc != VL_OK) return arc;
+        if (!h) return VL_ERR_INVALID_ARG;
+        if (!h->flat) {
+            vl::set_last_error("diversified (MMR) search is served by single-GPU flat indexes");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (nq == 0) return h->flat->search_mmr_batch(filter, queries, 0, q_len, k, fetch_k, lambda, metric, out_stride, nullptr,
+                                                      nullptr, nullptr);
+        if (!out_n) return VL_ERR_INVALID_ARG;
+        if ((!out_ids || !out_scores) && k != 0 && out_stride != 0) return VL_ERR_INVALID_ARG;
+        return h->flat->search_mmr_batch(filter, queries, nq, q_len, k, fetch_k, lambda, metric, out_stride, out_ids, out_scores,
+                                         out_n);
+    });
+}
+
+int vl_index_set_mmr_batch(vl_index* h, int mode)
+{
+    if (!h || !h->flat || mode < 0 || mode > 2) return VL_ERR_INVALID_ARG;
+    h->flat->set_mmr_batch(mode);
+    return VL_OK;
+}
+
+int vl_index_last_mmr_batch(const vl_index* h, uint64_t* routed, uint64_t* settled, uint64_t* handed_back, uint64_t* sequences)
+{
+    if (!h || !h->flat) return VL_ERR_INVALID_ARG;
+    h->flat->last_mmr_batch(routed, settled, handed_back, sequences);
+    return VL_OK;
+}
+
 static_assert(VL_GROUPED_MAX_K == vl::GROUPED_MAX_K, "the header states the kernels' limit");
 
 int vl_index_groups_create(vl_index* h, const uint64_t* ids, const uint64_t* group_keys, uint64_t n, uint64_t* out_groups,

@@ -14,6 +14,7 @@
 #include "subset_batch_plan.hpp"
 #include "masked_batch_plan.hpp"
 #include "grouped_batch_plan.hpp"
+#include "mmr_batch_plan.hpp"
 
 #include <chrono>
 
@@ -230,7 +231,7 @@ Workspace::~Workspace()
     void* dev[] = {d_q64, d_partials, d_partials64, d_result, d_nan, d_scores, d_okeys,
                    d_opos, d_out_pos, d_out_scores, d_positions, d_dists, rg_ctr, rg_cand, rg_scores, rg_keys, rg_pv, mmr_sim,
                    rb_ctr, rb_min, rb_sv_score, rb_sv_pos, gp_best, gp_first, gp_lists, gp_cand, gp_scores, gp_ctr, gp_out_keys,
-                   gb_keep, gb_m};
+                   gb_keep, gb_m, mb_ranked};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     void* host[] = {h_q64, h_result, h_nan, mf_h_q64, mf_h_result, mf_h_dom, k3_h_q64, k3_h_result, rg_h_ctr, rg_h_pos, rg_h_scores,
@@ -2337,29 +2338,141 @@ int GpuFlatIndex::search_mmr(uint64_t token, const double* query, uint64_t q_len
     if (n == 0 || k_cap == 0) return OK;
     if ((!query && dim_) || !out_scores) return ERR_INVALID_ARG;
     return run_search(nullptr, f.get(), [&](Workspace* ws) -> int {
-        const uint64_t rows = f ? f->m : n;
-        if (rows == 0) return OK;
-        const uint64_t fetch_eff = std::min<uint64_t>(fetch_k, rows);
-        const MmrReq req{std::min<uint64_t>(k_cap, fetch_eff), lambda};
-        if (req.k_out == 1) {
-            // sel = [0]: the best of search(q, fetch_k), whose errors are this call's
-            std::vector<uint64_t> pos(fetch_eff), ids(fetch_eff);
-            std::vector<double> scores(fetch_eff);
-            uint64_t got = 0;
-            VL_TRY(f ? search_subset(ws, f.get(), query, fetch_eff, metric, pos.data(), ids.data(), scores.data(), &got)
-                     : search_locked(ws, query, fetch_eff, metric, pos.data(), ids.data(), scores.data(), &got, false));
-            if (got >= 1) {
-                if (out_pos) out_pos[0] = pos[0];
-                if (out_ids) out_ids[0] = ids[0];
-                out_scores[0] = scores[0];
-                *out_n = 1;
-            }
-            return OK;
-        }
-        if (!ws->mmr_sim) VL_TRY(dev_alloc(&ws->mmr_sim, (size_t)MMR_MAX_FETCH * MMR_MAX_FETCH));
-        return f ? search_subset(ws, f.get(), query, fetch_eff, metric, out_pos, out_ids, out_scores, out_n, &req)
-                 : search_locked(ws, query, fetch_eff, metric, out_pos, out_ids, out_scores, out_n, false, false, &req);
+        return search_mmr_locked(ws, f.get(), query, k_cap, fetch_k, lambda, metric, out_pos, out_ids, out_scores, out_n);
     });
+}
+
+int GpuFlatIndex::search_mmr_locked(Workspace* ws, IdFilter* f, const double* query, uint64_t k_cap, uint64_t fetch_k, double lambda,
+                                    int metric, uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n) const
+{
+    const uint64_t rows = f ? f->m : ids_.size();
+    if (rows == 0) return OK;
+    const uint64_t fetch_eff = std::min<uint64_t>(fetch_k, rows);
+    const MmrReq req{std::min<uint64_t>(k_cap, fetch_eff), lambda};
+    if (req.k_out == 1) {
+        // sel = [0]: the best of search(q, fetch_k), whose errors are this call's
+        std::vector<uint64_t> pos(fetch_eff), ids(fetch_eff);
+        std::vector<double> scores(fetch_eff);
+        uint64_t got = 0;
+        VL_TRY(f ? search_subset(ws, f, query, fetch_eff, metric, pos.data(), ids.data(), scores.data(), &got)
+                 : search_locked(ws, query, fetch_eff, metric, pos.data(), ids.data(), scores.data(), &got, false));
+        if (got >= 1) {
+            if (out_pos) out_pos[0] = pos[0];
+            if (out_ids) out_ids[0] = ids[0];
+            out_scores[0] = scores[0];
+            *out_n = 1;
+        }
+        return OK;
+    }
+    if (!ws->mmr_sim) VL_TRY(dev_alloc(&ws->mmr_sim, (size_t)MMR_MAX_FETCH * MMR_MAX_FETCH));
+    return f ? search_subset(ws, f, query, fetch_eff, metric, out_pos, out_ids, out_scores, out_n, &req)
+             : search_locked(ws, query, fetch_eff, metric, out_pos, out_ids, out_scores, out_n, false, false, &req);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Batched diversified search: nq MMR queries against one index state.  MMR needs the first
+// n = min(fetch_k, m) rows of S's ranking, exact and in order, and nothing behind them: the certified prefix of the MFMA
+// batch filter's rescored 64-entry list (section 26) gives them whenever it is n long.  k_mmr_batch_rank decides that per
+// query, k_mmr_batch_select computes the n candidates' similarities and runs the selection; a query the pass does not
+// settle runs the single search's body under the same lock, so each row is the single call's answer bit for bit.
+// ---------------------------------------------------------------------------------------------
+int GpuFlatIndex::search_mmr_batch(uint64_t token, const double* queries, uint64_t nq, uint64_t q_len, uint64_t k, uint64_t fetch_k,
+                                   double lambda, int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores,
+                                   uint64_t* out_n) const
+{
+    uint64_t mb[4] = {0, 0, 0, 0};  // last_mmr_batch: routed, settled, handed back, sequences
+    auto publish = [&]() {
+        for (int i = 0; i < 4; ++i) last_mmrbatch_[i].store(mb[i], std::memory_order_relaxed);
+    };
+    if (nq == 0) {
+        publish();
+        return OK;
+    }
+    if (!out_n) return ERR_INVALID_ARG;
+    for (uint64_t i = 0; i < nq; ++i) out_n[i] = 0;
+    set_last_path(PATH_NONE);
+    VL_TRY(mmr_check_args(k, fetch_k, lambda));
+    std::shared_ptr<IdFilter> f;
+    if (token != 0) VL_TRY(find_filter(token, &f));
+    std::shared_lock<RwLock> lk;  // one index state for the whole batch
+    VL_TRY(lock_for_query(metric, q_len, &lk));
+    publish();
+    const uint64_t n = ids_.size();
+    const uint64_t k_cap = std::min<uint64_t>(k, out_stride);  // out_stride is the single call's capacity
+    if (n == 0 || k_cap == 0) return OK;
+    if ((!queries && dim_) || !out_scores) return ERR_INVALID_ARG;
+
+    WsLease lease(this, /*sync_always=*/true);
+    if (lease.status() != OK) return lease.status();
+    Workspace* const ws = lease.ws;
+    // an exclusion token's position list waits until a query is left to the single search: the pass reads a bitmap
+    if (f) VL_TRY(resolve_if_stale(ws, f.get(), /*need_list=*/!f->exclude));
+    InFlight searching(active_searches_);
+    const uint64_t m = f ? f->m : n;
+    if (m == 0) return OK;  // an empty S (search_mmr's early return)
+
+    std::vector<uint8_t> done(nq, 0);
+    {
+        const char* mf_env = getenv("VL_MFMA");
+        const char* mf_min = getenv("VL_MFMA_MIN_BATCH");
+        const MaskedBatchLimits lim{MFMA_MIN_ROWS, mf_min && *mf_min ? (uint64_t)atoi(mf_min) : (uint64_t)MFMA_MIN_BATCH,
+                                    (uint64_t)KFAST_MAX, mfma_sequence_queries((uint32_t)dim_)};
+        MmrBatchShape shp;
+        shp.index = {force_path_.load() == 0 && n_out_of_domain_ == 0 && dim_ != 0 && !(mf_env && mf_env[0] == '0') &&
+                         mfma_scan_supported((uint32_t)dim_, metric),
+                     n, (uint32_t)dim_, ld_, mfma_ldb((uint32_t)dim_)};
+        shp.rows_kernel = mfma_rows_kernel((uint32_t)dim_);
+        shp.filtered = f != nullptr;
+        shp.include = f && !f->exclude;
+        shp.m = m;
+        shp.i8_min_bytes = i8_min_bytes_;
+        shp.bf16_min_bytes = auto_min_bytes_;
+        if (mmr_batch_route(mmr_batch_.load(), shp, lim, nq, fetch_k)) {
+            const uint64_t n_need = std::min<uint64_t>(fetch_k, m);
+            const unsigned long long* keep = nullptr;
+            if (f && f->exclude) {
+                keep = f->d_keep;  // the token's own bitmap (section 24)
+            } else if (f) {        // an include token: its rows as a bitmap, in the borrowed workspace; no list is read
+                const uint64_t words = (n + 63) / 64;
+                VL_TRY(grow(HipMem{}, ws->gb_keep_cap, words, {dev_buf(ws->gb_keep, words)}));
+                VL_TRY(ensure_device_ids());
+                VL_HIP(launch_filter_bits(ws->stream, d_ids_, n, f->d_ids, f->ids.size(), ws->gb_keep, /*include=*/true));
+                keep = ws->gb_keep;
+            }
+            std::vector<uint32_t> qidx, mq, kq;
+            std::vector<const unsigned long long*> keep_of;
+            MaskedQueries desc{nullptr, nullptr, nullptr, nullptr};
+            if (keep) {  // every query of every sequence under the ONE bitmap of S
+                qidx.resize(nq);
+                for (uint64_t i = 0; i < nq; ++i) qidx[i] = (uint32_t)i;
+                mq.assign(nq, (uint32_t)m);
+                kq.assign(nq, (uint32_t)n_need);
+                keep_of.assign(nq, keep);
+                desc = {qidx.data(), keep_of.data(), mq.data(), kq.data()};
+            }
+            const MmrBatchReq req{m, n_need, std::min<uint64_t>(k_cap, n_need), lambda, out_stride};
+            VL_TRY(search_batch_mfma(ws, queries, nullptr, nq, out_stride, n_need, metric, nullptr, out_ids, out_scores, out_n, &done,
+                                     nullptr, keep ? &desc : nullptr, &mb[3], nullptr, &req));
+            mb[0] = nq;
+            for (uint64_t qi = 0; qi < nq; ++qi) mb[1] += done[qi] ? 1 : 0;
+            mb[2] = mb[0] - mb[1];
+        }
+    }
+    // what the pass did not settle (or everything), in ascending order: the first failure is the lowest failing query
+    bool list_ready = !(f && f->exclude);
+    for (uint64_t qi = 0; qi < nq; ++qi) {
+        if (done[qi]) continue;
+        if (!list_ready) {
+            std::lock_guard<std::mutex> fg(f->mu);
+            VL_TRY(ensure_plist(ws, f.get()));
+            list_ready = true;
+        }
+        VL_TRY(search_mmr_locked(ws, f.get(), queries + qi * dim_, k_cap, fetch_k, lambda, metric, nullptr,
+                                 out_ids ? out_ids + qi * out_stride : nullptr, out_scores + qi * out_stride, out_n + qi));
+    }
+    if (mb[1]) set_last_path(PATH_FAST);
+    publish();
+    return OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3180,12 +3293,15 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
                                     uint64_t k, uint64_t k_eff, int metric, uint64_t* out_pos, uint64_t* out_ids,
                                     double* out_scores, uint64_t* out_n, std::vector<uint8_t>* done,
                                     const ShardRecordSink* sink, const MaskedQueries* masked, uint64_t* n_sequences,
-                                    const GroupedReq* grouped) const
+                                    const GroupedReq* grouped, const MmrBatchReq* mmr) const
 {
     static_assert(sizeof(const unsigned long long*) == sizeof(double) && 2 * sizeof(uint32_t) == sizeof(double),
                   "the masked descriptor is staged as two words per query behind the norms");
     if (masked && (d_queries || sink || !mfma_rows_kernel((uint32_t)dim_))) return ERR_INVALID_ARG;
     if (grouped && (d_queries || sink || !out_ids || !grouped->out_keys || k_eff == 0 || k_eff > (uint64_t)KFAST_MAX))
+        return ERR_INVALID_ARG;
+    if (mmr && (grouped || d_queries || sink || k_eff != mmr->n || mmr->n == 0 || mmr->n > (uint64_t)KFAST_MAX || mmr->n > mmr->m ||
+                mmr->k_out == 0 || mmr->k_out > mmr->n || mmr->k_out > mmr->out_stride))
         return ERR_INVALID_ARG;
     if (n_sequences) *n_sequences = 0;
     const uint64_t n = ids_.size();
@@ -3194,6 +3310,7 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
     const void* slab16 = frag ? d_slab16f_ : d_slab16_;
     VL_TRY(ensure_mfma_scratch(ws));
     if (grouped) VL_TRY(ensure_set(HipMem{}, {pinned_buf(ws->gb_h_result, 2 * (size_t)MFMA_MAX_BATCH)}));
+    if (mmr) VL_TRY(ensure_set(HipMem{}, {dev_buf(ws->mb_ranked, (size_t)MFMA_MAX_BATCH)}));
     hipStream_t st = ws->stream;
     const double in_extra = IN_EXTRA_MFMA;  // bf16 rows and queries (mfma_scan.hpp)
     const uint64_t k_eff_all = k_eff;       // (a masked batch has its own per query)
@@ -3301,7 +3418,11 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
             VL_HIP(launch_batch_finalize_grouped(st, metric, ws->mf_lists, (int)g, d_master_, ws->mf_d_q64, d_norms, (uint32_t)dim_,
                                                  grouped->m, (uint32_t)k_eff, max_row_norm_, grouped->table->d_group_of_row, n,
                                                  ws->gb_h_result + (size_t)slot * MFMA_MAX_BATCH, in_extra, ws->mf_scores));
-        else if (masked)  // the certificate per query: n_rows = m_q, k = min(k, m_q) (DESIGN.md sections 23, 24)
+        else if (mmr) {  // the certified prefix of each list, then similarities and selection
+            VL_HIP(launch_batch_rescore(st, metric, ws->mf_lists, (int)g, d_master_, ws->mf_d_q64, (uint32_t)dim_, ws->mf_scores));
+            VL_HIP(launch_mmr_batch(st, metric, ws->mf_lists, ws->mf_scores, (int)g, d_norms, d_master_, (uint32_t)dim_, mmr->m, n,
+                                    (uint32_t)mmr->n, (uint32_t)mmr->k_out, mmr->lambda, max_row_norm_, in_extra, ws->mb_ranked, res));
+        } else if (masked)  // the certificate per query: n_rows = m_q, k = min(k, m_q) (DESIGN.md sections 23, 24)
             VL_HIP(launch_batch_finalize_rows(st, metric, ws->mf_lists, (int)g, d_master_, ws->mf_d_q64, d_norms, (uint32_t)dim_,
                                               d_m, d_m + g, max_row_norm_, res, in_extra, ws->mf_scores));
         else if (g >= 8 && !split_off)
@@ -3359,7 +3480,26 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
             out_n[qi] = want;
             (*done)[qi] = 1;
         }
-        for (uint32_t j = 0; !grouped && j < g; ++j) {
+        for (uint32_t j = 0; mmr && j < g; ++j) {  // settled queries: the selection, position -> id
+            const uint64_t qi = S.q0 + j;
+            const SearchResultBlock& r = res[j];
+            if (!S.in_domain[j] || r.flags != 0u) continue;
+            bool ok = r.n_out == mmr->k_out;
+            for (uint64_t i = 0; ok && i < mmr->k_out; ++i) ok = r.pos[i] < n;
+            if (!ok) {
+                set_last_error("the batched selection returned an out-of-range entry (kernel bug)");
+                return ERR_DEVICE;
+            }
+            for (uint64_t i = 0; i < mmr->k_out; ++i) {
+                const size_t o = qi * mmr->out_stride + i;
+                if (out_pos) out_pos[o] = r.pos[i];
+                if (out_ids) out_ids[o] = ids_[r.pos[i]];
+                out_scores[o] = r.score[i];
+            }
+            out_n[qi] = mmr->k_out;
+            (*done)[qi] = 1;
+        }
+        for (uint32_t j = 0; !grouped && !mmr && j < g; ++j) {
             const uint64_t qi = S.q0 + j;
             const SearchResultBlock& r = res[j];
             const uint64_t k_eff = masked ? masked->k[qi] : k_eff_all;

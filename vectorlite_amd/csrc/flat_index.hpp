@@ -123,6 +123,8 @@ struct Workspace {
     uint32_t* gb_m = nullptr;                   // [1]
     // diversified search (lazy): the candidates' pairwise similarities, [MMR_MAX_FETCH][MMR_MAX_FETCH] (8 MB)
     double* mmr_sim = nullptr;
+    // batched diversified search (lazy): the ranked candidates of a launch sequence's queries, between its two kernels
+    SearchResultBlock* mb_ranked = nullptr;  // [MFMA_MAX_BATCH]
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<float> q32;   // the f32 query handed to k_scan in its kernel arguments
     uint32_t seq = 0;         // stamp of the last single search issued from this workspace (h_result->seq)
@@ -369,6 +371,26 @@ public:
     // min(k, |C|, out_capacity) entries in selection order, scores = the candidates' reference scores.
     int search_mmr(uint64_t token, const double* query, uint64_t q_len, uint64_t k, uint64_t fetch_k, double lambda, int metric,
                    uint64_t out_capacity, uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;
+    // NEW (no reference counterpart): nq diversified searches against one index state; row i of the [nq, out_stride] outputs
+    // and out_n[i] are exactly search_mmr(token, queries + i * q_len, q_len, k, fetch_k, lambda, metric, out_stride, ...).
+    // Eligible batches (mmr_batch_plan.hpp) share passes of the bf16 MFMA filter, followed per query by the rescoring and
+    // the rank / similarity / selection stage (mmr.hip); whatever a pass does not settle, and every batch that is not
+    // eligible, runs the single search's body under the same lock.  Returns the status of the lowest-index failing query.
+    // DESIGN.md section 27.
+    int search_mmr_batch(uint64_t token, const double* queries, uint64_t nq, uint64_t q_len, uint64_t k, uint64_t fetch_k,
+                         double lambda, int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores,
+                         uint64_t* out_n) const;
+    // 0: always the loop.  1: the pass whenever the batch is eligible.  2 ("auto", the default): when its estimate is lower.
+    void set_mmr_batch(int mode) { mmr_batch_.store(mode); }
+    int mmr_batch() const { return mmr_batch_.load(); }
+    // the last search_mmr_batch on this handle: queries sent to the pass, those it settled, those it handed back to the
+    // single search, its launch sequences; all zero when the call looped
+    void last_mmr_batch(uint64_t* routed, uint64_t* settled, uint64_t* handed_back, uint64_t* sequences) const
+    {
+        uint64_t* out[4] = {routed, settled, handed_back, sequences};
+        for (int i = 0; i < 4; ++i)
+            if (out[i]) *out[i] = last_mmrbatch_[i].load(std::memory_order_relaxed);
+    }
     // NEW (no reference counterpart): the best row of each of the best k groups.  A group table maps
     // ids to caller-chosen u64 group keys; rows whose id it does not hold take no part.  With S = the FlatIndex of the rows
     // that have a group (and, token != 0, pass the filter) in storage order, the answer is search(q, len(S)) on S walked from
@@ -578,12 +600,26 @@ private:
         uint64_t out_stride;
         uint64_t* out_keys;
     };
+    // A batched diversified search riding on the sequence pipeline: k_mmr_batch_rank and
+    // k_mmr_batch_select take the rank / emit launch's place and settled queries are unpacked as (id, score) rows in selection
+    // order, out_stride apart.  S has m rows: every row of the index (masked == nullptr) or the rows under the one bitmap every
+    // query of `masked` names.  n = min(fetch_k, m) <= KFAST_MAX candidates, k_out = min(k, n, out_stride) >= 1 chosen.
+    struct MmrBatchReq {
+        uint64_t m;
+        uint64_t n;
+        uint64_t k_out;
+        double lambda;
+        uint64_t out_stride;
+    };
     int search_batch_mfma(Workspace* ws, const double* queries, const double* d_queries, uint64_t nq, uint64_t k,
                           uint64_t k_eff, int metric, uint64_t* out_pos, uint64_t* out_ids, double* out_scores,
                           uint64_t* out_n, std::vector<uint8_t>* done,
                           const ShardRecordSink* sink = nullptr,  // queries on the host, or d_queries on the device
                           const MaskedQueries* masked = nullptr, uint64_t* n_sequences = nullptr,
-                          const GroupedReq* grouped = nullptr) const;
+                          const GroupedReq* grouped = nullptr, const MmrBatchReq* mmr = nullptr) const;
+    // the locked body of search_mmr: mu_ held (shared), the filter resolved with its position list, n != 0, k_cap != 0
+    int search_mmr_locked(Workspace* ws, IdFilter* f, const double* query, uint64_t k_cap, uint64_t fetch_k, double lambda,
+                          int metric, uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;
     // the keep bitmap of S = the table's rows under f (nullptr: the table alone, cached on the table) and |S|; mu_ held,
     // t and f resolved.  No position list is built.
     int grouped_keep_bits(Workspace* ws, GroupTable* t, IdFilter* f, const unsigned long long** keep, uint64_t* m) const;
@@ -676,6 +712,8 @@ private:
     std::atomic<int> masked_batch_{2};  // MASKED_BATCH_AUTO
     mutable std::atomic<uint64_t> last_gbatch_[4] = {};
     std::atomic<int> grouped_batch_{2};  // GROUPED_BATCH_AUTO
+    mutable std::atomic<uint64_t> last_mmrbatch_[4] = {};
+    std::atomic<int> mmr_batch_{2};  // MMR_BATCH_AUTO
     std::atomic<uint64_t> last_delete_[6] = {};
     std::atomic<uint64_t> last_update_[7] = {};
     mutable std::mutex prof_mu_;

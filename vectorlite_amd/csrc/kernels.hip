@@ -380,9 +380,10 @@ __global__ __launch_bounds__(256) void k_filter_compact(const unsigned long long
 
 // The keep bitmap of an exclusion filter: bit p & 63 of keep[p >> 6] is set iff p < n and ids[p] is NOT in the set.  One
 // wave per word: the 64 lanes ballot their rows' membership, lane 0 stores the inverted word (bits at or past n are 0).
+// include != 0 (an include token's rows): the word itself, bit set iff ids[p] IS in the set.
 __global__ __launch_bounds__(256) void k_filter_bits(const unsigned long long* __restrict__ pos_ids, uint32_t n,
                                                      const unsigned long long* __restrict__ fids, uint32_t nf,
-                                                     uint32_t n_words, unsigned long long* __restrict__ keep)
+                                                     uint32_t n_words, unsigned long long* __restrict__ keep, uint32_t include)
 {
     const int lane = lane_id();
     const uint32_t n_waves = gridDim.x * 4;
@@ -390,7 +391,8 @@ __global__ __launch_bounds__(256) void k_filter_bits(const unsigned long long* _
         const uint32_t p = w * 64u + (uint32_t)lane;
         const bool there = p < n;
         const bool in_set = there && id_in_set(pos_ids[p], fids, nf);
-        const unsigned long long word = __ballot(there) & ~__ballot(in_set);
+        const unsigned long long in_word = __ballot(in_set);
+        const unsigned long long word = include ? in_word : (__ballot(there) & ~in_word);
         if (lane == 0) keep[w] = word;
     }
 }
@@ -2665,6 +2667,17 @@ hipError_t launch_batch_finalize_grouped(hipStream_t s, int metric, const Cand32
                                       index_rows, out, in_extra);
 }
 
+hipError_t launch_batch_rescore(hipStream_t s, int metric, const Cand32* lists, int nq, const double* master, const double* q64,
+                                uint32_t dim, double* scores)
+{
+    if (nq <= 0 || !lists || !master || !q64 || !scores) return hipErrorInvalidValue;
+    return dispatch_mfma_metric(metric, [&](auto M) -> hipError_t {
+        constexpr int MM = decltype(M)::value;
+        hipLaunchKernelGGL((k_batch_rescore<MM>), dim3((unsigned)nq * 4u), dim3(256), 0, s, lists, master, q64, dim, scores);
+        return hipGetLastError();
+    });
+}
+
 hipError_t launch_merge_finalize_multi(hipStream_t s, int metric, Cand32* partials, int n_lists_total, int n_parts,
                                        const double* master, const double* q64, const double* q_norm, uint32_t dim,
                                        uint64_t n_rows, uint32_t k, double max_row_norm, SearchResultBlock* out)
@@ -2906,12 +2919,13 @@ hipError_t launch_filter_compact(hipStream_t s, const unsigned long long* pos_id
 }
 
 hipError_t launch_filter_bits(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
-                              uint64_t nf, unsigned long long* keep)
+                              uint64_t nf, unsigned long long* keep, bool include)
 {
     if (n == 0 || n >= 0xFFFFFFFFull || nf >= 0xFFFFFFFFull) return hipErrorInvalidValue;
     const uint64_t n_words = (n + 63) / 64;
     const int grid = (int)std::min<uint64_t>((n_words + 3) / 4, FILTER_MAX_GRID);
-    hipLaunchKernelGGL(k_filter_bits, dim3(grid), dim3(256), 0, s, pos_ids, (uint32_t)n, fids, (uint32_t)nf, (uint32_t)n_words, keep);
+    hipLaunchKernelGGL(k_filter_bits, dim3(grid), dim3(256), 0, s, pos_ids, (uint32_t)n, fids, (uint32_t)nf, (uint32_t)n_words, keep,
+                       include ? 1u : 0u);
     return hipGetLastError();
 }
 

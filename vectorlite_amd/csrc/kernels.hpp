@@ -221,9 +221,10 @@ hipError_t launch_filter_count(hipStream_t s, const unsigned long long* pos_ids,
 hipError_t launch_filter_compact(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
                                  uint64_t nf, const uint32_t* offsets, uint64_t m, uint32_t* plist, bool invert = false);
 // An exclusion filter's keep bitmap: keep[0..(n + 63) / 64), bit p & 63 of word p >> 6 set iff p < n
-// and pos_ids[p] is not in the set (nf may be 0: every row kept).
+// and pos_ids[p] is not in the set (nf may be 0: every row kept).  include: the bit is set iff pos_ids[p] IS in the set (the
+// rows of an include token as a bitmap).
 hipError_t launch_filter_bits(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
-                              uint64_t nf, unsigned long long* keep);
+                              uint64_t nf, unsigned long long* keep, bool include = false);
 // K1 under a keep bitmap: launch_scan's partial lists without the rows whose bit is 0, on launch_scan's grid (sized from n).
 // Only at the strides VL_SCAN_VARIANTS specialises (scan_masked_supported(ld)), the stride's default shape; the query as
 // launch_scan_subset takes it (q32_host where scan_takes_qarg(ld), else q64 in device memory).
@@ -323,6 +324,11 @@ hipError_t launch_group_keep_bits(hipStream_t s, const uint32_t* group_of_row, u
                                   const unsigned long long* pos_ids, const unsigned long long* fids, uint64_t nf,
                                   unsigned long long* keep, uint32_t* m_out);
 
+// k_batch_rescore alone: scores[q * KP + i] = the reference f64 score of query q against the row of lists[q * KP + i] (the
+// batched MMR search runs its own stage behind it, mmr.hip).  The MFMA filter's metrics.
+hipError_t launch_batch_rescore(hipStream_t s, int metric, const Cand32* lists, int nq, const double* master, const double* q64,
+                                uint32_t dim, double* scores);
+
 // Batched range search: the device tail behind launch_mfma_range_candidates.  cand / cnt / cap are
 // the MFMA filter's per-query candidate buffers; ctr holds RBATCH_CTR_WORDS words per query, zeroed by the caller:
 // [TOTAL] rows of the query with score >= min_scores[q], [NAN] set when a rescored row is NaN, [WANT] entries emitted for
@@ -372,6 +378,17 @@ struct MmrSource {
 // seq != 0: out[0].seq = seq stored last, system-scope release (`out` pinned).  sim: MMR_MAX_FETCH^2 doubles.
 hipError_t launch_mmr(hipStream_t s, int metric, const double* master, uint32_t dim, const MmrSource& src, double* sim,
                       uint32_t k, double lambda, SearchResultBlock* out, uint32_t seq);
+
+// The batched form, behind k_batch_rescore: lists / scores as launch_batch_rank_collapse takes them
+// (rows of S only, n_rows = |S| > 0).  k_mmr_batch_rank certifies the prefix of each query's ranking that scores strictly
+// above bound_for_key(the list's 64th key) -- every candidate when the list holds all n_rows <= 64 rows -- and a query is
+// settled iff no score is NaN and the prefix holds n_need = min(fetch_k, n_rows) <= KFAST_MAX candidates; its first n_need
+// ranked candidates go to ranked[q] (device memory, nq blocks).  k_mmr_batch_select computes their pairwise similarities
+// in LDS and selects min(k, n_need) of them as k_mmr_select does: out[q] = the chosen (storage position, score bits) in
+// selection order, n_out, flags = 0; an unsettled query leaves n_out = 0 and RESULT_NEEDS_EXACT.  master: index_rows rows.
+hipError_t launch_mmr_batch(hipStream_t s, int metric, const Cand32* lists, const double* scores, int nq, const double* q_norms,
+                            const double* master, uint32_t dim, uint64_t n_rows, uint64_t index_rows, uint32_t n_need, uint32_t k,
+                            double lambda, double max_row_norm, double in_extra, SearchResultBlock* ranked, SearchResultBlock* out);
 
 // HNSW distance callbacks: u64 distance of query vs the rows at positions[0..m).
 hipError_t launch_hnsw_distances(hipStream_t s, int metric, const double* master, const double* q64,
