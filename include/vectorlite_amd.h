@@ -259,6 +259,54 @@ int vl_index_filter_create_excluding(vl_index *h, const uint64_t *ids, uint64_t 
 int vl_index_filter_rows(const vl_index *h, uint64_t filter, uint64_t *out_rows);
 int vl_index_filter_destroy(vl_index *h, uint64_t filter);
 
+/* NEW capability: filters by VALUE instead of by id list -- "newer than t", "tenant = 17", "price in [a, b]" -- resolved on
+ * the device, so a bound that changes per request costs one streaming pass over 8 bytes per row and column instead of a
+ * host sort and an upload of the passing ids.  DESIGN.md section 28.
+ * An ATTRIBUTE COLUMN maps ids to int64 values.  vl_index_attr_create: ids / values [n] in any order; a pair repeated exactly
+ * is fine, an id given two different values within one call is VL_ERR_INVALID_ARG (the message names the smallest such id;
+ * checked on the host before any device is touched), as are 2^32 - 1 pairs or more.  An id the index does not hold waits for
+ * a row with that id to be added; a row whose id the column does not hold HAS NO VALUE; duplicate-id rows all get their
+ * id's value.  *out_attr is a token of this handle from the filters' counter (never 0, never reused, not cloned, freed by
+ * vl_index_attr_destroy / vl_index_destroy); *out_rows (may be NULL) and vl_index_attr_rows = rows that have a value now.
+ * vl_index_attr_set upserts pairs: an id already held takes the new value, other ids are added, the same conflict rule
+ * within the call; a refused call leaves the column as it was.  It waits for running searches, like add and delete.
+ * Destroying a column leaves filter tokens made from it working; its memory goes with the last of them.
+ * A column costs 16 bytes per pair on host and device, and 8 bytes + 1 bit per ROW of the index on the device. */
+int vl_index_attr_create(vl_index *h, const uint64_t *ids, const int64_t *values, uint64_t n, uint64_t *out_attr,
+                         uint64_t *out_rows);
+int vl_index_attr_set(vl_index *h, uint64_t attr, const uint64_t *ids, const int64_t *values, uint64_t n);
+int vl_index_attr_rows(const vl_index *h, uint64_t attr, uint64_t *out_rows);
+int vl_index_attr_destroy(vl_index *h, uint64_t attr);
+/* A PREDICATE filter token: 1 to 4 clauses, ANDed.  A row qualifies iff, for every clause, it has a value v in that column
+ * and (lo <= v && v <= hi) != negate, compared as signed integers.  A row without a value never qualifies, even under
+ * negate; lo > hi is legal (it keeps nothing, or with negate every row that has a value); equality is lo == hi.  A clause
+ * count outside 1..4, reserved != 0, negate > 1 or an unknown column: VL_ERR_INVALID_ARG with a message.
+ * The token belongs to the filter token space: vl_index_filter_rows / vl_index_filter_destroy work on it, and every flat
+ * entry point that takes a filter token takes it, with the include token's semantics over "the FlatIndex holding only the
+ * qualifying rows in storage order" and the include token's errors (vl_index_search_batch_filters may mix all three kinds).
+ * It is resolved again on the first use after an add or delete or after vl_index_attr_set on one of its columns (the
+ * columns first, then the predicate).  It costs len / 8 bytes (the keep bitmap) plus 4 bytes per qualifying row once a call
+ * needs the position list; batches treat it as an exclusion token. */
+typedef struct {
+    uint64_t attr;
+    int64_t lo;
+    int64_t hi;
+    uint32_t negate;
+    uint32_t reserved;
+} vl_where_clause;
+int vl_index_filter_create_where(vl_index *h, const vl_where_clause *clauses, uint64_t n_clauses, uint64_t *out_filter,
+                                 uint64_t *out_rows);
+/* How a single vl_index_search_filtered under a predicate token runs.  0 (auto, the default; a clone keeps its source's
+ * mode): the masked int8 / bf16 / f32 ladder when len x (bytes per row of the ladder's first stage) is strictly below
+ * rows kept x the f32 row's bytes, else the position list -- near 25 % kept when the int8 copy goes first, near 50 % under
+ * bf16, never when f32 goes first.  1: always the list.  2: the ladder wherever its conditions hold (no forced path, no row
+ * outside the f32 domain, a stride the masked scan is compiled for, min(k, rows kept) <= 60), as exclusion tokens do.  The
+ * answers are the same bits in every mode.  Flat single-GPU handles; others and a mode outside 0..2: VL_ERR_INVALID_ARG. */
+int vl_index_set_where_route(vl_index *h, int mode);
+/* out4[0] = the route of the last single predicate-filtered search on this handle (0 list, 1 masked ladder), [1] = the rows
+ * its token kept, [2] = predicate resolutions, [3] = column resolutions on this handle so far. */
+int vl_index_last_where(const vl_index *h, uint64_t *out4);
+
 /* The filtered search, vl_index_search_cap's capacity rule: min(k, rows in the subset, out_capacity) entries, the prefix
  * of the k results. */
 int vl_index_search_filtered(const vl_index *h, uint64_t filter, const double *query, uint64_t q_len, uint64_t k,

@@ -51,6 +51,10 @@ extern "C" {
     fn vl_index_filter_create(h: *mut vl_index, ids: *const u64, n_ids: u64, out_filter: *mut u64, out_rows: *mut u64) -> c_int;
     fn vl_index_filter_create_excluding(h: *mut vl_index, ids: *const u64, n_ids: u64, out_filter: *mut u64, out_rows: *mut u64) -> c_int;
     fn vl_index_filter_destroy(h: *mut vl_index, filter: u64) -> c_int;
+    fn vl_index_attr_rows(h: *const vl_index, attr: u64, out_rows: *mut u64) -> c_int;
+    fn vl_index_attr_destroy(h: *mut vl_index, attr: u64) -> c_int;
+    fn vl_index_set_where_route(h: *mut vl_index, mode: c_int) -> c_int;
+    fn vl_index_last_where(h: *const vl_index, out4: *mut u64) -> c_int;
     fn vl_index_search_filtered(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, k: u64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_batch_filters(h: *const vl_index, filters: *const u64, n_filters: u64, queries: *const f64, nq: u64, q_len: u64, k: u64, metric: c_int, out_stride: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_last_filtered_batch(h: *const vl_index, batched: *mut u64, single: *mut u64, exact: *mut u64, launches: *mut u64) -> c_int;
@@ -97,6 +101,25 @@ extern "C" {
     fn vl_shard_search_batch_dev(shard: *const vl_index, comm: *mut vl_comm, d_queries: *const f64, nq: u64, q_len: u64, k: u64, metric: c_int, out_gpos: *mut u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_batch_dev(h: *const vl_index, d_queries: *const f64, nq: u64, q_len: u64, k: u64, metric: c_int, out_pos: *mut u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_batch_embeddings_f32(h: *const vl_index, embeddings: *const f32, nq: u64, dim: u64, normalize: c_int, embeddings_on_device: c_int, k: u64, metric: c_int, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
+}
+
+/// `vl_where_clause` of the header: one range clause of a predicate filter.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct vl_where_clause {
+    pub attr: u64,
+    pub lo: i64,
+    pub hi: i64,
+    pub negate: u32,
+    pub reserved: u32,
+}
+
+// The attribute-column entry points that take int64 values or the clause struct: kinds the signature test's table does
+// not hold, so these three were checked against the header by reading.
+extern "C" {
+    fn vl_index_attr_create(h: *mut vl_index, ids: *const u64, values: *const i64, n: u64, out_attr: *mut u64, out_rows: *mut u64) -> c_int;
+    fn vl_index_attr_set(h: *mut vl_index, attr: u64, ids: *const u64, values: *const i64, n: u64) -> c_int;
+    fn vl_index_filter_create_where(h: *mut vl_index, clauses: *const vl_where_clause, n_clauses: u64, out_filter: *mut u64, out_rows: *mut u64) -> c_int;
 }
 
 pub const VL_COMM_ID_BYTES: usize = 128;
@@ -441,6 +464,96 @@ impl GpuFlatIndex {
             VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
             _ => Err(VectorLiteError::InternalError(err)),
         }
+    }
+
+    /// An attribute column id -> i64 (no reference counterpart; the reference's `Vector::metadata` is not searchable): the
+    /// token `search_where` clauses refer to.  `ids` and `values` pair up in any order; an id with two different values is
+    /// an error.  Rows whose id the column does not hold have no value.  Single-GPU handles only.
+    pub fn attr_create(&self, ids: &[u64], values: &[i64]) -> VectorLiteResult<u64> {
+        if ids.len() != values.len() {
+            return Err(VectorLiteError::InternalError("attr_create: one value per id".to_string()));
+        }
+        let (mut token, mut rows) = (0u64, 0u64);
+        match unsafe { vl_index_attr_create(self.0.raw, ids.as_ptr(), values.as_ptr(), ids.len() as u64, &mut token, &mut rows) } {
+            VL_OK => Ok(token),
+            _ => Err(VectorLiteError::InternalError(last_error())),
+        }
+    }
+
+    /// Upserts pairs into a column: an id already held takes the new value.  Tokens made from the column are resolved again
+    /// on their next use.  A refused call leaves the column as it was.
+    pub fn attr_set(&self, attr: u64, ids: &[u64], values: &[i64]) -> VectorLiteResult<()> {
+        if ids.len() != values.len() {
+            return Err(VectorLiteError::InternalError("attr_set: one value per id".to_string()));
+        }
+        match unsafe { vl_index_attr_set(self.0.raw, attr, ids.as_ptr(), values.as_ptr(), ids.len() as u64) } {
+            VL_OK => Ok(()),
+            _ => Err(VectorLiteError::InternalError(last_error())),
+        }
+    }
+
+    /// Rows that have a value in the column now.
+    pub fn attr_rows(&self, attr: u64) -> VectorLiteResult<u64> {
+        let mut rows = 0u64;
+        match unsafe { vl_index_attr_rows(self.0.raw, attr, &mut rows) } {
+            VL_OK => Ok(rows),
+            _ => Err(VectorLiteError::InternalError(last_error())),
+        }
+    }
+
+    /// Frees a column token; filters made from it keep working.
+    pub fn attr_destroy(&self, attr: u64) {
+        unsafe { vl_index_attr_destroy(self.0.raw, attr) };
+    }
+
+    /// `search` among the rows that pass 1 to 4 ANDed range clauses over attribute columns (no reference counterpart):
+    /// a row qualifies iff for every clause it has a value v and `(lo <= v && v <= hi) != negate`.  The bitmap of the
+    /// qualifying rows is computed on the device.  Single-GPU handles only.
+    pub fn search_where(&self, clauses: &[vl_where_clause], query: &[f64], k: usize, metric: SimilarityMetric) -> VectorLiteResult<Vec<SearchResult>> {
+        let (mut token, mut rows) = (0u64, 0u64);
+        let rc = unsafe { vl_index_filter_create_where(self.0.raw, clauses.as_ptr(), clauses.len() as u64, &mut token, &mut rows) };
+        if rc != VL_OK {
+            return Err(VectorLiteError::InternalError(last_error()));
+        }
+        let cap = k.min(rows as usize).max(1);
+        let (mut out_ids, mut scores, mut n) = (vec![0u64; cap], vec![0f64; cap], 0u64);
+        let rc = unsafe {
+            vl_index_search_filtered(self.0.raw, token, query.as_ptr(), query.len() as u64, k as u64, metric_code(metric), cap as u64, out_ids.as_mut_ptr(), scores.as_mut_ptr(), &mut n)
+        };
+        let err = if rc == VL_OK { String::new() } else { last_error() };
+        unsafe { vl_index_filter_destroy(self.0.raw, token) };
+        match rc {
+            VL_OK => Ok((0..n as usize)
+                .map(|i| {
+                    let (text, metadata) = self.0.side.get(&out_ids[i]).cloned().unwrap_or_default();
+                    SearchResult { id: out_ids[i], score: scores[i], text, metadata }
+                })
+                .collect()),
+            VL_ERR_DIM_MISMATCH => {
+                let (mut e, mut a) = (0u64, 0u64);
+                unsafe { vl_last_dim_mismatch(&mut e, &mut a) };
+                Err(VectorLiteError::DimensionMismatch { expected: e as usize, actual: a as usize })
+            }
+            VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
+            _ => Err(VectorLiteError::InternalError(err)),
+        }
+    }
+
+    /// How a single search under a predicate token runs: 0 = auto (the masked ladder when its byte estimate is below the
+    /// position list's), 1 = the list, 2 = the ladder wherever its conditions hold.  Answers are the same in every mode.
+    pub fn set_where_route(&self, mode: i32) -> VectorLiteResult<()> {
+        match unsafe { vl_index_set_where_route(self.0.raw, mode as c_int) } {
+            VL_OK => Ok(()),
+            _ => Err(VectorLiteError::InternalError(last_error())),
+        }
+    }
+
+    /// The route of the last single predicate-filtered search (0 list, 1 masked ladder), the rows its token kept, and the
+    /// predicate and column resolutions on this handle so far.
+    pub fn last_where(&self) -> (u64, u64, u64, u64) {
+        let mut out = [0u64; 4];
+        unsafe { vl_index_last_where(self.0.raw, out.as_mut_ptr()) };
+        (out[0], out[1], out[2], out[3])
     }
 
     /// A batch of filtered searches, one id set per query (no reference counterpart): entry `i` is exactly

@@ -29,7 +29,7 @@ from . import _lib
 
 __all__ = [
     "SimilarityMetric", "Vector", "SearchResult", "FlatIndex", "MultiFlatIndex", "HNSWIndex", "VectorLiteError", "DimensionMismatch",
-    "MetricMismatch", "NaNScore", "DeviceError", "IndexOpError", "IdFilter", "WalkFilter", "GroupTable", "hnsw_score", "hnsw_level", "runtime_info",
+    "MetricMismatch", "NaNScore", "DeviceError", "IndexOpError", "IdFilter", "WalkFilter", "GroupTable", "AttrColumn", "hnsw_score", "hnsw_level", "runtime_info",
     "PATH_FAST", "PATH_EXACT_SELECT", "PATH_EXACT_SORT",
 ]
 
@@ -44,6 +44,7 @@ SINGLE_FILTER_MODES = {"f32": 0, "bf16": 1, "auto": 2}
 SINGLE_FILTER_I8 = 3
 # set_masked_batch: the modes of vl_index_set_masked_batch (2 = auto, what new handles start in)
 MASKED_BATCH_MODES = {"off": 0, "on": 1, "auto": 2}
+WHERE_ROUTES = {"auto": 0, "list": 1, "mask": 2}
 
 
 class SimilarityMetric(enum.IntEnum):
@@ -217,14 +218,20 @@ class IdFilter:
     (or leaving a `with` block) frees it.  An exclusion filter (`make_filter(ids, exclude=True)`,
     vl_index_filter_create_excluding; `exclude` is True) is the opposite set: the rows whose id is NOT in `ids` qualify."""
 
-    def __init__(self, index: "FlatIndex", token: int, exclude: bool = False):
+    def __init__(self, index: "FlatIndex", token: int, exclude: bool = False, columns=None):
         self._index = index
         self._token = token
         self._exclude = bool(exclude)
+        self._columns = tuple(columns) if columns is not None else None  # a predicate token keeps its columns referenced
 
     @property
     def token(self) -> int:
         return self._token
+
+    @property
+    def kind(self) -> str:
+        """"include", "exclude", or "where" (a predicate token, FlatIndex.make_filter_where)."""
+        return "where" if self._columns is not None else "exclude" if self._exclude else "include"
 
     @property
     def exclude(self) -> bool:
@@ -385,6 +392,112 @@ class GroupTable:
 def _u64_array(values) -> np.ndarray:
     return np.ascontiguousarray(np.fromiter((int(i) for i in values), dtype=np.uint64)
                                 if not isinstance(values, np.ndarray) else values.astype(np.uint64, copy=False))
+
+
+def _i64_array(values) -> np.ndarray:
+    return np.ascontiguousarray(np.fromiter((int(i) for i in values), dtype=np.int64)
+                                if not isinstance(values, np.ndarray) else values.astype(np.int64, copy=False))
+
+
+def _pi64(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+class AttrColumn:
+    """A map id -> int64 value of one FlatIndex (vl_index_attr_create): `make_filter_where` builds filter tokens from
+    range clauses over such columns, resolved on the device.  A row whose id the column does not hold has no value and
+    passes no clause; an id the index does not hold waits for a row with that id.  `rows()` = rows that have a value now;
+    `set(ids, values)` upserts pairs (tokens made from the column are resolved again on their next use); `close()` (or
+    leaving a `with` block) frees the token -- filters made from the column keep working."""
+
+    def __init__(self, index: "FlatIndex", token: int):
+        self._index = index
+        self._token = token
+
+    @property
+    def token(self) -> int:
+        return self._token
+
+    def _live(self) -> int:
+        if not self._token:
+            raise IndexOpError("attribute column is closed")
+        return self._token
+
+    def rows(self) -> int:
+        out = C.c_uint64(0)
+        rc = self._index._L.vl_index_attr_rows(self._index._h, self._live(), C.byref(out))
+        if rc == VL_ERR_INVALID_ARG:
+            raise IndexOpError(_last_error())
+        _raise(rc)
+        return int(out.value)
+
+    def set(self, ids, values) -> None:
+        ids, values = _u64_array(ids), _i64_array(values)
+        if ids.size != values.size:
+            raise ValueError("ids and values must have the same length")
+        rc = self._index._L.vl_index_attr_set(self._index._h, self._live(), _pu64(ids), _pi64(values), ids.size)
+        if rc == VL_ERR_INVALID_ARG:
+            raise IndexOpError(_last_error())
+        _raise(rc)
+
+    def close(self) -> None:
+        tok, self._token = self._token, 0
+        h = getattr(self._index, "_h", None)
+        if tok and h:
+            self._index._L.vl_index_attr_destroy(h, tok)
+
+    def __enter__(self) -> "AttrColumn":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _make_attribute(L, h, owner, ids, values) -> AttrColumn:
+    ids, values = _u64_array(ids), _i64_array(values)
+    if ids.size != values.size:
+        raise ValueError("ids and values must have the same length")
+    tok, rows = C.c_uint64(0), C.c_uint64(0)
+    rc = L.vl_index_attr_create(h, _pu64(ids), _pi64(values), ids.size, C.byref(tok), C.byref(rows))
+    if rc == VL_ERR_INVALID_ARG:
+        raise IndexOpError(_last_error())
+    _raise(rc)
+    return AttrColumn(owner, int(tok.value))
+
+
+_I64_MIN, _I64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+def _make_filter_where(L, h, owner, clauses, reserved: int = 0) -> IdFilter:
+    clauses = list(clauses)
+    arr = (_lib.WhereClause * max(len(clauses), 1))()
+    columns = []
+    for i, cl in enumerate(clauses):
+        if len(cl) not in (3, 4):
+            raise ValueError("a clause is (column, lo, hi) or (column, lo, hi, negate)")
+        col, lo, hi = cl[0], cl[1], cl[2]
+        if isinstance(col, AttrColumn):
+            if col._index is not owner:
+                raise ValueError("the column belongs to another index")
+            columns.append(col)
+            col = col._live()
+        arr[i].attr = int(col)
+        arr[i].lo = _I64_MIN if lo is None else int(lo)
+        arr[i].hi = _I64_MAX if hi is None else int(hi)
+        arr[i].negate = int(cl[3]) if len(cl) == 4 else 0
+        arr[i].reserved = reserved
+    tok, rows = C.c_uint64(0), C.c_uint64(0)
+    rc = L.vl_index_filter_create_where(h, arr, len(clauses), C.byref(tok), C.byref(rows))
+    if rc == VL_ERR_INVALID_ARG:
+        raise IndexOpError(_last_error())
+    _raise(rc)
+    return IdFilter(owner, int(tok.value), False, columns)
 
 
 def _make_groups(L, h, owner, ids, keys) -> GroupTable:
@@ -731,6 +844,34 @@ class FlatIndex:
         rows whose id is NOT in `ids` qualify (an empty `ids` keeps every row; a row added later under one of the ids is
         excluded from then on)."""
         return _make_filter(self._L, self._h, self, ids, exclude)
+
+    # ---- attribute columns and predicate filters -----------------------------------------------
+    def make_attribute(self, ids, values) -> AttrColumn:
+        """An AttrColumn mapping ids[i] -> values[i] (int64; any order; a pair repeated exactly is fine, an id with two
+        different values is an IndexOpError naming the smallest such id)."""
+        return _make_attribute(self._L, self._h, self, ids, values)
+
+    def make_filter_where(self, clauses) -> IdFilter:
+        """An IdFilter (kind "where") keeping the rows that pass every one of 1 to 4 clauses.  A clause is (column, lo,
+        hi) or (column, lo, hi, negate): the row has a value v in the AttrColumn and (lo <= v <= hi) != negate; None as a
+        bound is the int64 extreme.  A row without a value passes no clause, negated or not.  The bitmap is computed on the
+        device from the columns; the token is passed as `filter=` or inside `filters=[...]` like any other."""
+        return _make_filter_where(self._L, self._h, self, clauses)
+
+    def set_where_route(self, mode: str) -> None:
+        """How a single search under a predicate token runs: "auto" (new handles: the masked int8 / bf16 / f32 ladder when
+        its byte estimate is below the position list's), "list" or "mask".  Answers are identical in every mode."""
+        rc = self._L.vl_index_set_where_route(self._h, WHERE_ROUTES[mode])
+        if rc == VL_ERR_INVALID_ARG:
+            raise IndexOpError("the predicate route is a setting of single-GPU flat indexes")
+        _raise(rc)
+
+    def last_where(self) -> Dict[str, int]:
+        """The route of the last single predicate-filtered search on this handle (0 list, 1 masked ladder), the rows its
+        token kept, and the predicate and column resolutions on this handle so far."""
+        v = (C.c_uint64 * 4)()
+        _raise(self._L.vl_index_last_where(self._h, v))
+        return dict(zip(("route", "m", "resolutions", "column_resolutions"), (int(x) for x in v)))
 
     def _filter_token(self, filter):
         """(token, one-shot filter to close afterwards or None)"""
@@ -1692,6 +1833,14 @@ class HNSWIndex:
     def make_groups(self, ids, keys) -> GroupTable:
         """Grouped search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""
         return _make_groups(self._L, self._h, self, ids, keys)
+
+    def make_attribute(self, ids, values) -> AttrColumn:
+        """Attribute columns are served by single-GPU flat indexes: raises IndexOpError with the library's message."""
+        return _make_attribute(self._L, self._h, self, ids, values)
+
+    def make_filter_where(self, clauses) -> IdFilter:
+        """Predicate filters are served by single-GPU flat indexes: raises IndexOpError with the library's message."""
+        return _make_filter_where(self._L, self._h, self, clauses)
 
     def search_grouped_arrays(self, query, k: int, metric: int = 0, groups=None, filter=None):
         """Grouped search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""

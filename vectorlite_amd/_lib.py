@@ -22,6 +22,8 @@ SYMBOLS = [
     "vl_index_groups_create", "vl_index_groups_rows", "vl_index_groups_destroy", "vl_index_search_grouped",
     "vl_index_search_grouped_batch", "vl_index_set_grouped_batch", "vl_index_last_grouped_batch",
     "vl_index_search_mmr_batch", "vl_index_set_mmr_batch", "vl_index_last_mmr_batch",
+    "vl_index_attr_create", "vl_index_attr_set", "vl_index_attr_rows", "vl_index_attr_destroy", "vl_index_filter_create_where",
+    "vl_index_set_where_route", "vl_index_last_where",
     "vl_index_len", "vl_index_is_empty", "vl_index_dimension", "vl_index_get_vector", "vl_index_max_id",
     "vl_index_export", "vl_index_search_positions", "vl_index_search_batch_positions", "vl_index_search_batch_dev", "vl_index_search_batch_embeddings_f32", "vl_index_hnsw_distances", "vl_hnsw_score",
     "vl_last_error", "vl_last_dim_mismatch", "vl_last_path", "vl_index_force_path", "vl_index_set_single_filter",
@@ -36,6 +38,10 @@ SYMBOLS = [
 ]
 
 _lib = None
+
+
+class WhereClause(C.Structure):  # vl_where_clause
+    _fields_ = [("attr", C.c_uint64), ("lo", C.c_int64), ("hi", C.c_int64), ("negate", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 def load() -> C.CDLL:
@@ -115,6 +121,14 @@ def load() -> C.CDLL:
     sig("vl_index_search_mmr_batch", i32, [vp, u64, vp, u64, u64, u64, u64, f64, i32, u64, vp, vp, vp])
     sig("vl_index_set_mmr_batch", i32, [vp, i32])
     sig("vl_index_last_mmr_batch", i32, [vp, p_u64, p_u64, p_u64, p_u64])
+    p_i64 = C.POINTER(C.c_int64)
+    sig("vl_index_attr_create", i32, [vp, p_u64, p_i64, u64, p_u64, p_u64])
+    sig("vl_index_attr_set", i32, [vp, u64, p_u64, p_i64, u64])
+    sig("vl_index_attr_rows", i32, [vp, u64, p_u64])
+    sig("vl_index_attr_destroy", i32, [vp, u64])
+    sig("vl_index_filter_create_where", i32, [vp, C.POINTER(WhereClause), u64, p_u64, p_u64])
+    sig("vl_index_set_where_route", i32, [vp, i32])
+    sig("vl_index_last_where", i32, [vp, p_u64])
     sig("vl_index_len", u64, [vp])
     sig("vl_index_is_empty", i32, [vp])
     sig("vl_index_dimension", u64, [vp])

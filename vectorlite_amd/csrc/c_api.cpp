@@ -434,6 +434,90 @@ int vl_index_filter_destroy(vl_index* h, uint64_t filter)
     });
 }
 
+int vl_index_attr_create(vl_index* h, const uint64_t* ids, const int64_t* values, uint64_t n, uint64_t* out_attr, uint64_t* out_rows)
+{
+    return guarded([&]() -> int {
+        if (out_attr) *out_attr = 0;
+        if (!out_attr || ((!ids || !values) && n)) return VL_ERR_INVALID_ARG;
+        // the pairs are checked on the host before the handle is looked at: no device is needed
+        vl::AttrPlan plan;
+        uint64_t bad = 0;
+        const int prc = vl::attr_plan_build(ids, values, n, &plan, &bad);
+        if (prc != vl::ATTR_PLAN_OK) {
+            vl::set_last_error(prc == vl::ATTR_PLAN_TOO_MANY
+                                   ? "an attribute column holds fewer than 2^32 - 1 pairs"
+                                   : "attribute column: id " + std::to_string(bad) + " is given two different values");
+            return VL_ERR_INVALID_ARG;
+        }
+        VL_FILTER_HANDLE(h);
+        return h->flat->attr_create(std::move(plan), out_attr, out_rows);
+    });
+}
+
+int vl_index_attr_set(vl_index* h, uint64_t attr, const uint64_t* ids, const int64_t* values, uint64_t n)
+{
+    return guarded([&]() -> int {
+        VL_FILTER_HANDLE(h);
+        return h->flat->attr_set(attr, ids, values, n);
+    });
+}
+
+int vl_index_attr_rows(const vl_index* h, uint64_t attr, uint64_t* out_rows)
+{
+    return guarded([&]() -> int {
+        VL_FILTER_HANDLE(h);
+        if (!out_rows) return VL_ERR_INVALID_ARG;
+        return h->flat->attr_rows(attr, out_rows);
+    });
+}
+
+int vl_index_attr_destroy(vl_index* h, uint64_t attr)
+{
+    return guarded([&]() -> int {
+        VL_FILTER_HANDLE(h);
+        return h->flat->attr_destroy(attr);
+    });
+}
+
+int vl_index_filter_create_where(vl_index* h, const vl_where_clause* clauses, uint64_t n_clauses, uint64_t* out_filter,
+                                 uint64_t* out_rows)
+{
+    return guarded([&]() -> int {
+        if (out_filter) *out_filter = 0;
+        VL_FILTER_HANDLE(h);
+        if (!out_filter) return VL_ERR_INVALID_ARG;
+        if (n_clauses < 1 || n_clauses > 4) {
+            vl::set_last_error("a predicate filter takes 1 to 4 clauses");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (!clauses) return VL_ERR_INVALID_ARG;
+        vl::GpuFlatIndex::WhereSpec spec[4];
+        for (uint64_t i = 0; i < n_clauses; ++i) {
+            if (clauses[i].reserved != 0 || clauses[i].negate > 1) {
+                vl::set_last_error("predicate filter: clause " + std::to_string(i) +
+                                   (clauses[i].reserved != 0 ? " has a nonzero reserved field" : " has negate outside 0..1"));
+                return VL_ERR_INVALID_ARG;
+            }
+            spec[i] = {clauses[i].attr, clauses[i].lo, clauses[i].hi, clauses[i].negate != 0};
+        }
+        return h->flat->filter_create_where(spec, n_clauses, out_filter, out_rows);
+    });
+}
+
+int vl_index_set_where_route(vl_index* h, int mode)
+{
+    if (!h || !h->flat || mode < 0 || mode > 2) return VL_ERR_INVALID_ARG;
+    h->flat->set_where_route(mode);
+    return VL_OK;
+}
+
+int vl_index_last_where(const vl_index* h, uint64_t* out4)
+{
+    if (!h || !h->flat || !out4) return VL_ERR_INVALID_ARG;
+    h->flat->last_where(out4);
+    return VL_OK;
+}
+
 int vl_index_search_filtered(const vl_index* h, uint64_t filter, const double* query, uint64_t q_len, uint64_t k, int metric,
                              uint64_t out_capacity, uint64_t* out_ids, double* out_scores, uint64_t* out_n)
 {

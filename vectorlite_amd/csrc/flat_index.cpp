@@ -13,6 +13,7 @@
 #include "score_bound.hpp"
 #include "subset_batch_plan.hpp"
 #include "masked_batch_plan.hpp"
+#include "where_plan.hpp"
 #include "grouped_batch_plan.hpp"
 #include "mmr_batch_plan.hpp"
 
@@ -222,6 +223,7 @@ int token_take(std::mutex& mu, Map& table, uint64_t token, const char* unknown, 
 }
 constexpr const char* UNKNOWN_FILTER = "unknown or destroyed filter";
 constexpr const char* UNKNOWN_GROUPS = "unknown or destroyed group table";
+constexpr const char* UNKNOWN_ATTR = "unknown or destroyed attribute column";
 }  // namespace
 
 Workspace::~Workspace()
@@ -1147,7 +1149,7 @@ int GpuFlatIndex::lock_for_query(int metric, uint64_t q_len, std::shared_lock<Rw
 int GpuFlatIndex::resolve_if_stale(Workspace* ws, IdFilter* f, bool need_list) const
 {
     std::lock_guard<std::mutex> g(f->mu);
-    if (f->resolved_at != mutations_) VL_TRY(resolve_filter(ws, f));
+    if (filter_stale(f)) VL_TRY(resolve_filter(ws, f));
     return need_list ? ensure_plist(ws, f) : OK;
 }
 
@@ -1834,7 +1836,7 @@ int GpuFlatIndex::filter_create(const uint64_t* ids, uint64_t n_ids, uint64_t* o
     }
     auto f = std::make_shared<IdFilter>();
     f->device = device_;
-    f->exclude = exclude;
+    f->kind = exclude ? FilterKind::Exclude : FilterKind::Include;
     f->ids.assign(ids, ids + n_ids);
     std::sort(f->ids.begin(), f->ids.end());
     f->ids.erase(std::unique(f->ids.begin(), f->ids.end()), f->ids.end());
@@ -1877,7 +1879,7 @@ int GpuFlatIndex::filter_rows(uint64_t token, uint64_t* out_rows) const
     VL_TRY(find_filter(token, &f));
     std::shared_lock<RwLock> lk(mu_);
     std::lock_guard<std::mutex> fg(f->mu);
-    if (f->resolved_at != mutations_) {
+    if (filter_stale(f.get())) {
         WsLease lease(this);
         if (lease.status() != OK) return lease.status();
         VL_TRY(lease.done(resolve_filter(lease.ws, f.get())));
@@ -1893,7 +1895,7 @@ int GpuFlatIndex::filter_positions(uint64_t token, std::shared_ptr<IdFilter>* ke
     VL_TRY(find_filter(token, &f));
     std::shared_lock<RwLock> lk(mu_);
     std::lock_guard<std::mutex> fg(f->mu);
-    if (f->resolved_at != mutations_) {
+    if (filter_stale(f.get())) {
         WsLease lease(this);
         if (lease.status() != OK) return lease.status();
         VL_TRY(lease.done(resolve_filter(lease.ws, f.get())));
@@ -1913,17 +1915,23 @@ int GpuFlatIndex::filter_positions(uint64_t token, std::shared_ptr<IdFilter>* ke
 // sizes the list and the scan's grid), one launch; nothing per row crosses PCIe.
 // An exclusion filter: the same count with the predicate inverted, then the keep bitmap (k_filter_bits); the list waits for
 // ensure_plist.  Its empty id set resolves like any other: nf = 0 never reads the set.
+// A predicate filter: resolve_where (its columns, then one pass for bitmap and counts); the list waits likewise.
 int GpuFlatIndex::resolve_filter(Workspace* ws, IdFilter* f) const
 {
     const uint64_t n = ids_.size();
     f->m = 0;
     f->h_plist_valid = false;
-    f->plist_built = !f->exclude;
+    f->plist_built = !f->lazy_list();
     f->resolved_at = ~0ull;
-    if (n != 0 && (!f->ids.empty() || f->exclude)) {
+    if (f->kind == FilterKind::Where) {
+        VL_TRY(resolve_where(ws, f));
+        f->resolved_at = mutations_;
+        return OK;
+    }
+    if (n != 0 && (!f->ids.empty() || f->kind == FilterKind::Exclude)) {
         hipStream_t st = ws->stream;
         VL_TRY(ensure_device_ids());
-        VL_HIP(launch_filter_count(st, d_ids_, n, f->d_ids, f->ids.size(), f->d_counts, f->d_counts + FILTER_COUNTS_MAX, f->exclude));
+        VL_HIP(launch_filter_count(st, d_ids_, n, f->d_ids, f->ids.size(), f->d_counts, f->d_counts + FILTER_COUNTS_MAX, f->kind == FilterKind::Exclude));
         uint32_t m = 0;
         VL_HIP(hipMemcpyAsync(&m, f->d_counts + FILTER_COUNTS_MAX, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         VL_HIP(hipStreamSynchronize(st));
@@ -1931,7 +1939,7 @@ int GpuFlatIndex::resolve_filter(Workspace* ws, IdFilter* f) const
             set_last_error("filter resolution counted more rows than the index holds (kernel bug)");
             return ERR_DEVICE;
         }
-        if (f->exclude) {
+        if (f->kind == FilterKind::Exclude) {
             const uint64_t words = (n + 63) / 64;
             VL_TRY(grow(HipMem{}, f->keep_cap, words, {dev_buf(f->d_keep, words)}));
             VL_HIP(launch_filter_bits(st, d_ids_, n, f->d_ids, f->ids.size(), f->d_keep));
@@ -1957,11 +1965,253 @@ int GpuFlatIndex::ensure_plist(Workspace* ws, IdFilter* f) const
     const uint64_t n = ids_.size(), m = f->m;
     VL_TRY(grow(HipMem{}, f->plist_cap, m, {dev_buf(f->d_plist, m)}));
     if (n != 0 && m != 0) {
-        VL_HIP(launch_filter_compact(ws->stream, d_ids_, n, f->d_ids, f->ids.size(), f->d_counts, m, f->d_plist, true));
+        if (f->kind == FilterKind::Where)  // from the keep bitmap, in the predicate path's word-aligned chunks
+            VL_HIP(launch_where_compact(ws->stream, n, f->d_keep, f->d_counts, m, f->d_plist));
+        else
+            VL_HIP(launch_filter_compact(ws->stream, d_ids_, n, f->d_ids, f->ids.size(), f->d_counts, m, f->d_plist, true));
         VL_HIP(hipStreamSynchronize(ws->stream));
     }
     f->plist_built = true;
     return OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Attribute columns and predicate filter tokens.  A column is resolved like a group table
+// (k_attr_rows: value_of_row[] and the has-bitmap); a predicate token's resolution reads its columns once (k_where_bits) and
+// leaves what an exclusion token's leaves: m, the keep bitmap, chunk offsets, the list on demand (k_where_compact).
+// ---------------------------------------------------------------------------------------------
+AttrColumn::~AttrColumn()
+{
+    (void)hipSetDevice(device);
+    void* dev[] = {d_ids, d_values, d_value_of_row, d_has, d_rows};
+    for (void* p : dev)
+        if (p) (void)hipFree(p);
+}
+
+int GpuFlatIndex::find_attr(uint64_t token, std::shared_ptr<AttrColumn>* out) const
+{
+    return token_find(filters_mu_, attrs_, token, UNKNOWN_ATTR, out);
+}
+
+int GpuFlatIndex::upload_attr(AttrColumn* c) const
+{
+    const size_t np = c->plan.ids.size();
+    VL_HIP(hipSetDevice(device_));
+    VL_TRY(grow(HipMem{}, c->pairs_cap, np, {dev_buf(c->d_ids, np), dev_buf(c->d_values, np)}));
+    if (np) {
+        VL_HIP(hipMemcpy(c->d_ids, c->plan.ids.data(), np * sizeof(uint64_t), hipMemcpyHostToDevice));
+        VL_HIP(hipMemcpy(c->d_values, c->plan.values.data(), np * sizeof(int64_t), hipMemcpyHostToDevice));
+    }
+    return OK;
+}
+
+int GpuFlatIndex::attr_create(AttrPlan&& plan, uint64_t* out_token, uint64_t* out_rows)
+{
+    if (!out_token || plan.ids.size() != plan.values.size()) return ERR_INVALID_ARG;
+    *out_token = 0;
+    auto c = std::make_shared<AttrColumn>();
+    c->device = device_;
+    c->plan = std::move(plan);
+    VL_TRY(upload_attr(c.get()));
+    VL_TRY(dev_alloc(&c->d_rows, 1));
+    uint64_t rows = 0;
+    {
+        std::shared_lock<RwLock> lk(mu_);
+        std::lock_guard<std::mutex> cg(c->mu);
+        WsLease lease(this);
+        if (lease.status() != OK) return lease.status();
+        VL_TRY(lease.done(resolve_attr(lease.ws, c.get())));
+        rows = c->rows;
+    }
+    const uint64_t token = g_next_filter_token.fetch_add(1);
+    {
+        std::lock_guard<std::mutex> g(filters_mu_);
+        attrs_[token] = std::move(c);
+    }
+    *out_token = token;
+    if (out_rows) *out_rows = rows;
+    return OK;
+}
+
+// The exclusive index lock: no search holds a resolution of this column, or of a token made from it, while the plan and the
+// version move.  The next use of the column or of such a token resolves it again.
+int GpuFlatIndex::attr_set(uint64_t attr, const uint64_t* ids, const int64_t* values, uint64_t n)
+{
+    if ((!ids || !values) && n) return ERR_INVALID_ARG;
+    std::shared_ptr<AttrColumn> c;
+    VL_TRY(find_attr(attr, &c));
+    std::unique_lock<RwLock> lk(mu_);
+    std::lock_guard<std::mutex> cg(c->mu);
+    AttrPlan merged;
+    uint64_t bad = 0;
+    const int prc = attr_plan_merge(c->plan, ids, values, n, &merged, &bad);
+    if (prc != ATTR_PLAN_OK) {
+        set_last_error(prc == ATTR_PLAN_TOO_MANY ? "an attribute column holds fewer than 2^32 - 1 pairs"
+                                                 : "attribute column: id " + std::to_string(bad) + " is given two different values");
+        return ERR_INVALID_ARG;
+    }
+    std::swap(c->plan, merged);
+    const int rc = upload_attr(c.get());
+    if (rc != OK) {  // (the device copy may be gone: the old plan goes back up before the error is reported)
+        std::swap(c->plan, merged);
+        c->resolved_at = ~0ull;
+        (void)upload_attr(c.get());
+        return rc;
+    }
+    ++c->version;
+    return OK;
+}
+
+int GpuFlatIndex::attr_rows(uint64_t attr, uint64_t* out_rows) const
+{
+    if (!out_rows) return ERR_INVALID_ARG;
+    std::shared_ptr<AttrColumn> c;
+    VL_TRY(find_attr(attr, &c));
+    std::shared_lock<RwLock> lk(mu_);
+    std::lock_guard<std::mutex> cg(c->mu);
+    if (c->resolved_at != mutations_ || c->resolved_version != c->version) {
+        WsLease lease(this);
+        if (lease.status() != OK) return lease.status();
+        VL_TRY(lease.done(resolve_attr(lease.ws, c.get())));
+    }
+    *out_rows = c->rows;
+    return OK;
+}
+
+int GpuFlatIndex::attr_destroy(uint64_t attr)
+{
+    std::shared_ptr<AttrColumn> c;  // tokens made from it hold their own references: freed when the last of them goes
+    return token_take(filters_mu_, attrs_, attr, UNKNOWN_ATTR, &c);
+}
+
+int GpuFlatIndex::resolve_attr(Workspace* ws, AttrColumn* c) const
+{
+    const uint64_t n = ids_.size();
+    c->rows = 0;
+    c->resolved_at = ~0ull;
+    if (n != 0) {
+        hipStream_t st = ws->stream;
+        const uint64_t words = (n + 63) / 64;
+        VL_TRY(ensure_device_ids());
+        VL_TRY(grow(HipMem{}, c->rows_cap, n, {dev_buf(c->d_value_of_row, n)}));
+        VL_TRY(grow(HipMem{}, c->has_cap, words, {dev_buf(c->d_has, words)}));
+        VL_HIP(launch_attr_rows(st, d_ids_, n, c->d_ids, c->d_values, c->plan.ids.size(), c->d_value_of_row, c->d_has, c->d_rows));
+        uint32_t rows = 0;
+        VL_HIP(hipMemcpyAsync(&rows, c->d_rows, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipStreamSynchronize(st));
+        if (rows > n) {
+            set_last_error("column resolution counted more rows than the index holds (kernel bug)");
+            return ERR_DEVICE;
+        }
+        c->rows = rows;
+    }
+    c->resolved_at = mutations_;
+    c->resolved_version = c->version;
+    last_where_[3].fetch_add(1, std::memory_order_relaxed);
+    return OK;
+}
+
+int GpuFlatIndex::filter_create_where(const WhereSpec* clauses, uint64_t n_clauses, uint64_t* out_token, uint64_t* out_rows)
+{
+    if (!out_token) return ERR_INVALID_ARG;
+    *out_token = 0;
+    if (n_clauses < 1 || n_clauses > WHERE_MAX_CLAUSES) {
+        set_last_error("a predicate filter takes 1 to 4 clauses");
+        return ERR_INVALID_ARG;
+    }
+    if (!clauses) return ERR_INVALID_ARG;
+    auto f = std::make_shared<IdFilter>();
+    f->device = device_;
+    f->kind = FilterKind::Where;
+    for (uint64_t i = 0; i < n_clauses; ++i) {
+        std::shared_ptr<AttrColumn> c;
+        VL_TRY(find_attr(clauses[i].attr, &c));
+        f->clauses.push_back({std::move(c), clauses[i].lo, clauses[i].hi, clauses[i].negate, 0});
+    }
+    VL_HIP(hipSetDevice(device_));
+    VL_TRY(dev_alloc(&f->d_counts, (size_t)FILTER_COUNTS_MAX + 1));
+    uint64_t rows = 0;
+    {
+        std::shared_lock<RwLock> lk(mu_);
+        std::lock_guard<std::mutex> fg(f->mu);
+        WsLease lease(this);
+        if (lease.status() != OK) return lease.status();
+        VL_TRY(lease.done(resolve_filter(lease.ws, f.get())));
+        rows = f->m;
+    }
+    const uint64_t token = g_next_filter_token.fetch_add(1);
+    {
+        std::lock_guard<std::mutex> g(filters_mu_);
+        filters_[token] = std::move(f);
+    }
+    *out_token = token;
+    if (out_rows) *out_rows = rows;
+    return OK;
+}
+
+bool GpuFlatIndex::filter_stale(const IdFilter* f) const
+{
+    if (f->resolved_at != mutations_) return true;
+    for (const WhereClause& cl : f->clauses)
+        if (cl.version != cl.column->version) return true;  // (versions move under the exclusive index lock only)
+    return false;
+}
+
+// The stale columns first, then the predicate: one pass that writes the keep bitmap and the per-chunk counts together, the
+// scan that turns them into offsets and m, one 4-byte read-back.
+int GpuFlatIndex::resolve_where(Workspace* ws, IdFilter* f) const
+{
+    const uint64_t n = ids_.size();
+    WhereClausesDev dev{};
+    dev.n_clauses = (uint32_t)f->clauses.size();
+    for (size_t i = 0; i < f->clauses.size(); ++i) {
+        WhereClause& cl = f->clauses[i];
+        AttrColumn* c = cl.column.get();
+        std::lock_guard<std::mutex> cg(c->mu);
+        if (c->resolved_at != mutations_ || c->resolved_version != c->version) VL_TRY(resolve_attr(ws, c));
+        cl.version = c->version;
+        dev.value_of_row[i] = c->d_value_of_row;
+        dev.has[i] = c->d_has;
+        dev.lo[i] = cl.lo;
+        dev.hi[i] = cl.hi;
+        dev.negate[i] = cl.negate ? 1u : 0u;
+    }
+    if (n != 0) {
+        hipStream_t st = ws->stream;
+        const uint64_t words = (n + 63) / 64;
+        VL_TRY(grow(HipMem{}, f->keep_cap, words, {dev_buf(f->d_keep, words)}));
+        VL_HIP(launch_where_bits(st, n, dev, f->d_keep, f->d_counts, f->d_counts + FILTER_COUNTS_MAX));
+        uint32_t m = 0;
+        VL_HIP(hipMemcpyAsync(&m, f->d_counts + FILTER_COUNTS_MAX, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipStreamSynchronize(st));
+        if (m > n) {
+            set_last_error("predicate resolution counted more rows than the index holds (kernel bug)");
+            return ERR_DEVICE;
+        }
+        f->m = m;
+    }
+    last_where_[2].fetch_add(1, std::memory_order_relaxed);
+    return OK;
+}
+
+int GpuFlatIndex::where_first_stage(uint64_t n, int metric) const
+{
+    // search_locked's ladder under a mask, asked without spending a probe of a paused stage's window
+    const int mode = single_filter_.load(std::memory_order_relaxed);
+    const uint64_t slab = n * (uint64_t)ld_ * sizeof(float);
+    const bool i8 = ladder_stage(
+        FILTER_I8, mode, scan_i8_supported((uint32_t)dim_, metric) && !(mode == FILTER_AUTO && i8_unavailable_.load(std::memory_order_relaxed)),
+        slab, i8_min_bytes_,
+        [&] { return forced_stage_on(mask_i8_tries_.load(std::memory_order_relaxed), mask_i8_fails_.load(std::memory_order_relaxed)); },
+        [&] { return mask_i8_window_.on(); });
+    if (i8) return WHERE_STAGE_I8;
+    const bool bf16 = ladder_stage(
+        FILTER_BF16, mode,
+        scan_bf16_supported((uint32_t)dim_, metric) && !(mode == FILTER_AUTO && auto_unavailable_.load(std::memory_order_relaxed)), slab,
+        auto_min_bytes_,
+        [&] { return forced_stage_on(mask_bf16_tries_.load(std::memory_order_relaxed), mask_bf16_fails_.load(std::memory_order_relaxed)); },
+        [&] { return mask_bf16_window_.on(); });
+    return bf16 ? WHERE_STAGE_BF16 : WHERE_STAGE_F32;
 }
 
 int GpuFlatIndex::search_filtered(uint64_t token, const double* query, uint64_t q_len, uint64_t k, int metric,
@@ -1977,22 +2227,32 @@ int GpuFlatIndex::search_filtered(uint64_t token, const double* query, uint64_t 
     if ((!query && dim_) || !out_scores) return ERR_INVALID_ARG;
     // An exclusion filter leaves almost every row in play: where the single-query ladder's conditions hold (and the f32
     // stride is one the masked scan is compiled for) it runs that ladder under the keep bitmap and needs no list.
-    const bool ladder = f->exclude && force_path_.load() == 0 && n_out_of_domain_ == 0 && scan_masked_supported(ld_);
+    // A predicate filter may keep any share of the rows: where_plan.hpp weighs the ladder's first stage against the list.
+    const bool ladder = f->has_keep() && force_path_.load() == 0 && n_out_of_domain_ == 0 && scan_masked_supported(ld_);
+    const bool where = f->kind == FilterKind::Where;
     return run_search(nullptr, f.get(), [&](Workspace* ws) -> int {
+        bool take_ladder = ladder;
+        if (where) {
+            const WhereShape shp{ladder, ids_.size(), ld_, mfma_ldb((uint32_t)dim_), where_first_stage(ids_.size(), metric),
+                                 (uint64_t)KFAST_MAX};
+            take_ladder = where_route_mask(where_route_.load(), shp, f->m, k);
+            last_where_[0].store(take_ladder ? 1 : 0, std::memory_order_relaxed);
+            last_where_[1].store(f->m, std::memory_order_relaxed);
+        }
         if (f->m == 0) return OK;
         const uint64_t k_eff = std::min<uint64_t>(k, f->m);
         bool uncertified = false;
-        if (ladder && k_eff <= (uint64_t)KFAST_MAX) {
+        if (take_ladder && k_eff <= (uint64_t)KFAST_MAX) {
             const int rc = search_locked(ws, query, k_eff, metric, out_pos, out_ids, out_scores, out_n, false, false, nullptr, f.get());
             if (rc != MASK_UNCERTIFIED) return rc;
             uncertified = true;  // no masked stage certified it (or the query is out of the domain): the exact kernels
         }
-        if (f->exclude) {
+        if (f->lazy_list()) {
             std::lock_guard<std::mutex> fg(f->mu);
             VL_TRY(ensure_plist(ws, f.get()));
         }
         return search_subset(ws, f.get(), query, k_eff, metric, out_pos, out_ids, out_scores, out_n, nullptr, uncertified);
-    }, /*need_list=*/!f->exclude);
+    }, /*need_list=*/!f->lazy_list());
 }
 
 int GpuFlatIndex::search_subset(Workspace* ws, IdFilter* f, const double* query, uint64_t k_eff, int metric,
@@ -2124,7 +2384,7 @@ int GpuFlatIndex::search_batch_filters(const uint64_t* tokens, uint64_t n_filter
     hipStream_t st = ws->stream;
     // each stale filter once, whatever its number of jobs; an exclusion token's position list waits until one of its
     // queries needs it (need_list below): the masked MFMA pass reads the keep bitmap
-    for (const auto& f : filters) VL_TRY(resolve_if_stale(ws, f.get(), /*need_list=*/!f->exclude));
+    for (const auto& f : filters) VL_TRY(resolve_if_stale(ws, f.get(), /*need_list=*/!f->lazy_list()));
     InFlight searching(active_searches_);
 
     auto filter_at = [&](uint64_t qi) { return filters[filter_of[n_filters == 1 ? 0 : qi]].get(); };
@@ -2158,7 +2418,7 @@ int GpuFlatIndex::search_batch_filters(const uint64_t* tokens, uint64_t n_filter
         if (mode != MASKED_BATCH_OFF && shp.index_ok)
             for (uint64_t qi = 0; qi < nq; ++qi) {
                 const IdFilter* f = filter_at(qi);
-                if (f->exclude && masked_query_eligible(shp, lim, f->m, k)) {
+                if (f->has_keep() && masked_query_eligible(shp, lim, f->m, k)) {
                     elig.push_back((uint32_t)qi);
                     sum_m += f->m;
                 }
@@ -2200,7 +2460,7 @@ int GpuFlatIndex::search_batch_filters(const uint64_t* tokens, uint64_t n_filter
     // the position lists the jobs kernel and search_subset read: every token with a query left (one that keeps no row
     // is answered empty without a list)
     for (uint64_t qi = 0; qi < nq; ++qi)
-        if (!answered[qi] && filter_at(qi)->exclude && filter_at(qi)->m > 0) {
+        if (!answered[qi] && filter_at(qi)->lazy_list() && filter_at(qi)->m > 0) {
             const int rc = need_list(filter_at(qi));
             if (rc != OK) {
                 publish_masked();
@@ -2406,7 +2666,7 @@ int GpuFlatIndex::search_mmr_batch(uint64_t token, const double* queries, uint64
     if (lease.status() != OK) return lease.status();
     Workspace* const ws = lease.ws;
     // an exclusion token's position list waits until a query is left to the single search: the pass reads a bitmap
-    if (f) VL_TRY(resolve_if_stale(ws, f.get(), /*need_list=*/!f->exclude));
+    if (f) VL_TRY(resolve_if_stale(ws, f.get(), /*need_list=*/!f->lazy_list()));
     InFlight searching(active_searches_);
     const uint64_t m = f ? f->m : n;
     if (m == 0) return OK;  // an empty S (search_mmr's early return)
@@ -2423,14 +2683,14 @@ int GpuFlatIndex::search_mmr_batch(uint64_t token, const double* queries, uint64
                      n, (uint32_t)dim_, ld_, mfma_ldb((uint32_t)dim_)};
         shp.rows_kernel = mfma_rows_kernel((uint32_t)dim_);
         shp.filtered = f != nullptr;
-        shp.include = f && !f->exclude;
+        shp.include = f && !f->has_keep();
         shp.m = m;
         shp.i8_min_bytes = i8_min_bytes_;
         shp.bf16_min_bytes = auto_min_bytes_;
         if (mmr_batch_route(mmr_batch_.load(), shp, lim, nq, fetch_k)) {
             const uint64_t n_need = std::min<uint64_t>(fetch_k, m);
             const unsigned long long* keep = nullptr;
-            if (f && f->exclude) {
+            if (f && f->has_keep()) {
                 keep = f->d_keep;  // the token's own bitmap (section 24)
             } else if (f) {        // an include token: its rows as a bitmap, in the borrowed workspace; no list is read
                 const uint64_t words = (n + 63) / 64;
@@ -2459,7 +2719,7 @@ int GpuFlatIndex::search_mmr_batch(uint64_t token, const double* queries, uint64
         }
     }
     // what the pass did not settle (or everything), in ascending order: the first failure is the lowest failing query
-    bool list_ready = !(f && f->exclude);
+    bool list_ready = !(f && f->lazy_list());
     for (uint64_t qi = 0; qi < nq; ++qi) {
         if (done[qi]) continue;
         if (!list_ready) {
@@ -2945,7 +3205,7 @@ int GpuFlatIndex::grouped_keep_bits(Workspace* ws, GroupTable* t, IdFilter* f, c
         return OK;
     }
     VL_TRY(grow(HipMem{}, ws->gb_keep_cap, words, {dev_buf(ws->gb_keep, words)}));
-    if (f->exclude) {
+    if (f->has_keep()) {
         VL_HIP(launch_group_keep_bits(st, t->d_group_of_row, n, f->d_keep, nullptr, nullptr, 0, ws->gb_keep, ws->gb_m));
     } else {
         VL_TRY(ensure_device_ids());
@@ -3047,7 +3307,7 @@ int GpuFlatIndex::search_grouped_batch(uint64_t groups, uint64_t token, const do
         }
     }
     // what the pass did not settle (or everything), in ascending order: the first failure is the lowest failing query
-    bool list_ready = !(f && f->exclude);
+    bool list_ready = !(f && f->lazy_list());
     for (uint64_t qi = 0; qi < nq; ++qi) {
         if (done[qi]) continue;
         if (!list_ready) {
@@ -3897,6 +4157,7 @@ int GpuFlatIndex::clone(GpuFlatIndex** out) const
         VL_TRY(c->add_bulk(ids_.data(), d_master_, ids_.size(), /*validate=*/false, /*values_on_device=*/true));
     c->force_path_.store(force_path_.load());
     c->masked_batch_.store(masked_batch_.load());
+    c->where_route_.store(where_route_.load());
     *out = guard.release();
     return OK;
 }

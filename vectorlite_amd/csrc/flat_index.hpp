@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "rwlock.hpp"
+#include "attr_plan.hpp"
 #include "coalescer.hpp"
 #include "group_plan.hpp"
 #include "kernels.hpp"
@@ -162,23 +163,67 @@ struct WorkspacePool {
     size_t users = 0;
 };
 
+// An attribute column of one single-GPU flat handle (vl_index_attr_create): the caller's (id, int64)
+// pairs as an AttrPlan, and -- resolved like a group table, stale when the handle's mutation count or the column's version
+// moved -- value_of_row[position] and the "has a value" bitmap.  vl_index_attr_set swaps the plan and bumps the version
+// under the index's exclusive lock, so neither moves while a search holds the shared lock.
+struct AttrColumn {
+    std::mutex mu;                         // guards everything below (taken after the index lock and after a filter's mutex)
+    int device = 0;
+    AttrPlan plan;
+    uint64_t version = 1;                  // bumped by every successful vl_index_attr_set
+    unsigned long long* d_ids = nullptr;   // [pairs_cap] the plan on the device
+    long long* d_values = nullptr;
+    uint64_t pairs_cap = 0;
+    long long* d_value_of_row = nullptr;   // [rows_cap] 0 where the row has no value
+    uint64_t rows_cap = 0;
+    unsigned long long* d_has = nullptr;   // [has_cap] words, the keep bitmap's layout
+    uint64_t has_cap = 0;
+    uint32_t* d_rows = nullptr;            // one word: the resolution's count
+    uint64_t rows = 0;                     // rows that have a value
+    uint64_t resolved_at = ~0ull;          // the handle's mutation count and the version the resolution belongs to
+    uint64_t resolved_version = 0;
+
+    ~AttrColumn();
+};
+
+// Which rows a filter token keeps.  The consumers ask two things of a kind: whether its resolution leaves a keep bitmap
+// (d_keep), and whether its position list waits for the first call that needs one (ensure_plist).
+enum class FilterKind : uint8_t {
+    Include,  // the rows whose id is in the set: the list at once, no bitmap
+    Exclude,  // the rows whose id is NOT in the set: the bitmap, the list on demand
+    Where,    // the rows whose attribute values pass 1..4 range clauses: the bitmap, the list on demand
+};
+
+struct WhereClause {
+    std::shared_ptr<AttrColumn> column;  // the token's reference: the column outlives vl_index_attr_destroy
+    int64_t lo, hi;
+    bool negate;
+    uint64_t version;  // the column version this token's resolution read
+};
+
 // An id filter of one single-GPU flat handle (vl_index_filter_create): the caller's ids, sorted and deduplicated, and -- resolved
 // against the rows as they stood when the handle's mutation count was `resolved_at` -- the ascending storage positions of
 // every row whose id is in the set.  A search that finds the count moved on resolves it again first.
 // An EXCLUSION filter (vl_index_filter_create_excluding) qualifies the rows whose id is NOT in the set.
 // Its resolution is the count m and a keep bitmap over storage positions; the position list is built by the first call
 // that needs one after a resolution (ensure_plist), the masked single-query ladder never does.
+// A PREDICATE filter (vl_index_filter_create_where, section 28) holds no ids: its clauses refer to attribute columns, its
+// resolution is an exclusion filter's (m, the bitmap, the lazy list), and it is stale when a column's version moved too.
 struct IdFilter {
     std::mutex mu;                         // guards everything below (taken after the index lock)
     int device = 0;
-    bool exclude = false;                  // the kind: set at creation, never changes
+    FilterKind kind = FilterKind::Include;  // set at creation, never changes
+    bool has_keep() const { return kind != FilterKind::Include; }
+    bool lazy_list() const { return kind != FilterKind::Include; }
+    std::vector<WhereClause> clauses;      // Where only
     std::vector<uint64_t> ids;             // sorted, unique
     unsigned long long* d_ids = nullptr;   // the same on the device
     uint32_t* d_counts = nullptr;          // [FILTER_COUNTS_MAX + 1] resolution scratch: per-chunk offsets, then m
     uint32_t* d_plist = nullptr;           // [plist_cap] positions of the qualifying rows, ascending
     uint64_t plist_cap = 0;
-    bool plist_built = true;               // d_plist[0..m) belongs to this resolution (an exclusion filter: false until asked for)
-    unsigned long long* d_keep = nullptr;  // exclusion only: [keep_cap] words, bit p & 63 of word p >> 6 set iff row p qualifies
+    bool plist_built = true;               // d_plist[0..m) belongs to this resolution (a lazy list: false until asked for)
+    unsigned long long* d_keep = nullptr;  // has_keep() only: [keep_cap] words, bit p & 63 of word p >> 6 set iff row p qualifies
     uint64_t keep_cap = 0;
     uint64_t m = 0;                        // qualifying rows
     uint64_t resolved_at = ~0ull;          // the handle's mutation count the list belongs to (none yet)
@@ -308,6 +353,30 @@ public:
     // handle (never 0, never reused); ids may be unsorted and repeat; ids the index does not hold are ignored.
     // exclude: the rows whose id is NOT in the set qualify (n_ids = 0 keeps every row; an id added later is excluded then)
     int filter_create(const uint64_t* ids, uint64_t n_ids, uint64_t* out_token, uint64_t* out_rows, bool exclude = false);
+    // NEW (no reference counterpart): attribute columns (id -> int64) and filter tokens that keep the
+    // rows whose values pass 1..4 ANDed range clauses, resolved on the device (where.hip).  Column tokens come from the
+    // filters' counter.  attr_set upserts pairs (attr_plan_merge); a refusal leaves the column as it was.
+    int attr_create(AttrPlan&& plan, uint64_t* out_token, uint64_t* out_rows);  // the caller's pairs, planned (attr_plan.hpp)
+    int attr_set(uint64_t attr, const uint64_t* ids, const int64_t* values, uint64_t n);
+    int attr_rows(uint64_t attr, uint64_t* out_rows) const;  // rows that have a value now
+    int attr_destroy(uint64_t attr);                          // tokens made from the column keep it alive and keep working
+    struct WhereSpec {
+        uint64_t attr;
+        int64_t lo, hi;
+        bool negate;
+    };
+    // a row qualifies iff for every clause it has a value v in that column and (lo <= v && v <= hi) != negate
+    int filter_create_where(const WhereSpec* clauses, uint64_t n_clauses, uint64_t* out_token, uint64_t* out_rows);
+    // How a single search under a predicate token runs (where_plan.hpp).  0 ("auto", the default): the masked ladder when
+    // its byte estimate is below the list's.  1: the position list.  2: the ladder wherever its conditions hold.
+    void set_where_route(int mode) { where_route_.store(mode); }
+    int where_route() const { return where_route_.load(); }
+    // the route of the last single predicate-filtered search (0 list, 1 masked ladder), its m, and the predicate and
+    // column resolutions on this handle so far
+    void last_where(uint64_t out[4]) const
+    {
+        for (int i = 0; i < 4; ++i) out[i] = last_where_[i].load(std::memory_order_relaxed);
+    }
     int filter_rows(uint64_t token, uint64_t* out_rows) const;  // resolves the filter again if rows changed since
     int filter_destroy(uint64_t token);
     // for the HNSW graph layered on this row store (hnsw_index.cpp): the filter's ascending position list on the device,
@@ -558,6 +627,12 @@ private:
                   std::vector<double>* scores, const uint32_t* plist = nullptr, const MmrReq* mmr = nullptr) const;
     int find_filter(uint64_t token, std::shared_ptr<IdFilter>* out) const;  // VL_ERR_INVALID_ARG with a message: no such token
     int resolve_filter(Workspace* ws, IdFilter* f) const;  // mu_ held (shared or unique), f->mu held
+    bool filter_stale(const IdFilter* f) const;            // likewise: rows moved, or (a predicate token) a column's version did
+    int resolve_where(Workspace* ws, IdFilter* f) const;   // resolve_filter's body for a predicate token
+    int resolve_attr(Workspace* ws, AttrColumn* c) const;  // mu_ held, c->mu held
+    int upload_attr(AttrColumn* c) const;                  // c->plan -> the device; c->mu held or c not yet shared
+    int find_attr(uint64_t token, std::shared_ptr<AttrColumn>* out) const;
+    int where_first_stage(uint64_t n, int metric) const;   // WHERE_STAGE_*: the masked ladder's first stage as things stand
     // exact_only: the fast path already failed to certify this (query, filter) in a batched launch: straight to the exact kernels
     int search_subset(Workspace* ws, IdFilter* f, const double* query, uint64_t k_eff, int metric, uint64_t* out_pos,
                       uint64_t* out_ids, double* out_scores, uint64_t* out_n, const MmrReq* mmr = nullptr,
@@ -677,6 +752,9 @@ private:
     mutable std::mutex filters_mu_;  // the filter table; never held while an index lock or a filter's mutex is taken
     std::unordered_map<uint64_t, std::shared_ptr<IdFilter>> filters_;
     std::unordered_map<uint64_t, std::shared_ptr<GroupTable>> groups_;  // under filters_mu_ as well; tokens share the filters' counter
+    std::unordered_map<uint64_t, std::shared_ptr<AttrColumn>> attrs_;   // likewise
+    std::atomic<int> where_route_{0};  // WHERE_ROUTE_AUTO
+    mutable std::atomic<uint64_t> last_where_[4] = {};
 
     std::atomic<int> force_path_{0};
     std::atomic<int> single_filter_{FILTER_AUTO};

@@ -2907,6 +2907,13 @@ hipError_t launch_filter_count(hipStream_t s, const unsigned long long* pos_ids,
     return hipGetLastError();
 }
 
+hipError_t launch_filter_scan(hipStream_t s, uint32_t* counts, uint32_t nb, uint32_t* m_out)
+{
+    if (nb == 0 || nb > (uint32_t)FILTER_MAX_GRID || !counts || !m_out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_filter_scan, dim3(1), dim3(FILTER_MAX_GRID), 0, s, counts, nb, m_out);
+    return hipGetLastError();
+}
+
 hipError_t launch_filter_compact(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
                                  uint64_t nf, const uint32_t* offsets, uint64_t m, uint32_t* plist, bool invert)
 {

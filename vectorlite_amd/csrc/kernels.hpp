@@ -225,6 +225,32 @@ hipError_t launch_filter_compact(hipStream_t s, const unsigned long long* pos_id
 // rows of an include token as a bitmap).
 hipError_t launch_filter_bits(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
                               uint64_t nf, unsigned long long* keep, bool include = false);
+// the exclusive scan of launch_filter_count alone: counts[0..nb) in place, nb <= FILTER_COUNTS_MAX, total -> *m_out
+hipError_t launch_filter_scan(hipStream_t s, uint32_t* counts, uint32_t nb, uint32_t* m_out);
+
+// Attribute columns and predicate filter tokens (where.hip).
+// A column's resolution against pos_ids[0..n): fids[0..nf) sorted, unique, fvals[i] the value of fids[i] (nf may be 0).
+// value_of_row[p] = the value of row p's id, 0 where the column does not hold it; has[0..(n + 63) / 64) in the keep bitmap's
+// layout, bit set iff the column holds the row's id; *rows_out = the number of such rows.
+hipError_t launch_attr_rows(hipStream_t s, const unsigned long long* pos_ids, uint64_t n, const unsigned long long* fids,
+                            const long long* fvals, uint64_t nf, long long* value_of_row, unsigned long long* has, uint32_t* rows_out);
+// 1 to 4 clauses, ANDed: row p qualifies iff for every clause it has a value v and (lo <= v && v <= hi) != negate.
+struct WhereClausesDev {
+    const long long* value_of_row[4];
+    const unsigned long long* has[4];
+    long long lo[4], hi[4];
+    uint32_t negate[4];
+    uint32_t n_clauses;
+};
+// One pass over the clauses' columns: keep[0..(n + 63) / 64) (bits at or past n are 0; value_of_row is not read there),
+// counts[0..where_grid_for(n)) = exclusive offsets of the kept rows per chunk (where_plan.hpp: chunks of whole words),
+// *m_out = kept rows.  counts holds FILTER_COUNTS_MAX words.
+hipError_t launch_where_bits(hipStream_t s, uint64_t n, const WhereClausesDev& clauses, unsigned long long* keep, uint32_t* counts,
+                             uint32_t* m_out);
+// plist[0..m) = the positions whose keep bit is set, ascending; offsets = launch_where_bits' counts.
+hipError_t launch_where_compact(hipStream_t s, uint64_t n, const unsigned long long* keep, const uint32_t* offsets, uint64_t m,
+                                uint32_t* plist);
+
 // K1 under a keep bitmap: launch_scan's partial lists without the rows whose bit is 0, on launch_scan's grid (sized from n).
 // Only at the strides VL_SCAN_VARIANTS specialises (scan_masked_supported(ld)), the stride's default shape; the query as
 // launch_scan_subset takes it (q32_host where scan_takes_qarg(ld), else q64 in device memory).
