@@ -402,6 +402,35 @@ int vl_index_last_range_batch(const vl_index *h, uint64_t *mfma_queries, uint64_
 /* ... and the largest number of candidates the MFMA pass kept for one query it answered (0: none). */
 int vl_index_last_range_batch_candidates(const vl_index *h, uint64_t *max_candidates);
 
+/* NEW capability: the similarity SELF-JOIN -- which stored rows are near-duplicates of each other?  The answer is the set of
+ * unordered pairs of distinct storage positions i < j with score(row_i, row_j) >= min_score, where score is the reference's
+ * f64 score (src/lib.rs:425-572) bit for bit: pair (i, j) is in iff vl_index_search_range(h, 0, <stored row i>, dim,
+ * min_score, metric, ...) lists position j, and it is reported with that call's score bits.  Ties with the threshold are in.
+ * All four metrics are symmetric bit for bit (products, squared and absolute differences commute; cosine multiplies the
+ * two norms), so "row i is the query" and "row j is the query" name the same number.
+ * Order: score descending (-0.0 and +0.0 compare equal, as in every ranking here), then i ascending, then j ascending.
+ * *out_total = the exact number of qualifying pairs, always; *out_n = min(total, out_capacity) and the first *out_n pairs of
+ * that order are written as (ids[i], ids[j], score); duplicate ids are distinct rows.  out_capacity = 0 with NULL outputs
+ * is a legal "count only" call.  Fewer than two rows: VL_OK, 0 pairs.  NaN min_score: VL_ERR_INVALID_ARG.  A NaN score among
+ * the pairs the call has to compare: VL_ERR_NAN_SCORE.  Unknown metric as in vl_index_search_range.  HNSW and
+ * vl_flat_create_multi handles return VL_ERR_INVALID_ARG.  One hold of the reader lock for the whole call; it never joins a
+ * coalesced pass; other searches may run concurrently, add / delete / update wait.
+ * Routes (vl_index_set_join_route: 0 = auto, the default; 1 = loop; 2 = mfma):
+ *   loop  every stored row goes through the range machinery as a query and keeps the partners behind it.  All metrics, all
+ *         row lengths, out-of-domain rows, forced paths, a -inf threshold.
+ *   mfma  cosine, a row length the bf16 batch filter has a shape for (up to 768), in-domain rows, no forced path: one
+ *         triangular bf16 matrix-core pass over the index's own rows finds the candidate pairs, which are rescored in the
+ *         reference's f64 order, cut, and ranked on the device.  Auto takes it whenever eligible; mode 2 on an ineligible call
+ *         takes the loop and says so in vl_index_last_join.  The pass runs over ranges of column panels (128 rows; 96 for
+ *         row lengths above 512) sized to its candidate buffer (2^20 pairs; VL_JOIN_CAND_CAP lowers it): a range that
+ *         overflows is halved and run again, a single panel that still overflows is answered by the loop for its rows. */
+int vl_index_similarity_join(const vl_index *h, double min_score, int metric, uint64_t *out_ids_a, uint64_t *out_ids_b,
+                             double *out_scores, uint64_t out_capacity, uint64_t *out_n, uint64_t *out_total);
+int vl_index_set_join_route(vl_index *h, int mode); /* 0 auto, 1 loop, 2 mfma */
+/* The last successful vl_index_similarity_join on this handle, six words: the route taken (1 loop, 2 mfma), column panels
+ * the pass answered, panels handed back to the loop, candidate pairs the pass kept, qualifying pairs, launches of the pass. */
+int vl_index_last_join(const vl_index *h, uint64_t *out6);
+
 /* NEW capability (the reference only answers "the best k"): k results that are relevant but not k copies of the same
  * paragraph -- maximal marginal relevance (MMR) over the exact candidates of a search.
  * Candidates: C = FlatIndex::search(query, fetch_k, metric) (src/index/flat.rs:98-119) on the whole index (filter = 0) or on

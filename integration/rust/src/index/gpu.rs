@@ -64,6 +64,9 @@ extern "C" {
     fn vl_index_search_range_batch(h: *const vl_index, filter: u64, queries: *const f64, nq: u64, q_len: u64, min_scores: *const f64, metric: c_int, out_stride: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64, out_total: *mut u64) -> c_int;
     fn vl_index_last_range_batch(h: *const vl_index, mfma_queries: *mut u64, single_queries: *mut u64, exact_queries: *mut u64) -> c_int;
     fn vl_index_last_range_batch_candidates(h: *const vl_index, max_candidates: *mut u64) -> c_int;
+    fn vl_index_similarity_join(h: *const vl_index, min_score: f64, metric: c_int, out_ids_a: *mut u64, out_ids_b: *mut u64, out_scores: *mut f64, out_capacity: u64, out_n: *mut u64, out_total: *mut u64) -> c_int;
+    fn vl_index_set_join_route(h: *mut vl_index, mode: c_int) -> c_int;
+    fn vl_index_last_join(h: *const vl_index, out6: *mut u64) -> c_int;
     fn vl_index_groups_create(h: *mut vl_index, ids: *const u64, group_keys: *const u64, n: u64, out_groups: *mut u64, out_rows: *mut u64) -> c_int;
     fn vl_index_groups_rows(h: *const vl_index, groups: u64, out_rows: *mut u64, out_distinct: *mut u64) -> c_int;
     fn vl_index_groups_destroy(h: *mut vl_index, groups: u64) -> c_int;
@@ -692,6 +695,46 @@ impl GpuFlatIndex {
             vl_index_last_range_batch_candidates(self.0.raw, &mut d);
         }
         (a, b, c, d)
+    }
+
+    /// The similarity self-join (no reference counterpart): every pair of stored rows `i < j` (storage positions) whose
+    /// reference score is at least `min_score`, as `(id_a, id_b, score)` ordered by score descending, then `i`, then `j`; at
+    /// most `limit` pairs (None: all) and the exact number of qualifying pairs.  Single-GPU flat handles only.
+    pub fn similarity_join(&self, min_score: f64, metric: SimilarityMetric, limit: Option<usize>) -> VectorLiteResult<(Vec<(u64, u64, f64)>, usize)> {
+        let mut cap = limit.unwrap_or(4096);
+        loop {
+            let (mut a, mut b, mut s, mut n, mut total) = (vec![0u64; cap.max(1)], vec![0u64; cap.max(1)], vec![0f64; cap.max(1)], 0u64, 0u64);
+            let rc = unsafe {
+                vl_index_similarity_join(self.0.raw, min_score, metric_code(metric), a.as_mut_ptr(), b.as_mut_ptr(), s.as_mut_ptr(), cap as u64, &mut n, &mut total)
+            };
+            match rc {
+                VL_OK => {
+                    if limit.is_none() && total as usize > cap {
+                        cap = total as usize;
+                        continue;
+                    }
+                    return Ok(((0..n as usize).map(|i| (a[i], b[i], s[i])).collect(), total as usize));
+                }
+                VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
+                _ => return Err(VectorLiteError::InternalError(last_error())),
+            }
+        }
+    }
+
+    /// 0 = auto, 1 = loop, 2 = mfma (`vl_index_set_join_route`).
+    pub fn set_join_route(&self, mode: i32) -> VectorLiteResult<()> {
+        match unsafe { vl_index_set_join_route(self.0.raw, mode as c_int) } {
+            VL_OK => Ok(()),
+            _ => Err(VectorLiteError::InternalError(last_error())),
+        }
+    }
+
+    /// The last `similarity_join`: route (1 loop, 2 mfma), panels answered, panels handed back, candidate pairs, qualifying
+    /// pairs, launches.
+    pub fn last_join(&self) -> [u64; 6] {
+        let mut out = [0u64; 6];
+        unsafe { vl_index_last_join(self.0.raw, out.as_mut_ptr()) };
+        out
     }
 
     /// Every row whose score is at least `min_score` (no reference counterpart): the longest prefix of

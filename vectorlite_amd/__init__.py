@@ -575,6 +575,48 @@ def _search_range(L, h, query, min_score: float, metric: int, token: int, limit)
         return ids[:m].copy(), scores[:m].copy(), int(total.value)
 
 
+JOIN_ROUTES = {"auto": 0, "loop": 1, "mfma": 2}
+
+
+def _similarity_join(L, h, min_score: float, metric: int, limit):
+    """vl_index_similarity_join -> (ids_a, ids_b, scores, total).  limit=None: every pair (the first call's buffers hold
+    4096 pairs; a larger total is fetched by a second call sized from the first one's count)."""
+    cap = 4096 if limit is None else max(int(limit), 0)
+    while True:
+        ids_a = np.empty(max(cap, 1), dtype=np.uint64)
+        ids_b = np.empty(max(cap, 1), dtype=np.uint64)
+        scores = np.empty(max(cap, 1), dtype=np.float64)
+        n, total = C.c_uint64(0), C.c_uint64(0)
+        rc = L.vl_index_similarity_join(h, float(min_score), int(metric), ids_a.ctypes.data if cap else None,
+                                        ids_b.ctypes.data if cap else None, scores.ctypes.data if cap else None, cap,
+                                        C.byref(n), C.byref(total))
+        if rc == VL_ERR_INVALID_ARG:
+            raise IndexOpError(_last_error())
+        _raise(rc)
+        if limit is None and total.value > cap:
+            cap = int(total.value)
+            continue
+        m = int(n.value)
+        return ids_a[:m].copy(), ids_b[:m].copy(), scores[:m].copy(), int(total.value)
+
+
+def _set_join_route(L, h, mode: str) -> None:
+    if mode not in JOIN_ROUTES:
+        raise ValueError("mode must be 'auto', 'loop' or 'mfma'")
+    if L.vl_index_set_join_route(h, JOIN_ROUTES[mode]) != 0:
+        raise IndexOpError(_last_error())
+
+
+def _last_join(L, h) -> Dict[str, int]:
+    out = np.zeros(6, dtype=np.uint64)
+    if L.vl_index_last_join(h, out.ctypes.data) != 0:
+        raise IndexOpError(_last_error())
+    keys = ("route", "panels_answered", "panels_handed_back", "candidate_pairs", "qualifying_pairs", "launches")
+    d = {k: int(v) for k, v in zip(keys, out)}
+    d["route"] = {1: "loop", 2: "mfma"}.get(d["route"], d["route"])
+    return d
+
+
 def _search_range_batch(L, h, queries, min_score, metric: int, token: int, limit):
     """vl_index_search_range_batch -> (ids_list, scores_list, totals).  limit=None: everything.  The first call's rows hold
     64 entries; the queries whose total is larger -- only those -- are asked again as a second batch with rows sized from
@@ -956,6 +998,24 @@ class FlatIndex:
         _raise(self._L.vl_index_last_range_batch_candidates(self._h, C.byref(d)))
         return {"mfma_queries": int(a.value), "single_queries": int(b.value), "exact_queries": int(c.value),
                 "max_candidates": int(d.value)}
+
+    # ---- similarity self-join (near-duplicate pairs) ------------------------------------------
+    def similarity_join_arrays(self, min_score: float, metric: int = 0, limit=None):
+        """Every pair of stored rows i < j (storage positions) whose reference score is >= min_score, as (ids_a, ids_b,
+        scores, total): ordered by (score desc, i asc, j asc), `total` exact, the first `limit` pairs (None: all)."""
+        return _similarity_join(self._L, self._h, min_score, metric, limit)
+
+    def similarity_join(self, min_score: float, similarity_metric: int = SimilarityMetric.Cosine, limit=None):
+        a, b, s, _ = self.similarity_join_arrays(min_score, similarity_metric, limit)
+        return list(zip(a.tolist(), b.tolist(), s.tolist()))
+
+    def set_join_route(self, mode: str) -> None:
+        """'auto' (the MFMA pass whenever the call is eligible), 'loop', 'mfma' (vl_index_set_join_route)."""
+        _set_join_route(self._L, self._h, mode)
+
+    def last_join(self) -> Dict[str, int]:
+        """The last similarity_join on this handle (vl_index_last_join)."""
+        return _last_join(self._L, self._h)
 
     # ---- grouped search (best row per group) --------------------------------------------------
     def make_groups(self, ids, keys) -> GroupTable:
@@ -1813,6 +1873,19 @@ class HNSWIndex:
 
     def search_range_batch(self, queries, min_score, similarity_metric: int = SimilarityMetric.Cosine, filter=None, limit=None):
         return self.search_range_batch_arrays(queries, min_score, similarity_metric, filter, limit)
+
+    def similarity_join_arrays(self, min_score: float, metric: int = 0, limit=None):
+        """The similarity join is served by single-GPU flat indexes: raises IndexOpError with the library's message."""
+        return _similarity_join(self._L, self._h, min_score, metric, limit)
+
+    def similarity_join(self, min_score: float, similarity_metric: int = SimilarityMetric.Cosine, limit=None):
+        return self.similarity_join_arrays(min_score, similarity_metric, limit)
+
+    def set_join_route(self, mode: str) -> None:
+        _set_join_route(self._L, self._h, mode)
+
+    def last_join(self) -> Dict[str, int]:
+        return _last_join(self._L, self._h)
 
     def search_mmr_arrays(self, query, k: int, fetch_k: int = 20, lambda_mult: float = 0.5, metric: int = 0, filter=None):
         """Diversified search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""

@@ -18,7 +18,7 @@ SYMBOLS = [
     "vl_flat_create", "vl_flat_from_rows", "vl_flat_create_multi", "vl_index_parts", "vl_hnsw_create", "vl_hnsw_create_ex", "vl_index_type", "vl_index_metric", "vl_index_search_ef", "vl_index_clone", "vl_index_destroy", "vl_index_reserve",
     "vl_index_add", "vl_index_add_bulk", "vl_index_add_embeddings_f32", "vl_index_delete", "vl_index_delete_bulk", "vl_index_set_delete_bounce", "vl_index_last_delete", "vl_index_update", "vl_index_update_bulk", "vl_index_last_update", "vl_index_search", "vl_index_search_batch", "vl_index_search_cap", "vl_index_search_batch_cap",
     "vl_index_filter_create", "vl_index_filter_create_excluding", "vl_index_filter_rows", "vl_index_filter_destroy", "vl_index_search_filtered", "vl_index_search_batch_filtered", "vl_index_search_batch_filters", "vl_index_last_filtered_batch", "vl_index_set_masked_batch", "vl_index_last_masked_batch","vl_index_search_range", "vl_index_search_range_batch", "vl_index_last_range_batch",
-    "vl_index_last_range_batch_candidates", "vl_index_search_mmr",
+    "vl_index_last_range_batch_candidates", "vl_index_similarity_join", "vl_index_set_join_route", "vl_index_last_join", "vl_index_search_mmr",
     "vl_index_groups_create", "vl_index_groups_rows", "vl_index_groups_destroy", "vl_index_search_grouped",
     "vl_index_search_grouped_batch", "vl_index_set_grouped_batch", "vl_index_last_grouped_batch",
     "vl_index_search_mmr_batch", "vl_index_set_mmr_batch", "vl_index_last_mmr_batch",
@@ -110,6 +110,9 @@ def load() -> C.CDLL:
     sig("vl_index_search_range_batch", i32, [vp, u64, vp, u64, u64, vp, i32, u64, vp, vp, vp, vp])
     sig("vl_index_last_range_batch", i32, [vp, p_u64, p_u64, p_u64])
     sig("vl_index_last_range_batch_candidates", i32, [vp, p_u64])
+    sig("vl_index_similarity_join", i32, [vp, C.c_double, i32, vp, vp, vp, u64, p_u64, p_u64])
+    sig("vl_index_set_join_route", i32, [vp, i32])
+    sig("vl_index_last_join", i32, [vp, vp])
     sig("vl_index_search_mmr", i32, [vp, u64, vp, u64, u64, u64, C.c_double, i32, u64, vp, vp, p_u64])
     sig("vl_index_groups_create", i32, [vp, p_u64, p_u64, u64, p_u64, p_u64])
     sig("vl_index_groups_rows", i32, [vp, u64, p_u64, p_u64])

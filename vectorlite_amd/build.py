@@ -21,8 +21,11 @@ ARCH = "gfx950"
 # -ffp-contract=off: the exact kernels must round every multiply and every add separately, in the
 # reference's order (src/lib.rs:425-572); the f32 scan spells its FMAs out with fmaf().
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function", f"-I{INCLUDE}"]
-SOURCES = ["kernels.hip", "grouped.hip", "where.hip", "mmr.hip", "hnsw.hip", "mfma_scan.hip", "shard.hip", "flat_index.cpp", "multi_index.cpp", "hnsw_index.cpp", "shard_comm.cpp",
+SOURCES = ["kernels.hip", "grouped.hip", "where.hip", "mmr.hip", "hnsw.hip", "mfma_scan.hip", "join.hip", "shard.hip", "flat_index.cpp", "multi_index.cpp", "hnsw_index.cpp", "shard_comm.cpp",
            "vlc_loader.cpp", "c_api.cpp"]
+# join.hip's f32 epilogue is compiled without packed-f32 instructions (v_pk_*_f32); the older translation units keep the
+# flags they were measured with
+EXTRA = {"join.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 # RCCL (the row-shard all-gather, shard_comm.cpp): the ROCm copy; in a process that has imported torch the loader
 # resolves the same SONAME (librccl.so.1) to the copy torch already mapped, so there is one RCCL per process
 ROCM_LIB = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
@@ -61,7 +64,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         o = os.path.join(OBJ, os.path.splitext(src)[0] + ".o")
         objs.append(o)
         if force or _stale(o, [s] + headers):
-            cmd = [cc, f"--offload-arch={ARCH}"] + COMMON + os.environ.get("VL_EXTRA_CFLAGS", "").split() + ["-c", s, "-o", o]
+            cmd = [cc, f"--offload-arch={ARCH}"] + COMMON + os.environ.get("VL_EXTRA_CFLAGS", "").split() + EXTRA.get(src, []) + ["-c", s, "-o", o]
             if src.endswith(".cpp"):
                 cmd.insert(1, "-x")
                 cmd.insert(2, "hip")

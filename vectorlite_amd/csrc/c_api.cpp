@@ -579,6 +579,44 @@ int vl_index_last_range_batch_candidates(const vl_index* h, uint64_t* max_candid
     return VL_OK;
 }
 
+int vl_index_similarity_join(const vl_index* h, double min_score, int metric, uint64_t* out_ids_a, uint64_t* out_ids_b,
+                             double* out_scores, uint64_t out_capacity, uint64_t* out_n, uint64_t* out_total)
+{
+    return guarded([&]() -> int {
+        if (!h || !out_n || !out_total) return VL_ERR_INVALID_ARG;
+        *out_n = 0;
+        *out_total = 0;
+        if (!h->flat) {
+            vl::set_last_error("the similarity join is served by single-GPU flat indexes");
+            return VL_ERR_INVALID_ARG;
+        }
+        if ((!out_ids_a || !out_ids_b || !out_scores) && out_capacity != 0) return VL_ERR_INVALID_ARG;
+        return h->flat->similarity_join(min_score, metric, out_capacity, out_ids_a, out_ids_b, out_scores, out_n, out_total);
+    });
+}
+
+int vl_index_set_join_route(vl_index* h, int mode)
+{
+    if (!h || mode < 0 || mode > 2) return VL_ERR_INVALID_ARG;
+    if (!h->flat) {
+        vl::set_last_error("the similarity join is served by single-GPU flat indexes");
+        return VL_ERR_INVALID_ARG;
+    }
+    h->flat->set_join_route(mode);
+    return VL_OK;
+}
+
+int vl_index_last_join(const vl_index* h, uint64_t* out6)
+{
+    if (!h || !out6) return VL_ERR_INVALID_ARG;
+    if (!h->flat) {
+        vl::set_last_error("the similarity join is served by single-GPU flat indexes");
+        return VL_ERR_INVALID_ARG;
+    }
+    h->flat->last_join(out6);
+    return VL_OK;
+}
+
 static_assert(VL_MMR_MAX_FETCH == vl::MMR_MAX_FETCH, "the header states the kernels' limit");
 
 int vl_index_search_mmr(const vl_index* h, uint64_t filter, const double* query, uint64_t q_len, uint64_t k, uint64_t fetch_k,

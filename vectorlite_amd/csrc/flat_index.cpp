@@ -233,12 +233,12 @@ Workspace::~Workspace()
     void* dev[] = {d_q64, d_partials, d_partials64, d_result, d_nan, d_scores, d_okeys,
                    d_opos, d_out_pos, d_out_scores, d_positions, d_dists, rg_ctr, rg_cand, rg_scores, rg_keys, rg_pv, mmr_sim,
                    rb_ctr, rb_min, rb_sv_score, rb_sv_pos, gp_best, gp_first, gp_lists, gp_cand, gp_scores, gp_ctr, gp_out_keys,
-                   gb_keep, gb_m, mb_ranked};
+                   gb_keep, gb_m, mb_ranked, jn_cand, jn_cnt, jn_ctr, jn_keys, jn_pay};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     void* host[] = {h_q64, h_result, h_nan, mf_h_q64, mf_h_result, mf_h_dom, k3_h_q64, k3_h_result, rg_h_ctr, rg_h_pos, rg_h_scores,
                     rb_h_thr, rb_h_min, rb_h_ctr, rb_h_cnt, rb_h_pos, rb_h_scores, gp_h_ctr, gp_h_scores, gp_h_keys,
-                    gb_h_result};
+                    gb_h_result, jn_h};
     for (void* p : host)
         if (p) (void)hipHostFree(p);
     void* mfd[] = {mf.q_bf16, mf.gmax, mf.thr, mf.cand, mf.cnt, mf_d_q64, mf_lists, mf_scores, k3_d_q64};
@@ -4020,6 +4020,217 @@ int GpuFlatIndex::search_range_batch_mfma(Workspace* ws, const double* queries, 
             (*done)[qi] = 1;
         }
     }
+    return OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Similarity self-join: every pair of stored rows i < j with score >= min_score.
+// Two routes under one hold of the shared lock.  The loop is the definition: each row goes through search_range_locked as
+// a query and keeps its partners behind it.  The MFMA route runs join.hip's triangular pass over panel ranges sized to the
+// candidate buffer, rescores and cuts on the device, ranks the survivors there; a range whose counter overflowed is halved,
+// and a single panel that still overflows is answered by the loop for its rows.
+// ---------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t JOIN_CAND_CAP = 1u << 20;  // candidate pairs per launch (12 MB)
+constexpr size_t JOIN_SV_CAP = 1u << 18;      // survivors the first call's buffers hold (6 MB); grown to the total on demand
+constexpr uint64_t JOIN_LOOP_ROWS = 64;       // rows the loop route fetches from the master per copy
+uint32_t join_candidate_capacity()
+{
+    // VL_JOIN_CAND_CAP: a smaller candidate buffer (tests drive the split and the hand-back with it)
+    if (const char* e = getenv("VL_JOIN_CAND_CAP")) {
+        const long long v = atoll(e);
+        if (v >= 1 && v <= (long long)JOIN_CAND_CAP) return (uint32_t)v;
+    }
+    return JOIN_CAND_CAP;
+}
+// kernels.hip's desc_key on the host: ascending unsigned order = descending score, -0.0 == +0.0
+uint64_t join_desc_key(double s)
+{
+    s = s + 0.0;
+    uint64_t b;
+    memcpy(&b, &s, sizeof b);
+    const uint64_t asc = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+    return ~asc;
+}
+}  // namespace
+
+int GpuFlatIndex::join_loop_rows(Workspace* ws, uint64_t row0, uint64_t row1, double min_score, int metric, bool lower,
+                                 std::vector<JoinPair>* pairs, uint64_t* count) const
+{
+    std::vector<double> rows(std::max<size_t>((size_t)(JOIN_LOOP_ROWS * dim_), 1));
+    std::vector<uint64_t> pos(1024);
+    std::vector<double> sc(1024);
+    for (uint64_t r0 = row0; r0 < row1; r0 += JOIN_LOOP_ROWS) {
+        const uint64_t g = std::min<uint64_t>(JOIN_LOOP_ROWS, row1 - r0);
+        if (dim_) VL_HIP(hipMemcpy(rows.data(), d_master_ + r0 * dim_, (size_t)(g * dim_) * sizeof(double), hipMemcpyDeviceToHost));
+        for (uint64_t i = r0; i < r0 + g; ++i) {
+            uint64_t got = 0, total = 0;
+            for (int pass = 0; pass < 2; ++pass) {
+                InFlight searching(active_searches_);
+                VL_TRY(search_range_locked(ws, nullptr, rows.data() + (i - r0) * dim_, min_score, metric, pos.size(), pos.data(), nullptr,
+                                           sc.data(), &got, &total));
+                if (total <= pos.size()) break;
+                pos.resize(total);  // the index cannot change under the lock: the second call lists them all
+                sc.resize(total);
+            }
+            for (uint64_t e = 0; e < got; ++e) {
+                const uint64_t j = pos[e];
+                if (lower ? j >= i : j <= i) continue;
+                *count += 1;
+                if (pairs) pairs->push_back(JoinPair{join_desc_key(sc[e]), (std::min(i, j) << 32) | std::max(i, j), sc[e]});
+            }
+        }
+    }
+    return OK;
+}
+
+int GpuFlatIndex::join_mfma(Workspace* ws, double min_score, float thr, uint64_t out_capacity, std::vector<JoinPair>* pairs,
+                            uint64_t* total, uint64_t* stats) const
+{
+    const uint64_t n = ids_.size();
+    VL_TRY(ensure_bf16_slab(true));
+    const uint32_t cap = join_candidate_capacity();
+    VL_TRY(ensure_set(HipMem{}, {dev_buf(ws->jn_cand, JOIN_CAND_CAP), dev_buf(ws->jn_cnt, 1), dev_buf(ws->jn_ctr, JOIN_CTR_WORDS),
+                                 pinned_buf(ws->jn_h, 1 + JOIN_CTR_WORDS)}));
+    VL_TRY(grow(HipMem{}, ws->jn_sv_cap, JOIN_SV_CAP, {dev_buf(ws->jn_keys, JOIN_SV_CAP), dev_buf(ws->jn_pay, JOIN_SV_CAP)}));
+    hipStream_t st = ws->stream;
+    const JoinPlan plan = join_plan((uint32_t)n, join_qpb(mfma_ldb((uint32_t)dim_)));
+    const bool store = out_capacity != 0;
+    std::vector<uint32_t> handed;
+    uint64_t total_dev = 0;
+    for (int attempt = 0;; ++attempt) {
+        handed.clear();
+        stats[1] = stats[3] = 0;
+        VL_HIP(launch_join_clear(st, ws->jn_ctr));
+        std::vector<std::pair<uint32_t, uint32_t>> todo{{0u, plan.n_panels}};
+        while (!todo.empty()) {
+            const auto [y0, y1] = todo.back();
+            todo.pop_back();
+            VL_HIP(launch_join_rows(st, d_slab16f_, n, (uint32_t)dim_, y0, y1, thr, ws->jn_cand, ws->jn_cnt, cap));
+            VL_HIP(launch_join_rescore_cut(st, ws->jn_cand, ws->jn_cnt, cap, d_master_, (uint32_t)dim_, n, min_score, ws->jn_keys,
+                                           ws->jn_pay, store ? ws->jn_sv_cap : 0, ws->jn_ctr));
+            VL_HIP(hipMemcpyAsync(ws->jn_h, ws->jn_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            VL_HIP(hipStreamSynchronize(st));
+            stats[5] += 1;
+            const uint32_t cnt = *reinterpret_cast<const uint32_t*>(ws->jn_h);
+            if (cnt <= cap) {
+                stats[1] += y1 - y0;
+                stats[3] += cnt;
+            } else if (y1 - y0 > 1) {  // the range is halved and run again, the lower half first
+                const uint32_t mid = y0 + (y1 - y0) / 2;
+                todo.push_back({mid, y1});
+                todo.push_back({y0, mid});
+            } else {
+                handed.push_back(y0);
+            }
+        }
+        VL_HIP(hipMemcpyAsync(ws->jn_h + 1, ws->jn_ctr, JOIN_CTR_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipStreamSynchronize(st));
+        if (ws->jn_h[1 + JOIN_CTR_NAN]) {
+            set_last_error("NaN similarity score: the reference panics in partial_cmp().unwrap()");
+            return ERR_NAN_SCORE;
+        }
+        total_dev = ws->jn_h[1 + JOIN_CTR_TOTAL];
+        if (total_dev > stats[3]) {
+            set_last_error("similarity join counted more pairs than it rescored (kernel bug)");
+            return ERR_DEVICE;
+        }
+        if (!store || total_dev <= ws->jn_sv_cap) break;
+        if (attempt) {
+            set_last_error("similarity join survivors outgrew their buffer twice (kernel bug)");
+            return ERR_DEVICE;
+        }
+        // more survivors than the buffers hold: they are regrown to the count and the pass runs again
+        const size_t need = sort_capacity_for(total_dev);
+        VL_TRY(grow(HipMem{}, ws->jn_sv_cap, need, {dev_buf(ws->jn_keys, need), dev_buf(ws->jn_pay, need)}));
+    }
+    *total += total_dev;
+    stats[2] = handed.size();
+    if (store && total_dev) {
+        const uint64_t want = std::min<uint64_t>(total_dev, out_capacity);
+        VL_HIP(launch_join_rank(st, ws->jn_keys, ws->jn_pay, total_dev));
+        std::vector<JoinPay> got(want);
+        VL_HIP(hipMemcpyAsync(got.data(), ws->jn_pay, want * sizeof(JoinPay), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipStreamSynchronize(st));
+        pairs->reserve(want);
+        for (const JoinPay& g : got) {
+            double s;
+            memcpy(&s, &g.bits, sizeof s);
+            pairs->push_back(JoinPair{join_desc_key(s), g.ab, s});
+        }
+    }
+    // panels the pass could not hold: the loop answers their rows, each keeping its partners in FRONT of it (the pairs whose
+    // column lies in the panel; scores are symmetric bit for bit)
+    for (uint32_t y : handed)
+        VL_TRY(join_loop_rows(ws, (uint64_t)y * plan.qpb, std::min<uint64_t>(n, (uint64_t)(y + 1) * plan.qpb), min_score, COSINE, true,
+                              store ? pairs : nullptr, total));
+    return OK;
+}
+
+int GpuFlatIndex::similarity_join(double min_score, int metric, uint64_t out_capacity, uint64_t* out_ids_a, uint64_t* out_ids_b,
+                                  double* out_scores, uint64_t* out_n, uint64_t* out_total) const
+{
+    if (!out_n || !out_total) return ERR_INVALID_ARG;
+    *out_n = 0;
+    *out_total = 0;
+    std::shared_lock<RwLock> lk;  // one index state for the whole call
+    VL_TRY(lock_for_query(metric, dim_, &lk));
+    if (min_score != min_score) {
+        set_last_error("min_score is NaN");
+        return ERR_INVALID_ARG;
+    }
+    uint64_t stats[6] = {1, 0, 0, 0, 0, 0};
+    auto publish = [&]() {
+        for (int i = 0; i < 6; ++i) last_join_[i].store(stats[i], std::memory_order_relaxed);
+    };
+    const uint64_t n = ids_.size();
+    if (n < 2) {
+        publish();
+        return OK;
+    }
+    if (out_capacity != 0 && (!out_ids_a || !out_ids_b || !out_scores)) return ERR_INVALID_ARG;
+    WsLease lease(this, /*sync_always=*/true);
+    if (lease.status() != OK) return lease.status();
+    Workspace* const ws = lease.ws;
+
+    const char* mf_env = getenv("VL_MFMA");
+    float thr = INFINITY;
+    bool mfma = join_route_.load() != 1 && metric == COSINE && force_path_.load() == 0 && n_out_of_domain_ == 0 &&
+                !(mf_env && mf_env[0] == '0') && join_rows_supported((uint32_t)dim_) && n < 0x7FFFFFFFull;
+    // "no key is provably out" (a -inf threshold): every pair is a candidate, which is not a filter's job
+    if (mfma && join_key_threshold(mfma_ldb((uint32_t)dim_), min_score, &thr) == RANGE_KEYS_ALL) mfma = false;
+    std::vector<JoinPair> pairs;
+    uint64_t total = 0;
+    try {
+        if (mfma) {
+            stats[0] = 2;
+            VL_TRY(join_mfma(ws, min_score, thr, out_capacity, &pairs, &total, stats));
+        } else {
+            VL_TRY(join_loop_rows(ws, 0, n, min_score, metric, false, out_capacity ? &pairs : nullptr, &total));
+        }
+        // (score desc, i asc, j asc): the device's survivors arrive ranked, the loop's pairs row by row
+        std::sort(pairs.begin(), pairs.end(),
+                  [](const JoinPair& x, const JoinPair& y) { return x.key < y.key || (x.key == y.key && x.ab < y.ab); });
+    } catch (const std::bad_alloc&) {
+        set_last_error("out of host memory collecting the join's pairs");
+        return ERR_OOM;
+    }
+    const uint64_t want = std::min<uint64_t>(std::min<uint64_t>(total, out_capacity), pairs.size());
+    for (uint64_t i = 0; i < want; ++i) {
+        const uint64_t a = pairs[i].ab >> 32, b = pairs[i].ab & 0xFFFFFFFFull;
+        if (a >= n || b >= n || a >= b) {
+            set_last_error("similarity join returned an out-of-range pair (kernel bug)");
+            return ERR_DEVICE;
+        }
+        out_ids_a[i] = ids_[a];
+        out_ids_b[i] = ids_[b];
+        out_scores[i] = pairs[i].score;
+    }
+    *out_n = want;
+    *out_total = total;
+    stats[4] = total;
+    set_last_path(PATH_FAST);
+    publish();
     return OK;
 }
 

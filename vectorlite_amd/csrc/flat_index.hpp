@@ -22,6 +22,7 @@
 #include "attr_plan.hpp"
 #include "coalescer.hpp"
 #include "group_plan.hpp"
+#include "join.hpp"
 #include "kernels.hpp"
 #include "mfma_scan.hpp"
 #include "single_filter.hpp"
@@ -103,6 +104,15 @@ struct Workspace {
     uint32_t* rb_h_cnt = nullptr;    // pinned [MFMA_MAX_BATCH]
     uint32_t* rb_h_pos = nullptr;    // pinned [RBATCH_SPEC]: packed answers copied back before the host knows their number
     double* rb_h_scores = nullptr;   // pinned [RBATCH_SPEC]
+    // similarity self-join (lazy): one range's candidate pairs and their counter, the call's survivors (sort keys and
+    // payloads, jn_sv_cap entries), its counters
+    JoinCand* jn_cand = nullptr;             // [JOIN_CAND_CAP]
+    uint32_t* jn_cnt = nullptr;              // [1]
+    unsigned long long* jn_ctr = nullptr;    // [JOIN_CTR_WORDS]
+    unsigned long long* jn_h = nullptr;      // pinned [1 + JOIN_CTR_WORDS]: the range's counter, then the call's
+    unsigned long long* jn_keys = nullptr;
+    JoinPay* jn_pay = nullptr;
+    size_t jn_sv_cap = 0;
     // grouped search (lazy): pass 1's per-group slots and the collapse's first-appearance table ([gp_cap] each), the top
     // groups' positions and reference scores, its counters, the emitted group keys
     uint64_t* gp_best = nullptr;
@@ -434,6 +444,21 @@ public:
         if (exact) *exact = last_rbatch_[2].load(std::memory_order_relaxed);
         if (max_candidates) *max_candidates = last_rbatch_[3].load(std::memory_order_relaxed);
     }
+    // NEW (no reference counterpart): the similarity self-join: every pair of storage positions i < j
+    // with calculate(metric, row_i, row_j) >= min_score, ordered by (score desc with -0.0 == +0.0, i asc, j asc).  Pair (i, j)
+    // is in iff search_range(0, row_i, dim, min_score, metric, ...) lists position j, with that call's score bits.
+    // *out_total = qualifying pairs, always; the first min(total, out_capacity) are written.
+    int similarity_join(double min_score, int metric, uint64_t out_capacity, uint64_t* out_ids_a, uint64_t* out_ids_b,
+                        double* out_scores, uint64_t* out_n, uint64_t* out_total) const;
+    // 0 auto (the MFMA pass whenever the call is eligible), 1 always the loop over the range machinery, 2 the pass (an
+    // ineligible call still takes the loop and says so in last_join)
+    void set_join_route(int mode) { join_route_.store(mode); }
+    // the last similarity_join: route taken (1 loop, 2 mfma), panels the pass answered, panels handed to the loop, candidate
+    // pairs, qualifying pairs, launches of the pass
+    void last_join(uint64_t* out6) const
+    {
+        for (int i = 0; i < 6; ++i) out6[i] = last_join_[i].load(std::memory_order_relaxed);
+    }
     // NEW (no reference counterpart): maximal marginal relevance over C = FlatIndex::search(q, fetch_k, metric) on the whole
     // index (token 0) or the filter's rows: sel[0] = C[0], then greedily the candidate maximising
     // lambda * score - (1 - lambda) * (largest reference similarity to anything chosen), ties to the better-ranked one.
@@ -650,6 +675,17 @@ private:
     int search_range_batch_mfma(Workspace* ws, const double* queries, uint64_t nq, const double* min_scores, int metric,
                                 uint64_t out_stride, uint64_t* out_ids, double* out_scores, uint64_t* out_n, uint64_t* out_total,
                                 std::vector<uint8_t>* done, uint64_t* max_candidates) const;
+    // a join pair on the host, and the loop route over the rows [row0, row1) as queries (mu_ held): appends the pairs
+    // (i, j > i) that search_range_locked lists for row i, or only counts them (pairs == nullptr)
+    struct JoinPair {
+        uint64_t key;  // desc_key(score): ascending = score descending, -0.0 == +0.0
+        uint64_t ab;   // i << 32 | j
+        double score;
+    };
+    int join_loop_rows(Workspace* ws, uint64_t row0, uint64_t row1, double min_score, int metric, bool lower,
+                       std::vector<JoinPair>* pairs, uint64_t* count) const;  // lower: the partners in FRONT of each row instead
+    int join_mfma(Workspace* ws, double min_score, float thr, uint64_t out_capacity, std::vector<JoinPair>* pairs, uint64_t* total,
+                  uint64_t* stats) const;
     int wait_result(Workspace* ws, uint32_t seq) const;
     int ensure_i8_slab() const;  // lazily builds the int8 copy the single-query int8 filter streams
     int ensure_bf16_slab(bool frag_major) const;  // lazily builds the bf16 slab (row-major, or MFMA fragment order) a filter streams
@@ -792,6 +828,8 @@ private:
     std::atomic<int> grouped_batch_{2};  // GROUPED_BATCH_AUTO
     mutable std::atomic<uint64_t> last_mmrbatch_[4] = {};
     std::atomic<int> mmr_batch_{2};  // MMR_BATCH_AUTO
+    mutable std::atomic<uint64_t> last_join_[6] = {};
+    std::atomic<int> join_route_{0};  // 0 auto, 1 loop, 2 mfma
     std::atomic<uint64_t> last_delete_[6] = {};
     std::atomic<uint64_t> last_update_[7] = {};
     mutable std::mutex prof_mu_;

@@ -24,6 +24,7 @@
 #include "device_common.hpp"
 #include "scan_stream.hpp"
 #include "score_bound.hpp"
+#include "join.hpp"
 
 #include <math.h>
 #include <stdlib.h>
@@ -3133,6 +3134,135 @@ hipError_t launch_range_batch_tail(hipStream_t s, int metric, const Cand32* cand
     if (rc != hipSuccess) return rc;
     hipLaunchKernelGGL(k_rbatch_offsets, dim3(1), dim3(256), 0, s, cnt, cap, nq, emit_cap, ctr);
     if (emit_cap > 0) hipLaunchKernelGGL(k_rbatch_rank_emit, dim3(nq), dim3(256), 0, s, sv_score, sv_pos, ctr, out_pos, out_scores);
+    return hipGetLastError();
+}
+
+// ---- similarity self-join: the tail behind join.hip's candidate pass ---------------------------
+// Rescore + cut.  rescore_rows_par shares ONE query among the 16 rows of a tile; a tile of candidate PAIRS has 16 different
+// rows on either side, so this is its arithmetic with the query side tiled like the row side: all threads form the products
+// x y, x x, y y of a 16 x 48 tile (x = row b, y = row a, the call's "query"), then one lane per pair adds them in index order
+// -- wave 0 the `a` sums, wave 1 `b`, wave 2 `c`, each fl(acc + fl(product)) from 0.0 as Acc64<COSINE>::step does --
+// and Acc64::score() finishes.  Survivors are appended with one atomic per tile.
+__global__ __launch_bounds__(256) void k_join_rescore_cut(const JoinCand* __restrict__ cand, const uint32_t* __restrict__ cnt,
+                                                          uint32_t cap, const double* __restrict__ master, uint32_t dim,
+                                                          uint32_t n_rows, double min_score,
+                                                          unsigned long long* __restrict__ sv_keys, JoinPay* __restrict__ sv_pay,
+                                                          unsigned long long sv_cap, unsigned long long* __restrict__ ctr)
+{
+    const uint32_t m = *cnt;
+    if (m == 0 || m > cap) return;  // workgroup-uniform
+    __shared__ double tA[BF_ROWS][RP_CH + 1], tB[BF_ROWS][RP_CH + 1], tC[BF_ROWS][RP_CH + 1];
+    __shared__ double sum_b[BF_ROWS], sum_c[BF_ROWS];
+    __shared__ uint32_t sh_a[BF_ROWS], sh_b[BF_ROWS];
+    constexpr int PER = BF_ROWS * RP_CH / 256;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
+    for (uint32_t t0 = blockIdx.x * BF_ROWS; t0 < m; t0 += gridDim.x * BF_ROWS) {  // workgroup-uniform trip count
+        const int n_here = (int)((m - t0) < (uint32_t)BF_ROWS ? (m - t0) : (uint32_t)BF_ROWS);
+        __syncthreads();  // the previous tile's positions and sums are consumed
+        if (tid < BF_ROWS) {
+            const JoinCand c = cand[t0 + (uint32_t)(tid < n_here ? tid : n_here - 1)];
+            sh_a[tid] = c.a < n_rows ? c.a : n_rows - 1;
+            sh_b[tid] = c.b < n_rows ? c.b : n_rows - 1;
+        }
+        __syncthreads();
+        double acc = 0.0;
+        for (uint32_t c0 = 0; c0 < dim; c0 += RP_CH) {
+            const uint32_t cw = (dim - c0) < (uint32_t)RP_CH ? (dim - c0) : (uint32_t)RP_CH;
+            double x[PER], y[PER];
+#pragma unroll
+            for (int i = 0; i < PER; ++i) {  // clamped, never predicated: the duplicates are not summed
+                const int idx = tid + i * 256;
+                const int r = idx / RP_CH;
+                uint32_t col = c0 + (uint32_t)(idx % RP_CH);
+                col = col < dim ? col : dim - 1;
+                x[i] = master[(size_t)sh_b[r] * dim + col];
+                y[i] = master[(size_t)sh_a[r] * dim + col];
+            }
+            if (c0) __syncthreads();  // the previous tile is consumed
+#pragma unroll
+            for (int i = 0; i < PER; ++i) {
+                const int idx = tid + i * 256;
+                const int r = idx / RP_CH, cc = idx % RP_CH;
+                tA[r][cc] = x[i] * y[i];
+                tB[r][cc] = x[i] * x[i];
+                tC[r][cc] = y[i] * y[i];
+            }
+            __syncthreads();
+            if (wave < 3 && lane < n_here) {
+                const double* t = wave == 0 ? &tA[lane][0] : (wave == 1 ? &tB[lane][0] : &tC[lane][0]);
+                for (uint32_t cc = 0; cc < cw; ++cc) acc += t[cc];
+            }
+        }
+        if (wave == 1 && lane < BF_ROWS) sum_b[lane] = acc;
+        if (wave == 2 && lane < BF_ROWS) sum_c[lane] = acc;
+        __syncthreads();
+        if (wave == 0) {
+            const bool valid = lane < n_here;
+            Acc64<COSINE> A;
+            A.a = acc;
+            A.b = sum_b[lane & (BF_ROWS - 1)];
+            A.c = sum_c[lane & (BF_ROWS - 1)];
+            const double sc = valid ? A.score() : 0.0;
+            if (valid && sc != sc) atomicOr(ctr + JOIN_CTR_NAN, 1ull);
+            const bool keep = valid && sc >= min_score;
+            const unsigned long long bal = __ballot(keep);
+            if (bal != 0ull) {  // wave-uniform
+                unsigned long long base = 0;
+                if (lane == 0) base = atomicAdd(ctr + JOIN_CTR_TOTAL, (unsigned long long)__popcll(bal));
+                base = read_lane(base, 0);
+                const unsigned long long slot = base + (unsigned long long)__popcll(bal & ((1ull << lane) - 1ull));
+                if (keep && slot < sv_cap) {
+                    sv_keys[slot] = desc_key(sc);
+                    JoinPay p;
+                    p.ab = ((unsigned long long)sh_a[lane] << 32) | (unsigned long long)sh_b[lane];
+                    p.bits = (unsigned long long)__double_as_longlong(sc);
+                    sv_pay[slot] = p;
+                }
+            }
+        }
+    }
+}
+
+__global__ void k_join_clear_ctr(unsigned long long* __restrict__ ctr)
+{
+    if (threadIdx.x < JOIN_CTR_WORDS) ctr[threadIdx.x] = 0ull;
+}
+
+// entries that sort last, from the survivor count up to the sort's capacity
+__global__ void k_join_pad(unsigned long long* __restrict__ keys, JoinPay* __restrict__ pay, uint64_t total, uint64_t cap)
+{
+    for (uint64_t i = total + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * blockDim.x) {
+        keys[i] = ~0ull;
+        pay[i] = JoinPay{~0ull, 0ull};
+    }
+}
+
+hipError_t launch_join_clear(hipStream_t s, unsigned long long* ctr)
+{
+    hipLaunchKernelGGL(k_join_clear_ctr, dim3(1), dim3(64), 0, s, ctr);
+    return hipGetLastError();
+}
+
+hipError_t launch_join_rescore_cut(hipStream_t s, const JoinCand* cand, const uint32_t* cnt, uint32_t cap, const double* master,
+                                   uint32_t dim, uint64_t n_rows, double min_score, unsigned long long* sv_keys, JoinPay* sv_pay,
+                                   uint64_t sv_cap, unsigned long long* ctr)
+{
+    if (cap == 0 || dim == 0 || n_rows == 0 || n_rows >= 0xFFFFFFFFull) return hipErrorInvalidValue;
+    // the candidate count is the device's: enough workgroups for a full buffer, those without a tile leave at once
+    const uint32_t tiles = (cap + BF_ROWS - 1) / BF_ROWS;
+    const int grid = (int)(tiles < 2048u ? tiles : 2048u);
+    hipLaunchKernelGGL(k_join_rescore_cut, dim3(grid), dim3(256), 0, s, cand, cnt, cap, master, dim, (uint32_t)n_rows, min_score,
+                       sv_keys, sv_pay, (unsigned long long)sv_cap, ctr);
+    return hipGetLastError();
+}
+
+hipError_t launch_join_rank(hipStream_t s, unsigned long long* sv_keys, JoinPay* sv_pay, uint64_t total)
+{
+    if (total == 0 || total >= 0xFFFFFFFFull) return hipErrorInvalidValue;
+    const uint64_t cap = sort_capacity_for(total);
+    const int pgrid = (int)((cap / 256) < 4096 ? (cap / 256) : 4096);
+    hipLaunchKernelGGL(k_join_pad, dim3(pgrid), dim3(256), 0, s, sv_keys, sv_pay, total, cap);
+    bitonic_network<JoinPay>(s, sv_keys, sv_pay, cap);
     return hipGetLastError();
 }
 
