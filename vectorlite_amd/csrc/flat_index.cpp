@@ -1311,6 +1311,52 @@ int GpuFlatIndex::search_direct(const double* query, uint64_t q_len, uint64_t k,
     });
 }
 
+// mu_ held.  The environment is read per call: tests and tools switch the filter between calls of one process.
+BatchGate GpuFlatIndex::batch_gate(int metric, uint64_t nq, uint64_t k_eff) const
+{
+    const char* mf_env = getenv("VL_MFMA");
+    const char* mf_min = getenv("VL_MFMA_MIN_BATCH");
+    const uint32_t dim = (uint32_t)dim_;
+    return {force_path_.load(), n_out_of_domain_, dim_, ids_.size(), nq, k_eff, mf_env && mf_env[0] == '0',
+            mfma_scan_supported(dim, metric), mfma_rows_kernel(dim),
+            {MFMA_MIN_ROWS, mf_min && *mf_min ? (uint64_t)atoi(mf_min) : (uint64_t)MFMA_MIN_BATCH, (uint64_t)KFAST_MAX,
+             mfma_sequence_queries(dim)}};
+}
+
+int GpuFlatIndex::pass_then_redo(MfmaBatchReq req, uint64_t k, Redone* out) const
+{
+    std::vector<uint8_t> done(req.nq, 0);
+    req.done = &done;
+    {
+        WsLease lease(this, /*sync_always=*/true);
+        if (lease.status() != OK) return lease.status();
+        VL_TRY(search_batch_mfma(lease.ws, req));
+    }
+    set_last_path(PATH_FAST);
+    for (uint64_t qi = 0; qi < done.size(); ++qi)
+        if (!done[qi]) out->left.push_back(qi);
+    const uint64_t m = out->left.size();
+    if (m == 0) return OK;
+    std::vector<double> hq;
+    try {
+        hq.resize(m * dim_);
+        out->pos.resize(m * k);
+        out->ids.resize(m * k);
+        out->scores.resize(m * k);
+        out->n.assign(m, 0);
+    } catch (const std::bad_alloc&) {
+        set_last_error("out of host memory answering the queries the MFMA filter could not certify");
+        return ERR_OOM;
+    }
+    for (uint64_t i = 0; i < m; ++i) {
+        if (req.on_device)
+            VL_HIP(hipMemcpy(hq.data() + i * dim_, req.queries + out->left[i] * dim_, dim_ * sizeof(double), hipMemcpyDeviceToHost));
+        else
+            std::memcpy(hq.data() + i * dim_, req.queries + out->left[i] * dim_, dim_ * sizeof(double));
+    }
+    return search_batch_locked(hq.data(), m, dim_, k, req.metric, out->pos.data(), out->ids.data(), out->scores.data(), out->n.data());
+}
+
 // nq independent searches sharing slab passes: up to MFMA_MAX_BATCH queries per pass over the bf16 slab
 // (k_mfma_scan: cosine / dot / Euclidean, dim <= 768, >= MFMA_MIN_ROWS rows), otherwise groups of SCAN_BATCH_QB
 // queries per pass over the f32 slab (k_scan_batch).  Every query still gets its own exact rescoring, bound check
@@ -1343,6 +1389,8 @@ int GpuFlatIndex::search_batch_locked(const double* queries, uint64_t nq, uint64
 
     // row lengths without an 8-query f32 shape can still take the MFMA filter (its bf16 slab is padded to 128)
     const bool f32_batch = scan_batch_supported(ld_);
+    // what the 8-query f32 groups below ask for.  gate_topk tests the same four terms again among its own: it is the whole
+    // answer for search_batch_device and search_batch_to_record, which have no f32 groups to fall to
     const bool batchable = nq > 1 && force_path_.load() == 0 && k_eff <= (uint64_t)KFAST_MAX && n_out_of_domain_ == 0;
     auto out_at = [&](uint64_t* base, uint64_t qi) { return base ? base + qi * k : nullptr; };
     auto single = [&](uint64_t qi, bool skip_fast, bool skip_bf16 = false) -> int {
@@ -1356,12 +1404,8 @@ int GpuFlatIndex::search_batch_locked(const double* queries, uint64_t nq, uint64
 
     // two or more queries: bf16 MFMA candidate filter; whatever it cannot certify is redone below
     std::vector<uint8_t> done(nq, 0);
-    const char* mf_env = getenv("VL_MFMA");
-    const bool mfma_on = !(mf_env && mf_env[0] == '0');
-    const char* mf_min = getenv("VL_MFMA_MIN_BATCH");
-    const uint64_t mfma_min = mf_min && *mf_min ? (uint64_t)atoi(mf_min) : (uint64_t)MFMA_MIN_BATCH;
-    if (mfma_on && nq >= mfma_min && n >= MFMA_MIN_ROWS && mfma_scan_supported((uint32_t)dim_, metric)) {
-        VL_TRY(search_batch_mfma(ws, queries, nullptr, nq, k, k_eff, metric, out_pos, out_ids, out_scores, out_n, &done));
+    if (gate_topk(batch_gate(metric, nq, k_eff))) {
+        VL_TRY(search_batch_mfma(ws, {queries, false, nq, k, k_eff, metric, out_pos, out_ids, out_scores, out_n, &done}));
         uint64_t left = 0;
         for (uint64_t qi = 0; qi < nq; ++qi) left += done[qi] ? 0 : 1;
         if (left == 0) {
@@ -2404,26 +2448,20 @@ int GpuFlatIndex::search_batch_filters(const uint64_t* tokens, uint64_t n_filter
     //      (masked_batch_plan.hpp); what it does not certify joins the jobs below like any other query ----
     std::vector<uint8_t> answered(nq, 0);
     {
-        const uint64_t n = ids_.size();
-        const char* mf_env = getenv("VL_MFMA");
-        const char* mf_min = getenv("VL_MFMA_MIN_BATCH");
-        const MaskedBatchShape shp{may_batch && !(mf_env && mf_env[0] == '0') && mfma_scan_supported((uint32_t)dim_, metric) &&
-                                       mfma_rows_kernel((uint32_t)dim_),
-                                   n, (uint32_t)dim_, ld_, mfma_ldb((uint32_t)dim_)};
-        const MaskedBatchLimits lim{MFMA_MIN_ROWS, mf_min && *mf_min ? (uint64_t)atoi(mf_min) : (uint64_t)MFMA_MIN_BATCH,
-                                    (uint64_t)KFAST_MAX, mfma_sequence_queries((uint32_t)dim_)};
+        const BatchGate gate = batch_gate(metric, nq, k);
+        const MaskedBatchShape shp{gate_masked_index(gate), ids_.size(), (uint32_t)dim_, ld_, mfma_ldb((uint32_t)dim_)};
         const int mode = masked_batch_.load();
         std::vector<uint32_t> elig;
         uint64_t sum_m = 0;
         if (mode != MASKED_BATCH_OFF && shp.index_ok)
             for (uint64_t qi = 0; qi < nq; ++qi) {
                 const IdFilter* f = filter_at(qi);
-                if (f->has_keep() && masked_query_eligible(shp, lim, f->m, k)) {
+                if (f->has_keep() && masked_query_eligible(shp, gate.lim, f->m, k)) {
                     elig.push_back((uint32_t)qi);
                     sum_m += f->m;
                 }
             }
-        if (masked_batch_route(mode, shp, lim, elig.size(), sum_m)) {
+        if (masked_batch_route(mode, shp, gate.lim, elig.size(), sum_m)) {
             const uint64_t ne = elig.size();
             std::vector<const unsigned long long*> keep(ne);
             std::vector<uint32_t> mq(ne), kq(ne);
@@ -2437,8 +2475,8 @@ int GpuFlatIndex::search_batch_filters(const uint64_t* tokens, uint64_t n_filter
             std::vector<uint64_t> t_ids(ne * k), t_n(ne, 0);
             std::vector<double> t_scores(ne * k);
             std::vector<uint8_t> done(ne, 0);
-            const int rc = search_batch_mfma(ws, queries, nullptr, ne, k, k, metric, nullptr, t_ids.data(), t_scores.data(), t_n.data(),
-                                             &done, nullptr, &desc, &mb[3]);
+            const int rc = search_batch_mfma(
+                ws, {queries, false, ne, k, k, metric, nullptr, t_ids.data(), t_scores.data(), t_n.data(), &done, &desc, &mb[3]});
             if (rc != OK) {
                 publish_masked();
                 return rc;
@@ -2630,19 +2668,26 @@ int GpuFlatIndex::search_mmr_locked(Workspace* ws, IdFilter* f, const double* qu
 }
 
 // ---------------------------------------------------------------------------------------------
-// Batched diversified search (DESIGN.md section 27): nq MMR queries against one index state.  MMR needs the first
-// n = min(fetch_k, m) rows of S's ranking, exact and in order, and nothing behind them: the certified prefix of the MFMA
-// batch filter's rescored 64-entry list (section 26) gives them whenever it is n long.  k_mmr_batch_rank decides that per
-// query, k_mmr_batch_select computes the n candidates' similarities and runs the selection; a query the pass does not
-// settle runs the single search's body under the same lock, so each row is the single call's answer bit for bit.
+// The body the batched modes that ride on the sequence pipeline share.  `last`: the mode's four
+// counters (routed, settled, handed back, sequences), published as zeros once the call is admitted and again at its end.
+// k_cap: the rows a query may return (0: nothing to answer); args_ok: the entry point's rules on its pointers, reported once
+// the call is admitted and the index is known to hold rows.  t, f: the tokens admit looked up (either may stay null),
+// resolved here if rows changed since; a lazy position list waits until the first query is left to `single`, the pass
+// reads a bitmap.  The hooks, in the order they run:
+//   admit(&lk)        argument rules, token lookups, lock_for_query, and whatever else must fail before the counters change
+//   route(ws, &r)     the eligibility shape and the route decision, as a BatchRoute: S is empty, or the batch takes the
+//                     pass (with its tail, k_eff, |S| and S's one bitmap), or neither
+//   single(ws, qi)    the single search's body for query qi: what the pass did not settle, or everything
 // ---------------------------------------------------------------------------------------------
-int GpuFlatIndex::search_mmr_batch(uint64_t token, const double* queries, uint64_t nq, uint64_t q_len, uint64_t k, uint64_t fetch_k,
-                                   double lambda, int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores,
-                                   uint64_t* out_n) const
+template <typename Admit, typename Route, typename Single>
+int GpuFlatIndex::search_batched(std::atomic<uint64_t>* last, const std::shared_ptr<GroupTable>& t, const std::shared_ptr<IdFilter>& f,
+                                 const double* queries, uint64_t nq, int metric, uint64_t k_cap, bool args_ok, uint64_t out_stride,
+                                 uint64_t* out_ids, double* out_scores, uint64_t* out_n, Admit&& admit, Route&& route,
+                                 Single&& single) const
 {
-    uint64_t mb[4] = {0, 0, 0, 0};  // last_mmr_batch: routed, settled, handed back, sequences
+    uint64_t c[4] = {0, 0, 0, 0};
     auto publish = [&]() {
-        for (int i = 0; i < 4; ++i) last_mmrbatch_[i].store(mb[i], std::memory_order_relaxed);
+        for (int i = 0; i < 4; ++i) last[i].store(c[i], std::memory_order_relaxed);
     };
     if (nq == 0) {
         publish();
@@ -2651,72 +2696,31 @@ int GpuFlatIndex::search_mmr_batch(uint64_t token, const double* queries, uint64
     if (!out_n) return ERR_INVALID_ARG;
     for (uint64_t i = 0; i < nq; ++i) out_n[i] = 0;
     set_last_path(PATH_NONE);
-    VL_TRY(mmr_check_args(k, fetch_k, lambda));
-    std::shared_ptr<IdFilter> f;
-    if (token != 0) VL_TRY(find_filter(token, &f));
     std::shared_lock<RwLock> lk;  // one index state for the whole batch
-    VL_TRY(lock_for_query(metric, q_len, &lk));
+    VL_TRY(admit(&lk));
     publish();
-    const uint64_t n = ids_.size();
-    const uint64_t k_cap = std::min<uint64_t>(k, out_stride);  // out_stride is the single call's capacity
-    if (n == 0 || k_cap == 0) return OK;
-    if ((!queries && dim_) || !out_scores) return ERR_INVALID_ARG;
+    if (ids_.empty() || k_cap == 0) return OK;
+    if (!args_ok) return ERR_INVALID_ARG;
 
     WsLease lease(this, /*sync_always=*/true);
     if (lease.status() != OK) return lease.status();
     Workspace* const ws = lease.ws;
-    // an exclusion token's position list waits until a query is left to the single search: the pass reads a bitmap
-    if (f) VL_TRY(resolve_if_stale(ws, f.get(), /*need_list=*/!f->lazy_list()));
+    if (t) VL_TRY(resolve_if_stale(ws, t.get()));
+    if (f) VL_TRY(resolve_if_stale(ws, f.get(), /*need_list=*/false));
     InFlight searching(active_searches_);
-    const uint64_t m = f ? f->m : n;
-    if (m == 0) return OK;  // an empty S (search_mmr's early return)
-
     std::vector<uint8_t> done(nq, 0);
-    {
-        const char* mf_env = getenv("VL_MFMA");
-        const char* mf_min = getenv("VL_MFMA_MIN_BATCH");
-        const MaskedBatchLimits lim{MFMA_MIN_ROWS, mf_min && *mf_min ? (uint64_t)atoi(mf_min) : (uint64_t)MFMA_MIN_BATCH,
-                                    (uint64_t)KFAST_MAX, mfma_sequence_queries((uint32_t)dim_)};
-        MmrBatchShape shp;
-        shp.index = {force_path_.load() == 0 && n_out_of_domain_ == 0 && dim_ != 0 && !(mf_env && mf_env[0] == '0') &&
-                         mfma_scan_supported((uint32_t)dim_, metric),
-                     n, (uint32_t)dim_, ld_, mfma_ldb((uint32_t)dim_)};
-        shp.rows_kernel = mfma_rows_kernel((uint32_t)dim_);
-        shp.filtered = f != nullptr;
-        shp.include = f && !f->has_keep();
-        shp.m = m;
-        shp.i8_min_bytes = i8_min_bytes_;
-        shp.bf16_min_bytes = auto_min_bytes_;
-        if (mmr_batch_route(mmr_batch_.load(), shp, lim, nq, fetch_k)) {
-            const uint64_t n_need = std::min<uint64_t>(fetch_k, m);
-            const unsigned long long* keep = nullptr;
-            if (f && f->has_keep()) {
-                keep = f->d_keep;  // the token's own bitmap (section 24)
-            } else if (f) {        // an include token: its rows as a bitmap, in the borrowed workspace; no list is read
-                const uint64_t words = (n + 63) / 64;
-                VL_TRY(grow(HipMem{}, ws->gb_keep_cap, words, {dev_buf(ws->gb_keep, words)}));
-                VL_TRY(ensure_device_ids());
-                VL_HIP(launch_filter_bits(ws->stream, d_ids_, n, f->d_ids, f->ids.size(), ws->gb_keep, /*include=*/true));
-                keep = ws->gb_keep;
-            }
-            std::vector<uint32_t> qidx, mq, kq;
-            std::vector<const unsigned long long*> keep_of;
-            MaskedQueries desc{nullptr, nullptr, nullptr, nullptr};
-            if (keep) {  // every query of every sequence under the ONE bitmap of S
-                qidx.resize(nq);
-                for (uint64_t i = 0; i < nq; ++i) qidx[i] = (uint32_t)i;
-                mq.assign(nq, (uint32_t)m);
-                kq.assign(nq, (uint32_t)n_need);
-                keep_of.assign(nq, keep);
-                desc = {qidx.data(), keep_of.data(), mq.data(), kq.data()};
-            }
-            const MmrBatchReq req{m, n_need, std::min<uint64_t>(k_cap, n_need), lambda, out_stride};
-            VL_TRY(search_batch_mfma(ws, queries, nullptr, nq, out_stride, n_need, metric, nullptr, out_ids, out_scores, out_n, &done,
-                                     nullptr, keep ? &desc : nullptr, &mb[3], nullptr, &req));
-            mb[0] = nq;
-            for (uint64_t qi = 0; qi < nq; ++qi) mb[1] += done[qi] ? 1 : 0;
-            mb[2] = mb[0] - mb[1];
-        }
+    BatchRoute r;
+    VL_TRY(route(ws, &r));
+    if (r.empty) return OK;
+    if (r.take) {
+        const uint32_t m32 = (uint32_t)r.m;
+        const uint32_t k32 = (uint32_t)r.k_eff;
+        const MaskedQueries one{nullptr, &r.keep, &m32, &k32};  // every query of every sequence under the ONE bitmap of S
+        VL_TRY(search_batch_mfma(ws, {queries, false, nq, out_stride, r.k_eff, metric, nullptr, out_ids, out_scores, out_n, &done,
+                                      r.keep ? &one : nullptr, &c[3], r.tail, r.m}));
+        c[0] = nq;
+        for (uint64_t qi = 0; qi < nq; ++qi) c[1] += done[qi] ? 1 : 0;
+        c[2] = c[0] - c[1];
     }
     // what the pass did not settle (or everything), in ascending order: the first failure is the lowest failing query
     bool list_ready = !(f && f->lazy_list());
@@ -2727,12 +2731,67 @@ int GpuFlatIndex::search_mmr_batch(uint64_t token, const double* queries, uint64
             VL_TRY(ensure_plist(ws, f.get()));
             list_ready = true;
         }
-        VL_TRY(search_mmr_locked(ws, f.get(), queries + qi * dim_, k_cap, fetch_k, lambda, metric, nullptr,
-                                 out_ids ? out_ids + qi * out_stride : nullptr, out_scores + qi * out_stride, out_n + qi));
+        VL_TRY(single(ws, qi));
     }
-    if (mb[1]) set_last_path(PATH_FAST);
+    if (c[1]) set_last_path(PATH_FAST);
     publish();
     return OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Batched diversified search (DESIGN.md section 27): nq MMR queries against one index state.  MMR needs the first
+// n = min(fetch_k, m) rows of S's ranking, exact and in order, and nothing behind them: the certified prefix of the MFMA
+// batch filter's rescored 64-entry list (section 26) gives them whenever it is n long.  k_mmr_batch_rank decides that per
+// query, k_mmr_batch_select computes the n candidates' similarities and runs the selection; a query the pass does not
+// settle runs the single search's body under the same lock, so each row is the single call's answer bit for bit.
+// ---------------------------------------------------------------------------------------------
+int GpuFlatIndex::search_mmr_batch(uint64_t token, const double* queries, uint64_t nq, uint64_t q_len, uint64_t k, uint64_t fetch_k,
+                                   double lambda, int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores,
+                                   uint64_t* out_n) const
+{
+    std::shared_ptr<IdFilter> f;
+    const uint64_t k_cap = std::min<uint64_t>(k, out_stride);  // out_stride is the single call's capacity
+    return search_batched(
+        last_mmrbatch_, nullptr, f, queries, nq, metric, k_cap, (queries || !dim_) && out_scores, out_stride, out_ids, out_scores, out_n,
+        [&](std::shared_lock<RwLock>* lk) -> int {
+            VL_TRY(mmr_check_args(k, fetch_k, lambda));
+            if (token != 0) VL_TRY(find_filter(token, &f));
+            return lock_for_query(metric, q_len, lk);
+        },
+        [&](Workspace* ws, BatchRoute* r) -> int {
+            const uint64_t n = ids_.size();
+            const uint64_t m = f ? f->m : n;
+            r->empty = m == 0;  // (search_mmr's early return)
+            if (r->empty) return OK;
+            const BatchGate gate = batch_gate(metric, nq, std::min<uint64_t>(fetch_k, m));
+            MmrBatchShape shp;
+            shp.index = {gate_tail_index(gate), n, (uint32_t)dim_, ld_, mfma_ldb((uint32_t)dim_)};
+            shp.rows_kernel = gate.rows_kernel;
+            shp.filtered = f != nullptr;
+            shp.include = f && !f->has_keep();
+            shp.m = m;
+            shp.i8_min_bytes = i8_min_bytes_;
+            shp.bf16_min_bytes = auto_min_bytes_;
+            if (!mmr_batch_route(mmr_batch_.load(), shp, gate.lim, nq, fetch_k)) return OK;
+            if (f && f->has_keep()) {
+                r->keep = f->d_keep;  // the token's own bitmap (section 24)
+            } else if (f) {          // an include token: its rows as a bitmap, in the borrowed workspace; no list is read
+                const uint64_t words = (n + 63) / 64;
+                VL_TRY(grow(HipMem{}, ws->gb_keep_cap, words, {dev_buf(ws->gb_keep, words)}));
+                VL_TRY(ensure_device_ids());
+                VL_HIP(launch_filter_bits(ws->stream, d_ids_, n, f->d_ids, f->ids.size(), ws->gb_keep, /*include=*/true));
+                r->keep = ws->gb_keep;
+            }
+            r->take = true;
+            r->m = m;
+            r->k_eff = gate.k_eff;
+            r->tail = MmrTail{std::min<uint64_t>(k_cap, gate.k_eff), lambda};
+            return OK;
+        },
+        [&](Workspace* ws, uint64_t qi) -> int {
+            return search_mmr_locked(ws, f.get(), queries + qi * dim_, k_cap, fetch_k, lambda, metric, nullptr,
+                                     out_ids ? out_ids + qi * out_stride : nullptr, out_scores + qi * out_stride, out_n + qi);
+        });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3225,102 +3284,54 @@ int GpuFlatIndex::search_grouped_batch(uint64_t groups, uint64_t token, const do
                                        uint64_t k, int metric, uint64_t out_stride, uint64_t* out_group_keys, uint64_t* out_ids,
                                        double* out_scores, uint64_t* out_n) const
 {
-    uint64_t gb[4] = {0, 0, 0, 0};  // last_grouped_batch: routed, settled, handed back, sequences
-    auto publish = [&]() {
-        for (int i = 0; i < 4; ++i) last_gbatch_[i].store(gb[i], std::memory_order_relaxed);
-    };
-    if (nq == 0) {
-        publish();
-        return OK;
-    }
-    if (!out_n) return ERR_INVALID_ARG;
-    for (uint64_t i = 0; i < nq; ++i) out_n[i] = 0;
-    set_last_path(PATH_NONE);
-    if (k > GROUPED_MAX_K) {
-        set_last_error("grouped search: k exceeds VL_GROUPED_MAX_K (1024)");
-        return ERR_INVALID_ARG;
-    }
     std::shared_ptr<GroupTable> t;
-    VL_TRY(find_groups(groups, &t));
     std::shared_ptr<IdFilter> f;
-    if (token != 0) VL_TRY(find_filter(token, &f));
-    std::shared_lock<RwLock> lk;  // one index state for the whole batch
-    VL_TRY(lock_for_query(metric, q_len, &lk));
-    if (k > out_stride) {
-        set_last_error("grouped batch: k exceeds out_stride");
-        return ERR_INVALID_ARG;
-    }
-    publish();
-    if (ids_.empty() || k == 0) return OK;
-    if ((!queries && dim_) || !out_scores || !out_group_keys || !out_ids) return ERR_INVALID_ARG;
-
-    WsLease lease(this, /*sync_always=*/true);
-    if (lease.status() != OK) return lease.status();
-    Workspace* const ws = lease.ws;
-    VL_TRY(resolve_if_stale(ws, t.get()));
-    // an exclusion token's position list waits until a query is left to the single search: the pass reads a bitmap
-    if (f) VL_TRY(resolve_if_stale(ws, f.get(), /*need_list=*/false));
-    InFlight searching(active_searches_);
-    if (t->rows.m == 0 || (f && f->m == 0)) return OK;  // an empty S (search_grouped's early return)
-
-    const uint64_t n = ids_.size();
-    std::vector<uint8_t> done(nq, 0);
-    {
-        const char* mf_env = getenv("VL_MFMA");
-        const char* mf_min = getenv("VL_MFMA_MIN_BATCH");
-        const MaskedBatchLimits lim{MFMA_MIN_ROWS, mf_min && *mf_min ? (uint64_t)atoi(mf_min) : (uint64_t)MFMA_MIN_BATCH,
-                                    (uint64_t)KFAST_MAX, mfma_sequence_queries((uint32_t)dim_)};
-        GroupedBatchShape shp;
-        shp.index = {force_path_.load() == 0 && n_out_of_domain_ == 0 && dim_ != 0 && !(mf_env && mf_env[0] == '0') &&
-                         mfma_scan_supported((uint32_t)dim_, metric),
-                     n, (uint32_t)dim_, ld_, mfma_ldb((uint32_t)dim_)};
-        shp.rows_kernel = mfma_rows_kernel((uint32_t)dim_);
-        shp.needs_bitmap = f != nullptr || t->rows.m != n;
-        shp.m = f ? std::min<uint64_t>(t->rows.m, f->m) : t->rows.m;  // an upper bound until the bitmap is counted
-        const int mode = grouped_batch_.load();
-        // (the loop's estimate grows with m: a batch that loops at the upper bound loops at the counted m as well)
-        if (grouped_batch_route(mode, shp, lim, nq, k)) {
-            const unsigned long long* keep = nullptr;
+    return search_batched(
+        last_gbatch_, t, f, queries, nq, metric, k, (queries || !dim_) && out_scores && out_group_keys && out_ids, out_stride, out_ids,
+        out_scores, out_n,
+        [&](std::shared_lock<RwLock>* lk) -> int {
+            if (k > GROUPED_MAX_K) {
+                set_last_error("grouped search: k exceeds VL_GROUPED_MAX_K (1024)");
+                return ERR_INVALID_ARG;
+            }
+            VL_TRY(find_groups(groups, &t));
+            if (token != 0) VL_TRY(find_filter(token, &f));
+            VL_TRY(lock_for_query(metric, q_len, lk));
+            if (k > out_stride) {
+                set_last_error("grouped batch: k exceeds out_stride");
+                return ERR_INVALID_ARG;
+            }
+            return OK;
+        },
+        [&](Workspace* ws, BatchRoute* r) -> int {
+            r->empty = t->rows.m == 0 || (f && f->m == 0);  // (search_grouped's early return)
+            if (r->empty) return OK;
+            const uint64_t n = ids_.size();
+            const BatchGate gate = batch_gate(metric, nq, k);
+            GroupedBatchShape shp;
+            shp.index = {gate_tail_index(gate), n, (uint32_t)dim_, ld_, mfma_ldb((uint32_t)dim_)};
+            shp.rows_kernel = gate.rows_kernel;
+            shp.needs_bitmap = f != nullptr || t->rows.m != n;
+            shp.m = f ? std::min<uint64_t>(t->rows.m, f->m) : t->rows.m;  // an upper bound until the bitmap is counted
+            const int mode = grouped_batch_.load();
+            // (the loop's estimate grows with m: a batch that loops at the upper bound loops at the counted m as well)
+            if (!grouped_batch_route(mode, shp, gate.lim, nq, k)) return OK;
             if (shp.needs_bitmap) {
-                VL_TRY(grouped_keep_bits(ws, t.get(), f.get(), &keep, &shp.m));
-                if (shp.m == 0) return OK;  // the filter keeps no grouped row
+                VL_TRY(grouped_keep_bits(ws, t.get(), f.get(), &r->keep, &shp.m));
+                r->empty = shp.m == 0;  // the filter keeps no grouped row
+                if (r->empty) return OK;
             }
-            if (grouped_batch_route(mode, shp, lim, nq, k)) {
-                std::vector<uint32_t> qidx, mq, kq;
-                std::vector<const unsigned long long*> keep_of;
-                MaskedQueries desc{nullptr, nullptr, nullptr, nullptr};
-                if (keep) {  // every query of every sequence under the ONE bitmap of S
-                    qidx.resize(nq);
-                    for (uint64_t i = 0; i < nq; ++i) qidx[i] = (uint32_t)i;
-                    mq.assign(nq, (uint32_t)shp.m);
-                    kq.assign(nq, (uint32_t)k);
-                    keep_of.assign(nq, keep);
-                    desc = {qidx.data(), keep_of.data(), mq.data(), kq.data()};
-                }
-                const GroupedReq req{t.get(), shp.m, out_stride, out_group_keys};
-                VL_TRY(search_batch_mfma(ws, queries, nullptr, nq, out_stride, k, metric, nullptr, out_ids, out_scores, out_n, &done,
-                                         nullptr, keep ? &desc : nullptr, &gb[3], &req));
-                gb[0] = nq;
-                for (uint64_t qi = 0; qi < nq; ++qi) gb[1] += done[qi] ? 1 : 0;
-                gb[2] = gb[0] - gb[1];
-            }
-        }
-    }
-    // what the pass did not settle (or everything), in ascending order: the first failure is the lowest failing query
-    bool list_ready = !(f && f->lazy_list());
-    for (uint64_t qi = 0; qi < nq; ++qi) {
-        if (done[qi]) continue;
-        if (!list_ready) {
-            std::lock_guard<std::mutex> fg(f->mu);
-            VL_TRY(ensure_plist(ws, f.get()));
-            list_ready = true;
-        }
-        VL_TRY(search_grouped_locked(ws, t.get(), f.get(), queries + qi * dim_, k, metric, out_stride, out_group_keys + qi * out_stride,
-                                     nullptr, out_ids + qi * out_stride, out_scores + qi * out_stride, out_n + qi));
-    }
-    if (gb[1]) set_last_path(PATH_FAST);
-    publish();
-    return OK;
+            r->take = grouped_batch_route(mode, shp, gate.lim, nq, k);
+            r->m = shp.m;
+            r->k_eff = k;
+            r->tail = GroupedTail{t.get(), out_group_keys};
+            return OK;
+        },
+        [&](Workspace* ws, uint64_t qi) -> int {
+            return search_grouped_locked(ws, t.get(), f.get(), queries + qi * dim_, k, metric, out_stride,
+                                         out_group_keys + qi * out_stride, nullptr, out_ids + qi * out_stride,
+                                         out_scores + qi * out_stride, out_n + qi);
+        });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3449,13 +3460,7 @@ int GpuFlatIndex::search_batch_to_record(const double* queries, bool queries_on_
     const uint64_t n = ids_.size();
     if (n == 0 || q_len != dim_) return OK;  // (errors and empty shards are the host path's to report)
     const uint64_t k_eff = std::min<uint64_t>(ks, n);
-    const char* mf_env = getenv("VL_MFMA");
-    const char* mf_min = getenv("VL_MFMA_MIN_BATCH");
-    const uint64_t mfma_min = mf_min && *mf_min ? (uint64_t)atoi(mf_min) : (uint64_t)MFMA_MIN_BATCH;
-    const bool direct = nq > 1 && force_path_.load() == 0 && k_eff <= (uint64_t)KFAST_MAX && n_out_of_domain_ == 0 &&
-                        !(mf_env && mf_env[0] == '0') && nq >= mfma_min && n >= MFMA_MIN_ROWS &&
-                        mfma_scan_supported((uint32_t)dim_, metric) && nq * ks < (1ull << 31);
-    if (!direct) return OK;
+    if (!gate_record(batch_gate(metric, nq, k_eff), ks)) return OK;
     VL_TRY(ensure_device_ids());
     ShardRecordSink sink;
     sink.cnt = d_record + SHARD_HDR_WORDS;
@@ -3465,9 +3470,7 @@ int GpuFlatIndex::search_batch_to_record(const double* queries, bool queries_on_
     sink.pos_to_id = d_ids_;
     sink.row_offset = row_offset;
     sink.ks = (uint32_t)ks;
-    // host-side answers of the queries the filter certifies are not needed (the record is the answer); the others come back
-    // through `done` and are redone below
-    std::vector<uint8_t> done(nq, 0);
+    // host-side answers of the queries the filter certifies are not needed (the record is the answer)
     std::vector<uint64_t> cnt(nq, 0);
     std::vector<uint64_t> pos, ids;
     std::vector<double> sc;
@@ -3479,44 +3482,25 @@ int GpuFlatIndex::search_batch_to_record(const double* queries, bool queries_on_
         set_last_error("out of host memory in the shard search");
         return ERR_OOM;
     }
-    {
-        WsLease lease(this, /*sync_always=*/true);
-        if (lease.status() != OK) return lease.status();
-        VL_TRY(search_batch_mfma(lease.ws, queries_on_device ? nullptr : queries, queries_on_device ? queries : nullptr, nq, ks, k_eff, metric,
-                                 pos.data(), ids.data(), sc.data(), cnt.data(), &done, &sink));
-    }
-    set_last_path(PATH_FAST);
     // what the filter could not certify: the host paths answer those queries (under the same shared lock: one index state
-    // for the whole batch) and their slices of the record are patched; typically none
-    std::vector<uint64_t> left;
-    for (uint64_t qi = 0; qi < nq; ++qi)
-        if (!done[qi]) left.push_back(qi);
-    if (!left.empty()) {
-        const uint64_t m = left.size();
-        std::vector<double> hq(m * dim_);
-        for (uint64_t i = 0; i < m; ++i) {
-            if (queries_on_device)
-                VL_HIP(hipMemcpy(hq.data() + i * dim_, queries + left[i] * dim_, dim_ * sizeof(double), hipMemcpyDeviceToHost));
-            else
-                std::memcpy(hq.data() + i * dim_, queries + left[i] * dim_, dim_ * sizeof(double));
+    // for the whole batch) and their slices of the record are patched
+    Redone t;
+    VL_TRY(pass_then_redo({queries, queries_on_device, nq, ks, k_eff, metric, pos.data(), ids.data(), sc.data(), cnt.data(), nullptr,
+                           nullptr, nullptr, &sink},
+                          ks, &t));
+    for (uint64_t i = 0; i < t.left.size(); ++i) {
+        const uint64_t qi = t.left[i], c = std::min<uint64_t>(t.n[i], ks);
+        std::vector<unsigned long long> buf(3 * ks, 0ull);
+        for (uint64_t j = 0; j < c; ++j) {
+            std::memcpy(&buf[j], &t.scores[i * ks + j], 8);
+            buf[ks + j] = t.pos[i * ks + j] + row_offset;
+            buf[2 * ks + j] = t.ids[i * ks + j];
         }
-        std::vector<uint64_t> t_pos(m * ks), t_ids(m * ks), t_n(m, 0);
-        std::vector<double> t_sc(m * ks);
-        VL_TRY(search_batch_locked(hq.data(), m, dim_, ks, metric, t_pos.data(), t_ids.data(), t_sc.data(), t_n.data()));
-        for (uint64_t i = 0; i < m; ++i) {
-            const uint64_t qi = left[i], c = std::min<uint64_t>(t_n[i], ks);
-            std::vector<unsigned long long> buf(3 * ks, 0ull);
-            for (uint64_t j = 0; j < c; ++j) {
-                std::memcpy(&buf[j], &t_sc[i * ks + j], 8);
-                buf[ks + j] = t_pos[i * ks + j] + row_offset;
-                buf[2 * ks + j] = t_ids[i * ks + j];
-            }
-            const unsigned long long c64 = c;
-            VL_HIP(hipMemcpy(sink.cnt + qi, &c64, 8, hipMemcpyHostToDevice));
-            VL_HIP(hipMemcpy(sink.score_bits + qi * ks, buf.data(), ks * 8, hipMemcpyHostToDevice));
-            VL_HIP(hipMemcpy(sink.gpos + qi * ks, buf.data() + ks, ks * 8, hipMemcpyHostToDevice));
-            VL_HIP(hipMemcpy(sink.ids + qi * ks, buf.data() + 2 * ks, ks * 8, hipMemcpyHostToDevice));
-        }
+        const unsigned long long c64 = c;
+        VL_HIP(hipMemcpy(sink.cnt + qi, &c64, 8, hipMemcpyHostToDevice));
+        VL_HIP(hipMemcpy(sink.score_bits + qi * ks, buf.data(), ks * 8, hipMemcpyHostToDevice));
+        VL_HIP(hipMemcpy(sink.gpos + qi * ks, buf.data() + ks, ks * 8, hipMemcpyHostToDevice));
+        VL_HIP(hipMemcpy(sink.ids + qi * ks, buf.data() + 2 * ks, ks * 8, hipMemcpyHostToDevice));
     }
     *handled = true;
     return OK;
@@ -3549,23 +3533,25 @@ int GpuFlatIndex::ensure_mfma_scratch(Workspace* ws) const
 
 // Cosine / dot / Euclidean batches of >= MFMA_MIN_BATCH queries.  done[qi] is set for every query
 // answered here; the caller redoes the others (bound check failed, candidate overflow, ...).
-int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const double* d_queries, uint64_t nq,
-                                    uint64_t k, uint64_t k_eff, int metric, uint64_t* out_pos, uint64_t* out_ids,
-                                    double* out_scores, uint64_t* out_n, std::vector<uint8_t>* done,
-                                    const ShardRecordSink* sink, const MaskedQueries* masked, uint64_t* n_sequences,
-                                    const GroupedReq* grouped, const MmrBatchReq* mmr) const
+int GpuFlatIndex::search_batch_mfma(Workspace* ws, const MfmaBatchReq& R) const
 {
     static_assert(sizeof(const unsigned long long*) == sizeof(double) && 2 * sizeof(uint32_t) == sizeof(double),
                   "the masked descriptor is staged as two words per query behind the norms");
-    if (masked && (d_queries || sink || !mfma_rows_kernel((uint32_t)dim_))) return ERR_INVALID_ARG;
-    if (grouped && (d_queries || sink || !out_ids || !grouped->out_keys || k_eff == 0 || k_eff > (uint64_t)KFAST_MAX))
-        return ERR_INVALID_ARG;
-    if (mmr && (grouped || d_queries || sink || k_eff != mmr->n || mmr->n == 0 || mmr->n > (uint64_t)KFAST_MAX || mmr->n > mmr->m ||
-                mmr->k_out == 0 || mmr->k_out > mmr->n || mmr->k_out > mmr->out_stride))
-        return ERR_INVALID_ARG;
-    if (n_sequences) *n_sequences = 0;
-    const uint64_t n = ids_.size();
+    const MaskedQueries* const masked = R.masked;
+    const ShardRecordSink* const* const record = std::get_if<const ShardRecordSink*>(&R.tail);
+    const GroupedTail* const grouped = std::get_if<GroupedTail>(&R.tail);
+    const MmrTail* const mmr = std::get_if<MmrTail>(&R.tail);
+    const uint64_t nq = R.nq, k_eff = R.k_eff;
+    const int metric = R.metric;
     const bool frag = mfma_rows_kernel((uint32_t)dim_);  // which kernel, hence which slab layout
+    // a mask and the grouped and MMR tails stage host queries; a mask needs the row-stationary kernel and fills no record
+    if (((masked || grouped || mmr) && R.on_device) || (masked && (record || !frag)) ||
+        (grouped && (!R.out_ids || !grouped->out_keys || k_eff == 0 || k_eff > (uint64_t)KFAST_MAX)) ||
+        (mmr && (k_eff == 0 || k_eff > (uint64_t)KFAST_MAX || k_eff > R.m || mmr->k_out == 0 || mmr->k_out > k_eff ||
+                 mmr->k_out > R.stride)))
+        return ERR_INVALID_ARG;
+    if (R.n_sequences) *R.n_sequences = 0;
+    const uint64_t n = ids_.size();
     VL_TRY(ensure_bf16_slab(frag));
     const void* slab16 = frag ? d_slab16f_ : d_slab16_;
     VL_TRY(ensure_mfma_scratch(ws));
@@ -3573,7 +3559,6 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
     if (mmr) VL_TRY(ensure_set(HipMem{}, {dev_buf(ws->mb_ranked, (size_t)MFMA_MAX_BATCH)}));
     hipStream_t st = ws->stream;
     const double in_extra = IN_EXTRA_MFMA;  // bf16 rows and queries (mfma_scan.hpp)
-    const uint64_t k_eff_all = k_eff;       // (a masked batch has its own per query)
     const bool prof = profile_.load();
     static const bool trace = getenv("VL_TRACE_BATCH") != nullptr;  // diagnostic: host-side phases of a sequence on stderr
     auto now = [] { return std::chrono::steady_clock::now(); };
@@ -3595,6 +3580,110 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
         std::chrono::steady_clock::time_point t0, t1, t2;
     } sq[2];
     const bool pipelined = !prof;  // (the profile's event pair brackets one sequence at a time)
+    // ---- the tails: per sequence of g queries in `slot`, what is launched behind the candidate pass and how the settled
+    //      queries are unpacked.  One unpack loop over the sequence's result blocks `res`: a tail says whether a block settled
+    //      its query and with how many rows, checks what it alone knows of them (every position is checked here), and writes
+    //      what goes out beside (position, id, score) ----
+    auto result_blocks = [&](int slot) { return ws->mf_h_result + (size_t)slot * MFMA_MAX_BATCH; };
+    auto unpack = [&](const SeqState& S, const auto* res, const char* bug, auto settled, auto entries_ok, auto extra_out) -> int {
+        for (uint32_t j = 0; j < S.g; ++j) {
+            const uint64_t qi = S.q0 + j;
+            const auto& r = res[j];
+            uint64_t rows = 0;
+            if (!S.in_domain[j] || !settled(r, qi, &rows)) continue;
+            bool ok = entries_ok(r, rows);
+            for (uint64_t i = 0; ok && i < rows; ++i) ok = r.pos[i] < n;
+            if (!ok) {
+                set_last_error(bug);
+                return ERR_DEVICE;
+            }
+            const uint64_t want = std::min<uint64_t>(rows, R.stride);
+            const size_t o = (size_t)(qi * R.stride);
+            extra_out(r, o, want);
+            for (uint64_t i = 0; i < want; ++i) {  // (every position was checked above, under the tail's own message)
+                if (R.out_pos) R.out_pos[o + i] = r.pos[i];
+                if (R.out_ids) R.out_ids[o + i] = ids_[r.pos[i]];
+                R.out_scores[o + i] = r.score[i];
+            }
+            R.out_n[qi] = want;
+            (*R.done)[qi] = 1;
+        }
+        return OK;
+    };
+    auto nothing_beside = [](const auto&, size_t, uint64_t) {};
+    // top-k, and the shard record: the rescoring split over four workgroups per query + a rank / emit launch
+    // (launch_batch_finalize); a handful of queries keeps the one-workgroup-per-query kernel (one launch less).  Under a mask
+    // the certificate is per query: n_rows = m_q, k = min(k, m_q) (DESIGN.md sections 23, 24)
+    auto launch_topk = [&](int slot, uint32_t g, uint64_t q0) -> hipError_t {
+        static const bool split_off = []() { const char* v = getenv("VL_BATCH_FINALIZE"); return v && v[0] == '0'; }();
+        const double* d_norms = ws->mf_d_q64 + (size_t)g * dim_;
+        const uint32_t* d_m = reinterpret_cast<const uint32_t*>(d_norms + 2 * (size_t)g);
+        ShardRecordSink seq_sink;
+        if (record) {  // this sequence's queries sit at [q0, q0 + g) of the record
+            seq_sink = **record;
+            seq_sink.q0 = (uint32_t)q0;
+        }
+        if (masked)
+            return launch_batch_finalize_rows(st, metric, ws->mf_lists, (int)g, d_master_, ws->mf_d_q64, d_norms, (uint32_t)dim_, d_m,
+                                              d_m + g, max_row_norm_, result_blocks(slot), in_extra, ws->mf_scores);
+        if (g >= 8 && !split_off)
+            return launch_batch_finalize(st, metric, ws->mf_lists, (int)g, d_master_, ws->mf_d_q64, d_norms, (uint32_t)dim_, n,
+                                         (uint32_t)k_eff, max_row_norm_, result_blocks(slot), in_extra, ws->mf_scores,
+                                         record ? &seq_sink : nullptr);
+        return launch_merge_finalize(st, metric, ws->mf_lists, 1, (int)g, d_master_, ws->mf_d_q64, d_norms, (uint32_t)dim_, n,
+                                     (uint32_t)k_eff, max_row_norm_, result_blocks(slot), in_extra, 0, record ? &seq_sink : nullptr);
+    };
+    auto unpack_topk = [&](const SeqState& S, int slot) -> int {
+        return unpack(
+            S, result_blocks(slot), "MFMA path returned an out-of-range position (kernel bug)",
+            [&](const SearchResultBlock& r, uint64_t qi, uint64_t* rows) {
+                *rows = masked ? masked->k[masked->at(qi)] : k_eff;
+                return !(r.flags & RESULT_NEEDS_EXACT) && r.n_out == *rows;
+            },
+            [](const SearchResultBlock&, uint64_t) { return true; }, nothing_beside);
+    };
+    // grouped: the certified prefix of each list, collapsed to one row per group; settled queries
+    // come back as (group number, position, score), group number -> key
+    auto launch_grouped = [&](int slot, uint32_t g) -> hipError_t {
+        return launch_batch_finalize_grouped(st, metric, ws->mf_lists, (int)g, d_master_, ws->mf_d_q64, ws->mf_d_q64 + (size_t)g * dim_,
+                                             (uint32_t)dim_, R.m, (uint32_t)k_eff, max_row_norm_, grouped->table->d_group_of_row,
+                                             n, ws->gb_h_result + (size_t)slot * MFMA_MAX_BATCH, in_extra, ws->mf_scores);
+    };
+    auto unpack_grouped = [&](const SeqState& S, int slot) -> int {
+        const std::vector<uint64_t>& keys = grouped->table->keys;
+        return unpack(
+            S, ws->gb_h_result + (size_t)slot * MFMA_MAX_BATCH, "grouped MFMA path returned an out-of-range entry (kernel bug)",
+            [&](const GroupedResultBlock& r, uint64_t, uint64_t* rows) {
+                *rows = r.n_out;
+                return r.flags == 0u;
+            },
+            [&](const GroupedResultBlock& r, uint64_t rows) {
+                bool ok = rows <= k_eff;
+                for (uint64_t i = 0; ok && i < rows; ++i) ok = r.group[i] < keys.size();
+                return ok;
+            },
+            [&](const GroupedResultBlock& r, size_t o, uint64_t want) {
+                for (uint64_t i = 0; i < want; ++i) grouped->out_keys[o + i] = keys[r.group[i]];
+            });
+    };
+    // MMR: the certified prefix of each list, then similarities and selection; settled queries come
+    // back as the selection, in its order
+    auto launch_mmr = [&](int slot, uint32_t g) -> hipError_t {
+        const hipError_t e = launch_batch_rescore(st, metric, ws->mf_lists, (int)g, d_master_, ws->mf_d_q64, (uint32_t)dim_, ws->mf_scores);
+        if (e != hipSuccess) return e;
+        return launch_mmr_batch(st, metric, ws->mf_lists, ws->mf_scores, (int)g, ws->mf_d_q64 + (size_t)g * dim_, d_master_,
+                                (uint32_t)dim_, R.m, n, (uint32_t)k_eff, (uint32_t)mmr->k_out, mmr->lambda, max_row_norm_, in_extra,
+                                ws->mb_ranked, result_blocks(slot));
+    };
+    auto unpack_mmr = [&](const SeqState& S, int slot) -> int {
+        return unpack(
+            S, result_blocks(slot), "the batched selection returned an out-of-range entry (kernel bug)",
+            [&](const SearchResultBlock& r, uint64_t, uint64_t* rows) {
+                *rows = mmr->k_out;
+                return r.flags == 0u;
+            },
+            [](const SearchResultBlock& r, uint64_t rows) { return r.n_out == rows; }, nothing_beside);
+    };
     auto enqueue = [&](int slot, uint64_t q0) -> int {
         SeqState& S = sq[slot];
         S.q0 = q0;
@@ -3603,16 +3692,15 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
         S.t0 = now();
         const uint32_t g = S.g;
         S.in_domain.assign(g, 0);
-        SearchResultBlock* res = ws->mf_h_result + (size_t)slot * MFMA_MAX_BATCH;
         unsigned char* dom = ws->mf_h_dom + (size_t)slot * MFMA_MAX_BATCH;
         bool prepared = false;
-        if (d_queries) {  // already on this GPU: staged by a kernel; the flags land in pinned memory, read after the wait
+        if (R.on_device) {  // already on this GPU: staged by a kernel; the flags land in pinned memory, read after the wait
             hipError_t pe = hipSuccess;
-            prepared = frag && launch_prepare_queries(st, d_queries + q0 * dim_, g, (uint32_t)dim_, DOMAIN_MAX_ABS, DOMAIN_MIN_NORM,
+            prepared = frag && launch_prepare_queries(st, R.queries + q0 * dim_, g, (uint32_t)dim_, DOMAIN_MAX_ABS, DOMAIN_MIN_NORM,
                                                       ws->mf_d_q64, ws->mf_d_q64 + (size_t)g * dim_, dom, ws->mf, &pe);
             VL_HIP(pe);
             if (!prepared)
-                VL_HIP(launch_stage_queries(st, d_queries + q0 * dim_, g, (uint32_t)dim_, DOMAIN_MAX_ABS, DOMAIN_MIN_NORM,
+                VL_HIP(launch_stage_queries(st, R.queries + q0 * dim_, g, (uint32_t)dim_, DOMAIN_MAX_ABS, DOMAIN_MIN_NORM,
                                             ws->mf_d_q64, ws->mf_d_q64 + (size_t)g * dim_, dom));
         } else {
             // Host queries go to pinned memory (domain test, norm) and over PCIe in pieces: the copy of one piece runs
@@ -3627,8 +3715,8 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
             for (uint32_t j0 = 0; j0 < g; j0 += piece) {
                 const uint32_t j1 = std::min<uint32_t>(g, j0 + piece);
                 for (uint32_t j = j0; j < j1; ++j) {
-                    const uint64_t src = masked ? masked->qidx[q0 + j] : q0 + j;
-                    S.in_domain[j] = stage_query(queries + src * dim_, ws->mf_h_q64 + (size_t)j * dim_, dim_, &norms[j]) ? 1 : 0;
+                    const uint64_t src = masked && masked->qidx ? masked->qidx[q0 + j] : q0 + j;
+                    S.in_domain[j] = stage_query(R.queries + src * dim_, ws->mf_h_q64 + (size_t)j * dim_, dim_, &norms[j]) ? 1 : 0;
                 }
                 VL_HIP(hipMemcpyAsync(ws->mf_d_q64 + (size_t)j0 * dim_, ws->mf_h_q64 + (size_t)j0 * dim_,
                                       (size_t)(j1 - j0) * dim_ * sizeof(double), hipMemcpyHostToDevice, st));
@@ -3639,9 +3727,9 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
                 const unsigned long long** h_keep = reinterpret_cast<const unsigned long long**>(norms + g);
                 uint32_t* h_m = reinterpret_cast<uint32_t*>(norms + 2 * (size_t)g);
                 for (uint32_t j = 0; j < g; ++j) {
-                    h_keep[j] = masked->keep[q0 + j];
-                    h_m[j] = masked->m[q0 + j];
-                    h_m[g + j] = masked->k[q0 + j];
+                    h_keep[j] = masked->keep[masked->at(q0 + j)];
+                    h_m[j] = masked->m[masked->at(q0 + j)];
+                    h_m[g + j] = masked->k[masked->at(q0 + j)];
                 }
             }
             VL_HIP(hipMemcpyAsync(ws->mf_d_q64 + (size_t)g * dim_, norms, (size_t)g * (masked ? 3 : 1) * sizeof(double),
@@ -3654,7 +3742,6 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
         MfmaLaunchInfo li;
         const double* d_norms = ws->mf_d_q64 + (size_t)g * dim_;
         const unsigned long long* const* d_keep_of = reinterpret_cast<const unsigned long long* const*>(d_norms + g);
-        const uint32_t* d_m = reinterpret_cast<const uint32_t*>(d_norms + 2 * (size_t)g);
         if (masked)
             VL_HIP(launch_mfma_candidates_masked(st, metric, slab16, d_norm16_, d_sqnorm_, ws->mf_d_q64, g, n, (uint32_t)dim_,
                                                  ws->mf, d_keep_of, ws->mf_lists, &li));
@@ -3666,35 +3753,14 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
             for (int i = 0; i < 6; ++i) last_filter_[i].store(v[i], std::memory_order_relaxed);
         }
         if (prof) VL_HIP(hipEventRecord(ws->ev1, st));
-        ShardRecordSink seq_sink;
-        if (sink) {  // this sequence's queries sit at [q0, q0 + g) of the record
-            seq_sink = *sink;
-            seq_sink.q0 = (uint32_t)q0;
-        }
-        // batches: the rescoring split over four workgroups per query + a rank / emit launch (launch_batch_finalize); a handful
-        // of queries keeps the one-workgroup-per-query kernel (one launch less)
-        static const bool split_off = []() { const char* v = getenv("VL_BATCH_FINALIZE"); return v && v[0] == '0'; }();
-        if (grouped)  // the certified prefix of each list, collapsed to one row per group
-            VL_HIP(launch_batch_finalize_grouped(st, metric, ws->mf_lists, (int)g, d_master_, ws->mf_d_q64, d_norms, (uint32_t)dim_,
-                                                 grouped->m, (uint32_t)k_eff, max_row_norm_, grouped->table->d_group_of_row, n,
-                                                 ws->gb_h_result + (size_t)slot * MFMA_MAX_BATCH, in_extra, ws->mf_scores));
-        else if (mmr) {  // the certified prefix of each list, then similarities and selection
-            VL_HIP(launch_batch_rescore(st, metric, ws->mf_lists, (int)g, d_master_, ws->mf_d_q64, (uint32_t)dim_, ws->mf_scores));
-            VL_HIP(launch_mmr_batch(st, metric, ws->mf_lists, ws->mf_scores, (int)g, d_norms, d_master_, (uint32_t)dim_, mmr->m, n,
-                                    (uint32_t)mmr->n, (uint32_t)mmr->k_out, mmr->lambda, max_row_norm_, in_extra, ws->mb_ranked, res));
-        } else if (masked)  // the certificate per query: n_rows = m_q, k = min(k, m_q) (DESIGN.md sections 23, 24)
-            VL_HIP(launch_batch_finalize_rows(st, metric, ws->mf_lists, (int)g, d_master_, ws->mf_d_q64, d_norms, (uint32_t)dim_,
-                                              d_m, d_m + g, max_row_norm_, res, in_extra, ws->mf_scores));
-        else if (g >= 8 && !split_off)
-            VL_HIP(launch_batch_finalize(st, metric, ws->mf_lists, (int)g, d_master_, ws->mf_d_q64, ws->mf_d_q64 + (size_t)g * dim_,
-                                         (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_, res, in_extra, ws->mf_scores,
-                                         sink ? &seq_sink : nullptr));
+        if (grouped)
+            VL_HIP(launch_grouped(slot, g));
+        else if (mmr)
+            VL_HIP(launch_mmr(slot, g));
         else
-            VL_HIP(launch_merge_finalize(st, metric, ws->mf_lists, 1, (int)g, d_master_, ws->mf_d_q64,
-                                         ws->mf_d_q64 + (size_t)g * dim_, (uint32_t)dim_, n, (uint32_t)k_eff, max_row_norm_,
-                                         res, in_extra, 0, sink ? &seq_sink : nullptr));
+            VL_HIP(launch_topk(slot, g, q0));
         VL_HIP(hipEventRecord(ws->mf_ev_done[slot], st));
-        if (n_sequences) ++*n_sequences;
+        if (R.n_sequences) ++*R.n_sequences;
         S.t2 = now();
         return OK;
     };
@@ -3703,82 +3769,27 @@ int GpuFlatIndex::search_batch_mfma(Workspace* ws, const double* queries, const 
         if (!S.live) return OK;
         S.live = false;
         const uint32_t g = S.g;
-        const SearchResultBlock* res = ws->mf_h_result + (size_t)slot * MFMA_MAX_BATCH;
         const unsigned char* dom = ws->mf_h_dom + (size_t)slot * MFMA_MAX_BATCH;
         VL_HIP(hipEventSynchronize(ws->mf_ev_done[slot]));
-        if (d_queries)
+        if (R.on_device)
             for (uint32_t j = 0; j < g; ++j) S.in_domain[j] = dom[j];
         const auto t_3 = now();
         if (prof) {
             uint64_t bytes = n * (uint64_t)mfma_ldb((uint32_t)dim_) * 2;
             if (masked) {  // and every distinct bitmap of the sequence once
-                std::vector<const unsigned long long*> maps(masked->keep + S.q0, masked->keep + S.q0 + g);
+                std::vector<const unsigned long long*> maps(g);
+                for (uint32_t j = 0; j < g; ++j) maps[j] = masked->keep[masked->at(S.q0 + j)];
                 std::sort(maps.begin(), maps.end());
                 bytes += (uint64_t)(std::unique(maps.begin(), maps.end()) - maps.begin()) * (n / 8);
             }
             VL_TRY(account_profile(ws, bytes));
         }
-        for (uint32_t j = 0; grouped && j < g; ++j) {  // settled queries: position -> id, group number -> key
-            const uint64_t qi = S.q0 + j;
-            const GroupedResultBlock& r = ws->gb_h_result[(size_t)slot * MFMA_MAX_BATCH + j];
-            if (!S.in_domain[j] || r.flags != 0u) continue;
-            const std::vector<uint64_t>& keys = grouped->table->keys;
-            bool ok = r.n_out <= k_eff_all;
-            for (uint64_t i = 0; ok && i < r.n_out; ++i) ok = r.pos[i] < n && r.group[i] < keys.size();
-            if (!ok) {
-                set_last_error("grouped MFMA path returned an out-of-range entry (kernel bug)");
-                return ERR_DEVICE;
-            }
-            const uint64_t want = std::min<uint64_t>(r.n_out, grouped->out_stride);
-            for (uint64_t i = 0; i < want; ++i) {
-                const size_t o = qi * grouped->out_stride + i;
-                grouped->out_keys[o] = keys[r.group[i]];
-                if (out_pos) out_pos[o] = r.pos[i];
-                out_ids[o] = ids_[r.pos[i]];
-                out_scores[o] = r.score[i];
-            }
-            out_n[qi] = want;
-            (*done)[qi] = 1;
-        }
-        for (uint32_t j = 0; mmr && j < g; ++j) {  // settled queries: the selection, position -> id
-            const uint64_t qi = S.q0 + j;
-            const SearchResultBlock& r = res[j];
-            if (!S.in_domain[j] || r.flags != 0u) continue;
-            bool ok = r.n_out == mmr->k_out;
-            for (uint64_t i = 0; ok && i < mmr->k_out; ++i) ok = r.pos[i] < n;
-            if (!ok) {
-                set_last_error("the batched selection returned an out-of-range entry (kernel bug)");
-                return ERR_DEVICE;
-            }
-            for (uint64_t i = 0; i < mmr->k_out; ++i) {
-                const size_t o = qi * mmr->out_stride + i;
-                if (out_pos) out_pos[o] = r.pos[i];
-                if (out_ids) out_ids[o] = ids_[r.pos[i]];
-                out_scores[o] = r.score[i];
-            }
-            out_n[qi] = mmr->k_out;
-            (*done)[qi] = 1;
-        }
-        for (uint32_t j = 0; !grouped && !mmr && j < g; ++j) {
-            const uint64_t qi = S.q0 + j;
-            const SearchResultBlock& r = res[j];
-            const uint64_t k_eff = masked ? masked->k[qi] : k_eff_all;
-            if (!S.in_domain[j] || (r.flags & RESULT_NEEDS_EXACT) || r.n_out != k_eff) continue;
-            bool ok = true;
-            for (uint64_t i = 0; i < k_eff; ++i) ok = ok && r.pos[i] < n;
-            if (!ok) {
-                set_last_error("MFMA path returned an out-of-range position (kernel bug)");
-                return ERR_DEVICE;
-            }
-            for (uint64_t i = 0; i < k_eff; ++i) {
-                const uint32_t p = r.pos[i];
-                if (out_pos) out_pos[qi * k + i] = p;
-                if (out_ids) out_ids[qi * k + i] = ids_[p];
-                out_scores[qi * k + i] = r.score[i];
-            }
-            out_n[qi] = k_eff;
-            (*done)[qi] = 1;
-        }
+        if (grouped)
+            VL_TRY(unpack_grouped(S, slot));
+        else if (mmr)
+            VL_TRY(unpack_mmr(S, slot));
+        else
+            VL_TRY(unpack_topk(S, slot));
         if (trace) {
             const auto t4 = now();
             fprintf(stderr, "[vl batch] %u queries: stage %ld us, enqueue %ld us, wait %ld us, unpack %ld us\n", g, us(S.t0, S.t1),
@@ -3893,16 +3904,11 @@ int GpuFlatIndex::search_range_batch(uint64_t token, const double* queries, uint
     };
 
     std::vector<uint8_t> done(nq_run, 0);
-    const char* mf_env = getenv("VL_MFMA");
-    const char* mf_min = getenv("VL_MFMA_MIN_BATCH");
-    const uint64_t mfma_min = mf_min && *mf_min ? (uint64_t)atoi(mf_min) : (uint64_t)MFMA_MIN_BATCH;
     // (no minimum row count: the floor of the top-k batch belongs to its sampling pass, and this route has none)
     // The filter keeps `key >= thr`, which drops a NaN key, where the single scan's `!(key <= tau)` keeps it.  That is sound
     // only because NaN keys cannot occur on this route: rows outside the fast-path domain (n_out_of_domain_ != 0) take the
     // whole batch off it, and a query outside the domain is staged as zeros with thr = +inf and answered by the single call.
-    const bool fast = !f && nq_run >= mfma_min && force_path_.load() == 0 && n_out_of_domain_ == 0 && !(mf_env && mf_env[0] == '0') &&
-                      mfma_scan_supported((uint32_t)dim_, metric) && mfma_rows_kernel((uint32_t)dim_);
-    if (fast) {
+    if (gate_range(batch_gate(metric, nq_run, 0), f != nullptr)) {
         VL_TRY(search_range_batch_mfma(ws, queries, nq_run, min_scores, metric, out_stride, out_ids, out_scores, out_n, out_total,
                                        &done, &routes[3]));
         for (uint64_t qi = 0; qi < nq_run; ++qi) routes[0] += done[qi] ? 1 : 0;
@@ -4193,10 +4199,8 @@ int GpuFlatIndex::similarity_join(double min_score, int metric, uint64_t out_cap
     if (lease.status() != OK) return lease.status();
     Workspace* const ws = lease.ws;
 
-    const char* mf_env = getenv("VL_MFMA");
     float thr = INFINITY;
-    bool mfma = join_route_.load() != 1 && metric == COSINE && force_path_.load() == 0 && n_out_of_domain_ == 0 &&
-                !(mf_env && mf_env[0] == '0') && join_rows_supported((uint32_t)dim_) && n < 0x7FFFFFFFull;
+    bool mfma = gate_join(batch_gate(metric, 0, 0), join_route_.load() == 1, metric == COSINE, join_rows_supported((uint32_t)dim_));
     // "no key is provably out" (a -inf threshold): every pair is a candidate, which is not a filter's job
     if (mfma && join_key_threshold(mfma_ldb((uint32_t)dim_), min_score, &thr) == RANGE_KEYS_ALL) mfma = false;
     std::vector<JoinPair> pairs;
@@ -4264,54 +4268,22 @@ int GpuFlatIndex::search_batch_device(const double* d_queries, uint64_t nq, uint
     if (n == 0 || k == 0) return OK;
     if (!d_queries || !out_scores) return ERR_INVALID_ARG;
     const uint64_t k_eff = std::min<uint64_t>(k, n);
-    const char* mf_env = getenv("VL_MFMA");
-    const char* mf_min = getenv("VL_MFMA_MIN_BATCH");
-    const uint64_t mfma_min = mf_min && *mf_min ? (uint64_t)atoi(mf_min) : (uint64_t)MFMA_MIN_BATCH;
-    const bool direct = nq > 1 && force_path_.load() == 0 &&
-                        k_eff <= (uint64_t)KFAST_MAX && n_out_of_domain_ == 0 && !(mf_env && mf_env[0] == '0') &&
-                        nq >= mfma_min && n >= MFMA_MIN_ROWS && mfma_scan_supported((uint32_t)dim_, metric);
-    if (!direct) {
+    if (!gate_topk(batch_gate(metric, nq, k_eff))) {
         lk.unlock();
         return via_host();
     }
-    std::vector<uint8_t> done(nq, 0);
-    {
-        WsLease lease(this, /*sync_always=*/true);
-        if (lease.status() != OK) return lease.status();
-        VL_TRY(search_batch_mfma(lease.ws, nullptr, d_queries, nq, k, k_eff, metric, out_pos, out_ids, out_scores, out_n, &done));
-    }
-    set_last_path(PATH_FAST);
     // what the filter could not certify (ties, candidate overflow, a query outside the fast-path domain): those queries
-    // go to the host and through search_batch(), results scattered back
-    std::vector<uint64_t> left;
-    for (uint64_t qi = 0; qi < nq; ++qi)
-        if (!done[qi]) left.push_back(qi);
-    if (left.empty()) return OK;
-    const uint64_t m = left.size();
-    std::vector<double> hq;
-    std::vector<uint64_t> t_pos, t_ids, t_n;
-    std::vector<double> t_sc;
-    try {
-        hq.resize(m * dim_);
-        t_pos.resize(m * k_eff);
-        t_ids.resize(m * k_eff);
-        t_sc.resize(m * k_eff);
-        t_n.resize(m);
-    } catch (const std::bad_alloc&) {
-        set_last_error("out of host memory answering the queries the MFMA filter could not certify");
-        return ERR_OOM;
-    }
-    for (uint64_t i = 0; i < m; ++i)
-        VL_HIP(hipMemcpy(hq.data() + i * dim_, d_queries + left[i] * dim_, dim_ * sizeof(double), hipMemcpyDeviceToHost));
-    VL_TRY(search_batch_locked(hq.data(), m, dim_, k_eff, metric, t_pos.data(), t_ids.data(), t_sc.data(), t_n.data()));  // still under the caller's shared lock: one index state for the whole batch
-    for (uint64_t i = 0; i < m; ++i) {
-        const uint64_t qi = left[i];
-        for (uint64_t j = 0; j < t_n[i]; ++j) {
-            if (out_pos) out_pos[qi * k + j] = t_pos[i * k_eff + j];
-            if (out_ids) out_ids[qi * k + j] = t_ids[i * k_eff + j];
-            out_scores[qi * k + j] = t_sc[i * k_eff + j];
+    // go to the host and through search_batch_locked, still under this call's shared lock; results scattered back
+    Redone t;
+    VL_TRY(pass_then_redo({d_queries, true, nq, k, k_eff, metric, out_pos, out_ids, out_scores, out_n}, k_eff, &t));
+    for (uint64_t i = 0; i < t.left.size(); ++i) {
+        const uint64_t qi = t.left[i];
+        for (uint64_t j = 0; j < t.n[i]; ++j) {
+            if (out_pos) out_pos[qi * k + j] = t.pos[i * k_eff + j];
+            if (out_ids) out_ids[qi * k + j] = t.ids[i * k_eff + j];
+            out_scores[qi * k + j] = t.scores[i * k_eff + j];
         }
-        out_n[qi] = t_n[i];
+        out_n[qi] = t.n[i];
     }
     return OK;
 }

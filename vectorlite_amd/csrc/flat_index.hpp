@@ -16,10 +16,12 @@
 #include <shared_mutex>
 #include <string>
 #include <unordered_map>
+#include <variant>
 #include <vector>
 
 #include "rwlock.hpp"
 #include "attr_plan.hpp"
+#include "batch_gate.hpp"
 #include "coalescer.hpp"
 #include "group_plan.hpp"
 #include "join.hpp"
@@ -692,42 +694,81 @@ private:
     int ensure_mfma_scratch(Workspace* ws) const;
     int search_batch_locked(const double* queries, uint64_t nq, uint64_t q_len, uint64_t k, int metric, uint64_t* out_pos,
                             uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;  // mu_ held (shared)
-    // Per-query descriptor of a masked batch (exclusion tokens): sequence query j is the caller's
-    // query qidx[j] (host queries only) under the keep bitmap keep[j] (a device pointer), which keeps m[j] > 0 rows; it asks
-    // for k[j] = min(k, m[j]) rows.  Outputs and `done` are indexed by j, at stride k.
+    // The masked batch's descriptor (exclusion tokens), outputs and `done` indexed by sequence query j.
+    // Per query: j is the caller's query qidx[j] under the keep bitmap keep[j] (a device pointer), which keeps m[j] > 0 rows;
+    // it asks for k[j] = min(k, m[j]) rows.  Uniform (qidx == nullptr): every query j is the caller's query j, and keep, m
+    // and k hold one entry for all of them.
     struct MaskedQueries {
         const uint32_t* qidx;
         const unsigned long long* const* keep;
         const uint32_t* m;
         const uint32_t* k;
+        uint64_t at(uint64_t j) const { return qidx ? j : 0; }  // the entry of keep, m and k that query j reads
     };
-    // A batched grouped search riding on the sequence pipeline: k_batch_rank_collapse takes the
-    // rank / emit launch's place and settled queries are unpacked as (group key, id, score) rows, out_stride apart.  S has m
-    // rows: every row of the index (masked == nullptr) or the rows under the one bitmap every query of `masked` names.
-    // Host queries only; out_pos / out_n / done as ever, out_ids and out_scores at stride out_stride like out_keys.
-    struct GroupedReq {
+    // What the sequence pipeline does behind the candidate pass, one per request.  std::monostate, top-k: the rescoring and
+    // the rank / emit launch, (position, id, score) rows.  A ShardRecordSink: the same, written into a row shard's exchange
+    // record on the device as well.  Grouped (section 26): k_batch_rank_collapse in the rank / emit launch's place, (group
+    // key, id, score) rows.  Mmr (section 27): k_mmr_batch_rank and k_mmr_batch_select over the request's k_eff =
+    // min(fetch_k, m) <= KFAST_MAX candidates, (id, score) rows in selection order, k_out = min(k, k_eff, stride) >= 1 of
+    // them.  S, for the last two, has m rows: every row of the index (no MaskedQueries) or the rows under its one bitmap.
+    struct GroupedTail {
         const GroupTable* table;
-        uint64_t m;
-        uint64_t out_stride;
         uint64_t* out_keys;
     };
-    // A batched diversified search riding on the sequence pipeline: k_mmr_batch_rank and
-    // k_mmr_batch_select take the rank / emit launch's place and settled queries are unpacked as (id, score) rows in selection
-    // order, out_stride apart.  S has m rows: every row of the index (masked == nullptr) or the rows under the one bitmap every
-    // query of `masked` names.  n = min(fetch_k, m) <= KFAST_MAX candidates, k_out = min(k, n, out_stride) >= 1 chosen.
-    struct MmrBatchReq {
-        uint64_t m;
-        uint64_t n;
+    struct MmrTail {
         uint64_t k_out;
         double lambda;
-        uint64_t out_stride;
     };
-    int search_batch_mfma(Workspace* ws, const double* queries, const double* d_queries, uint64_t nq, uint64_t k,
-                          uint64_t k_eff, int metric, uint64_t* out_pos, uint64_t* out_ids, double* out_scores,
-                          uint64_t* out_n, std::vector<uint8_t>* done,
-                          const ShardRecordSink* sink = nullptr,  // queries on the host, or d_queries on the device
-                          const MaskedQueries* masked = nullptr, uint64_t* n_sequences = nullptr,
-                          const GroupedReq* grouped = nullptr, const MmrBatchReq* mmr = nullptr) const;
+    using MfmaTail = std::variant<std::monostate, const ShardRecordSink*, GroupedTail, MmrTail>;
+    // One call of the sequence pipeline.  Row qi of the outputs starts at qi * stride; out_pos and (but for the grouped tail)
+    // out_ids may be null.  done[qi] is set for every query answered; the caller redoes the others.
+    struct MfmaBatchReq {
+        const double* queries;
+        bool on_device;  // where `queries` lives; device queries take the top-k and record tails only, without a mask
+        uint64_t nq;
+        uint64_t stride;
+        uint64_t k_eff;
+        int metric;
+        uint64_t* out_pos;
+        uint64_t* out_ids;
+        double* out_scores;
+        uint64_t* out_n;
+        std::vector<uint8_t>* done;
+        const MaskedQueries* masked = nullptr;
+        uint64_t* n_sequences = nullptr;  // receives the launch sequences enqueued
+        MfmaTail tail;
+        uint64_t m = 0;  // the grouped and MMR tails: the rows of S
+    };
+    int search_batch_mfma(Workspace* ws, const MfmaBatchReq& req) const;
+    // The facts the MFMA routes decide on (batch_gate.hpp): the only reader of VL_MFMA and VL_MFMA_MIN_BATCH, per call.
+    BatchGate batch_gate(int metric, uint64_t nq, uint64_t k_eff) const;
+    // mu_ held.  The pass over req (its `done` is supplied here) under a lease of its own, then the queries `left` undone:
+    // gathered onto the host and answered by search_batch_locked under the caller's lock, k rows apart.  Typically none.
+    struct Redone {
+        std::vector<uint64_t> left;  // the queries redone, ascending; row i of the others is query left[i]'s
+        std::vector<uint64_t> pos;
+        std::vector<uint64_t> ids;
+        std::vector<uint64_t> n;
+        std::vector<double> scores;
+    };
+    int pass_then_redo(MfmaBatchReq req, uint64_t k, Redone* out) const;
+    // What search_grouped_batch and search_mmr_batch share (section 19, flat_index.cpp): counters, the lock, the lease, the
+    // pass and the ascending loop over what it did not settle.
+    // What a route hook decides.  empty: S holds no row, the call ends with OK.  take: the batch goes through the pass, k_eff
+    // rows a query over the m rows of S under its one bitmap `keep` (null: the whole index), with this tail.  Neither: every
+    // query runs its single body, and the other fields are not read.
+    struct BatchRoute {
+        bool empty = false;
+        bool take = false;
+        const unsigned long long* keep = nullptr;
+        uint64_t m = 0;
+        uint64_t k_eff = 0;
+        MfmaTail tail;
+    };
+    template <typename Admit, typename Route, typename Single>
+    int search_batched(std::atomic<uint64_t>* last, const std::shared_ptr<GroupTable>& t, const std::shared_ptr<IdFilter>& f,
+                       const double* queries, uint64_t nq, int metric, uint64_t k_cap, bool args_ok, uint64_t out_stride,
+                       uint64_t* out_ids, double* out_scores, uint64_t* out_n, Admit&& admit, Route&& route, Single&& single) const;
     // the locked body of search_mmr: mu_ held (shared), the filter resolved with its position list, n != 0, k_cap != 0
     int search_mmr_locked(Workspace* ws, IdFilter* f, const double* query, uint64_t k_cap, uint64_t fetch_k, double lambda,
                           int metric, uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;
