@@ -420,13 +420,16 @@ int vl_index_last_range_batch_candidates(const vl_index *h, uint64_t *max_candid
  *         row lengths, out-of-domain rows, forced paths, a -inf threshold.
  *   mfma  cosine, a row length the bf16 batch filter has a shape for (up to 768), in-domain rows, no forced path: one
  *         triangular bf16 matrix-core pass over the index's own rows finds the candidate pairs, which are rescored in the
- *         reference's f64 order, cut, and ranked on the device.  Auto takes it whenever eligible; mode 2 on an ineligible call
- *         takes the loop and says so in vl_index_last_join.  The pass runs over ranges of column panels (128 rows; 96 for
+ *         reference's f64 order, cut, and ranked on the device.  Auto takes it whenever eligible.  Mode 2 also takes it for
+ *         Euclidean and dot-product calls under the same conditions (the same pass with a per-pair test on the two rows'
+ *         norms, and a min_score that leaves something to filter: above 0 for Euclidean, not -inf for dot); auto keeps those
+ *         two metrics on the loop.  Mode 2 on an ineligible call (Manhattan, an unsupported row length, ...) takes the loop
+ *         and says so in vl_index_last_join.  The pass runs over ranges of column panels (128 rows; 96 for
  *         row lengths above 512) sized to its candidate buffer (2^20 pairs; VL_JOIN_CAND_CAP lowers it): a range that
  *         overflows is halved and run again, a single panel that still overflows is answered by the loop for its rows. */
 int vl_index_similarity_join(const vl_index *h, double min_score, int metric, uint64_t *out_ids_a, uint64_t *out_ids_b,
                              double *out_scores, uint64_t out_capacity, uint64_t *out_n, uint64_t *out_total);
-int vl_index_set_join_route(vl_index *h, int mode); /* 0 auto, 1 loop, 2 mfma */
+int vl_index_set_join_route(vl_index *h, int mode); /* 0 auto, 1 loop, 2 mfma (cosine, and Euclidean / dot, where eligible) */
 /* The last successful vl_index_similarity_join on this handle, six words: the route taken (1 loop, 2 mfma), column panels
  * the pass answered, panels handed back to the loop, candidate pairs the pass kept, qualifying pairs, launches of the pass. */
 int vl_index_last_join(const vl_index *h, uint64_t *out6);

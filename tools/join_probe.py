@@ -5,11 +5,14 @@ alternated call by call, the median wall ms of
   (c) search_range_batch_arrays answering the first --ref-queries stored rows as external queries over the same rows with
       the same threshold -- k_mfma_rows' launch; scaled by rows / ref-queries it is the yardstick for k_join_rows, which
       does half the multiply-adds and stages no queries,
-with last_join's counts.  Median of --repeats alternated repeats of --calls calls; "spread" = (max - min) of the (a) repeat
-medians over their median.  One JSON line per size on stdout and in profiles/join_<n>x<dim>.jsonl.  Per-kernel times: run
+with last_join's counts.  --metric cosine | euclidean | dot picks the metric of all three (Euclidean and dot reach the pass
+only through the mfma route; on unit rows the planted pairs score ~0.76 and ~0.95 there, so --min-score defaults to 0.75
+for Euclidean and 0.9 otherwise).  Median of --repeats alternated repeats of --calls calls; "spread" = (max - min) of the (a) repeat
+medians over their median.  One JSON line per size on stdout and in profiles/join_<n>x<dim>.jsonl
+(join_<metric>_<n>x<dim>.jsonl for Euclidean and dot).  Per-kernel times: run
 `rocprofv3 --kernel-trace --stats -- python tools/join_probe.py --trace-calls 3` (no counters in that run).
 
-    python tools/join_probe.py [--rows 100000,1000000] [--dim 384] [--min-score 0.9] [--repeats 3] [--calls 3]
+    python tools/join_probe.py [--rows 100000,1000000] [--dim 384] [--metric cosine] [--min-score 0.9] [--repeats 3] [--calls 3]
 """
 import argparse
 import json
@@ -27,7 +30,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", default="100000,1000000")
     ap.add_argument("--dim", type=int, default=384)
-    ap.add_argument("--min-score", type=float, default=0.9)
+    ap.add_argument("--metric", choices=["cosine", "euclidean", "dot"], default="cosine")
+    ap.add_argument("--min-score", type=float, default=None)
     ap.add_argument("--planted", type=int, default=1000, help="near-duplicate pairs planted at cosine ~0.95")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--calls", type=int, default=3)
@@ -38,6 +42,9 @@ def main():
 
     import vectorlite_amd as V
 
+    metric = {"cosine": 0, "euclidean": 1, "dot": 3}[args.metric]
+    if args.min_score is None:
+        args.min_score = 0.75 if args.metric == "euclidean" else 0.9
     dim = args.dim
     for n in [int(r) for r in args.rows.split(",")]:
         rng = np.random.default_rng(n)
@@ -53,7 +60,7 @@ def main():
         def run(route):
             idx.set_join_route(route)
             t0 = time.perf_counter()
-            out = idx.similarity_join_arrays(args.min_score, 0, limit=4096)
+            out = idx.similarity_join_arrays(args.min_score, metric, limit=4096)
             return time.perf_counter() - t0, out[3], idx.last_join()
 
         nq = min(args.ref_queries, n)
@@ -61,7 +68,7 @@ def main():
 
         def run_ref():
             t0 = time.perf_counter()
-            idx.search_range_batch_arrays(ref_q, args.min_score, 0, limit=16)
+            idx.search_range_batch_arrays(ref_q, args.min_score, metric, limit=16)
             return time.perf_counter() - t0
 
         if args.trace_calls:
@@ -86,7 +93,7 @@ def main():
             if loop:
                 b_meds.append(float(np.median(tb)) * 1e3)
         a, c = float(np.median(a_meds)), float(np.median(c_meds))
-        rec = {"what": "similarity_join", "rows": n, "dim": dim, "min_score": args.min_score, "qualifying_pairs": total,
+        rec = {"what": "similarity_join", "metric": args.metric, "rows": n, "dim": dim, "min_score": args.min_score, "qualifying_pairs": total,
                "last_join": lj, "a_mfma_ms": round(a, 3), "a_medians": [round(x, 3) for x in a_meds],
                "a_spread": round((max(a_meds) - min(a_meds)) / a, 4), "ref_queries": nq, "c_range_batch_ms": round(c, 3),
                "c_scaled_to_n_queries_ms": round(c * n / nq, 3)}
@@ -96,7 +103,8 @@ def main():
                         "loop_total_matches": loop_total == total})
         line = json.dumps(rec)
         print(line, flush=True)
-        path = os.path.join(ROOT, "profiles", f"join_{n}x{dim}.jsonl")
+        name = f"join_{n}x{dim}.jsonl" if metric == 0 else f"join_{args.metric}_{n}x{dim}.jsonl"
+        path = os.path.join(ROOT, "profiles", name)
         os.makedirs(os.path.dirname(path), exist_ok=True)
         with open(path, "w") as fh:
             fh.write(line + "\n")

@@ -1010,7 +1010,9 @@ class FlatIndex:
         return list(zip(a.tolist(), b.tolist(), s.tolist()))
 
     def set_join_route(self, mode: str) -> None:
-        """'auto' (the MFMA pass whenever the call is eligible), 'loop', 'mfma' (vl_index_set_join_route)."""
+        """'auto' (the MFMA pass whenever a cosine call is eligible; Euclidean and dot stay on the loop), 'loop', 'mfma' (the
+        pass for cosine, Euclidean and dot calls that are eligible; any other call takes the loop and last_join says so)
+        (vl_index_set_join_route)."""
         _set_join_route(self._L, self._h, mode)
 
     def last_join(self) -> Dict[str, int]:

@@ -63,8 +63,9 @@ inline bool gate_range(const BatchGate& g, bool filtered)
     return !filtered && g.nq >= g.lim.min_batch && gate_core(g) && g.rows_kernel;
 }
 
-// The self-join: its own kernel, so join_rows_supported(dim) in mfma_scan_supported's place; cosine only; positions travel
-// as 31-bit halves of a pair; one call is one pass, so no minimum batch.
+// The self-join: its own kernel, so join_rows_supported(dim, metric) in mfma_scan_supported's place; `cosine` = the metric
+// has a pass on the call's route (cosine always; Euclidean and dot when the route is mfma); positions travel as 31-bit
+// halves of a pair; one call is one pass, so no minimum batch.
 inline bool gate_join(const BatchGate& g, bool route_loop, bool cosine, bool join_rows_supported)
 {
     return !route_loop && cosine && g.forced_path == 0 && g.out_of_domain == 0 && !g.env_off && join_rows_supported &&

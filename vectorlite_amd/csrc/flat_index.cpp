@@ -4090,8 +4090,8 @@ int GpuFlatIndex::join_loop_rows(Workspace* ws, uint64_t row0, uint64_t row1, do
     return OK;
 }
 
-int GpuFlatIndex::join_mfma(Workspace* ws, double min_score, float thr, uint64_t out_capacity, std::vector<JoinPair>* pairs,
-                            uint64_t* total, uint64_t* stats) const
+int GpuFlatIndex::join_mfma(Workspace* ws, double min_score, int metric, float thr, uint64_t out_capacity,
+                            std::vector<JoinPair>* pairs, uint64_t* total, uint64_t* stats) const
 {
     const uint64_t n = ids_.size();
     VL_TRY(ensure_bf16_slab(true));
@@ -4112,8 +4112,8 @@ int GpuFlatIndex::join_mfma(Workspace* ws, double min_score, float thr, uint64_t
         while (!todo.empty()) {
             const auto [y0, y1] = todo.back();
             todo.pop_back();
-            VL_HIP(launch_join_rows(st, d_slab16f_, n, (uint32_t)dim_, y0, y1, thr, ws->jn_cand, ws->jn_cnt, cap));
-            VL_HIP(launch_join_rescore_cut(st, ws->jn_cand, ws->jn_cnt, cap, d_master_, (uint32_t)dim_, n, min_score, ws->jn_keys,
+            VL_HIP(launch_join_rows(st, metric, d_slab16f_, d_norm16_, n, (uint32_t)dim_, y0, y1, thr, ws->jn_cand, ws->jn_cnt, cap));
+            VL_HIP(launch_join_rescore_cut(st, metric, ws->jn_cand, ws->jn_cnt, cap, d_master_, (uint32_t)dim_, n, min_score, ws->jn_keys,
                                            ws->jn_pay, store ? ws->jn_sv_cap : 0, ws->jn_ctr));
             VL_HIP(hipMemcpyAsync(ws->jn_h, ws->jn_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             VL_HIP(hipStreamSynchronize(st));
@@ -4168,7 +4168,7 @@ int GpuFlatIndex::join_mfma(Workspace* ws, double min_score, float thr, uint64_t
     // panels the pass could not hold: the loop answers their rows, each keeping its partners in FRONT of it (the pairs whose
     // column lies in the panel; scores are symmetric bit for bit)
     for (uint32_t y : handed)
-        VL_TRY(join_loop_rows(ws, (uint64_t)y * plan.qpb, std::min<uint64_t>(n, (uint64_t)(y + 1) * plan.qpb), min_score, COSINE, true,
+        VL_TRY(join_loop_rows(ws, (uint64_t)y * plan.qpb, std::min<uint64_t>(n, (uint64_t)(y + 1) * plan.qpb), min_score, metric, true,
                               store ? pairs : nullptr, total));
     return OK;
 }
@@ -4200,15 +4200,25 @@ int GpuFlatIndex::similarity_join(double min_score, int metric, uint64_t out_cap
     Workspace* const ws = lease.ws;
 
     float thr = INFINITY;
-    bool mfma = gate_join(batch_gate(metric, 0, 0), join_route_.load() == 1, metric == COSINE, join_rows_supported((uint32_t)dim_));
-    // "no key is provably out" (a -inf threshold): every pair is a candidate, which is not a filter's job
-    if (mfma && join_key_threshold(mfma_ldb((uint32_t)dim_), min_score, &thr) == RANGE_KEYS_ALL) mfma = false;
+    // this metric has a pass on this route: cosine always; Euclidean and dot only when the caller asked for it (mode 2) --
+    // `auto` keeps them on the loop until the pass has been measured against it
+    const int route = join_route_.load();
+    const bool has_pass = metric == COSINE || (route == 2 && (metric == EUCLIDEAN || metric == DOT));
+    bool mfma = gate_join(batch_gate(metric, 0, 0), route == 1, has_pass, join_rows_supported((uint32_t)dim_, metric));
+    // "no key is provably out" (a -inf threshold; for the per-pair metrics, for the pair of largest norms): every pair is a
+    // candidate, which is not a filter's job
+    if (mfma) {
+        const uint32_t ldb = mfma_ldb((uint32_t)dim_);
+        const RangeKeys keys = metric == COSINE ? join_key_threshold(ldb, min_score, &thr)
+                                                : join_pair_threshold(metric, ldb, max_row_norm_, min_score, &thr);
+        if (keys == RANGE_KEYS_ALL) mfma = false;
+    }
     std::vector<JoinPair> pairs;
     uint64_t total = 0;
     try {
         if (mfma) {
             stats[0] = 2;
-            VL_TRY(join_mfma(ws, min_score, thr, out_capacity, &pairs, &total, stats));
+            VL_TRY(join_mfma(ws, min_score, metric, thr, out_capacity, &pairs, &total, stats));
         } else {
             VL_TRY(join_loop_rows(ws, 0, n, min_score, metric, false, out_capacity ? &pairs : nullptr, &total));
         }

@@ -686,8 +686,8 @@ private:
     };
     int join_loop_rows(Workspace* ws, uint64_t row0, uint64_t row1, double min_score, int metric, bool lower,
                        std::vector<JoinPair>* pairs, uint64_t* count) const;  // lower: the partners in FRONT of each row instead
-    int join_mfma(Workspace* ws, double min_score, float thr, uint64_t out_capacity, std::vector<JoinPair>* pairs, uint64_t* total,
-                  uint64_t* stats) const;
+    int join_mfma(Workspace* ws, double min_score, int metric, float thr, uint64_t out_capacity, std::vector<JoinPair>* pairs,
+                  uint64_t* total, uint64_t* stats) const;
     int wait_result(Workspace* ws, uint32_t seq) const;
     int ensure_i8_slab() const;  // lazily builds the int8 copy the single-query int8 filter streams
     int ensure_bf16_slab(bool frag_major) const;  // lazily builds the bf16 slab (row-major, or MFMA fragment order) a filter streams

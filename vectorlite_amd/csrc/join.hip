@@ -1,7 +1,7 @@
 // join.hip -- the similarity self-join's candidate pass: a triangular bf16 MFMA pass in which both
 // operands are blocks of the index's own fragment-major slab.
 //
-// k_join_rows<KSTEPS> is a symmetric rank-k update on the matrix cores (v_mfma_f32_16x16x32_bf16):
+// k_join_rows<KSTEPS, METRIC> is a symmetric rank-k update on the matrix cores (v_mfma_f32_16x16x32_bf16):
 //   B = a column PANEL of QPB consecutive stored rows (128; 96 at stride 768), copied once per stretch into LDS as it lies
 //       in the slab.  For the 16x16x32 shape lane (c16, kg) of a B fragment holds column c16, k-group kg -- the piece order
 //       of an A fragment -- so a 1 KB slab chunk IS a B fragment: no re-layout, no row padding, one ds_read_b128 per lane
@@ -11,7 +11,8 @@
 //       wave's next block, so a load has a whole block's MFMAs to land.
 //   C = a 32 x QPB tile per wave: every A fragment feeds QPB / 16 MFMAs, every B fragment two.
 // join_plan.hpp deals the (panel, block) units to the workgroups.  One scalar threshold serves the whole launch: the
-// epilogue is a max tree over the tile, one compare and one branch; the candidate code behind it keeps pos_a < pos_b <
+// epilogue is a max tree over the tile (cosine: over the sums; Euclidean and dot: over join_pair_key of each sum and the
+// two rows' norms), one compare and one branch; the candidate code behind it keeps pos_a < pos_b <
 // n_rows (which drops the mirrored half of a diagonal unit, the self pair and the rows past the end) and appends
 // (pos_a, pos_b, key) to the wave's LDS ring; a flush reserves its entries in the global buffer with ONE returning atomic.
 #include "join.hpp"
@@ -39,10 +40,13 @@ __device__ __forceinline__ float jmax3(float a, float b, float c)
     return __builtin_fmaxf(__builtin_fmaxf(a, b), c);  // folds to v_max3_f32
 }
 
-template <int KSTEPS>
+// METRIC: COSINE compares the key itself.  DOT and EUCLIDEAN compare join_pair_key (join_plan.hpp) of the key and the row's
+// and the column's f32 norms: row_norm is norm16, e32 is join_pair_e32.
+template <int KSTEPS, int METRIC>
 __global__ __launch_bounds__(JOIN_NW * 64) void k_join_rows(const unsigned char* __restrict__ slab, uint32_t n_rows, uint32_t y0,
                                                             uint32_t y1, float thr, JoinCand* __restrict__ cand,
-                                                            uint32_t* __restrict__ cnt, uint32_t cap)
+                                                            uint32_t* __restrict__ cnt, uint32_t cap,
+                                                            const float* __restrict__ row_norm, float e32)
 {
     constexpr int LDB = KSTEPS * 16;
     constexpr int ROW_BYTES = LDB * 2;
@@ -52,14 +56,17 @@ __global__ __launch_bounds__(JOIN_NW * 64) void k_join_rows(const unsigned char*
     constexpr int PH = KS32 > 12 ? 4 : 1;                  // K phases: 16 = 4 x 4 (stride 512), 24 = 4 x 6 (stride 768)
     constexpr int KSP = KS32 / PH;                         // A fragments a wave holds per 16-row half block
     constexpr int GROUP_BYTES = 16 * ROW_BYTES;            // one 16-row group of the slab: KS32 chunks of 1 KB
+    constexpr bool PAIR = METRIC != COSINE;                // per-pair scalars in the epilogue
+    constexpr int COL_BYTES = PAIR ? QPB * 4 : 0;          // the panel rows' norms
     static_assert(KS32 % PH == 0 && QPB % 32 == 0, "whole K phases; panels are whole row blocks");
-    static_assert(QPB * ROW_BYTES + JOIN_NW * JOIN_SEG * 12 <= 160 * 1024, "panel and rings fit the LDS");
+    static_assert(QPB * ROW_BYTES + JOIN_NW * JOIN_SEG * 12 + COL_BYTES <= 160 * 1024, "panel, rings and column scalars fit the LDS");
 
-    __shared__ __attribute__((aligned(16))) unsigned char lds[QPB * ROW_BYTES + JOIN_NW * JOIN_SEG * 12];
+    __shared__ __attribute__((aligned(16))) unsigned char lds[QPB * ROW_BYTES + JOIN_NW * JOIN_SEG * 12 + COL_BYTES];
     unsigned char* panel = lds;                                                       // [QB][KS32] chunks of 1 KB
     uint32_t* ring_a = reinterpret_cast<uint32_t*>(lds + (size_t)QPB * ROW_BYTES);    // [NW][SEG]
     uint32_t* ring_b = ring_a + JOIN_NW * JOIN_SEG;
     float* ring_key = reinterpret_cast<float*>(ring_b + JOIN_NW * JOIN_SEG);
+    float* col_n = ring_key + JOIN_NW * JOIN_SEG;  // [QPB] (PAIR)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -129,6 +136,10 @@ __global__ __launch_bounds__(JOIN_NW * 64) void k_join_rows(const unsigned char*
                 if (g0 + (uint32_t)(c / GROUP_PIECES) < n_groups) v = *reinterpret_cast<const u32x4*>(src + (size_t)c * 16);
                 *reinterpret_cast<u32x4*>(panel + (size_t)c * 16) = v;
             }
+            if (PAIR && tid < QPB) {  // the panel rows' norms next to it; rows past the end are zero rows
+                const uint32_t pos = col0 + (uint32_t)tid;
+                col_n[tid] = pos < n_rows ? row_norm[pos] : 0.f;
+            }
         }
         __syncthreads();
 
@@ -137,6 +148,13 @@ __global__ __launch_bounds__(JOIN_NW * 64) void k_join_rows(const unsigned char*
             const unsigned char* pn = a_ptr(nxt);
             const unsigned char* pc = a_ptr(b);
             const uint32_t row0 = b * JOIN_BLOCK_ROWS;
+            // the norms of this lane's rows 16 rb + 4 kg + jj, requested in front of the MFMAs (the array is allocated in whole
+            // 64-row tiles; entries past the last row are never part of a kept pair)
+            f32x4 ra[2];
+            if (PAIR) {
+#pragma unroll
+                for (int rb = 0; rb < 2; ++rb) ra[rb] = *reinterpret_cast<const f32x4*>(row_norm + row0 + 16 * rb + 4 * kg);
+            }
             f32x4 acc[2][QB];
 #pragma unroll
             for (int rb = 0; rb < 2; ++rb)
@@ -161,39 +179,82 @@ __global__ __launch_bounds__(JOIN_NW * 64) void k_join_rows(const unsigned char*
                 }
             }
             // ---- epilogue: C layout of a 16x16 block: column = lane & 15 (panel row), row = 4 (lane >> 4) + reg ----
-            float m = -INFINITY;
-#pragma unroll
-            for (int j = 0; j < QB; ++j)
-#pragma unroll
-                for (int rb = 0; rb < 2; ++rb) {
-                    m = jmax3(m, acc[rb][j][0], acc[rb][j][1]);
-                    m = jmax3(m, acc[rb][j][2], acc[rb][j][3]);
+            auto append = [&](bool is_cand, uint32_t pos_a, uint32_t pos_b, float key) {  // wave-uniform call
+                const unsigned long long mk = __builtin_amdgcn_ballot_w64(is_cand);
+                if (mk == 0ull) return;
+                if (my_cnt + 64u > (uint32_t)JOIN_SEG) flush_wave();
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+                if (is_cand) {
+                    const uint32_t e = my_cnt + rank;
+                    my_a[e] = pos_a;
+                    my_b[e] = pos_b;
+                    my_key[e] = key;
                 }
-            if (__builtin_amdgcn_ballot_w64(m >= thr) == 0ull) continue;
-            // rare off the diagonal; only THIS wave pays for it
+                my_cnt += (uint32_t)__popcll(mk);
+            };
+            if constexpr (!PAIR) {
+                float m = -INFINITY;
 #pragma unroll
-            for (int j = 0; j < QB; ++j) {
-                const uint32_t pos_b = col0 + (uint32_t)(16 * j + c16);
+                for (int j = 0; j < QB; ++j)
 #pragma unroll
-                for (int rb = 0; rb < 2; ++rb) {
-                    const float mrb = fmaxf(fmaxf(acc[rb][j][0], acc[rb][j][1]), fmaxf(acc[rb][j][2], acc[rb][j][3]));
-                    if (__builtin_amdgcn_ballot_w64(mrb >= thr) == 0ull) continue;  // wave-uniform
+                    for (int rb = 0; rb < 2; ++rb) {
+                        m = jmax3(m, acc[rb][j][0], acc[rb][j][1]);
+                        m = jmax3(m, acc[rb][j][2], acc[rb][j][3]);
+                    }
+                if (__builtin_amdgcn_ballot_w64(m >= thr) == 0ull) continue;
+                // rare off the diagonal; only THIS wave pays for it
 #pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        const float key = acc[rb][j][jj];
-                        const uint32_t pos_a = row0 + (uint32_t)(16 * rb + 4 * kg + jj);
-                        const bool is_cand = key >= thr && pos_a < pos_b && pos_b < n_rows;
-                        const unsigned long long mk = __builtin_amdgcn_ballot_w64(is_cand);
-                        if (mk == 0ull) continue;  // wave-uniform
-                        if (my_cnt + 64u > (uint32_t)JOIN_SEG) flush_wave();
-                        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-                        if (is_cand) {
-                            const uint32_t e = my_cnt + rank;
-                            my_a[e] = pos_a;
-                            my_b[e] = pos_b;
-                            my_key[e] = key;
+                for (int j = 0; j < QB; ++j) {
+                    const uint32_t pos_b = col0 + (uint32_t)(16 * j + c16);
+#pragma unroll
+                    for (int rb = 0; rb < 2; ++rb) {
+                        const float mrb = fmaxf(fmaxf(acc[rb][j][0], acc[rb][j][1]), fmaxf(acc[rb][j][2], acc[rb][j][3]));
+                        if (__builtin_amdgcn_ballot_w64(mrb >= thr) == 0ull) continue;  // wave-uniform
+#pragma unroll
+                        for (int jj = 0; jj < 4; ++jj) {
+                            const float key = acc[rb][j][jj];
+                            const uint32_t pos_a = row0 + (uint32_t)(16 * rb + 4 * kg + jj);
+                            append(key >= thr && pos_a < pos_b && pos_b < n_rows, pos_a, pos_b, key);
                         }
-                        my_cnt += (uint32_t)__popcll(mk);
+                    }
+                }
+            } else {
+                // The transformed key of row (rb, jj) against column c16 of block j.  The column's scalars come from the LDS
+                // where they are used (one ds_read per 8 keys): QB or 2 QB more registers held across the MFMAs do not fit
+                // next to the accumulators and the A fragments at stride 384.  The common path keeps only the maximum; the
+                // candidate path forms the keys again -- from a copy of e32 the compiler cannot see through, or it would keep
+                // the common path's 64 keys for it -- so no key array is live across the branch.
+                auto pair_key = [&](int rb, int j, int jj, float e, float nbc) -> float {
+                    return join_pair_key<METRIC>(acc[rb][j][jj], e, ra[rb][jj], nbc);
+                };
+                float m = -INFINITY;
+#pragma unroll
+                for (int j = 0; j < QB; ++j) {
+                    const float nbc = col_n[16 * j + c16];
+#pragma unroll
+                    for (int rb = 0; rb < 2; ++rb) {
+                        m = jmax3(m, pair_key(rb, j, 0, e32, nbc), pair_key(rb, j, 1, e32, nbc));
+                        m = jmax3(m, pair_key(rb, j, 2, e32, nbc), pair_key(rb, j, 3, e32, nbc));
+                    }
+                }
+                if (__builtin_amdgcn_ballot_w64(m >= thr) == 0ull) continue;
+                float e_again = e32;
+                asm volatile("" : "+s"(e_again));
+#pragma unroll
+                for (int j = 0; j < QB; ++j) {
+                    const uint32_t pos_b = col0 + (uint32_t)(16 * j + c16);
+                    const float nbc = col_n[16 * j + c16];
+#pragma unroll
+                    for (int rb = 0; rb < 2; ++rb) {
+                        const float k0 = pair_key(rb, j, 0, e_again, nbc), k1 = pair_key(rb, j, 1, e_again, nbc);
+                        const float k2 = pair_key(rb, j, 2, e_again, nbc), k3 = pair_key(rb, j, 3, e_again, nbc);
+                        if (__builtin_amdgcn_ballot_w64(fmaxf(fmaxf(k0, k1), fmaxf(k2, k3)) >= thr) == 0ull) continue;  // wave-uniform
+#pragma unroll
+                        for (int jj = 0; jj < 4; ++jj) {
+                            const float tk = jj == 0 ? k0 : (jj == 1 ? k1 : (jj == 2 ? k2 : k3));
+                            const uint32_t pos_a = row0 + (uint32_t)(16 * rb + 4 * kg + jj);
+                            append(tk >= thr && pos_a < pos_b && pos_b < n_rows, pos_a, pos_b, acc[rb][j][jj]);
+                        }
                     }
                 }
             }
@@ -208,28 +269,53 @@ __global__ void k_join_clear(uint32_t* __restrict__ cnt)
     if (threadIdx.x == 0) *cnt = 0u;
 }
 
-template <int KSTEPS>
-hipError_t launch_rows(hipStream_t s, const void* slab, uint32_t n_rows, uint32_t y0, uint32_t y1, float thr, JoinCand* cand,
-                       uint32_t* cnt, uint32_t cap, uint32_t grid)
+struct RowsArgs {
+    const void* slab;
+    uint32_t n_rows, y0, y1;
+    float thr;
+    JoinCand* cand;
+    uint32_t* cnt;
+    uint32_t cap, grid;
+    const float* row_norm;
+    float e32;
+};
+
+template <int KSTEPS, int METRIC>
+hipError_t launch_rows(hipStream_t s, const RowsArgs& a)
 {
-    hipLaunchKernelGGL(k_join_clear, dim3(1), dim3(64), 0, s, cnt);
-    hipLaunchKernelGGL((k_join_rows<KSTEPS>), dim3(grid), dim3(JOIN_NW * 64), 0, s, reinterpret_cast<const unsigned char*>(slab),
-                       n_rows, y0, y1, thr, cand, cnt, cap);
+    hipLaunchKernelGGL(k_join_clear, dim3(1), dim3(64), 0, s, a.cnt);
+    hipLaunchKernelGGL((k_join_rows<KSTEPS, METRIC>), dim3(a.grid), dim3(JOIN_NW * 64), 0, s,
+                       reinterpret_cast<const unsigned char*>(a.slab), a.n_rows, a.y0, a.y1, a.thr, a.cand, a.cnt, a.cap, a.row_norm,
+                       a.e32);
     return hipGetLastError();
+}
+
+template <int METRIC>
+hipError_t launch_rows_ldb(hipStream_t s, uint32_t ldb, const RowsArgs& a)
+{
+    switch (ldb) {
+    case 128: return launch_rows<8, METRIC>(s, a);
+    case 256: return launch_rows<16, METRIC>(s, a);
+    case 384: return launch_rows<24, METRIC>(s, a);
+    case 512: return launch_rows<32, METRIC>(s, a);
+    default: return launch_rows<48, METRIC>(s, a);
+    }
 }
 
 }  // namespace
 
-bool join_rows_supported(uint32_t dim)
+bool join_rows_supported(uint32_t dim, int metric)
 {
     const uint32_t ldb = mfma_ldb(dim);
+    if (metric != COSINE && metric != EUCLIDEAN && metric != DOT) return false;
     return dim >= 1 && (ldb == 128 || ldb == 256 || ldb == 384 || ldb == 512 || ldb == 768) && mfma_rows_kernel(dim);
 }
 
-hipError_t launch_join_rows(hipStream_t s, const void* slab_frag, uint64_t n_rows, uint32_t dim, uint32_t y0, uint32_t y1, float thr,
-                            JoinCand* cand, uint32_t* cnt, uint32_t cap, JoinLaunchInfo* info)
+hipError_t launch_join_rows(hipStream_t s, int metric, const void* slab_frag, const float* row_norm, uint64_t n_rows, uint32_t dim,
+                            uint32_t y0, uint32_t y1, float thr, JoinCand* cand, uint32_t* cnt, uint32_t cap, JoinLaunchInfo* info)
 {
-    if (!join_rows_supported(dim) || n_rows < 2 || n_rows >= 0x7FFFFFFFull || cap == 0) return hipErrorInvalidValue;
+    if (!join_rows_supported(dim, metric) || n_rows < 2 || n_rows >= 0x7FFFFFFFull || cap == 0) return hipErrorInvalidValue;
+    if (metric != COSINE && !row_norm) return hipErrorInvalidValue;
     const uint32_t ldb = mfma_ldb(dim);
     const JoinPlan plan = join_plan((uint32_t)n_rows, join_qpb(ldb));
     if (y0 >= y1 || y1 > plan.n_panels) return hipErrorInvalidValue;
@@ -244,12 +330,11 @@ hipError_t launch_join_rows(hipStream_t s, const void* slab_frag, uint64_t n_row
         info->grid = (int)grid;
         info->units = units;
     }
-    switch (ldb) {
-    case 128: return launch_rows<8>(s, slab_frag, (uint32_t)n_rows, y0, y1, thr, cand, cnt, cap, grid);
-    case 256: return launch_rows<16>(s, slab_frag, (uint32_t)n_rows, y0, y1, thr, cand, cnt, cap, grid);
-    case 384: return launch_rows<24>(s, slab_frag, (uint32_t)n_rows, y0, y1, thr, cand, cnt, cap, grid);
-    case 512: return launch_rows<32>(s, slab_frag, (uint32_t)n_rows, y0, y1, thr, cand, cnt, cap, grid);
-    default: return launch_rows<48>(s, slab_frag, (uint32_t)n_rows, y0, y1, thr, cand, cnt, cap, grid);
+    const RowsArgs a{slab_frag, (uint32_t)n_rows, y0, y1, thr, cand, cnt, cap, grid, row_norm, join_pair_e32(ldb)};
+    switch (metric) {
+    case COSINE: return launch_rows_ldb<COSINE>(s, ldb, a);
+    case EUCLIDEAN: return launch_rows_ldb<EUCLIDEAN>(s, ldb, a);
+    default: return launch_rows_ldb<DOT>(s, ldb, a);
     }
 }
 

@@ -113,4 +113,92 @@ inline RangeKeys join_key_threshold(uint32_t n, double min_score, float* thr)
     return range_key_threshold(BOUND_COSINE, n, 1.0, 1.0, min_score - JOIN_SELF_EXTRA, JOIN_IN_EXTRA, thr);
 }
 
+// ---- Euclidean and dot: a per-pair test on the same cosine key -----------------------------------------------------------
+// c = the pair's cosine key.  The real cosine of two non-zero rows is at most C(c) = c + E: join_bound_for_key's additive
+// terms (the bound on the reference's f64 cosine) plus 2e-12 for that f64 cosine's own distance from the real one
+// ((n + 4) 2^-52 < 1.8e-13) and for the f64 terms listed at join_pair_bound.  Derivation in DESIGN.md section 29.
+inline double join_pair_extra(uint32_t n)
+{
+    return join_bound_for_key(0.0f, n) + 2e-12;
+}
+
+// Upper bound on the reference's f64 score of a pair with key <= c and REAL norms na, nb; weakly increasing in c (a
+// composition of correctly rounded monotone steps, like bound_for_key).
+//   dot:        a.b <= na nb C(c); the reference's sum is within (n + 2) 2^-52 na nb of a.b (Cauchy-Schwarz on sum |x_i y_i|).
+//   Euclidean:  dist^2 >= na^2 + nb^2 - 2 na nb C(c); the reference's sum of squared differences, its sqrt and 1 / (1 + d)
+//               stay inside the (1 - 1e-12) and (1 + 1e-15) factors bound_for_key<EUCLIDEAN> uses for the same steps.
+template <int METRIC>
+inline double join_pair_bound(float c, uint32_t n, double na, double nb)
+{
+    static_assert(METRIC == BOUND_DOT || METRIC == BOUND_EUCLIDEAN, "cosine has join_bound_for_key");
+    const double p = na * nb;
+    const double ab_hi = p > 0.0 ? ((double)c + join_pair_extra(n)) * p : 0.0;  // a zero row: a.b = 0 whatever the key
+    if (METRIC == BOUND_DOT) return ab_hi + ((double)n + 2.0) * 2.220446049250313e-16 * p;
+    double d2 = na * na + nb * nb - 2.0 * ab_hi;
+    if (!(d2 > 0.0)) d2 = 0.0;
+    return (1.0 / (1.0 + sqrt(d2) * (1.0 - 1e-12))) * (1.0 + 1e-15);
+}
+
+// x rounded to f32 upwards / downwards (+-inf and values beyond the f32 range included)
+inline float join_f32_up(double x)
+{
+    const float f = (float)x;
+    return (double)f < x ? ordered_to_f32(f32_to_ordered(f) + 1u) : f;
+}
+inline float join_f32_down(double x)
+{
+    const float f = (float)x;
+    return (double)f > x ? ordered_to_f32(f32_to_ordered(f) - 1u) : f;
+}
+
+// The device works in f32 on the stored norm16 = fl32(|x|), within 1.001 u of the real norm (u = 2^-24), and forms the
+// squared norms from it (3.01 u): sqnorm = fl32(|x|^2) would save 2 u of that and cost the kernel a second pair of per-row
+// arrays in registers and LDS.  Its E carries 16 u more than join_pair_extra: 1.1 u for the rounding of c + E, 4.2 u for
+// na32 * nb32 and the product with it, and for Euclidean 6.4 u for the squares, their sum and the final difference, which
+// are relative to na^2 + nb^2 <= dist^2 + 2 na nb and so split into a relative term on dist^2 (join_pair_threshold) and
+// this one.
+inline float join_pair_e32(uint32_t n)
+{
+    return join_f32_up(join_pair_extra(n) + 16.0 * 5.9604644775390625e-08);
+}
+
+// The transformed key the kernel's epilogue compares with ONE launch scalar: a pair is a candidate iff it is >= thr.
+//   dot:        an upper bound on a.b                 (c + E32) (na nb)
+//   Euclidean:  minus a lower bound on dist^2         2 (c + E32) (na nb) - (na na + nb nb)
+// Every operation is a single f32 rounding (2 w is exact, so a contracted 2 w - h is the same value; the translation
+// units that use this are compiled with -ffp-contract=off, which keeps na na + nb nb two products and a sum).
+template <int METRIC>
+VL_XCD_HD inline float join_pair_key(float c, float e32, float na, float nb)
+{
+    if (METRIC == BOUND_COSINE) return c;
+    const float w = (c + e32) * (na * nb);
+    if (METRIC == BOUND_DOT) return w;
+    return 2.0f * w - (na * na + nb * nb);
+}
+
+// The launch scalar for join_pair_key (dot or Euclidean), R = the largest row norm.  No pair whose join_pair_bound reaches
+// min_score fails `join_pair_key >= *thr`.
+//   RANGE_KEYS_ALL:  no key is provably out for the pair of largest norms (dot -inf, Euclidean min_score <= 0): not a
+//                    filter's job, *thr is not written.
+//   RANGE_KEYS_NONE: every key is provably out (Euclidean min_score > 1; dot > 0 over zero rows): *thr = +inf.
+//   dot:        thr = min_score rounded DOWN to f32 (E32's margin leaves the transformed key above the bound itself).
+//   Euclidean:  thr = -T rounded down, T = D^2 (1 + 8 u), D the largest distance whose bound reaches min_score:
+//               D = ((1 + 1e-15) / min_score - 1) / (1 - 1e-12), with 2^-50 added for the rounding of the quotient and the
+//               subtraction and a factor 1 + 1e-11 over the f64 steps of this function.
+inline RangeKeys join_pair_threshold(int metric, uint32_t n, double R, double min_score, float* thr)
+{
+    const bool dot = metric == BOUND_DOT;
+    auto bound = [&](float c) { return dot ? join_pair_bound<BOUND_DOT>(c, n, R, R) : join_pair_bound<BOUND_EUCLIDEAN>(c, n, R, R); };
+    if (bound(-INFINITY) >= min_score) return RANGE_KEYS_ALL;
+    *thr = INFINITY;
+    if (!(bound(INFINITY) >= min_score)) return RANGE_KEYS_NONE;
+    if (dot) {
+        *thr = join_f32_down(min_score);
+        return RANGE_KEYS_FROM;
+    }
+    const double D = (((1.0 + 1e-15) / min_score - 1.0) + 8.881784197001252e-16) * (1.0 + 1e-11) / (1.0 - 1e-12);
+    *thr = -join_f32_up(D * D * (1.0 + 8.0 * 5.9604644775390625e-08));
+    return RANGE_KEYS_FROM;
+}
+
 }  // namespace vl

@@ -3143,6 +3143,8 @@ hipError_t launch_range_batch_tail(hipStream_t s, int metric, const Cand32* cand
 // x y, x x, y y of a 16 x 48 tile (x = row b, y = row a, the call's "query"), then one lane per pair adds them in index order
 // -- wave 0 the `a` sums, wave 1 `b`, wave 2 `c`, each fl(acc + fl(product)) from 0.0 as Acc64<COSINE>::step does --
 // and Acc64::score() finishes.  Survivors are appended with one atomic per tile.
+// Dot and Euclidean have one sum: the tile holds x y or (x - y)^2, wave 0 adds it from Acc64's own starting value.
+template <int METRIC>
 __global__ __launch_bounds__(256) void k_join_rescore_cut(const JoinCand* __restrict__ cand, const uint32_t* __restrict__ cnt,
                                                           uint32_t cap, const double* __restrict__ master, uint32_t dim,
                                                           uint32_t n_rows, double min_score,
@@ -3165,7 +3167,9 @@ __global__ __launch_bounds__(256) void k_join_rescore_cut(const JoinCand* __rest
             sh_b[tid] = c.b < n_rows ? c.b : n_rows - 1;
         }
         __syncthreads();
-        double acc = 0.0;
+        Acc64<METRIC> A;
+        A.init();
+        double acc = wave == 0 ? A.a : 0.0;
         for (uint32_t c0 = 0; c0 < dim; c0 += RP_CH) {
             const uint32_t cw = (dim - c0) < (uint32_t)RP_CH ? (dim - c0) : (uint32_t)RP_CH;
             double x[PER], y[PER];
@@ -3183,25 +3187,35 @@ __global__ __launch_bounds__(256) void k_join_rescore_cut(const JoinCand* __rest
             for (int i = 0; i < PER; ++i) {
                 const int idx = tid + i * 256;
                 const int r = idx / RP_CH, cc = idx % RP_CH;
-                tA[r][cc] = x[i] * y[i];
-                tB[r][cc] = x[i] * x[i];
-                tC[r][cc] = y[i] * y[i];
+                if (METRIC == EUCLIDEAN) {
+                    const double d = x[i] - y[i];
+                    tA[r][cc] = d * d;
+                } else {
+                    tA[r][cc] = x[i] * y[i];
+                }
+                if (METRIC == COSINE) {
+                    tB[r][cc] = x[i] * x[i];
+                    tC[r][cc] = y[i] * y[i];
+                }
             }
             __syncthreads();
-            if (wave < 3 && lane < n_here) {
+            if (wave < (METRIC == COSINE ? 3 : 1) && lane < n_here) {
                 const double* t = wave == 0 ? &tA[lane][0] : (wave == 1 ? &tB[lane][0] : &tC[lane][0]);
                 for (uint32_t cc = 0; cc < cw; ++cc) acc += t[cc];
             }
         }
-        if (wave == 1 && lane < BF_ROWS) sum_b[lane] = acc;
-        if (wave == 2 && lane < BF_ROWS) sum_c[lane] = acc;
-        __syncthreads();
+        if (METRIC == COSINE) {
+            if (wave == 1 && lane < BF_ROWS) sum_b[lane] = acc;
+            if (wave == 2 && lane < BF_ROWS) sum_c[lane] = acc;
+            __syncthreads();
+        }
         if (wave == 0) {
             const bool valid = lane < n_here;
-            Acc64<COSINE> A;
             A.a = acc;
-            A.b = sum_b[lane & (BF_ROWS - 1)];
-            A.c = sum_c[lane & (BF_ROWS - 1)];
+            if (METRIC == COSINE) {
+                A.b = sum_b[lane & (BF_ROWS - 1)];
+                A.c = sum_c[lane & (BF_ROWS - 1)];
+            }
             const double sc = valid ? A.score() : 0.0;
             if (valid && sc != sc) atomicOr(ctr + JOIN_CTR_NAN, 1ull);
             const bool keep = valid && sc >= min_score;
@@ -3243,7 +3257,7 @@ hipError_t launch_join_clear(hipStream_t s, unsigned long long* ctr)
     return hipGetLastError();
 }
 
-hipError_t launch_join_rescore_cut(hipStream_t s, const JoinCand* cand, const uint32_t* cnt, uint32_t cap, const double* master,
+hipError_t launch_join_rescore_cut(hipStream_t s, int metric, const JoinCand* cand, const uint32_t* cnt, uint32_t cap, const double* master,
                                    uint32_t dim, uint64_t n_rows, double min_score, unsigned long long* sv_keys, JoinPay* sv_pay,
                                    uint64_t sv_cap, unsigned long long* ctr)
 {
@@ -3251,9 +3265,17 @@ hipError_t launch_join_rescore_cut(hipStream_t s, const JoinCand* cand, const ui
     // the candidate count is the device's: enough workgroups for a full buffer, those without a tile leave at once
     const uint32_t tiles = (cap + BF_ROWS - 1) / BF_ROWS;
     const int grid = (int)(tiles < 2048u ? tiles : 2048u);
-    hipLaunchKernelGGL(k_join_rescore_cut, dim3(grid), dim3(256), 0, s, cand, cnt, cap, master, dim, (uint32_t)n_rows, min_score,
-                       sv_keys, sv_pay, (unsigned long long)sv_cap, ctr);
-    return hipGetLastError();
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, cand, cnt, cap, master, dim, (uint32_t)n_rows, min_score, sv_keys,
+                           sv_pay, (unsigned long long)sv_cap, ctr);
+        return hipGetLastError();
+    };
+    switch (metric) {
+    case COSINE: return launch(k_join_rescore_cut<COSINE>);
+    case EUCLIDEAN: return launch(k_join_rescore_cut<EUCLIDEAN>);
+    case DOT: return launch(k_join_rescore_cut<DOT>);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 hipError_t launch_join_rank(hipStream_t s, unsigned long long* sv_keys, JoinPay* sv_pay, uint64_t total)
