@@ -570,6 +570,33 @@ int vl_index_set_grouped_batch(vl_index *h, int mode);
 int vl_index_last_grouped_batch(const vl_index *h, uint64_t *routed, uint64_t *settled, uint64_t *handed_back,
                                 uint64_t *sequences);
 
+/* NEW (no reference counterpart): late-interaction (MaxSim) search, "the best k documents for a query that is a set of
+ * vectors" over an index whose documents are groups of rows (ColBERT / ColPali token or patch embeddings).
+ * groups: a token of vl_index_groups_create; G = its distinct groups with at least one stored row; rows without a group
+ * take no part.  queries: [n_tokens, q_len] f64.  With s(q, x) the reference score vl_index_search returns,
+ *     m_t(g)   = max over the rows x of g of s(q_t, x)
+ *     score(g) = ((m_0(g) + m_1(g)) + m_2(g)) + ...        f64, token order, no contraction
+ * the answer is the k groups of largest score as (group key, score bits), ties by ascending group key;
+ * *out_n = min(k, |G|, out_capacity), and the answer for a smaller k is a prefix of the answer for a larger one.
+ * VL_ERR_NAN_SCORE iff some s(q_t, x) over a grouped row is NaN.  VL_ERR_DIM_MISMATCH as in vl_index_search (whenever
+ * len != 0).  VL_ERR_INVALID_ARG: k > VL_GROUPED_MAX_K, n_tokens outside [1, VL_MAXSIM_MAX_TOKENS], an unknown or destroyed
+ * groups token (0 included), an unknown metric -- checked in that order, before the dimension.  k = 0, an empty index or a
+ * table without a stored row: *out_n = 0, VL_OK.  Single-GPU flat handles only.  The call holds the handle's shared lock
+ * throughout, never joins a coalesced pass, and the token follows the index through add / delete as in
+ * vl_index_search_grouped.
+ * Route (vl_index_last_maxsim, vl_last_path): the bf16 MFMA candidate pass with its certification (VL_PATH_FAST) for
+ * cosine / Euclidean / dot, a row length up to 768, k <= 64, in-domain rows and tokens and no forced path; the exact route
+ * (VL_PATH_EXACT_SORT: one exact scan per token) otherwise, and whenever more than 4096 groups (VL_MAXSIM_CAND_CAP in the
+ * environment lowers it) or 2^20 of their rows survive the bound, or the key table would exceed 256 MB.  Both routes
+ * return the same bits.
+ * vl_index_last_maxsim, four words of the last call on this handle: route (0 none, 1 mfma, 2 exact), survivor groups,
+ * their member rows, token chunks of the pass. */
+#define VL_MAXSIM_MAX_TOKENS 128
+int vl_index_search_maxsim(const vl_index *h, uint64_t groups, const double *queries, uint64_t n_tokens, uint64_t q_len,
+                           uint64_t k, int metric, uint64_t out_capacity, uint64_t *out_group_keys, double *out_scores,
+                           uint64_t *out_n);
+int vl_index_last_maxsim(const vl_index *h, uint64_t *out4);
+
 uint64_t vl_index_len(const vl_index *h);      /* len()       src/index/flat.rs:121-123 */
 int vl_index_is_empty(const vl_index *h);      /* is_empty()  src/index/flat.rs:125-127 */
 uint64_t vl_index_dimension(const vl_index *h);/* dimension() src/index/flat.rs:133-135 */

@@ -72,6 +72,8 @@ extern "C" {
     fn vl_index_groups_destroy(h: *mut vl_index, groups: u64) -> c_int;
     fn vl_index_search_grouped(h: *const vl_index, groups: u64, filter: u64, query: *const f64, q_len: u64, k: u64, metric: c_int, out_capacity: u64, out_group_keys: *mut u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_grouped_batch(h: *const vl_index, groups: u64, filter: u64, queries: *const f64, nq: u64, q_len: u64, k: u64, metric: c_int, out_stride: u64, out_group_keys: *mut u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
+    fn vl_index_search_maxsim(h: *const vl_index, groups: u64, queries: *const f64, n_tokens: u64, q_len: u64, k: u64, metric: c_int, out_capacity: u64, out_group_keys: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
+    fn vl_index_last_maxsim(h: *const vl_index, out4: *mut u64) -> c_int;
     fn vl_index_search_mmr(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, k: u64, fetch_k: u64, lambda: f64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_mmr_batch(h: *const vl_index, filter: u64, queries: *const f64, nq: u64, q_len: u64, k: u64, fetch_k: u64, lambda: f64, metric: c_int, out_stride: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_set_mmr_batch(h: *mut vl_index, mode: c_int) -> c_int;

@@ -530,6 +530,35 @@ def _search_grouped(L, h, query, k: int, metric: int, groups_token: int, filter_
     return keys[:m].copy(), ids[:m].copy(), scores[:m].copy()
 
 
+def _search_maxsim(L, h, queries, k: int, metric: int, groups_token: int):
+    """vl_index_search_maxsim -> (group_keys, scores), best group first."""
+    Q = np.ascontiguousarray(_f64(queries))
+    if Q.ndim != 2:
+        raise ValueError("queries must be [n_tokens, dim]")
+    n_tokens, q_len = Q.shape
+    k = min(max(int(k), 0), 1 << 62)
+    cap = max(min(k, VL_GROUPED_MAX_K), 1)
+    keys = np.empty(cap, dtype=np.uint64)
+    scores = np.empty(cap, dtype=np.float64)
+    n = C.c_uint64(0)
+    rc = L.vl_index_search_maxsim(h, int(groups_token), Q.ctypes.data, n_tokens, q_len, k, int(metric), cap, keys.ctypes.data,
+                                  scores.ctypes.data, C.byref(n))
+    if rc == VL_ERR_INVALID_ARG:
+        raise IndexOpError(_last_error())
+    _raise(rc)
+    m = int(n.value)
+    return keys[:m].copy(), scores[:m].copy()
+
+
+def _last_maxsim(L, h) -> Dict[str, int]:
+    out = np.zeros(4, dtype=np.uint64)
+    if L.vl_index_last_maxsim(h, out.ctypes.data) != 0:
+        raise IndexOpError(_last_error())
+    d = {k: int(v) for k, v in zip(("route", "survivors", "member_rows", "chunks"), out)}
+    d["route"] = {1: "mfma", 2: "exact"}.get(d["route"], d["route"])
+    return d
+
+
 GROUPED_BATCH_MODES = {"off": 0, "on": 1, "auto": 2}
 
 
@@ -1051,6 +1080,27 @@ class FlatIndex:
             text, md = self._meta.get(i, ("", None))
             out.append((g, SearchResult(id=i, score=s, text=text, metadata=md)))
         return out
+
+    # ---- late-interaction (MaxSim) search over grouped rows -----------------------------------
+    def search_maxsim_arrays(self, queries, k: int, metric: int = 0, groups=None):
+        """(group_keys, scores) of the k best groups of `groups` (a GroupTable of this index: one group per document, one
+        row per token or patch) for a query of several vectors, queries [n_tokens, dim], 1 <= n_tokens <= 128:
+        score(group) = the token-order f64 sum over the query's tokens of the token's best reference score among the
+        group's rows.  Ties come out by ascending group key; rows whose id the table does not hold take no part."""
+        if not isinstance(groups, GroupTable):
+            raise ValueError("groups must be a GroupTable of this index (make_groups)")
+        if groups._index is not self:
+            raise ValueError("the group table belongs to another index")
+        return _search_maxsim(self._L, self._h, queries, k, metric, groups.token)
+
+    def search_maxsim(self, queries, k: int, similarity_metric: int = SimilarityMetric.Cosine, groups=None) -> List[Tuple[int, float]]:
+        keys, scores = self.search_maxsim_arrays(queries, k, similarity_metric, groups=groups)
+        return list(zip(keys.tolist(), scores.tolist()))
+
+    def last_maxsim(self) -> Dict[str, int]:
+        """The last search_maxsim on this handle (vl_index_last_maxsim): route ("mfma" or "exact"), survivor groups, their
+        member rows, token chunks of the candidate pass."""
+        return _last_maxsim(self._L, self._h)
 
     def search_grouped_batch_arrays(self, queries, k: int, metric: int = 0, groups=None, filter=None, exclude=None):
         """(group_keys [nq, k], ids [nq, k], scores [nq, k], n [nq]) for queries [nq, dim]: the first n[i] entries of row i

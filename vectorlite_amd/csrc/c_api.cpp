@@ -747,6 +747,46 @@ int vl_index_search_grouped(const vl_index* h, uint64_t groups, uint64_t filter,
     });
 }
 
+static_assert(VL_MAXSIM_MAX_TOKENS == vl::MAXSIM_MAX_TOKENS, "the header states the kernels' limit");
+
+int vl_index_search_maxsim(const vl_index* h, uint64_t groups, const double* queries, uint64_t n_tokens, uint64_t q_len, uint64_t k,
+                           int metric, uint64_t out_capacity, uint64_t* out_group_keys, double* out_scores, uint64_t* out_n)
+{
+    return guarded([&]() -> int {
+        if (out_n) *out_n = 0;
+        if (k > VL_GROUPED_MAX_K) {  // before the handle is looked at: no device is needed
+            vl::set_last_error("late-interaction search: k exceeds VL_GROUPED_MAX_K (1024)");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (n_tokens < 1 || n_tokens > VL_MAXSIM_MAX_TOKENS) {
+            vl::set_last_error("late-interaction search: n_tokens must lie in [1, VL_MAXSIM_MAX_TOKENS (128)]");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (groups == 0) {
+            vl::set_last_error("unknown or destroyed group table");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (!h || !out_n) return VL_ERR_INVALID_ARG;
+        if (!h->flat) {
+            vl::set_last_error("late-interaction search is served by single-GPU flat indexes");
+            return VL_ERR_INVALID_ARG;
+        }
+        if ((!out_group_keys || !out_scores) && k != 0 && out_capacity != 0) return VL_ERR_INVALID_ARG;
+        return h->flat->search_maxsim(groups, queries, n_tokens, q_len, k, metric, out_capacity, out_group_keys, out_scores, out_n);
+    });
+}
+
+int vl_index_last_maxsim(const vl_index* h, uint64_t* out4)
+{
+    if (!h || !out4) return VL_ERR_INVALID_ARG;
+    if (!h->flat) {
+        vl::set_last_error("late-interaction search is served by single-GPU flat indexes");
+        return VL_ERR_INVALID_ARG;
+    }
+    h->flat->last_maxsim(out4);
+    return VL_OK;
+}
+
 int vl_index_search_grouped_batch(const vl_index* h, uint64_t groups, uint64_t filter, const double* queries, uint64_t nq,
                                   uint64_t q_len, uint64_t k, int metric, uint64_t out_stride, uint64_t* out_group_keys,
                                   uint64_t* out_ids, double* out_scores, uint64_t* out_n)

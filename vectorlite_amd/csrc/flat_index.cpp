@@ -233,12 +233,12 @@ Workspace::~Workspace()
     void* dev[] = {d_q64, d_partials, d_partials64, d_result, d_nan, d_scores, d_okeys,
                    d_opos, d_out_pos, d_out_scores, d_positions, d_dists, rg_ctr, rg_cand, rg_scores, rg_keys, rg_pv, mmr_sim,
                    rb_ctr, rb_min, rb_sv_score, rb_sv_pos, gp_best, gp_first, gp_lists, gp_cand, gp_scores, gp_ctr, gp_out_keys,
-                   gb_keep, gb_m, mb_ranked, jn_cand, jn_cnt, jn_ctr, jn_keys, jn_pay};
+                   gb_keep, gb_m, mb_ranked, jn_cand, jn_cnt, jn_ctr, jn_keys, jn_pay, ms_dev};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     void* host[] = {h_q64, h_result, h_nan, mf_h_q64, mf_h_result, mf_h_dom, k3_h_q64, k3_h_result, rg_h_ctr, rg_h_pos, rg_h_scores,
                     rb_h_thr, rb_h_min, rb_h_ctr, rb_h_cnt, rb_h_pos, rb_h_scores, gp_h_ctr, gp_h_scores, gp_h_keys,
-                    gb_h_result, jn_h};
+                    gb_h_result, jn_h, ms_host};
     for (void* p : host)
         if (p) (void)hipHostFree(p);
     void* mfd[] = {mf.q_bf16, mf.gmax, mf.thr, mf.cand, mf.cnt, mf_d_q64, mf_lists, mf_scores, k3_d_q64};
@@ -4245,6 +4245,307 @@ int GpuFlatIndex::similarity_join(double min_score, int metric, uint64_t out_cap
     stats[4] = total;
     set_last_path(PATH_FAST);
     publish();
+    return OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Late-interaction (MaxSim) search over grouped rows: the query is a set of token vectors, a
+// group's score the token-order f64 sum of each token's best reference score among the group's rows.
+// The MFMA route: one candidate pass (maxsim.hip) leaves the best bf16 key of every (token, group); the bound turns a group's
+// keys into an upper bound U of its score; the 64 groups of largest U are scored exactly, L = the k-th best of those scores,
+// and every group with U >= L -- no other group can be among the k best -- is scored exactly and ranked on the device.
+// The exact route is the definition: per token one exact scan, a segmented max into E1[group], acc[group] += E1[group].
+// ---------------------------------------------------------------------------------------------
+namespace {
+uint32_t maxsim_candidate_capacity()
+{
+    // VL_MAXSIM_CAND_CAP: fewer survivor groups per call (tests drive the hand-over to the exact route with it)
+    if (const char* e = getenv("VL_MAXSIM_CAND_CAP")) {
+        const long long v = atoll(e);
+        if (v >= 1 && v <= (long long)MAXSIM_CAND_CAP) return (uint32_t)v;
+    }
+    return MAXSIM_CAND_CAP;
+}
+// The call's buffers, carved from the workspace's two blocks at 256-byte steps: take() with a null base only measures.
+struct MaxsimCarver {
+    unsigned char* base;
+    size_t off = 0;
+    template <typename T>
+    T* take(size_t count)
+    {
+        off = (off + 255) & ~(size_t)255;
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += count * sizeof(T);
+        return p;
+    }
+};
+int ensure_maxsim_ws(Workspace* ws, size_t dev_bytes, size_t host_bytes)
+{
+    if (ws->ms_dev_cap < dev_bytes) {
+        VL_HIP(hipStreamSynchronize(ws->stream));
+        if (ws->ms_dev) (void)hipFree(ws->ms_dev);
+        ws->ms_dev_cap = 0;
+        VL_TRY(dev_alloc(&ws->ms_dev, dev_bytes));
+        ws->ms_dev_cap = dev_bytes;
+    }
+    if (ws->ms_host_cap < host_bytes) {
+        VL_HIP(hipStreamSynchronize(ws->stream));
+        if (ws->ms_host) (void)hipHostFree(ws->ms_host);
+        ws->ms_host_cap = 0;
+        VL_TRY(pinned_alloc(&ws->ms_host, host_bytes));
+        ws->ms_host_cap = host_bytes;
+    }
+    return OK;
+}
+constexpr const char* MAXSIM_NAN = "NaN similarity score: the reference panics in partial_cmp().unwrap()";
+}  // namespace
+
+int GpuFlatIndex::search_maxsim(uint64_t groups, const double* queries, uint64_t n_tokens, uint64_t q_len, uint64_t k, int metric,
+                                uint64_t out_capacity, uint64_t* out_group_keys, double* out_scores, uint64_t* out_n) const
+{
+    if (!out_n) return ERR_INVALID_ARG;
+    *out_n = 0;
+    set_last_path(PATH_NONE);
+    if (k > GROUPED_MAX_K) {
+        set_last_error("late-interaction search: k exceeds VL_GROUPED_MAX_K (1024)");
+        return ERR_INVALID_ARG;
+    }
+    if (n_tokens < 1 || n_tokens > MAXSIM_MAX_TOKENS) {
+        set_last_error("late-interaction search: n_tokens must lie in [1, VL_MAXSIM_MAX_TOKENS (128)]");
+        return ERR_INVALID_ARG;
+    }
+    std::shared_ptr<GroupTable> t;
+    VL_TRY(find_groups(groups, &t));
+    std::shared_lock<RwLock> lk;
+    VL_TRY(lock_for_query(metric, q_len, &lk));
+    uint64_t stats[4] = {0, 0, 0, 0};
+    auto publish = [&]() {
+        for (int i = 0; i < 4; ++i) last_maxsim_[i].store(stats[i], std::memory_order_relaxed);
+    };
+    if (ids_.empty() || k == 0) {
+        publish();
+        return OK;
+    }
+    if ((!queries && dim_) || (out_capacity != 0 && (!out_scores || !out_group_keys))) return ERR_INVALID_ARG;
+    const int rc = run_search(t.get(), nullptr, [&](Workspace* ws) -> int {
+        if (t->rows.m == 0) return OK;
+        const uint32_t T = (uint32_t)n_tokens;
+        const uint64_t n = ids_.size(), ng = t->keys.size();
+        const BatchGate gate = batch_gate(metric, n_tokens, k);
+        bool fast = gate_tail_index(gate) && gate.rows_kernel && maxsim_rows_supported((uint32_t)dim_, metric) && k <= (uint64_t)KP &&
+                    n < 0xFFFFFFE0ull && (uint64_t)T * ng * sizeof(uint32_t) <= MAXSIM_M_BYTES;
+        for (uint32_t i = 0; fast && i < T; ++i) fast = query_in_domain(queries + (size_t)i * dim_, dim_);
+        if (fast) {
+            bool certified = false;
+            VL_TRY(maxsim_mfma(ws, t.get(), queries, T, k, metric, out_capacity, out_group_keys, out_scores, out_n, stats, &certified));
+            if (certified) {
+                stats[0] = 1;
+                set_last_path(PATH_FAST);
+                return OK;
+            }
+        }
+        stats[0] = 2;
+        set_last_path(PATH_EXACT_SORT);
+        return maxsim_exact(ws, t.get(), queries, T, k, metric, out_capacity, out_group_keys, out_scores, out_n);
+    });
+    if (rc == OK) publish();
+    return rc;
+}
+
+int GpuFlatIndex::maxsim_mfma(Workspace* ws, const GroupTable* t, const double* queries, uint32_t T, uint64_t k, int metric,
+                              uint64_t out_capacity, uint64_t* out_group_keys, double* out_scores, uint64_t* out_n, uint64_t* stats,
+                              bool* certified) const
+{
+    *certified = false;
+    const uint64_t n = ids_.size();
+    const uint32_t ng = (uint32_t)t->keys.size();
+    const uint32_t ldb = mfma_ldb((uint32_t)dim_);
+    const uint32_t cap = maxsim_candidate_capacity();
+    const size_t qn = (size_t)T * dim_;
+    constexpr uint32_t Q_PAD = 2 * MAXSIM_MAX_TOKENS;  // whole token chunks past the last token (2 x 96 at stride 768)
+    VL_TRY(ensure_bf16_slab(true));
+
+    MaxsimCarver dv{nullptr}, hv{nullptr};
+    double *q_src, *q64, *q_norm, *U, *scores, *o_scores, *h_q, *h_scores, *h_o_scores;
+    void* q16;
+    uint32_t *cnt, *M, *flag, *list, *ctr, *h_ctr;
+    Cand64* lists;
+    MaxsimMember* members;
+    unsigned long long *E, *o_keys, *h_o_keys;
+    unsigned char* h_dom;
+    auto carve = [&]() {
+        q_src = dv.take<double>(qn);
+        q64 = dv.take<double>(qn);
+        q_norm = dv.take<double>(T);
+        q16 = dv.take<unsigned char>((size_t)Q_PAD * ldb * 2);
+        cnt = dv.take<uint32_t>(Q_PAD);
+        M = dv.take<uint32_t>((size_t)T * ng);
+        U = dv.take<double>(ng);
+        flag = dv.take<uint32_t>(ng);
+        lists = dv.take<Cand64>((size_t)MAXSIM_TOP_LISTS * KP);
+        list = dv.take<uint32_t>(MAXSIM_CAND_CAP);
+        members = dv.take<MaxsimMember>(MAXSIM_ROW_CAP);
+        E = dv.take<unsigned long long>((size_t)MAXSIM_CAND_CAP * T);
+        scores = dv.take<double>(MAXSIM_CAND_CAP);
+        ctr = dv.take<uint32_t>(MAXSIM_CTR_WORDS);
+        o_keys = dv.take<unsigned long long>(KP);
+        o_scores = dv.take<double>(KP);
+        h_q = hv.take<double>(qn);
+        h_dom = hv.take<unsigned char>(MAXSIM_MAX_TOKENS);
+        h_ctr = hv.take<uint32_t>(MAXSIM_CTR_WORDS);
+        h_scores = hv.take<double>(KP);
+        h_o_keys = hv.take<unsigned long long>(KP);
+        h_o_scores = hv.take<double>(KP);
+    };
+    carve();
+    VL_TRY(ensure_maxsim_ws(ws, dv.off, hv.off));
+    dv = MaxsimCarver{ws->ms_dev};
+    hv = MaxsimCarver{ws->ms_host};
+    carve();
+
+    hipStream_t st = ws->stream;
+    const uint32_t* gor = t->d_group_of_row;
+    memcpy(h_q, queries, qn * sizeof(double));
+    VL_HIP(hipMemcpyAsync(q_src, h_q, qn * sizeof(double), hipMemcpyHostToDevice, st));
+    MfmaScratch w;
+    w.q_bf16 = q16;
+    w.cnt = cnt;
+    w.nq_cap = MAXSIM_MAX_TOKENS;
+    w.nq_pad_cap = Q_PAD;
+    hipError_t pe = hipSuccess;
+    if (!launch_prepare_queries(st, q_src, T, (uint32_t)dim_, DOMAIN_MAX_ABS, DOMAIN_MIN_NORM, q64, q_norm, h_dom, w, &pe)) return OK;
+    VL_HIP(pe);
+    VL_HIP(launch_maxsim_fill(st, ctr, MAXSIM_CTR_WORDS, 0u));
+    VL_HIP(launch_maxsim_fill(st, M, (uint64_t)T * ng, MAXSIM_KEY_NEG_INF));
+    VL_HIP(launch_maxsim_fill(st, flag, ng, MAXSIM_NO_CAND));
+    MaxsimRowsInfo info;
+    VL_HIP(launch_maxsim_rows(st, metric, d_slab16f_, d_norm16_, d_sqnorm_, q16, T, n, (uint32_t)dim_, gor, ng, M, &info));
+    VL_HIP(launch_maxsim_upper(st, metric, M, T, ng, ldb, max_row_norm_, q_norm, U, lists, list, flag, ctr));
+    // round 1: the 64 groups of largest U, scored exactly
+    VL_HIP(launch_maxsim_fill64(st, E, (size_t)KP * T, 0ull));
+    VL_HIP(launch_maxsim_score(st, metric, d_master_, q64, T, (uint32_t)dim_, gor, n, ng, flag, ctr + MAXSIM_CTR_TOP, (uint32_t)KP,
+                               members, MAXSIM_ROW_CAP, E, scores, ctr));
+    VL_HIP(hipMemcpyAsync(h_ctr, ctr, MAXSIM_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    VL_HIP(hipMemcpyAsync(h_scores, scores, KP * sizeof(double), hipMemcpyDeviceToHost, st));
+    VL_HIP(hipStreamSynchronize(st));
+    stats[3] = (uint64_t)info.chunks;
+    for (uint32_t i = 0; i < T; ++i)
+        if (!h_dom[i]) return OK;  // (the host's verdict, confirmed by the device's)
+    if (h_ctr[MAXSIM_CTR_MEMBERS] > MAXSIM_ROW_CAP) return OK;
+    if (h_ctr[MAXSIM_CTR_NAN]) {
+        set_last_error(MAXSIM_NAN);
+        return ERR_NAN_SCORE;
+    }
+    const uint64_t n_groups = h_ctr[MAXSIM_CTR_GROUPS], c = h_ctr[MAXSIM_CTR_TOP];
+    const uint64_t k_eff = std::min<uint64_t>(k, n_groups);
+    if (n_groups > ng || c != std::min<uint64_t>(n_groups, KP) || k_eff > c || k_eff == 0) {
+        set_last_error("late-interaction search counted its groups inconsistently (kernel bug)");
+        return ERR_DEVICE;
+    }
+    // L = the k-th best exact score among them: k groups reach L, so the k-th best score overall is >= L
+    std::vector<double> top(h_scores, h_scores + c);
+    std::nth_element(top.begin(), top.begin() + (k_eff - 1), top.end(), [](double a, double b) { return a > b; });
+    const double L = top[k_eff - 1];
+
+    // round 2: every group whose upper bound reaches L, ties included
+    VL_HIP(launch_maxsim_fill(st, flag, ng, MAXSIM_NO_CAND));
+    VL_HIP(launch_maxsim_fill(st, ctr + MAXSIM_CTR_SURVIVORS, 2, 0u));  // SURVIVORS and MEMBERS
+    VL_HIP(launch_maxsim_survivors(st, U, ng, L, cap, list, flag, ctr));
+    VL_HIP(launch_maxsim_fill64(st, E, (size_t)cap * T, 0ull));
+    VL_HIP(launch_maxsim_score(st, metric, d_master_, q64, T, (uint32_t)dim_, gor, n, ng, flag, ctr + MAXSIM_CTR_SURVIVORS, cap, members,
+                               MAXSIM_ROW_CAP, E, scores, ctr));
+    VL_HIP(launch_maxsim_rank(st, list, scores, ctr + MAXSIM_CTR_SURVIVORS, cap, t->d_keys, (uint32_t)k_eff, o_keys, o_scores));
+    VL_HIP(hipMemcpyAsync(h_ctr, ctr, MAXSIM_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    VL_HIP(hipMemcpyAsync(h_o_keys, o_keys, k_eff * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    VL_HIP(hipMemcpyAsync(h_o_scores, o_scores, k_eff * sizeof(double), hipMemcpyDeviceToHost, st));
+    VL_HIP(hipStreamSynchronize(st));
+    const uint64_t sv = h_ctr[MAXSIM_CTR_SURVIVORS], rows = h_ctr[MAXSIM_CTR_MEMBERS];
+    stats[1] = sv;
+    stats[2] = rows;
+    if (sv > cap || rows > MAXSIM_ROW_CAP) return OK;  // a cap exceeded: the exact route answers
+    if (h_ctr[MAXSIM_CTR_NAN]) {
+        set_last_error(MAXSIM_NAN);
+        return ERR_NAN_SCORE;
+    }
+    if (sv < k_eff || sv > n_groups || rows > n) {
+        set_last_error("late-interaction search lost a group between its rounds (kernel bug)");
+        return ERR_DEVICE;
+    }
+    const uint64_t want = std::min<uint64_t>(k_eff, out_capacity);
+    for (uint64_t i = 0; i < want; ++i) {
+        out_group_keys[i] = h_o_keys[i];
+        out_scores[i] = h_o_scores[i];
+    }
+    *out_n = want;
+    *certified = true;
+    return OK;
+}
+
+int GpuFlatIndex::maxsim_exact(Workspace* ws, const GroupTable* t, const double* queries, uint32_t T, uint64_t k, int metric,
+                               uint64_t out_capacity, uint64_t* out_group_keys, double* out_scores, uint64_t* out_n) const
+{
+    const uint64_t n = ids_.size();
+    const uint32_t ng = (uint32_t)t->keys.size();
+    const size_t qn = (size_t)T * dim_;
+    MaxsimCarver dv{nullptr}, hv{nullptr};
+    double *q64, *acc, *h_q, *h_acc;
+    unsigned long long* E1;
+    uint32_t *ctr, *h_ctr;
+    auto carve = [&]() {
+        q64 = dv.take<double>(qn + 1);
+        E1 = dv.take<unsigned long long>(ng);
+        acc = dv.take<double>(ng);
+        ctr = dv.take<uint32_t>(MAXSIM_CTR_WORDS);
+        h_q = hv.take<double>(qn + 1);
+        h_acc = hv.take<double>(ng);
+        h_ctr = hv.take<uint32_t>(MAXSIM_CTR_WORDS);
+    };
+    carve();
+    VL_TRY(ensure_maxsim_ws(ws, dv.off, hv.off));
+    dv = MaxsimCarver{ws->ms_dev};
+    hv = MaxsimCarver{ws->ms_host};
+    carve();
+    VL_TRY(ensure_scores(ws, n));
+
+    hipStream_t st = ws->stream;
+    if (qn) memcpy(h_q, queries, qn * sizeof(double));
+    VL_HIP(hipMemcpyAsync(q64, h_q, (qn + 1) * sizeof(double), hipMemcpyHostToDevice, st));
+    VL_HIP(launch_maxsim_fill(st, ctr, MAXSIM_CTR_WORDS, 0u));
+    VL_HIP(launch_maxsim_fill64(st, E1, ng, 0ull));
+    for (uint32_t i = 0; i < T; ++i) {
+        // (the scan's own flag also covers rows without a group, which take no part: word 5 is not read)
+        VL_HIP(launch_exact_scan(st, metric, d_master_, q64 + (size_t)i * dim_, n, (uint32_t)dim_, ws->d_scores, ctr + 5));
+        VL_HIP(launch_maxsim_token(st, ws->d_scores, t->d_group_of_row, n, ng, i == 0, E1, acc, ctr));
+    }
+    VL_HIP(hipMemcpyAsync(h_acc, acc, (size_t)ng * sizeof(double), hipMemcpyDeviceToHost, st));
+    VL_HIP(hipMemcpyAsync(h_ctr, ctr, MAXSIM_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    VL_HIP(hipStreamSynchronize(st));
+    if (h_ctr[MAXSIM_CTR_NAN]) {
+        set_last_error(MAXSIM_NAN);
+        return ERR_NAN_SCORE;
+    }
+    // sort and cut on the host: (score desc, group key asc) over the groups that hold a row
+    std::vector<uint32_t> order;
+    try {
+        order.reserve(ng);
+        for (uint32_t g = 0; g < ng; ++g) {
+            uint64_t bits;
+            memcpy(&bits, &h_acc[g], sizeof bits);
+            if (bits != MAXSIM_EMPTY_BITS) order.push_back(g);
+        }
+    } catch (const std::bad_alloc&) {
+        set_last_error("out of host memory ranking the groups");
+        return ERR_OOM;
+    }
+    const uint64_t k_eff = std::min<uint64_t>(k, order.size());
+    auto in_front = [&](uint32_t a, uint32_t b) { return h_acc[a] > h_acc[b] || (h_acc[a] == h_acc[b] && t->keys[a] < t->keys[b]); };
+    std::partial_sort(order.begin(), order.begin() + k_eff, order.end(), in_front);
+    const uint64_t want = std::min<uint64_t>(k_eff, out_capacity);
+    for (uint64_t i = 0; i < want; ++i) {
+        out_group_keys[i] = t->keys[order[i]];
+        out_scores[i] = h_acc[order[i]];
+    }
+    *out_n = want;
     return OK;
 }
 

@@ -26,6 +26,7 @@
 #include "group_plan.hpp"
 #include "join.hpp"
 #include "kernels.hpp"
+#include "maxsim.hpp"
 #include "mfma_scan.hpp"
 #include "single_filter.hpp"
 
@@ -138,6 +139,11 @@ struct Workspace {
     double* mmr_sim = nullptr;
     // batched diversified search (lazy): the ranked candidates of a launch sequence's queries, between its two kernels
     SearchResultBlock* mb_ranked = nullptr;  // [MFMA_MAX_BATCH]
+    // late-interaction (MaxSim) search (lazy): one device block and one pinned block, carved per call (flat_index.cpp)
+    unsigned char* ms_dev = nullptr;
+    size_t ms_dev_cap = 0;
+    unsigned char* ms_host = nullptr;  // pinned
+    size_t ms_host_cap = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<float> q32;   // the f32 query handed to k_scan in its kernel arguments
     uint32_t seq = 0;         // stamp of the last single search issued from this workspace (h_result->seq)
@@ -505,6 +511,16 @@ public:
     int search_grouped_batch(uint64_t groups, uint64_t token, const double* queries, uint64_t nq, uint64_t q_len, uint64_t k,
                              int metric, uint64_t out_stride, uint64_t* out_group_keys, uint64_t* out_ids, double* out_scores,
                              uint64_t* out_n) const;
+    // NEW (no reference counterpart): late-interaction (MaxSim) search over the rows of a group table.
+    // queries: [n_tokens, q_len].  score(g) = the token-order f64 sum over t of the best reference score of token t among the
+    // rows of g; the k best groups by (score desc, group key asc) as (key, score).  Rows without a group take no part.
+    int search_maxsim(uint64_t groups, const double* queries, uint64_t n_tokens, uint64_t q_len, uint64_t k, int metric,
+                      uint64_t out_capacity, uint64_t* out_group_keys, double* out_scores, uint64_t* out_n) const;
+    // the last search_maxsim on this handle: route (0 none, 1 mfma, 2 exact), survivor groups, their member rows, token chunks
+    void last_maxsim(uint64_t* out4) const
+    {
+        for (int i = 0; i < 4; ++i) out4[i] = last_maxsim_[i].load(std::memory_order_relaxed);
+    }
     // 0: always the loop.  1: the pass whenever the batch is eligible.  2 ("auto", the default): when its estimate is lower.
     void set_grouped_batch(int mode) { grouped_batch_.store(mode); }
     int grouped_batch() const { return grouped_batch_.load(); }
@@ -688,6 +704,13 @@ private:
                        std::vector<JoinPair>* pairs, uint64_t* count) const;  // lower: the partners in FRONT of each row instead
     int join_mfma(Workspace* ws, double min_score, int metric, float thr, uint64_t out_capacity, std::vector<JoinPair>* pairs,
                   uint64_t* total, uint64_t* stats) const;
+    // search_maxsim's body (mu_ held, t resolved and not empty, 1 <= k): the MFMA route, which leaves *certified false when a
+    // cap is exceeded, and the exact route; both write the answer and stats[1..3]
+    int maxsim_mfma(Workspace* ws, const GroupTable* t, const double* queries, uint32_t n_tokens, uint64_t k, int metric,
+                    uint64_t out_capacity, uint64_t* out_group_keys, double* out_scores, uint64_t* out_n, uint64_t* stats,
+                    bool* certified) const;
+    int maxsim_exact(Workspace* ws, const GroupTable* t, const double* queries, uint32_t n_tokens, uint64_t k, int metric,
+                     uint64_t out_capacity, uint64_t* out_group_keys, double* out_scores, uint64_t* out_n) const;
     int wait_result(Workspace* ws, uint32_t seq) const;
     int ensure_i8_slab() const;  // lazily builds the int8 copy the single-query int8 filter streams
     int ensure_bf16_slab(bool frag_major) const;  // lazily builds the bf16 slab (row-major, or MFMA fragment order) a filter streams
@@ -870,6 +893,7 @@ private:
     mutable std::atomic<uint64_t> last_mmrbatch_[4] = {};
     std::atomic<int> mmr_batch_{2};  // MMR_BATCH_AUTO
     mutable std::atomic<uint64_t> last_join_[6] = {};
+    mutable std::atomic<uint64_t> last_maxsim_[4] = {};
     std::atomic<int> join_route_{0};  // 0 auto, 1 loop, 2 mfma
     std::atomic<uint64_t> last_delete_[6] = {};
     std::atomic<uint64_t> last_update_[7] = {};

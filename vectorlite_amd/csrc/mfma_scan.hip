@@ -21,6 +21,7 @@
 // A query whose check fails (or whose buffer overflows) is redone on the f32 path by the host.
 #include "mfma_scan.hpp"
 #include "filter_plan.hpp"
+#include "maxsim_plan.hpp"
 #include "xcd_map.hpp"
 
 #include <stdio.h>
@@ -523,6 +524,11 @@ constexpr int RS_NWAVES = RS_NWAVES_OVERRIDE;
 #define RS_HQB1 4   // query blocks per half while the whole K stays in registers (strides <= 384 could hold 6: see the anatomy file)
 #endif
 constexpr int rs_qpb(uint32_t ldb) { return ldb <= 384 ? 32 * RS_HQB1 : (ldb <= 512 ? 128 : 16 * RS_HQB768); }
+#if RS_HQB1 == 4 && RS_HQB768 == 6  // (the shipped shapes; diagnostic builds do not run the MaxSim pass)
+static_assert(rs_qpb(128) == (int)maxsim_qpb(128) && rs_qpb(384) == (int)maxsim_qpb(384) && rs_qpb(512) == (int)maxsim_qpb(512) &&
+                  rs_qpb(768) == (int)maxsim_qpb(768),
+              "the MaxSim pass reads its tokens in the chunks the prepare kernel pads them to");
+#endif
 // ring entries per wave: 192, or 128 where the queries leave less LDS
 constexpr int rs_seg(uint32_t ldb) { return (size_t)rs_qpb(ldb) * (ldb * 2 + 32) + 8 * 192 * 10 + 1024 <= 160 * 1024 ? 192 : 128; }
 
