@@ -597,6 +597,34 @@ int vl_index_search_maxsim(const vl_index *h, uint64_t groups, const double *que
                            uint64_t *out_n);
 int vl_index_last_maxsim(const vl_index *h, uint64_t *out4);
 
+/* NEW (no reference counterpart): nearest-label assignment, "for every stored row, which of these vectors is best" -- the
+ * assignment step of k-means and IVF builds, nearest-centroid or zero-shot labelling of a whole corpus.
+ * labels: [n_labels, q_len] f64, 1 <= n_labels <= VL_ASSIGN_MAX_LABELS.  With s(x, y) the reference score vl_index_search
+ * returns (symmetric bit for bit in all four metrics), the answer for the row at storage position p is
+ *     (label[p], score[p]) = the first entry of FlatIndex(labels, ids 0 .. n_labels - 1).search(row_p, 1, metric):
+ * the largest score, -0.0 and +0.0 equal, ties to the lowest label index, the score with the winning label's own f64 bits.
+ * Output in storage order: out_ids[p], out_labels[p], out_scores[p] for p < *out_n = min(len, out_capacity); duplicate ids
+ * are distinct rows.  VL_ERR_NAN_SCORE iff some s(row, label) is NaN.  VL_ERR_INVALID_ARG: n_labels outside its range, an
+ * unknown metric -- checked in that order, before the dimension.  VL_ERR_DIM_MISMATCH as in vl_index_search (whenever
+ * len != 0).  An empty index: *out_n = 0, VL_OK.  Single-GPU flat handles only.  The call holds the handle's shared lock
+ * throughout and never joins a coalesced pass.
+ * Routes (vl_index_set_assign_route: 0 = auto, the default; 1 = exact; 2 = mfma where eligible -- today the same as auto):
+ *   mfma   (VL_PATH_FAST) cosine / Euclidean / dot, a row length up to 768, in-domain rows and labels, no forced path,
+ *          VL_MFMA not 0, fewer than 2^32 - 32 rows: a bf16 MFMA pass that keeps the rows in registers and streams the labels
+ *          leaves a seed label per row; the seed's exact score S bounds the row's best from below; a second pass keeps every
+ *          label whose upper bound reaches S; those pairs are scored exactly.  No certification fallback.  The pass runs over
+ *          row ranges sized to a candidate buffer of 2^22 pairs (VL_ASSIGN_CAND_CAP in the environment lowers it, never
+ *          below 32 n_labels); a range that overflows is halved.
+ *   exact  (VL_PATH_EXACT_SORT) one exact scan per label, folded per row.
+ * Both routes return the same bits.
+ * vl_index_last_assign, six words of the last call on this handle: route (0 none, 1 mfma, 2 exact), row ranges answered,
+ * ranges that overflowed and were split, candidate pairs kept by the second pass, launches of the pass, label chunks. */
+#define VL_ASSIGN_MAX_LABELS 4096
+int vl_index_assign(const vl_index *h, const double *labels, uint64_t n_labels, uint64_t q_len, int metric,
+                    uint64_t out_capacity, uint64_t *out_ids, uint64_t *out_labels, double *out_scores, uint64_t *out_n);
+int vl_index_set_assign_route(vl_index *h, int mode); /* 0 auto (default), 1 exact, 2 mfma where eligible */
+int vl_index_last_assign(const vl_index *h, uint64_t *out6);
+
 uint64_t vl_index_len(const vl_index *h);      /* len()       src/index/flat.rs:121-123 */
 int vl_index_is_empty(const vl_index *h);      /* is_empty()  src/index/flat.rs:125-127 */
 uint64_t vl_index_dimension(const vl_index *h);/* dimension() src/index/flat.rs:133-135 */

@@ -74,6 +74,9 @@ extern "C" {
     fn vl_index_search_grouped_batch(h: *const vl_index, groups: u64, filter: u64, queries: *const f64, nq: u64, q_len: u64, k: u64, metric: c_int, out_stride: u64, out_group_keys: *mut u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_maxsim(h: *const vl_index, groups: u64, queries: *const f64, n_tokens: u64, q_len: u64, k: u64, metric: c_int, out_capacity: u64, out_group_keys: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_last_maxsim(h: *const vl_index, out4: *mut u64) -> c_int;
+    fn vl_index_assign(h: *const vl_index, labels: *const f64, n_labels: u64, q_len: u64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_labels: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
+    fn vl_index_set_assign_route(h: *mut vl_index, mode: c_int) -> c_int;
+    fn vl_index_last_assign(h: *const vl_index, out6: *mut u64) -> c_int;
     fn vl_index_search_mmr(h: *const vl_index, filter: u64, query: *const f64, q_len: u64, k: u64, fetch_k: u64, lambda: f64, metric: c_int, out_capacity: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_search_mmr_batch(h: *const vl_index, filter: u64, queries: *const f64, nq: u64, q_len: u64, k: u64, fetch_k: u64, lambda: f64, metric: c_int, out_stride: u64, out_ids: *mut u64, out_scores: *mut f64, out_n: *mut u64) -> c_int;
     fn vl_index_set_mmr_batch(h: *mut vl_index, mode: c_int) -> c_int;
@@ -721,6 +724,42 @@ impl GpuFlatIndex {
                 _ => return Err(VectorLiteError::InternalError(last_error())),
             }
         }
+    }
+
+    /// Nearest-label assignment (no reference counterpart): for every stored row, in storage order, `(id, label, score)` of
+    /// the best of `labels` (1 ..= 4096 vectors of the index's dimension) under the reference score: ties go to the lowest
+    /// label index, the score carries the winning label's own bits.  Single-GPU flat handles only.
+    pub fn assign(&self, labels: &[Vec<f64>], metric: SimilarityMetric) -> VectorLiteResult<Vec<(u64, u64, f64)>> {
+        let q_len = labels.first().map_or(0, |l| l.len());
+        if labels.iter().any(|l| l.len() != q_len) {
+            return Err(VectorLiteError::InternalError("labels differ in length".to_string()));
+        }
+        let flat: Vec<f64> = labels.iter().flatten().copied().collect();
+        let cap = unsafe { vl_index_len(self.0.raw) }.max(1) as usize;
+        let (mut ids, mut lab, mut s, mut n) = (vec![0u64; cap], vec![0u64; cap], vec![0f64; cap], 0u64);
+        let rc = unsafe {
+            vl_index_assign(self.0.raw, flat.as_ptr(), labels.len() as u64, q_len as u64, metric_code(metric), cap as u64, ids.as_mut_ptr(), lab.as_mut_ptr(), s.as_mut_ptr(), &mut n)
+        };
+        match rc {
+            VL_OK => Ok((0..n as usize).map(|i| (ids[i], lab[i], s[i])).collect()),
+            VL_ERR_NAN_SCORE => panic!("NaN similarity score"),
+            _ => Err(VectorLiteError::InternalError(last_error())),
+        }
+    }
+
+    /// 0 = auto, 1 = exact, 2 = mfma where eligible (`vl_index_set_assign_route`).
+    pub fn set_assign_route(&self, mode: i32) -> VectorLiteResult<()> {
+        match unsafe { vl_index_set_assign_route(self.0.raw, mode as c_int) } {
+            VL_OK => Ok(()),
+            _ => Err(VectorLiteError::InternalError(last_error())),
+        }
+    }
+
+    /// The last `assign`: route (1 mfma, 2 exact), row ranges answered, ranges split, candidate pairs, launches, label chunks.
+    pub fn last_assign(&self) -> [u64; 6] {
+        let mut out = [0u64; 6];
+        unsafe { vl_index_last_assign(self.0.raw, out.as_mut_ptr()) };
+        out
     }
 
     /// 0 = auto, 1 = loop, 2 = mfma (`vl_index_set_join_route`).

@@ -559,6 +559,38 @@ def _last_maxsim(L, h) -> Dict[str, int]:
     return d
 
 
+ASSIGN_ROUTES = {"auto": 0, "exact": 1, "mfma": 2}
+
+
+def _assign(L, h, labels, metric: int):
+    """vl_index_assign -> (ids, labels, scores) in storage order."""
+    Y = np.ascontiguousarray(_f64(labels))
+    if Y.ndim != 2:
+        raise ValueError("labels must be [n_labels, dim]")
+    n_labels, q_len = Y.shape
+    cap = max(int(L.vl_index_len(h)), 1)
+    ids = np.empty(cap, dtype=np.uint64)
+    lab = np.empty(cap, dtype=np.uint64)
+    scores = np.empty(cap, dtype=np.float64)
+    n = C.c_uint64(0)
+    rc = L.vl_index_assign(h, Y.ctypes.data, n_labels, q_len, int(metric), cap, ids.ctypes.data, lab.ctypes.data, scores.ctypes.data,
+                           C.byref(n))
+    if rc == VL_ERR_INVALID_ARG:
+        raise IndexOpError(_last_error())
+    _raise(rc)
+    m = int(n.value)
+    return ids[:m].copy(), lab[:m].copy(), scores[:m].copy()
+
+
+def _last_assign(L, h) -> Dict[str, int]:
+    out = np.zeros(6, dtype=np.uint64)
+    if L.vl_index_last_assign(h, out.ctypes.data) != 0:
+        raise IndexOpError(_last_error())
+    d = {k: int(v) for k, v in zip(("route", "ranges", "split", "candidates", "launches", "chunks"), out)}
+    d["route"] = {1: "mfma", 2: "exact"}.get(d["route"], d["route"])
+    return d
+
+
 GROUPED_BATCH_MODES = {"off": 0, "on": 1, "auto": 2}
 
 
@@ -1101,6 +1133,26 @@ class FlatIndex:
         """The last search_maxsim on this handle (vl_index_last_maxsim): route ("mfma" or "exact"), survivor groups, their
         member rows, token chunks of the candidate pass."""
         return _last_maxsim(self._L, self._h)
+
+    # ---- nearest-label assignment of every stored row -----------------------------------------
+    def assign(self, labels, metric: int = 0):
+        """(ids u64[n], labels u64[n], scores f64[n]) in storage order: for every stored row the best of labels [n_labels,
+        dim] (1 <= n_labels <= 4096) under the reference score -- the first entry of FlatIndex(labels).search(row, 1, metric):
+        ties to the lowest label index, the score with the winner's own bits (vl_index_assign)."""
+        return _assign(self._L, self._h, labels, metric)
+
+    def set_assign_route(self, mode: str) -> None:
+        """'auto' (the MFMA route whenever the call is eligible), 'exact' (one exact scan per label), 'mfma' (today the same
+        as auto) (vl_index_set_assign_route)."""
+        if mode not in ASSIGN_ROUTES:
+            raise ValueError("mode must be one of " + ", ".join(ASSIGN_ROUTES))
+        if self._L.vl_index_set_assign_route(self._h, ASSIGN_ROUTES[mode]) != 0:
+            raise IndexOpError(_last_error())
+
+    def last_assign(self) -> Dict[str, int]:
+        """The last assign on this handle (vl_index_last_assign): route ("mfma" or "exact"), row ranges answered, ranges
+        split, candidate pairs kept by the second pass, launches of the pass, label chunks."""
+        return _last_assign(self._L, self._h)
 
     def search_grouped_batch_arrays(self, queries, k: int, metric: int = 0, groups=None, filter=None, exclude=None):
         """(group_keys [nq, k], ids [nq, k], scores [nq, k], n [nq]) for queries [nq, dim]: the first n[i] entries of row i

@@ -72,4 +72,12 @@ inline bool gate_join(const BatchGate& g, bool route_loop, bool cosine, bool joi
            g.rows < 0x7FFFFFFFull;
 }
 
+// The nearest-label assignment: g.nq = the labels.  `route_exact` = the caller asked for the exact
+// route; `has_pass` = cosine, Euclidean or dot; `labels_in_domain` = every label is inside the fast-path domain.  Row
+// positions travel as 32-bit words in whole 32-row blocks.  No row floor: there is no sampling pass.
+inline bool gate_assign(const BatchGate& g, bool route_exact, bool has_pass, bool labels_in_domain)
+{
+    return !route_exact && has_pass && g.rows_kernel && gate_tail_index(g) && labels_in_domain && g.rows < 0xFFFFFFE0ull;
+}
+
 }  // namespace vl

@@ -787,6 +787,52 @@ int vl_index_last_maxsim(const vl_index* h, uint64_t* out4)
     return VL_OK;
 }
 
+static_assert(VL_ASSIGN_MAX_LABELS == vl::ASSIGN_MAX_LABELS, "the header states the kernels' limit");
+
+int vl_index_assign(const vl_index* h, const double* labels, uint64_t n_labels, uint64_t q_len, int metric, uint64_t out_capacity,
+                    uint64_t* out_ids, uint64_t* out_labels, double* out_scores, uint64_t* out_n)
+{
+    return guarded([&]() -> int {
+        if (out_n) *out_n = 0;
+        if (n_labels < 1 || n_labels > VL_ASSIGN_MAX_LABELS) {  // before the handle is looked at: no device is needed
+            vl::set_last_error("assign: n_labels must lie in [1, VL_ASSIGN_MAX_LABELS (4096)]");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (metric < 0 || metric > 3) {
+            vl::set_last_error("assign: unknown metric");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (!h || !out_n) return VL_ERR_INVALID_ARG;
+        if (!h->flat) {
+            vl::set_last_error("assign is served by single-GPU flat indexes");
+            return VL_ERR_INVALID_ARG;
+        }
+        if ((!out_ids || !out_labels || !out_scores) && out_capacity != 0) return VL_ERR_INVALID_ARG;
+        return h->flat->assign(labels, n_labels, q_len, metric, out_capacity, out_ids, out_labels, out_scores, out_n);
+    });
+}
+
+int vl_index_set_assign_route(vl_index* h, int mode)
+{
+    if (!h || mode < 0 || mode > 2) return VL_ERR_INVALID_ARG;
+    if (!h->flat) {
+        vl::set_last_error("assign is served by single-GPU flat indexes");
+        return VL_ERR_INVALID_ARG;
+    }
+    return h->flat->set_assign_route(mode);
+}
+
+int vl_index_last_assign(const vl_index* h, uint64_t* out6)
+{
+    if (!h || !out6) return VL_ERR_INVALID_ARG;
+    if (!h->flat) {
+        vl::set_last_error("assign is served by single-GPU flat indexes");
+        return VL_ERR_INVALID_ARG;
+    }
+    h->flat->last_assign(out6);
+    return VL_OK;
+}
+
 int vl_index_search_grouped_batch(const vl_index* h, uint64_t groups, uint64_t filter, const double* queries, uint64_t nq,
                                   uint64_t q_len, uint64_t k, int metric, uint64_t out_stride, uint64_t* out_group_keys,
                                   uint64_t* out_ids, double* out_scores, uint64_t* out_n)

@@ -4549,6 +4549,245 @@ int GpuFlatIndex::maxsim_exact(Workspace* ws, const GroupTable* t, const double*
     return OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Nearest-label assignment of every stored row: per row the best of n_labels external vectors.
+// The MFMA route walks the rows in ranges of 32-row blocks sized to the candidate buffer.  Per range: k_assign_rows mode 0
+// leaves a seed label per row, k_assign_seed scores (row, seed) exactly, mode 1 keeps every other label whose bound reaches
+// that score, and the tail scores those pairs exactly and picks the winner.  A range whose candidates overflow the buffer is
+// halved.  The exact route is the definition: one exact scan per label, folded into (best, label) per row.
+// ---------------------------------------------------------------------------------------------
+namespace {
+uint32_t assign_candidate_capacity()
+{
+    // VL_ASSIGN_CAND_CAP: a smaller candidate buffer (tests drive the range split with it)
+    if (const char* e = getenv("VL_ASSIGN_CAND_CAP")) {
+        const long long v = atoll(e);
+        if (v >= 1 && v <= (long long)ASSIGN_CAND_CAP) return (uint32_t)v;
+    }
+    return ASSIGN_CAND_CAP;
+}
+constexpr const char* ASSIGN_NAN = "NaN similarity score: the reference panics in partial_cmp().unwrap()";
+}  // namespace
+
+int GpuFlatIndex::assign(const double* labels, uint64_t n_labels, uint64_t q_len, int metric, uint64_t out_capacity, uint64_t* out_ids,
+                         uint64_t* out_labels, double* out_scores, uint64_t* out_n) const
+{
+    if (!out_n) return ERR_INVALID_ARG;
+    *out_n = 0;
+    set_last_path(PATH_NONE);
+    if (n_labels < 1 || n_labels > ASSIGN_MAX_LABELS) {
+        set_last_error("assign: n_labels must lie in [1, VL_ASSIGN_MAX_LABELS (4096)]");
+        return ERR_INVALID_ARG;
+    }
+    std::shared_lock<RwLock> lk;  // one index state for the whole call
+    VL_TRY(lock_for_query(metric, q_len, &lk));
+    uint64_t stats[6] = {0, 0, 0, 0, 0, 0};
+    auto publish = [&]() {
+        for (int i = 0; i < 6; ++i) last_assign_[i].store(stats[i], std::memory_order_relaxed);
+    };
+    const uint64_t n = ids_.size();
+    if (n == 0) {
+        publish();
+        return OK;
+    }
+    if ((!labels && dim_) || (out_capacity != 0 && (!out_ids || !out_labels || !out_scores))) return ERR_INVALID_ARG;
+    const uint64_t n_out = std::min<uint64_t>(n, out_capacity);
+    const uint32_t L = (uint32_t)n_labels;
+    const int rc = run_search(nullptr, nullptr, [&](Workspace* ws) -> int {
+        const BatchGate gate = batch_gate(metric, n_labels, 1);
+        const bool has_pass = assign_rows_supported((uint32_t)dim_, metric);
+        bool fast = gate_assign(gate, assign_route_.load() == 1, has_pass, true);
+        for (uint32_t i = 0; fast && i < L; ++i) fast = query_in_domain(labels + (size_t)i * dim_, dim_);
+        if (fast) {
+            bool done = false;
+            VL_TRY(assign_mfma(ws, labels, L, metric, n_out, out_labels, out_scores, stats, &done));
+            if (done) {
+                stats[0] = 1;
+                set_last_path(PATH_FAST);
+                return OK;
+            }
+        }
+        for (int i = 0; i < 6; ++i) stats[i] = 0;
+        stats[0] = 2;
+        set_last_path(PATH_EXACT_SORT);
+        return assign_exact(ws, labels, L, metric, n_out, out_labels, out_scores);
+    });
+    if (rc != OK) return rc;
+    for (uint64_t p = 0; p < n_out; ++p) out_ids[p] = ids_[p];
+    *out_n = n_out;
+    publish();
+    return OK;
+}
+
+int GpuFlatIndex::assign_mfma(Workspace* ws, const double* labels, uint32_t L, int metric, uint64_t n_out, uint64_t* out_labels,
+                              double* out_scores, uint64_t* stats, bool* done) const
+{
+    *done = false;
+    const uint64_t n = ids_.size();
+    const uint32_t ldb = mfma_ldb((uint32_t)dim_);
+    const uint32_t ch = assign_chunk(ldb), n_chunks = (L + ch - 1) / ch, l_pad = n_chunks * ch;
+    const uint32_t rq = maxsim_qpb(ldb);                            // the staging kernel pads to whole chunks of this many
+    const uint32_t per_launch = (uint32_t)MFMA_MAX_BATCH / rq * rq;  // labels per staging launch: whole chunks
+    const uint32_t q_rows = (L + rq - 1) / rq * rq;
+    const uint32_t cap = assign_cap(assign_candidate_capacity(), L);
+    const uint32_t n_blocks = (uint32_t)((n + ASSIGN_BLOCK_ROWS - 1) / ASSIGN_BLOCK_ROWS);
+    const uint32_t step = std::min<uint32_t>(assign_range_blocks(cap), n_blocks);
+    const size_t rr = (size_t)step * ASSIGN_BLOCK_ROWS, ln = (size_t)L * dim_;
+    VL_TRY(ensure_bf16_slab(true));
+
+    MaxsimCarver dv{nullptr}, hv{nullptr};
+    double *l_src, *l64, *l_norm, *h_l;
+    void* q16;
+    float *la, *lb_seed, *lb_keep;
+    uint32_t *cnt, *ctr, *h_ctr;
+    AssignRows rows;
+    AssignCand* cand;
+    unsigned char* h_dom;
+    auto carve = [&]() {
+        l_src = dv.take<double>(ln);
+        l64 = dv.take<double>(ln);
+        l_norm = dv.take<double>(L);
+        q16 = dv.take<unsigned char>((size_t)q_rows * ldb * 2);
+        cnt = dv.take<uint32_t>(q_rows);
+        la = dv.take<float>(l_pad);
+        lb_seed = dv.take<float>(l_pad);
+        lb_keep = dv.take<float>(l_pad);
+        rows.seeds = dv.take<AssignSeed>(rr);
+        rows.S = dv.take<double>(rr);
+        rows.thr = dv.take<float>(rr);
+        rows.seed_label = dv.take<uint32_t>(rr);
+        rows.best = dv.take<unsigned long long>(rr);
+        rows.winner = dv.take<uint32_t>(rr);
+        rows.out_labels = dv.take<unsigned long long>(rr);
+        rows.out_scores = dv.take<double>(rr);
+        cand = dv.take<AssignCand>(cap);
+        ctr = dv.take<uint32_t>(ASSIGN_CTR_WORDS);
+        h_l = hv.take<double>(ln);
+        h_dom = hv.take<unsigned char>(L);
+        h_ctr = hv.take<uint32_t>(ASSIGN_CTR_WORDS);
+    };
+    carve();
+    VL_TRY(ensure_maxsim_ws(ws, dv.off, hv.off));
+    dv = MaxsimCarver{ws->ms_dev};
+    hv = MaxsimCarver{ws->ms_host};
+    carve();
+
+    // ---- staging: the labels' f64 copy, norms and bf16 image (zero rows up to whole chunks), then their f32 scalars ----
+    hipStream_t st = ws->stream;
+    memcpy(h_l, labels, ln * sizeof(double));
+    VL_HIP(hipMemcpyAsync(l_src, h_l, ln * sizeof(double), hipMemcpyHostToDevice, st));
+    for (uint32_t off = 0; off < L; off += per_launch) {
+        const uint32_t m = std::min<uint32_t>(per_launch, L - off);
+        MfmaScratch w;
+        w.q_bf16 = static_cast<unsigned char*>(q16) + (size_t)off * ldb * 2;
+        w.cnt = cnt + off;
+        w.nq_cap = (uint32_t)MFMA_MAX_BATCH;
+        w.nq_pad_cap = q_rows - off;
+        hipError_t pe = hipSuccess;
+        if (!launch_prepare_queries(st, l_src + (size_t)off * dim_, m, (uint32_t)dim_, DOMAIN_MAX_ABS, DOMAIN_MIN_NORM,
+                                    l64 + (size_t)off * dim_, l_norm + off, h_dom + off, w, &pe))
+            return OK;
+        VL_HIP(pe);
+    }
+    VL_HIP(launch_assign_labels(st, metric, l_norm, L, l_pad, ldb, max_row_norm_, la, lb_seed, lb_keep));
+    VL_HIP(launch_maxsim_fill(st, ctr, ASSIGN_CTR_WORDS, 0u));
+    VL_HIP(hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < L; ++i)
+        if (!h_dom[i]) return OK;  // (the host's verdict, confirmed by the device's)
+
+    stats[5] = n_chunks;
+    std::vector<AssignRange> todo = assign_ranges(n_blocks, step);
+    while (!todo.empty()) {
+        const AssignRange r = todo.back();
+        todo.pop_back();
+        VL_HIP(launch_maxsim_fill(st, ctr + ASSIGN_CTR_CAND, 1, 0u));
+        VL_HIP(launch_assign_rows(st, metric, 0, d_slab16f_, d_norm16_, q16, la, lb_seed, L, n, (uint32_t)dim_, r, rows, cand, cap, ctr));
+        VL_HIP(launch_assign_seed(st, metric, d_master_, l64, d_sqnorm_, L, n, (uint32_t)dim_, r, rows, ctr));
+        VL_HIP(launch_assign_rows(st, metric, 1, d_slab16f_, d_norm16_, q16, la, lb_keep, L, n, (uint32_t)dim_, r, rows, cand, cap, ctr));
+        VL_HIP(launch_assign_finish(st, metric, d_master_, l64, L, n, (uint32_t)dim_, r, rows, cand, cap, ctr));
+        VL_HIP(hipMemcpyAsync(h_ctr, ctr, ASSIGN_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipStreamSynchronize(st));
+        stats[4] += 2;
+        if (h_ctr[ASSIGN_CTR_NAN]) {
+            set_last_error(ASSIGN_NAN);
+            return ERR_NAN_SCORE;
+        }
+        if (h_ctr[ASSIGN_CTR_CAND] > cap) {  // halved and run again, the lower half first
+            if (!assign_split(&todo, r)) {
+                set_last_error("assign: one 32-row block overflowed the candidate buffer (kernel bug)");
+                return ERR_DEVICE;
+            }
+            stats[2] += 1;
+            continue;
+        }
+        stats[1] += 1;
+        stats[3] += h_ctr[ASSIGN_CTR_CAND];
+        const uint64_t p0 = (uint64_t)r.b0 * ASSIGN_BLOCK_ROWS, p1 = std::min<uint64_t>((uint64_t)r.b1 * ASSIGN_BLOCK_ROWS, n_out);
+        if (p0 < p1) {
+            VL_HIP(hipMemcpy(out_labels + p0, rows.out_labels, (p1 - p0) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            VL_HIP(hipMemcpy(out_scores + p0, rows.out_scores, (p1 - p0) * sizeof(double), hipMemcpyDeviceToHost));
+        }
+    }
+    for (uint64_t p = 0; p < n_out; ++p)
+        if (out_labels[p] >= L) {
+            set_last_error("assign returned an out-of-range label (kernel bug)");
+            return ERR_DEVICE;
+        }
+    *done = true;
+    return OK;
+}
+
+int GpuFlatIndex::assign_exact(Workspace* ws, const double* labels, uint32_t L, int metric, uint64_t n_out, uint64_t* out_labels,
+                               double* out_scores) const
+{
+    const uint64_t n = ids_.size();
+    const size_t ln = (size_t)L * dim_;
+    MaxsimCarver dv{nullptr}, hv{nullptr};
+    double *l64, *best, *h_l;
+    uint32_t *label, *ctr, *h_ctr;
+    auto carve = [&]() {
+        l64 = dv.take<double>(ln + 1);
+        best = dv.take<double>(n);
+        label = dv.take<uint32_t>(n);
+        ctr = dv.take<uint32_t>(ASSIGN_CTR_WORDS);
+        h_l = hv.take<double>(ln + 1);
+        h_ctr = hv.take<uint32_t>(ASSIGN_CTR_WORDS);
+    };
+    carve();
+    VL_TRY(ensure_maxsim_ws(ws, dv.off, hv.off));
+    dv = MaxsimCarver{ws->ms_dev};
+    hv = MaxsimCarver{ws->ms_host};
+    carve();
+    VL_TRY(ensure_scores(ws, n));
+
+    hipStream_t st = ws->stream;
+    if (ln) memcpy(h_l, labels, ln * sizeof(double));
+    VL_HIP(hipMemcpyAsync(l64, h_l, (ln + 1) * sizeof(double), hipMemcpyHostToDevice, st));
+    VL_HIP(launch_maxsim_fill(st, ctr, ASSIGN_CTR_WORDS, 0u));
+    for (uint32_t l = 0; l < L; ++l) {
+        VL_HIP(launch_exact_scan(st, metric, d_master_, l64 + (size_t)l * dim_, n, (uint32_t)dim_, ws->d_scores, ctr + ASSIGN_CTR_NAN));
+        VL_HIP(launch_assign_fold(st, ws->d_scores, n, l, best, label, ctr));
+    }
+    VL_HIP(hipMemcpyAsync(h_ctr, ctr, ASSIGN_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    VL_HIP(hipStreamSynchronize(st));
+    if (h_ctr[ASSIGN_CTR_NAN]) {
+        set_last_error(ASSIGN_NAN);
+        return ERR_NAN_SCORE;
+    }
+    if (n_out == 0) return OK;
+    std::vector<uint32_t> h_label;
+    try {
+        h_label.resize(n_out);
+    } catch (const std::bad_alloc&) {
+        set_last_error("out of host memory collecting the labels");
+        return ERR_OOM;
+    }
+    VL_HIP(hipMemcpy(h_label.data(), label, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    VL_HIP(hipMemcpy(out_scores, best, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    for (uint64_t p = 0; p < n_out; ++p) out_labels[p] = h_label[p];
+    return OK;
+}
+
 // Queries in device memory.  The MFMA batch path takes them where they are; everything else goes through the host.
 int GpuFlatIndex::search_batch_device(const double* d_queries, uint64_t nq, uint64_t q_len, uint64_t k, int metric,
                                       uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n) const

@@ -23,6 +23,7 @@
 #include "attr_plan.hpp"
 #include "batch_gate.hpp"
 #include "coalescer.hpp"
+#include "assign.hpp"
 #include "group_plan.hpp"
 #include "join.hpp"
 #include "kernels.hpp"
@@ -521,6 +522,24 @@ public:
     {
         for (int i = 0; i < 4; ++i) out4[i] = last_maxsim_[i].load(std::memory_order_relaxed);
     }
+    // NEW (no reference counterpart): nearest-label assignment of every stored row.  labels:
+    // [n_labels, q_len], 1 <= n_labels <= ASSIGN_MAX_LABELS.  For the row at storage position p < min(len, out_capacity):
+    // out_ids[p], and (out_labels[p], out_scores[p]) = the first entry of FlatIndex(labels, ids 0 ..).search(row_p, 1, metric).
+    int assign(const double* labels, uint64_t n_labels, uint64_t q_len, int metric, uint64_t out_capacity, uint64_t* out_ids,
+               uint64_t* out_labels, double* out_scores, uint64_t* out_n) const;
+    // 0 auto, 1 exact, 2 mfma where eligible (today the same as auto)
+    int set_assign_route(int mode)
+    {
+        if (mode < 0 || mode > 2) return ERR_INVALID_ARG;
+        assign_route_.store(mode);
+        return OK;
+    }
+    // the last assign on this handle: route (0 none, 1 mfma, 2 exact), row ranges answered, ranges split, candidate pairs kept,
+    // launches of the pass, label chunks
+    void last_assign(uint64_t* out6) const
+    {
+        for (int i = 0; i < 6; ++i) out6[i] = last_assign_[i].load(std::memory_order_relaxed);
+    }
     // 0: always the loop.  1: the pass whenever the batch is eligible.  2 ("auto", the default): when its estimate is lower.
     void set_grouped_batch(int mode) { grouped_batch_.store(mode); }
     int grouped_batch() const { return grouped_batch_.load(); }
@@ -711,6 +730,12 @@ private:
                     bool* certified) const;
     int maxsim_exact(Workspace* ws, const GroupTable* t, const double* queries, uint32_t n_tokens, uint64_t k, int metric,
                      uint64_t out_capacity, uint64_t* out_group_keys, double* out_scores, uint64_t* out_n) const;
+    // assign's body (mu_ held, the index not empty): the MFMA route, which leaves *done false when a label turns out to lie
+    // outside the domain, and the exact route; both write out_labels / out_scores[0 .. n_out) and stats[1..5]
+    int assign_mfma(Workspace* ws, const double* labels, uint32_t n_labels, int metric, uint64_t n_out, uint64_t* out_labels,
+                    double* out_scores, uint64_t* stats, bool* done) const;
+    int assign_exact(Workspace* ws, const double* labels, uint32_t n_labels, int metric, uint64_t n_out, uint64_t* out_labels,
+                     double* out_scores) const;
     int wait_result(Workspace* ws, uint32_t seq) const;
     int ensure_i8_slab() const;  // lazily builds the int8 copy the single-query int8 filter streams
     int ensure_bf16_slab(bool frag_major) const;  // lazily builds the bf16 slab (row-major, or MFMA fragment order) a filter streams
@@ -894,6 +919,8 @@ private:
     std::atomic<int> mmr_batch_{2};  // MMR_BATCH_AUTO
     mutable std::atomic<uint64_t> last_join_[6] = {};
     mutable std::atomic<uint64_t> last_maxsim_[4] = {};
+    mutable std::atomic<uint64_t> last_assign_[6] = {};
+    std::atomic<int> assign_route_{0};  // 0 auto, 1 exact, 2 mfma
     std::atomic<int> join_route_{0};  // 0 auto, 1 loop, 2 mfma
     std::atomic<uint64_t> last_delete_[6] = {};
     std::atomic<uint64_t> last_update_[7] = {};
