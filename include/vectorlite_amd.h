@@ -625,6 +625,36 @@ int vl_index_assign(const vl_index *h, const double *labels, uint64_t n_labels, 
 int vl_index_set_assign_route(vl_index *h, int mode); /* 0 auto (default), 1 exact, 2 mfma where eligible */
 int vl_index_last_assign(const vl_index *h, uint64_t *out6);
 
+/* NEW (no reference counterpart): the exact k-nearest-neighbour graph of the stored rows, "for every stored row, which k other
+ * stored rows are nearest" -- the input of UMAP / t-SNE, graph clustering, label propagation and outlier scores.
+ * 1 <= k <= VL_KNN_MAX_K; *out_kk = kk = min(k, len - 1).  With s(x, y) the reference score vl_index_search returns, the list
+ * of the row at storage position p is every other position j != p ranked by s(row_p, row_j) (row p the query, bit for bit;
+ * -0.0 and +0.0 equal, ties to the lower storage position), cut at kk entries.  Equivalently: the first k + 1 entries of
+ * the positional search(row_p, k + 1) without position p where it appears, the first kk of what remains.  Duplicate ids are
+ * distinct rows; identical rows are each other's neighbours; a row is never its own.
+ * Output in storage order for p < *out_n = min(len, out_capacity): out_ids[p], and at [p kk, (p + 1) kk) of out_nbr_ids and
+ * out_scores the neighbours' ids and scores (the arrays hold out_capacity * k entries).  Fewer than two rows: VL_OK with
+ * kk = 0.  VL_ERR_NAN_SCORE iff a score that decides a list is NaN.  VL_ERR_INVALID_ARG: k outside its range, an unknown
+ * metric -- checked in that order, before anything about the rows.  Single-GPU flat handles only.  The call holds the
+ * handle's shared lock throughout and never joins a coalesced pass.
+ * Routes (vl_index_set_knn_route: 0 = auto, the default; 1 = exact; 2 = mfma where eligible -- today the same as auto):
+ *   mfma   (VL_PATH_FAST) cosine / Euclidean / dot, a row length up to 768, in-domain rows, no forced path, VL_MFMA not 0,
+ *          fewer than 2^32 - 32 rows, len - 1 >= k: a bf16 MFMA pass over the full square (rows in registers, the slab's own
+ *          rows streaming) carries a top-k list per row and leaves k seed partners; their exact scores give S, the k-th
+ *          best; a second pass keeps every partner whose similarity-join key test reaches S; seeds and kept pairs are
+ *          scored exactly, sorted and cut.  No host trip of the rows, no certification, no fallback.  The pass runs over row
+ *          ranges sized to a candidate buffer of 2^22 pairs (VL_KNN_CAND_CAP in the environment lowers it, never below
+ *          32 k); a range that overflows is halved, and a single 32-row block that still overflows takes the exact route.
+ *   exact  (VL_PATH_EXACT_SORT) the definition: per row the locked positional search for k + 1 entries, position p dropped.
+ * Both routes return the same bits.
+ * vl_index_last_knn, six words of the last call on this handle: route (0 none, 1 mfma, 2 exact), seed candidates, candidates
+ * kept by the second pass, ranges that overflowed and were split, rows handed to the exact route, launches of the pass. */
+#define VL_KNN_MAX_K 32
+int vl_index_knn_graph(const vl_index *h, uint64_t k, int metric, uint64_t out_capacity, uint64_t *out_ids,
+                       uint64_t *out_nbr_ids, double *out_scores, uint64_t *out_n, uint64_t *out_kk);
+int vl_index_set_knn_route(vl_index *h, int mode); /* 0 auto (default), 1 exact, 2 mfma where eligible */
+int vl_index_last_knn(const vl_index *h, uint64_t *out6);
+
 uint64_t vl_index_len(const vl_index *h);      /* len()       src/index/flat.rs:121-123 */
 int vl_index_is_empty(const vl_index *h);      /* is_empty()  src/index/flat.rs:125-127 */
 uint64_t vl_index_dimension(const vl_index *h);/* dimension() src/index/flat.rs:133-135 */

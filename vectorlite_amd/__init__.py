@@ -591,6 +591,43 @@ def _last_assign(L, h) -> Dict[str, int]:
     return d
 
 
+KNN_ROUTES = {"auto": 0, "exact": 1, "mfma": 2}
+
+
+def _knn_graph(L, h, k: int, metric):
+    """vl_index_knn_graph -> (ids [n], nbr_ids [n, kk], scores [n, kk]) in storage order."""
+    k = int(k)
+    cap = max(int(L.vl_index_len(h)), 1)
+    width = min(max(k, 1), 32)
+    ids = np.empty(cap, dtype=np.uint64)
+    nbr = np.empty(cap * width, dtype=np.uint64)
+    scores = np.empty(cap * width, dtype=np.float64)
+    n, kk = C.c_uint64(0), C.c_uint64(0)
+    rc = L.vl_index_knn_graph(h, max(k, 0), int(0 if metric is None else metric), cap, ids.ctypes.data, nbr.ctypes.data,
+                              scores.ctypes.data, C.byref(n), C.byref(kk))
+    if rc == VL_ERR_INVALID_ARG:
+        raise IndexOpError(_last_error())
+    _raise(rc)
+    m, w = int(n.value), int(kk.value)
+    return ids[:m].copy(), nbr[:m * w].reshape(m, w).copy(), scores[:m * w].reshape(m, w).copy()
+
+
+def _set_knn_route(L, h, mode: str) -> None:
+    if mode not in KNN_ROUTES:
+        raise ValueError("mode must be one of " + ", ".join(KNN_ROUTES))
+    if L.vl_index_set_knn_route(h, KNN_ROUTES[mode]) != 0:
+        raise IndexOpError(_last_error())
+
+
+def _last_knn(L, h) -> Dict[str, int]:
+    out = np.zeros(6, dtype=np.uint64)
+    if L.vl_index_last_knn(h, out.ctypes.data) != 0:
+        raise IndexOpError(_last_error())
+    d = {k: int(v) for k, v in zip(("route", "seeds", "kept", "split", "exact_rows", "launches"), out)}
+    d["route"] = {1: "mfma", 2: "exact"}.get(d["route"], d["route"])
+    return d
+
+
 GROUPED_BATCH_MODES = {"off": 0, "on": 1, "auto": 2}
 
 
@@ -1153,6 +1190,24 @@ class FlatIndex:
         """The last assign on this handle (vl_index_last_assign): route ("mfma" or "exact"), row ranges answered, ranges
         split, candidate pairs kept by the second pass, launches of the pass, label chunks."""
         return _last_assign(self._L, self._h)
+
+    # ---- k-nearest-neighbour graph of the stored rows ---------------------------------------------
+    def knn_graph(self, k: int, metric=None):
+        """(ids u64[n], nbr_ids u64[n, kk], scores f64[n, kk]) in storage order, kk = min(k, n - 1), 1 <= k <= 32: for every
+        stored row its kk best OTHER rows under the reference score (metric None = cosine) -- the positional search(row,
+        k + 1) without the row itself: ties to the lower storage position, the reference's own score bits
+        (vl_index_knn_graph)."""
+        return _knn_graph(self._L, self._h, k, metric)
+
+    def set_knn_route(self, mode: str) -> None:
+        """'auto' (the MFMA route whenever the call is eligible), 'exact' (one positional search per row), 'mfma' (today the
+        same as auto) (vl_index_set_knn_route)."""
+        _set_knn_route(self._L, self._h, mode)
+
+    def last_knn(self) -> Dict[str, int]:
+        """The last knn_graph on this handle (vl_index_last_knn): route ("mfma" or "exact"), seed candidates, candidates kept
+        by the second pass, ranges split, rows handed to the exact route, launches of the pass."""
+        return _last_knn(self._L, self._h)
 
     def search_grouped_batch_arrays(self, queries, k: int, metric: int = 0, groups=None, filter=None, exclude=None):
         """(group_keys [nq, k], ids [nq, k], scores [nq, k], n [nq]) for queries [nq, dim]: the first n[i] entries of row i
@@ -1990,6 +2045,16 @@ class HNSWIndex:
 
     def last_join(self) -> Dict[str, int]:
         return _last_join(self._L, self._h)
+
+    def knn_graph(self, k: int, metric=None):
+        """The neighbour graph is served by single-GPU flat indexes: raises IndexOpError with the library's message."""
+        return _knn_graph(self._L, self._h, k, metric)
+
+    def set_knn_route(self, mode: str) -> None:
+        _set_knn_route(self._L, self._h, mode)
+
+    def last_knn(self) -> Dict[str, int]:
+        return _last_knn(self._L, self._h)
 
     def search_mmr_arrays(self, query, k: int, fetch_k: int = 20, lambda_mult: float = 0.5, metric: int = 0, filter=None):
         """Diversified search is served by single-GPU flat indexes: raises IndexOpError with the library's message."""

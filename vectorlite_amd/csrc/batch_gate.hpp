@@ -80,4 +80,13 @@ inline bool gate_assign(const BatchGate& g, bool route_exact, bool has_pass, boo
     return !route_exact && has_pass && g.rows_kernel && gate_tail_index(g) && labels_in_domain && g.rows < 0xFFFFFFE0ull;
 }
 
+// The k-nearest-neighbour graph: g.k_eff = k, g.nq unused.  gate_assign's conditions without labels;
+// on top of them every row must have k other rows (len - 1 >= k), or each row keeps every other row and the exact route
+// answers.
+inline bool gate_knn(const BatchGate& g, bool route_exact, bool has_pass)
+{
+    return !route_exact && has_pass && g.rows_kernel && gate_tail_index(g) && g.rows < 0xFFFFFFE0ull && g.rows >= 1 &&
+           g.rows - 1 >= g.k_eff;
+}
+
 }  // namespace vl

@@ -833,6 +833,53 @@ int vl_index_last_assign(const vl_index* h, uint64_t* out6)
     return VL_OK;
 }
 
+static_assert(VL_KNN_MAX_K == vl::KNN_MAX_K, "the header states the kernels' limit");
+
+int vl_index_knn_graph(const vl_index* h, uint64_t k, int metric, uint64_t out_capacity, uint64_t* out_ids, uint64_t* out_nbr_ids,
+                       double* out_scores, uint64_t* out_n, uint64_t* out_kk)
+{
+    return guarded([&]() -> int {
+        if (out_n) *out_n = 0;
+        if (out_kk) *out_kk = 0;
+        if (k < 1 || k > VL_KNN_MAX_K) {  // before the handle is looked at: no device is needed
+            vl::set_last_error("knn_graph: k must lie in [1, VL_KNN_MAX_K (32)]");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (metric < 0 || metric > 3) {
+            vl::set_last_error("knn_graph: unknown metric");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (!h || !out_n || !out_kk) return VL_ERR_INVALID_ARG;
+        if (!h->flat) {
+            vl::set_last_error("knn_graph is served by single-GPU flat indexes");
+            return VL_ERR_INVALID_ARG;
+        }
+        if ((!out_ids || !out_nbr_ids || !out_scores) && out_capacity != 0) return VL_ERR_INVALID_ARG;
+        return h->flat->knn_graph(k, metric, out_capacity, out_ids, out_nbr_ids, out_scores, out_n, out_kk);
+    });
+}
+
+int vl_index_set_knn_route(vl_index* h, int mode)
+{
+    if (!h || mode < 0 || mode > 2) return VL_ERR_INVALID_ARG;
+    if (!h->flat) {
+        vl::set_last_error("knn_graph is served by single-GPU flat indexes");
+        return VL_ERR_INVALID_ARG;
+    }
+    return h->flat->set_knn_route(mode);
+}
+
+int vl_index_last_knn(const vl_index* h, uint64_t* out6)
+{
+    if (!h || !out6) return VL_ERR_INVALID_ARG;
+    if (!h->flat) {
+        vl::set_last_error("knn_graph is served by single-GPU flat indexes");
+        return VL_ERR_INVALID_ARG;
+    }
+    h->flat->last_knn(out6);
+    return VL_OK;
+}
+
 int vl_index_search_grouped_batch(const vl_index* h, uint64_t groups, uint64_t filter, const double* queries, uint64_t nq,
                                   uint64_t q_len, uint64_t k, int metric, uint64_t out_stride, uint64_t* out_group_keys,
                                   uint64_t* out_ids, double* out_scores, uint64_t* out_n)

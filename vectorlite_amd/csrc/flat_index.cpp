@@ -4788,6 +4788,205 @@ int GpuFlatIndex::assign_exact(Workspace* ws, const double* labels, uint32_t L, 
     return OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Exact k-nearest-neighbour graph of the stored rows: per row its k best OTHER rows.
+// The MFMA route walks the rows in ranges of 32-row blocks sized to the candidate buffer.  Per range: k_knn_rows mode 0 leaves
+// k seed partners per row, k_knn_seed scores them exactly and turns the k-th best score S into the join's key threshold,
+// mode 1 keeps every partner whose key test reaches it, and the tail scores the kept pairs exactly, sorts seeds and kept
+// pairs by (row, score desc, partner) and emits the first kk distinct partners per row.  A range whose kept pairs overflow
+// the buffer is halved; a single block that still overflows goes to the exact route.  The exact route is the definition:
+// each row goes through the positional search for k + 1 entries and drops itself.
+// ---------------------------------------------------------------------------------------------
+namespace {
+constexpr uint64_t KNN_LOOP_ROWS = 64;  // rows the exact route fetches from the master per copy
+uint32_t knn_candidate_capacity()
+{
+    // VL_KNN_CAND_CAP: a smaller candidate buffer (tests drive the range split and the hand-over with it)
+    if (const char* e = getenv("VL_KNN_CAND_CAP")) {
+        const long long v = atoll(e);
+        if (v >= 1 && v <= (long long)KNN_CAND_CAP) return (uint32_t)v;
+    }
+    return KNN_CAND_CAP;
+}
+}  // namespace
+
+int GpuFlatIndex::knn_graph(uint64_t k, int metric, uint64_t out_capacity, uint64_t* out_ids, uint64_t* out_nbr_ids, double* out_scores,
+                            uint64_t* out_n, uint64_t* out_kk) const
+{
+    if (!out_n || !out_kk) return ERR_INVALID_ARG;
+    *out_n = 0;
+    *out_kk = 0;
+    set_last_path(PATH_NONE);
+    if (k < 1 || k > KNN_MAX_K) {
+        set_last_error("knn_graph: k must lie in [1, VL_KNN_MAX_K (32)]");
+        return ERR_INVALID_ARG;
+    }
+    std::shared_lock<RwLock> lk;  // one index state for the whole call
+    VL_TRY(lock_for_query(metric, dim_, &lk));
+    uint64_t stats[6] = {0, 0, 0, 0, 0, 0};
+    auto publish = [&]() {
+        for (int i = 0; i < 6; ++i) last_knn_[i].store(stats[i], std::memory_order_relaxed);
+    };
+    const uint64_t n = ids_.size();
+    if (out_capacity != 0 && (!out_ids || !out_nbr_ids || !out_scores)) return ERR_INVALID_ARG;
+    const uint64_t n_out = std::min<uint64_t>(n, out_capacity);
+    if (n < 2) {  // no row has a partner
+        for (uint64_t p = 0; p < n_out; ++p) out_ids[p] = ids_[p];
+        *out_n = n_out;
+        publish();
+        return OK;
+    }
+    const uint32_t kk = (uint32_t)std::min<uint64_t>(k, n - 1);
+    const int rc = run_search(nullptr, nullptr, [&](Workspace* ws) -> int {
+        const BatchGate gate = batch_gate(metric, 1, k);
+        if (gate_knn(gate, knn_route_.load() == 1, knn_rows_supported((uint32_t)dim_, metric))) {
+            stats[0] = 1;
+            const int frc = knn_mfma(ws, (uint32_t)k, metric, n_out, out_nbr_ids, out_scores, stats);
+            set_last_path(PATH_FAST);
+            return frc;
+        }
+        stats[0] = 2;
+        stats[4] = n;
+        const int erc = knn_exact_rows(ws, 0, n, (uint32_t)k, metric, n_out, out_nbr_ids, out_scores);
+        set_last_path(PATH_EXACT_SORT);
+        return erc;
+    });
+    if (rc != OK) return rc;
+    for (uint64_t e = 0; e < n_out * kk; ++e) {  // positions -> ids
+        if (out_nbr_ids[e] >= n) {
+            set_last_error("knn_graph returned an out-of-range position (kernel bug)");
+            return ERR_DEVICE;
+        }
+        out_nbr_ids[e] = ids_[out_nbr_ids[e]];
+    }
+    for (uint64_t p = 0; p < n_out; ++p) out_ids[p] = ids_[p];
+    *out_n = n_out;
+    *out_kk = kk;
+    publish();
+    return OK;
+}
+
+int GpuFlatIndex::knn_exact_rows(Workspace* ws, uint64_t r0, uint64_t r1, uint32_t k, int metric, uint64_t n_out, uint64_t* out_nbr,
+                                 double* out_scores) const
+{
+    const uint64_t n = ids_.size();
+    const uint64_t kk = std::min<uint64_t>(k, n - 1), fetch = std::min<uint64_t>((uint64_t)k + 1, n);
+    std::vector<double> rows(std::max<size_t>((size_t)(KNN_LOOP_ROWS * dim_), 1));
+    uint64_t pos[KNN_MAX_K + 1];
+    double sc[KNN_MAX_K + 1];
+    r1 = std::min(r1, n_out);
+    for (uint64_t g0 = r0; g0 < r1; g0 += KNN_LOOP_ROWS) {
+        const uint64_t g = std::min<uint64_t>(KNN_LOOP_ROWS, r1 - g0);
+        if (dim_) VL_HIP(hipMemcpy(rows.data(), d_master_ + g0 * dim_, (size_t)(g * dim_) * sizeof(double), hipMemcpyDeviceToHost));
+        for (uint64_t i = g0; i < g0 + g; ++i) {
+            uint64_t got = 0;
+            VL_TRY(search_locked(ws, rows.data() + (i - g0) * dim_, fetch, metric, pos, nullptr, sc, &got, false));
+            uint64_t m = 0;
+            for (uint64_t e = 0; e < got && m < kk; ++e) {  // position i is dropped where it appears
+                if (pos[e] == i) continue;
+                out_nbr[i * kk + m] = pos[e];
+                out_scores[i * kk + m] = sc[e];
+                ++m;
+            }
+            if (m != kk) {
+                set_last_error("knn_graph: the positional search returned too few rows");
+                return ERR_DEVICE;
+            }
+        }
+    }
+    return OK;
+}
+
+int GpuFlatIndex::knn_mfma(Workspace* ws, uint32_t k, int metric, uint64_t n_out, uint64_t* out_nbr, double* out_scores,
+                           uint64_t* stats) const
+{
+    const uint64_t n = ids_.size();
+    const uint32_t kk = k;  // the gate: n - 1 >= k
+    const uint32_t cap = knn_cap(knn_candidate_capacity(), k);
+    const uint32_t n_blocks = (uint32_t)((n + KNN_BLOCK_ROWS - 1) / KNN_BLOCK_ROWS);
+    const uint32_t step = std::min<uint32_t>(knn_range_blocks(cap, k), n_blocks);
+    const size_t rr = (size_t)step * KNN_BLOCK_ROWS;
+    const size_t rec_cap = (size_t)sort_capacity_for(rr * k + cap);
+    VL_TRY(ensure_bf16_slab(true));
+
+    MaxsimCarver dv{nullptr}, hv{nullptr};
+    KnnRows rows;
+    KnnCand* cand;
+    uint32_t *ctr, *h_ctr, *h_pos;
+    double* h_sc;
+    auto carve = [&]() {
+        rows.seeds = dv.take<uint32_t>(rr * k);
+        rows.thr = dv.take<float>(rr);
+        rows.rec_keys = dv.take<unsigned long long>(rec_cap);
+        rows.rec_pay = dv.take<KnnPay>(rec_cap);
+        rows.out_pos = dv.take<uint32_t>(rr * kk);
+        rows.out_scores = dv.take<double>(rr * kk);
+        cand = dv.take<KnnCand>(cap);
+        ctr = dv.take<uint32_t>(KNN_CTR_WORDS);
+        h_ctr = hv.take<uint32_t>(KNN_CTR_WORDS);
+        h_pos = hv.take<uint32_t>(rr * kk);
+        h_sc = hv.take<double>(rr * kk);
+    };
+    carve();
+    VL_TRY(ensure_maxsim_ws(ws, dv.off, hv.off));
+    dv = MaxsimCarver{ws->ms_dev};
+    hv = MaxsimCarver{ws->ms_host};
+    carve();
+
+    hipStream_t st = ws->stream;
+    VL_HIP(launch_maxsim_fill(st, ctr, KNN_CTR_WORDS, 0u));
+    std::vector<AssignRange> todo = assign_ranges(n_blocks, step);
+    while (!todo.empty()) {
+        const AssignRange r = todo.back();
+        todo.pop_back();
+        const uint64_t p0 = (uint64_t)r.b0 * KNN_BLOCK_ROWS, p1 = std::min<uint64_t>((uint64_t)r.b1 * KNN_BLOCK_ROWS, n);
+        const uint64_t range_rows = (uint64_t)(r.b1 - r.b0) * KNN_BLOCK_ROWS;
+        VL_HIP(launch_maxsim_fill(st, ctr + KNN_CTR_CAND, 1, 0u));
+        VL_HIP(launch_knn_rows(st, metric, 0, d_slab16f_, d_norm16_, n, (uint32_t)dim_, r, k, rows, cand, cap, ctr));
+        VL_HIP(launch_knn_seed(st, metric, d_master_, n, (uint32_t)dim_, r, k, max_row_norm_, rows, ctr));
+        VL_HIP(launch_knn_rows(st, metric, 1, d_slab16f_, d_norm16_, n, (uint32_t)dim_, r, k, rows, cand, cap, ctr));
+        VL_HIP(hipMemcpyAsync(h_ctr, ctr, KNN_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipStreamSynchronize(st));
+        stats[5] += 2;
+        if (h_ctr[KNN_CTR_NAN]) {
+            set_last_error("NaN similarity score: the reference panics in partial_cmp().unwrap()");
+            return ERR_NAN_SCORE;
+        }
+        const uint32_t kept = h_ctr[KNN_CTR_CAND];
+        if (kept > cap) {  // halved and run again, the lower half first; a single block goes to the exact route
+            if (assign_split(&todo, r)) {
+                stats[3] += 1;
+            } else {
+                stats[4] += p1 - p0;
+                VL_TRY(knn_exact_rows(ws, p0, p1, k, metric, n_out, out_nbr, out_scores));
+            }
+            continue;
+        }
+        stats[1] += (p1 - p0) * k;
+        stats[2] += kept;
+        const uint64_t total = range_rows * k + kept;
+        VL_HIP(launch_knn_pairs(st, metric, d_master_, n, (uint32_t)dim_, r, k, rows, cand, cap, ctr));
+        VL_HIP(launch_knn_rank(st, rows.rec_keys, rows.rec_pay, total));
+        VL_HIP(launch_knn_emit(st, n, r, kk, total, rows));
+        const uint64_t q1 = std::min<uint64_t>(p1, n_out);
+        if (p0 < q1) {
+            VL_HIP(hipMemcpyAsync(h_pos, rows.out_pos, (q1 - p0) * kk * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            VL_HIP(hipMemcpyAsync(h_sc, rows.out_scores, (q1 - p0) * kk * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        VL_HIP(hipMemcpyAsync(h_ctr, ctr, KNN_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipStreamSynchronize(st));
+        if (h_ctr[KNN_CTR_NAN]) {
+            set_last_error("NaN similarity score: the reference panics in partial_cmp().unwrap()");
+            return ERR_NAN_SCORE;
+        }
+        for (uint64_t e = 0; p0 < q1 && e < (q1 - p0) * kk; ++e) {
+            out_nbr[p0 * kk + e] = h_pos[e] == 0xFFFFFFFFu ? ~0ull : h_pos[e];  // (checked against len by the caller)
+            out_scores[p0 * kk + e] = h_sc[e];
+        }
+    }
+    return OK;
+}
+
 // Queries in device memory.  The MFMA batch path takes them where they are; everything else goes through the host.
 int GpuFlatIndex::search_batch_device(const double* d_queries, uint64_t nq, uint64_t q_len, uint64_t k, int metric,
                                       uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n) const

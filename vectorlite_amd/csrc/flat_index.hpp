@@ -24,6 +24,7 @@
 #include "batch_gate.hpp"
 #include "coalescer.hpp"
 #include "assign.hpp"
+#include "knn.hpp"
 #include "group_plan.hpp"
 #include "join.hpp"
 #include "kernels.hpp"
@@ -540,6 +541,25 @@ public:
     {
         for (int i = 0; i < 6; ++i) out6[i] = last_assign_[i].load(std::memory_order_relaxed);
     }
+    // NEW (no reference counterpart): the exact k-nearest-neighbour graph of the stored rows.
+    // 1 <= k <= KNN_MAX_K; *out_kk = min(k, len - 1).  For the row at storage position p < min(len, out_capacity): out_ids[p],
+    // and at [p kk, (p + 1) kk) of out_nbr_ids / out_scores its kk best OTHER positions: the positional search(row_p, k + 1)
+    // without position p, cut at kk (ties to the lower position, -0.0 == +0.0, the reference's own score bits).
+    int knn_graph(uint64_t k, int metric, uint64_t out_capacity, uint64_t* out_ids, uint64_t* out_nbr_ids, double* out_scores,
+                  uint64_t* out_n, uint64_t* out_kk) const;
+    // 0 auto, 1 exact, 2 mfma where eligible (today the same as auto)
+    int set_knn_route(int mode)
+    {
+        if (mode < 0 || mode > 2) return ERR_INVALID_ARG;
+        knn_route_.store(mode);
+        return OK;
+    }
+    // the last knn_graph on this handle: route (0 none, 1 mfma, 2 exact), seed candidates, kept candidates, ranges split, rows
+    // handed to the exact route, launches of the pass
+    void last_knn(uint64_t* out6) const
+    {
+        for (int i = 0; i < 6; ++i) out6[i] = last_knn_[i].load(std::memory_order_relaxed);
+    }
     // 0: always the loop.  1: the pass whenever the batch is eligible.  2 ("auto", the default): when its estimate is lower.
     void set_grouped_batch(int mode) { grouped_batch_.store(mode); }
     int grouped_batch() const { return grouped_batch_.load(); }
@@ -736,6 +756,11 @@ private:
                     double* out_scores, uint64_t* stats, bool* done) const;
     int assign_exact(Workspace* ws, const double* labels, uint32_t n_labels, int metric, uint64_t n_out, uint64_t* out_labels,
                      double* out_scores) const;
+    // knn_graph's body (mu_ held, n - 1 >= 1): the MFMA route over every row, and the exact route over the rows [r0, r1);
+    // both write positions and scores at stride kk for the rows below n_out
+    int knn_mfma(Workspace* ws, uint32_t k, int metric, uint64_t n_out, uint64_t* out_nbr, double* out_scores, uint64_t* stats) const;
+    int knn_exact_rows(Workspace* ws, uint64_t r0, uint64_t r1, uint32_t k, int metric, uint64_t n_out, uint64_t* out_nbr,
+                       double* out_scores) const;
     int wait_result(Workspace* ws, uint32_t seq) const;
     int ensure_i8_slab() const;  // lazily builds the int8 copy the single-query int8 filter streams
     int ensure_bf16_slab(bool frag_major) const;  // lazily builds the bf16 slab (row-major, or MFMA fragment order) a filter streams
@@ -921,6 +946,8 @@ private:
     mutable std::atomic<uint64_t> last_maxsim_[4] = {};
     mutable std::atomic<uint64_t> last_assign_[6] = {};
     std::atomic<int> assign_route_{0};  // 0 auto, 1 exact, 2 mfma
+    mutable std::atomic<uint64_t> last_knn_[6] = {};
+    std::atomic<int> knn_route_{0};  // 0 auto, 1 exact, 2 mfma
     std::atomic<int> join_route_{0};  // 0 auto, 1 loop, 2 mfma
     std::atomic<uint64_t> last_delete_[6] = {};
     std::atomic<uint64_t> last_update_[7] = {};

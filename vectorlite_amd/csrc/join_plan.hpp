@@ -100,7 +100,7 @@ constexpr double JOIN_SELF_EXTRA = 1e-12;
 constexpr double JOIN_IN_EXTRA = 0.0079;  // IN_EXTRA_MFMA (mfma_scan.hpp; asserted equal in join.hip)
 
 // upper bound on the reference score of a pair whose key is <= t (weakly increasing in t, like bound_for_key)
-inline double join_bound_for_key(float t, uint32_t n)
+VL_BOUND_HD double join_bound_for_key(float t, uint32_t n)
 {
     return bound_for_key<BOUND_COSINE>(t, n, 1.0, 1.0, JOIN_IN_EXTRA) + JOIN_SELF_EXTRA;
 }
@@ -108,7 +108,7 @@ inline double join_bound_for_key(float t, uint32_t n)
 // The smallest key that is not provably below min_score (range_key_threshold's convention and return values).  The additive
 // term moves the score threshold instead of the bound: bound(t) + E >= s is tested as bound(t) >= fl(s - E), and the one
 // rounding of s - E (2^-53 relative) is covered by E's factor of two over what it has to hold.
-inline RangeKeys join_key_threshold(uint32_t n, double min_score, float* thr)
+VL_BOUND_HD RangeKeys join_key_threshold(uint32_t n, double min_score, float* thr)
 {
     return range_key_threshold(BOUND_COSINE, n, 1.0, 1.0, min_score - JOIN_SELF_EXTRA, JOIN_IN_EXTRA, thr);
 }
@@ -117,7 +117,7 @@ inline RangeKeys join_key_threshold(uint32_t n, double min_score, float* thr)
 // c = the pair's cosine key.  The real cosine of two non-zero rows is at most C(c) = c + E: join_bound_for_key's additive
 // terms (the bound on the reference's f64 cosine) plus 2e-12 for that f64 cosine's own distance from the real one
 // ((n + 4) 2^-52 < 1.8e-13) and for the f64 terms listed at join_pair_bound.  Derivation in DESIGN.md section 29.
-inline double join_pair_extra(uint32_t n)
+VL_BOUND_HD double join_pair_extra(uint32_t n)
 {
     return join_bound_for_key(0.0f, n) + 2e-12;
 }
@@ -128,7 +128,7 @@ inline double join_pair_extra(uint32_t n)
 //   Euclidean:  dist^2 >= na^2 + nb^2 - 2 na nb C(c); the reference's sum of squared differences, its sqrt and 1 / (1 + d)
 //               stay inside the (1 - 1e-12) and (1 + 1e-15) factors bound_for_key<EUCLIDEAN> uses for the same steps.
 template <int METRIC>
-inline double join_pair_bound(float c, uint32_t n, double na, double nb)
+VL_BOUND_HD double join_pair_bound(float c, uint32_t n, double na, double nb)
 {
     static_assert(METRIC == BOUND_DOT || METRIC == BOUND_EUCLIDEAN, "cosine has join_bound_for_key");
     const double p = na * nb;
@@ -140,12 +140,12 @@ inline double join_pair_bound(float c, uint32_t n, double na, double nb)
 }
 
 // x rounded to f32 upwards / downwards (+-inf and values beyond the f32 range included)
-inline float join_f32_up(double x)
+VL_BOUND_HD float join_f32_up(double x)
 {
     const float f = (float)x;
     return (double)f < x ? ordered_to_f32(f32_to_ordered(f) + 1u) : f;
 }
-inline float join_f32_down(double x)
+VL_BOUND_HD float join_f32_down(double x)
 {
     const float f = (float)x;
     return (double)f > x ? ordered_to_f32(f32_to_ordered(f) - 1u) : f;
@@ -157,7 +157,7 @@ inline float join_f32_down(double x)
 // na32 * nb32 and the product with it, and for Euclidean 6.4 u for the squares, their sum and the final difference, which
 // are relative to na^2 + nb^2 <= dist^2 + 2 na nb and so split into a relative term on dist^2 (join_pair_threshold) and
 // this one.
-inline float join_pair_e32(uint32_t n)
+VL_BOUND_HD float join_pair_e32(uint32_t n)
 {
     return join_f32_up(join_pair_extra(n) + 16.0 * 5.9604644775390625e-08);
 }
@@ -185,7 +185,7 @@ VL_XCD_HD inline float join_pair_key(float c, float e32, float na, float nb)
 //   Euclidean:  thr = -T rounded down, T = D^2 (1 + 8 u), D the largest distance whose bound reaches min_score:
 //               D = ((1 + 1e-15) / min_score - 1) / (1 - 1e-12), with 2^-50 added for the rounding of the quotient and the
 //               subtraction and a factor 1 + 1e-11 over the f64 steps of this function.
-inline RangeKeys join_pair_threshold(int metric, uint32_t n, double R, double min_score, float* thr)
+VL_BOUND_HD RangeKeys join_pair_threshold(int metric, uint32_t n, double R, double min_score, float* thr)
 {
     const bool dot = metric == BOUND_DOT;
     auto bound = [&](float c) { return dot ? join_pair_bound<BOUND_DOT>(c, n, R, R) : join_pair_bound<BOUND_EUCLIDEAN>(c, n, R, R); };

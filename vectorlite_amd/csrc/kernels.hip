@@ -25,6 +25,7 @@
 #include "scan_stream.hpp"
 #include "score_bound.hpp"
 #include "join.hpp"
+#include "knn.hpp"
 
 #include <math.h>
 #include <stdlib.h>
@@ -3285,6 +3286,26 @@ hipError_t launch_join_rank(hipStream_t s, unsigned long long* sv_keys, JoinPay*
     const int pgrid = (int)((cap / 256) < 4096 ? (cap / 256) : 4096);
     hipLaunchKernelGGL(k_join_pad, dim3(pgrid), dim3(256), 0, s, sv_keys, sv_pay, total, cap);
     bitonic_network<JoinPay>(s, sv_keys, sv_pay, cap);
+    return hipGetLastError();
+}
+
+// ---- k-nearest-neighbour graph: the ranking behind knn.hip's scoring kernels -------------------------
+// records that sort last, from the record count up to the sort's capacity
+__global__ void k_knn_pad(unsigned long long* __restrict__ keys, KnnPay* __restrict__ pay, uint64_t total, uint64_t cap)
+{
+    for (uint64_t i = total + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * blockDim.x) {
+        keys[i] = ~0ull;
+        pay[i] = KnnPay{~0ull, 0xFFFFFFFFu, 0u};
+    }
+}
+
+hipError_t launch_knn_rank(hipStream_t s, unsigned long long* rec_keys, KnnPay* rec_pay, uint64_t total)
+{
+    if (total == 0 || total >= 0xFFFFFFFFull) return hipErrorInvalidValue;
+    const uint64_t cap = sort_capacity_for(total);
+    const int pgrid = (int)((cap / 256) < 4096 ? (cap / 256) : 4096);
+    hipLaunchKernelGGL(k_knn_pad, dim3(pgrid), dim3(256), 0, s, rec_keys, rec_pay, total, cap);
+    bitonic_network<KnnPay>(s, rec_keys, rec_pay, cap);
     return hipGetLastError();
 }
 

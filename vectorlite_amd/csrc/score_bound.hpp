@@ -58,15 +58,15 @@ VL_BOUND_HD double bound_for_key(float t_key, uint32_t n, double R, double Q, do
     return (1.0 / (1.0 + d_lo * (1.0 - 1e-12))) * (1.0 + 1e-15);
 }
 
-// ---- the score threshold of a range search, in key space (host) ------------------------------------------------------
+// ---- the score threshold of a range search, in key space (host; per row in k_knn_seed) -------------------------------
 // f32 values from -inf to +inf as unsigned integers in ascending order (-0.0 directly below +0.0), and back.
-inline uint32_t f32_to_ordered(float f)
+VL_BOUND_HD uint32_t f32_to_ordered(float f)
 {
     uint32_t b;
     memcpy(&b, &f, sizeof b);
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
-inline float ordered_to_f32(uint32_t o)
+VL_BOUND_HD float ordered_to_f32(uint32_t o)
 {
     const uint32_t b = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
     float f;
@@ -81,7 +81,7 @@ inline float ordered_to_f32(uint32_t o)
 // The device tests !(key <= tau), which keeps a NaN key among the candidates.
 // `in_extra`: the bound's input-rounding term of the filter whose keys are compared (0: the f32 scan).
 template <int METRIC>
-inline bool range_tau(uint32_t n, double R, double Q, double min_score, float* tau, double in_extra = 0.0)
+VL_BOUND_HD bool range_tau(uint32_t n, double R, double Q, double min_score, float* tau, double in_extra = 0.0)
 {
     auto out = [&](uint32_t o) { return bound_for_key<METRIC>(ordered_to_f32(o), n, R, Q, in_extra) < min_score; };
     uint32_t lo = f32_to_ordered(-INFINITY), hi = f32_to_ordered(INFINITY);
@@ -99,7 +99,7 @@ inline bool range_tau(uint32_t n, double R, double Q, double min_score, float* t
     return true;
 }
 
-inline bool range_tau(int metric, uint32_t n, double R, double Q, double min_score, float* tau, double in_extra = 0.0)
+VL_BOUND_HD bool range_tau(int metric, uint32_t n, double R, double Q, double min_score, float* tau, double in_extra = 0.0)
 {
     switch (metric) {
     case BOUND_COSINE: return range_tau<BOUND_COSINE>(n, R, Q, min_score, tau, in_extra);
@@ -115,7 +115,7 @@ inline bool range_tau(int metric, uint32_t n, double R, double Q, double min_sco
 // -- every row is a candidate and *thr is not written.  RANGE_KEYS_NONE: every key is provably out (a +inf threshold) --
 // no row can qualify; *thr = +inf, which no finite key reaches.
 enum RangeKeys : int { RANGE_KEYS_ALL = 0, RANGE_KEYS_FROM = 1, RANGE_KEYS_NONE = 2 };
-inline RangeKeys range_key_threshold(int metric, uint32_t n, double R, double Q, double min_score, double in_extra, float* thr)
+VL_BOUND_HD RangeKeys range_key_threshold(int metric, uint32_t n, double R, double Q, double min_score, double in_extra, float* thr)
 {
     float tau = 0.0f;
     if (!range_tau(metric, n, R, Q, min_score, &tau, in_extra)) return RANGE_KEYS_ALL;
