@@ -655,6 +655,38 @@ int vl_index_knn_graph(const vl_index *h, uint64_t k, int metric, uint64_t out_c
 int vl_index_set_knn_route(vl_index *h, int mode); /* 0 auto (default), 1 exact, 2 mfma where eligible */
 int vl_index_last_knn(const vl_index *h, uint64_t *out6);
 
+/* NEW (no reference counterpart): search by positive and negative examples, "rows like any of these, and unlike those" --
+ * the recommendation / discovery call: several liked items, a few disliked ones, one ranked answer.
+ * positives: [n_pos, q_len], 1 <= n_pos <= VL_EXAMPLES_MAX_POS; negatives: [n_neg, q_len], 0 <= n_neg <= VL_EXAMPLES_MAX_NEG
+ * (may be NULL when n_neg == 0).  With s(q, x) the reference score vl_index_search returns for `metric`, for every stored
+ * row x:
+ *     P(x) = max_i s(p_i, x)        N(x) = max_j s(n_j, x)  (n_neg > 0)        (the maxima treat -0.0 as below +0.0)
+ *     f(x) = P(x)           if n_neg == 0 or P(x) > N(x)   (strict)
+ *          = -(N(x) N(x))   otherwise                      (one f64 multiply, then the negation)
+ * The answer is the k rows of largest f as (id, f bits), ties to the lower storage position; *out_n = min(k, len,
+ * out_capacity), and the answer for a smaller k is a prefix of the answer for a larger one.  One positive and no negative:
+ * vl_index_search.
+ * VL_ERR_NAN_SCORE iff some s(example, x) over a stored row is NaN.  VL_ERR_DIM_MISMATCH as in vl_index_search (whenever
+ * len != 0).  VL_ERR_INVALID_ARG: n_pos or n_neg outside their limits, an unknown metric -- checked in that order, before
+ * the dimension.  k = 0 or an empty index: *out_n = 0, VL_OK.  Single-GPU flat handles only.  The call holds the handle's
+ * shared lock throughout, borrows a workspace and never joins a coalesced pass.
+ * Route (vl_index_last_examples, vl_last_path):
+ *   mfma   (VL_PATH_FAST) cosine / Euclidean / dot, a row length up to 768, k <= 64, in-domain rows and examples, no forced
+ *          path, VL_MFMA not 0: one bf16 MFMA pass leaves two floats per row (the best key of each side on a scale shared
+ *          by the examples); the 64 rows of largest estimated f are scored exactly, and every row whose upper bound reaches
+ *          the k-th best of those scores is scored exactly and ranked.
+ *   exact  (VL_PATH_EXACT_SORT) otherwise, and whenever more than 8192 rows (VL_EXAMPLES_CAND_CAP in the environment lowers
+ *          it) survive the bound: one exact scan per example folded into P and N, then the exact selection or sort.
+ * Both routes return the same bits.
+ * vl_index_last_examples, four words of the last call on this handle: route (0 none, 1 mfma, 2 exact), seed rows scored,
+ * survivor rows, 16-example blocks of the pass. */
+#define VL_EXAMPLES_MAX_POS 64
+#define VL_EXAMPLES_MAX_NEG 32
+int vl_index_search_examples(const vl_index *h, const double *positives, uint64_t n_pos, const double *negatives,
+                             uint64_t n_neg, uint64_t q_len, uint64_t k, int metric, uint64_t out_capacity,
+                             uint64_t *out_ids, double *out_scores, uint64_t *out_n);
+int vl_index_last_examples(const vl_index *h, uint64_t *out4);
+
 uint64_t vl_index_len(const vl_index *h);      /* len()       src/index/flat.rs:121-123 */
 int vl_index_is_empty(const vl_index *h);      /* is_empty()  src/index/flat.rs:125-127 */
 uint64_t vl_index_dimension(const vl_index *h);/* dimension() src/index/flat.rs:133-135 */

@@ -559,6 +559,38 @@ def _last_maxsim(L, h) -> Dict[str, int]:
     return d
 
 
+def _search_examples(L, h, positives, negatives, k: int, metric: int):
+    """vl_index_search_examples -> (ids, scores), best row first."""
+    P = np.ascontiguousarray(_f64(positives))
+    if P.ndim != 2:
+        raise ValueError("positives must be [n_pos, dim]")
+    n_pos, q_len = P.shape
+    N = np.zeros((0, q_len)) if negatives is None else np.ascontiguousarray(_f64(negatives))
+    if N.ndim != 2 or (N.shape[0] and N.shape[1] != q_len):
+        raise ValueError("negatives must be [n_neg, dim] with the positives' dim")
+    k = min(max(int(k), 0), 1 << 62)
+    cap = max(min(k, int(L.vl_index_len(h))), 1)
+    ids = np.empty(cap, dtype=np.uint64)
+    scores = np.empty(cap, dtype=np.float64)
+    n = C.c_uint64(0)
+    rc = L.vl_index_search_examples(h, P.ctypes.data, n_pos, N.ctypes.data if N.shape[0] else None, N.shape[0], q_len, k,
+                                    int(metric), cap, ids.ctypes.data, scores.ctypes.data, C.byref(n))
+    if rc == VL_ERR_INVALID_ARG:
+        raise IndexOpError(_last_error())
+    _raise(rc)
+    m = int(n.value)
+    return ids[:m].copy(), scores[:m].copy()
+
+
+def _last_examples(L, h) -> Dict[str, int]:
+    out = np.zeros(4, dtype=np.uint64)
+    if L.vl_index_last_examples(h, out.ctypes.data) != 0:
+        raise IndexOpError(_last_error())
+    d = {k: int(v) for k, v in zip(("route", "seeds", "survivors", "blocks"), out)}
+    d["route"] = {1: "mfma", 2: "exact"}.get(d["route"], d["route"])
+    return d
+
+
 ASSIGN_ROUTES = {"auto": 0, "exact": 1, "mfma": 2}
 
 
@@ -1170,6 +1202,27 @@ class FlatIndex:
         """The last search_maxsim on this handle (vl_index_last_maxsim): route ("mfma" or "exact"), survivor groups, their
         member rows, token chunks of the candidate pass."""
         return _last_maxsim(self._L, self._h)
+
+    # ---- search by positive and negative examples ----------------------------------------------
+    def search_examples_arrays(self, positives, negatives=None, k: int = 10, metric: int = 0):
+        """(ids, scores) of the k rows of largest f for positives [n_pos, dim] (1 <= n_pos <= 64) and negatives [n_neg, dim]
+        (n_neg <= 32, or None): with P(x) / N(x) the best reference score of row x among the positives / negatives, f = P
+        when there is no negative or P > N, else -(N * N).  Ties come out by storage position
+        (vl_index_search_examples)."""
+        return _search_examples(self._L, self._h, positives, negatives, k, metric)
+
+    def search_examples(self, positives, negatives=None, k: int = 10, metric: int = SimilarityMetric.Cosine) -> List[SearchResult]:
+        ids, scores = self.search_examples_arrays(positives, negatives, k, metric)
+        out = []
+        for i, s in zip(ids.tolist(), scores.tolist()):
+            text, md = self._meta.get(i, ("", None))
+            out.append(SearchResult(id=i, score=s, text=text, metadata=md))
+        return out
+
+    def last_examples(self) -> Dict[str, int]:
+        """The last search_examples on this handle (vl_index_last_examples): route ("mfma" or "exact"), seed rows scored,
+        survivor rows, 16-example blocks of the candidate pass."""
+        return _last_examples(self._L, self._h)
 
     # ---- nearest-label assignment of every stored row -----------------------------------------
     def assign(self, labels, metric: int = 0):

@@ -5,6 +5,7 @@
 
 #include <stdint.h>
 
+#include "examples_plan.hpp"
 #include "masked_batch_plan.hpp"
 
 namespace vl {
@@ -87,6 +88,15 @@ inline bool gate_knn(const BatchGate& g, bool route_exact, bool has_pass)
 {
     return !route_exact && has_pass && g.rows_kernel && gate_tail_index(g) && g.rows < 0xFFFFFFE0ull && g.rows >= 1 &&
            g.rows - 1 >= g.k_eff;
+}
+
+// The search by examples: g.nq = the examples, g.k_eff = k.  gate_assign's conditions with the forced
+// path in the route setter's place (gate_core reads it); on top of them the seed list must hold k rows.  `has_pass` =
+// cosine, Euclidean or dot; `examples_in_domain` = every positive and negative is inside the fast-path domain.
+inline bool gate_examples(const BatchGate& g, bool has_pass, bool examples_in_domain)
+{
+    return has_pass && g.rows_kernel && gate_tail_index(g) && examples_in_domain && g.rows < 0xFFFFFFE0ull &&
+           g.k_eff <= EXAMPLES_FAST_MAX_K;
 }
 
 }  // namespace vl

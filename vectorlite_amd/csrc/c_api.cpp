@@ -880,6 +880,48 @@ int vl_index_last_knn(const vl_index* h, uint64_t* out6)
     return VL_OK;
 }
 
+static_assert(VL_EXAMPLES_MAX_POS == vl::EXAMPLES_MAX_POS && VL_EXAMPLES_MAX_NEG == vl::EXAMPLES_MAX_NEG,
+              "the header states the kernels' limits");
+
+int vl_index_search_examples(const vl_index* h, const double* positives, uint64_t n_pos, const double* negatives, uint64_t n_neg,
+                             uint64_t q_len, uint64_t k, int metric, uint64_t out_capacity, uint64_t* out_ids, double* out_scores,
+                             uint64_t* out_n)
+{
+    return guarded([&]() -> int {
+        if (out_n) *out_n = 0;
+        if (n_pos < 1 || n_pos > VL_EXAMPLES_MAX_POS) {  // before the handle is looked at: no device is needed
+            vl::set_last_error("search by examples: n_pos must lie in [1, VL_EXAMPLES_MAX_POS (64)]");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (n_neg > VL_EXAMPLES_MAX_NEG) {
+            vl::set_last_error("search by examples: n_neg exceeds VL_EXAMPLES_MAX_NEG (32)");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (metric < 0 || metric > 3) {
+            vl::set_last_error("search by examples: unknown metric");
+            return VL_ERR_INVALID_ARG;
+        }
+        if (!h || !out_n) return VL_ERR_INVALID_ARG;
+        if (!h->flat) {
+            vl::set_last_error("search by examples is served by single-GPU flat indexes");
+            return VL_ERR_INVALID_ARG;
+        }
+        if ((!out_ids || !out_scores) && k != 0 && out_capacity != 0) return VL_ERR_INVALID_ARG;
+        return h->flat->search_examples(positives, n_pos, negatives, n_neg, q_len, k, metric, out_capacity, out_ids, out_scores, out_n);
+    });
+}
+
+int vl_index_last_examples(const vl_index* h, uint64_t* out4)
+{
+    if (!h || !out4) return VL_ERR_INVALID_ARG;
+    if (!h->flat) {
+        vl::set_last_error("search by examples is served by single-GPU flat indexes");
+        return VL_ERR_INVALID_ARG;
+    }
+    h->flat->last_examples(out4);
+    return VL_OK;
+}
+
 int vl_index_search_grouped_batch(const vl_index* h, uint64_t groups, uint64_t filter, const double* queries, uint64_t nq,
                                   uint64_t q_len, uint64_t k, int metric, uint64_t out_stride, uint64_t* out_group_keys,
                                   uint64_t* out_ids, double* out_scores, uint64_t* out_n)

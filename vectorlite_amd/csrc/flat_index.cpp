@@ -5038,6 +5038,299 @@ int GpuFlatIndex::search_batch_device(const double* d_queries, uint64_t nq, uint
 }
 
 // ---------------------------------------------------------------------------------------------
+// Search by positive and negative examples: f(x) fuses the reference scores of row x against every
+// example.  The MFMA route: one candidate pass (examples.hip) leaves per row the best mapped bf16 key of each side; the 64
+// rows of largest estimated f are scored exactly, L = the k-th best of those f, and every row whose upper bound U reaches L
+// -- no other row can be among the k best -- is scored exactly and ranked on the device.
+// The exact route is the definition: per example one exact scan folded into P[x] / N[x], then f[x] through the exact
+// selection or sort.
+// ---------------------------------------------------------------------------------------------
+namespace {
+uint32_t examples_candidate_capacity()
+{
+    // VL_EXAMPLES_CAND_CAP: fewer survivor rows per call (tests drive the hand-over to the exact route with it)
+    if (const char* e = getenv("VL_EXAMPLES_CAND_CAP")) {
+        const long long v = atoll(e);
+        if (v >= 1 && v <= (long long)EXAMPLES_CAND_CAP) return (uint32_t)v;
+    }
+    return EXAMPLES_CAND_CAP;
+}
+constexpr const char* EXAMPLES_NAN = "NaN similarity score: the reference panics in partial_cmp().unwrap()";
+}  // namespace
+
+int GpuFlatIndex::search_examples(const double* positives, uint64_t n_pos, const double* negatives, uint64_t n_neg, uint64_t q_len,
+                                  uint64_t k, int metric, uint64_t out_capacity, uint64_t* out_ids, double* out_scores,
+                                  uint64_t* out_n) const
+{
+    if (!out_n) return ERR_INVALID_ARG;
+    *out_n = 0;
+    set_last_path(PATH_NONE);
+    if (n_pos < 1 || n_pos > EXAMPLES_MAX_POS) {
+        set_last_error("search by examples: n_pos must lie in [1, VL_EXAMPLES_MAX_POS (64)]");
+        return ERR_INVALID_ARG;
+    }
+    if (n_neg > EXAMPLES_MAX_NEG) {
+        set_last_error("search by examples: n_neg exceeds VL_EXAMPLES_MAX_NEG (32)");
+        return ERR_INVALID_ARG;
+    }
+    std::shared_lock<RwLock> lk;  // one index state for the whole call
+    VL_TRY(lock_for_query(metric, q_len, &lk));
+    uint64_t stats[4] = {0, 0, 0, 0};
+    auto publish = [&]() {
+        for (int i = 0; i < 4; ++i) last_examples_[i].store(stats[i], std::memory_order_relaxed);
+    };
+    if (ids_.empty() || k == 0) {
+        publish();
+        return OK;
+    }
+    if (((!positives || (n_neg && !negatives)) && dim_) || (out_capacity != 0 && (!out_ids || !out_scores))) return ERR_INVALID_ARG;
+    const uint32_t a = (uint32_t)n_pos, b = (uint32_t)n_neg;
+    const int rc = run_search(nullptr, nullptr, [&](Workspace* ws) -> int {
+        const BatchGate gate = batch_gate(metric, n_pos + n_neg, k);
+        bool fast = gate_examples(gate, examples_rows_supported((uint32_t)dim_, metric), true);
+        for (uint32_t i = 0; fast && i < a; ++i) fast = query_in_domain(positives + (size_t)i * dim_, dim_);
+        for (uint32_t i = 0; fast && i < b; ++i) fast = query_in_domain(negatives + (size_t)i * dim_, dim_);
+        if (fast) {
+            bool certified = false;
+            VL_TRY(examples_mfma(ws, positives, a, negatives, b, k, metric, out_capacity, out_ids, out_scores, out_n, stats, &certified));
+            if (certified) {
+                stats[0] = 1;
+                set_last_path(PATH_FAST);
+                return OK;
+            }
+        }
+        stats[0] = 2;
+        set_last_path(PATH_EXACT_SORT);
+        return examples_exact(ws, positives, a, negatives, b, k, metric, out_capacity, out_ids, out_scores, out_n);
+    });
+    if (rc == OK) publish();
+    return rc;
+}
+
+int GpuFlatIndex::examples_mfma(Workspace* ws, const double* positives, uint32_t a, const double* negatives, uint32_t b, uint64_t k,
+                                int metric, uint64_t out_capacity, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
+                                uint64_t* stats, bool* certified) const
+{
+    *certified = false;
+    const uint64_t n = ids_.size();
+    const uint32_t ldb = mfma_ldb((uint32_t)dim_);
+    const uint32_t cap = examples_candidate_capacity();
+    const uint32_t T = a + b, pb = examples_blocks(a);
+    const size_t an = (size_t)a * dim_, qn = (size_t)T * dim_;
+    // the staging kernel pads each side to a whole chunk of maxsim_qpb(ldb) <= 128 image rows; the negatives start at row 16 pb
+    constexpr uint32_t Q_ROWS = EXAMPLES_MAX_POS + 128;
+    VL_TRY(ensure_bf16_slab(true));
+
+    MaxsimCarver dv{nullptr}, hv{nullptr};
+    double *q_src, *q64, *q_norm, *q_max, *f, *o_f, *h_q, *h_f, *h_o_f;
+    unsigned char *q16, *h_dom;
+    uint32_t *cnt, *list, *ctr, *o_pos, *h_ctr, *h_o_pos;
+    ExamplesMap* map;
+    float2* K;
+    Cand32* lists;
+    auto carve = [&]() {
+        q_src = dv.take<double>(qn);
+        q64 = dv.take<double>(qn);
+        q_norm = dv.take<double>(T);
+        q_max = dv.take<double>(1);
+        q16 = dv.take<unsigned char>((size_t)Q_ROWS * ldb * 2);
+        cnt = dv.take<uint32_t>(Q_ROWS);
+        map = dv.take<ExamplesMap>(EXAMPLES_MAX_COLS);
+        K = dv.take<float2>(n);
+        lists = dv.take<Cand32>((size_t)EXAMPLES_TOP_LISTS * KP);
+        list = dv.take<uint32_t>(EXAMPLES_CAND_CAP);
+        f = dv.take<double>(EXAMPLES_CAND_CAP);
+        ctr = dv.take<uint32_t>(EXAMPLES_CTR_WORDS);
+        o_pos = dv.take<uint32_t>(KP);
+        o_f = dv.take<double>(KP);
+        h_q = hv.take<double>(qn);
+        h_dom = hv.take<unsigned char>(T);
+        h_ctr = hv.take<uint32_t>(EXAMPLES_CTR_WORDS);
+        h_f = hv.take<double>(KP);
+        h_o_pos = hv.take<uint32_t>(KP);
+        h_o_f = hv.take<double>(KP);
+    };
+    carve();
+    VL_TRY(ensure_maxsim_ws(ws, dv.off, hv.off));
+    dv = MaxsimCarver{ws->ms_dev};
+    hv = MaxsimCarver{ws->ms_host};
+    carve();
+
+    // ---- staging: the f64 copy, the norms and the bf16 image, positives first, the negatives from a fresh 16-column block ----
+    hipStream_t st = ws->stream;
+    memcpy(h_q, positives, an * sizeof(double));
+    if (b) memcpy(h_q + an, negatives, (qn - an) * sizeof(double));
+    VL_HIP(hipMemcpyAsync(q_src, h_q, qn * sizeof(double), hipMemcpyHostToDevice, st));
+    for (int side = 0; side < (b ? 2 : 1); ++side) {
+        const uint32_t e0 = side ? a : 0u, m = side ? b : a, row0 = side ? 16u * pb : 0u;
+        MfmaScratch w;
+        w.q_bf16 = q16 + (size_t)row0 * ldb * 2;
+        w.cnt = cnt + row0;
+        w.nq_cap = EXAMPLES_MAX_POS;
+        w.nq_pad_cap = Q_ROWS - row0;
+        hipError_t pe = hipSuccess;
+        if (!launch_prepare_queries(st, q_src + (size_t)e0 * dim_, m, (uint32_t)dim_, DOMAIN_MAX_ABS, DOMAIN_MIN_NORM,
+                                    q64 + (size_t)e0 * dim_, q_norm + e0, h_dom + e0, w, &pe))
+            return OK;
+        VL_HIP(pe);
+    }
+    VL_HIP(launch_maxsim_fill(st, ctr, EXAMPLES_CTR_WORDS, 0u));
+    VL_HIP(launch_examples_map(st, metric, q_norm, a, b, map, q_max));
+    ExamplesRowsInfo info;
+    VL_HIP(launch_examples_rows(st, metric, d_slab16f_, d_norm16_, d_sqnorm_, q16, map, a, b, n, (uint32_t)dim_, K, &info));
+    // round 1: the 64 rows of largest estimated f, scored exactly
+    VL_HIP(launch_examples_seed(st, metric, K, n, b != 0, lists, list, ctr));
+    VL_HIP(launch_examples_exact(st, metric, d_master_, q64, a, b, (uint32_t)dim_, list, ctr + EXAMPLES_CTR_SEEDS, (uint32_t)KP, n, f, ctr));
+    VL_HIP(hipMemcpyAsync(h_ctr, ctr, EXAMPLES_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    VL_HIP(hipMemcpyAsync(h_f, f, KP * sizeof(double), hipMemcpyDeviceToHost, st));
+    VL_HIP(hipStreamSynchronize(st));
+    stats[3] = (uint64_t)info.blocks;
+    for (uint32_t i = 0; i < T; ++i)
+        if (!h_dom[i]) return OK;  // (the host's verdict, confirmed by the device's)
+    if (h_ctr[EXAMPLES_CTR_NAN]) {
+        set_last_error(EXAMPLES_NAN);
+        return ERR_NAN_SCORE;
+    }
+    const uint64_t c = h_ctr[EXAMPLES_CTR_SEEDS], k_eff = std::min<uint64_t>(k, n);
+    if (c != std::min<uint64_t>(n, KP) || k_eff > c || k_eff == 0) {
+        set_last_error("search by examples counted its seeds inconsistently (kernel bug)");
+        return ERR_DEVICE;
+    }
+    stats[1] = c;
+    // L = the k-th best exact f among them: k rows reach L, so the k-th best f overall is >= L
+    std::vector<double> top(h_f, h_f + c);
+    std::nth_element(top.begin(), top.begin() + (k_eff - 1), top.end(), [](double x, double y) { return x > y; });
+    const double L = top[k_eff - 1];
+
+    // round 2: every row whose upper bound reaches L, ties included
+    VL_HIP(launch_examples_survivors(st, metric, K, n, b != 0, ldb, max_row_norm_, q_max, L, cap, list, ctr));
+    VL_HIP(launch_examples_exact(st, metric, d_master_, q64, a, b, (uint32_t)dim_, list, ctr + EXAMPLES_CTR_SURVIVORS, cap, n, f, ctr));
+    VL_HIP(launch_examples_rank(st, list, f, ctr + EXAMPLES_CTR_SURVIVORS, cap, (uint32_t)k_eff, o_pos, o_f));
+    VL_HIP(hipMemcpyAsync(h_ctr, ctr, EXAMPLES_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    VL_HIP(hipMemcpyAsync(h_o_pos, o_pos, k_eff * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    VL_HIP(hipMemcpyAsync(h_o_f, o_f, k_eff * sizeof(double), hipMemcpyDeviceToHost, st));
+    VL_HIP(hipStreamSynchronize(st));
+    const uint64_t sv = h_ctr[EXAMPLES_CTR_SURVIVORS];
+    stats[2] = sv;
+    if (sv > cap) return OK;  // the cap exceeded: the exact route answers
+    if (h_ctr[EXAMPLES_CTR_NAN]) {
+        set_last_error(EXAMPLES_NAN);
+        return ERR_NAN_SCORE;
+    }
+    if (sv < k_eff || sv > n) {
+        set_last_error("search by examples lost a row between its rounds (kernel bug)");
+        return ERR_DEVICE;
+    }
+    const uint64_t want = std::min<uint64_t>(k_eff, out_capacity);
+    for (uint64_t i = 0; i < want; ++i) {
+        if (h_o_pos[i] >= n) {
+            set_last_error("search by examples returned an out-of-range position (kernel bug)");
+            return ERR_DEVICE;
+        }
+        out_ids[i] = ids_[h_o_pos[i]];
+        out_scores[i] = h_o_f[i];
+    }
+    *out_n = want;
+    *certified = true;
+    return OK;
+}
+
+int GpuFlatIndex::examples_exact(Workspace* ws, const double* positives, uint32_t a, const double* negatives, uint32_t b, uint64_t k,
+                                 int metric, uint64_t out_capacity, uint64_t* out_ids, double* out_scores, uint64_t* out_n) const
+{
+    const uint64_t n = ids_.size(), k_eff = std::min<uint64_t>(k, n);
+    const size_t an = (size_t)a * dim_, qn = (size_t)(a + b) * dim_;
+    MaxsimCarver dv{nullptr}, hv{nullptr};
+    double *q64, *P, *N, *h_q;
+    uint32_t *ctr, *h_ctr;
+    auto carve = [&]() {
+        q64 = dv.take<double>(qn + 1);
+        P = dv.take<double>(n);
+        N = dv.take<double>(b ? n : 1);
+        ctr = dv.take<uint32_t>(EXAMPLES_CTR_WORDS);
+        h_q = hv.take<double>(qn + 1);
+        h_ctr = hv.take<uint32_t>(EXAMPLES_CTR_WORDS);
+    };
+    carve();
+    VL_TRY(ensure_maxsim_ws(ws, dv.off, hv.off));
+    dv = MaxsimCarver{ws->ms_dev};
+    hv = MaxsimCarver{ws->ms_host};
+    carve();
+    VL_TRY(ensure_scores(ws, n));
+
+    hipStream_t st = ws->stream;
+    if (an) memcpy(h_q, positives, an * sizeof(double));
+    if (qn > an) memcpy(h_q + an, negatives, (qn - an) * sizeof(double));
+    VL_HIP(hipMemcpyAsync(q64, h_q, (qn + 1) * sizeof(double), hipMemcpyHostToDevice, st));
+    VL_HIP(launch_maxsim_fill(st, ctr, EXAMPLES_CTR_WORDS, 0u));
+    for (uint32_t i = 0; i < a + b; ++i) {
+        VL_HIP(launch_exact_scan(st, metric, d_master_, q64 + (size_t)i * dim_, n, (uint32_t)dim_, ws->d_scores, ctr + EXAMPLES_CTR_NAN));
+        VL_HIP(launch_examples_fold(st, ws->d_scores, n, i == 0 || i == a, i < a ? P : N, ctr));
+    }
+    VL_HIP(launch_examples_fuse(st, P, b ? N : nullptr, n, ws->d_scores));
+    VL_HIP(hipMemcpyAsync(h_ctr, ctr, EXAMPLES_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+
+    // the k best by (f desc, position asc): run_exact's rounds of 64 or the full sort
+    std::vector<uint32_t> pos;
+    std::vector<double> scores;
+    try {
+        pos.resize(k_eff);
+        scores.resize(k_eff);
+    } catch (const std::bad_alloc&) {
+        set_last_error("out of host memory collecting the answer");
+        return ERR_OOM;
+    }
+    const uint64_t rounds = (k_eff + KP - 1) / KP;
+    const uint64_t max_rounds = std::min<uint64_t>(SELECT_MAX_ROUNDS, std::max<uint64_t>(2, n / 250000));
+    const bool use_select = rounds <= max_rounds && force_path_.load() != PATH_EXACT_SORT;
+    if (use_select) {
+        for (uint64_t r = 0; r < rounds; ++r) {
+            const uint32_t kr = (uint32_t)std::min<uint64_t>(KP, k_eff - r * KP);
+            VL_HIP(launch_exact_select(st, ws->d_scores, n, kr, ws->d_partials64, ctr + EXAMPLES_CTR_NAN, ws->d_result + r,
+                                       r ? ws->d_result + (r - 1) : nullptr));
+        }
+        VL_HIP(hipMemcpyAsync(ws->h_result, ws->d_result, rounds * sizeof(SearchResultBlock), hipMemcpyDeviceToHost, st));
+    } else {
+        const uint64_t cap = sort_capacity_for(n);
+        VL_TRY(grow(HipMem{}, ws->sort_cap, cap, {dev_buf(ws->d_okeys, cap), dev_buf(ws->d_opos, cap)}));
+        VL_TRY(ensure_out(ws, k_eff));
+        VL_HIP(launch_exact_sort(st, ws->d_scores, n, k_eff, ws->d_okeys, ws->d_opos, ws->d_out_pos, ws->d_out_scores));
+        VL_HIP(hipMemcpyAsync(pos.data(), ws->d_out_pos, k_eff * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipMemcpyAsync(scores.data(), ws->d_out_scores, k_eff * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    VL_HIP(hipStreamSynchronize(st));
+    if (h_ctr[EXAMPLES_CTR_NAN]) {
+        set_last_error(EXAMPLES_NAN);
+        return ERR_NAN_SCORE;
+    }
+    if (use_select) {
+        for (uint64_t r = 0; r < rounds; ++r) {
+            const SearchResultBlock& blk = ws->h_result[r];
+            const uint64_t kr = std::min<uint64_t>(KP, k_eff - r * KP);
+            if (blk.n_out != kr) {
+                set_last_error("exact select returned an unexpected result count");
+                return ERR_DEVICE;
+            }
+            for (uint64_t i = 0; i < kr; ++i) {
+                pos[r * KP + i] = blk.pos[i];
+                scores[r * KP + i] = blk.score[i];
+            }
+        }
+    }
+    const uint64_t want = std::min<uint64_t>(k_eff, out_capacity);
+    for (uint64_t i = 0; i < want; ++i) {
+        if (pos[i] >= n) {
+            set_last_error("search by examples returned an out-of-range position (kernel bug)");
+            return ERR_DEVICE;
+        }
+        out_ids[i] = ids_[pos[i]];
+        out_scores[i] = scores[i];
+    }
+    *out_n = want;
+    return OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // point lookups / export / clone
 // ---------------------------------------------------------------------------------------------
 int GpuFlatIndex::get_vector(uint64_t id, double* out) const

@@ -24,6 +24,7 @@
 #include "batch_gate.hpp"
 #include "coalescer.hpp"
 #include "assign.hpp"
+#include "examples.hpp"
 #include "knn.hpp"
 #include "group_plan.hpp"
 #include "join.hpp"
@@ -560,6 +561,18 @@ public:
     {
         for (int i = 0; i < 6; ++i) out6[i] = last_knn_[i].load(std::memory_order_relaxed);
     }
+    // NEW (no reference counterpart): search by positive and negative examples.  positives: [n_pos,
+    // q_len], 1 <= n_pos <= EXAMPLES_MAX_POS; negatives: [n_neg, q_len], n_neg <= EXAMPLES_MAX_NEG.  With P(x) / N(x) the
+    // ordered maxima of the reference scores of row x against the positives / negatives: f = P when n_neg == 0 or P > N,
+    // else -(N N); the k rows of largest f by (f desc, position asc) as (id, f).
+    int search_examples(const double* positives, uint64_t n_pos, const double* negatives, uint64_t n_neg, uint64_t q_len, uint64_t k,
+                        int metric, uint64_t out_capacity, uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;
+    // the last search_examples on this handle: route (0 none, 1 mfma, 2 exact), seed rows scored, survivor rows, 16-example
+    // blocks of the pass
+    void last_examples(uint64_t* out4) const
+    {
+        for (int i = 0; i < 4; ++i) out4[i] = last_examples_[i].load(std::memory_order_relaxed);
+    }
     // 0: always the loop.  1: the pass whenever the batch is eligible.  2 ("auto", the default): when its estimate is lower.
     void set_grouped_batch(int mode) { grouped_batch_.store(mode); }
     int grouped_batch() const { return grouped_batch_.load(); }
@@ -761,6 +774,13 @@ private:
     int knn_mfma(Workspace* ws, uint32_t k, int metric, uint64_t n_out, uint64_t* out_nbr, double* out_scores, uint64_t* stats) const;
     int knn_exact_rows(Workspace* ws, uint64_t r0, uint64_t r1, uint32_t k, int metric, uint64_t n_out, uint64_t* out_nbr,
                        double* out_scores) const;
+    // search_examples' body (mu_ held, the index not empty, 1 <= k): the MFMA route, which leaves *certified false when the
+    // survivors exceed the cap, and the exact route; both write the answer, the first stats[1..3]
+    int examples_mfma(Workspace* ws, const double* positives, uint32_t a, const double* negatives, uint32_t b, uint64_t k, int metric,
+                      uint64_t out_capacity, uint64_t* out_ids, double* out_scores, uint64_t* out_n, uint64_t* stats,
+                      bool* certified) const;
+    int examples_exact(Workspace* ws, const double* positives, uint32_t a, const double* negatives, uint32_t b, uint64_t k, int metric,
+                       uint64_t out_capacity, uint64_t* out_ids, double* out_scores, uint64_t* out_n) const;
     int wait_result(Workspace* ws, uint32_t seq) const;
     int ensure_i8_slab() const;  // lazily builds the int8 copy the single-query int8 filter streams
     int ensure_bf16_slab(bool frag_major) const;  // lazily builds the bf16 slab (row-major, or MFMA fragment order) a filter streams
@@ -947,6 +967,7 @@ private:
     mutable std::atomic<uint64_t> last_assign_[6] = {};
     std::atomic<int> assign_route_{0};  // 0 auto, 1 exact, 2 mfma
     mutable std::atomic<uint64_t> last_knn_[6] = {};
+    mutable std::atomic<uint64_t> last_examples_[4] = {};
     std::atomic<int> knn_route_{0};  // 0 auto, 1 exact, 2 mfma
     std::atomic<int> join_route_{0};  // 0 auto, 1 loop, 2 mfma
     std::atomic<uint64_t> last_delete_[6] = {};
