@@ -355,6 +355,19 @@ int vl_index_set_masked_batch(vl_index *h, int mode);
 int vl_index_last_masked_batch(const vl_index *h, uint64_t *routed, uint64_t *certified, uint64_t *redone,
                                uint64_t *sequences, uint64_t *lists_built);
 
+/* How vl_index_search_batch* answer 60 < min(k, rows) <= VL_DEEP_MAX_K.  mode 0: the loop of single searches.  1, and 2
+ * (what new handles start in): the deep-k batch -- a sampled threshold, the MFMA pass stage by stage over growing row
+ * ranges, a certificate from the exact scores of the k rows of largest key -- wherever the handle has no forced path and no
+ * row outside the f32 domain, the metric is cosine, dot or Euclidean with a row length the row-stationary MFMA kernel has a
+ * shape for, the index holds at least 8192 rows and the call at least two queries.  Row i of the answer is bit for bit
+ * vl_index_search(queries[i], k) in every mode: a query the route does not certify is answered by that call.  Flat
+ * single-GPU handles; others: VL_ERR_INVALID_ARG, as is a mode outside 0..2. */
+#define VL_DEEP_MAX_K 1024
+int vl_index_set_deep_batch(vl_index *h, int mode);
+/* Of the last vl_index_search_batch* on this handle: out[0] = queries sent to the deep-k batch, out[1] = those it
+ * certified, out[2] = those it handed back to the single search, out[3] = its launch sequences. */
+int vl_index_last_deep_batch(const vl_index *h, uint64_t out[4]);
+
 /* NEW capability (the reference only answers "the best k"): every row that is at least this similar.  min_score is a
  * score in the reference's sense (higher is better for all four metrics, src/lib.rs:425-572; Euclidean and Manhattan are
  * 1 / (1 + d)).  The answer is the LONGEST PREFIX of FlatIndex::search(q, len, metric) (src/index/flat.rs:98-119) whose

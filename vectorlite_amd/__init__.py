@@ -44,6 +44,7 @@ SINGLE_FILTER_MODES = {"f32": 0, "bf16": 1, "auto": 2}
 SINGLE_FILTER_I8 = 3
 # set_masked_batch: the modes of vl_index_set_masked_batch (2 = auto, what new handles start in)
 MASKED_BATCH_MODES = {"off": 0, "on": 1, "auto": 2}
+VL_DEEP_MAX_K = 1024  # the largest k the deep-k batch answers (set_deep_batch shares the modes above)
 WHERE_ROUTES = {"auto": 0, "list": 1, "mask": 2}
 
 
@@ -1467,6 +1468,17 @@ class FlatIndex:
         v = [C.c_uint64(0) for _ in range(5)]
         _raise(self._L.vl_index_last_masked_batch(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("routed", "certified", "redone", "sequences", "lists_built"), (int(x.value) for x in v)))
+
+    def set_deep_batch(self, mode: str) -> None:
+        """How search_batch answers 60 < k <= VL_DEEP_MAX_K: "off" (the loop of single searches) or "on" / "auto" (new
+        handles: the deep-k MFMA batch wherever it applies).  Answers are identical in every mode."""
+        _raise(self._L.vl_index_set_deep_batch(self._h, MASKED_BATCH_MODES[mode]))
+
+    def last_deep_batch(self):
+        """Of the last search_batch on this handle: (routed, certified, handed back, sequences) of the deep-k batch."""
+        v = (C.c_uint64 * 4)()
+        _raise(self._L.vl_index_last_deep_batch(self._h, v))
+        return tuple(int(x) for x in v)
 
     def search_batch_device(self, queries, k: int, metric: int = 0, with_positions: bool = False):
         """search_batch for queries that are already on this index's GPU: `queries` is a contiguous float64 torch tensor

@@ -25,6 +25,7 @@ SYMBOLS = [
     "vl_index_assign", "vl_index_set_assign_route", "vl_index_last_assign",
     "vl_index_knn_graph", "vl_index_set_knn_route", "vl_index_last_knn",
     "vl_index_search_examples", "vl_index_last_examples",
+    "vl_index_set_deep_batch", "vl_index_last_deep_batch",
     "vl_index_search_mmr_batch", "vl_index_set_mmr_batch", "vl_index_last_mmr_batch",
     "vl_index_attr_create", "vl_index_attr_set", "vl_index_attr_rows", "vl_index_attr_destroy", "vl_index_filter_create_where",
     "vl_index_set_where_route", "vl_index_last_where",
@@ -110,6 +111,8 @@ def load() -> C.CDLL:
     sig("vl_index_last_filtered_batch", i32, [vp, p_u64, p_u64, p_u64, p_u64])
     sig("vl_index_set_masked_batch", i32, [vp, i32])
     sig("vl_index_last_masked_batch", i32, [vp, p_u64, p_u64, p_u64, p_u64, p_u64])
+    sig("vl_index_set_deep_batch", i32, [vp, i32])
+    sig("vl_index_last_deep_batch", i32, [vp, vp])
     sig("vl_index_search_range", i32, [vp, u64, vp, u64, C.c_double, i32, vp, vp, u64, p_u64, p_u64])
     sig("vl_index_search_range_batch", i32, [vp, u64, vp, u64, u64, vp, i32, u64, vp, vp, vp, vp])
     sig("vl_index_last_range_batch", i32, [vp, p_u64, p_u64, p_u64])

@@ -21,7 +21,7 @@ ARCH = "gfx950"
 # -ffp-contract=off: the exact kernels must round every multiply and every add separately, in the
 # reference's order (src/lib.rs:425-572); the f32 scan spells its FMAs out with fmaf().
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function", f"-I{INCLUDE}"]
-SOURCES = ["kernels.hip", "grouped.hip", "where.hip", "mmr.hip", "hnsw.hip", "mfma_scan.hip", "join.hip", "maxsim.hip", "assign.hip", "knn.hip", "examples.hip", "shard.hip", "flat_index.cpp", "multi_index.cpp", "hnsw_index.cpp", "shard_comm.cpp",
+SOURCES = ["kernels.hip", "grouped.hip", "where.hip", "mmr.hip", "hnsw.hip", "mfma_scan.hip", "join.hip", "maxsim.hip", "assign.hip", "knn.hip", "examples.hip", "deep_batch.hip", "shard.hip", "flat_index.cpp", "multi_index.cpp", "hnsw_index.cpp", "shard_comm.cpp",
            "vlc_loader.cpp", "c_api.cpp"]
 # join.hip's f32 epilogue is compiled without packed-f32 instructions (v_pk_*_f32); the older translation units keep the
 # flags they were measured with

@@ -36,6 +36,14 @@ inline bool gate_topk(const BatchGate& g)
     return gate_core(g) && g.nq > 1 && g.k_eff <= g.lim.k_max && g.nq >= g.lim.min_batch && g.rows >= g.lim.min_rows;
 }
 
+// The deep-k batch: gate_topk with k_eff above the list's margin, up to `deep_max_k`
+// (VL_DEEP_MAX_K), on the row-stationary kernel.  Never true together with gate_topk.
+inline bool gate_deep(const BatchGate& g, uint64_t deep_max_k = 1024)
+{
+    return gate_core(g) && g.rows_kernel && g.nq > 1 && g.k_eff > g.lim.k_max && g.k_eff <= deep_max_k && g.nq >= g.lim.min_batch &&
+           g.rows >= g.lim.min_rows;
+}
+
 // ... written into a shard's exchange record at stride ks: the record's planes are indexed with 32-bit words
 inline bool gate_record(const BatchGate& g, uint64_t ks)
 {

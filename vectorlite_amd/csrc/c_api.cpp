@@ -1009,6 +1009,21 @@ int vl_index_last_masked_batch(const vl_index* h, uint64_t* routed, uint64_t* ce
     return VL_OK;
 }
 
+int vl_index_set_deep_batch(vl_index* h, int mode)
+{
+    if (!h || !h->flat || mode < 0 || mode > 2) return VL_ERR_INVALID_ARG;
+    h->flat->set_deep_batch(mode);
+    return VL_OK;
+}
+
+int vl_index_last_deep_batch(const vl_index* h, uint64_t out[4])
+{
+    static_assert(VL_DEEP_MAX_K == vl::DEEP_MAX_K, "the header's constant is the plan's");
+    if (!h || !h->flat || !out) return VL_ERR_INVALID_ARG;
+    h->flat->last_deep_batch(out);
+    return VL_OK;
+}
+
 int vl_index_search_batch_cap(const vl_index* h, const double* queries, uint64_t nq, uint64_t q_len, uint64_t k,
                               int metric, uint64_t out_stride, uint64_t* out_ids, double* out_scores, uint64_t* out_n)
 {

@@ -233,12 +233,13 @@ Workspace::~Workspace()
     void* dev[] = {d_q64, d_partials, d_partials64, d_result, d_nan, d_scores, d_okeys,
                    d_opos, d_out_pos, d_out_scores, d_positions, d_dists, rg_ctr, rg_cand, rg_scores, rg_keys, rg_pv, mmr_sim,
                    rb_ctr, rb_min, rb_sv_score, rb_sv_pos, gp_best, gp_first, gp_lists, gp_cand, gp_scores, gp_ctr, gp_out_keys,
-                   gb_keep, gb_m, mb_ranked, jn_cand, jn_cnt, jn_ctr, jn_keys, jn_pay, ms_dev};
+                   gb_keep, gb_m, mb_ranked, jn_cand, jn_cnt, jn_ctr, jn_keys, jn_pay, ms_dev, dp_gm, dp_thr, dp_mask, dp_seed, dp_seed_cnt,
+                   dp_L};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     void* host[] = {h_q64, h_result, h_nan, mf_h_q64, mf_h_result, mf_h_dom, k3_h_q64, k3_h_result, rg_h_ctr, rg_h_pos, rg_h_scores,
                     rb_h_thr, rb_h_min, rb_h_ctr, rb_h_cnt, rb_h_pos, rb_h_scores, gp_h_ctr, gp_h_scores, gp_h_keys,
-                    gb_h_result, jn_h, ms_host};
+                    gb_h_result, jn_h, ms_host, dp_h_thr, dp_h_L};
     for (void* p : host)
         if (p) (void)hipHostFree(p);
     void* mfd[] = {mf.q_bf16, mf.gmax, mf.thr, mf.cand, mf.cnt, mf_d_q64, mf_lists, mf_scores, k3_d_q64};
@@ -1397,6 +1398,26 @@ int GpuFlatIndex::search_batch_locked(const double* queries, uint64_t nq, uint64
         return search_locked(ws, queries + qi * dim_, k_eff, metric, out_at(out_pos, qi), out_at(out_ids, qi),
                              out_scores + qi * k, out_n + qi, skip_fast, skip_bf16);
     };
+    // k_eff beyond the candidate list's margin: the deep-k batch; what it does not certify goes to
+    // the single call in ascending order, like everything did before.  search_batch_device and the shard record reach
+    // this through their host route.
+    uint64_t deep[4] = {0, 0, 0, 0};  // last_deep_batch: routed, certified, handed back, sequences
+    auto publish_deep = [&]() {
+        for (int i = 0; i < 4; ++i) last_deep_[i].store(deep[i], std::memory_order_relaxed);
+    };
+    if (deep_batch_.load() != 0 && gate_deep(batch_gate(metric, nq, k_eff), DEEP_MAX_K)) {
+        std::vector<uint8_t> done(nq, 0);
+        VL_TRY(search_batch_deep(ws, queries, nq, k, k_eff, metric, out_pos, out_ids, out_scores, out_n, &done, &deep[3]));
+        deep[0] = nq;
+        for (uint64_t qi = 0; qi < nq; ++qi) deep[1] += done[qi] ? 1 : 0;
+        deep[2] = nq - deep[1];
+        if (deep[1]) set_last_path(PATH_FAST);
+        for (uint64_t qi = 0; qi < nq; ++qi)
+            if (!done[qi]) VL_TRY(single(qi, false));
+        publish_deep();
+        return OK;
+    }
+    publish_deep();
     if (!batchable) {
         for (uint64_t qi = 0; qi < nq; ++qi) VL_TRY(single(qi, false));
         return OK;
@@ -4023,6 +4044,174 @@ int GpuFlatIndex::search_range_batch_mfma(Workspace* ws, const double* queries, 
                 out_ids ? out_ids + qi * out_stride : nullptr, out_scores + qi * out_stride));
             out_n[qi] = want;
             out_total[qi] = c[RBATCH_CTR_TOTAL];
+            (*done)[qi] = 1;
+        }
+    }
+    return OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Deep-k batch: search_batch with KFAST_MAX < k_eff <= DEEP_MAX_K.  Per launch sequence: a sampled
+// bootstrap threshold (k_deep_sample, k_deep_select), the shipped pass-1 kernel stage by stage over growing row ranges with
+// the K'-th best key so far as the next threshold and the buffer compacted to it, then the certificate: the k entries of
+// largest key are scored exactly, L = their smallest score, thr = the smallest key not provably below L; thr >= the last
+// threshold T proves that the buffer's entries with key >= thr hold every row scoring >= L.  They are rescored and ranked
+// by the batched range search's tail.  A query leaves the route when thr < T, a counter exceeds the capacity, a score is
+// NaN, more than RBATCH_SEG rows survive or it lies outside the fast-path domain: the caller's single call answers it.
+// ---------------------------------------------------------------------------------------------
+namespace {
+uint32_t deep_candidate_capacity()
+{
+    // VL_DEEP_BATCH_CAND_CAP: smaller per-query candidate buffers (tests drive the hand-back with it)
+    if (const char* e = getenv("VL_DEEP_BATCH_CAND_CAP")) {
+        const long long v = atoll(e);
+        if (v >= 1 && v <= (long long)DEEP_CAND_CAP) return (uint32_t)v;
+    }
+    return DEEP_CAND_CAP;
+}
+uint64_t deep_first_rows()
+{
+    // VL_DEEP_BATCH_FIRST_ROWS: the rows of the first stage (tests reach several stages on a small index with it)
+    if (const char* e = getenv("VL_DEEP_BATCH_FIRST_ROWS")) {
+        const long long v = atoll(e);
+        if (v >= 32) return (uint64_t)v;
+    }
+    return 0;
+}
+}  // namespace
+
+int GpuFlatIndex::search_batch_deep(Workspace* ws, const double* queries, uint64_t nq, uint64_t k, uint64_t k_eff, int metric,
+                                    uint64_t* out_pos, uint64_t* out_ids, double* out_scores, uint64_t* out_n,
+                                    std::vector<uint8_t>* done, uint64_t* sequences) const
+{
+    const uint64_t n = ids_.size();
+    const uint32_t dim = (uint32_t)dim_;
+    const uint32_t qpb = mfma_rows_chunk_queries(dim);
+    const uint32_t cap = deep_candidate_capacity();
+    const DeepPlan plan = deep_plan(n, (uint32_t)k_eff, cap, qpb, deep_first_rows());
+    if (!plan.ok || !deep_sample_supported(dim, metric)) return OK;  // every query goes back to the single call
+    VL_TRY(ensure_bf16_slab(true));
+    VL_TRY(ensure_mfma_scratch(ws));
+    const uint32_t seq = std::min<uint32_t>(plan.seq_queries, ws->mf.nq_cap);
+    VL_TRY(ensure_range_batch_ws(ws, seq));
+    VL_TRY(ensure_set(HipMem{}, {dev_buf(ws->dp_gm, (size_t)DEEP_SELECT_MAX * DEEP_SEQ_QUERIES), dev_buf(ws->dp_thr, (size_t)MFMA_MAX_BATCH),
+                                 dev_buf(ws->dp_mask, (size_t)MFMA_MAX_BATCH), dev_buf(ws->dp_seed, (size_t)DEEP_SEQ_QUERIES * RBATCH_SEG),
+                                 dev_buf(ws->dp_seed_cnt, (size_t)MFMA_MAX_BATCH), dev_buf(ws->dp_L, (size_t)MFMA_MAX_BATCH),
+                                 pinned_buf(ws->dp_h_thr, (size_t)MFMA_MAX_BATCH), pinned_buf(ws->dp_h_L, (size_t)MFMA_MAX_BATCH)}));
+    hipStream_t st = ws->stream;
+    const uint32_t ldb = mfma_ldb(dim);
+    const uint32_t kk = (uint32_t)k_eff;
+    std::vector<uint8_t> staged;
+    std::vector<double> norms;
+    for (uint64_t q0 = 0; q0 < nq; q0 += seq) {
+        const uint32_t g = (uint32_t)std::min<uint64_t>(seq, nq - q0);
+        const uint32_t g_pad = (g + qpb - 1) / qpb * qpb;
+        VL_TRY(ensure_range_ws(ws, 0, (size_t)g * kk));  // (allocates only while the stream is idle: every sequence ends in a sync)
+        if (ws->mf_h2d_pending) {  // a top-k batch's copies out of the pinned staging area
+            VL_HIP(hipEventSynchronize(ws->mf_ev_h2d));
+            ws->mf_h2d_pending = false;
+        }
+        *sequences += 1;
+        // ---- stage: the queries as the top-k batch stages them; mask = +inf keeps a query out of every buffer ----
+        staged.assign(g, 0);
+        norms.assign(g, 0.0);
+        for (uint32_t j = 0; j < g; ++j) {
+            const bool in_domain = stage_query(queries + (q0 + j) * dim_, ws->mf_h_q64 + (size_t)j * dim_, dim_, &norms[j]);
+            staged[j] = in_domain && norms[j] > 0.0;  // a zero query ties on every row: the single call's to answer
+            ws->rb_h_thr[j] = staged[j] ? -INFINITY : INFINITY;
+            ws->rb_h_min[j] = -INFINITY;  // the seeds' rescoring cuts nothing
+        }
+        VL_HIP(hipMemcpyAsync(ws->mf_d_q64, ws->mf_h_q64, (size_t)g * dim_ * sizeof(double), hipMemcpyHostToDevice, st));
+        VL_HIP(hipMemcpyAsync(ws->dp_mask, ws->rb_h_thr, (size_t)g * sizeof(float), hipMemcpyHostToDevice, st));
+        VL_HIP(hipMemcpyAsync(ws->rb_min, ws->rb_h_min, (size_t)g * sizeof(double), hipMemcpyHostToDevice, st));
+        auto stage = [&](const float* thr, uint32_t b0, uint32_t b1, bool prepare) -> hipError_t {
+            return launch_mfma_stage_candidates(st, metric, d_slab16f_, d_norm16_, d_sqnorm_, ws->mf_d_q64, g, n, dim, ws->mf, thr, b0, b1,
+                                                cap, prepare);
+        };
+        VL_HIP(stage(nullptr, 0, 0, true));
+        // ---- bootstrap threshold: a lower bound of the sample_rank-th best key of the whole index ----
+        if (plan.sampled)
+            VL_HIP(launch_deep_sample(st, metric, d_slab16f_, d_norm16_, d_sqnorm_, ws->mf.q_bf16, g_pad, plan.sample_blocks, n, dim,
+                                      ws->dp_gm));
+        VL_HIP(launch_deep_select_sample(st, ws->dp_gm, g_pad, plan.groups, plan.sample_rank, g, ws->dp_mask, ws->mf.thr));
+        // ---- stages: every block once; between stages T = the K'-th largest key so far and the buffer compacted to it ----
+        for (uint32_t s = 0; s < plan.n_stages; ++s) {
+            const uint32_t A = plan.stripes[s];
+            if (A <= 1) {
+                VL_HIP(stage(ws->mf.thr, plan.stage_end[s], plan.stage_end[s + 1], false));
+            } else {  // a dense stage: A launches, each with every A-th query of a chunk collecting (deep_stripes)
+                const uint32_t launches = std::min<uint32_t>(A, std::min<uint32_t>(qpb, g));
+                for (uint32_t a = 0; a < launches; ++a) {
+                    VL_HIP(launch_deep_stripe(st, ws->mf.thr, g, qpb, A, a, ws->dp_thr));
+                    VL_HIP(stage(ws->dp_thr, plan.stage_end[s], plan.stage_end[s + 1], false));
+                }
+            }
+            if (s + 1 < plan.n_stages)
+                VL_HIP(launch_deep_select(st, ws->mf.cand, ws->mf.cnt, cap, g, plan.kprime, ws->mf.thr, true, ws->mf.cand, ws->mf.cnt, cap));
+        }
+        // ---- seeds: the entries of the k largest keys (with their ties), scored exactly; L = the smallest score ----
+        VL_HIP(launch_deep_select(st, ws->mf.cand, ws->mf.cnt, cap, g, kk, ws->dp_thr, false, ws->dp_seed, ws->dp_seed_cnt, RBATCH_SEG));
+        VL_HIP(launch_deep_clear(st, ws->rb_ctr, g * RBATCH_CTR_WORDS));
+        VL_HIP(launch_range_batch_tail(st, metric, ws->dp_seed, ws->dp_seed_cnt, RBATCH_SEG, g, d_master_, ws->mf_d_q64, ws->rb_min, dim, n,
+                                       0, ws->rb_sv_score, ws->rb_sv_pos, ws->rb_ctr, ws->d_out_pos, ws->d_out_scores));
+        VL_HIP(launch_deep_seed_min(st, ws->rb_sv_score, RBATCH_SEG, ws->rb_ctr, RBATCH_CTR_WORDS, g, ws->dp_L));
+        VL_HIP(hipMemcpyAsync(ws->dp_h_L, ws->dp_L, (size_t)g * sizeof(double), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipMemcpyAsync(ws->dp_h_thr, ws->mf.thr, (size_t)g * sizeof(float), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipMemcpyAsync(ws->rb_h_cnt, ws->mf.cnt, (size_t)g * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipStreamSynchronize(st));
+        // ---- the certificate, per query: thr (every row scoring >= L has key >= thr) against T (the buffer holds every
+        //      row with key >= T).  (R, Q, n, in_extra) are the batched range search's. ----
+        for (uint32_t j = 0; j < g; ++j) {
+            const double L = ws->dp_h_L[j];
+            float thr = INFINITY;
+            bool ok = staged[j] && L == L && ws->rb_h_cnt[j] <= cap;
+            if (ok) ok = range_key_threshold(metric, ldb, max_row_norm_, norms[j], L, IN_EXTRA_MFMA, &thr) == RANGE_KEYS_FROM;
+            ok = ok && thr >= ws->dp_h_thr[j] && thr < INFINITY;
+            staged[j] = ok;
+            ws->rb_h_thr[j] = ok ? thr : INFINITY;
+            ws->rb_h_min[j] = ok ? L : INFINITY;
+        }
+        VL_HIP(hipMemcpyAsync(ws->mf.thr, ws->rb_h_thr, (size_t)g * sizeof(float), hipMemcpyHostToDevice, st));
+        VL_HIP(hipMemcpyAsync(ws->rb_min, ws->rb_h_min, (size_t)g * sizeof(double), hipMemcpyHostToDevice, st));
+        VL_HIP(launch_deep_select(st, ws->mf.cand, ws->mf.cnt, cap, g, 0, ws->mf.thr, false, ws->mf.cand, ws->mf.cnt, cap));
+        VL_HIP(launch_deep_clear(st, ws->rb_ctr, g * RBATCH_CTR_WORDS));
+        VL_HIP(launch_range_batch_tail(st, metric, ws->mf.cand, ws->mf.cnt, cap, g, d_master_, ws->mf_d_q64, ws->rb_min, dim, n, kk,
+                                       ws->rb_sv_score, ws->rb_sv_pos, ws->rb_ctr, ws->d_out_pos, ws->d_out_scores));
+        // one copy back: counters and the packed answers (as much of them as the speculative buffer holds)
+        const size_t spec = std::min<size_t>((size_t)g * kk, RBATCH_SPEC);
+        VL_HIP(hipMemcpyAsync(ws->rb_h_ctr, ws->rb_ctr, (size_t)g * RBATCH_CTR_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipMemcpyAsync(ws->rb_h_cnt, ws->mf.cnt, (size_t)g * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipMemcpyAsync(ws->rb_h_pos, ws->d_out_pos, spec * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipMemcpyAsync(ws->rb_h_scores, ws->d_out_scores, spec * sizeof(double), hipMemcpyDeviceToHost, st));
+        VL_HIP(hipStreamSynchronize(st));
+        size_t packed = 0;
+        for (uint32_t j = 0; j < g; ++j) {
+            const uint32_t* c = ws->rb_h_ctr + (size_t)j * RBATCH_CTR_WORDS;
+            // k survivors at least: the seeds themselves score >= L and have key >= thr
+            const bool ok = staged[j] && ws->rb_h_cnt[j] <= cap && c[RBATCH_CTR_NAN] == 0 && c[RBATCH_CTR_TOTAL] <= RBATCH_SEG &&
+                            c[RBATCH_CTR_TOTAL] >= kk && c[RBATCH_CTR_WANT] == kk && (size_t)c[RBATCH_CTR_OFF] + kk <= (size_t)g * kk;
+            staged[j] = ok;
+            if (ok) packed = std::max(packed, (size_t)c[RBATCH_CTR_OFF] + kk);
+        }
+        std::vector<uint32_t> more_pos;
+        std::vector<double> more_scores;
+        if (packed > spec) {  // the rest of the packed answers
+            more_pos.resize(packed - spec);
+            more_scores.resize(packed - spec);
+            VL_HIP(hipMemcpyAsync(more_pos.data(), ws->d_out_pos + spec, (packed - spec) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            VL_HIP(hipMemcpyAsync(more_scores.data(), ws->d_out_scores + spec, (packed - spec) * sizeof(double), hipMemcpyDeviceToHost,
+                                  st));
+            VL_HIP(hipStreamSynchronize(st));
+        }
+        for (uint32_t j = 0; j < g; ++j) {
+            if (!staged[j]) continue;
+            const uint64_t qi = q0 + j;
+            const size_t off = ws->rb_h_ctr[(size_t)j * RBATCH_CTR_WORDS + RBATCH_CTR_OFF];
+            VL_TRY(deliver(
+                "deep-k batch", ids_, kk, [&](uint64_t i) { return off + i < spec ? ws->rb_h_pos[off + i] : more_pos[off + i - spec]; },
+                [&](uint64_t i) { return off + i < spec ? ws->rb_h_scores[off + i] : more_scores[off + i - spec]; },
+                out_pos ? out_pos + qi * k : nullptr, out_ids ? out_ids + qi * k : nullptr, out_scores + qi * k));
+            out_n[qi] = kk;
             (*done)[qi] = 1;
         }
     }

@@ -24,6 +24,7 @@
 #include "batch_gate.hpp"
 #include "coalescer.hpp"
 #include "assign.hpp"
+#include "deep_batch.hpp"
 #include "examples.hpp"
 #include "knn.hpp"
 #include "group_plan.hpp"
@@ -110,6 +111,16 @@ struct Workspace {
     uint32_t* rb_h_cnt = nullptr;    // pinned [MFMA_MAX_BATCH]
     uint32_t* rb_h_pos = nullptr;    // pinned [RBATCH_SPEC]: packed answers copied back before the host knows their number
     double* rb_h_scores = nullptr;   // pinned [RBATCH_SPEC]
+    // deep-k batch (lazy): the sample's group maxima, the stripe's thresholds, the per-query mask,
+    // the seeds (entries and counters), L; pinned: thresholds and L of one launch sequence
+    float* dp_gm = nullptr;          // [DEEP_SELECT_MAX groups, dp_nq_pad]
+    float* dp_thr = nullptr;         // [MFMA_MAX_BATCH]
+    float* dp_mask = nullptr;        // [MFMA_MAX_BATCH]
+    Cand32* dp_seed = nullptr;       // [DEEP_SEQ_QUERIES + chunk, RBATCH_SEG]
+    uint32_t* dp_seed_cnt = nullptr; // [MFMA_MAX_BATCH]
+    double* dp_L = nullptr;          // [MFMA_MAX_BATCH]
+    float* dp_h_thr = nullptr;       // pinned [MFMA_MAX_BATCH]
+    double* dp_h_L = nullptr;        // pinned [MFMA_MAX_BATCH]
     // similarity self-join (lazy): one range's candidate pairs and their counter, the call's survivors (sort keys and
     // payloads, jn_sv_cap entries), its counters
     JoinCand* jn_cand = nullptr;             // [JOIN_CAND_CAP]
@@ -436,6 +447,16 @@ public:
         for (int i = 0; i < 5; ++i)
             if (out[i]) *out[i] = last_mbatch_[i].load(std::memory_order_relaxed);
     }
+    // How search_batch answers KFAST_MAX < k_eff <= DEEP_MAX_K.  0: the loop of single calls.  1 and 2
+    // ("auto", the default): the deep-k batch wherever gate_deep holds.
+    void set_deep_batch(int mode) { deep_batch_.store(mode); }
+    int deep_batch() const { return deep_batch_.load(); }
+    // the last search_batch on this handle: queries sent to the deep-k batch, those it certified, those it handed back to
+    // the single call, its launch sequences
+    void last_deep_batch(uint64_t out[4]) const
+    {
+        for (int i = 0; i < 4; ++i) out[i] = last_deep_[i].load(std::memory_order_relaxed);
+    }
     // NEW (no reference counterpart): every row whose score is >= min_score -- the longest prefix of FlatIndex::search(q, len,
     // metric) with score >= min_score, over the filter's rows when token != 0.  *out_total = rows that qualify, always;
     // min(total, out_capacity) entries are written (out_capacity = 0: count only, outputs may be null).
@@ -742,6 +763,9 @@ private:
                               uint64_t out_capacity, uint64_t* out_group_keys, uint64_t* out_pos, uint64_t* out_ids,
                               double* out_scores, uint64_t* out_n) const;
     // the MFMA route of search_range_batch (mu_ held, whole index): done[qi] is set for every query answered here
+    // the deep-k batch over host queries: done[qi] is set for every query answered here; stats += {certified, sequences}
+    int search_batch_deep(Workspace* ws, const double* queries, uint64_t nq, uint64_t k, uint64_t k_eff, int metric, uint64_t* out_pos,
+                          uint64_t* out_ids, double* out_scores, uint64_t* out_n, std::vector<uint8_t>* done, uint64_t* sequences) const;
     int search_range_batch_mfma(Workspace* ws, const double* queries, uint64_t nq, const double* min_scores, int metric,
                                 uint64_t out_stride, uint64_t* out_ids, double* out_scores, uint64_t* out_n, uint64_t* out_total,
                                 std::vector<uint8_t>* done, uint64_t* max_candidates) const;
@@ -955,6 +979,8 @@ private:
     mutable std::atomic<int> last_scan_variant_{0}, last_scan_grid_{0}, last_scan_qarg_{0};
     mutable std::atomic<int> last_filter_[6] = {};
     mutable std::atomic<uint64_t> last_rbatch_[4] = {};
+    std::atomic<int> deep_batch_{2};
+    mutable std::atomic<uint64_t> last_deep_[4] = {};
     mutable std::atomic<uint64_t> last_fbatch_[4] = {};
     mutable std::atomic<uint64_t> last_mbatch_[5] = {};
     std::atomic<int> masked_batch_{2};  // MASKED_BATCH_AUTO

@@ -2288,6 +2288,64 @@ hipError_t launch_mfma_range_candidates(hipStream_t s, int metric, const void* s
     return hipGetLastError();
 }
 
+// One stage of the deep-k batch: the same pass-1 kernel over the 32-row blocks [blk_begin, blk_end)
+// with the caller's thresholds and capacity.  prepare: first write the queries' bf16 rows and clear the counters.
+hipError_t launch_mfma_stage_candidates(hipStream_t s, int metric, const void* slab_frag, const float* row_norm,
+                                        const float* row_sqnorm, const double* q64, uint32_t nq, uint64_t n_rows, uint32_t dim,
+                                        const MfmaScratch& w, const float* thr, uint32_t blk_begin, uint32_t blk_end,
+                                        uint32_t cand_cap, bool prepare)
+{
+    if (nq == 0 || n_rows == 0 || n_rows >= 0xFFFFFFFFull || cand_cap == 0) return hipErrorInvalidValue;
+    if (!mfma_scan_supported(dim, metric) || !mfma_rows_kernel(dim) || nq > w.nq_cap) return hipErrorInvalidValue;
+    if ((uint64_t)nq * cand_cap > (uint64_t)w.nq_cap * MFMA_CAND_CAP) return hipErrorInvalidValue;  // the buffer's entries
+    const uint32_t n_blk = (uint32_t)((n_rows + 31) / 32);
+    if (blk_begin > blk_end || blk_end > n_blk) return hipErrorInvalidValue;
+    const uint32_t ldb = mfma_ldb(dim);
+    __bf16* q16 = reinterpret_cast<__bf16*>(w.q_bf16);
+    const __bf16* slab = reinterpret_cast<const __bf16*>(slab_frag);
+    const uint32_t rq = (uint32_t)rs_qpb(ldb);
+    const uint32_t nq_pad = (nq + rq - 1) / rq * rq;
+    if (nq_pad > w.nq_pad_cap) return hipErrorInvalidValue;
+    const uint32_t chunks = nq_pad / rq;
+    if (prepare) {
+        const size_t total = (size_t)nq_pad * ldb;
+        const int grid = (int)std::min<size_t>((total + 255) / 256, 4096);
+        hipLaunchKernelGGL(k_queries_bf16, dim3(grid), dim3(256), 0, s, q64, nq, nq_pad, dim, ldb, q16);
+        const hipError_t e = hipMemsetAsync(w.cnt, 0, (size_t)nq_pad * sizeof(uint32_t), s);
+        if (e != hipSuccess) return e;
+    }
+    if (blk_begin == blk_end) return hipGetLastError();
+    if (!thr) return hipErrorInvalidValue;
+    const uint32_t wg_cap = (uint32_t)env_grid(chunks);
+    const uint32_t gx = std::max<uint32_t>(1u, std::min<uint32_t>((blk_end - blk_begin + RS_NWAVES - 1) / RS_NWAVES, wg_cap));
+    const bool stream = pass1_streams(chunks);
+    bool launched = false;
+#define VL_RSTAGE2(K, MET)                                                                                                       \
+    {                                                                                                                            \
+        if (stream)                                                                                                              \
+            hipLaunchKernelGGL((k_mfma_rows<K, 1, MET, 2, RS_NWAVES, true>), dim3(gx, chunks), dim3(RS_NWAVES * 64), 0, s, slab, \
+                               row_norm, row_sqnorm, q16, nq, blk_begin, blk_end, (uint32_t)n_rows, (int*)nullptr, 0u, 1u, thr,   \
+                               w.cand, w.cnt, cand_cap);                                                                         \
+        else                                                                                                                     \
+            hipLaunchKernelGGL((k_mfma_rows<K, 1, MET>), dim3(gx, chunks), dim3(RS_NWAVES * 64), 0, s, slab, row_norm,           \
+                               row_sqnorm, q16, nq, blk_begin, blk_end, (uint32_t)n_rows, (int*)nullptr, 0u, 1u, thr, w.cand,     \
+                               w.cnt, cand_cap);                                                                                 \
+        launched = true;                                                                                                         \
+    }
+#define VL_RSTAGE(K)                                            \
+    if (!launched && ldb == (uint32_t)(K * 16)) {               \
+        if (metric == COSINE) VL_RSTAGE2(K, COSINE)             \
+        else if (metric == EUCLIDEAN) VL_RSTAGE2(K, EUCLIDEAN)  \
+        else VL_RSTAGE2(K, DOT)                                 \
+    }
+    VL_MFMA_KSTEPS(VL_RSTAGE)
+#undef VL_RSTAGE
+#undef VL_RSTAGE2
+    return launched ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+uint32_t mfma_rows_chunk_queries(uint32_t dim) { return (uint32_t)rs_qpb(mfma_ldb(dim)); }
+
 namespace {
 // What launch_scan_bf16 and launch_scan_i8 decide the same way: which listed (G, VPL, U) runs at a row stride of `ldc`
 // 16-byte chunks, with how many workgroups, and the variant code the search reports.

@@ -141,6 +141,18 @@ hipError_t launch_mfma_range_candidates(hipStream_t s, int metric, const void* s
                                         const float* row_sqnorm, const double* q64, uint32_t nq, uint64_t n_rows, uint32_t dim,
                                         const MfmaScratch& w, uint32_t cand_cap, MfmaLaunchInfo* info = nullptr);
 
+// One stage of the deep-k batch: the same pass-1 kernel over the 32-row blocks [blk_begin, blk_end)
+// only, with thresholds thr[q] of the caller's (device memory, not necessarily w.thr) and cand_cap entries per query at
+// w.cand[q * cand_cap ..] -- cand_cap may exceed MFMA_CAND_CAP as long as nq * cand_cap entries fit the buffer.  The
+// counters carry over from launch to launch.  prepare = true first writes the queries' bf16 rows into w.q_bf16 (whole
+// chunks, zero rows for padding) and clears the counters; an empty block range then launches nothing else.
+hipError_t launch_mfma_stage_candidates(hipStream_t s, int metric, const void* slab_frag, const float* row_norm,
+                                        const float* row_sqnorm, const double* q64, uint32_t nq, uint64_t n_rows, uint32_t dim,
+                                        const MfmaScratch& w, const float* thr, uint32_t blk_begin, uint32_t blk_end,
+                                        uint32_t cand_cap, bool prepare);
+// queries per chunk of the row-stationary kernel at this dimension (128, or 96 at stride 768)
+uint32_t mfma_rows_chunk_queries(uint32_t dim);
+
 // Single-query scan of the bf16 slab (the single-query candidate filter): per-workgroup top-64 lists like launch_scan.
 // Two ways to hand over the query, as launch_scan: q32_host != nullptr is the f32 query rounded from the f64 one to
 // nearest even and zero padded to mfma_ldb(dim) floats, copied into the kernel arguments (q64 may then be null);
